@@ -652,6 +652,47 @@ def conv3d_leg(dev, samples=(2, 16), D=5, S=128, cin=13, cout=64, iters=5):
     return out
 
 
+DUMP_SAMPLE = 1 << 22                    # elements kept of an output larger than this (a fixed, seeded sample): <= 16 MB per array
+
+
+def dump_outputs(out_dir, ts, loss):
+    """`--dump-outputs DIR`: what the timed path handed its caller in its LAST timed step, as DIR/<name>.npy (float32 / float64), so
+    that two builds run with the same arguments (same seeded inputs and weights) can be compared output for output:
+      loss            the step's Tversky loss, shape (1,)
+      logits          TrainStep.last_logits, [B, 2, H, W] (flattened sample of DUMP_SAMPLE, numpy default_rng(1), when larger)
+      counts          TrainStep.last_counts (the loss's confusion counts), float64
+      params, grads   the flat parameters after the step's SGD update and the gradients it applied (TrainStep.flat_params /
+                      flat_grads): the same sorted sample of DUMP_SAMPLE positions of each (numpy default_rng(0)) when larger
+      bn_buffers      every BatchNorm running mean / variance after the step, concatenated in state-dict order
+    At most 3 x 16 MB plus a few kB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def sample(flat, idx):
+        return flat if idx is None else flat[idx]
+
+    n = ts.flat_params.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    logits = ts.last_logits.detach().float().cpu().numpy()
+    if logits.size > DUMP_SAMPLE:
+        logits = logits.reshape(-1)[np.sort(np.random.default_rng(1).choice(logits.size, DUMP_SAMPLE, replace=False))]
+    bufs = [v.detach().float().reshape(-1).cpu() for k, v in ts.model.state_dict().items()
+            if k.endswith('.running_mean') or k.endswith('.running_var')]
+    arrays = {
+        'loss': loss.detach().float().reshape(1).cpu().numpy(),
+        'logits': logits,
+        'counts': ts.last_counts.detach().cpu().numpy().astype(np.float64),
+        'params': sample(ts.flat_params.detach().cpu().numpy(), idx),
+        'grads': sample(ts.flat_grads.detach().cpu().numpy(), idx),
+        'bn_buffers': torch.cat(bufs).numpy() if bufs else np.zeros(0, np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -721,10 +762,15 @@ def main():
     ap.add_argument('--force-collectives', action='store_true',
                     help='N=1 only: the HEADLINE loop itself issues its gradient-bucket all-reduces through RCCL (world size 1)')
     ap.add_argument('--windows', type=int, default=3,
-                    help='consecutive timed windows of --steps steps each; the headline is the MEDIAN window (all are reported)')
+                    help='the --steps timed steps are split into this many consecutive windows (at most one per step); the headline '
+                         'is the MEDIAN window\'s ms per step (all are reported)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)')
     ap.add_argument('--engine-set', default='', help='A/B runs only: engine attributes for the headline loop, e.g. fwd_chains=2,fwd_chain_levels=2')
     ap.add_argument('--launcher-selftest', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # --gpus N without a launcher above us: become the launcher (N ranks under torch.distributed.run), or refuse
     what, detail = launch_plan(args.gpus, os.environ, visible_devices(), sys.argv[1:])
@@ -834,16 +880,18 @@ def main():
     if not args.no_roofline:
         eng.prof = []
     picks = []
-    # `--windows` consecutive windows of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides and reduced with
-    # MAX over the ranks; the headline is the MEDIAN window (all are reported), so that a 1-2 % change is resolvable from one record:
-    # value = steps * B * world / median window, ms_per_step * steps = that window.
+    # EXACTLY --steps timed steps, split into `--windows` consecutive windows of (nearly) equal length, each bracketed by barrier +
+    # synchronize on both sides and reduced with MAX over the ranks; the headline is the MEDIAN window's ms per step (all are reported),
+    # so that a 1-2 % change is resolvable from one record: value = B * world / ms_per_step.
+    n_win = max(1, min(args.windows, args.steps))
+    win_steps = [args.steps // n_win + (1 if i < args.steps % n_win else 0) for i in range(n_win)]
     windows, enqueue_s, k = [], 0.0, 0
-    for _ in range(max(1, args.windows)):
+    for n_steps in win_steps:
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(n_steps):
             eng.prof_pick = k % n_dom if n_dom else None      # step k brackets the (k mod n)-th launch of the dominant kernel
             picks.append(eng.prof_pick)
             k += 1
@@ -857,18 +905,18 @@ def main():
             t = torch.tensor([w], dtype=torch.float64, device=dev if backend != 'gloo' else 'cpu')
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             w = float(t.item())
-        windows.append(w)
+        windows.append(w / n_steps)
         enqueue_s += enq
-    enqueue_s /= len(windows)
     enqueue_max_s = enqueue_s
     if world > 1:                                              # the slowest rank's host loop (8 ranks share one host)
         t = torch.tensor([enqueue_s], dtype=torch.float64, device=dev if backend != 'gloo' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         enqueue_max_s = float(t.item())
-    elapsed = sorted(windows)[len(windows) // 2]
     prof, eng.prof, eng.prof_pick = eng.prof, None, None
     loss_val = float(loss.item())
-    ms_step = elapsed / args.steps * 1e3
+    ms_step = sorted(windows)[len(windows) // 2] * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, loss)
 
     roofline = None
     if prof:
@@ -920,14 +968,14 @@ def main():
             roofline['grid'] = {'blocks': blocks, 'cus': cus, 'concurrent_with': 'the dz chain (data-gradient convs, BatchNorm / unpool / upsample backward) on the other stream',
                                 'frac_of_occupied_cus': achieved / peak * cus / min(blocks, cus)}
     if rank == 0:
-        pairs = args.steps * B * world
-        value = pairs / elapsed
+        value = B * world / (ms_step * 1e-3)
         peak = MFMA_F32_PEAK if args.precision == 'fp32' else MFMA_BF16_PEAK
         out = {
             'metric': 'patch-pairs/sec (fwd+bwd) 13-band 128x128', 'value': value, 'unit': 'patch-pairs/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': ms_step, 'windows_ms_per_step': [w / args.steps * 1e3 for w in windows],
-            'timing': f'median of {len(windows)} consecutive windows of {args.steps} steps (barrier + synchronize around each, max over ranks)',
+            'ms_per_step': ms_step, 'windows_ms_per_step': [w * 1e3 for w in windows],
+            'timing': f'{args.steps} timed steps in {len(windows)} consecutive windows of {win_steps} steps: ms per step of the median window '
+                      f'(barrier + synchronize around each, max over ranks)',
             'higher_is_better': True, 'scaling': 'weak',
             'vs_baseline': None, 'dtype': args.precision, 'data': 'synthetic',
             'config': {'workload': f'BiDateNet({C},2) {C}-band {S}x{S} patch pairs, batch {B}/GPU, '

@@ -2,6 +2,8 @@
 container (TEST INFRASTRUCTURE; see oracle/__init__.py).
 
     python oracle/make_golden.py            # needs /root/reference (read-only)
+    python oracle/make_golden.py losses     # only the loss fixtures (G5, G9)
+    python oracle/make_golden.py pickle     # only the reference checkpoint fixture (G10)
 
 The reference's Python never travels to the GPU box; only the outputs written
 here do.  Parameters are not stored: both sides regenerate them from
@@ -225,6 +227,25 @@ def _loss_case_more(ref_metrics, oracle):
     print('g9_losses_more:', {k: round(float(v), 6) for k, v in out.items() if np.ndim(v) == 0})
 
 
+def _pickle_case(BiDateNet):
+    """G10: the reference's own whole-module checkpoint -- torch.save of nn.DataParallel(BiDateNet(3, 2)) as train.py:222 writes it,
+    wrapped as utils/helpers.py:333-335 does -- and the state dict of the same wrapper, gzip-compressed.  Every parameter holds a ramp
+    of period 251 offset by its position in parameters() instead of random values: the 54 MB of tensors compress to a few kB, and a
+    key or layout mix-up on loading still changes what a test compares."""
+    import gzip
+    import io
+    torch.manual_seed(3)
+    m = torch.nn.DataParallel(BiDateNet(3, 2)).cpu()
+    with torch.no_grad():
+        for i, p in enumerate(m.parameters()):
+            p.copy_(((torch.arange(p.numel()) % 251).float() / 251.0 + i).reshape(p.shape))
+    for name, obj in (('g10_reference_module_pickle.pt.gz', m), ('g10_reference_state_dict.pt.gz', m.state_dict())):
+        buf = io.BytesIO()
+        torch.save(obj, buf)
+        with gzip.GzipFile(os.path.join(OUT, name), 'wb', compresslevel=9, mtime=0) as f:
+            f.write(buf.getvalue())
+
+
 def main():
     sys.path.insert(0, ROOT)
     from oracle import bidate_oracle as oracle
@@ -236,6 +257,9 @@ def main():
         _loss_case(ref_metrics, oracle)
         _loss_case_more(ref_metrics, oracle)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == 'pickle':        # regenerate only the checkpoint fixture
+        _pickle_case(BiDateNet)
+        return
     _train_case(BiDateNet, ref_metrics, oracle, filler, 'g1_c3_b4_s32', 3, 4, 32)
     _train_case(BiDateNet, ref_metrics, oracle, filler, 'g2_c13_b2_s128', 13, 2, 128)
     _train_case(BiDateNet, ref_metrics, oracle, filler, 'g4_c13_b2_s90', 13, 2, 90)
@@ -244,6 +268,7 @@ def main():
     _loss_case(ref_metrics, oracle)
     _loss_case_more(ref_metrics, oracle)
     _loader_case(ref_dl, ref_inf, oracle)
+    _pickle_case(BiDateNet)
 
 
 if __name__ == '__main__':
