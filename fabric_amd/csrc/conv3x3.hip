@@ -25,9 +25,6 @@
 // float32 source: BatchNorm+ReLU and the hi / lo split inside the staging).
 #include "common.hpp"
 #include <type_traits>
-#ifndef BDN_X3_FUSED
-#define BDN_X3_FUSED 1      /* A/B switch of the round (tools/build_lib_variant.sh old "-DBDN_X3_FUSED=0") */
-#endif
 
 struct ConvArgs {
     const void* in0; const void* in1; int C0, C1;
@@ -1000,17 +997,6 @@ static int dispatch_conv_bb(const ConvArgs& a, const ConvPlan& p, hipStream_t st
     return launch_conv<bf16s, 128, 8, 16, 1, 64, 2, 2, false, bf16s, false, true>(a, g.n_mtiles, st);
 }
 
-// bf16x3 setting: same tile geometry as the plan above (the caller sizes the statistics buffer from it), 64-wide column tiles,
-// float32 outputs; the reduction runs over 3*Cin channels (hi|lo of the split operand, then its hi part again).
-template <int CKB>
-static int dispatch_conv_x3(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
-    const TileGeom& g = p.g;
-    if (g.TH == 16) return launch_conv<bf16s, CKB, 16, 16, 1, 64, 4, 1, false, float>(a, g.n_mtiles, st);
-    if (g.TI == 1 && p.BN == 128) return launch_conv<bf16s, CKB, 8, 16, 1, 128, 1, 4, false, float>(a, g.n_mtiles, st);   // wide layers: as the bf16 path
-    if (g.TI == 1) return launch_conv<bf16s, CKB, 8, 16, 1, 64, 2, 2, false, float>(a, g.n_mtiles, st);
-    return launch_conv<bf16s, CKB, 8, 8, 2, 64, 2, 2, false, float>(a, g.n_mtiles, st);
-}
-
 // bf16x3 with the split product fused into one reduction (operands of at least 64 channels): two patches per chunk in LDS, so no 16x16 tiles
 static ConvPlan conv_plan_x3f(int N, int H, int W, int Cout, int imgs_per_group) {
     ConvPlan p;
@@ -1035,7 +1021,7 @@ static int dispatch_conv_x3f(const ConvArgs& a, const ConvPlan& p, hipStream_t s
 // tiles of a launch by operand type: the bf16x3 kernels with the fused split product have their own tile plan
 extern "C" int bdn_conv3x3_num_mtiles_ex(int dtype, int N, int H, int W, int C0, int Cout, int imgs_per_group) {
     if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || imgs_per_group <= 0) return 0;
-    if (BDN_X3_FUSED && (dtype == BDN_BF16X3 || dtype == BDN_BF16X2) && C0 % 16 == 0) return conv_plan_x3f(N, H, W, Cout, imgs_per_group).g.n_mtiles;
+    if ((dtype == BDN_BF16X3 || dtype == BDN_BF16X2) && C0 % 16 == 0) return conv_plan_x3f(N, H, W, Cout, imgs_per_group).g.n_mtiles;
     return conv_plan(N, H, W, Cout, imgs_per_group).g.n_mtiles;
 }
 
@@ -1063,14 +1049,12 @@ static int conv3x3_impl(int dtype, const void* in0, int C0, const void* in1, int
     a.in0 = in0; a.in1 = in1; a.C0 = C0; a.C1 = C1; a.ld0 = C0; a.ld1 = C1;
     a.w_kgroups = 0;
     if (dtype == BDN_BF16X3 || dtype == BDN_BF16X2) {
-        // in0 is the split operand of bdn_split_pack: [N,H,W,2*C0] bf16 = hi(C0) | lo(C0).  K = [hi | lo | hi] against the
+        // in0 is the split operand of bdn_split_pack: [N,H,W,2*C0] bf16 = hi(C0) | lo(C0), staged as two patches per chunk against the
         // packed filter image [w_hi | w_hi | w_lo]: a_hi*w_hi + a_lo*w_hi + a_hi*w_lo accumulate in the same f32 MFMA tile.
-        // BDN_BF16X2: K = [hi | lo] against the first two thirds of every image row -- a_hi*w_hi + a_lo*w_hi
+        // BDN_BF16X2: the first two terms -- a_hi*w_hi + a_lo*w_hi
         if (in1 || in_mode != BDN_IN_PLAIN) BDN_FAIL(BDN_E_ARG, "conv3x3(bf16x3): one split-packed, plain operand (bdn_split_pack does cat / BatchNorm+ReLU)");
         if (C0 % 16) BDN_FAIL(BDN_E_SHAPE, "conv3x3(bf16x3): C0=%d must be a multiple of 16", C0);
-        if (BDN_X3_FUSED) { a.in1 = nullptr; a.C0 = C0; a.C1 = 0; a.ld0 = 2 * C0; a.ld1 = 0; a.w_kgroups = 3 * C0 / 16; }     // fused split product (below)
-        else if (dtype == BDN_BF16X3) { a.in1 = in0; a.C0 = 2 * C0; a.C1 = C0; a.ld0 = a.ld1 = 2 * C0; }
-        else { a.in1 = nullptr; a.C0 = 2 * C0; a.C1 = 0; a.ld0 = 2 * C0; a.ld1 = 0; a.w_kgroups = 3 * C0 / 16; }
+        a.in1 = nullptr; a.C0 = C0; a.C1 = 0; a.ld0 = 2 * C0; a.ld1 = 0; a.w_kgroups = 3 * C0 / 16;
     }
     {   // the kernels address every tensor as one uniform base + a 32-bit byte offset
         const size_t npix = (size_t)N * H * W, es = dtype == BDN_F32 ? 4 : 2, oes = dtype == BDN_BF16 ? 2 : 4;      // (bf16x3 / bf16x2: bf16 operands, float32 outputs)
@@ -1085,7 +1069,7 @@ static int conv3x3_impl(int dtype, const void* in0, int C0, const void* in1, int
     a.N = N; a.H = H; a.W = W; a.Cout = Cout;
     a.ep_scale = a.ep_shift = nullptr; a.ep_mul = nullptr; a.ep_pool = nullptr; a.pair_stride = 0;
     a.cls_w = a.cls_b = nullptr; a.cls_n = 0; a.cls_logits = nullptr; a.cls_mask = nullptr; a.cls_origins = nullptr; a.cls_H = a.cls_W = 0; a.x3_split = nullptr;
-    const bool x3f = BDN_X3_FUSED && (dtype == BDN_BF16X3 || dtype == BDN_BF16X2);       // (C0 % 16 == 0 was checked above: 64-channel chunks where C0 allows, else 16)
+    const bool x3f = (dtype == BDN_BF16X3 || dtype == BDN_BF16X2);       // (C0 % 16 == 0 was checked above: 64-channel chunks where C0 allows, else 16)
     const ConvPlan g = x3f ? conv_plan_x3f(N, H, W, Cout, imgs_per_group) : conv_plan(N, H, W, Cout, imgs_per_group);
     a.tiles_y = g.g.tiles_y; a.tiles_x = g.g.tiles_x; a.n_ntiles = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1105,9 +1089,6 @@ static int conv3x3_impl(int dtype, const void* in0, int C0, const void* in1, int
         if (C0 % 32 == 0 && C1 % 32 == 0) return dispatch_conv<float, 128>(a, g, st);
         if (C0 % 16 == 0 && C1 % 16 == 0) return dispatch_conv<float, 64>(a, g, st);
         BDN_FAIL(BDN_E_SHAPE, "conv3x3(f32): C0=%d C1=%d must be multiples of 16", C0, C1);
-    } else if (dtype == BDN_BF16X3 || dtype == BDN_BF16X2) {
-        if ((a.C0 / 2) % 64 == 0) return dispatch_conv_x3<128>(a, g, st);
-        return dispatch_conv_x3<32>(a, g, st);
     }
     BDN_FAIL(BDN_E_ARG, "conv3x3: bad dtype %d", dtype);
 }

@@ -1132,9 +1132,6 @@ static void launch_wgrad_reduce(const float* partial, float* dw, int S, int Cout
 //   flags bits 0-1   phases (bdn_conv3x3_wgrad_ex)
 //   flags bits 8-11  kernel override: 0 = the library's choice, BDN_WG_SIMPLE forces the one-chunk-at-a-time kernel
 //   flags bits 16-28 target grid size of the GEMM (0 = default, one block per CU)
-#ifndef BDN_WG_X3_FUSED
-#define BDN_WG_X3_FUSED 1     /* A/B switch of the round (tools/build_lib_variant.sh old "-DBDN_WG_X3_FUSED=0") */
-#endif
 constexpr int WG_SIMPLE_MULT = 2;
 constexpr int WG_X3_SKIP = 1 << 30;          // internal plan flag, see wgrad_plan
 constexpr int WG_X3_TWO = 1 << 29;           // internal plan flag (BDN_BF16X2): only the hi half of dz -- the [lo, hi] quadrant is left out as well
@@ -1227,7 +1224,7 @@ extern "C" int bdn_conv3x3_wgrad_ex(int dtype, const void* dz, int Cout,
             BDN_FAIL(BDN_E_SHAPE, "wgrad(bf16x3): Cout=%d must be a multiple of 32, C0=%d of 8, Cin_real=%d <= C0", Cout, C0, Cin_real);
         if (N <= 0 || H <= 0 || W <= 0 || imgs_per_group <= 0 || N % imgs_per_group)
             BDN_FAIL(BDN_E_SHAPE, "wgrad(bf16x3): bad N=%d H=%d W=%d imgs_per_group=%d", N, H, W, imgs_per_group);
-        if (BDN_WG_X3_FUSED && Cout % 64 == 0 && C0 % 64 == 0 && (size_t)N * H * W * 2 * (size_t)(Cout > C0 ? Cout : C0) < ((size_t)1 << 31)) {
+        if (Cout % 64 == 0 && C0 % 64 == 0 && (size_t)N * H * W * 2 * (size_t)(Cout > C0 ? Cout : C0) < ((size_t)1 << 31)) {
             // full 64-channel tiles on 8 x 16 spatial tiles: the terms of the split product in one accumulator (wgrad7x_kernel), the plan of
             // the LOGICAL [Cout] x [C0] problem, the plain split-K reduction straight into dw
             const WgPlan pf = wgrad_plan(BDN_BF16, N, H, W, Cout, C0, 0, imgs_per_group, BDN_IN_PLAIN, phases);

@@ -132,7 +132,7 @@ class Workspace:
                 for key in d_._shapes:
                     d_[key]
         lib = _lib.load()
-        n_stats = n_bnb = n_wg = 1
+        n_stats = n_bnb = 1
         for L in eng.layers:
             hk, wk = self.dims[L.level - 1]
             n, ipg = (2 * B, B) if L.enc else (B, B)
@@ -146,51 +146,52 @@ class Workspace:
             if L.enc:                                 # enc_skip_bwd leaves its BatchNorm-backward partials here too
                 n_stats = max(n_stats, 2 * lib.bdn_enc_skip_bwd_rows(eng.dt, B, hk, wk, L.cout) * 2 * L.cout)
             n_bnb = max(n_bnb, lib.bdn_bn_bwd_workspace_bytes(eng.dt, n, hk, wk, L.cout, ipg) // 4)
-            if not eng.x3:                            # bf16x3 sizes its doubled-operand workspace per call (split_buf)
-                for blocks in (0, 512):               # 512: head room for A/B runs of engine.wgrad_blocks (any grid up to 512 fits)
-                    n_wg = max(n_wg, lib.bdn_wgrad_workspace_bytes_ex(eng.dt, n, hk, wk, L.cout, L.cin, 0, ipg, IN_PLAIN, wg_flags(3, 0, blocks)) // 4)
         self.stats = f32(n_stats)
         self.bnws = torch.empty(2 * 64 * 2 * 1024, dtype=torch.float64, device=device)
-        self._chain2 = None        # (stats, bnws) of the second forward chain, allocated when the two-chain forward first runs
-        self.n_bnb, self.n_wg = n_bnb, n_wg
-        L1 = eng.layers[0]                                # the first conv's fused weight-gradient GEMM runs beside another layer's
-        self.n_wg1 = max(lib.bdn_wgrad_workspace_bytes_ex(dt_, 2 * B, H, W, L1.cout, L1.cin, 0, B, IN_PLAIN, wg_flags(3, 0, blocks)) // 4
-                         for blocks in (0, 256, 512) for dt_ in ((eng.dt, BDN_BF16) if eng.x3 else (eng.dt,)))      # (0 / 512: the plain GEMM when it runs on the chain's stream, engine.last_wgrad_on_chain)
+        self.n_bnb = n_bnb
         self._bwd = None
         self._split = {}
+        self._wg, self._wg_bytes = {}, {}
         self._outc_ws = None
         self.logits = None
         self.x0_split = False      # bf16x3: the last pack_input stored the first convolution's split operand instead of x0
         self.leased = False        # True while a live autograd graph still needs this workspace's z / bn tables for its backward
         self.generation = 0        # bumped by every forward that overwrites the buffers (models/bidate_model.py checks it before a backward)
 
+    def _grown(self, bufs, key, numel, dtype):
+        """bufs[key], grown on demand to at least numel elements."""
+        t = bufs.get(key)
+        if t is None or t.numel() < numel:
+            if t is not None:
+                # the buffer being replaced may still be in use by a weight-gradient GEMM queued on the second stream: its block must not be
+                # handed out again before that stream has passed this point
+                from . import streams
+                t.record_stream(streams.get('wgrad', self.x0.device))
+            t = bufs[key] = torch.empty(numel, dtype=dtype, device=self.x0.device)
+        return t[:numel]
+
     def split_buf(self, which, numel):
         """bf16x3: buffer of a split GEMM operand ([.., 2C] bf16 = hi | lo), grown on demand.  Keys: ('a', layer) the layer's input
         operand, written by its training forward and read again by its weight-gradient GEMM; ('d', layer) its dz, split once on the
         chain's stream for the data-gradient conv and the weight-gradient GEMM (per layer: the weight-gradient stream may lag a
-        layer behind); 'a' the shared operand buffer of eval forwards; 'p' the weight-gradient GEMM's workspace on its stream."""
-        t = self._split.get(which)
-        if t is None or t.numel() < numel:
-            if t is not None:
-                # the buffer being replaced may still be read by a weight-gradient GEMM queued on the second stream: its block must not be
-                # handed out again before that stream has passed this point
-                from . import streams
-                t.record_stream(streams.get('wgrad', self.x0.device))
-            t = torch.empty(numel, dtype=torch.bfloat16, device=self.x0.device)
-            self._split[which] = t
-        return t[:numel]
+        layer behind); 'a' the shared operand buffer of eval forwards."""
+        return self._grown(self._split, which, numel, torch.bfloat16)
+
+    def wgrad_scratch(self, role, size_fn, *args):
+        """float32 partial-tile scratch of one weight-gradient launch, one buffer per role: 'wgrad' (the GEMMs on the weight-gradient
+        stream) and 'chain' (the GEMM or bdn_conv3x3_wgrad_bnbwd on the chain's stream, beside the other role's).  The buffer grows to
+        what the library reports for THIS call: size_fn(*args) is 'bdn_wgrad_workspace_bytes_ex' with the launch's own arguments and
+        flags word, or 'bdn_wgrad_workspace_bytes' for bdn_conv3x3_wgrad_bnbwd.  Sizes are cached per call: a steady-state step asks
+        the library nothing and allocates nothing."""
+        nb = self._wg_bytes.get((size_fn, args))
+        if nb is None:
+            nb = self._wg_bytes[size_fn, args] = getattr(_lib.load(), size_fn)(*args)
+        return self._grown(self._wg, role, max(nb // 4, 1), torch.float32)
 
     def release_split(self):
         """bf16x3: drop the per-layer operand-split buffers (at B=16, 128x128 about 1.5 GB per workspace that has trained).  They are
         re-grown on demand by the next training forward; an eval-only phase after training calls this (BiDateNet.eval() does)."""
         self._split = {}
-
-    def chain2(self):
-        """Per-tile statistics buffer and finalize scratch of the forward's second chain (date 2 on its own stream): the two chains'
-        convolutions are in flight at once, so they cannot share ws.stats / ws.bnws."""
-        if self._chain2 is None:
-            self._chain2 = (torch.empty_like(self.stats), torch.empty_like(self.bnws))
-        return self._chain2
 
     def outc_ws(self, eng):
         """Scratch of bdn_outc_bwd (per-block partial classifier gradients)."""
@@ -202,8 +203,6 @@ class Workspace:
     def bwd_scratch(self, device):
         if self._bwd is None:
             self._bwd = dict(bnb=torch.empty(self.n_bnb, dtype=torch.float32, device=device),
-                             wg=torch.empty(self.n_wg, dtype=torch.float32, device=device),
-                             wg1=torch.empty(self.n_wg1, dtype=torch.float32, device=device),
                              sums=torch.empty(2 * 2 * 1024, dtype=torch.float32, device=device))
         return self._bwd
 
@@ -252,11 +251,6 @@ class BiDateEngine:
         # all four +0.2 % -- everything within ~0.2 % of noise on that box; on a second box e1b alone is +0.6 % against e1b+d4a.
         # The two full-resolution layers are kept (134 + 268 MB of dz reads less)
         self.fold_bn_bwd = ('e1b', 'd4a')
-        # forward schedule.  fwd_chains = 2: the two dates go through encoder levels 1..fwd_chain_levels as two B-image chains on two streams
-        # (_encoder_two_chains; bit-identical, measured +0.1...+1.3 % step time in round 5: off)
-        self.fwd_chains = 1
-        self.fwd_chain_levels = 3
-        self._fwd_handoffs = {}
         self.wgrad_kernel = 0           # per-call kernel override of the weight-gradient GEMM (0 = the library's choice, _lib.WG_*)
         # bf16x3 settings: terms of the split product in the BACKWARD GEMMs.  The forward always keeps three (logits within 1e-3 of the reference:
         # north_star's bar).  'bf16x3' (the parity setting) keeps three in the backward as well; 'bf16x3-fast' is the explicit opt-in to two
@@ -299,29 +293,37 @@ class BiDateEngine:
         """Symbol of the conv3x3_kernel instantiation bdn_conv3x3 dispatches to: asked from the library's own dispatcher."""
         return _lib.load().bdn_conv3x3_variant(self.mdt, n, h, w, c0 + c1 if self.x3 else c0, 0 if self.x3 else c1, cout, ipg).decode()
 
-    def _timed_conv(self, n, h, w, c0, c1, cout, ipg, *args, fn='bdn_conv3x3', bb=False):
-        name = None
-        if self.prof is not None:                   # BatchNorm-backward-on-load and float32-source launches have their own dispatchers: ask them
-            if bb:
-                name = _lib.load().bdn_conv3x3_dgrad_bb_variant(n, h, w, cout, ipg).decode()
-            elif fn == 'bdn_conv3x3_x3src':
-                name = _lib.load().bdn_conv3x3_x3src_variant(args[0], n, h, w, c0, cout, ipg).decode()
-            else:
-                name = self.conv_kernel_name(n, h, w, c0, c1, cout, ipg)
-        if self.prof is None or (self.prof_filter is not None and name not in self.prof_filter):
-            call(fn, *args)
-            return
-        if self.prof_pick is not None:              # sparse sampling: bracket only the prof_pick-th matching launch of this step
-            self._prof_seen += 1
-            if self._prof_seen - 1 != self.prof_pick:
-                call(fn, *args)
+    def _timed(self, name, flops, fn, *args, split=None):
+        """call(fn, *args), bracketed when profiling picks the launch: self.prof is a list, name() (asked only then) is in prof_filter
+        (if set) and the launch is the prof_pick-th one of the step that is (if set).  A picked launch sits between two timing events
+        recorded on the current stream and (name, flops, e0, e1) is appended to self.prof.  split = (timed, rest): a picked launch is
+        issued as call(*timed) between the events and call(*rest) behind them (the weight-gradient GEMM apart from its reduction)."""
+        if self.prof is not None:
+            name = name()
+            picked = self.prof_filter is None or name in self.prof_filter
+            if picked and self.prof_pick is not None:      # sparse sampling: bracket only the prof_pick-th matching launch of this step
+                self._prof_seen += 1
+                picked = self._prof_seen - 1 == self.prof_pick
+            if picked:
+                timed, rest = split or ((fn, *args), None)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                call(*timed)
+                e1.record()
+                if rest:
+                    call(*rest)
+                self.prof.append((name, flops, e0, e1))
                 return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
         call(fn, *args)
-        e1.record()
-        self.prof.append((name,
-                          2.0 * n * h * w * cout * 9 * (c0 + c1), e0, e1))
+
+    def _timed_conv(self, n, h, w, c0, c1, cout, ipg, *args, fn='bdn_conv3x3', bb=False):
+        def name():                                 # BatchNorm-backward-on-load and float32-source launches have their own dispatchers: ask them
+            if bb:
+                return _lib.load().bdn_conv3x3_dgrad_bb_variant(n, h, w, cout, ipg).decode()
+            if fn == 'bdn_conv3x3_x3src':
+                return _lib.load().bdn_conv3x3_x3src_variant(args[0], n, h, w, c0, cout, ipg).decode()
+            return self.conv_kernel_name(n, h, w, c0, c1, cout, ipg)
+        self._timed(name, 2.0 * n * h * w * cout * 9 * (c0 + c1), fn, *args)
 
     # ------------------------------------------------------------------ helpers
     def mtiles(self, n, h, w, c0, cout, ipg):
@@ -364,39 +366,30 @@ class BiDateEngine:
 
     def _pack_all(self, P):
         import struct
-        if self.x3:
-            # split filter images, three times the reduction length: [w_hi | w_hi | w_lo] (csrc/x3.hip); all layers in one launch
-            ptrs = tuple(P[f'{L.conv}.weight'].data_ptr() for L in self.layers)
-            if self._pack_desc is None or self._pack_desc[0] != ptrs:
-                dev = P[f'{self.layers[0].conv}.weight'].device
-                self._packed, rec = {}, b''
-                for L in self.layers:
-                    wf = torch.empty(L.cout, 9, 3 * L.cin, dtype=torch.bfloat16, device=dev)
-                    wd = torch.empty(L.cin, 9, 3 * L.cout, dtype=torch.bfloat16, device=dev) if L.name != 'e1a' else None
-                    self._packed[L.conv] = (wf, wd)
-                    rec += struct.pack('<QQQiiii', P[f'{L.conv}.weight'].data_ptr(), wf.data_ptr(),
-                                       wd.data_ptr() if wd is not None else 0, L.cout, L.cin_real, L.cin, 0)
-                self._pack_desc = (ptrs, torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(dev))
-            call('bdn_pack_weights_multi', BDN_BF16X3, ptr(self._pack_desc[1]), len(self.layers), _lib.stream_ptr())
-            self._packed_versions = tuple(P[f'{L.conv}.weight']._version for L in self.layers)
-            self._packed_valid = True
-            return
         ptrs = tuple(P[f'{L.conv}.weight'].data_ptr() for L in self.layers)
         if self._pack_desc is None or self._pack_desc[0] != ptrs:
+            # bf16x3: split filter images, three times the reduction length: [w_hi | w_hi | w_lo] (csrc/x3.hip)
+            kx, pdt = (3, torch.bfloat16) if self.x3 else (1, self.tdtype)
             dev = P[f'{self.layers[0].conv}.weight'].device
-            rec = b''
-            self._packed = {}
+            self._packed, rec = {}, b''
             for L in self.layers:
-                wf = torch.empty(L.cout, 9, L.cin, dtype=self.tdtype, device=dev)
-                wd = torch.empty(L.cin, 9, L.cout, dtype=self.tdtype, device=dev) if L.name != 'e1a' else None
+                wf = torch.empty(L.cout, 9, kx * L.cin, dtype=pdt, device=dev)
+                wd = torch.empty(L.cin, 9, kx * L.cout, dtype=pdt, device=dev) if L.name != 'e1a' else None
                 self._packed[L.conv] = (wf, wd)
                 rec += struct.pack('<QQQiiii', P[f'{L.conv}.weight'].data_ptr(), wf.data_ptr(),
                                    wd.data_ptr() if wd is not None else 0, L.cout, L.cin_real, L.cin, 0)
-            desc = torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(dev)
-            self._pack_desc = (ptrs, desc)
-        call('bdn_pack_weights_multi', self.dt, ptr(self._pack_desc[1]), len(self.layers), _lib.stream_ptr())
+            self._pack_desc = (ptrs, torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(dev))
+        call('bdn_pack_weights_multi', self.mdt, ptr(self._pack_desc[1]), len(self.layers), _lib.stream_ptr())
         self._packed_versions = tuple(P[f'{L.conv}.weight']._version for L in self.layers)
         self._packed_valid = True
+
+    def _check_packed(self, P):
+        """Mark the packed images stale when an optimizer touched the master weights (version counters) or they were re-pointed at
+        other storage.  In-place writes through `p.data` (p.data.copy_(ema), p.data.clamp_()) bump NEITHER: call invalidate_weights()
+        after such an update (BiDateNet.load_state_dict / _apply do it themselves)."""
+        if self._packed_valid and (self._packed_versions != tuple(P[f'{L.conv}.weight']._version for L in self.layers) or
+                                   self._pack_desc[0] != tuple(P[f'{L.conv}.weight'].data_ptr() for L in self.layers)):
+            self._packed_valid = False
 
     def invalidate_weights(self):
         self._packed_valid = False
@@ -408,20 +401,11 @@ class BiDateEngine:
                 if not ws.leased:
                     ws.release_split()
 
-    def _conv(self, ws, L, P, in0, c0, in1, c1, in_mode, in_bn, n, ipg, training, st, reuse_eval_bn=False, presplit=False,
-              date=None, before_finalize=None, after_finalize=None):
-        """One conv3x3 + BatchNorm statistics stage.  date = 0 / 1: the launch covers ONE date's B images of an encoder layer (two-chain
-        forward): its slice of z, its row of the BatchNorm table, and -- for date 1, whose launches run beside date 0's -- the second
-        chain's statistics buffers.  before_finalize / after_finalize: callables around the finalize launch (the running statistics
-        see date 0 then date 1, so date 1's finalize is ordered behind date 0's)."""
+    def _conv(self, ws, L, P, in0, c0, in1, c1, in_mode, in_bn, n, ipg, training, st, reuse_eval_bn=False, presplit=False):
+        """One conv3x3 + BatchNorm statistics stage."""
         hk, wk = ws.dims[L.level - 1]
         wf, _ = self._weights(L, P, False)
-        z = ws.z[L.name]
-        stats, bnws, bn = ws.stats, ws.bnws, ws.bn[L.name]
-        if date is not None:
-            z, bn = z[date * n:(date + 1) * n], bn[date:date + 1]
-            if date == 1:
-                stats, bnws = ws.chain2()
+        z, bn = ws.z[L.name], ws.bn[L.name]
         xs = self.x3_src_f32
         if self.x3 and in1 is None and not presplit and c0 % 64 == 0 and c0 <= 512 and xs and \
                 (not isinstance(xs, (tuple, list, set)) or L.name in xs or (not training and c0 <= 128)):
@@ -431,7 +415,7 @@ class BiDateEngine:
             sp = ws.split_buf(('a', L.name), n * hk * wk * 2 * c0) if training else None
             self._timed_conv(n, hk, wk, c0, 0, L.cout, ipg,
                              self.mdt, ptr(in0), c0, in_mode, ptr(in_bn), ipg, ptr(wf), ptr(P[f'{L.conv}.bias']), ptr(z),
-                             ptr(stats) if training else None, ptr(sp), n, hk, wk, L.cout, st, fn='bdn_conv3x3_x3src')
+                             ptr(ws.stats) if training else None, ptr(sp), n, hk, wk, L.cout, st, fn='bdn_conv3x3_x3src')
         else:
             if self.x3:
                 # the operand split does the cat and the BatchNorm+ReLU the f32 kernel would apply on load
@@ -442,19 +426,15 @@ class BiDateEngine:
                 in0, c0, in1, c1, in_mode, in_bn = sp, c0 + c1, None, 0, IN_PLAIN, None
             self._timed_conv(n, hk, wk, c0, c1, L.cout, ipg,
                              self.mdt, ptr(in0), c0, ptr(in1), c1, in_mode, ptr(in_bn), ipg,
-                             ptr(wf), ptr(P[f'{L.conv}.bias']), ptr(z), ptr(stats) if training else None,
+                             ptr(wf), ptr(P[f'{L.conv}.bias']), ptr(z), ptr(ws.stats) if training else None,
                              n, hk, wk, L.cout, st)
         G = n // ipg
         if training:
             nt = self.mtiles(n, hk, wk, c0 + c1, L.cout, ipg)
-            if before_finalize is not None:
-                before_finalize()
-            call('bdn_bn_finalize', ptr(stats), nt, G, L.cout, ipg * hk * wk,
+            call('bdn_bn_finalize', ptr(ws.stats), nt, G, L.cout, ipg * hk * wk,
                  ptr(P[f'{L.bn}.weight']), ptr(P[f'{L.bn}.bias']), BN_EPS, BN_MOMENTUM,
                  ptr(P[f'{L.bn}.running_mean']), ptr(P[f'{L.bn}.running_var']),
-                 ptr(P[f'{L.bn}.num_batches_tracked']), ptr(bn), ptr(bnws), st)
-            if after_finalize is not None:
-                after_finalize()
+                 ptr(P[f'{L.bn}.num_batches_tracked']), ptr(bn), ptr(ws.bnws), st)
         elif not reuse_eval_bn:
             call('bdn_bn_eval', ptr(P[f'{L.bn}.weight']), ptr(P[f'{L.bn}.bias']),
                  ptr(P[f'{L.bn}.running_mean']), ptr(P[f'{L.bn}.running_var']), BN_EPS, G, L.cout, ptr(bn), st)
@@ -534,21 +514,13 @@ class BiDateEngine:
         dev = ws.x0.device
         st = _lib.stream_ptr()
         _lib.PHASE = 'fwd'
-        by = {L.name: L for L in self.layers}
-        if self._packed_valid and (self._packed_versions != tuple(P[f'{L.conv}.weight']._version for L in self.layers) or
-                                   self._pack_desc[0] != tuple(P[f'{L.conv}.weight'].data_ptr() for L in self.layers)):
-            # an optimizer touched the master weights (version counters), or they were re-pointed at other storage.
-            # In-place writes through `p.data` (p.data.copy_(ema), p.data.clamp_()) bump NEITHER: call
-            # invalidate_weights() after such an update (BiDateNet.load_state_dict / _apply do it themselves).
-            self._packed_valid = False
         if not training and self._use_eval_schedule():
             return self._forward_eval(ws, P, reuse_tables=reuse_eval_bn)
+        self._check_packed(P)
+        by = {L.name: L for L in self.layers}
         rb = reuse_eval_bn and not training
-        k_first = 1
-        if self.fwd_chains == 2 and training and not self.x3:
-            k_first = self._encoder_two_chains(ws, P, by, st)
         # ---- shared encoder on both dates (2B images, 2 statistic groups)
-        for k in range(k_first, 6):
+        for k in range(1, 6):
             hk, wk = ws.dims[k - 1]
             La, Lb = by[f'e{k}a'], by[f'e{k}b']
             pre = self.x3 and training                      # bf16x3 training: pooled maps, skips and upsampled maps are stored as split operands
@@ -592,10 +564,12 @@ class BiDateEngine:
     def _use_eval_schedule(self):
         return self.eval_fused and not self.x3
 
-    def eval_tables(self, P):
+    def eval_tables(self, P, refold=True):
         """Eval-mode BatchNorm of all 18 layers folded with the conv biases (bdn_bn_eval_fold_multi: one launch on the current stream).
         Returns {layer name: (scale [Cout], shift [Cout])}; the buffers are cached per parameter storage and REWRITTEN by every call
-        (running statistics move without a version bump)."""
+        (running statistics move without a version bump).  refold=False: the caller knows the tables already hold P's running statistics;
+        they are folded anyway when P's parameters live at other storage than the cached tables were folded from.  One shared buffer:
+        calls must not run concurrently on two streams."""
         import struct
         keys = [(f'{L.bn}.weight', f'{L.bn}.bias', f'{L.bn}.running_mean', f'{L.bn}.running_var', f'{L.conv}.bias') for L in self.layers]
         ptrs = tuple(P[k].data_ptr() for ks in keys for k in ks)
@@ -611,7 +585,9 @@ class BiDateEngine:
             ident = torch.zeros(1, 4, self.layers[-1].cout, dtype=torch.float32, device=dev)   # {mean 0, invstd 1, scale 1, shift 0}: relu(bn(a)) = a for a >= 0
             ident[:, 1:3] = 1.0
             self._ev = (ptrs, torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(dev), views, ident, tab)
-        call('bdn_bn_eval_fold_multi', ptr(self._ev[1]), len(self.layers), max(L.cout for L in self.layers), BN_EPS, _lib.stream_ptr())
+            refold = True
+        if refold:
+            call('bdn_bn_eval_fold_multi', ptr(self._ev[1]), len(self.layers), max(L.cout for L in self.layers), BN_EPS, _lib.stream_ptr())
         return self._ev[2]
 
     def _forward_eval(self, ws, P, reuse_tables=False, mask=None, origins=None, scene_hw=None):
@@ -628,10 +604,8 @@ class BiDateEngine:
         st = _lib.stream_ptr()
         _lib.PHASE = 'fwd'
         by = {L.name: L for L in self.layers}
-        if self._packed_valid and (self._packed_versions != tuple(P[f'{L.conv}.weight']._version for L in self.layers) or
-                                   self._pack_desc[0] != tuple(P[f'{L.conv}.weight'].data_ptr() for L in self.layers)):
-            self._packed_valid = False
-        ev = self._ev[2] if (reuse_tables and self._ev is not None) else self.eval_tables(P)
+        self._check_packed(P)
+        ev = self.eval_tables(P, refold=not reuse_tables)
 
         def stage(L, in0, c0, in1, c1, out, n, hk, wk, mul=None, pool=None):
             wf, _ = self._weights(L, P, False)
@@ -686,66 +660,6 @@ class BiDateEngine:
                     call('bdn_argmax', ptr(logits), ptr(mask), B, self.n_classes, H, W, st)
                 return None
         return logits
-
-    def _fwd_handoff(self, dev, i):
-        pool = self._fwd_handoffs.setdefault(dev.index, [])
-        while len(pool) <= i:
-            from .streams import HandOff
-            with torch.cuda.device(dev):
-                pool.append(HandOff())
-        return pool[i]
-
-    def _encoder_two_chains(self, ws, P, by, st):
-        """Encoder levels 1..fwd_chain_levels with the two dates as two independent B-image chains: date 0 on the current (chain) stream,
-        date 1 on the library's second stream (idle in forward).  The reference runs the dates one after the other through the same
-        modules (models/bidate_model.py:23-33); here they were one 2B batch with two statistic groups -- the split changes no arithmetic
-        (same tiles, same per-group reductions) but lets one date's convolutions run while the other's dependent reduce / finalize / pool
-        launches drain.  Ordering kept by events: the running statistics and num_batches_tracked are updated by date 0's finalize first,
-        then by date 1's (reference order).  Date 0's chain pools its own map; date 1's chain forms the skip f_k (it needs date 0's z and
-        table: ordered behind date 0's finalize of that layer already) together with ITS pooled map in one pass.  Measured (round 5, six
-        more variants of where the products run / which stream / how many levels): +0.1...+1.3 % step time -- the option stays OFF.
-        Returns the first level the joined schedule continues with."""
-        from . import streams
-        B = ws.B
-        dev = ws.x0.device
-        main = torch.cuda.current_stream(dev)
-        second = streams.get('wgrad', dev)
-        Lmax = max(1, min(4, self.fwd_chain_levels))
-        ev = [0]
-
-        def new_ev():
-            ev[0] += 1
-            return self._fwd_handoff(dev, ev[0] - 1)
-
-        self._weights(self.layers[0], P, False)              # (re)pack the filter images NOW, on the chain stream, in front of the fork
-        start = new_ev()
-        start.signal(main)                                   # packed input and packed weights are ready
-        start.wait(second)
-        chains = ((0, main, st), (1, second, second.cuda_stream))
-        fin_events = {}
-        for k in range(1, Lmax + 1):
-            hk, wk = ws.dims[k - 1]
-            La, Lb = by[f'e{k}a'], by[f'e{k}b']
-            src = ws.x0 if k == 1 else ws.pool[k]
-            for L in (La, Lb):
-                fin_events[L.name] = new_ev()
-            for d, stream, sp in chains:
-                with torch.cuda.stream(stream):
-                    def order(L, d=d, stream=stream):
-                        if d == 0:
-                            return dict(after_finalize=lambda: fin_events[L.name].signal(stream))
-                        return dict(before_finalize=lambda: fin_events[L.name].wait(stream))
-                    za, bna = self._conv(ws, La, P, src[d * B:(d + 1) * B], La.cin, None, 0, IN_PLAIN, None, B, B, True, sp, date=d, **order(La))
-                    zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, B, B, True, sp, date=d, **order(Lb))
-                    if d == 0:
-                        call('bdn_bnrelu_pool', self.dt, ptr(zb), ptr(bnb), B, ptr(ws.pool[k + 1][:B]), B, hk, wk, ENC_CH[k - 1], sp)
-                    else:
-                        call('bdn_product_pool_dates', self.dt, ptr(ws.z[Lb.name]), ptr(ws.bn[Lb.name]), ptr(ws.f[k]), ptr(ws.pool[k + 1]), 2,
-                             B, hk, wk, ENC_CH[k - 1], sp)
-        join = new_ev()
-        join.signal(second)
-        join.wait(main)
-        return Lmax + 1
 
     # ------------------------------------------------------------------ backward
     def backward(self, ws, dlogits, P, grads, on_ready=None, zero_bias_grads=True, wgrad_stream=True):
@@ -813,10 +727,9 @@ class BiDateEngine:
                 return dz, out, self.mtiles(n, hk, wk, L.cout, L.cin, ipg) // G
             return dz, out
 
-        def wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, stp, part_key='p'):
-            """The weight-gradient GEMM and its reduction; with profiling on, the GEMM alone sits between two events
-            recorded on the stream it is launched on."""
-            lib = _lib.load()
+        def wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, stp, role='wgrad'):
+            """The weight-gradient GEMM and its reduction, its partial tiles in the role's scratch (Workspace.wgrad_scratch); with
+            profiling on, the GEMM alone sits between two events recorded on the stream it is launched on (bf16x3: not timed)."""
             if self.x3:
                 # both operands were split already: the activations by this layer's forward, dz by split_dz() on the chain's stream
                 # (per-layer buffers: the weight-gradient stream may still read one while the chain splits the next layer's)
@@ -825,38 +738,26 @@ class BiDateEngine:
                 blk_ = self.x3_tail_wgrad_blocks if (L.name == 'e1b' and self.x3_tail_wgrad_blocks and self.x3_bwd_terms == 3) else self.wgrad_blocks
                 flg = wg_flags(1 if self._diag_skip_reduce else 3, 0, blk_)      # (_diag_skip_reduce: timing diagnostics only)
                 xdt = BDN_BF16X2 if self.x3_bwd_terms == 2 else BDN_BF16X3
-                nb = lib.bdn_wgrad_workspace_bytes_ex(xdt, n, hk, wk, L.cout, c0 + c1, 0, ipg, IN_PLAIN, flg)
-                part = ws.split_buf(part_key, nb // 2)        # ('p1': the one GEMM that runs on the chain's stream beside the queue's own)
+                part = ws.wgrad_scratch(role, 'bdn_wgrad_workspace_bytes_ex', xdt, n, hk, wk, L.cout, c0 + c1, 0, ipg, IN_PLAIN, flg)
                 call('bdn_conv3x3_wgrad_ex', xdt, ptr(sd), L.cout, ptr(sw), c0 + c1, None, 0, IN_PLAIN, None, ipg,
                      ptr(part), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk, flg, stp)
                 return
             wk_, blk_ = self.wgrad_kernel, self.wgrad_blocks
+            flg = wg_flags(1 if self._diag_skip_reduce else 3, wk_, blk_)
+            part = ws.wgrad_scratch(role, 'bdn_wgrad_workspace_bytes_ex', self.dt, n, hk, wk, L.cout, c0, c1, ipg, mode, flg)
             args = (self.dt, ptr(dz), L.cout, ptr(in0), c0, ptr(in1), c1, mode, ptr(in_bn), ipg,
-                    ptr(sc['wg1' if part_key == 'p1' else 'wg']), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk)
-            name = None
-            if self.prof is not None:
-                v = lib.bdn_conv3x3_wgrad_variant(self.dt, n, hk, wk, L.cout, c0, c1, ipg, mode, wg_flags(3, wk_, blk_))
+                    ptr(part), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk)
+
+            def name():
+                v = _lib.load().bdn_conv3x3_wgrad_variant(self.dt, n, hk, wk, L.cout, c0, c1, ipg, mode, wg_flags(3, wk_, blk_))
                 if v == WG_ROLE:
-                    name = f'wgrad7_kernel<{"true" if mode == IN_BNRELU else "false"}>'
-                else:
-                    small = wk <= 8 and hk <= 8 and ipg % 2 == 0
-                    name = (f'wgrad_kernel<{"bf16" if self.precision == "bf16" else "f32"},8,{"8,2" if small else "16,1"},'
-                            f'{"true" if c0 + c1 <= 32 else "false"}>')
-                if self.prof_filter is not None and name not in self.prof_filter:
-                    name = None
-                elif self.prof_pick is not None:
-                    self._prof_seen += 1
-                    if self._prof_seen - 1 != self.prof_pick:
-                        name = None
-            if name is None:
-                call('bdn_conv3x3_wgrad_ex', *args, wg_flags(1 if self._diag_skip_reduce else 3, wk_, blk_), stp)
-                return
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call('bdn_conv3x3_wgrad_ex', *args, wg_flags(1, wk_, blk_), stp)
-            e1.record()
-            call('bdn_conv3x3_wgrad_ex', *args, wg_flags(2, wk_, blk_), stp)
-            self.prof.append((name, 2.0 * n * hk * wk * L.cout * 9 * (c0 + c1), e0, e1))
+                    return f'wgrad7_kernel<{"true" if mode == IN_BNRELU else "false"}>'
+                small = wk <= 8 and hk <= 8 and ipg % 2 == 0
+                return (f'wgrad_kernel<{"bf16" if self.precision == "bf16" else "f32"},8,{"8,2" if small else "16,1"},'
+                        f'{"true" if c0 + c1 <= 32 else "false"}>')
+            self._timed(name, 2.0 * n * hk * wk * L.cout * 9 * (c0 + c1), 'bdn_conv3x3_wgrad_ex', *args, flg, stp,
+                        split=(('bdn_conv3x3_wgrad_ex', *args, wg_flags(1, wk_, blk_), stp),
+                               ('bdn_conv3x3_wgrad_ex', *args, wg_flags(2, wk_, blk_), stp)))
 
         n_hand = [0]
 
@@ -894,7 +795,7 @@ class BiDateEngine:
                 # run and the second queue is still busy with the layer before it -- the two GEMMs run side by side instead of one behind
                 # the other (bf16x3: 0.36 ms behind a 1.3 ms GEMM at the end of the step).  The chain then joins the second queue: the
                 # bucket this ready() may release holds gradients whose GEMMs are still queued there.
-                wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, st, part_key='p1')
+                wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, st, role='chain')
                 if zero_bias_grads:
                     grads[f'{L.conv}.bias'].zero_()
                 handoff(side, main)
@@ -1028,17 +929,11 @@ class BiDateEngine:
                     fin = ws.split_buf(('a', La.name), 2 * B * hk * wk * 2 * La.cin)
                 else:
                     fdt, fin = self.dt, ws.x0
-                wargs = (fdt, ptr(dAa), La.cout, ptr(ws.z[La.name]), ptr(ws.bn[La.name]), ptr(sc['sums']), B, La.cout,
-                         ptr(fin), La.cin, ptr(sc['wg1']), ptr(grads[f'{La.conv}.weight']), La.cin_real, 2 * B, hk, wk, st)
                 if not self._diag_skip_wgrad:
-                    if self.prof is not None and (self.prof_filter is None or 'wgrad_first_kernel' in self.prof_filter):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        call('bdn_conv3x3_wgrad_bnbwd', *wargs)
-                        e1.record()
-                        self.prof.append(('wgrad_first_kernel', 2.0 * 2 * B * hk * wk * La.cout * 9 * La.cin, e0, e1))
-                    else:
-                        call('bdn_conv3x3_wgrad_bnbwd', *wargs)
+                    part = ws.wgrad_scratch('chain', 'bdn_wgrad_workspace_bytes', 2 * B, hk, wk, La.cout, La.cin, B)
+                    self._timed(lambda: 'wgrad_first_kernel', 2.0 * 2 * B * hk * wk * La.cout * 9 * La.cin, 'bdn_conv3x3_wgrad_bnbwd',
+                                fdt, ptr(dAa), La.cout, ptr(ws.z[La.name]), ptr(ws.bn[La.name]), ptr(sc['sums']), B, La.cout,
+                                ptr(fin), La.cin, ptr(part), ptr(grads[f'{La.conv}.weight']), La.cin_real, 2 * B, hk, wk, st)
                 if zero_bias_grads:
                     grads[f'{La.conv}.bias'].zero_()
                 if side is not None:

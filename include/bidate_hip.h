@@ -309,11 +309,6 @@ int bdn_fuse_product(int dtype, const void* z, const float* bn, void* f,
  * f [B,H,W,C] = relu(a_d2*a_d1), pool [2B,H/2,W/2,C] = MaxPool2d(2)(a), a = relu(bn(z)), z [2B,H,W,C] date 1 first. */
 int bdn_product_pool(int dtype, const void* z, const float* bn, void* f, void* pool,
                      int B, int H, int W, int C, void* stream);
-/* The same pass writing the pooled maps of SOME dates only (pool_dates: bit 0 = date 1, bit 1 = date 2; f is always written): the
- * two-chain forward runs the dates of models/bidate_model.py:23-33 on two streams, where the chain of date 2 forms the skip and its own
- * pooled map while date 1's chain pools its own map with bdn_bnrelu_pool (same values, bit for bit). */
-int bdn_product_pool_dates(int dtype, const void* z, const float* bn, void* f, void* pool, int pool_dates,
-                           int B, int H, int W, int C, void* stream);
 
 /* bf16x3 setting (float32 z): both outputs stored directly as the [hi | lo] bf16 operands of the convolutions that consume them -- f into
  * channels [0, C) of the decoder stage's two-source operand f_split [B,H,W,f_ld] (lo half f_half channels further), pool as

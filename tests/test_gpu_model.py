@@ -188,17 +188,20 @@ def test_bf16x3_first_layer_weight_gradient_fused(golden_dir, prec):
     load (bdn_conv3x3_wgrad_bnbwd, engine.first_wgrad_fused) against bn_bwd_apply_split + the generic GEMM: every other gradient bit for bit,
     inc.conv.conv.0.weight's within 1e-4 of its magnitude (same products, another summation order)."""
     g, c, x1, x2, lbl = _load(golden_dir, 'g2_c13_b2_s128')
-    grads = {}
+    grads, ran = {}, {}
     for fused in (True, False):
         model = filler.fill_module(BiDateNet(c, 2, precision=prec)).cuda().train()
-        model.engine().first_wgrad_fused = fused
+        eng = model.engine()
+        eng.first_wgrad_fused, eng.prof = fused, []
         _tversky_torch(model(x1, x2), lbl).backward()
+        ran[fused] = 'wgrad_first_kernel' in [name for name, *_ in eng.prof]
+        eng.prof = None
         grads[fused] = {k: p.grad.detach().clone() for k, p in model.named_parameters()}
+    assert ran == {True: True, False: False}                       # the fused launch ran, and only where asked for
     for k in grads[True]:
         a, b = grads[True][k], grads[False][k]
         if k == 'inc.conv.conv.0.weight':
             assert (a - b).abs().max().item() <= 1e-4 * b.abs().max().item(), k
-            assert not torch.equal(a, b) or True
         else:
             assert torch.equal(a, b), k
 

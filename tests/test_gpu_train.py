@@ -126,36 +126,43 @@ def test_three_train_steps_same_speed():
     assert max(med) <= 1.02 * min(med), med
 
 
-@pytest.mark.parametrize('prec', ['bf16', 'fp32'])
-@pytest.mark.parametrize('shape', [(13, 6, 128, 128), (3, 4, 40, 72), (13, 2, 90, 90)])
-def test_two_chain_forward_is_bit_identical(prec, shape):
-    """engine.fwd_chains = 2 runs the two dates of encoder levels 1-3 as two chains on two streams (reference order of the dates,
-    models/bidate_model.py:23-33, is kept for the running statistics by events).  It must change NO bit: logits, loss, every BatchNorm
-    table and buffer, every gradient and the parameters after three SGD steps equal the one-chain schedule's, for 1..4 split levels."""
-    c, b, h, w = shape
-    x1, x2, lbl = filler.make_inputs(b, c, h, seed=5, size_w=w)
-    x1, x2, lbl = torch.from_numpy(x1).cuda(), torch.from_numpy(x2).cuda(), torch.from_numpy(lbl).cuda()
+@pytest.mark.parametrize('prec', ['bf16', 'fp32', 'bf16x3', 'bf16x3-fast'])
+def test_wgrad_scratch_fits_every_launch(prec, monkeypatch):
+    """Every weight-gradient launch of a backward gets a partial-tile scratch of at least the bytes the library reports for that exact
+    call (bdn_wgrad_workspace_bytes_ex with the launch's own arguments and flags; bdn_wgrad_workspace_bytes for bdn_conv3x3_wgrad_bnbwd),
+    also for grids and kernel overrides other than the default plan.  The GEMMs are recorded, not launched."""
+    from fabric_amd import _lib, engine, streams
+    lib = _lib.load()
+    c, b, s = 13, 2, 128
+    x1, x2, _ = filler.make_inputs(b, c, s, seed=5)
+    x1, x2 = torch.from_numpy(x1).cuda(), torch.from_numpy(x2).cuda()
+    model = filler.fill_module(BiDateNet(c, 2, precision=prec)).cuda().train()
+    eng = model.engine()
+    P = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
+    grads = {k: torch.zeros_like(p) for k, p in model.named_parameters()}
+    side = streams.get('wgrad', x1.device).cuda_stream
+    launches, real_call, ws = [], engine.call, None
 
-    def run(chains, levels):
-        model = filler.fill_module(BiDateNet(c, 2, precision=prec)).cuda().train()
-        eng = model.engine()
-        eng.fwd_chains, eng.fwd_chain_levels = chains, levels
-        ts = TrainStep(model, lr=0.05)
-        out = []
-        for _ in range(3):
-            loss = ts.step(x1, x2, lbl)
-            ws = eng.workspace(b, h, w, x1.device)
-            out += [loss.clone(), ts.last_logits.clone(), ts.flat_grads.clone()] + [ws.bn[L.name].clone() for L in eng.layers]
-            out += [ws.f[k].clone() for k in range(1, 6)] + [ws.pool[k].clone() for k in range(2, 6)]
-        torch.cuda.synchronize()
-        return out + [v.clone() for v in model.state_dict().values()]
-
-    ref = run(1, 3)
-    for levels in (3, 1, 2, 4):
-        got = run(2, levels)
-        assert len(got) == len(ref)
-        for i, (a_, r_) in enumerate(zip(got, ref)):
-            assert torch.equal(a_, r_), (levels, i)
+    def recording_call(fn, *a):             # checks each launch's scratch when it is issued (a later launch may grow the buffer)
+        if fn == 'bdn_conv3x3_wgrad_ex':    # (dtype, dz, Cout, in0, C0, in1, C1, in_mode, in_bn, ipg, partial, dw, Cin_real, N, H, W, flags, stream)
+            size = ('bdn_wgrad_workspace_bytes_ex', a[0], a[13], a[14], a[15], a[2], a[4], a[6], a[9], a[7], a[16])
+        elif fn == 'bdn_conv3x3_wgrad_bnbwd':   # (dtype, dA, ldA, z, bn, sums, ipg, Cout, in0, C0, partial, dw, Cin_real, N, H, W, stream)
+            size = ('bdn_wgrad_workspace_bytes', a[13], a[14], a[15], a[7], a[9], a[6])
+        else:
+            return real_call(fn, *a)
+        need = getattr(lib, size[0])(*size[1:])
+        buf = ws.wgrad_scratch('wgrad' if a[-1] == side else 'chain', *size)
+        launches.append((size, buf.data_ptr() == a[10] and buf.untyped_storage().nbytes() >= need))
+    monkeypatch.setattr(engine, 'call', recording_call)
+    for blocks in (0, 512, 768):
+        for kernel in (0, _lib.WG_SIMPLE):
+            eng.wgrad_blocks, eng.wgrad_kernel = blocks, kernel
+            logits, ws = eng.forward(x1, x2, P, training=True)
+            launches.clear()
+            eng.backward(ws, torch.zeros_like(logits), P, grads)
+            torch.cuda.synchronize()
+            assert len(launches) == len(eng.layers)
+            assert all(ok for _, ok in launches), (blocks, kernel, [size for size, ok in launches if not ok])
 
 
 def test_bn_backward_folded_into_the_data_gradient_conv_matches_the_separate_pass():
