@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('BIDATE_LIB') or os.path.join(_HERE, 'csrc', 'libbidat
 
 BDN_F32, BDN_BF16, BDN_BF16X3, BDN_BF16X2 = 0, 1, 2, 3
 IN_PLAIN, IN_BNRELU = 0, 1
+EVAL_STAGE, EVAL_PAIR, EVAL_CLS = 0, 1, 2
 WG_SIMPLE, WG_ROLE = 1, 5
 
 
@@ -78,6 +79,7 @@ SIGNATURES = {
     'bdn_tversky': (_i, [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_conv3x3_variant': (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i, _i]),
     'bdn_conv3x3_dgrad_bb_variant': (C.c_char_p, [_i, _i, _i, _i, _i]),
+    'bdn_conv3x3_eval_variant': (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i, _i]),
     'bdn_conv3x3_x3src_variant': (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
     'bdn_conv3x3_dgrad_bs': (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     'bdn_conv3x3_dgrad_bb': (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

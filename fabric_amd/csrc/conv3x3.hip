@@ -1298,6 +1298,25 @@ extern "C" int bdn_conv3x3_eval_cls(int dtype, const void* in0, int C0, const vo
                              Hs, Ws, N, H, W, Cout, stream);
 }
 
+// which instantiation an eval-mode entry point runs (kind BDN_EVAL_STAGE / _PAIR / _CLS): the entry point itself in query mode.  The fused
+// consumers (mul, pool, logits / mask / stitching) are runtime arguments of the same instantiation and do not change the answer.
+extern "C" const char* bdn_conv3x3_eval_variant(int kind, int dtype, int N, int H, int W, int C0, int C1, int Cout) {
+    g_conv_variant[0] = 0;
+    g_conv_query = true;
+    void* dummy = reinterpret_cast<void*>(16);             // never dereferenced: nothing is launched in query mode
+    const float* fd = reinterpret_cast<const float*>(dummy);
+    int rc = BDN_E_ARG;
+    if (kind == BDN_EVAL_STAGE)
+        rc = bdn_conv3x3_eval(dtype, dummy, C0, C1 ? dummy : nullptr, C1, dummy, fd, fd, dummy, nullptr, nullptr, N, H, W, Cout, nullptr);
+    else if (kind == BDN_EVAL_PAIR && C1 == 0)
+        rc = bdn_conv3x3_eval_pair(dtype, dummy, C0, dummy, fd, fd, dummy, nullptr, N, H, W, Cout, nullptr);
+    else if (kind == BDN_EVAL_CLS && C1 == 0)
+        rc = bdn_conv3x3_eval_cls(dtype, dummy, C0, dummy, fd, fd, nullptr, fd, fd, 2, reinterpret_cast<float*>(dummy), nullptr, nullptr,
+                                  0, 0, N, H, W, Cout, nullptr);
+    g_conv_query = false;
+    return rc == BDN_OK ? g_conv_variant : "";
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // 3x3x3 convolution, stride 1, zero padding 1 in depth / height / width -- the building block of BASELINE configs[3], the
 // multi-date 3-D U-Net (5 dates x 13 bands x 128 x 128).  The reference tree has NO source for that model (UNetLSTM/ is an

@@ -1187,7 +1187,10 @@ extern "C" size_t bdn_wgrad_workspace_bytes(int N, int H, int W, int Cout, int C
     // default flags, any dtype / source split / input mode: the largest plan
     const size_t a = bdn_wgrad_workspace_bytes_ex(BDN_F32, N, H, W, Cout, Cin, 0, imgs_per_group, BDN_IN_PLAIN, 0);
     const size_t b = bdn_wgrad_workspace_bytes_ex(BDN_BF16, N, H, W, Cout, Cin, 0, imgs_per_group, BDN_IN_PLAIN, 0);
-    const size_t c = bdn_wgrad_workspace_bytes_ex(BDN_BF16X3, N, H, W, Cout, Cin, 0, imgs_per_group, BDN_IN_PLAIN, 0);
+    const size_t c3 = bdn_wgrad_workspace_bytes_ex(BDN_BF16X3, N, H, W, Cout, Cin, 0, imgs_per_group, BDN_IN_PLAIN, 0);
+    // BDN_BF16X2 leaves the [lo, hi] quadrant out as well: fewer tiles, so more splits -- on small maps its doubled-operand plan is the larger
+    const size_t c2 = bdn_wgrad_workspace_bytes_ex(BDN_BF16X2, N, H, W, Cout, Cin, 0, imgs_per_group, BDN_IN_PLAIN, 0);
+    const size_t c = c3 > c2 ? c3 : c2;
     // bdn_conv3x3_wgrad_bnbwd (first layer, end of backward) plans its own, larger grid
     const size_t d = Cin <= 32 ? bdn_wgrad_workspace_bytes_ex(BDN_BF16, N, H, W, Cout, Cin, 0, imgs_per_group, BDN_IN_PLAIN, BDN_WG_FLAGS(0, 0, 256)) : 0;
     size_t m = a > b ? a : b;

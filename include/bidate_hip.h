@@ -261,6 +261,11 @@ int bdn_conv3x3_eval_pair(int dtype, const void* in, int C0, const void* w, cons
 int bdn_conv3x3_eval_cls(int dtype, const void* in0, int C0, const void* w, const float* ep_scale, const float* ep_shift, void* act_out,
                          const float* cls_w, const float* cls_b, int ncls, float* logits, uint8_t* mask, const int32_t* origins,
                          int Hs, int Ws, int N, int H, int W, int Cout, void* stream);
+/* Name of the kernel instantiation an eval-mode entry point runs for a shape (as bdn_conv3x3_variant; "" for an unsupported shape):
+ * kind BDN_EVAL_STAGE = bdn_conv3x3_eval (N images, sources C0 | C1), BDN_EVAL_PAIR = bdn_conv3x3_eval_pair (N = B pairs, C1 = 0),
+ * BDN_EVAL_CLS = bdn_conv3x3_eval_cls (C1 = 0).  The fused consumers do not change the instantiation.  Thread-local buffer. */
+enum { BDN_EVAL_STAGE = 0, BDN_EVAL_PAIR = 1, BDN_EVAL_CLS = 2 };
+const char* bdn_conv3x3_eval_variant(int kind, int dtype, int N, int H, int W, int C0, int C1, int Cout);
 
 /* ---- BatchNorm2d + ReLU backward (autograd of models/unet_parts.py:14-15,17-18) ----
  * g = dA * [z*scale+shift > 0]; sums[g][0][c] = sum g, sums[g][1][c] = sum g*xhat (layout [G][2][C]);

@@ -86,12 +86,15 @@ def bn_table(G, C, seed=0):
 
 
 def bnrelu_ref(precision, z_nchw, bn, ipg):
-    """relu(z*scale+shift) per group, rounded to the storage type like every kernel does."""
+    """relu(z*scale+shift) per group, rounded to the storage type like every kernel does: the kernels evaluate z*scale+shift with ONE
+    fused multiply-add (one rounding to float32, csrc/common.hpp bnrelu_unit), emulated here in float64 (the product of two float32
+    values is exact there) and rounded once to float32 -- a separate multiply and add round twice, and on a small map the few bf16 values
+    that then round the other way move a weight gradient by more than its bar."""
     out = torch.empty_like(z_nchw)
     G = bn.shape[0]
     for g in range(G):
         s = slice(g * ipg, (g + 1) * ipg)
-        out[s] = torch.relu(z_nchw[s] * bn[g, 2][None, :, None, None] + bn[g, 3][None, :, None, None])
+        out[s] = torch.relu((z_nchw[s].double() * bn[g, 2].double()[None, :, None, None] + bn[g, 3].double()[None, :, None, None]).float())
     return rnd(precision, out)
 
 

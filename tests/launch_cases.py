@@ -1,0 +1,418 @@
+"""The launch-shape table: one row per kernel instantiation that BiDateNet runs, at the smallest shape that selects it.
+
+In this library the SHAPE of a launch picks the kernel instantiation (tile shape, wave layout, 64- or 128-wide column tiles,
+single-chunk, eval epilogue, split-K plan).  Each row below names an entry point, its numerics, a shape and options, and the exact
+instantiation that shape must select; tests/test_launch_cases_cpu.py checks that against the library's own dispatchers (host-side
+queries, no GPU), tests/test_gpu_launch_shapes.py runs every row against a float64 reference.  The enumeration functions at the end
+walk one training step / eval forward of BiDateNet layer by layer (fabric_amd/engine.py) and name what each launch runs, so the CPU
+test can require that every instantiation of the real step has a row; the GPU test records the launches of real steps and checks that
+they equal this enumeration.
+
+Shapes are ragged (H % 8 != 0, W % 16 != 0) wherever the plan allows it.  A plain module (like tests/gpu_util.py), not a conftest.
+"""
+from collections import namedtuple
+
+from fabric_amd import _lib
+from fabric_amd._lib import (BDN_BF16, BDN_BF16X2, BDN_BF16X3, BDN_F32, EVAL_CLS, EVAL_PAIR, EVAL_STAGE, IN_BNRELU, IN_PLAIN, WG_ROLE,
+                             wg_flags)
+
+DTYPE = {'fp32': BDN_F32, 'bf16': BDN_BF16, 'bf16x3': BDN_BF16X3, 'bf16x2': BDN_BF16X2}
+
+# op           entry point
+#   fwd        bdn_conv3x3 forward, per-tile statistics when `stats` (then bdn_bn_finalize on them)
+#   dgrad      bdn_conv3x3 on dz with the data-gradient filter image (C0 = the layer's Cout, Cout = its Cin)
+#   dgrad_bs   bdn_conv3x3_dgrad_bs (masked gradient + BatchNorm-backward partial sums of the producing layer)
+#   dgrad_bb   bdn_conv3x3_dgrad_bb (BatchNorm backward of the layer applied on load; C0 = 64)
+#   x3         bdn_conv3x3 on the bdn_split_pack operand (prec bf16x3 / bf16x2; forward and data gradient run the same kernels)
+#   x3src      bdn_conv3x3_x3src (float32 operand, BatchNorm+ReLU and the split on load when `bnrelu`)
+#   eval / eval_pair / eval_cls   bdn_conv3x3_eval / _eval_pair (N = B pairs) / _eval_cls
+#   wgrad      bdn_conv3x3_wgrad_ex at default flags (bf16x3 / bf16x2: split operands); `lanes` = split lanes of its reduction
+#   wgrad_bnbwd  bdn_conv3x3_wgrad_bnbwd (first layer, C0 = 16, Cout = 64)
+Row = namedtuple('Row', 'op prec N H W C0 C1 Cout ipg bnrelu stats inst lanes')
+
+
+def _r(op, prec, N, H, W, C0, C1, Cout, ipg, inst, bnrelu=False, stats=True, lanes=None):
+    return Row(op, prec, N, H, W, C0, C1, Cout, ipg, bnrelu, stats, inst, lanes)
+
+
+def _ck(t, cfg, to, bb=False, ev=False, x3=0, xf=False):
+    return (f'conv3x3_kernel<{t},{cfg},{to},false,{"true" if bb else "false"},{"true" if ev else "false"},{x3},'
+            f'{"true" if xf else "false"}>')
+
+
+BF, F32 = 'bf16', 'float'
+# tile configurations: CKB, TH, TW, TI, BN, WM, WN, ONE
+K816_128 = '128,8,16,1,128,1,4,false'
+K816_128_ONE = '128,8,16,1,128,1,4,true'
+K816_64 = '128,8,16,1,64,2,2,false'
+K1616_ONE = '128,16,16,1,64,2,2,true'
+K1616 = '128,16,16,1,64,4,1,false'
+K88_64 = '128,8,8,2,64,2,2,false'
+K88_128 = '128,8,8,2,128,2,2,false'
+
+ROWS = [
+    # ---- forward + statistics, bf16 and fp32.  BN = 128 needs n_mtiles * Cout / 128 >= 512 (conv_plan): 4 x 61 x 125 on 8 x 16 tiles is
+    # 4 * 8 * 8 = 256 tiles x 2 column tiles = 512 -- the smallest ragged shape at Cout = 256
+    _r('fwd', 'bf16', 4, 61, 125, 64, 64, 256, 2, _ck(BF, K816_128, BF)),                       # two sources, two chunks
+    _r('fwd', 'bf16', 4, 61, 125, 128, 0, 256, 2, _ck(BF, K816_128, BF), bnrelu=True),          # BatchNorm+ReLU on load
+    _r('fwd', 'bf16', 4, 61, 125, 64, 0, 256, 2, _ck(BF, K816_128_ONE, BF)),                    # single chunk
+    _r('fwd', 'bf16', 4, 61, 125, 64, 0, 256, 2, _ck(BF, K816_128_ONE, BF), bnrelu=True),
+    _r('fwd', 'fp32', 4, 61, 125, 64, 64, 256, 2, _ck(F32, K816_128, F32)),
+    _r('fwd', 'fp32', 4, 61, 125, 128, 0, 256, 2, _ck(F32, K816_128, F32), bnrelu=True),
+    # the BN threshold itself: 3 x 37 x 270 = 3 * 5 * 17 = 255 tiles (510 blocks) stays at BN = 64, 4 x 37 x 270 = 340 tiles goes to 128
+    _r('fwd', 'bf16', 3, 37, 270, 128, 0, 256, 1, _ck(BF, K816_64, BF), bnrelu=True),
+    _r('fwd', 'bf16', 4, 37, 270, 128, 0, 256, 2, _ck(BF, K816_128, BF), bnrelu=True),
+    # 64-wide outputs on 16 x 16 tiles; 8 x 8 maps with two images per tile (BN = 128 at 512 channels)
+    _r('fwd', 'bf16', 4, 29, 45, 64, 0, 64, 2, _ck(BF, K1616_ONE, BF), bnrelu=True),
+    _r('fwd', 'bf16', 4, 29, 45, 16, 0, 64, 2, _ck(BF, '32,16,16,1,64,2,2,true', BF)),          # the 13(16)-band first layer
+    _r('fwd', 'bf16', 2, 29, 45, 128, 64, 64, 2, _ck(BF, K1616, BF)),
+    _r('fwd', 'bf16', 4, 8, 8, 256, 256, 256, 2, _ck(BF, K88_64, BF)),
+    _r('fwd', 'bf16', 4, 7, 5, 512, 0, 512, 2, _ck(BF, K88_64, BF), bnrelu=True),
+    _r('fwd', 'fp32', 4, 29, 45, 64, 0, 64, 2, _ck(F32, '128,16,16,1,64,4,1,false', F32), bnrelu=True),
+    _r('fwd', 'fp32', 4, 29, 45, 16, 0, 64, 2, _ck(F32, '64,16,16,1,64,2,2,true', F32)),
+    _r('fwd', 'fp32', 3, 37, 270, 128, 0, 256, 1, _ck(F32, K816_64, F32), bnrelu=True),
+    _r('fwd', 'fp32', 4, 7, 5, 512, 0, 512, 2, _ck(F32, K88_64, F32), bnrelu=True),
+    # ---- plain data gradient (dz of Cout = C0 channels -> Cin = Cout channels)
+    _r('dgrad', 'bf16', 4, 61, 125, 128, 0, 256, 2, _ck(BF, K816_128, BF)),
+    _r('dgrad', 'fp32', 4, 61, 125, 128, 0, 256, 2, _ck(F32, K816_128, F32)),
+    _r('dgrad', 'bf16', 2, 29, 45, 128, 0, 64, 2, _ck(BF, K1616, BF)),
+    _r('dgrad', 'bf16', 4, 7, 5, 512, 0, 512, 2, _ck(BF, K88_64, BF)),
+    # ---- masked data gradient with the producing layer's BatchNorm-backward partial sums
+    _r('dgrad_bs', 'bf16', 4, 61, 125, 128, 0, 256, 2, _ck(BF, K816_128, BF)),
+    _r('dgrad_bs', 'bf16', 4, 61, 125, 64, 0, 256, 2, _ck(BF, K816_128_ONE, BF)),
+    _r('dgrad_bs', 'bf16', 4, 29, 45, 64, 0, 64, 2, _ck(BF, K1616_ONE, BF)),
+    _r('dgrad_bs', 'bf16', 4, 29, 45, 128, 0, 64, 2, _ck(BF, K1616, BF)),
+    _r('dgrad_bs', 'bf16', 4, 37, 53, 256, 0, 128, 2, _ck(BF, K816_64, BF)),
+    _r('dgrad_bs', 'fp32', 4, 61, 125, 128, 0, 256, 2, _ck(F32, K816_128, F32)),
+    _r('dgrad_bs', 'fp32', 4, 29, 45, 64, 0, 64, 2, _ck(F32, K1616, F32)),
+    _r('dgrad_bs', 'fp32', 4, 7, 5, 512, 0, 512, 2, _ck(F32, K88_64, F32)),
+    # ---- BatchNorm backward on load: all three instantiations
+    _r('dgrad_bb', 'bf16', 4, 29, 45, 64, 0, 64, 2, _ck(BF, K1616_ONE, BF, bb=True)),
+    _r('dgrad_bb', 'bf16', 4, 61, 125, 64, 0, 256, 2, _ck(BF, K816_128_ONE, BF, bb=True)),
+    _r('dgrad_bb', 'bf16', 2, 37, 53, 64, 0, 128, 1, _ck(BF, K816_64, BF, bb=True)),
+    # ---- bf16x3 / bf16x2 on the split operand (X3 = terms; 64-channel chunks, or 16 for the first layer)
+    _r('x3', 'bf16x3', 4, 61, 125, 128, 0, 256, 2, _ck(BF, K816_128, F32, x3=3)),
+    _r('x3', 'bf16x3', 4, 29, 45, 192, 0, 64, 2, _ck(BF, K816_64, F32, x3=3)),
+    _r('x3', 'bf16x3', 4, 7, 5, 512, 0, 512, 2, _ck(BF, K88_64, F32, x3=3)),
+    _r('x3', 'bf16x3', 4, 29, 45, 16, 0, 64, 2, _ck(BF, '32,8,16,1,64,2,2,false', F32, x3=3)),
+    _r('x3', 'bf16x2', 4, 61, 125, 128, 0, 256, 2, _ck(BF, K816_128, F32, x3=2)),
+    _r('x3', 'bf16x2', 4, 29, 45, 192, 0, 64, 2, _ck(BF, K816_64, F32, x3=2)),
+    _r('x3', 'bf16x2', 4, 7, 5, 512, 0, 512, 2, _ck(BF, K88_64, F32, x3=2)),
+    _r('x3src', 'bf16x3', 4, 61, 125, 128, 0, 256, 2, _ck(BF, K816_128, F32, x3=3, xf=True), bnrelu=True),
+    _r('x3src', 'bf16x3', 4, 29, 45, 64, 0, 64, 2, _ck(BF, K816_64, F32, x3=3, xf=True), bnrelu=True),
+    _r('x3src', 'bf16x3', 4, 7, 5, 512, 0, 512, 2, _ck(BF, K88_64, F32, x3=3, xf=True), bnrelu=True),
+    _r('x3src', 'bf16x3', 4, 61, 125, 64, 0, 256, 2, _ck(BF, K816_128, F32, x3=3, xf=True), stats=False),       # plain operand (eval)
+    _r('x3src', 'bf16x2', 4, 61, 125, 128, 0, 256, 2, _ck(BF, K816_128, F32, x3=2, xf=True), bnrelu=True),
+    # ---- eval epilogue (EV): stage, date pair (N = B pairs), classifier
+    _r('eval', 'bf16', 4, 61, 125, 64, 64, 256, 1, _ck(BF, K816_128, BF, ev=True)),
+    _r('eval', 'bf16', 4, 61, 125, 64, 0, 256, 1, _ck(BF, K816_128_ONE, BF, ev=True)),
+    _r('eval', 'bf16', 3, 37, 270, 128, 0, 256, 1, _ck(BF, K816_64, BF, ev=True)),
+    _r('eval', 'bf16', 4, 29, 45, 64, 0, 64, 1, _ck(BF, K1616_ONE, BF, ev=True)),
+    _r('eval', 'bf16', 4, 29, 45, 16, 0, 64, 1, _ck(BF, '32,16,16,1,64,2,2,true', BF, ev=True)),
+    _r('eval', 'bf16', 2, 29, 45, 128, 64, 64, 1, _ck(BF, K1616, BF, ev=True)),
+    _r('eval', 'bf16', 256, 7, 5, 64, 0, 512, 1, _ck(BF, K88_128, BF, ev=True)),              # 128 tiles of two images x 4: BN = 128
+    _r('eval', 'bf16', 4, 7, 5, 512, 0, 512, 1, _ck(BF, K88_64, BF, ev=True)),
+    _r('eval', 'fp32', 4, 61, 125, 64, 64, 256, 1, _ck(F32, K816_128, F32, ev=True)),
+    _r('eval', 'fp32', 4, 29, 45, 16, 0, 64, 1, _ck(F32, '64,16,16,1,64,2,2,true', F32, ev=True)),
+    _r('eval', 'fp32', 3, 37, 270, 128, 0, 256, 1, _ck(F32, K816_64, F32, ev=True)),
+    _r('eval', 'fp32', 256, 7, 5, 64, 0, 512, 1, _ck(F32, K88_128, F32, ev=True)),
+    _r('eval', 'fp32', 4, 7, 5, 512, 0, 512, 1, _ck(F32, K88_64, F32, ev=True)),
+    _r('eval_pair', 'bf16', 4, 29, 45, 64, 0, 64, 1, _ck(BF, '128,8,16,2,64,2,2,true', BF, ev=True)),
+    _r('eval_pair', 'bf16', 4, 29, 45, 128, 0, 64, 1, _ck(BF, '128,8,16,2,64,4,1,false', BF, ev=True)),
+    _r('eval_pair', 'bf16', 8, 61, 61, 128, 0, 128, 1, _ck(BF, '128,8,8,2,128,1,4,false', BF, ev=True)),
+    _r('eval_pair', 'bf16', 128, 8, 8, 512, 0, 512, 1, _ck(BF, K88_128, BF, ev=True)),
+    _r('eval_pair', 'bf16', 4, 7, 5, 512, 0, 512, 1, _ck(BF, K88_64, BF, ev=True)),
+    _r('eval_pair', 'fp32', 8, 61, 61, 128, 0, 128, 1, _ck(F32, '128,8,8,2,128,1,4,false', F32, ev=True)),
+    _r('eval_pair', 'fp32', 4, 29, 45, 128, 0, 64, 1, _ck(F32, '128,8,16,2,64,4,1,false', F32, ev=True)),
+    _r('eval_cls', 'bf16', 4, 29, 45, 64, 0, 64, 1, _ck(BF, K1616_ONE, BF, ev=True)),
+    _r('eval_cls', 'fp32', 4, 29, 45, 64, 0, 64, 1, _ck(F32, K1616, F32, ev=True)),
+    # ---- weight gradient at the production plan (default flags: 128 blocks, per_split >> 1 with a ragged last split).  lanes = split lanes
+    # of the fixed-order reduction (launch_wgrad_reduce): 16 for a 64 x 16 filter, 8 for 64 x 64, 4 for 128 x 64, 2 for 128 x 128,
+    # 1 from 256 x 128 on
+    _r('wgrad', 'bf16', 4, 61, 125, 64, 0, 64, 2, 'wgrad7_kernel<true>', bnrelu=True, lanes=8),
+    _r('wgrad', 'bf16', 4, 61, 125, 64, 0, 128, 2, 'wgrad7_kernel<false>', lanes=4),
+    _r('wgrad', 'bf16', 4, 61, 125, 64, 64, 128, 2, 'wgrad7_kernel<false>', lanes=2),
+    _r('wgrad', 'bf16', 4, 29, 45, 128, 128, 256, 2, 'wgrad7_kernel<false>', lanes=1),
+    _r('wgrad', 'bf16', 4, 29, 45, 128, 0, 128, 2, 'wgrad7_kernel<true>', bnrelu=True, lanes=2),
+    _r('wgrad', 'bf16', 8, 8, 8, 512, 0, 512, 4, 'wgrad_kernel<bf16,8,8,2,false>', bnrelu=True, lanes=1),
+    _r('wgrad', 'bf16', 8, 8, 8, 512, 512, 512, 4, 'wgrad_kernel<bf16,8,8,2,false>', lanes=1),
+    _r('wgrad', 'fp32', 4, 61, 125, 16, 0, 64, 2, 'wgrad_kernel<f32,8,16,1,true>', lanes=16),
+    _r('wgrad', 'fp32', 4, 29, 45, 64, 0, 64, 2, 'wgrad_kernel<f32,8,16,1,false>', bnrelu=True, lanes=8),
+    _r('wgrad', 'fp32', 8, 8, 8, 512, 0, 512, 4, 'wgrad_kernel<f32,8,8,2,false>', bnrelu=True, lanes=1),
+    _r('wgrad', 'bf16x3', 4, 61, 125, 64, 0, 128, 2, 'wgrad7x_kernel<3>', lanes=4),
+    _r('wgrad', 'bf16x3', 4, 29, 45, 128, 0, 128, 2, 'wgrad7x_kernel<3>', lanes=2),
+    _r('wgrad', 'bf16x3', 8, 8, 8, 512, 0, 512, 4, 'wgrad_kernel<bf16,8,8,2,false>+wgrad_x3_combine_kernel', lanes=1),
+    _r('wgrad', 'bf16x2', 4, 61, 125, 64, 0, 64, 2, 'wgrad7x_kernel<2>', lanes=8),
+    _r('wgrad', 'bf16x2', 8, 8, 8, 512, 0, 512, 4, 'wgrad_kernel<bf16,8,8,2,false>+wgrad_x3_combine_kernel', lanes=1),
+    # the first layer: 256-block grid, 16 split lanes
+    _r('wgrad_bnbwd', 'bf16', 4, 61, 125, 16, 0, 64, 2, 'wgrad_first_kernel', lanes=16),
+    _r('wgrad_bnbwd', 'bf16x3', 4, 61, 125, 16, 0, 64, 2, 'wgrad_first_x3_kernel<3>', lanes=16),
+    _r('wgrad_bnbwd', 'bf16x2', 4, 61, 125, 16, 0, 64, 2, 'wgrad_first_x3_kernel<2>', lanes=16),
+]
+
+
+def row_id(r):
+    return (f'{r.op}-{r.prec}-{r.N}x{r.H}x{r.W}-{r.C0}' + (f'+{r.C1}' if r.C1 else '') + f'-{r.Cout}-g{r.ipg}'
+            + ('-bnrelu' if r.bnrelu else '') + ('' if r.stats else '-nostats'))
+
+
+# ---- statistics reductions on synthetic partials: (rows per group, G).  bdn_bn_finalize / bdn_bn_bwd_finalize take the one-launch path up
+# to 512 rows per group and the two-stage reduce_rows_kernel + finalize above it (513: ragged last block); 4096 and 8192 are the production
+# counts of level 1 (batch 64 / 128 on 16 x 16 tiles: 4096 rows per date), where the row-split count is capped at 64
+STATS_CASES = [(512, 1), (512, 2), (513, 1), (513, 2), (4096, 1), (4096, 2), (8192, 1), (8192, 2)]
+
+
+# ------------------------------------------------------------------ instantiation of a launch, from the library's dispatchers
+def _s(b):
+    return b.decode()
+
+
+def conv_inst(dtype, N, H, W, C0, C1, Cout, ipg):
+    return _s(_lib.load().bdn_conv3x3_variant(dtype, N, H, W, C0, C1, Cout, ipg))
+
+
+def x3src_inst(dtype, N, H, W, C0, Cout, ipg):
+    return _s(_lib.load().bdn_conv3x3_x3src_variant(dtype, N, H, W, C0, Cout, ipg))
+
+
+def bb_inst(N, H, W, Cout, ipg):
+    return _s(_lib.load().bdn_conv3x3_dgrad_bb_variant(N, H, W, Cout, ipg))
+
+
+def eval_inst(kind, dtype, N, H, W, C0, C1, Cout):
+    return _s(_lib.load().bdn_conv3x3_eval_variant(kind, dtype, N, H, W, C0, C1, Cout))
+
+
+def _reduce_lanes(S, plane):
+    """Split lanes of wgrad_reduce_kernel<SL>: a HAND COPY of the rule in wgrad.hip launch_wgrad_reduce, which has no query entry point.
+    Nothing checks the copy against the C code -- the GPU test maps recorded calls through this same function -- so a change of that rule
+    must be mirrored here, or the lanes the rows claim go stale unnoticed."""
+    sl = 1
+    while sl < 16 and sl * 2 <= S and plane // (256 // (sl * 2)) < 256:
+        sl *= 2
+    return sl
+
+
+def _splits(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags):
+    """Split count S of a weight-gradient plan, read back from its workspace size (S x (2 when Cin <= 32) x 9 Cout Cin floats)."""
+    nb = _lib.load().bdn_wgrad_workspace_bytes_ex(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
+    per = 9 * Cout * (C0 + C1) * 4 * (2 if C0 + C1 <= 32 else 1)
+    assert nb % per == 0, (nb, per)
+    return nb // per
+
+
+def wgrad_inst(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags=wg_flags()):
+    """(GEMM instantiation, split lanes of its reduction) of bdn_conv3x3_wgrad_ex.  The family comes from bdn_conv3x3_wgrad_variant and the
+    split count from the plan's workspace size (both the library's own answers); the tile geometry of the one-chunk-at-a-time kernel and the
+    bf16x3 fused / doubled-operand choice are HAND COPIES of pick_tile (common.hpp) and bdn_conv3x3_wgrad_ex, unchecked against the C code
+    like _reduce_lanes."""
+    lib = _lib.load()
+    small = H <= 8 and W <= 8 and ipg % 2 == 0
+    if dtype in (BDN_BF16X3, BDN_BF16X2):
+        terms = 3 if dtype == BDN_BF16X3 else 2
+        if Cout % 64 == 0 and C0 % 64 == 0 and \
+                lib.bdn_conv3x3_wgrad_variant(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, flags) == WG_ROLE:
+            return f'wgrad7x_kernel<{terms}>', _reduce_lanes(_splits(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, flags), Cout * C0)
+        # the doubled operands through the bf16 GEMM (internal plan flags: the lo x lo quadrant left out), then the quadrant sum
+        xfl = (1 << 30) | ((1 << 29) if terms == 2 else 0)
+        g, lanes = wgrad_inst(BDN_BF16, N, H, W, 2 * Cout, 2 * C0, 0, ipg, IN_PLAIN, flags | xfl)
+        return f'{g}+wgrad_x3_combine_kernel', lanes
+    v = lib.bdn_conv3x3_wgrad_variant(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
+    ks = C0 + C1 <= 32
+    if v == WG_ROLE:
+        g = f'wgrad7_kernel<{"true" if mode == IN_BNRELU else "false"}>'
+    else:
+        g = f'wgrad_kernel<{"bf16" if dtype == BDN_BF16 else "f32"},8,{"8,2" if small else "16,1"},{"true" if ks else "false"}>'
+    S = _splits(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
+    return g, _reduce_lanes(S * (2 if ks else 1), Cout * (C0 + C1))
+
+
+def wgrad_bnbwd_inst(dtype, N, H, W, Cout, C0, ipg):
+    """(instantiation, split lanes) of bdn_conv3x3_wgrad_bnbwd: its own 256-block plan of the bf16 first-layer shape."""
+    S = _splits(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, wg_flags(0, 0, 256))
+    name = 'wgrad_first_kernel' if dtype == BDN_BF16 else f'wgrad_first_x3_kernel<{3 if dtype == BDN_BF16X3 else 2}>'
+    return name, _reduce_lanes(S, Cout * C0)
+
+
+def instantiation(r):
+    """What the row's launch runs, asked from the library (for wgrad rows: the GEMM; `lanes` is checked apart)."""
+    dt = DTYPE[r.prec]
+    if r.op in ('fwd', 'dgrad', 'dgrad_bs', 'x3'):
+        return conv_inst(dt, r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg)
+    if r.op == 'dgrad_bb':
+        return bb_inst(r.N, r.H, r.W, r.Cout, r.ipg)
+    if r.op == 'x3src':
+        return x3src_inst(dt, r.N, r.H, r.W, r.C0, r.Cout, r.ipg)
+    if r.op in ('eval', 'eval_pair', 'eval_cls'):
+        kind = {'eval': EVAL_STAGE, 'eval_pair': EVAL_PAIR, 'eval_cls': EVAL_CLS}[r.op]
+        return eval_inst(kind, dt, r.N, r.H, r.W, r.C0, r.C1, r.Cout)
+    if r.op == 'wgrad':
+        return wgrad_inst(dt, r.N, r.H, r.W, r.Cout, r.C0, r.C1, r.ipg, IN_BNRELU if r.bnrelu else IN_PLAIN)[0]
+    if r.op == 'wgrad_bnbwd':
+        return wgrad_bnbwd_inst(dt, r.N, r.H, r.W, r.Cout, r.C0, r.ipg)[0]
+    raise ValueError(r.op)
+
+
+def reduce_lanes(r):
+    dt = DTYPE[r.prec]
+    if r.op == 'wgrad':
+        return wgrad_inst(dt, r.N, r.H, r.W, r.Cout, r.C0, r.C1, r.ipg, IN_BNRELU if r.bnrelu else IN_PLAIN)[1]
+    return wgrad_bnbwd_inst(dt, r.N, r.H, r.W, r.Cout, r.C0, r.ipg)[1]
+
+
+def covered():
+    """Every instantiation some row selects, with the wgrad rows' reductions."""
+    out = {i for r in ROWS for i in r.inst.split('+')}
+    out |= {f'wgrad_reduce_kernel<{r.lanes}>' for r in ROWS if r.lanes}
+    return out
+
+
+# ------------------------------------------------------------------ what BiDateNet launches (mirrors fabric_amd/engine.py)
+def _layers(n_channels):
+    from fabric_amd.engine import build_layers
+    return {L.name: L for L in build_layers(n_channels)}
+
+
+def call_instantiations(name, args):
+    """Instantiations run by one recorded library call (name, args as passed to _lib.call); empty for entry points without MFMA GEMMs."""
+    a = args
+    if name == 'bdn_conv3x3':
+        return [conv_inst(a[0], a[12], a[13], a[14], a[2], a[4], a[15], a[7])]
+    if name == 'bdn_conv3x3_dgrad_bs':
+        return [conv_inst(a[0], a[9], a[10], a[11], a[2], 0, a[12], a[7])]
+    if name == 'bdn_conv3x3_dgrad_bb':
+        return [bb_inst(a[13], a[14], a[15], a[16], a[6])]
+    if name == 'bdn_conv3x3_x3src':
+        return [x3src_inst(a[0], a[11], a[12], a[13], a[2], a[14], a[5])]
+    if name == 'bdn_conv3x3_eval':
+        return [eval_inst(EVAL_STAGE, a[0], a[11], a[12], a[13], a[2], a[4] if a[3] else 0, a[14])]
+    if name == 'bdn_conv3x3_eval_pair':
+        return [eval_inst(EVAL_PAIR, a[0], a[8], a[9], a[10], a[2], 0, a[11])]
+    if name == 'bdn_conv3x3_eval_cls':
+        return [eval_inst(EVAL_CLS, a[0], a[15], a[16], a[17], a[2], 0, a[18])]
+    if name == 'bdn_conv3x3_wgrad_ex':
+        g, sl = wgrad_inst(a[0], a[13], a[14], a[15], a[2], a[4], a[6] if a[5] else 0, a[9], a[7], a[16])
+        return g.split('+') + [f'wgrad_reduce_kernel<{sl}>']
+    if name == 'bdn_conv3x3_wgrad_bnbwd':
+        g, sl = wgrad_bnbwd_inst(a[0], a[13], a[14], a[15], a[7], a[9], a[6])
+        return [g, f'wgrad_reduce_kernel<{sl}>']
+    return []
+
+
+MFMA_ENTRY_POINTS = ('bdn_conv3x3', 'bdn_conv3x3_dgrad_bs', 'bdn_conv3x3_dgrad_bb', 'bdn_conv3x3_x3src', 'bdn_conv3x3_eval',
+                     'bdn_conv3x3_eval_pair', 'bdn_conv3x3_eval_cls', 'bdn_conv3x3_wgrad_ex', 'bdn_conv3x3_wgrad_bnbwd')
+
+
+def train_step_instantiations(precision, B=64, S=128, n_channels=13):
+    """The instantiations of one training step (forward + backward) of BiDateNet(n_channels, 2) at batch B on S x S patches with the
+    engine's default settings, layer by layer as fabric_amd/engine.py launches them."""
+    from fabric_amd.engine import BiDateEngine, ENC_CH
+    eng = BiDateEngine(n_channels, 2, precision)
+    by = _layers(n_channels)
+    dims = [(S >> k, S >> k) for k in range(5)]
+    x3 = eng.x3
+    mdt, dt = eng.mdt, eng.dt
+    out = set()
+    add = out.update
+
+    def fwd(L, n, split_src):
+        h, w = dims[L.level - 1]
+        if x3 and not split_src:              # one float32 source of >= 64 channels: bdn_conv3x3_x3src
+            add([x3src_inst(mdt, n, h, w, L.cin, L.cout, B)])
+        elif x3:
+            add([conv_inst(mdt, n, h, w, L.cin, 0, L.cout, B)])
+        elif L.name.startswith('d') and L.name.endswith('a'):
+            ck = ENC_CH[L.level - 1]
+            add([conv_inst(dt, n, h, w, ck, L.cin - ck, L.cout, B)])
+        else:
+            add([conv_inst(dt, n, h, w, L.cin, 0, L.cout, B)])
+
+    for k in range(1, 6):
+        fwd(by[f'e{k}a'], 2 * B, True)
+        fwd(by[f'e{k}b'], 2 * B, False)
+    for j in range(1, 5):
+        fwd(by[f'd{j}a'], B, True)
+        fwd(by[f'd{j}b'], B, False)
+
+    ddt = BDN_BF16X2 if (x3 and eng.x3_bwd_terms == 2) else mdt
+    fold = set(eng.fold_bn_bwd) if mdt == BDN_BF16 else set()
+
+    def wgrad(L, n, c0, c1, mode):
+        h, w = dims[L.level - 1]
+        if x3:
+            blk = eng.x3_tail_wgrad_blocks if (L.name == 'e1b' and eng.x3_tail_wgrad_blocks and eng.x3_bwd_terms == 3) else eng.wgrad_blocks
+            xdt = BDN_BF16X2 if eng.x3_bwd_terms == 2 else BDN_BF16X3
+            g, sl = wgrad_inst(xdt, n, h, w, L.cout, c0 + c1, 0, B, IN_PLAIN, wg_flags(3, 0, blk))
+        else:
+            g, sl = wgrad_inst(dt, n, h, w, L.cout, c0, c1, B, mode, wg_flags(3, eng.wgrad_kernel, eng.wgrad_blocks))
+        add(g.split('+') + [f'wgrad_reduce_kernel<{sl}>'])
+
+    def dgrad(L, n):                          # plain and with fused statistics: the same dispatcher
+        h, w = dims[L.level - 1]
+        add([conv_inst(ddt, n, h, w, L.cout, 0, L.cin, B)])
+
+    def folded(L, n):
+        h, w = dims[L.level - 1]
+        return L.name in fold and L.cout == 64 and min(h, w) > 8
+
+    for j in range(4, 0, -1):
+        k = 5 - j
+        La, Lb = by[f'd{j}a'], by[f'd{j}b']
+        ck = ENC_CH[k - 1]
+        h, w = dims[k - 1]
+        wgrad(Lb, B, Lb.cin, 0, IN_BNRELU)
+        if folded(Lb, B):
+            add([bb_inst(B, h, w, Lb.cin, B)])
+        else:
+            dgrad(Lb, B)
+        if folded(La, B):
+            add([bb_inst(B, h, w, La.cin, B)])
+        else:
+            dgrad(La, B)
+        wgrad(La, B, ck, La.cin - ck, IN_PLAIN)
+    for k in range(5, 0, -1):
+        La, Lb = by[f'e{k}a'], by[f'e{k}b']
+        h, w = dims[k - 1]
+        if folded(Lb, 2 * B):
+            add([bb_inst(2 * B, h, w, Lb.cin, B)])
+        else:
+            dgrad(Lb, 2 * B)
+        wgrad(Lb, 2 * B, Lb.cin, 0, IN_BNRELU)
+        if k == 1 and eng.first_wgrad_fused and _lib.load().bdn_conv3x3_wgrad_bnbwd_supported(mdt, 2 * B, h, w, La.cout, La.cin, B):
+            fdt = (BDN_BF16X2 if eng.x3_bwd_terms == 2 else BDN_BF16X3) if x3 else dt
+            g, sl = wgrad_bnbwd_inst(fdt, 2 * B, h, w, La.cout, La.cin, B)
+            add([g, f'wgrad_reduce_kernel<{sl}>'])
+            continue
+        if folded(La, 2 * B) and k > 1:
+            add([bb_inst(2 * B, h, w, La.cin, B)])
+        elif k > 1:
+            dgrad(La, 2 * B)
+        wgrad(La, 2 * B, La.cin, 0, IN_PLAIN)
+    return out
+
+
+def eval_forward_instantiations(precision, B, S=128, n_channels=13):
+    """The instantiations of one eval-mode forward (the eval-shaped schedule of bf16 / fp32, fabric_amd/engine.py _forward_eval)."""
+    from fabric_amd.engine import BiDateEngine, ENC_CH
+    eng = BiDateEngine(n_channels, 2, precision)
+    assert eng._use_eval_schedule()
+    by = _layers(n_channels)
+    dt = eng.dt
+    out = set()
+    for k in range(1, 6):
+        h = w = S >> (k - 1)
+        La, Lb = by[f'e{k}a'], by[f'e{k}b']
+        out.add(eval_inst(EVAL_STAGE, dt, 2 * B, h, w, La.cin, 0, La.cout))
+        if k in eng.eval_pair:
+            out.add(eval_inst(EVAL_PAIR, dt, B, h, w, Lb.cin, 0, Lb.cout))
+        else:
+            out.add(eval_inst(EVAL_STAGE, dt, B, h, w, Lb.cin, 0, Lb.cout))
+    cprev = ENC_CH[4]
+    for j in range(1, 5):
+        k = 5 - j
+        h = w = S >> (k - 1)
+        La, Lb = by[f'd{j}a'], by[f'd{j}b']
+        out.add(eval_inst(EVAL_STAGE, dt, B, h, w, ENC_CH[k - 1], cprev, La.cout))
+        out.add(eval_inst(EVAL_CLS if j == 4 else EVAL_STAGE, dt, B, h, w, Lb.cin, 0, Lb.cout))
+        cprev = Lb.cout
+    return out

@@ -60,7 +60,7 @@ EVAL_CASES = [
     (4, 8, 8, 128, 128, 0, 128, True, False),     # 8x8 maps: two images per tile (level 5: product only)
     (3, 8, 8, 128, 128, 0, 128, True, True),      # odd image count: one image per tile on an 8x8 map
     (1, 11, 45, 64, 64, 0, 192, True, True),      # odd sizes: floor pooling drops the last row / column, Cout not a multiple of 128
-    (2, 22, 45, 128, 128, 0, 256, True, True),    # ragged 8x16 tiles, BN = 128 column tiles
+    (2, 22, 45, 128, 128, 0, 256, True, True),    # ragged 8x16 tiles (18 tiles x 2 column tiles: BN = 64; tests/launch_cases.py has BN = 128)
     (8, 64, 64, 64, 64, 0, 64, True, True),       # 128 tiles
     (2, 6, 6, 256, 256, 0, 64, False, True),      # tiny map
 ]

@@ -34,7 +34,7 @@ CONV_CASES = [
     (2, 5, 5, 64, 64, 0, 64, False, 2),        # odd tiny map (90-pixel patches end at 5x5)
     (1, 11, 45, 64, 64, 0, 192, True, 1),      # odd sizes, Cout not a multiple of 128
     (3, 17, 16, 128, 128, 128, 256, False, 3), # three images, two sources
-    (8, 64, 64, 64, 64, 0, 64, True, 4),       # 256 tiles: two-stage statistics reduction
+    (8, 64, 64, 64, 64, 0, 64, True, 4),       # 128 16x16 tiles, 64 rows per group (the one-launch reduction; the two-stage one: tests/test_gpu_launch_shapes.py)
 ]
 
 
