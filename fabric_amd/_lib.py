@@ -19,7 +19,7 @@ def wg_flags(phases=3, kernel=0, blocks=0):
     """BDN_WG_FLAGS of include/bidate_hip.h."""
     return phases | (kernel << 8) | (blocks << 16)
 
-_vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 
 # name -> (restype, argtypes); mirrors include/bidate_hip.h one to one
 SIGNATURES = {
@@ -96,6 +96,8 @@ SIGNATURES = {
     'bdn_argmax': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_argmax_stitch': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'bdn_sgd_step': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
+    'bdn_sgd_momentum_step': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _sz, _vp]),
+    'bdn_adam_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, C.c_double, C.c_double, _f, _f, _i, _i64, _sz, _vp]),
 }
 
 _lib = None

@@ -915,6 +915,158 @@ extern "C" int bdn_sgd_step(float* params, const float* grads, float lr, float g
     return BDN_OK;
 }
 
+// ============================================================ momentum SGD / Adam / AdamW (train.py:55-56,95)
+// torch.optim's single-tensor update rules over the flat f32 buffers, one element per lane and OPT_VEC float4s in flight per
+// thread (every load of a pass is issued before the first store).  Memory-bound: the grid is capped at 8 blocks per CU of the
+// 256 and grid-strides the rest.  No LDS, no atomics: every element's result depends only on its own inputs (bit-reproducible).
+// IEEE division and sqrt (hipcc's default correctly rounded f32 divide / sqrt).
+constexpr int OPT_VEC = 4;
+
+static inline unsigned opt_grid(size_t n4) {
+    const size_t b = (n4 + 256 * OPT_VEC - 1) / (256 * OPT_VEC);
+    return (unsigned)(b == 0 ? 1 : (b < 2048 ? b : 2048));
+}
+
+struct SgdmParams { float lr, grad_scale, momentum, damp1 /* 1 - dampening */, weight_decay; int first, nesterov; };
+
+// SGD (torch 2.10 _single_tensor_sgd): g = s*grad (+ wd*p); buf = g on the first step, momentum*buf + (1-dampening)*g after it;
+// g = g + momentum*buf (nesterov) or buf; p -= lr*g.  MOM = false: no momentum buffer is read or written.
+template <bool MOM>
+__device__ __forceinline__ void sgdm_elem(float& p, float gr, float& buf, const SgdmParams& a) {
+    float g = a.grad_scale * gr;
+    if (a.weight_decay != 0.f) g = g + a.weight_decay * p;
+    if (MOM) {
+        buf = a.first ? g : a.momentum * buf + a.damp1 * g;
+        g = a.nesterov ? g + a.momentum * buf : buf;
+    }
+    p = p - a.lr * g;
+}
+
+template <bool MOM>
+__global__ void __launch_bounds__(256) sgdm_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                   SgdmParams a, size_t n4, size_t n) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t base = (size_t)blockIdx.x * 256 + threadIdx.x; base < n4; base += stride * OPT_VEC) {
+        float4 P[OPT_VEC], G[OPT_VEC], M[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                P[u] = reinterpret_cast<const float4*>(p)[i]; G[u] = reinterpret_cast<const float4*>(g)[i];
+                if (MOM && !a.first) M[u] = reinterpret_cast<const float4*>(buf)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                sgdm_elem<MOM>(P[u].x, G[u].x, M[u].x, a); sgdm_elem<MOM>(P[u].y, G[u].y, M[u].y, a);
+                sgdm_elem<MOM>(P[u].z, G[u].z, M[u].z, a); sgdm_elem<MOM>(P[u].w, G[u].w, M[u].w, a);
+                reinterpret_cast<float4*>(p)[i] = P[u];
+                if (MOM) reinterpret_cast<float4*>(buf)[i] = M[u];
+            }
+        }
+    }
+    // the n % 4 trailing elements (never for a FlatLayout buffer: every tensor is padded to 4 floats)
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        const size_t k = n4 * 4 + threadIdx.x;
+        float m = (MOM && !a.first) ? buf[k] : 0.f, q = p[k];
+        sgdm_elem<MOM>(q, g[k], m, a);
+        p[k] = q;
+        if (MOM) buf[k] = m;
+    }
+}
+
+extern "C" int bdn_sgd_momentum_step(float* params, const float* grads, float* momentum_buf, float lr, float grad_scale, float momentum,
+                                     float dampening, float weight_decay, int nesterov, int first_step, size_t n, void* stream) {
+    if (!params || !grads) BDN_FAIL(BDN_E_ARG, "sgd_momentum_step: null pointer");
+    if ((momentum != 0.f) != (momentum_buf != nullptr))
+        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step: momentum_buf must be given iff momentum != 0");
+    if (nesterov && (momentum <= 0.f || dampening != 0.f))
+        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step: nesterov needs momentum > 0 and zero dampening");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15)
+        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step: buffers must be 16-byte aligned");
+    if (n == 0) return BDN_OK;
+    const size_t n4 = n / 4;
+    const SgdmParams a{lr, grad_scale, momentum, (float)(1.0 - (double)dampening), weight_decay, first_step ? 1 : 0, nesterov ? 1 : 0};
+    if (momentum_buf)
+        hipLaunchKernelGGL(sgdm_kernel<true>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, params, grads, momentum_buf, a, n4, n);
+    else
+        hipLaunchKernelGGL(sgdm_kernel<false>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, params, grads, momentum_buf, a, n4, n);
+    BDN_CHECK_LAUNCH("sgd_momentum_step");
+    return BDN_OK;
+}
+
+struct AdamParams { float grad_scale, w1 /* lerp weight 1 - beta1 */, beta2, c2 /* 1 - beta2 */, eps, l2 /* Adam's coupled weight
+                    decay */, decay /* AdamW: 1 - lr*wd */, step_size /* lr / bc1 */, bc2_sqrt; int lerp_hi; };
+
+// Adam / AdamW (torch 2.10 _single_tensor_adam): g = s*grad; AdamW p *= 1 - lr*wd, Adam g += wd*p; m = lerp(m, g, 1-beta1);
+// v = beta2*v + (1-beta2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps).  lerp as torch evaluates it: weight < 0.5 ? m + w*(g-m)
+// : g - (g-m)*(1-w).
+__device__ __forceinline__ void adam_elem(float& p, float gr, float& m, float& v, const AdamParams& a) {
+    float g = a.grad_scale * gr;
+    p = p * a.decay;
+    if (a.l2 != 0.f) g = g + a.l2 * p;
+    m = a.lerp_hi ? g - (g - m) * (1.f - a.w1) : m + a.w1 * (g - m);
+    v = a.beta2 * v + a.c2 * g * g;
+    const float den = sqrtf(v) / a.bc2_sqrt + a.eps;
+    p = p - a.step_size * (m / den);
+}
+
+__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, AdamParams a, size_t n4, size_t n) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t base = (size_t)blockIdx.x * 256 + threadIdx.x; base < n4; base += stride * OPT_VEC) {
+        float4 P[OPT_VEC], G[OPT_VEC], M[OPT_VEC], V[OPT_VEC];
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                P[u] = reinterpret_cast<const float4*>(p)[i]; G[u] = reinterpret_cast<const float4*>(g)[i];
+                M[u] = reinterpret_cast<const float4*>(m)[i]; V[u] = reinterpret_cast<const float4*>(v)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                adam_elem(P[u].x, G[u].x, M[u].x, V[u].x, a); adam_elem(P[u].y, G[u].y, M[u].y, V[u].y, a);
+                adam_elem(P[u].z, G[u].z, M[u].z, V[u].z, a); adam_elem(P[u].w, G[u].w, M[u].w, V[u].w, a);
+                reinterpret_cast<float4*>(p)[i] = P[u]; reinterpret_cast<float4*>(m)[i] = M[u]; reinterpret_cast<float4*>(v)[i] = V[u];
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        const size_t k = n4 * 4 + threadIdx.x;
+        float q = p[k], mk = m[k], vk = v[k];
+        adam_elem(q, g[k], mk, vk, a);
+        p[k] = q; m[k] = mk; v[k] = vk;
+    }
+}
+
+extern "C" int bdn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float lr, float grad_scale,
+                             double beta1, double beta2, float eps, float weight_decay, int decoupled_weight_decay, long long step,
+                             size_t n, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq) BDN_FAIL(BDN_E_ARG, "adam_step: null pointer");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15)
+        BDN_FAIL(BDN_E_ARG, "adam_step: buffers must be 16-byte aligned");
+    if (step < 1) BDN_FAIL(BDN_E_ARG, "adam_step: step must be >= 1 (1-based, counted after the increment), got %lld", step);
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0))
+        BDN_FAIL(BDN_E_ARG, "adam_step: betas must lie in [0, 1)");
+    if (n == 0) return BDN_OK;
+    // 1 - beta and the bias corrections in double on the host, as torch computes them from Python floats: no device sync
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    const float w1 = (float)(1.0 - beta1);
+    const bool dec = decoupled_weight_decay != 0;
+    const AdamParams a{grad_scale, w1, (float)beta2, (float)(1.0 - beta2), eps, dec ? 0.f : weight_decay,
+                       dec ? (float)(1.0 - (double)lr * (double)weight_decay) : 1.f, (float)((double)lr / bc1), (float)std::sqrt(bc2),
+                       w1 >= 0.5f ? 1 : 0};
+    const size_t n4 = n / 4;
+    hipLaunchKernelGGL(adam_kernel, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, a, n4, n);
+    BDN_CHECK_LAUNCH("adam_step");
+    return BDN_OK;
+}
+
 // ============================================================ misc
 static thread_local char g_err[512] = "";
 void bdn_set_error(const char* fmt, ...) {

@@ -5,6 +5,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
 
     python -m fabric_amd.train --synthetic --epochs 1                                   # needs an MI355X
     python -m fabric_amd.train --metadata metadata.json --dataset_dir ./onera/          # an OSCD directory tree
+    python -m fabric_amd.train --synthetic --epochs 4 --optimizer adamw --resume ./log/checkpoint_epoch_1.state_dict.pt
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
 predicted tile by tile (utils/inference.py) -- here on the device-resident city stacks -- and written as PNG masks.
@@ -12,6 +13,7 @@ predicted tile by tile (utils/inference.py) -- here on the device-resident city 
 import argparse
 import json
 import os
+import re
 
 import torch
 import torch.utils.data
@@ -103,7 +105,8 @@ def validate(model, loader, dev, patch_size, criterion, feeder=None):
 
 def train_epoch_autograd(model, criterion, optimizer, loader, dev, patch_size, world=1, feeder=None):
     """The reference loop itself (train.py:83-101) for the criteria the fused step does not cover (dice / jaccard / focal):
-    autograd through the one-node BiDateNet function, torch.optim.SGD, gradients averaged over the ranks after backward."""
+    autograd through the one-node BiDateNet function, a torch.optim optimizer (make_torch_optimizer), gradients averaged over the
+    ranks after backward."""
     from .parallel import allreduce_mean_grads
     from .utils.metrics import batch_prf_from_counts, confusion_counts
     model.train()
@@ -123,10 +126,46 @@ def train_epoch_autograd(model, criterion, optimizer, loader, dev, patch_size, w
     return get_mean_metrics(metrics)
 
 
-def save_if_better(model, mean_val_metrics, best_metrics, metadata, epoch, out_dir):
+def optimizer_kwargs(opt):
+    """The update rule of the --optimizer / --momentum / --nesterov / --weight_decay / --betas / --adam_eps flags as TrainStep keywords."""
+    return dict(optimizer=opt.optimizer, momentum=opt.momentum, nesterov=opt.nesterov, weight_decay=opt.weight_decay,
+                betas=tuple(opt.betas), adam_eps=opt.adam_eps)
+
+
+def make_torch_optimizer(params, lr, optimizer='sgd', momentum=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8):
+    """The torch.optim optimizer of the autograd route for the same flags (validated by fabric_amd.optim.OptimConfig like the fused
+    step's).  The defaults give train.py:55's optim.SGD(lr)."""
+    from .optim import OptimConfig
+    c = OptimConfig(optimizer, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=weight_decay, betas=betas, eps=adam_eps)
+    if c.kind == 'sgd':
+        return torch.optim.SGD(params, lr=c.lr, momentum=c.momentum, nesterov=c.nesterov, weight_decay=c.weight_decay)
+    cls = torch.optim.AdamW if c.kind == 'adamw' else torch.optim.Adam
+    return cls(params, lr=c.lr, betas=c.betas, eps=c.eps, weight_decay=c.weight_decay)
+
+
+_CKPT = re.compile(r'checkpoint_epoch_(\d+)\.state_dict\.pt$')
+
+
+def resume_from(path, device=None, precision=None):
+    """--resume DIR/checkpoint_epoch_N.state_dict.pt: (model, optimizer state or None, first epoch N + 1).  The weights and BatchNorm
+    buffers come through load_checkpoint; the optimizer state is the sibling optimizer_epoch_N.pt save_if_better wrote, in
+    torch.optim's state_dict() format (absent for a stateless optimizer)."""
+    from .utils.helpers import load_checkpoint
+    m = _CKPT.search(os.path.basename(path))
+    if not m:
+        raise SystemExit(f'--resume {path}: expected a checkpoint_epoch_N.state_dict.pt written by this program')
+    epoch = int(m.group(1))
+    model = load_checkpoint(path, device=device, precision=precision, allow_pickle=False)
+    opt_path = os.path.join(os.path.dirname(path), f'optimizer_epoch_{epoch}.pt')
+    opt_sd = torch.load(opt_path, map_location='cpu', weights_only=True) if os.path.exists(opt_path) else None
+    return model, opt_sd, epoch + 1
+
+
+def save_if_better(model, mean_val_metrics, best_metrics, metadata, epoch, out_dir, optimizer_state=None):
     """train.py:207-227: when validation precision, recall OR F1 improved, write `checkpoint_epoch_N.pt` (the pickled
     module, as the reference does with torch.save(model, ...)) and `metadata_epoch_N.json` (the run's metadata plus
-    `validation_metrics`).  The upload to the outputs store / comet is out of scope.  Returns the new best metrics."""
+    `validation_metrics`), and, when `optimizer_state` (torch.optim's state_dict() format) holds any state, `optimizer_epoch_N.pt`.
+    The upload to the outputs store / comet is out of scope.  Returns the new best metrics."""
     keys = ('cd_precisions', 'cd_recalls', 'cd_f1scores')
     if not any(mean_val_metrics[k] > best_metrics[k] for k in keys):
         return best_metrics
@@ -141,7 +180,17 @@ def save_if_better(model, mean_val_metrics, best_metrics, metadata, epoch, out_d
     # with model.load_state_dict(torch.load(path)) and here with fabric_amd.utils.helpers.load_checkpoint
     torch.save({'module.' + k: v.detach().cpu() for k, v in model.state_dict().items()},
                os.path.join(out_dir, f'checkpoint_epoch_{epoch}.state_dict.pt'))
+    if optimizer_state is not None and optimizer_state['state']:
+        torch.save(_to_cpu(optimizer_state), os.path.join(out_dir, f'optimizer_epoch_{epoch}.pt'))
     return mean_val_metrics
+
+
+def _to_cpu(obj):
+    if torch.is_tensor(obj):
+        return obj.detach().cpu()
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    return obj
 
 
 def main(argv=None):
@@ -157,6 +206,15 @@ def main(argv=None):
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'bf16x3', 'bf16x3-fast', 'fp32'])
     ap.add_argument('--seed', type=int, default=0, help='seeds the shard permutation, the augmentation draws and the initial weights identically on every rank')
     ap.add_argument('--focal_gamma', type=float, default=None, help='required by --loss_function focal (utils/helpers.py:291)')
+    ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam', 'adamw'],
+                    help='sgd is train.py:55 (optim.SGD); adam / adamw the torch.optim rules (train.py:56 is a commented-out Adam)')
+    ap.add_argument('--momentum', type=float, default=0.0, help='sgd only')
+    ap.add_argument('--nesterov', action='store_true', help='sgd only, needs --momentum')
+    ap.add_argument('--weight_decay', type=float, default=None, help="default: torch's (0 for sgd and adam, 1e-2 for adamw)")
+    ap.add_argument('--betas', type=float, nargs=2, default=[0.9, 0.999], help='adam / adamw')
+    ap.add_argument('--adam_eps', type=float, default=1e-8, help='adam / adamw')
+    ap.add_argument('--resume', default=None, help='DIR/checkpoint_epoch_N.state_dict.pt (and its sibling optimizer_epoch_N.pt): '
+                                                   'continue at epoch N + 1 of --epochs')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
                                                      "band_stds, ...): its entries become defaults like utils/parser.py:7-10")
     pre, _ = ap.parse_known_args(argv)
@@ -173,6 +231,12 @@ def main(argv=None):
                          f"(utils/helpers.py:288-314); its bce branch cannot run on BiDateNet's logits and is not built")
     if opt.loss_function == 'focal' and opt.focal_gamma is None:
         raise SystemExit('--loss_function focal needs --focal_gamma')
+    from .optim import OptimConfig
+    try:
+        OptimConfig(opt.optimizer, lr=opt.learning_rate, momentum=opt.momentum, nesterov=opt.nesterov, weight_decay=opt.weight_decay,
+                    betas=opt.betas, eps=opt.adam_eps)
+    except ValueError as e:
+        raise SystemExit(f'--optimizer {opt.optimizer}: {e}')
 
     # one process per GPU (launched by torch.distributed.run): RANK / LOCAL_RANK / WORLD_SIZE from the environment
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -203,26 +267,34 @@ def main(argv=None):
                                             rank=rank, world_size=world, seed=opt.seed)
     random.seed(opt.seed * 7919 + rank)                    # different augmentation draws per rank from here on
     model = BiDateNet(len(opt.band_ids) if opt.band_ids else 13, 2, precision=opt.precision).to(dev)
+    opt_sd, first_epoch = None, 0
+    if opt.resume:
+        model, opt_sd, first_epoch = resume_from(opt.resume, dev, opt.precision)
     fused = opt.loss_function == 'tversky'
     from .input_pipeline import DeviceFeeder
     from .utils.helpers import get_criterion
     feeder = DeviceFeeder(dev)                             # ONE feeder (copy stream, staging threads, device slots) for the whole run
     criterion = get_criterion(opt)                         # validation reports the criterion the run optimises (train.py:137)
     if fused:
-        step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta)
+        step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta,
+                         **optimizer_kwargs(opt))
+        if opt_sd is not None:
+            step.load_optimizer_state_dict(opt_sd)
         if world > 1:
             # measure (and, if it is the slow one, repair) the placement of RCCL's collective stream BEFORE the loop adopts the chain's stream
             rep = step.guard_collectives(opt.batch_size, opt.patch_size, opt.patch_size)
             if rank == 0:
                 print(json.dumps({'collectives_guard': rep}), flush=True)
     else:
-        optimizer = torch.optim.SGD(model.parameters(), lr=opt.learning_rate)      # train.py:55
+        optimizer = make_torch_optimizer(model.parameters(), opt.learning_rate, **optimizer_kwargs(opt))      # train.py:55
+        if opt_sd is not None:
+            optimizer.load_state_dict(opt_sd)
         if world > 1:
             for p in model.parameters():
                 dist.broadcast(p.data, src=0)
     best = {'cd_f1scores': -1, 'cd_recalls': -1, 'cd_precisions': -1}              # train.py:62
     run_meta = dict(meta, **{k: getattr(opt, k) for k in DEFAULTS}, precision=opt.precision, world_size=world)
-    for epoch in range(opt.epochs):
+    for epoch in range(first_epoch, opt.epochs):
         train_loader.sampler.set_epoch(epoch)
         if fused:
             tr = train_epoch(step, train_loader, dev, opt.patch_size, feeder)
@@ -242,7 +314,8 @@ def main(argv=None):
                 mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
                 ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}.png'), (mask * 255).cpu().numpy())
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
-            best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir)
+            best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
+                                  step.optimizer_state_dict() if fused else optimizer.state_dict())
     feeder.close()
     if world > 1:
         dist.destroy_process_group()

@@ -1,7 +1,7 @@
 """The train.py step (reference train.py:83-101 + optim.SGD, train.py:55) as one fused schedule:
 
     to-device tensors -> forward -> Tversky loss (+ argmax TP/FP/FN counts) -> backward
-    -> bucketed gradient all-reduce overlapped with backward -> SGD
+    -> bucketed gradient all-reduce overlapped with backward -> SGD (or momentum SGD / Adam / AdamW: fabric_amd/optim.py)
 
 with no host synchronisation inside the step (the reference syncs every step for sklearn
 P/R/F1 and a comet upload, train.py:103-115; here the counts stay on the device).
@@ -14,17 +14,26 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from . import optim as _optim
 from .engine import param_order
 from .parallel import FlatLayout, GradBucketer
 
 
 class TrainStep:
     def __init__(self, model, lr=1e-3, tversky_alpha=0.1, tversky_beta=0.9, eps=1e-7,
-                 process_group=None, n_buckets=4, distributed=True, force_collectives=False, guard=True):
-        """guard: when the step issues collectives (world > 1, or force_collectives) and guard_collectives() has not been called, the
+                 process_group=None, n_buckets=4, distributed=True, force_collectives=False, guard=True,
+                 optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8):
+        """optimizer: 'sgd' (torch.optim.SGD: momentum, dampening, nesterov, weight_decay), 'adam' or 'adamw' (torch.optim.Adam / AdamW:
+        betas, adam_eps, weight_decay); weight_decay=None is torch's default (0 for sgd and adam, 1e-2 for adamw).  The default, plain
+        SGD, is the reference's optim.SGD(lr) (train.py:55) and keeps no state; the other rules keep theirs in flat f32 buffers in the
+        gradient layout (`opt_state`), with `opt_step` the number of updates applied.  `lr` may be reassigned between steps.
+
+        guard: when the step issues collectives (world > 1, or force_collectives) and guard_collectives() has not been called, the
         first step() runs it in its measure-only form (replace_streams=False: it may defer the buckets, it never swaps a stream the
         caller may already have adopted) and reports / warns about a stream arrangement in which they slow the step down."""
         self.model, self.lr = model, lr
+        self.optim = _optim.OptimConfig(optimizer, lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
+                                        weight_decay=weight_decay, betas=betas, eps=adam_eps)
         self._guard = guard
         self.collectives_report = None
         self.alpha, self.beta, self.eps = tversky_alpha, tversky_beta, eps
@@ -47,6 +56,9 @@ class TrainStep:
             p.data = v
             p.grad = self.layout.view(self.flat_grads, k)
         self.grads = {k: self.layout.view(self.flat_grads, k) for k, _ in named}
+        self._names = [k for k, _ in named]                  # model.parameters() order: torch.optim's state indices
+        self.opt_state = {key: torch.zeros_like(self.flat_params) for key in self.optim.state_keys()}
+        self.opt_step = 0
         bias_tail = [k for k in order if k.endswith('.bias') and k.split('.')[-2] in ('0', '3')]
         self.bucketer = GradBucketer(self.layout, self.flat_grads, n_buckets, process_group, keys_no_reduce=bias_tail,
                                      enabled=self.world > 1 or force_collectives, force=force_collectives)
@@ -148,7 +160,8 @@ class TrainStep:
         the collective stream on the chain's hardware queue it measured as slow as overlapping.)  Afterwards the arrangement that
         measured BEST is the one restored -- streams.restore() puts a displaced stream back -- and the report's `overhead_frac` is
         the number measured on exactly that arrangement.  With several ranks every decision is taken on the MAX
-        over ranks, so all ranks walk the same path.  Parameters, BatchNorm buffers and the bucketer state are restored.
+        over ranks, so all ranks walk the same path.  Parameters, BatchNorm buffers, the optimizer state (and its step count) and the
+        bucketer state are restored.
 
         replace_streams=False (what the automatic call inside the first step() uses): the stream remedies are skipped -- a caller that
         already runs its loop on step.stream() must not have that stream swapped under it -- and only deferring is available.
@@ -166,7 +179,7 @@ class TrainStep:
         self.collectives_report = {'running': True}                     # re-entrancy: _step below must not call the guard again
         ok = False
         eng = self.model.engine()
-        saved = saved_flat = None
+        saved = saved_flat = saved_opt = None
         tried = []
         from . import streams as _streams
         orig_streams = (_streams.get('chain', dev), _streams.get('wgrad', dev))     # put back if a measurement raises half-way
@@ -178,6 +191,7 @@ class TrainStep:
             lbl = (torch.rand(B, H, W, generator=g) < 0.1).to(torch.uint8).to(dev)
             saved = {k: v.clone() for k, v in self._P.items()}
             saved_flat = self.flat_params.clone()
+            saved_opt = ({k: v.clone() for k, v in self.opt_state.items()}, self.opt_step)
 
             def timed(collectives, defer=False):
                 self.bucketer.enabled, self.bucketer.defer = collectives, defer
@@ -254,6 +268,10 @@ class TrainStep:
                 for k, v in saved.items():
                     self._P[k].copy_(v)
                 self.flat_params.copy_(saved_flat)
+            if saved_opt is not None:
+                for k, v in saved_opt[0].items():
+                    self.opt_state[k].copy_(v)
+                self.opt_step = saved_opt[1]
             eng.invalidate_weights()
             torch.cuda.synchronize(dev)
             if not ok:
@@ -282,10 +300,50 @@ class TrainStep:
                   float(self.eps), tvws.data_ptr(), loss.data_ptr(), counts.data_ptr(), dlogits.data_ptr(), B, C, H, W, st)
         eng.backward(ws, dlogits, P, self.grads, on_ready=self.bucketer.on_ready, zero_bias_grads=False)
         self.bucketer.finish()
-        # p -= lr * (sum of rank gradients) / world : per-rank loss, averaged gradients (standard DDP)
-        _lib.call('bdn_sgd_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), float(self.lr),
-                  1.0 / self.world, self.layout.total, st)
+        self._update(st)
         eng.invalidate_weights()                              # packed bf16/f32 GEMM images are now stale
         self.last_counts = counts
         self.last_logits = logits
         return loss.clone()
+
+    def _update(self, st):
+        """The optimizer update on stream `st` with g = (sum of rank gradients) / world: per-rank loss, averaged gradients (standard DDP;
+        SURVEY.md 8e).  Host-side scalars only: the step count is a Python int, nothing syncs."""
+        o, n = self.optim, self.layout.total
+        if o.plain:                                          # p -= lr * g: the reference's optim.SGD(lr)
+            _lib.call('bdn_sgd_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), float(self.lr), 1.0 / self.world, n, st)
+            return
+        first = self.opt_step == 0
+        self.opt_step += 1
+        if o.kind == 'sgd':
+            buf = self.opt_state.get('momentum_buffer')
+            _lib.call('bdn_sgd_momentum_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), _lib.ptr(buf), float(self.lr),
+                      1.0 / self.world, o.momentum, o.dampening, o.weight_decay, int(o.nesterov), int(first), n, st)
+        else:
+            _lib.call('bdn_adam_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state['exp_avg'].data_ptr(),
+                      self.opt_state['exp_avg_sq'].data_ptr(), float(self.lr), 1.0 / self.world, o.betas[0], o.betas[1], o.eps,
+                      o.weight_decay, int(o.kind == 'adamw'), self.opt_step, n, st)
+
+    # ------------------------------------------------------------------ optimizer state in torch.optim's format
+    def optimizer_state_dict(self):
+        """The optimizer state as ``torch.optim.{SGD,Adam,AdamW}(model.parameters()).state_dict()`` holds it (state keyed by the index in
+        model.parameters(); param_groups with torch 2.10's keys).  The tensors are copies taken on the current stream, not views of the
+        live buffers."""
+        self.optim.lr = float(self.lr)
+        self.stream(self.flat_params.device)
+        torch.cuda.current_stream(self.flat_params.device).wait_stream(self._hp)        # after the last step's update
+        return _optim.flat_to_torch(self.optim, self.layout, self._names, self.opt_state, self.opt_step)
+
+    def load_optimizer_state_dict(self, sd):
+        """Load a torch.optim SGD / Adam / AdamW ``state_dict()`` of ``model.parameters()`` (or optimizer_state_dict()'s output).  As
+        torch does, the saved group's hyperparameters (lr included) replace the step's own.  Raises ValueError when the saved rule is
+        of the other family (SGD vs Adam), or its parameter count, shapes or per-parameter state do not fit this model."""
+        dev = self.flat_params.device
+        cfg, flat, step = _optim.torch_to_flat(sd, self.layout, self._names, dev)
+        if cfg.family != self.optim.family:
+            raise ValueError(f'optimizer state of {cfg.kind}, but this step runs {self.optim.kind}')
+        hp = self.stream(dev)
+        hp.wait_stream(torch.cuda.current_stream(dev))                                   # the copies above are ordered before the next step
+        for t in self.opt_state.values():
+            t.record_stream(hp)                                                          # a step still in flight may read the old buffers
+        self.optim, self.lr, self.opt_state, self.opt_step = cfg, cfg.lr, flat, step

@@ -430,6 +430,19 @@ int bdn_argmax_stitch(const float* logits, const int32_t* origins, uint8_t* mask
 
 /* ---- optim.SGD(lr) step, train.py:55,95: p -= lr * grad_scale * g over a flat f32 buffer ---- */
 int bdn_sgd_step(float* params, const float* grads, float lr, float grad_scale, size_t n, void* stream);
+/* ---- optim.SGD(momentum, dampening, weight_decay, nesterov) step, train.py:55-56,95 (torch 2.10 single-tensor rule), g = grad_scale * grads:
+ * g += weight_decay*p; buf = g on the first step, momentum*buf + (1-dampening)*g after it; g = g + momentum*buf (nesterov) or buf; p -= lr*g.
+ * momentum_buf: NULL iff momentum == 0.  All buffers 16-byte aligned f32 of n elements. ---- */
+int bdn_sgd_momentum_step(float* params, const float* grads, float* momentum_buf, float lr, float grad_scale, float momentum,
+                          float dampening, float weight_decay, int nesterov, int first_step, size_t n, void* stream);
+/* ---- optim.Adam / optim.AdamW step, train.py:56,95 (torch 2.10 single-tensor rule), g = grad_scale * grads: weight decay as
+ * p *= 1 - lr*wd (decoupled_weight_decay, AdamW) or g += wd*p (Adam); m = m + (1-beta1)*(g-m); v = beta2*v + (1-beta2)*g*g;
+ * p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps), bc_i = 1 - beta_i^step computed in double on the host.
+ * step: 1-based, the count AFTER this step's increment (no device sync).  The betas are double, as torch's hyperparameters are: 1 - beta2
+ * of a float 0.999 is 1.3e-5 away from 1 - 0.999, a hundred float32 ulps. ---- */
+int bdn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float lr, float grad_scale,
+                  double beta1, double beta2, float eps, float weight_decay, int decoupled_weight_decay, long long step,
+                  size_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,116 @@
+"""Micro-benchmark (test infrastructure) of the fused step's update rules:
+  (a) each update kernel alone at BiDateNet(13, 2)'s flat buffer size (13,401,156 floats), HIP events over --reps back-to-back launches
+      after a warm-up: us per launch and TB/s of the bytes the rule moves (plain SGD 3, momentum SGD 5, Adam / AdamW 7 buffer passes);
+  (b) the bf16 B=64 128x128 train step in ms for sgd, sgd + momentum, adam and adamw, interleaved in one process like tools/ab_cfg.py
+      (--rounds rounds of 5 warm-up + --steps timed steps per rule), median and difference to plain SGD.
+    python tools/bench_optim.py [--reps 200] [--rounds 4] [--steps 20] [--skip-step]
+Prints one JSON line at the end."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from fabric_amd import BiDateNet, _lib
+from fabric_amd.train_step import TrainStep
+
+N = 13_401_156                     # FlatLayout(BiDateNet(13, 2)).total: 13,401,154 parameters, each tensor padded to 4 floats
+HBM_PEAK = 8.0                     # TB/s, MI355X spec
+
+
+def kernels(reps):
+    dev = torch.device('cuda', 0)
+    g = torch.Generator(device='cpu').manual_seed(0)
+    p = torch.randn(N, generator=g).to(dev)
+    gr = (torch.randn(N, generator=g) * 1e-3).to(dev)
+    buf, m, v = torch.zeros(N, device=dev), torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+    st = _lib.stream_ptr()
+    step = [0]
+
+    def adam(decoupled):
+        def f():
+            step[0] += 1
+            _lib.call('bdn_adam_step', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), 1e-3, 1.0, 0.9, 0.999, 1e-8, 1e-2,
+                      decoupled, step[0], N, st)
+        return f
+    cases = [
+        ('sgd', 3, lambda: _lib.call('bdn_sgd_step', p.data_ptr(), gr.data_ptr(), 1e-3, 1.0, N, st)),
+        ('sgd_momentum', 5, lambda: _lib.call('bdn_sgd_momentum_step', p.data_ptr(), gr.data_ptr(), buf.data_ptr(), 1e-3, 1.0, 0.9, 0.0,
+                                              0.0, 0, 0, N, st)),
+        ('sgd_nesterov_wd', 5, lambda: _lib.call('bdn_sgd_momentum_step', p.data_ptr(), gr.data_ptr(), buf.data_ptr(), 1e-3, 1.0, 0.9,
+                                                 0.0, 1e-4, 1, 0, N, st)),
+        ('adam', 7, adam(0)),
+        ('adamw', 7, adam(1)),
+    ]
+    out = {}
+    for name, passes, fn in cases:
+        for _ in range(20):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) / reps * 1e3
+        tbs = passes * 4 * N / us * 1e-6
+        out[name] = {'us': round(us, 2), 'MB': round(passes * 4 * N / 1e6, 1), 'TB_s': round(tbs, 2), 'frac_of_8TBs': round(tbs / HBM_PEAK, 3)}
+        print(f'{name:18s} {us:8.1f} us  {passes * 4 * N / 1e6:6.1f} MB  {tbs:5.2f} TB/s  ({tbs / HBM_PEAK * 100:4.1f} % of 8 TB/s)', flush=True)
+    return out
+
+
+def steps(rounds, n_steps, batch=64):
+    dev = torch.device('cuda', 0)
+    g = torch.Generator(device='cpu').manual_seed(1)
+    x1 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    x2 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    lbl = (torch.rand(batch, 128, 128, generator=g) < 0.1).to(torch.uint8).to(dev)
+    rules = [('sgd', {}), ('sgd_momentum', dict(optimizer='sgd', momentum=0.9)), ('adam', dict(optimizer='adam')),
+             ('adamw', dict(optimizer='adamw'))]
+    ts = {}
+    for name, kw in rules:
+        torch.manual_seed(0)
+        ts[name] = TrainStep(BiDateNet(13, 2, precision='bf16').to(dev).train(), lr=1e-4, **kw)
+    res = {name: [] for name, _ in rules}
+    with torch.cuda.stream(ts['sgd'].stream()):                # every TrainStep shares the process's chain stream
+        for _ in range(rounds):
+            for name, _ in rules:
+                s = ts[name]
+                for _ in range(5):
+                    s.step(x1, x2, lbl)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n_steps):
+                    s.step(x1, x2, lbl)
+                e1.record()
+                torch.cuda.synchronize()
+                res[name].append(e0.elapsed_time(e1) / n_steps)
+    base = statistics.median(res['sgd'])
+    out = {}
+    for name, _ in rules:
+        med = statistics.median(res[name])
+        out[name] = {'ms': round(med, 4), 'delta_us': round((med - base) * 1e3, 1), 'rounds_ms': [round(t, 4) for t in res[name]]}
+        print(f'step {name:14s} median {med:.4f} ms  ({(med - base) * 1e3:+7.1f} us vs sgd)  {out[name]["rounds_ms"]}', flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=200)
+    ap.add_argument('--rounds', type=int, default=4)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--skip-step', action='store_true')
+    a = ap.parse_args()
+    res = {'n': N, 'kernels': kernels(max(a.reps, 200))}
+    if not a.skip_step:
+        res['step_bf16_b64'] = steps(a.rounds, a.steps)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
