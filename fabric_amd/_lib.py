@@ -95,6 +95,7 @@ SIGNATURES = {
     'bdn_upload_band': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'bdn_argmax': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_argmax_stitch': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'bdn_sample_patches': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'bdn_sgd_step': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
     'bdn_sgd_momentum_step': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _sz, _vp]),
     'bdn_adam_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, C.c_double, C.c_double, _f, _f, _i, _i64, _sz, _vp]),

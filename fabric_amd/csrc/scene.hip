@@ -2,6 +2,8 @@
 // The two dates of a scene stay resident in HBM as band planes; tiles are gathered straight into the packed
 // NHWC batch and predictions are written straight into the scene mask -- no host-side patch stack.
 #include "common.hpp"
+#include <climits>
+#include <type_traits>
 
 static inline unsigned grid_for(size_t n, int block = 256) { return (unsigned)((n + block - 1) / block); }
 
@@ -147,5 +149,120 @@ extern "C" int bdn_argmax_stitch(const float* logits, const int32_t* origins, ui
     hipLaunchKernelGGL(argmax_stitch_kernel, dim3(grid_for((size_t)n_tiles * p * p)), dim3(256), 0, (hipStream_t)stream,
                        logits, origins, mask, n_tiles, ncls, p, H, W, (size_t)p * p);
     BDN_CHECK_LAUNCH("argmax_stitch");
+    return BDN_OK;
+}
+
+// ============================================================ sample_patches: training patch pairs cut from HBM-resident cities
+// reference: utils/dataloaders.py:148-165 (onera_siamese_loader: crop + rot90 + two flips, per item) and the DataLoader's
+// default_collate, for a whole batch.  One descriptor (city, row, col, sym) per sample; sym = 4 t + 2 rr + rc is the dihedral
+// element of fabric_amd.utils.dataloaders._apply_symmetry: transpose if t, then reverse the rows if rr, then the columns if rc.
+// With W the S x S window at (row, col):  out[i][j] = t ? W[cj][ri] : W[ri][cj],  ri = rr ? S-1-i : i,  cj = rc ? S-1-j : j.
+// Pure data movement: floats travel as 32-bit patterns (NaN payloads, -0.0 and inf arrive unchanged), there is no arithmetic.
+// A block copies one 64 x 64 output tile of one plane.  Lane x walks an output row, so every store is one contiguous row segment per
+// wave.  Without transpose the load is also one row segment (descending under rc).  With transpose the tile is first loaded along
+// source rows into LDS and then read down an LDS column: a row pitch of 65 dwords puts the 64 lanes of a column read (and of a row
+// write) on distinct banks of their 32-lane groups.  Source rows start at arbitrary columns and S need not be a multiple of 4, so
+// the accesses are dwords (bytes for labels): 64 lanes x 4 B = 256 B per wave instruction, 16 independent loads per thread in flight.
+struct SampleCity { const float* images; const uint8_t* labels; int32_t H, W; };       // bdn_sample_patches' city record, 24 bytes
+
+constexpr int SP_TILE = 64, SP_WAVES = 4, SP_ROWS = SP_TILE / SP_WAVES;
+
+template <bool LABELS>
+__global__ __launch_bounds__(SP_TILE * SP_WAVES) void sample_patches_kernel(const SampleCity* __restrict__ cities, const int4* __restrict__ desc,
+                                                                            int C, int S, int tiles, uint32_t* __restrict__ o1,
+                                                                            uint32_t* __restrict__ o2, uint8_t* __restrict__ ol) {
+    using T = typename std::conditional<LABELS, uint8_t, uint32_t>::type;
+    __shared__ uint32_t lds[SP_TILE][SP_TILE + 1];
+    const int planes = LABELS ? 1 : 2 * C;
+    int b = blockIdx.x;
+    const int tt = b % (tiles * tiles); b /= tiles * tiles;
+    const int p = b % planes, s = b / planes;
+    const int4 d = desc[s];                                  // (city, row, col, sym), validated on the host
+    const SampleCity ct = cities[d.x];
+    const int t = d.w >> 2, rr = (d.w >> 1) & 1, rc = d.w & 1;
+    const int i0 = (tt / tiles) * SP_TILE, j0 = (tt % tiles) * SP_TILE;
+    const int ni = min(SP_TILE, S - i0), nj = min(SP_TILE, S - j0);
+    const size_t W = (size_t)ct.W, SS = (size_t)S * S;
+    const T* src;
+    T* dst;
+    if (LABELS) {
+        src = reinterpret_cast<const T*>(ct.labels);
+        dst = reinterpret_cast<T*>(ol + s * SS);
+    } else {
+        const int date = p >= C, c = p - date * C;
+        src = reinterpret_cast<const T*>(ct.images) + (size_t)p * ct.H * W;      // images [2][C][H][W]: plane p = date * C + c
+        dst = reinterpret_cast<T*>((date ? o2 : o1) + ((size_t)s * C + c) * SS);
+    }
+    src += (size_t)d.y * W + d.z;                            // window origin
+    const int x = threadIdx.x, y = threadIdx.y;
+    T v[SP_ROWS];
+    if (!t) {
+        const int j = j0 + x, cj = rc ? S - 1 - j : j;
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) {
+            const int i = i0 + y + k * SP_WAVES, ri = rr ? S - 1 - i : i;
+            if (x < nj && i < i0 + ni) v[k] = src[(size_t)ri * W + cj];
+        }
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) {
+            const int i = i0 + y + k * SP_WAVES;
+            if (x < nj && i < i0 + ni) dst[(size_t)i * S + j] = v[k];
+        }
+        return;
+    }
+    // transposed: output rows i take source columns ri, output columns j take source rows cj.  The source block is rows
+    // [a0, a0 + nj) x columns [b0, b0 + ni) of the window; lds[a - a0][b - b0] holds W[a][b].
+    const int a0 = rc ? S - j0 - nj : j0, b0 = rr ? S - i0 - ni : i0;
+#pragma unroll
+    for (int k = 0; k < SP_ROWS; k++) {
+        const int a = y + k * SP_WAVES;
+        if (x < ni && a < nj) v[k] = src[(size_t)(a0 + a) * W + b0 + x];
+    }
+#pragma unroll
+    for (int k = 0; k < SP_ROWS; k++) {
+        const int a = y + k * SP_WAVES;
+        if (x < ni && a < nj) lds[a][x] = (uint32_t)v[k];
+    }
+    __syncthreads();
+    const int jj = x, aa = rc ? nj - 1 - jj : jj;            // a - a0 of output column j0 + jj
+#pragma unroll
+    for (int k = 0; k < SP_ROWS; k++) {
+        const int ii = y + k * SP_WAVES, bb = rr ? ni - 1 - ii : ii;
+        if (jj < nj && ii < ni) dst[(size_t)(i0 + ii) * S + j0 + jj] = (T)lds[aa][bb];
+    }
+}
+
+extern "C" int bdn_sample_patches(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
+                                  const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
+                                  float* out_d1, float* out_d2, uint8_t* out_labels, void* stream) {
+    if (!cities_dev || !city_hw_host || !desc_host || !desc_dev || !out_d1 || !out_d2 || !out_labels)
+        BDN_FAIL(BDN_E_ARG, "sample_patches: null pointer");
+    if ((uintptr_t)desc_dev % 16 || (uintptr_t)cities_dev % 8) BDN_FAIL(BDN_E_ARG, "sample_patches: desc_dev must be 16-byte and cities_dev 8-byte aligned");
+    if (n <= 0 || S <= 0 || C <= 0 || n_cities <= 0)
+        BDN_FAIL(BDN_E_SHAPE, "sample_patches: need n, S, C, n_cities > 0 (got n=%d S=%d C=%d n_cities=%d)", n, S, C, n_cities);
+    for (int k = 0; k < n_cities; k++)
+        if (city_hw_host[2 * k] <= 0 || city_hw_host[2 * k + 1] <= 0)
+            BDN_FAIL(BDN_E_SHAPE, "sample_patches: city %d has shape %d x %d", k, city_hw_host[2 * k], city_hw_host[2 * k + 1]);
+    for (int k = 0; k < n; k++) {                            // every address the kernel forms comes from a descriptor checked here
+        const int32_t* e = desc_host + 4 * (size_t)k;
+        const int city = e[0], row = e[1], col = e[2], sym = e[3];
+        if (city < 0 || city >= n_cities) BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: city %d outside [0, %d)", k, city, n_cities);
+        if (sym < 0 || sym > 7) BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: sym %d outside [0, 8)", k, sym);
+        const long long H = city_hw_host[2 * city], W = city_hw_host[2 * city + 1];
+        if (row < 0 || (long long)row + S > H)
+            BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: row %d + S %d outside H %lld of city %d", k, row, S, H, city);
+        if (col < 0 || (long long)col + S > W)
+            BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: col %d + S %d outside W %lld of city %d", k, col, S, W, city);
+    }
+    const long long tiles = (S + SP_TILE - 1) / SP_TILE, img_blocks = (long long)n * 2 * C * tiles * tiles;
+    if (img_blocks > INT_MAX) BDN_FAIL(BDN_E_SHAPE, "sample_patches: %lld blocks exceed the grid", img_blocks);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(SP_TILE, SP_WAVES);
+    hipLaunchKernelGGL(sample_patches_kernel<false>, dim3((unsigned)img_blocks), block, 0, st, (const SampleCity*)cities_dev,
+                       (const int4*)desc_dev, C, S, (int)tiles, (uint32_t*)out_d1, (uint32_t*)out_d2, out_labels);
+    BDN_CHECK_LAUNCH("sample_patches");
+    hipLaunchKernelGGL(sample_patches_kernel<true>, dim3((unsigned)(n * tiles * tiles)), block, 0, st, (const SampleCity*)cities_dev,
+                       (const int4*)desc_dev, C, S, (int)tiles, (uint32_t*)out_d1, (uint32_t*)out_d2, out_labels);
+    BDN_CHECK_LAUNCH("sample_patches (labels)");
     return BDN_OK;
 }

@@ -1,0 +1,152 @@
+"""Training patch pairs cut out of HBM-resident city stacks (bdn_sample_patches) instead of on the host.
+
+The host path (reference utils/dataloaders.py:148-198 + utils/helpers.py:250-257) crops every patch pair with numpy, collates the
+batch, pins it and copies it over PCIe.  `DevicePatchLoader` keeps the city stacks on the device and sends only the batch's
+descriptors, (city, row, col, symmetry) as int32, through a pinned ring; one launch on the current stream then writes the batch.
+It yields what `DataLoader(dataset, batch_size, sampler=sampler, drop_last=drop_last, num_workers=0)` yields, moved to the device,
+bit for bit: the same index order and batch boundaries, and the same `_draw_symmetry()` calls from the global `random`, in the same
+order, when `dataset.aug`.
+
+    loader = DevicePatchLoader(train_ds, stacks, batch_size=64, sampler=ShardSampler(len(train_ds), rank, world, seed))
+    for x1, x2, y in loader:            # device tensors; valid until the next iteration (the contract of DeviceFeeder)
+        loss = step.step(x1, x2, y)
+"""
+import numpy as np
+import torch
+import torch.utils.data
+
+from . import _lib
+from .utils.dataloaders import _draw_symmetry
+
+
+def symmetry_code(sym):
+    """(transpose, reverse rows, reverse columns) -> the `sym` field 4 t + 2 rr + rc of a descriptor."""
+    t, rr, rc = sym
+    return 4 * int(t) + 2 * int(rr) + int(rc)
+
+
+def plan_descriptors(dataset, indices, city_index, out=None):
+    """Host half of one batch, no device needed: int32 [len(indices)][4] = (city, row, col, sym) for items `indices` of the
+    OneraPreloader `dataset`, drawing one symmetry per item from the global `random` exactly as `dataset[i]` does (only when
+    `dataset.aug`).  `city_index`: {city name: row of the city table}.  `out`: an int32 array to fill (a view of it is returned)."""
+    n = len(indices)
+    table = np.empty((n, 4), np.int32) if out is None else out[:n]
+    for k, idx in enumerate(indices):
+        city, i, j = dataset.imgs[idx]
+        table[k] = (city_index[city], i, j, symmetry_code(_draw_symmetry()) if dataset.aug else 0)
+    return table
+
+
+def batch_sampler(dataset, batch_size, sampler=None, drop_last=False):
+    """The batches of indices that DataLoader(dataset, batch_size, sampler=sampler, drop_last=drop_last) visits."""
+    return torch.utils.data.BatchSampler(sampler if sampler is not None else torch.utils.data.SequentialSampler(dataset),
+                                         batch_size, drop_last)
+
+
+def plan_epoch(dataset, city_index, batch_size, sampler=None, drop_last=False):
+    """The descriptor tables of one pass of DevicePatchLoader, planned on the host alone (no device): one int32 [n][4] per batch."""
+    for indices in batch_sampler(dataset, batch_size, sampler, drop_last):
+        yield plan_descriptors(dataset, indices, city_index)
+
+
+def device_stacks(stacks, device):
+    """{city: {'images': float32 [2,C,H,W], 'labels': uint8 [H,W]}} on `device`: device tensors are kept as they are (no copy),
+    numpy arrays and CPU tensors are uploaded.  Share the result between loaders to upload once."""
+    device = torch.device(device)
+    out = {}
+    for city, d in stacks.items():
+        e = {}
+        for key, dtype in (('images', torch.float32), ('labels', torch.uint8)):
+            t = d[key] if torch.is_tensor(d[key]) else torch.from_numpy(np.asarray(d[key]))
+            if t.dtype != dtype or not t.is_contiguous():
+                raise RuntimeError(f'fabric_amd: city {city!r}: {key} must be contiguous {dtype}, got {t.dtype}'
+                                   f'{"" if t.is_contiguous() else " (not contiguous)"}')
+            e[key] = t if t.device == device else t.to(device)
+        out[city] = e
+    return out
+
+
+class _Slot:
+    def __init__(self, batch_size, C, S, device):
+        self.desc_pin = torch.empty((batch_size, 4), dtype=torch.int32, pin_memory=True)
+        self.desc_np = self.desc_pin.numpy()
+        self.desc_dev = torch.empty((batch_size, 4), dtype=torch.int32, device=device)
+        self.d1 = torch.empty((batch_size, C, S, S), dtype=torch.float32, device=device)
+        self.d2 = torch.empty_like(self.d1)
+        self.labels = torch.empty((batch_size, S, S), dtype=torch.uint8, device=device)
+        self.done = None          # recorded after the launch: the copy out of desc_pin is over once it has completed
+
+
+class DevicePatchLoader:
+    """Batches of `dataset` (an OneraPreloader: its `imgs`, `input_size` and `aug` are used) sampled on the device from `stacks`
+    ({city: {'images', 'labels'}}; see device_stacks).  `depth` (>= 2) slots of pinned descriptors and device outputs are cycled;
+    a slot's pinned table is rewritten only after the launch that read it `depth` batches ago has completed."""
+
+    def __init__(self, dataset, stacks, batch_size, sampler=None, drop_last=False, device=None, depth=3):
+        self.dataset = dataset
+        self.batch_sampler = batch_sampler(dataset, batch_size, sampler, drop_last)
+        self.sampler = self.batch_sampler.sampler
+        self.batch_size, self.drop_last, self.S = int(batch_size), drop_last, int(dataset.input_size)
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise RuntimeError('fabric_amd: DevicePatchLoader needs a ROCm device')
+        self.stacks = device_stacks(stacks, self.device)          # held: the table below points into these tensors
+        self.cities = sorted(self.stacks)
+        self.city_index = {c: k for k, c in enumerate(self.cities)}          # row of the city table: cities in sorted order
+        shapes = []
+        for c in self.cities:
+            im, lb = self.stacks[c]['images'], self.stacks[c]['labels']
+            if im.dim() != 4 or im.shape[0] != 2 or lb.dim() != 2 or tuple(im.shape[2:]) != tuple(lb.shape):
+                raise RuntimeError(f'fabric_amd: city {c!r}: need images [2,C,H,W] and labels [H,W], got {tuple(im.shape)} and {tuple(lb.shape)}')
+            shapes.append(tuple(im.shape[1:]))
+        if len({s[0] for s in shapes}) != 1:
+            raise RuntimeError(f'fabric_amd: all cities need the same number of bands, got {sorted({s[0] for s in shapes})}')
+        self.C = shapes[0][0]
+        self.city_hw = np.ascontiguousarray([s[1:] for s in shapes], dtype=np.int32)
+        rec = np.zeros((len(self.cities), 3), np.int64)           # { const float* images; const uint8_t* labels; int32 H, W; }
+        for k, c in enumerate(self.cities):
+            h, w = (int(v) for v in self.city_hw[k])
+            rec[k] = (self.stacks[c]['images'].data_ptr(), self.stacks[c]['labels'].data_ptr(), h | (w << 32))
+        self.city_table = torch.from_numpy(rec).to(self.device)
+        self.depth = max(2, int(depth))
+        self.slots = [_Slot(self.batch_size, self.C, self.S, self.device) for _ in range(self.depth)]
+        torch.cuda.synchronize(self.device)                       # uploads and allocations are complete before any stream reads them
+        self._k = 0
+        self._streams = set()
+
+    def _long_lived(self):
+        yield self.city_table
+        for city in self.stacks.values():
+            yield from (city['images'], city['labels'])
+        for slot in self.slots:
+            yield from (slot.desc_dev, slot.d1, slot.d2, slot.labels)
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def __iter__(self):
+        for indices in self.batch_sampler:
+            yield self._sample(indices)
+
+    def _sample(self, indices):
+        """Plan the batch on the host, copy its descriptors through the next pinned slot and launch on the current stream."""
+        slot = self.slots[self._k % self.depth]
+        self._k += 1
+        if slot.done is not None:
+            slot.done.synchronize()                               # the copy that read desc_pin `depth` batches ago has run
+        n = len(indices)
+        plan_descriptors(self.dataset, indices, self.city_index, out=slot.desc_np)
+        cur = torch.cuda.current_stream(self.device)
+        desc_dev = slot.desc_dev[:n]
+        desc_dev.copy_(slot.desc_pin[:n], non_blocking=True)
+        d1, d2, labels = slot.d1[:n], slot.d2[:n], slot.labels[:n]
+        _lib.call('bdn_sample_patches', self.city_table.data_ptr(), self.city_hw.ctypes.data, len(self.cities), self.C,
+                  slot.desc_pin.data_ptr(), desc_dev.data_ptr(), n, self.S, d1.data_ptr(), d2.data_ptr(), labels.data_ptr(),
+                  cur.cuda_stream)
+        if cur.cuda_stream not in self._streams:                 # memory allocated at construction, read and written on this stream
+            self._streams.add(cur.cuda_stream)
+            for t in self._long_lived():
+                t.record_stream(cur)
+        slot.done = torch.cuda.Event()
+        slot.done.record(cur)
+        return d1, d2, labels

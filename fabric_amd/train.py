@@ -37,12 +37,7 @@ def make_loaders(full_load, val_cities, patch_size, stride, batch_size, augmenta
     shuffle (utils/dataloaders.py:171) consumes, and sorted first so that the reference's set-ordered city list
     (utils/dataloaders.py:55) cannot differ between ranks.  Call `train_loader.sampler.set_epoch(e)` every epoch."""
     from .parallel import ShardSampler
-    shapes = {c: d['labels'].shape for c, d in full_load.items()}
-    train_meta, val_meta = metadata_from_shapes(shapes, val_cities, patch_size, stride)
-    train_meta = sorted(train_meta)                        # rank-independent base order; the sampler owns the shuffling
-    train_ds = OneraPreloader('', train_meta, full_load, patch_size, augmentation)
-    train_ds.imgs.sort()                                   # undo the constructor's process-local shuffle (same list object)
-    val_ds = OneraPreloader('', val_meta, full_load, patch_size, False)
+    train_ds, val_ds = _patch_datasets(full_load, val_cities, patch_size, stride, augmentation)
     sampler = ShardSampler(len(train_ds), rank, world_size, seed=seed)
     kw = dict(batch_size=batch_size, num_workers=num_workers, pin_memory=True)   # pinned batches: the copy stream DMAs them without staging
     # Augmentation draws (global `random`, utils/dataloaders.py:150-156) must differ between ranks.  With worker processes every worker
@@ -53,6 +48,44 @@ def make_loaders(full_load, val_cities, patch_size, stride, batch_size, augmenta
     return (torch.utils.data.DataLoader(train_ds, sampler=sampler, drop_last=True, generator=gen,
                                         worker_init_fn=_RankWorkerSeed(seed, rank), **kw),
             torch.utils.data.DataLoader(val_ds, shuffle=False, **kw))
+
+
+def _patch_datasets(full_load, val_cities, patch_size, stride, augmentation):
+    """The training and validation OneraPreloader datasets of make_loaders / make_device_loaders."""
+    shapes = {c: tuple(d['labels'].shape) for c, d in full_load.items()}
+    train_meta, val_meta = metadata_from_shapes(shapes, val_cities, patch_size, stride)
+    train_meta = sorted(train_meta)                        # rank-independent base order; the sampler owns the shuffling
+    train_ds = OneraPreloader('', train_meta, full_load, patch_size, augmentation)
+    train_ds.imgs.sort()                                   # undo the constructor's process-local shuffle (same list object)
+    val_ds = OneraPreloader('', val_meta, full_load, patch_size, False)
+    return train_ds, val_ds
+
+
+def make_device_loaders(full_load, val_cities, patch_size, stride, batch_size, augmentation, rank=0, world_size=1, seed=0,
+                        device=None):
+    """make_loaders with the patches cut on the device (fabric_amd.device_loader): the same datasets, built and sorted the same way,
+    the same ShardSampler and drop_last for training, no augmentation and no drop_last for validation.  `full_load`'s city stacks are
+    used in place when they are device tensors (ingest's device= output) and uploaded once otherwise; both loaders share them.  The
+    augmentation draws come from the process's global `random` at iteration time, as with make_loaders(num_workers=0)."""
+    from .device_loader import DevicePatchLoader, device_stacks
+    from .parallel import ShardSampler
+    device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    train_ds, val_ds = _patch_datasets(full_load, val_cities, patch_size, stride, augmentation)
+    stacks = device_stacks(full_load, device)
+    sampler = ShardSampler(len(train_ds), rank, world_size, seed=seed)
+    return (DevicePatchLoader(train_ds, stacks, batch_size, sampler=sampler, drop_last=True, device=device),
+            DevicePatchLoader(val_ds, stacks, batch_size, device=device))
+
+
+def _device_batches(loader, dev, feeder):
+    """The device batches of `loader`: a DevicePatchLoader samples them itself (on the current stream), any other loader goes through
+    `feeder` or, without one, a plain copy per batch."""
+    from .device_loader import DevicePatchLoader
+    if isinstance(loader, DevicePatchLoader):
+        return iter(loader)
+    if feeder is not None:
+        return feeder(loader)
+    return ((b1.to(dev), b2.to(dev), lb.to(dev)) for b1, b2, lb in loader)
 
 
 class _RankWorkerSeed:
@@ -70,12 +103,14 @@ class _RankWorkerSeed:
 def train_epoch(step, loader, dev, patch_size, feeder=None):
     """train.py:73-118 without the per-step host round trip: losses / counts are read back once per epoch, and the
     host -> device copies of batch k+1 (train.py:83-85) run on a copy stream under the step of batch k."""
+    from .device_loader import DevicePatchLoader
     from .input_pipeline import DeviceFeeder
     step.model.train()
     recs = []
-    feeder = feeder or DeviceFeeder(dev)
+    if not isinstance(loader, DevicePatchLoader):
+        feeder = feeder or DeviceFeeder(dev)
     with torch.cuda.stream(step.stream()):                # the loop lives on the step's own stream: no joins per step
-        for b1, b2, labels in feeder(loader):
+        for b1, b2, labels in _device_batches(loader, dev, feeder):
             loss = step.step(b1, b2, labels)
             recs.append((loss, step.last_counts.clone(), labels.shape[0]))
     torch.cuda.current_stream(dev).wait_stream(step.stream())
@@ -93,8 +128,7 @@ def validate(model, loader, dev, patch_size, criterion, feeder=None):
     from .utils.metrics import confusion_counts
     model.eval()
     metrics = initialize_metrics()
-    batches = feeder(loader) if feeder is not None else ((b1.to(dev), b2.to(dev), lb.to(dev)) for b1, b2, lb in loader)
-    for b1, b2, labels in batches:
+    for b1, b2, labels in _device_batches(loader, dev, feeder):
         logits = model(b1, b2)
         loss = criterion(logits, labels.long())
         c = confusion_counts(logits, labels).cpu()
@@ -111,8 +145,7 @@ def train_epoch_autograd(model, criterion, optimizer, loader, dev, patch_size, w
     from .utils.metrics import batch_prf_from_counts, confusion_counts
     model.train()
     metrics = initialize_metrics()
-    batches = feeder(loader) if feeder is not None else ((b1.to(dev), b2.to(dev), lb.to(dev)) for b1, b2, lb in loader)
-    for b1, b2, labels in batches:
+    for b1, b2, labels in _device_batches(loader, dev, feeder):
         optimizer.zero_grad()
         logits = model(b1, b2)
         loss = criterion(logits, labels.long())
@@ -215,6 +248,9 @@ def main(argv=None):
     ap.add_argument('--adam_eps', type=float, default=1e-8, help='adam / adamw')
     ap.add_argument('--resume', default=None, help='DIR/checkpoint_epoch_N.state_dict.pt (and its sibling optimizer_epoch_N.pt): '
                                                    'continue at epoch N + 1 of --epochs')
+    ap.add_argument('--device_patches', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=False,
+                    help='cut and augment the patch pairs on the device from city stacks kept in HBM (fabric_amd.device_loader) '
+                         'instead of on the host; --num_workers does not apply then')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
                                                      "band_stds, ...): its entries become defaults like utils/parser.py:7-10")
     pre, _ = ap.parse_known_args(argv)
@@ -260,11 +296,18 @@ def main(argv=None):
                              'metadata.json); or use --synthetic')
         from .utils import ingest
         scenes = ingest.full_onera_loader(opt.dataset_dir, opt, device=dev)      # city stacks stay in HBM for the scene pass
-        data = {c: {'images': d['images'].cpu().numpy(), 'labels': d['labels']} for c, d in scenes.items()}
+        if opt.device_patches:                             # the patch sampler reads the same HBM stacks: no round trip through the host
+            data = {c: {'images': d['images'], 'labels': d['labels']} for c, d in scenes.items()}
+        else:
+            data = {c: {'images': d['images'].cpu().numpy(), 'labels': d['labels']} for c, d in scenes.items()}
         val_cities = [c for c in opt.validation_cities if c in data]
-    train_loader, val_loader = make_loaders(data, val_cities, opt.patch_size, opt.stride // 2 if opt.synthetic else opt.stride,
-                                            opt.batch_size, opt.augmentation, num_workers=opt.num_workers,
-                                            rank=rank, world_size=world, seed=opt.seed)
+    stride = opt.stride // 2 if opt.synthetic else opt.stride
+    if opt.device_patches:
+        train_loader, val_loader = make_device_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
+                                                       rank=rank, world_size=world, seed=opt.seed, device=dev)
+    else:
+        train_loader, val_loader = make_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
+                                                num_workers=opt.num_workers, rank=rank, world_size=world, seed=opt.seed)
     random.seed(opt.seed * 7919 + rank)                    # different augmentation draws per rank from here on
     model = BiDateNet(len(opt.band_ids) if opt.band_ids else 13, 2, precision=opt.precision).to(dev)
     opt_sd, first_epoch = None, 0
@@ -273,7 +316,8 @@ def main(argv=None):
     fused = opt.loss_function == 'tversky'
     from .input_pipeline import DeviceFeeder
     from .utils.helpers import get_criterion
-    feeder = DeviceFeeder(dev)                             # ONE feeder (copy stream, staging threads, device slots) for the whole run
+    # ONE feeder (copy stream, staging threads, device slots) for the whole run; device-sampled batches need none
+    feeder = None if opt.device_patches else DeviceFeeder(dev)
     criterion = get_criterion(opt)                         # validation reports the criterion the run optimises (train.py:137)
     if fused:
         step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta,
@@ -316,7 +360,8 @@ def main(argv=None):
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
                                   step.optimizer_state_dict() if fused else optimizer.state_dict())
-    feeder.close()
+    if feeder is not None:
+        feeder.close()
     if world > 1:
         dist.destroy_process_group()
 

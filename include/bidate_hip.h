@@ -428,6 +428,18 @@ int bdn_argmax(const float* logits, uint8_t* out, int n, int ncls, int H, int W,
 int bdn_argmax_stitch(const float* logits, const int32_t* origins, uint8_t* mask,
                       int n_tiles, int ncls, int p, int H, int W, void* stream);
 
+/* ---- training patch pairs on the device: utils/dataloaders.py:148-165 (onera_siamese_loader) + the DataLoader collate, for a batch ----
+ * cities_dev: DEVICE array of n_cities records { const float* images; const uint8_t* labels; int32 H, W; } (24 bytes each, 8-byte
+ * aligned): images [2][C][H][W] f32 and labels [H][W] uint8, both contiguous.  city_hw_host: HOST int32 [n_cities][2] = (H, W), the
+ * same values as the records.  desc_host: HOST int32 [n][4] = (city, row, col, sym), every one checked here before anything is
+ * launched (city in range, sym in 0..7, 0 <= row, row + S <= H, 0 <= col, col + S <= W); desc_dev: the same table in device memory,
+ * 16-byte aligned, which the kernel reads.  sym = 4 t + 2 rr + rc: transpose the window if t, then reverse its rows if rr, then its
+ * columns if rc (fabric_amd.utils.dataloaders._apply_symmetry).  out_d1, out_d2: [n][C][S][S] f32 (date 1, date 2); out_labels:
+ * [n][S][S] uint8.  Bits are moved, never computed: the output equals the host crop bit for bit. */
+int bdn_sample_patches(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
+                       const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
+                       float* out_d1, float* out_d2, uint8_t* out_labels, void* stream);
+
 /* ---- optim.SGD(lr) step, train.py:55,95: p -= lr * grad_scale * g over a flat f32 buffer ---- */
 int bdn_sgd_step(float* params, const float* grads, float lr, float grad_scale, size_t n, void* stream);
 /* ---- optim.SGD(momentum, dampening, weight_decay, nesterov) step, train.py:55-56,95 (torch 2.10 single-tensor rule), g = grad_scale * grads:
