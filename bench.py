@@ -8,14 +8,22 @@ backward + gradient all-reduce + SGD) on synthetic 13-band 128x128 patch pairs, 
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0 (contract in the task description).  `value` is measured with the inputs resident in HBM.
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line; the roofline
+rides on the timed steps themselves (below).  Everything else it can measure runs only with --full:
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
 Extra objects on the same line:
   roofline       the dominant MFMA kernel of the step: algorithmic FLOP per launch / launch time measured with HIP events on
                  the launch stream inside the timed region (one launch bracketed per step, every launch shape weighted
                  equally), against the dense bf16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md); HBM bytes per launch and
                  per step from the committed PMC passes (profiles/);
+With --full only (the legs from collectives on: N = 1 and bf16, unless --no-extras):
+  step_classes   where the step's time goes, per launch class and per queue, from one instrumented untimed step;
   cpu_baseline   the oracle's stock-torch assembly of the reference graph timed on the host cores (rank 0, N=1 only): median of 5
                  steps at B=16 and at B=4, at the fastest thread count;
-  collectives    the same step with its five gradient-bucket all-reduces forced through RCCL (one rank), timed beside the local step;
+  collectives    the same step with its five gradient-bucket all-reduces forced through RCCL (one rank), timed beside the local step
+                 (with N > 1 or --force-collectives, in every run: the set-up guard's report on the headline loop's own all-reduces);
   mfma_ceiling   a bare MFMA loop on zero and on random bf16 operands: the data-dependent (power-bound) ceiling of the matrix cores;
   host_fed       the same step fed from pinned HOST memory through fabric_amd.input_pipeline.DeviceFeeder (PCIe inclusive);
   parity_setting pairs/s of the two float32-class settings (bf16x3: logits within 1e-3; fp32: exact f32 MFMA);
@@ -755,9 +763,11 @@ def main():
     ap.add_argument('--size', type=int, default=128)
     ap.add_argument('--channels', type=int, default=13)
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'bf16x3', 'bf16x3-fast', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: step_classes, cpu_baseline and (N = 1, bf16) the extra legs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-roofline', action='store_true', help='skip the per-launch HIP events')
-    ap.add_argument('--no-extras', action='store_true', help='skip the host_fed / parity_setting / scene legs')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the host_fed / parity_setting / scene legs')
     ap.add_argument('--scene-size', type=int, default=10000)
     ap.add_argument('--force-collectives', action='store_true',
                     help='N=1 only: the HEADLINE loop itself issues its gradient-bucket all-reduces through RCCL (world size 1)')
@@ -866,13 +876,15 @@ def main():
         dom_family = max(fam_all.items(), key=lambda kv: kv[1][2])[0]
         eng.prof_filter = tuple(fam_all[dom_family][3])          # every instantiation of the family with the most time per step
     classes = None
-    if not args.no_roofline and rank == 0:
+    if not args.no_roofline and rank == 0 and args.full:
         try:
             classes = step_classes(ts, x1, x2, lbl, B, dev)
         except Exception as e:
             classes = {'error': f'{type(e).__name__}: {e}'}
     elif not args.no_roofline:
-        ts.step(x1, x2, lbl)                  # the other ranks run the same (uninstrumented) step: collectives stay matched
+        # the other ranks, and without --full every rank, run the same step uninstrumented: collectives stay matched, and the timed
+        # steps start from the same weights with or without --full
+        ts.step(x1, x2, lbl)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -999,7 +1011,7 @@ def main():
             out['hbm_bytes_per_step'] = hb[0]
             out['hbm_frac'] = hb[0] / (ms_step * 1e-3) / HBM_PEAK
             out['hbm_source'] = hb[1] + ' (PMC FETCH_SIZE x2 + WRITE_SIZE summed over every kernel of a step; bytes/step divided by this run\'s step time and 8 TB/s)'
-        if world == 1 and not args.no_extras and args.precision == 'bf16':
+        if world == 1 and args.full and not args.no_extras and args.precision == 'bf16':
             mc = mfma_ceiling()
             if mc is not None:
                 out['mfma_ceiling'] = mc
@@ -1032,7 +1044,7 @@ def main():
             if isinstance(out.get('conv3d'), dict) and 'error' not in out['conv3d']:
                 out['conv3d']['rocprof'] = leg_profile('conv3d', 0, 0, 'tools/bench_conv3d_block.py under rocprofv3: per-instantiation average launch times (CKB = 32: the '
                                                        '13 -> 64 layers, 128: the 64 -> 64 layers; D3 = true marks the 3x3x3 walk); the 2 x 5 and 16 x 5 batches share an instantiation')
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
         json_out.write(json.dumps(out) + '\n')
         json_out.flush()

@@ -342,14 +342,15 @@ def test_bench_two_ranks_end_to_end_on_one_device(tmp_path):
     """bench.py's N > 1 code path for real: torch.distributed.run with two ranks (the driver's command line), both on cuda:0 with gloo
     in place of RCCL (BENCH_BACKEND=gloo: the one thing a single-GPU box cannot do is give each rank its own device).  One JSON line
     from rank 0 with n_gpus == 2, weak scaling, whole-job value = 2 ranks x batch / ms_per_step, the 3 timed steps in three windows;
-    --dump-outputs writes rank 0's last-step outputs as float32 / float64 .npy files."""
+    --full adds rank 0's instrumented step (step_classes) beside the other rank's plain one; --dump-outputs writes rank 0's last-step
+    outputs as float32 / float64 .npy files."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env['BENCH_BACKEND'] = 'gloo'
     port = str(36000 + os.getpid() % 2000)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1', '--master-port', port,
            os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2', '--batch', '8', '--size', '64',
-           '--dump-outputs', str(tmp_path / 'out')]
+           '--full', '--dump-outputs', str(tmp_path / 'out')]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith('{"metric"')]
