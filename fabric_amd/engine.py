@@ -25,7 +25,6 @@ ENC_CH = (64, 128, 256, 512, 512)           # models/bidate_model.py:10-14
 DEC_OUT = (256, 128, 64, 64)                # models/bidate_model.py:16-19
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
-FUSE_UPS_BS = 1          # tools/archive/ab_attr.py switch: upsample2x_bwd leaves the BatchNorm-backward partial sums (0: separate reduction pass)
 
 
 def _round_up(v, m):
@@ -267,9 +266,6 @@ class BiDateEngine:
         # queue.  True = every eligible layer (no split pass left in a step), a tuple of layer names = only those (eval forwards then take it
         # for operands of <= 128 channels), False = none (rounds 3-5; the checker of the fused form in tests)
         self.x3_src_f32 = True
-        # the first convolution's weight gradient (the last GEMM of a backward pass, where the bf16 path runs its fused first-layer kernel on the chain's
-        # stream) is launched on the chain's stream instead of behind the previous layer's GEMM on the second queue (fp32 / bf16x3 settings)
-        self.last_wgrad_on_chain = True
         # the first convolution's weight gradient with its BatchNorm backward applied on load (bdn_conv3x3_wgrad_bnbwd: bf16 since round 2,
         # bf16x3 / bf16x3-fast since round 6); False = bn_bwd_apply + the generic GEMM (the checker of the fused form in tests)
         self.first_wgrad_fused = True
@@ -279,8 +275,6 @@ class BiDateEngine:
         self.x3_tail_wgrad_blocks = 512
         self.wgrad_blocks = 0           # per-call target grid of the weight-gradient GEMM (0 = the library's default: half the CUs)
         self._handoffs = {}             # device index -> reusable device-local events, one per hand-off of a backward pass
-        self._diag_skip_wgrad = False
-        self._diag_skip_handoff = 0     # timing diagnostics only (results WRONG): 1 = the weight-gradient GEMMs are released without the event hand-off
         self._diag_skip_reduce = 0      # timing diagnostics only (results WRONG): 1 = the split-K reductions of the weight-gradient GEMMs are not launched
         self.prof_pick = None      # with prof_filter: index of the one matching launch per step that gets the event pair
         self._prof_seen = 0
@@ -661,6 +655,55 @@ class BiDateEngine:
                 return None
         return logits
 
+    # ------------------------------------------------------------------ backward schedule rules (tests/launch_cases.py asks them too)
+    @property
+    def bwd_dtype(self):
+        """dtype of every backward GEMM (data gradient, weight gradient, first-layer weight gradient): bf16x3-fast runs them on two terms."""
+        return BDN_BF16X2 if (self.x3 and self.x3_bwd_terms == 2) else self.mdt
+
+    def folds_bn_bwd(self, L, h, w):
+        """Does layer L on an h x w map apply its BatchNorm backward inside its data-gradient conv (bdn_conv3x3_dgrad_bb)?  bf16 only, 64
+        output channels, maps above 8 x 8 (the kernel refuses smaller ones); never the last layer (the classifier's backward forms its dz)
+        nor the first (no data gradient)."""
+        return (self.mdt == BDN_BF16 and L.name in self.fold_bn_bwd and L.cout == 64 and min(h, w) > 8
+                and L is not self.layers[0] and L is not self.layers[-1])
+
+    def first_wgrad_dtype(self, n, h, w, ipg):
+        """dtype of the first layer's weight gradient with its BatchNorm backward applied on load (bdn_conv3x3_wgrad_bnbwd) at this shape,
+        or None: the first layer then takes bn_bwd and the generic GEMM."""
+        L = self.layers[0]
+        if self.first_wgrad_fused and _lib.load().bdn_conv3x3_wgrad_bnbwd_supported(self.mdt, n, h, w, L.cout, L.cin, ipg):
+            return self.bwd_dtype
+        return None
+
+    def wgrad_launch(self, L, c0, c1, mode):
+        """(dtype, c0, c1, mode, flags word) of layer L's weight-gradient GEMM on an operand of c0 (+ c1) channels in `mode`.  bf16x3: one
+        split operand of c0 + c1 channels; the LAST GEMM on the second queue (e1b) on a grid of its own in the three-term backward."""
+        phases = 1 if self._diag_skip_reduce else 3          # (_diag_skip_reduce: timing diagnostics only)
+        if self.x3:
+            tail = L.name == 'e1b' and self.x3_tail_wgrad_blocks and self.x3_bwd_terms == 3
+            return self.bwd_dtype, c0 + c1, 0, IN_PLAIN, wg_flags(phases, 0, self.x3_tail_wgrad_blocks if tail else self.wgrad_blocks)
+        return self.dt, c0, c1, mode, wg_flags(phases, self.wgrad_kernel, self.wgrad_blocks)
+
+    @staticmethod
+    def wgrad_gemm_name(dtype, n, h, w, cout, c0, c1, ipg, mode, flags):
+        """The GEMM instantiation(s) bdn_conv3x3_wgrad_ex runs, '+'-joined.  The family is the library's answer (bdn_conv3x3_wgrad_variant);
+        the tile geometry of the one-chunk-at-a-time kernel and the bf16x3 fused / doubled-operand choice are HAND COPIES of pick_tile
+        (common.hpp) and bdn_conv3x3_wgrad_ex: tests/test_gpu_launch_shapes.py checks them against recorded launches."""
+        lib = _lib.load()
+        if dtype in (BDN_BF16X3, BDN_BF16X2):
+            terms = 3 if dtype == BDN_BF16X3 else 2
+            if cout % 64 == 0 and c0 % 64 == 0 and lib.bdn_conv3x3_wgrad_variant(BDN_BF16, n, h, w, cout, c0, 0, ipg, IN_PLAIN, flags) == WG_ROLE:
+                return f'wgrad7x_kernel<{terms}>'
+            # the doubled operands through the bf16 GEMM (internal plan flags: the lo x lo quadrant left out), then the quadrant sum
+            xfl = (1 << 30) | ((1 << 29) if terms == 2 else 0)
+            return BiDateEngine.wgrad_gemm_name(BDN_BF16, n, h, w, 2 * cout, 2 * c0, 0, ipg, IN_PLAIN, flags | xfl) + '+wgrad_x3_combine_kernel'
+        if lib.bdn_conv3x3_wgrad_variant(dtype, n, h, w, cout, c0, c1, ipg, mode, flags) == WG_ROLE:
+            return f'wgrad7_kernel<{"true" if mode == IN_BNRELU else "false"}>'
+        small = h <= 8 and w <= 8 and ipg % 2 == 0
+        return (f'wgrad_kernel<{"bf16" if dtype == BDN_BF16 else "f32"},8,{"8,2" if small else "16,1"},'
+                f'{"true" if c0 + c1 <= 32 else "false"}>')
+
     # ------------------------------------------------------------------ backward
     def backward(self, ws, dlogits, P, grads, on_ready=None, zero_bias_grads=True, wgrad_stream=True):
         """Gradient of the last training-mode forward on `ws`.
@@ -680,15 +723,34 @@ class BiDateEngine:
         _lib.PHASE = 'bwd'
         by = {L.name: L for L in self.layers}
         sc = ws.bwd_scratch(dev)
-        td, es = self.tdtype, self.esize
-        e = lambda *s: torch.empty(*s, dtype=td, device=dev)
+        e = lambda *s: torch.empty(*s, dtype=self.tdtype, device=dev)
         ready = on_ready or (lambda keys: None)
         main = torch.cuda.current_stream(dev)
         side = self._side_stream(dev) if wgrad_stream else None
+        keep = []                                    # every temporary lives to the end of the pass: the second queue may still read it
+        n_hand = [0]
 
-        def bn_bwd(L, dA, ldA, n, ipg, fused_rows=0):
-            """BatchNorm+ReLU backward of layer L.  fused_rows > 0: the kernel that produced dA already left the
-            per-tile partial sums (sum g, sum g*z) in ws.stats, fused_rows rows per statistic group."""
+        def handoff(src, dst):
+            """Order what `dst` enqueues from now on behind what `src` has enqueued: a device-local event without the system-scope
+            fence of a default event (streams.HandOff; 6.213 -> 6.187 ms per step in one process), one reusable event per hand-off."""
+            pool = self._handoffs.setdefault(dev.index, [])      # events belong to the device they were created on
+            if n_hand[0] == len(pool):
+                from .streams import HandOff
+                with torch.cuda.device(dev):
+                    pool.append(HandOff())
+            ho = pool[n_hand[0]]
+            n_hand[0] += 1
+            ho.signal(src)
+            ho.wait(dst)
+
+        def bn_bwd_finalize(L, n, ipg, rows):
+            """Sums, dgamma and dbeta of layer L's BatchNorm backward from the `rows` per-tile partial sums per group in ws.stats."""
+            call('bdn_bn_bwd_finalize', ptr(ws.bn[L.name]), n // ipg, L.cout, ptr(ws.stats), rows, 1, ptr(sc['sums']),
+                 ptr(grads[f'{L.bn}.weight']), ptr(grads[f'{L.bn}.bias']), ptr(ws.bnws), st)
+
+        def bn_bwd(L, dA, ldA, n, ipg, fused_rows):
+            """BatchNorm+ReLU backward of layer L: its dz, or None when bf16x3 left it split already.  fused_rows > 0: the kernel that
+            produced dA already left the per-tile partial sums (sum g, sum g*z) in ws.stats, fused_rows rows per statistic group."""
             hk, wk = ws.dims[L.level - 1]
             if fused_rows and self.x3:
                 # bf16x3: dz leaves the pass as the [hi | lo] operand of its two consumers (per-layer buffer: the weight-gradient stream may
@@ -708,14 +770,24 @@ class BiDateEngine:
                      ptr(sc['bnb']), ptr(sc['sums']), ptr(grads[f'{L.bn}.weight']), ptr(grads[f'{L.bn}.bias']), ptr(dz), st)
             return dz
 
-        def fold_dgrad(L, dA, n, ipg, fused_rows, prev=None):
-            """BatchNorm+ReLU backward of layer L applied while its data-gradient conv stages dz (no bn_bwd_apply pass): the partial sums in
-            ws.stats are finalized (sums, dgamma, dbeta), then ONE kernel forms dz on load, convolves it and stores it for the weight
-            gradient.  Returns (dz, dA_prev[, rows])."""
+        def head_bwd(L, rows):
+            """dz of the last layer from dlogits: bdn_outc_bwd left its BatchNorm-backward partial sums and bdn_outc_bn_bwd_apply
+            recomputes dA = round(sum_k dlogits[k] w[k][c]) on the fly (bit-identical dz, 134 MB less footprint).  bf16x3: dz leaves
+            split (None is returned)."""
             hk, wk = ws.dims[L.level - 1]
-            G = n // ipg
-            call('bdn_bn_bwd_finalize', ptr(ws.bn[L.name]), G, L.cout, ptr(ws.stats), fused_rows, 1, ptr(sc['sums']),
-                 ptr(grads[f'{L.bn}.weight']), ptr(grads[f'{L.bn}.bias']), ptr(ws.bnws), st)
+            dz = None if self.x3 else e(B, hk, wk, L.cout)
+            out = ws.split_buf(('d', L.name), B * hk * wk * 2 * L.cout) if self.x3 else dz
+            bn_bwd_finalize(L, B, B, rows)
+            call('bdn_outc_bn_bwd_apply', self.mdt, ptr(dlogits), ptr(P['outc.conv.weight']), ptr(ws.z[L.name]),
+                 ptr(ws.bn[L.name]), B, ptr(sc['sums']), ptr(out), B, hk, wk, L.cout, self.n_classes, st)
+            return dz
+
+        def fold_dgrad(L, dA, n, ipg, rows, prev):
+            """BatchNorm+ReLU backward of layer L applied while its data-gradient conv stages dz (no bn_bwd pass): the partial sums in
+            ws.stats are finalized (sums, dgamma, dbeta), then ONE kernel forms dz on load, convolves it and stores it for the weight
+            gradient.  Returns (dz, gradient on L's input, rows as dgrad())."""
+            hk, wk = ws.dims[L.level - 1]
+            bn_bwd_finalize(L, n, ipg, rows)
             _, wd = self._weights(L, P, True)
             dz, out = e(n, hk, wk, L.cout), e(n, hk, wk, L.cin)
             has = prev is not None
@@ -723,131 +795,124 @@ class BiDateEngine:
                              self.mdt, dA, L.cout, ptr(ws.z[L.name]), ptr(ws.bn[L.name]), ptr(sc['sums']), ipg, ptr(wd), ptr(out),
                              ptr(ws.z[prev.name]) if has else None, ptr(ws.bn[prev.name]) if has else None, ptr(ws.stats) if has else None,
                              ptr(dz), n, hk, wk, L.cin, st, fn='bdn_conv3x3_dgrad_bb', bb=True)
-            if has:
-                return dz, out, self.mtiles(n, hk, wk, L.cout, L.cin, ipg) // G
-            return dz, out
+            return dz, out, self.mtiles(n, hk, wk, L.cout, L.cin, ipg) // (n // ipg) if has else 0
 
-        def wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, stp, role='wgrad'):
-            """The weight-gradient GEMM and its reduction, its partial tiles in the role's scratch (Workspace.wgrad_scratch); with
-            profiling on, the GEMM alone sits between two events recorded on the stream it is launched on (bf16x3: not timed)."""
+        def dgrad(L, dz, n, ipg, prev):
+            """Data gradient of layer L's conv: (gradient on its input, rows).  prev = the layer whose relu(bn(z)) is this conv's input:
+            its BatchNorm-backward partial sums are then produced by the epilogue, `rows` rows per statistic group (else rows = 0)."""
+            hk, wk = ws.dims[L.level - 1]
+            _, wd = self._weights(L, P, True)
+            out = e(n, hk, wk, L.cin)
             if self.x3:
-                # both operands were split already: the activations by this layer's forward, dz by split_dz() on the chain's stream
-                # (per-layer buffers: the weight-gradient stream may still read one while the chain splits the next layer's)
-                sd = ws.split_buf(('d', L.name), n * hk * wk * 2 * L.cout)
-                sw = ws.split_buf(('a', L.name), n * hk * wk * 2 * (c0 + c1))
-                blk_ = self.x3_tail_wgrad_blocks if (L.name == 'e1b' and self.x3_tail_wgrad_blocks and self.x3_bwd_terms == 3) else self.wgrad_blocks
-                flg = wg_flags(1 if self._diag_skip_reduce else 3, 0, blk_)      # (_diag_skip_reduce: timing diagnostics only)
-                xdt = BDN_BF16X2 if self.x3_bwd_terms == 2 else BDN_BF16X3
-                part = ws.wgrad_scratch(role, 'bdn_wgrad_workspace_bytes_ex', xdt, n, hk, wk, L.cout, c0 + c1, 0, ipg, IN_PLAIN, flg)
-                call('bdn_conv3x3_wgrad_ex', xdt, ptr(sd), L.cout, ptr(sw), c0 + c1, None, 0, IN_PLAIN, None, ipg,
-                     ptr(part), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk, flg, stp)
-                return
-            wk_, blk_ = self.wgrad_kernel, self.wgrad_blocks
-            flg = wg_flags(1 if self._diag_skip_reduce else 3, wk_, blk_)
-            part = ws.wgrad_scratch(role, 'bdn_wgrad_workspace_bytes_ex', self.dt, n, hk, wk, L.cout, c0, c1, ipg, mode, flg)
-            args = (self.dt, ptr(dz), L.cout, ptr(in0), c0, ptr(in1), c1, mode, ptr(in_bn), ipg,
-                    ptr(part), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk)
-
-            def name():
-                v = _lib.load().bdn_conv3x3_wgrad_variant(self.dt, n, hk, wk, L.cout, c0, c1, ipg, mode, wg_flags(3, wk_, blk_))
-                if v == WG_ROLE:
-                    return f'wgrad7_kernel<{"true" if mode == IN_BNRELU else "false"}>'
-                small = wk <= 8 and hk <= 8 and ipg % 2 == 0
-                return (f'wgrad_kernel<{"bf16" if self.precision == "bf16" else "f32"},8,{"8,2" if small else "16,1"},'
-                        f'{"true" if c0 + c1 <= 32 else "false"}>')
-            self._timed(name, 2.0 * n * hk * wk * L.cout * 9 * (c0 + c1), 'bdn_conv3x3_wgrad_ex', *args, flg, stp,
-                        split=(('bdn_conv3x3_wgrad_ex', *args, wg_flags(1, wk_, blk_), stp),
-                               ('bdn_conv3x3_wgrad_ex', *args, wg_flags(2, wk_, blk_), stp)))
-
-        n_hand = [0]
-
-        def handoff(src, dst):
-            """Order what `dst` enqueues from now on behind what `src` has enqueued: a device-local event without the system-scope
-            fence of a default event (streams.HandOff; 6.213 -> 6.187 ms per step in one process), one reusable event per hand-off."""
-            pool = self._handoffs.setdefault(dev.index, [])      # events belong to the device they were created on
-            if n_hand[0] == len(pool):
-                from .streams import HandOff
-                with torch.cuda.device(dev):
-                    pool.append(HandOff())
-            ho = pool[n_hand[0]]
-            n_hand[0] += 1
-            if self._diag_skip_handoff:
-                return
-            ho.signal(src)
-            ho.wait(dst)
+                dz = ws.split_buf(('d', L.name), n * hk * wk * 2 * L.cout)     # left split by bn_bwd / head_bwd / split_dz
+            if prev is None:
+                self._timed_conv(n, hk, wk, L.cout, 0, L.cin, ipg,
+                                 self.bwd_dtype, ptr(dz), L.cout, None, 0, IN_PLAIN, None, ipg,
+                                 ptr(wd), None, ptr(out), None, n, hk, wk, L.cin, st)
+                return out, 0
+            self._timed_conv(n, hk, wk, L.cout, 0, L.cin, ipg,
+                             self.bwd_dtype, ptr(dz), L.cout, ptr(wd), ptr(out), ptr(ws.z[prev.name]), ptr(ws.bn[prev.name]),
+                             ipg, ptr(ws.stats), n, hk, wk, L.cin, st, fn='bdn_conv3x3_dgrad_bs')
+            return out, self.mtiles(n, hk, wk, L.cout, L.cin, ipg) // (n // ipg)
 
         def split_dz(L, dz, n, ipg):
             """bf16x3: the [hi | lo] split of layer L's dz, once, for its data-gradient conv AND its weight-gradient GEMM."""
             hk, wk = ws.dims[L.level - 1]
             sp = ws.split_buf(('d', L.name), n * hk * wk * 2 * L.cout)
             call('bdn_split_pack', ptr(dz), L.cout, None, 0, IN_PLAIN, None, ipg, ptr(sp), n, hk, wk, st)
-            return sp
 
-        def wgrad(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, on_main=False):
-            if self.x3 and dz is not None:
-                split_dz(L, dz, n, ipg)              # on the chain's stream, before the hand-off below (bn_bwd already left the split otherwise)
-            if self._diag_skip_wgrad:                # tools/ab_step.py diagnostic only: how long is the dz chain alone?
-                return
+        def wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, stp, role):
+            """The weight-gradient GEMM and its reduction, its partial tiles in the role's scratch (Workspace.wgrad_scratch); with
+            profiling on, the GEMM alone sits between two events recorded on the stream it is launched on (bf16x3: not timed)."""
             hk, wk = ws.dims[L.level - 1]
-            keys = [f'{L.bn}.weight', f'{L.bn}.bias', f'{L.conv}.weight', f'{L.conv}.bias']
-            if on_main and side is not None:
-                # the LAST weight gradient of the pass (the first convolution's) on the chain's own stream: nothing of the chain is left to
-                # run and the second queue is still busy with the layer before it -- the two GEMMs run side by side instead of one behind
-                # the other (bf16x3: 0.36 ms behind a 1.3 ms GEMM at the end of the step).  The chain then joins the second queue: the
-                # bucket this ready() may release holds gradients whose GEMMs are still queued there.
-                wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, st, role='chain')
-                if zero_bias_grads:
-                    grads[f'{L.conv}.bias'].zero_()
-                handoff(side, main)
-                ready(keys)
-                return
-            if side is None:
-                wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, st)
-                if zero_bias_grads:                  # feeds a BatchNorm: gradient is identically zero
-                    grads[f'{L.conv}.bias'].zero_()
-                ready(keys)
-                return
-            handoff(main, side)                      # dz, the BatchNorm gradients and everything before them
-            with torch.cuda.stream(side):
-                wgrad_call(L, dz, in0, c0, in1, c1, mode, in_bn, n, ipg, hk, wk, side.cuda_stream)
-                if zero_bias_grads:
-                    grads[f'{L.conv}.bias'].zero_()
-                ready(keys)                          # a bucket all-reduce launched here is ordered behind this wgrad
-
-        def dgrad(L, dz, n, ipg, prev=None):
-            """Data gradient of layer L's conv.  prev = the layer whose relu(bn(z)) is this conv's input: its
-            BatchNorm-backward partial sums are then produced by the epilogue (returns rows per statistic group)."""
-            hk, wk = ws.dims[L.level - 1]
-            _, wd = self._weights(L, P, True)
-            out = e(n, hk, wk, L.cin)
             if self.x3:
-                dz = ws.split_buf(('d', L.name), n * hk * wk * 2 * L.cout)     # written by split_dz() when this layer's wgrad was released
-            ddt = BDN_BF16X2 if (self.x3 and self.x3_bwd_terms == 2) else self.mdt
-            if prev is None:
-                self._timed_conv(n, hk, wk, L.cout, 0, L.cin, ipg,
-                                 ddt, ptr(dz), L.cout, None, 0, IN_PLAIN, None, ipg,
-                                 ptr(wd), None, ptr(out), None, n, hk, wk, L.cin, st)
-                return out
-            self._timed_conv(n, hk, wk, L.cout, 0, L.cin, ipg,
-                             ddt, ptr(dz), L.cout, ptr(wd), ptr(out), ptr(ws.z[prev.name]), ptr(ws.bn[prev.name]),
-                             ipg, ptr(ws.stats), n, hk, wk, L.cin, st, fn='bdn_conv3x3_dgrad_bs')
-            rows = self.mtiles(n, hk, wk, L.cout, L.cin, ipg) // (n // ipg)
-            return out, rows
+                # both operands were split already: the activations by this layer's forward, dz on the chain's stream (per-layer
+                # buffers: the weight-gradient stream may still read one while the chain splits the next layer's)
+                dz = ws.split_buf(('d', L.name), n * hk * wk * 2 * L.cout)
+                in0, in1, in_bn = ws.split_buf(('a', L.name), n * hk * wk * 2 * (c0 + c1)), None, None
+            dt, c0, c1, mode, flg = self.wgrad_launch(L, c0, c1, mode)
+            part = ws.wgrad_scratch(role, 'bdn_wgrad_workspace_bytes_ex', dt, n, hk, wk, L.cout, c0, c1, ipg, mode, flg)
+            args = (dt, ptr(dz), L.cout, ptr(in0), c0, ptr(in1), c1, mode, ptr(in_bn), ipg,
+                    ptr(part), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk)
+            if self.x3:
+                call('bdn_conv3x3_wgrad_ex', *args, flg, stp)
+                return
+            ph = flg & ~3                            # the flags word without its phase bits
+            self._timed(lambda: self.wgrad_gemm_name(dt, n, hk, wk, L.cout, c0, c1, ipg, mode, ph | 3),
+                        2.0 * n * hk * wk * L.cout * 9 * (c0 + c1), 'bdn_conv3x3_wgrad_ex', *args, flg, stp,
+                        split=(('bdn_conv3x3_wgrad_ex', *args, ph | 1, stp), ('bdn_conv3x3_wgrad_ex', *args, ph | 2, stp)))
 
-        # ---- classifier: its data gradient is never stored -- bdn_outc_bwd leaves the BatchNorm-backward partial sums of d4b, and
-        # d4b's BatchNorm backward recomputes dA = round(sum_k dlogits[k] w[k][c]) (bit-identical dz, 134 MB less footprint)
+        def release(L, launch, last):
+            """Enqueue layer L's weight gradient, launch(stream, scratch role), zero its conv-bias gradient (it feeds a BatchNorm: the
+            gradient is identically zero) and report the layer's gradients ready.  Normally on the weight-gradient stream, behind a
+            hand-off of dz, the BatchNorm gradients and everything before them.  The LAST weight gradient of the pass (the first
+            convolution's) runs on the chain's own stream: nothing of the chain is left to run and the second queue is still busy with the
+            layer before it, so the two GEMMs run side by side instead of one behind the other (bf16x3: 0.36 ms behind a 1.3 ms GEMM at
+            the end of the step).  The chain then joins the second queue: the bucket this ready() may release holds gradients whose GEMMs
+            are still queued there.  Without a second stream everything runs on the chain's."""
+            keys = [f'{L.bn}.weight', f'{L.bn}.bias', f'{L.conv}.weight', f'{L.conv}.bias']
+            if side is not None and not last:
+                handoff(main, side)
+                with torch.cuda.stream(side):
+                    launch(side.cuda_stream, 'wgrad')
+                    if zero_bias_grads:
+                        grads[f'{L.conv}.bias'].zero_()
+                    ready(keys)                      # a bucket all-reduce launched here is ordered behind this wgrad
+                return
+            launch(st, 'chain' if side is not None else 'wgrad')
+            if zero_bias_grads:
+                grads[f'{L.conv}.bias'].zero_()
+            if side is not None:
+                handoff(side, main)
+            ready(keys)
+
+        def layer(L, n, dA, ldA, rows, operand, prev=None):
+            """Backward of conv layer L (n images, B per statistic group): its dz, the release of its weight gradient, its data gradient.
+            dA (pointer, leading dimension ldA): the gradient on relu(bn(z)) of L; rows: rows per statistic group of the BatchNorm-backward
+            partial sums its producer left in ws.stats (0: none).  dA None: the last layer, whose dz comes from the classifier's backward.
+            operand = (in0, c0, in1, c1, mode, in_bn): the weight gradient's input operand; prev as in dgrad().  Returns (gradient on
+            L's input, rows of prev's partial sums); (None, 0) for the first layer, which has no data gradient."""
+            hk, wk = ws.dims[L.level - 1]
+            first = L is self.layers[0]
+            fdt = self.first_wgrad_dtype(n, hk, wk, B) if first else None
+            if fdt is not None:
+                # the first conv's dz has one reader, so its BatchNorm backward is applied inside the weight-gradient GEMM's staging and
+                # the largest tensor of the step is never written.  bf16x3: float32 dA and z, the kernel splits dz into bf16 hi + lo in
+                # its staging and takes the input's split operand the forward left
+                bn_bwd_finalize(L, n, B, rows)
+                fin = ws.split_buf(('a', L.name), n * hk * wk * 2 * L.cin) if self.x3 else ws.x0
+
+                def launch(stp, role):               # always on the chain's stream (last=True): the 'chain' scratch
+                    part = ws.wgrad_scratch('chain', 'bdn_wgrad_workspace_bytes', n, hk, wk, L.cout, L.cin, B)
+                    self._timed(lambda: 'wgrad_first_kernel', 2.0 * n * hk * wk * L.cout * 9 * L.cin, 'bdn_conv3x3_wgrad_bnbwd',
+                                fdt, dA, L.cout, ptr(ws.z[L.name]), ptr(ws.bn[L.name]), ptr(sc['sums']), B, L.cout,
+                                ptr(fin), L.cin, ptr(part), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk, stp)
+                release(L, launch, last=True)
+                return None, 0
+            out, rows_out = None, 0
+            if dA is None:
+                dz = head_bwd(L, rows)
+            elif rows and self.folds_bn_bwd(L, hk, wk):      # folding finalizes the producer's partial sums: they must exist
+                dz, out, rows_out = fold_dgrad(L, dA, n, B, rows, prev)
+            else:
+                dz = bn_bwd(L, dA, ldA, n, B, rows)
+            if self.x3 and dz is not None:
+                split_dz(L, dz, n, B)                # on the chain's stream, before the hand-off of the release
+            release(L, lambda stp, role: wgrad_call(L, dz, *operand, n, B, stp, role), last=first)
+            if out is None and not first:
+                out, rows_out = dgrad(L, dz, n, B, prev)
+            keep.extend((dz, out))
+            return out, rows_out
+
+        # ---- classifier: its data gradient is never stored -- bdn_outc_bwd leaves the BatchNorm-backward partial sums of d4b
         L4b = by['d4b']
         call('bdn_outc_bwd', self.dt, ptr(dlogits), ptr(ws.z['d4b']), ptr(ws.bn['d4b']), ptr(P['outc.conv.weight']),
              None, ptr(grads['outc.conv.weight']), ptr(grads['outc.conv.bias']), ptr(ws.stats),
              ptr(ws.outc_ws(self)), B, H, W, L4b.cout, self.n_classes, st)
-        rows_head = _lib.load().bdn_outc_bwd_rows(self.dt, B, H, W, L4b.cout)
         ready(['outc.conv.weight', 'outc.conv.bias'])
-        # ---- decoder
-        dA_ptr, ldA, rows_up = None, 0, 0
-        fold = set(self.fold_bn_bwd) if (self.mdt == BDN_BF16) else set()
-        keep = []
+        # ---- decoder: d_j b on the gradient upsample2x_bwd(_bs) leaves (j = 4: on the classifier's), d_j a on d_j b's data gradient
+        dA, ldA, rows = None, 0, _lib.load().bdn_outc_bwd_rows(self.dt, B, H, W, L4b.cout)
         dcat = {}
-        dF5 = None
         for j in range(4, 0, -1):
             k = 5 - j
             hk, wk = ws.dims[k - 1]
@@ -855,107 +920,37 @@ class BiDateEngine:
             La, Lb = by[f'd{j}a'], by[f'd{j}b']
             ck = ENC_CH[k - 1]
             cprev = La.cin - ck
-            folded_b = False
-            if j == 4:
-                # bf16x3: dz leaves the pass as the [hi | lo] operand of its two consumers (no float32 dz, no split pass over it)
-                dzb = None if self.x3 else e(B, hk, wk, Lb.cout)
-                dz_out = ws.split_buf(('d', Lb.name), B * hk * wk * 2 * Lb.cout) if self.x3 else dzb
-                call('bdn_bn_bwd_finalize', ptr(ws.bn[Lb.name]), 1, Lb.cout, ptr(ws.stats), rows_head, 1, ptr(sc['sums']),
-                     ptr(grads[f'{Lb.bn}.weight']), ptr(grads[f'{Lb.bn}.bias']), ptr(ws.bnws), st)
-                call('bdn_outc_bn_bwd_apply', self.mdt if self.x3 else self.dt, ptr(dlogits), ptr(P['outc.conv.weight']), ptr(ws.z[Lb.name]),
-                     ptr(ws.bn[Lb.name]), B, ptr(sc['sums']), ptr(dz_out), B, hk, wk, Lb.cout, self.n_classes, st)
-            elif Lb.name in fold and rows_up and ldA == Lb.cout == 64 and min(hk, wk) > 8:
-                dzb, dAa, rows = fold_dgrad(Lb, dA_ptr, B, B, rows_up, prev=La)
-                folded_b = True
-            else:
-                dzb = bn_bwd(Lb, dA_ptr, ldA, B, B, fused_rows=rows_up)     # dA came from upsample2x_bwd(_bs)
-            wgrad(Lb, dzb, ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name], B, B)
-            if not folded_b:
-                dAa, rows = dgrad(Lb, dzb, B, B, prev=La)
-            if La.name in fold and La.cout == 64 and min(hk, wk) > 8:     # (bdn_conv3x3_dgrad_bb refuses maps of 8x8 and below)
-                dza, dc = fold_dgrad(La, ptr(dAa), B, B, rows)
-                wgrad(La, dza, ws.f[k], ck, ws.U[j], cprev, IN_PLAIN, None, B, B)
-            else:
-                dza = bn_bwd(La, ptr(dAa), La.cout, B, B, fused_rows=rows)
-                # bf16x3: the operand is the split buffer the forward left (('a', layer)); the float32 skip / upsampled map do not exist
-                wgrad(La, dza, None if self.x3 else ws.f[k], ck, None if self.x3 else ws.U[j], cprev, IN_PLAIN, None, B, B)
-                dc = dgrad(La, dza, B, B)                   # [B,hk,wk, ck + cprev] = [dF_k | dU_j]
-            dcat[k] = dc
+            dAa, rows = layer(Lb, B, dA, ldA, rows, (ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name]), prev=La)
+            # bf16x3: the operand is the split buffer the forward left (('a', layer)); the float32 skip / upsampled map do not exist
+            dc, _ = layer(La, B, ptr(dAa), La.cout, rows, (None if self.x3 else ws.f[k], ck, None if self.x3 else ws.U[j], cprev, IN_PLAIN, None))
+            dcat[k] = dc                             # [B,hk,wk, ck + cprev] = [dF_k | dU_j]
             dprev = e(B, hs, wsrc, cprev)
-            rows_up = _lib.load().bdn_upsample2x_bwd_rows(self.dt, B, hs, wsrc, cprev) if (j > 1 and FUSE_UPS_BS) else 0
-            if rows_up:
+            keep.append(dprev)
+            rows = _lib.load().bdn_upsample2x_bwd_rows(self.dt, B, hs, wsrc, cprev) if j > 1 else 0
+            if rows:
                 # the gradient lands on relu(bn(z)) of the previous decoder stage: its BatchNorm-backward partial sums come out of the same pass
                 Lp = by[f'd{j - 1}b']
-                call('bdn_upsample2x_bwd_bs', self.dt, dc.data_ptr() + ck * es, La.cin, ptr(dprev), ptr(ws.z[Lp.name]), ptr(ws.bn[Lp.name]),
-                     ptr(ws.stats), B, hs, wsrc, hk, wk, cprev, st)
+                call('bdn_upsample2x_bwd_bs', self.dt, dc.data_ptr() + ck * self.esize, La.cin, ptr(dprev), ptr(ws.z[Lp.name]),
+                     ptr(ws.bn[Lp.name]), ptr(ws.stats), B, hs, wsrc, hk, wk, cprev, st)
             else:
-                call('bdn_upsample2x_bwd', self.dt, dc.data_ptr() + ck * es, La.cin, ptr(dprev), B, hs, wsrc, hk, wk, cprev, st)
-            keep += [dzb, dAa, dza, dprev]
-            if j > 1:
-                dA_ptr, ldA = ptr(dprev), cprev
-            else:
-                dF5 = dprev
-        # ---- encoder (both dates at once)
-        dP = None
+                call('bdn_upsample2x_bwd', self.dt, dc.data_ptr() + ck * self.esize, La.cin, ptr(dprev), B, hs, wsrc, hk, wk, cprev, st)
+            dA, ldA = ptr(dprev), cprev
+        # ---- encoder (both dates at once): e_k b on the gradient enc_skip_bwd leaves, e_k a on e_k b's data gradient
+        dF, dP = dprev, None
         for k in range(5, 0, -1):
             hk, wk = ws.dims[k - 1]
             La, Lb = by[f'e{k}a'], by[f'e{k}b']
             ck = ENC_CH[k - 1]
-            if k == 5:
-                dF_ptr, ldF = ptr(dF5), ck
-            else:
-                dF_ptr, ldF = ptr(dcat[k]), dcat[k].shape[3]
-            rows_b = _lib.load().bdn_enc_skip_bwd_rows(self.dt, B, hk, wk, ck)
+            if k < 5:
+                dF = dcat[k]
             dAb = e(2 * B, hk, wk, ck)
-            call('bdn_enc_skip_bwd', self.dt, dF_ptr, ldF, ptr(ws.z[Lb.name]), ptr(ws.bn[Lb.name]),
+            keep.append(dAb)
+            call('bdn_enc_skip_bwd', self.dt, ptr(dF), dF.shape[3], ptr(ws.z[Lb.name]), ptr(ws.bn[Lb.name]),
                  ptr(dP), ptr(dAb), ptr(ws.stats), B, hk, wk, ck, st)
-            if Lb.name in fold and min(hk, wk) > 8 and Lb.cout == 64:
-                dzb, dAa, rows = fold_dgrad(Lb, ptr(dAb), 2 * B, B, rows_b, prev=La)
-                wgrad(Lb, dzb, ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name], 2 * B, B)
-            else:
-                dzb = bn_bwd(Lb, ptr(dAb), ck, 2 * B, B, fused_rows=rows_b)
-                wgrad(Lb, dzb, ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name], 2 * B, B)
-                dAa, rows = dgrad(Lb, dzb, 2 * B, B, prev=La)
-            if k == 1 and self.first_wgrad_fused and _lib.load().bdn_conv3x3_wgrad_bnbwd_supported(self.mdt, 2 * B, hk, wk, La.cout, La.cin, B):
-                # the first conv has no data gradient: its dz has one reader, so the BatchNorm backward is applied inside
-                # that weight-gradient GEMM's staging and the largest tensor of the step is never written (on the main
-                # stream: nothing of the chain is left to run, the side stream is still busy with e1b's GEMM).
-                # bf16x3 (round 6): float32 dA and z, the kernel splits dz into bf16 hi + lo in its staging and takes the input's split
-                # operand the forward left; terms of the split product as engine.x3_bwd_terms
-                call('bdn_bn_bwd_finalize', ptr(ws.bn[La.name]), 2, La.cout, ptr(ws.stats), rows, 1, ptr(sc['sums']),
-                     ptr(grads[f'{La.bn}.weight']), ptr(grads[f'{La.bn}.bias']), ptr(ws.bnws), st)
-                if self.x3:
-                    fdt = BDN_BF16X2 if self.x3_bwd_terms == 2 else BDN_BF16X3
-                    fin = ws.split_buf(('a', La.name), 2 * B * hk * wk * 2 * La.cin)
-                else:
-                    fdt, fin = self.dt, ws.x0
-                if not self._diag_skip_wgrad:
-                    part = ws.wgrad_scratch('chain', 'bdn_wgrad_workspace_bytes', 2 * B, hk, wk, La.cout, La.cin, B)
-                    self._timed(lambda: 'wgrad_first_kernel', 2.0 * 2 * B * hk * wk * La.cout * 9 * La.cin, 'bdn_conv3x3_wgrad_bnbwd',
-                                fdt, ptr(dAa), La.cout, ptr(ws.z[La.name]), ptr(ws.bn[La.name]), ptr(sc['sums']), B, La.cout,
-                                ptr(fin), La.cin, ptr(part), ptr(grads[f'{La.conv}.weight']), La.cin_real, 2 * B, hk, wk, st)
-                if zero_bias_grads:
-                    grads[f'{La.conv}.bias'].zero_()
-                if side is not None:
-                    # this ready() may launch the LAST bucket's all-reduce, ordered behind the current (main) stream only;
-                    # the bucket also holds e1b / e2a weight gradients whose GEMM + reduction are still queued on the side
-                    # stream, so main joins side first (nothing of the chain is left to delay)
-                    handoff(side, main)
-                ready([f'{La.bn}.weight', f'{La.bn}.bias', f'{La.conv}.weight', f'{La.conv}.bias'])
-                keep += [dAb, dzb, dAa, dP]
-                dP = None
-                continue
+            dAa, rows = layer(Lb, 2 * B, ptr(dAb), ck, _lib.load().bdn_enc_skip_bwd_rows(self.dt, B, hk, wk, ck),
+                              (ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name]), prev=La)
             src = ws.x0 if k == 1 else (None if self.x3 else ws.pool[k])
-            if La.name in fold and k > 1 and min(hk, wk) > 8 and La.cout == 64:
-                dza, dP_new = fold_dgrad(La, ptr(dAa), 2 * B, B, rows)
-                wgrad(La, dza, src, La.cin, None, 0, IN_PLAIN, None, 2 * B, B)
-                keep += [dAb, dzb, dAa, dza, dP]
-                dP = dP_new
-                continue
-            dza = bn_bwd(La, ptr(dAa), La.cout, 2 * B, B, fused_rows=rows)
-            wgrad(La, dza, src, La.cin, None, 0, IN_PLAIN, None, 2 * B, B, on_main=(k == 1 and self.last_wgrad_on_chain))
-            keep += [dAb, dzb, dAa, dza, dP]
-            dP = dgrad(La, dza, 2 * B, B) if k > 1 else None
+            dP, _ = layer(La, 2 * B, ptr(dAa), La.cout, rows, (src, La.cin, None, 0, IN_PLAIN, None))
         if side is not None:
             handoff(side, main)                      # every weight gradient is complete before the caller's next kernel
         return grads

@@ -13,7 +13,8 @@ Shapes are ragged (H % 8 != 0, W % 16 != 0) wherever the plan allows it.  A plai
 from collections import namedtuple
 
 from fabric_amd import _lib
-from fabric_amd._lib import (BDN_BF16, BDN_BF16X2, BDN_BF16X3, BDN_F32, EVAL_CLS, EVAL_PAIR, EVAL_STAGE, IN_BNRELU, IN_PLAIN, WG_ROLE,
+from fabric_amd.engine import BiDateEngine
+from fabric_amd._lib import (BDN_BF16, BDN_BF16X2, BDN_BF16X3, BDN_F32, EVAL_CLS, EVAL_PAIR, EVAL_STAGE, IN_BNRELU, IN_PLAIN,
                              wg_flags)
 
 DTYPE = {'fp32': BDN_F32, 'bf16': BDN_BF16, 'bf16x3': BDN_BF16X3, 'bf16x2': BDN_BF16X2}
@@ -202,27 +203,16 @@ def _splits(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags):
 
 
 def wgrad_inst(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags=wg_flags()):
-    """(GEMM instantiation, split lanes of its reduction) of bdn_conv3x3_wgrad_ex.  The family comes from bdn_conv3x3_wgrad_variant and the
-    split count from the plan's workspace size (both the library's own answers); the tile geometry of the one-chunk-at-a-time kernel and the
-    bf16x3 fused / doubled-operand choice are HAND COPIES of pick_tile (common.hpp) and bdn_conv3x3_wgrad_ex, unchecked against the C code
-    like _reduce_lanes."""
-    lib = _lib.load()
-    small = H <= 8 and W <= 8 and ipg % 2 == 0
+    """(GEMM instantiation, split lanes of its reduction) of bdn_conv3x3_wgrad_ex.  The GEMM is the engine's answer
+    (BiDateEngine.wgrad_gemm_name), the split count comes from the plan's workspace size (the library's own answer)."""
+    g = BiDateEngine.wgrad_gemm_name(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
     if dtype in (BDN_BF16X3, BDN_BF16X2):
-        terms = 3 if dtype == BDN_BF16X3 else 2
-        if Cout % 64 == 0 and C0 % 64 == 0 and \
-                lib.bdn_conv3x3_wgrad_variant(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, flags) == WG_ROLE:
-            return f'wgrad7x_kernel<{terms}>', _reduce_lanes(_splits(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, flags), Cout * C0)
+        if not g.endswith('+wgrad_x3_combine_kernel'):
+            return g, _reduce_lanes(_splits(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, flags), Cout * C0)
         # the doubled operands through the bf16 GEMM (internal plan flags: the lo x lo quadrant left out), then the quadrant sum
-        xfl = (1 << 30) | ((1 << 29) if terms == 2 else 0)
-        g, lanes = wgrad_inst(BDN_BF16, N, H, W, 2 * Cout, 2 * C0, 0, ipg, IN_PLAIN, flags | xfl)
-        return f'{g}+wgrad_x3_combine_kernel', lanes
-    v = lib.bdn_conv3x3_wgrad_variant(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
+        xfl = (1 << 30) | ((1 << 29) if dtype == BDN_BF16X2 else 0)
+        return g, wgrad_inst(BDN_BF16, N, H, W, 2 * Cout, 2 * C0, 0, ipg, IN_PLAIN, flags | xfl)[1]
     ks = C0 + C1 <= 32
-    if v == WG_ROLE:
-        g = f'wgrad7_kernel<{"true" if mode == IN_BNRELU else "false"}>'
-    else:
-        g = f'wgrad_kernel<{"bf16" if dtype == BDN_BF16 else "f32"},8,{"8,2" if small else "16,1"},{"true" if ks else "false"}>'
     S = _splits(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
     return g, _reduce_lanes(S * (2 if ks else 1), Cout * (C0 + C1))
 
@@ -305,8 +295,8 @@ MFMA_ENTRY_POINTS = ('bdn_conv3x3', 'bdn_conv3x3_dgrad_bs', 'bdn_conv3x3_dgrad_b
 
 def train_step_instantiations(precision, B=64, S=128, n_channels=13):
     """The instantiations of one training step (forward + backward) of BiDateNet(n_channels, 2) at batch B on S x S patches with the
-    engine's default settings, layer by layer as fabric_amd/engine.py launches them."""
-    from fabric_amd.engine import BiDateEngine, ENC_CH
+    engine's default settings, layer by layer as fabric_amd/engine.py launches them; every backward decision is the engine's own."""
+    from fabric_amd.engine import ENC_CH
     eng = BiDateEngine(n_channels, 2, precision)
     by = _layers(n_channels)
     dims = [(S >> k, S >> k) for k in range(5)]
@@ -334,66 +324,36 @@ def train_step_instantiations(precision, B=64, S=128, n_channels=13):
         fwd(by[f'd{j}a'], B, True)
         fwd(by[f'd{j}b'], B, False)
 
-    ddt = BDN_BF16X2 if (x3 and eng.x3_bwd_terms == 2) else mdt
-    fold = set(eng.fold_bn_bwd) if mdt == BDN_BF16 else set()
-
-    def wgrad(L, n, c0, c1, mode):
+    def layer(L, n, c0, c1, mode):            # the engine's per-layer backward: dz (maybe folded into the data gradient), wgrad, dgrad
         h, w = dims[L.level - 1]
-        if x3:
-            blk = eng.x3_tail_wgrad_blocks if (L.name == 'e1b' and eng.x3_tail_wgrad_blocks and eng.x3_bwd_terms == 3) else eng.wgrad_blocks
-            xdt = BDN_BF16X2 if eng.x3_bwd_terms == 2 else BDN_BF16X3
-            g, sl = wgrad_inst(xdt, n, h, w, L.cout, c0 + c1, 0, B, IN_PLAIN, wg_flags(3, 0, blk))
-        else:
-            g, sl = wgrad_inst(dt, n, h, w, L.cout, c0, c1, B, mode, wg_flags(3, eng.wgrad_kernel, eng.wgrad_blocks))
+        if L.name == 'e1a':
+            fdt = eng.first_wgrad_dtype(n, h, w, B)
+            if fdt is not None:
+                g, sl = wgrad_bnbwd_inst(fdt, n, h, w, L.cout, L.cin, B)
+                add([g, f'wgrad_reduce_kernel<{sl}>'])
+                return
+        wdt, wc0, wc1, wmode, flg = eng.wgrad_launch(L, c0, c1, mode)
+        g, sl = wgrad_inst(wdt, n, h, w, L.cout, wc0, wc1, B, wmode, flg)
         add(g.split('+') + [f'wgrad_reduce_kernel<{sl}>'])
-
-    def dgrad(L, n):                          # plain and with fused statistics: the same dispatcher
-        h, w = dims[L.level - 1]
-        add([conv_inst(ddt, n, h, w, L.cout, 0, L.cin, B)])
-
-    def folded(L, n):
-        h, w = dims[L.level - 1]
-        return L.name in fold and L.cout == 64 and min(h, w) > 8
+        if eng.folds_bn_bwd(L, h, w):
+            add([bb_inst(n, h, w, L.cin, B)])
+        elif L.name != 'e1a':                 # plain and with fused statistics: the same dispatcher
+            add([conv_inst(eng.bwd_dtype, n, h, w, L.cout, 0, L.cin, B)])
 
     for j in range(4, 0, -1):
-        k = 5 - j
         La, Lb = by[f'd{j}a'], by[f'd{j}b']
-        ck = ENC_CH[k - 1]
-        h, w = dims[k - 1]
-        wgrad(Lb, B, Lb.cin, 0, IN_BNRELU)
-        if folded(Lb, B):
-            add([bb_inst(B, h, w, Lb.cin, B)])
-        else:
-            dgrad(Lb, B)
-        if folded(La, B):
-            add([bb_inst(B, h, w, La.cin, B)])
-        else:
-            dgrad(La, B)
-        wgrad(La, B, ck, La.cin - ck, IN_PLAIN)
+        ck = ENC_CH[La.level - 1]
+        layer(Lb, B, Lb.cin, 0, IN_BNRELU)
+        layer(La, B, ck, La.cin - ck, IN_PLAIN)
     for k in range(5, 0, -1):
-        La, Lb = by[f'e{k}a'], by[f'e{k}b']
-        h, w = dims[k - 1]
-        if folded(Lb, 2 * B):
-            add([bb_inst(2 * B, h, w, Lb.cin, B)])
-        else:
-            dgrad(Lb, 2 * B)
-        wgrad(Lb, 2 * B, Lb.cin, 0, IN_BNRELU)
-        if k == 1 and eng.first_wgrad_fused and _lib.load().bdn_conv3x3_wgrad_bnbwd_supported(mdt, 2 * B, h, w, La.cout, La.cin, B):
-            fdt = (BDN_BF16X2 if eng.x3_bwd_terms == 2 else BDN_BF16X3) if x3 else dt
-            g, sl = wgrad_bnbwd_inst(fdt, 2 * B, h, w, La.cout, La.cin, B)
-            add([g, f'wgrad_reduce_kernel<{sl}>'])
-            continue
-        if folded(La, 2 * B) and k > 1:
-            add([bb_inst(2 * B, h, w, La.cin, B)])
-        elif k > 1:
-            dgrad(La, 2 * B)
-        wgrad(La, 2 * B, La.cin, 0, IN_PLAIN)
+        layer(by[f'e{k}b'], 2 * B, by[f'e{k}b'].cin, 0, IN_BNRELU)
+        layer(by[f'e{k}a'], 2 * B, by[f'e{k}a'].cin, 0, IN_PLAIN)
     return out
 
 
 def eval_forward_instantiations(precision, B, S=128, n_channels=13):
     """The instantiations of one eval-mode forward (the eval-shaped schedule of bf16 / fp32, fabric_amd/engine.py _forward_eval)."""
-    from fabric_amd.engine import BiDateEngine, ENC_CH
+    from fabric_amd.engine import ENC_CH
     eng = BiDateEngine(n_channels, 2, precision)
     assert eng._use_eval_schedule()
     by = _layers(n_channels)

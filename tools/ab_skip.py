@@ -20,6 +20,7 @@ CLASSES = {
     'upsample2x_bwd': lambda n, a: n in ('bdn_upsample2x_bwd', 'bdn_upsample2x_bwd_bs'),
     'product_pool': lambda n, a: n in ('bdn_product_pool', 'bdn_fuse_product'),
     'enc_skip_bwd': lambda n, a: n == 'bdn_enc_skip_bwd',
+    'handoff': lambda n, a: n in ('bdn_event_record', 'bdn_stream_wait_event'),      # streams.HandOff: the cross-stream event hand-offs
     'pack': lambda n, a: n in ('bdn_pack_input', 'bdn_pack_weights_multi'),
     'head+loss': lambda n, a: n in ('bdn_outc_fwd', 'bdn_tversky', 'bdn_outc_bwd'),
     'wgrad(all)': lambda n, a: n in ('bdn_conv3x3_wgrad_ex', 'bdn_conv3x3_wgrad_bnbwd'),
