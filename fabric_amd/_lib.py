@@ -95,6 +95,10 @@ SIGNATURES = {
     'bdn_upload_band': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'bdn_argmax': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_argmax_stitch': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'bdn_gather_tiles_sym': (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'bdn_blend_fold': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_blend_stitch': (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'bdn_blend_finalize': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'bdn_sample_patches': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'bdn_sgd_step': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
     'bdn_sgd_momentum_step': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _sz, _vp]),

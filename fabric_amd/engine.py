@@ -472,6 +472,8 @@ class BiDateEngine:
     def forward_tiles(self, scene_d1, scene_d2, origins, P, patch_size, reuse_eval_bn=False, slot=0, scene_mask=None):
         """Eval-mode forward of the tiles at `origins` (device int32 [n,2] = (y0,x0)) of a scene whose two dates
         are resident as [C,H,W] float32 band planes (train.py:190-197 without the host-side patch stack).
+        origins may also be a symmetry table, int32 [n,3] = (y0,x0,sym): every tile is then gathered under its symmetry of the square
+        (bdn_gather_tiles_sym; sym as in fabric_amd.utils.dataloaders._apply_symmetry) and only logits can be returned.
         reuse_eval_bn: the BatchNorm tables of this workspace (eval-shaped schedule: of the engine) are already those of P's running statistics.
         scene_mask: uint8 [H,W] device tensor -- the class index of every pixel of these tiles is written straight into it
         (utils/inference.py:187-236 ownership rule) and no logits are returned.
@@ -484,12 +486,17 @@ class BiDateEngine:
             raise RuntimeError('scene planes must be float32 and origins int32')
         if not (scene_d1.is_contiguous() and scene_d2.is_contiguous() and origins.is_contiguous()):
             raise RuntimeError('scene planes and origins must be contiguous')
+        if origins.dim() != 2 or origins.shape[1] not in (2, 3):
+            raise RuntimeError(f'origins must be int32 [n,2] (y0,x0) or a symmetry table [n,3] (y0,x0,sym), got {tuple(origins.shape)}')
+        sym = origins.shape[1] == 3
+        if sym and scene_mask is not None:
+            raise RuntimeError('a symmetry table gives logits in the tiles\' own orientation: no scene_mask')
         C, H, W = scene_d1.shape
         n, p = origins.shape[0], patch_size
         ws = self.workspace(n, p, p, scene_d1.device, slot)
         ws.generation += 1
         ws.x0_split = False
-        call('bdn_gather_tiles', self.dt, ptr(scene_d1), ptr(scene_d2), ptr(origins), ptr(ws.x0),
+        call('bdn_gather_tiles_sym' if sym else 'bdn_gather_tiles', self.dt, ptr(scene_d1), ptr(scene_d2), ptr(origins), ptr(ws.x0),
              n, C, H, W, p, self.cp, _lib.stream_ptr())
         if scene_mask is not None:
             if scene_mask.dtype != torch.uint8 or tuple(scene_mask.shape) != (H, W) or not scene_mask.is_contiguous() or not scene_mask.is_cuda:

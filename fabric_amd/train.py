@@ -15,6 +15,7 @@ import json
 import os
 import re
 
+import numpy as np
 import torch
 import torch.utils.data
 
@@ -226,6 +227,15 @@ def _to_cpu(obj):
     return obj
 
 
+def scene_scores(mask, label):
+    """Counts of a full-scene change mask against the city's label map (class 1 positive) and the precision / recall / F1 they give
+    (batch_prf_from_counts: 0 where a ratio has no denominator)."""
+    m, l = np.asarray(mask) == 1, np.asarray(label) != 0
+    counts = np.array([(m & l).sum(), (m & ~l).sum(), (~m & l).sum()])
+    pr, rc, f1 = batch_prf_from_counts(counts)
+    return {'tp': int(counts[0]), 'fp': int(counts[1]), 'fn': int(counts[2]), 'precision': pr, 'recall': rc, 'f1': f1}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Training change detection network (HIP path)')
     for k, v in DEFAULTS.items():
@@ -251,6 +261,12 @@ def main(argv=None):
     ap.add_argument('--device_patches', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=False,
                     help='cut and augment the patch pairs on the device from city stacks kept in HBM (fabric_amd.device_loader) '
                          'instead of on the host; --num_workers does not apply then')
+    ap.add_argument('--scene_stride', type=int, default=0,
+                    help='full validation scenes: 0 = the reference\'s non-overlapping argmax masks (predict_scene); N > 0 = tiles every N px, '
+                         'softmax probabilities blended (predict_scene_blended), also writes {city}_epoch_{e}_proba.png and a scene F1 line')
+    ap.add_argument('--scene_window', default='gaussian', choices=['gaussian', 'flat'], help='blending weights of --scene_stride N > 0')
+    ap.add_argument('--scene_tta', type=int, default=1, choices=[1, 2, 4, 8],
+                    help='symmetries of the square averaged per tile with --scene_stride N > 0: codes (0,), (0,1), (0,1,2,3), 0..7')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
                                                      "band_stds, ...): its entries become defaults like utils/parser.py:7-10")
     pre, _ = ap.parse_known_args(argv)
@@ -350,13 +366,24 @@ def main(argv=None):
                               **{'validate_' + k: float(v) for k, v in va.items()}}), flush=True)
         if scenes is not None and rank == 0:                   # train.py:182-205: full validation images
             from .utils import ingest
-            from .utils.inference import predict_scene
+            from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
             os.makedirs(opt.log_dir, exist_ok=True)
             model.eval()
+            scene_counts = {}
             for city in val_cities:
                 st = scenes[city]['images']
-                mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
+                if opt.scene_stride > 0:
+                    proba, mask = predict_scene_blended(model, st[0], st[1], patch_size=opt.patch_size, stride=opt.scene_stride,
+                                                        window=opt.scene_window, symmetries=TTA_SYMMETRIES[opt.scene_tta],
+                                                        batch_size=opt.batch_size)
+                    ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}_proba.png'),
+                                          torch.round(proba[1] * 255).to(torch.uint8).cpu().numpy())
+                    scene_counts[city] = scene_scores(mask.cpu().numpy(), scenes[city]['labels'])
+                else:
+                    mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
                 ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}.png'), (mask * 255).cpu().numpy())
+            if opt.scene_stride > 0:
+                print(json.dumps({'epoch': epoch, 'scene': scene_counts}), flush=True)
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
                                   step.optimizer_state_dict() if fused else optimizer.state_dict())

@@ -13,6 +13,11 @@ Two ways in:
 Tiles are independent: several GPUs take disjoint slices of the tile list (``shard=(rank, world)``); the only
 exchange is the optional final merge of the uint8 masks.
 
+``predict_scene_blended`` goes beyond the reference: overlapping tiles at any stride (``blend_tile_origins``), every tile
+optionally under several symmetries of the square (test-time augmentation), and a window-weighted average of the softmax
+probabilities instead of the last tile's argmax -- class probabilities [ncls,H,W] and their argmax, the same bits for any batch
+split and for one scan lane or two (``bdn_gather_tiles_sym``, ``bdn_blend_fold`` / ``_stitch`` / ``_finalize``).
+
 ``generate_patches`` (utils/inference.py:20-70) reads the band files through fabric_amd.utils.ingest; comet logging
 (``log_full_image``) is outside this path.
 """
@@ -126,10 +131,7 @@ def predict_scene(model, scene_d1, scene_d2, patch_size=128, batch_size=64, shar
     stay below 4 GB (32-bit byte offsets); the widest one is the operand of a 64-channel full-resolution layer at 2 * batch_size
     images: 64 channels x 2 bytes in the bf16 setting (<= 1023 tiles of 128 x 128), 64 x 4 bytes in fp32 (<= 511) and the
     [hi | lo] split of the concatenated 128-channel decoder input, 256 x 2 bytes at batch_size images, in bf16x3 (<= 511)."""
-    eng_ = model.engine()
-    widest = max(2 * batch_size * 64 * eng_.esize, batch_size * 2 * 128 * 2 if eng_.x3 else 0)      # bytes per pixel position of the widest tensor
-    if widest * patch_size * patch_size >= 1 << 32:
-        raise ValueError(f'batch_size={batch_size} tiles of {patch_size} px make a 4 GB tensor in the {eng_.precision} setting; use a smaller batch')
+    _check_widest(model.engine(), batch_size, patch_size)
     P = _eval_params(model)
     eng = model.engine()
     dev = next(model.parameters()).device
@@ -157,16 +159,199 @@ def predict_scene(model, scene_d1, scene_d2, patch_size=128, batch_size=64, shar
     origins = torch.from_numpy(o_np).to(dev)
     mask = torch.zeros(h, w, dtype=torch.uint8, device=dev) if shard is not None \
         else torch.empty(h, w, dtype=torch.uint8, device=dev)
-    # Tile batches are independent: they alternate between the caller's stream and the library's second stream (idle outside training),
-    # each with its own workspace, so that one batch's HBM-bound stages (tile gather, pooling, upsampling, classifier, stitching) run
-    # under the other's convolutions (+1.5 %).  The second lane needs a second full workspace (several GB at 256 tiles): it is created
-    # under the CALLER's stream (its blocks belong to the caller's allocator pool) and dropped again on exit, so a training workspace
-    # of the same process can take the memory over.  two_streams=None: only when the device has room for it; False: the single-stream loop.
+    cur, lanes, seen = _open_lanes(eng, P, dev, hi - lo, batch_size, patch_size, two_streams)
+    _fork_lanes(cur, lanes, (d1, d2, mask, origins))
+    try:
+        for it, i in enumerate(range(lo, hi, batch_size)):
+            j = min(hi, i + batch_size)
+            o = origins[i:j]
+            nb = o.shape[0]
+            k = it % len(lanes)
+            with torch.cuda.stream(lanes[k]):
+                if feed is not None:
+                    feed.need_rows(int(o_np[i:j, 0].max()) + patch_size, lanes[k])     # this lane waits for the last band these tiles read
+                eng.forward_tiles(d1, d2, o, P, patch_size, reuse_eval_bn=nb in seen[k], slot=k, scene_mask=mask)
+                seen[k].add(nb)
+    finally:
+        _join_lanes(eng, cur, lanes)
+        if feed is not None:
+            feed.close()          # also on an exception: the consumer stream joins every upload before the planes can be freed
+    if shard is not None and merge and shard[1] > 1:
+        import torch.distributed as dist
+        dist.all_reduce(mask, op=dist.ReduceOp.MAX)
+    return mask
+
+
+# ------------------------------------------------------------------ blended scan: overlapping tiles, softmax blend, symmetry averaging
+TTA_SYMMETRIES = {1: (0,), 2: (0, 1), 4: (0, 1, 2, 3), 8: tuple(range(8))}       # train.py --scene_tta
+
+
+def symmetry_bits(code):
+    """Symmetry code 4 t + 2 rr + rc -> the (t, rr, rc) of fabric_amd.utils.dataloaders._apply_symmetry (transpose if t, then reverse
+    the rows if rr, then the columns if rc; bdn_sample_patches' encoding)."""
+    return bool(code & 4), bool(code & 2), bool(code & 1)
+
+
+def inverse_symmetry(code):
+    """The code that undoes `code`: flips and the plain transpose are their own inverses; transpose-then-flip is undone by the other flip."""
+    t, rr, rc = symmetry_bits(code)
+    return 4 + 2 * rc + rr if t else code
+
+
+def blend_tile_origins(h, w, p, stride):
+    """Tile plan of the blended scan: ys = 0, s, 2s, ... while <= h - p, then h - p if the last one is not; xs alike.
+    Returns (origins int32 [len(ys) * len(xs), 2] in row-major order (tile iy * len(xs) + ix at (ys[iy], xs[ix])), ys, xs).
+    stride == p on multiples of p gives the reference's tile set (tile_origins)."""
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= p:
+        raise ValueError(f'stride must be an integer in [1, {p}], got {stride!r}')
+    if h < p or w < p:
+        raise ValueError(f'scene {h}x{w} is smaller than one {p}x{p} patch')
+
+    def axis(n):
+        v = list(range(0, n - p + 1, stride))
+        if v[-1] != n - p:
+            v.append(n - p)
+        return np.asarray(v, dtype=np.int64)
+    ys, xs = axis(h), axis(w)
+    origins = np.stack(np.meshgrid(ys, xs, indexing='ij'), -1).reshape(-1, 2).astype(np.int32)
+    return origins, ys, xs
+
+
+def blend_window(p, window='gaussian'):
+    """float32 [p,p] CPU tensor of the blending weights.  'flat': ones; 'gaussian': g(y) g(x), g(t) = exp(-(t + 0.5 - p/2)^2 / (2 (p/8)^2)),
+    evaluated in float64 and rounded once; a tensor: the caller's weights as they are (check_blend_args checks them)."""
+    if isinstance(window, torch.Tensor):
+        return window.detach().to('cpu', torch.float32).contiguous()
+    if window == 'flat':
+        return torch.ones(p, p, dtype=torch.float32)
+    t = np.arange(p, dtype=np.float64)
+    g = np.exp(-0.5 * ((t + 0.5 - p / 2) / (p / 8)) ** 2)
+    return torch.from_numpy(np.outer(g, g).astype(np.float32))
+
+
+def check_blend_args(h, w, patch_size, stride, window, symmetries, n_classes, batch_size=1):
+    """Validate the arguments of predict_scene_blended without touching a device.  Returns (stride, symmetry codes as a tuple)."""
+    p = patch_size
+    if isinstance(p, bool) or int(p) != p or p < 1:
+        raise ValueError(f'patch_size must be a positive integer, got {p!r}')
+    if h < p or w < p:
+        raise ValueError(f'scene {h}x{w} is smaller than one {p}x{p} patch')
+    stride = p // 2 if stride is None else stride
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= p:
+        raise ValueError(f'stride must be an integer in [1, {p}] (None: {p // 2}), got {stride!r}')
+    if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError(f'batch_size must be a positive integer, got {batch_size!r}')
+    syms = tuple(range(8)) if isinstance(symmetries, str) and symmetries == 'all' else symmetries
+    if isinstance(syms, str) or not hasattr(syms, '__iter__'):
+        raise ValueError(f"symmetries must be codes in 0..7 or 'all', got {symmetries!r}")
+    syms = tuple(syms)
+    if not syms or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c <= 7 for c in syms):
+        raise ValueError(f'symmetries must be a non-empty sequence of codes in 0..7, got {symmetries!r}')
+    if len(set(syms)) != len(syms):
+        raise ValueError(f'symmetry codes must be distinct, got {syms}')
+    if isinstance(window, torch.Tensor):
+        if window.dtype != torch.float32 or tuple(window.shape) != (p, p):
+            raise ValueError(f'a window tensor must be float32 [{p},{p}], got {window.dtype} {tuple(window.shape)}')
+        if not bool(torch.isfinite(window).all()) or not bool((window > 0).all()):
+            raise ValueError('window weights must be finite and strictly positive')
+    elif not (isinstance(window, str) and window in ('flat', 'gaussian')):
+        raise ValueError(f"window must be 'gaussian', 'flat' or a float32 [{p},{p}] tensor, got {window!r}")
+    if n_classes == 1:
+        raise ValueError('one class: its softmax is constant 1; the blended scan needs n_classes >= 2 (a sigmoid head is not supported)')
+    if n_classes < 2:
+        raise ValueError(f'n_classes must be >= 2, got {n_classes}')
+    return int(stride), tuple(int(c) for c in syms)
+
+
+@torch.no_grad()
+def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None, window='gaussian', symmetries=(0,), batch_size=64,
+                          band_rows=None, two_streams=None):
+    """Class probabilities of a whole scene from overlapping tiles.
+
+    Tiles of patch_size at `stride` (default patch_size // 2; blend_tile_origins), each under every code of `symmetries` (codes 0..7 of
+    _apply_symmetry, or 'all').  Forward images are (tile, symmetry) pairs in tile-major order, the symmetries in the order given; a
+    batch is batch_size consecutive images (the 4 GB bound of predict_scene applies to batch_size).  Every image's softmax is mapped back
+    through the inverse symmetry and weighted by `window` ('gaussian', 'flat' or a strictly positive float32 [p,p] tensor in scene
+    orientation).  Returns (proba float32 [n_classes,H,W] = sum w softmax / sum w over every image that covers a pixel, mask uint8 [H,W]
+    = its argmax, first maximum winning), both on the model's device.  Bit-reproducible, and the same bits for any batch_size split of
+    the same logits and for one lane or two.  scene_d1 / scene_d2, band_rows and two_streams as in predict_scene."""
+    eng = model.engine()
+    s1, s2 = torch.as_tensor(scene_d1), torch.as_tensor(scene_d2)
+    if s1.dim() != 3 or s1.shape != s2.shape:
+        raise RuntimeError(f'expected two [C,H,W] scenes of one shape, got {tuple(s1.shape)} and {tuple(s2.shape)}')
+    _, h, w = s1.shape
+    p, ncls = patch_size, eng.n_classes
+    stride, syms = check_blend_args(h, w, p, stride, window, symmetries, ncls, batch_size)
+    _check_widest(eng, batch_size, p)
+    P = _eval_params(model)
+    dev = next(model.parameters()).device
+    o_np, _, _ = blend_tile_origins(h, w, p, stride)
+    S = len(syms)
+    table_np = np.concatenate([np.repeat(o_np, S, axis=0), np.tile(np.asarray(syms, dtype=np.int32), len(o_np))[:, None]], 1).astype(np.int32)
+    n = len(table_np)
+    feed = None
+    if s1.is_cuda and s2.is_cuda:
+        d1 = s1.to(device=dev, dtype=torch.float32).contiguous()
+        d2 = s2.to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        feed = _SceneFeeder(s1.cpu(), s2.cpu(), dev, band_rows or max(p, 256))
+        d1, d2 = feed.d1, feed.d2
+    table = torch.from_numpy(table_np).to(dev)
+    win = blend_window(p, window).to(dev)
+    proba = torch.zeros(ncls, h, w, dtype=torch.float32, device=dev)        # sum of w softmax until bdn_blend_finalize divides in place
+    wsum = torch.zeros(h, w, dtype=torch.float32, device=dev)
+    mask = torch.empty(h, w, dtype=torch.uint8, device=dev)
+    cur, lanes, seen = _open_lanes(eng, P, dev, n, batch_size, p, two_streams)
+    folds = [torch.empty(min(batch_size, n), ncls, p, p, dtype=torch.float32, device=dev) for _ in lanes]   # per lane: the batch's weighted probabilities
+    _fork_lanes(cur, lanes, (d1, d2, table, win, proba, wsum, *folds))
+    # Each lane runs gather -> forward -> fold of its batch; the stitches, which add into the shared sums, are chained across the lanes by
+    # events (batch i's stitch waits for batch i - 1's) while the other lane's next forward runs under them.
+    prev = None
+    try:
+        for it, i in enumerate(range(0, n, batch_size)):
+            j = min(n, i + batch_size)
+            nb, k = j - i, it % len(lanes)
+            with torch.cuda.stream(lanes[k]):
+                if feed is not None:
+                    feed.need_rows(int(table_np[i:j, 0].max()) + p, lanes[k])
+                logits, _ = eng.forward_tiles(d1, d2, table[i:j], P, p, reuse_eval_bn=nb in seen[k], slot=k)
+                seen[k].add(nb)
+                st = _lib.stream_ptr()
+                _lib.call('bdn_blend_fold', _lib.ptr(logits), _lib.ptr(table[i:j]), _lib.ptr(win), _lib.ptr(folds[k]), nb, ncls, p, st)
+                if prev is not None:
+                    lanes[k].wait_event(prev)
+                _lib.call('bdn_blend_stitch', _lib.ptr(folds[k]), _lib.ptr(win), _lib.ptr(proba), _lib.ptr(wsum), i, nb, S, ncls, h, w, p, stride, st)
+                if len(lanes) > 1:
+                    prev = torch.cuda.Event()
+                    prev.record(lanes[k])
+    finally:
+        _join_lanes(eng, cur, lanes)
+        if feed is not None:
+            feed.close()
+    _lib.call('bdn_blend_finalize', _lib.ptr(proba), _lib.ptr(wsum), _lib.ptr(mask), ncls, h, w, _lib.stream_ptr())
+    return proba, mask
+
+
+def _check_widest(eng, batch_size, patch_size):
+    widest = max(2 * batch_size * 64 * eng.esize, batch_size * 2 * 128 * 2 if eng.x3 else 0)      # bytes per pixel position of the widest tensor
+    if widest * patch_size * patch_size >= 1 << 32:
+        raise ValueError(f'batch_size={batch_size} tiles of {patch_size} px make a 4 GB tensor in the {eng.precision} setting; use a smaller batch')
+
+
+def _open_lanes(eng, P, dev, n, batch_size, patch_size, two_streams):
+    """The scan lanes of n forward images in batches of batch_size: returns (caller's stream, lanes, per-lane set of batch sizes whose
+    eval BatchNorm tables are already folded).
+    Tile batches are independent: they alternate between the caller's stream and the library's second stream (idle outside training),
+    each with its own workspace, so that one batch's HBM-bound stages (tile gather, pooling, upsampling, classifier, stitching) run
+    under the other's convolutions (+1.5 %).  The second lane needs a second full workspace (several GB at 256 tiles): it is created
+    under the CALLER's stream (its blocks belong to the caller's allocator pool) and dropped again on exit (_join_lanes), so a training
+    workspace of the same process can take the memory over.  two_streams=None: only when the device has room for it; False: the
+    single-stream loop."""
     from .. import streams as _streams
     cur = torch.cuda.current_stream(dev)
-    want_two = (hi - lo) > batch_size and two_streams is not False
+    want_two = n > batch_size and two_streams is not False
     if want_two:
-        nb0 = min(batch_size, hi - lo)
+        nb0 = min(batch_size, n)
         a0 = torch.cuda.memory_allocated(dev)
         eng.workspace(nb0, patch_size, patch_size, dev, 0)
         first_ws = max(torch.cuda.memory_allocated(dev) - a0, 0)           # 0 when slot 0 existed already: then size it from the tensors
@@ -182,34 +367,25 @@ def predict_scene(model, scene_d1, scene_d2, patch_size=128, batch_size=64, shar
         eng._weights(eng.layers[0], P, False)            # the filter images are packed once, on the caller's stream, before the fork
         if eng._use_eval_schedule():
             eng.eval_tables(P)                           # and so are the folded BatchNorm tables both lanes read
-            seen = [{min(batch_size, hi - lo), (hi - lo) % batch_size or batch_size} for _ in lanes]
-        for nb_ in {min(batch_size, hi - lo), (hi - lo) % batch_size or batch_size}:
+            seen = [{min(batch_size, n), n % batch_size or batch_size} for _ in lanes]
+        for nb_ in {min(batch_size, n), n % batch_size or batch_size}:
             eng.workspace(nb_, patch_size, patch_size, dev, 1)             # second lane's buffers: allocated under the caller's stream
+    return cur, lanes, seen
+
+
+def _fork_lanes(cur, lanes, tensors):
+    """The second lane starts behind everything the caller's stream has enqueued; the tensors both lanes use stay theirs until it is done."""
+    if len(lanes) > 1:
         lanes[1].wait_stream(cur)
-        for t in (d1, d2, mask, origins):
+        for t in tensors:
             t.record_stream(lanes[1])
-    try:
-        for it, i in enumerate(range(lo, hi, batch_size)):
-            j = min(hi, i + batch_size)
-            o = origins[i:j]
-            nb = o.shape[0]
-            k = it % len(lanes)
-            with torch.cuda.stream(lanes[k]):
-                if feed is not None:
-                    feed.need_rows(int(o_np[i:j, 0].max()) + patch_size, lanes[k])     # this lane waits for the last band these tiles read
-                eng.forward_tiles(d1, d2, o, P, patch_size, reuse_eval_bn=nb in seen[k], slot=k, scene_mask=mask)
-                seen[k].add(nb)
-    finally:
-        for ln in lanes[1:]:
-            cur.wait_stream(ln)
-        if len(lanes) > 1:
-            eng.drop_workspaces(slot=1)                  # back to the caller's pool (ordered behind the join above)
-        if feed is not None:
-            feed.close()          # also on an exception: the consumer stream joins every upload before the planes can be freed
-    if shard is not None and merge and shard[1] > 1:
-        import torch.distributed as dist
-        dist.all_reduce(mask, op=dist.ReduceOp.MAX)
-    return mask
+
+
+def _join_lanes(eng, cur, lanes):
+    for ln in lanes[1:]:
+        cur.wait_stream(ln)
+    if len(lanes) > 1:
+        eng.drop_workspaces(slot=1)                  # back to the caller's pool (ordered behind the join above)
 
 
 class _SceneFeeder:

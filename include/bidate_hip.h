@@ -428,6 +428,28 @@ int bdn_argmax(const float* logits, uint8_t* out, int n, int ncls, int H, int W,
 int bdn_argmax_stitch(const float* logits, const int32_t* origins, uint8_t* mask,
                       int n_tiles, int ncls, int p, int H, int W, void* stream);
 
+/* ---- full-scene change probabilities from blended overlapping tiles: utils/inference.py:134-236 and train.py:182-205, generalized ----
+ * Tile plan of an H x W scene at stride s (1 <= s <= p): ys[k] = min(k s, H - p) for k < ny = (H - p) / s + 1 + ((H - p) % s != 0),
+ * xs alike; tile g = ky nx + kx (row-major).  Forward images are (tile, symmetry) pairs in tile-major order, n_syms per tile: image
+ * i = g n_syms + k shows tile g under the k-th symmetry code.  sym = 4 t + 2 rr + rc as in bdn_sample_patches.
+ * bdn_gather_tiles_sym: bdn_gather_tiles with table = device int32 [n_tiles][3] = (y0, x0, sym): tile i holds the p x p window at
+ *   (y0, x0) of both dates under sym.  out: [2*n_tiles][p][p][Cpad] (date-1 tiles first).  Rows outside the scene or with sym outside
+ *   0..7 give zero tiles (the caller checks the table).
+ * bdn_blend_fold: logits [n_img][ncls][p][p] f32 of n_img forward images whose symmetries are table[i][2] (the gather's table) ->
+ *   out [n_img][ncls][p][p] f32 = window[a][b] * softmax over classes, mapped back through the inverse symmetry into scene orientation.
+ *   window: [p][p] f32, strictly positive.
+ * bdn_blend_stitch: the folded images [img0, img0 + n_img) of the plan (H, W, p, stride, n_syms) added into acc [ncls][H][W] and their
+ *   window weights into wsum [H][W].  Each pixel adds its covering images in ascending image index into one register: the same bits for
+ *   any split of the images into batches, provided the batches' stitches are ordered on the device.  No float atomics.
+ * bdn_blend_finalize: acc /= wsum in place (= the class probabilities) and mask [H][W] uint8 = their argmax (first maximum wins,
+ *   train.py:199).  2 <= ncls <= 256. */
+int bdn_gather_tiles_sym(int dtype, const float* scene_d1, const float* scene_d2, const int32_t* table,
+                         void* out, int n_tiles, int C, int H, int W, int p, int Cpad, void* stream);
+int bdn_blend_fold(const float* logits, const int32_t* table, const float* window, float* out, int n_img, int ncls, int p, void* stream);
+int bdn_blend_stitch(const float* fold, const float* window, float* acc, float* wsum, long long img0, int n_img,
+                     int n_syms, int ncls, int H, int W, int p, int stride, void* stream);
+int bdn_blend_finalize(float* acc, const float* wsum, uint8_t* mask, int ncls, int H, int W, void* stream);
+
 /* ---- training patch pairs on the device: utils/dataloaders.py:148-165 (onera_siamese_loader) + the DataLoader collate, for a batch ----
  * cities_dev: DEVICE array of n_cities records { const float* images; const uint8_t* labels; int32 H, W; } (24 bytes each, 8-byte
  * aligned): images [2][C][H][W] f32 and labels [H][W] uint8, both contiguous.  city_hw_host: HOST int32 [n_cities][2] = (H, W), the
