@@ -513,3 +513,103 @@ extern "C" int bdn_bn_bwd(int dtype, const void* dA, int ldA, const void* z, con
     if (dtype == BDN_F32) return bn_bwd_impl<float>(dA, ldA, z, bn, imgs_per_group, N, H, W, C, ws, sums, dgamma, dbeta, dz, (hipStream_t)stream);
     BDN_FAIL(BDN_E_ARG, "bn_bwd: bad dtype");
 }
+
+// ---------------------------------------------------------------- backward on running statistics (frozen BatchNorm, model.eval())
+// y = (z - running_mean) * rsqrt(running_var + eps) * gamma + beta with the statistics constants: dz = scale * g under the ReLU mask, no
+// mean-correction terms.  The table is bdn_bn_eval's ({running_mean, invstd, scale, shift}), so the partial sums every fused producer
+// leaves (sum g, sum g*z) finalize to dbeta = sum g and dgamma = sum g * xhat with xhat on the running statistics, exactly as in
+// training.  Then the conv bias in front of the BatchNorm gets dbias = scale * dbeta, and `sums` is zeroed: every consumer that forms
+// dz = scale * (g - s0/M - xhat * s1/M) from `sums` (bdn_bn_bwd_apply's kernel, bdn_conv3x3_dgrad_bb, bdn_conv3x3_wgrad_bnbwd,
+// bdn_outc_bn_bwd_apply, bdn_conv3x3_dgrad_first) then forms scale * g with its unchanged arithmetic.
+__global__ void bn_bwd_freeze_kernel(const float* __restrict__ bn, int G, int C, float* __restrict__ sums,
+                                     const float* __restrict__ dbeta, float* __restrict__ dbias) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    if (dbias) dbias[c] = bn_row(bn, 0, 2, C)[c] * dbeta[c];
+    for (int g = 0; g < G; g++) {
+        sums[((size_t)g * 2 + 0) * C + c] = 0.f;
+        sums[((size_t)g * 2 + 1) * C + c] = 0.f;
+    }
+}
+
+static void launch_bn_bwd_finalize_frozen(const float* bn, const float* partial, int rows_per_group, int G, int C, int raw_moment,
+                                          float* sums, float* dgamma, float* dbeta, float* dbias, void* ws2, hipStream_t st) {
+    launch_bn_bwd_finalize(partial, rows_per_group, G, C, sums, dgamma, dbeta, raw_moment ? bn : (const float*)nullptr, ws2, st);
+    hipLaunchKernelGGL(bn_bwd_freeze_kernel, dim3((C + 255) / 256), dim3(256), 0, st, bn, G, C, sums, dbeta, dbias);
+}
+
+extern "C" int bdn_bn_bwd_finalize_frozen(const float* bn, int G, int C, const float* partial, int rows_per_group, int raw_moment,
+                                          float* sums, float* dgamma, float* dbeta, float* dbias, void* scratch, void* stream) {
+    if (!bn || !partial || !sums || !dbeta) BDN_FAIL(BDN_E_ARG, "bn_bwd_finalize_frozen: null pointer");
+    if (G <= 0 || C <= 0 || C % 16 || C > 1024 || 1024 % C || rows_per_group <= 0) BDN_FAIL(BDN_E_SHAPE, "bn_bwd_finalize_frozen: bad shape");
+    launch_bn_bwd_finalize_frozen(bn, partial, rows_per_group, G, C, raw_moment, sums, dgamma, dbeta, dbias, scratch, (hipStream_t)stream);
+    BDN_CHECK_LAUNCH("bn_bwd_finalize_frozen");
+    return BDN_OK;
+}
+
+// bdn_bn_bwd_apply / bdn_bn_bwd_apply_split on running statistics: dtype BDN_BF16 / BDN_F32 store dz [N,H,W,C], BDN_BF16X3 the split
+// operand [N,H,W,2 C] bf16 = hi | lo (float32 dA and z)
+extern "C" int bdn_bn_bwd_apply_frozen(int dtype, const void* dA, int ldA, const void* z, const float* bn,
+                                       int imgs_per_group, int N, int H, int W, int C,
+                                       const float* partial, int rows_per_group, int raw_moment,
+                                       float* sums, float* dgamma, float* dbeta, float* dbias, void* dz, void* scratch, void* stream) {
+    if (!dA || !z || !bn || !partial || !sums || !dbeta || !dz) BDN_FAIL(BDN_E_ARG, "bn_bwd_apply_frozen: null pointer");
+    if (N <= 0 || imgs_per_group <= 0 || N % imgs_per_group || C % 16 || ldA < C || ldA % 16 || rows_per_group <= 0 || H <= 0 || W <= 0)
+        BDN_FAIL(BDN_E_SHAPE, "bn_bwd_apply_frozen: bad shape");
+    if (C > 1024 || 1024 % C) BDN_FAIL(BDN_E_SHAPE, "bn_bwd_apply_frozen: C=%d must divide 1024", C);
+    if (dtype != BDN_BF16 && dtype != BDN_F32 && dtype != BDN_BF16X3) BDN_FAIL(BDN_E_ARG, "bn_bwd_apply_frozen: bad dtype");
+    hipStream_t st = (hipStream_t)stream;
+    const int G = N / imgs_per_group;
+    launch_bn_bwd_finalize_frozen(bn, partial, rows_per_group, G, C, raw_moment, sums, dgamma, dbeta, dbias, scratch, st);
+    BDN_CHECK_LAUNCH("bn_bwd_finalize_frozen");
+    const int epu = dtype == BDN_BF16 ? 8 : 4;
+    const int ppg = imgs_per_group * H * W;
+    const int ppb = bnb_pix_per_block(ppg, 256 / (C / epu));
+    const int bpg = (ppg + ppb - 1) / ppb;
+    if (dtype == BDN_BF16)
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16s>), dim3(G * bpg), dim3(256), 0, st,
+                           (const bf16s*)dA, ldA, (const bf16s*)z, bn, sums, ppg, bpg, ppb, C, (bf16s*)dz);
+    else if (dtype == BDN_F32)
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), dim3(G * bpg), dim3(256), 0, st,
+                           (const float*)dA, ldA, (const float*)z, bn, sums, ppg, bpg, ppb, C, (float*)dz);
+    else
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3(G * bpg), dim3(256), 0, st,
+                           (const float*)dA, ldA, (const float*)z, bn, sums, ppg, bpg, ppb, C, (float*)dz);
+    BDN_CHECK_LAUNCH("bn_bwd_apply_frozen");
+    return BDN_OK;
+}
+
+// bdn_bn_bwd on running statistics (the producer left no partial sums): reduction pass, frozen finalize, dz = scale * g
+extern "C" int bdn_bn_bwd_frozen(int dtype, const void* dA, int ldA, const void* z, const float* bn,
+                                 int imgs_per_group, int N, int H, int W, int C,
+                                 float* ws, float* sums, float* dgamma, float* dbeta, float* dbias, void* dz, void* stream) {
+    if (!dA || !z || !bn || !ws || !sums || !dbeta || !dz) BDN_FAIL(BDN_E_ARG, "bn_bwd_frozen: null pointer");
+    if (N <= 0 || imgs_per_group <= 0 || N % imgs_per_group || C % 16 || ldA < C || ldA % 16 || H <= 0 || W <= 0)
+        BDN_FAIL(BDN_E_SHAPE, "bn_bwd_frozen: bad shape");
+    if (C > 1024 || 1024 % C) BDN_FAIL(BDN_E_SHAPE, "bn_bwd_frozen: C=%d must divide 1024", C);
+    if (dtype != BDN_BF16 && dtype != BDN_F32) BDN_FAIL(BDN_E_ARG, "bn_bwd_frozen: bad dtype");
+    hipStream_t st = (hipStream_t)stream;
+    const int epu = dtype == BDN_BF16 ? 8 : 4;
+    const int G = N / imgs_per_group;
+    const int ppg = imgs_per_group * H * W;
+    const int ppb = bnb_pix_per_block(ppg, 256 / (C / epu));
+    const int bpg = (ppg + ppb - 1) / ppb;
+    void* ws2 = reinterpret_cast<unsigned char*>(ws) + bnb_partial_bytes((size_t)G * bpg, C);
+    if (dtype == BDN_BF16)
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16s>, dim3(G * bpg), dim3(256), 256 * 8 * 2 * sizeof(float), st,
+                           (const bf16s*)dA, ldA, (const bf16s*)z, bn, ppg, bpg, ppb, C, ws);
+    else
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(G * bpg), dim3(256), 256 * 4 * 2 * sizeof(float), st,
+                           (const float*)dA, ldA, (const float*)z, bn, ppg, bpg, ppb, C, ws);
+    BDN_CHECK_LAUNCH("bn_bwd_reduce");
+    launch_bn_bwd_finalize_frozen(bn, ws, bpg, G, C, 0, sums, dgamma, dbeta, dbias, ws2, st);
+    BDN_CHECK_LAUNCH("bn_bwd_finalize_frozen");
+    if (dtype == BDN_BF16)
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16s>), dim3(G * bpg), dim3(256), 0, st,
+                           (const bf16s*)dA, ldA, (const bf16s*)z, bn, sums, ppg, bpg, ppb, C, (bf16s*)dz);
+    else
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), dim3(G * bpg), dim3(256), 0, st,
+                           (const float*)dA, ldA, (const float*)z, bn, sums, ppg, bpg, ppb, C, (float*)dz);
+    BDN_CHECK_LAUNCH("bn_bwd_apply_frozen");
+    return BDN_OK;
+}

@@ -395,9 +395,11 @@ class BiDateEngine:
                 if not ws.leased:
                     ws.release_split()
 
-    def _conv(self, ws, L, P, in0, c0, in1, c1, in_mode, in_bn, n, ipg, training, st, reuse_eval_bn=False, presplit=False):
-        """One conv3x3 + BatchNorm statistics stage."""
+    def _conv(self, ws, L, P, in0, c0, in1, c1, in_mode, in_bn, n, ipg, training, st, reuse_eval_bn=False, presplit=False, frozen=False):
+        """One conv3x3 + BatchNorm statistics stage.  frozen: the training layout (bf16x3: per-layer split operands kept for the weight
+        gradient) on a running-statistics table -- the forward an eval-mode backward recomputes."""
         hk, wk = ws.dims[L.level - 1]
+        keep = training or frozen
         wf, _ = self._weights(L, P, False)
         z, bn = ws.z[L.name], ws.bn[L.name]
         xs = self.x3_src_f32
@@ -406,7 +408,7 @@ class BiDateEngine:
             # one float32 source of >= 64 channels (the second convolution of every double_conv): BatchNorm+ReLU and the hi / lo split are
             # applied inside the convolution's staging (bdn_conv3x3_x3src); in training the tile's own pixels of the split operand are
             # stored as a by-product for the layer's weight-gradient GEMM -- no bdn_split_pack launch
-            sp = ws.split_buf(('a', L.name), n * hk * wk * 2 * c0) if training else None
+            sp = ws.split_buf(('a', L.name), n * hk * wk * 2 * c0) if keep else None
             self._timed_conv(n, hk, wk, c0, 0, L.cout, ipg,
                              self.mdt, ptr(in0), c0, in_mode, ptr(in_bn), ipg, ptr(wf), ptr(P[f'{L.conv}.bias']), ptr(z),
                              ptr(ws.stats) if training else None, ptr(sp), n, hk, wk, L.cout, st, fn='bdn_conv3x3_x3src')
@@ -414,7 +416,7 @@ class BiDateEngine:
             if self.x3:
                 # the operand split does the cat and the BatchNorm+ReLU the f32 kernel would apply on load
                 # training: one buffer per layer, kept for the layer's weight-gradient GEMM (the same operand: no second split in backward)
-                sp = ws.split_buf(('a', L.name) if training else 'a', n * hk * wk * 2 * (c0 + c1))
+                sp = ws.split_buf(('a', L.name) if keep else 'a', n * hk * wk * 2 * (c0 + c1))
                 if not presplit:                         # presplit: the producers of the operand (product_pool / upsample2x) stored it split already
                     call('bdn_split_pack', ptr(in0), c0, ptr(in1), c1, in_mode, ptr(in_bn), ipg, ptr(sp), n, hk, wk, st)
                 in0, c0, in1, c1, in_mode, in_bn = sp, c0 + c1, None, 0, IN_PLAIN, None
@@ -435,11 +437,12 @@ class BiDateEngine:
         return z, bn
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x_d1, x_d2, P, training=True, class_map=False):
+    def forward(self, x_d1, x_d2, P, training=True, class_map=False, frozen=False):
         """x_d1, x_d2: [B,C,H,W] float32 CUDA tensors (reference layout).  P: state-dict-keyed tensors.
         Returns (logits [B,n_classes,H,W] float32, workspace).  class_map=True (eval mode only): returns the uint8 [B,H,W] map
         torch.max(logits, 1)[1] (train.py:199) instead of the logits -- on the eval-shaped schedule it comes straight out of the last
-        convolution's epilogue."""
+        convolution's epilogue.  frozen=True (training=False): the training-layout forward on P's running statistics, whose activations
+        backward(bn_mode='running') reads -- what an eval-mode backward recomputes."""
         self._prof_seen = 0
         if not (x_d1.is_cuda and x_d2.is_cuda):
             raise RuntimeError('fabric_amd: BiDateNet runs only on a ROCm device (MI355X); '
@@ -453,7 +456,7 @@ class BiDateEngine:
         ws.generation += 1
         ws.x0_split = self.x3 and not class_map
         if ws.x0_split:            # bf16x3: the packed input leaves as the first convolution's [hi | lo] operand (no float32 x0, no split pass)
-            sp = ws.split_buf(('a', self.layers[0].name) if training else 'a', 2 * B * H * W * 2 * self.cp)
+            sp = ws.split_buf(('a', self.layers[0].name) if training or frozen else 'a', 2 * B * H * W * 2 * self.cp)
             call('bdn_pack_input', BDN_BF16X3, ptr(x_d1), ptr(x_d2), ptr(sp), B, C, H, W, self.cp, _lib.stream_ptr())
         else:
             call('bdn_pack_input', self.dt, ptr(x_d1), ptr(x_d2), ptr(ws.x0), B, C, H, W, self.cp, _lib.stream_ptr())
@@ -467,7 +470,7 @@ class BiDateEngine:
                 logits = self._forward_packed(ws, P, False)
                 call('bdn_argmax', ptr(logits), ptr(cd), B, self.n_classes, H, W, _lib.stream_ptr())
             return cd, ws
-        return self._forward_packed(ws, P, training), ws
+        return self._forward_packed(ws, P, training, frozen=frozen and not training), ws
 
     def forward_tiles(self, scene_d1, scene_d2, origins, P, patch_size, reuse_eval_bn=False, slot=0, scene_mask=None):
         """Eval-mode forward of the tiles at `origins` (device int32 [n,2] = (y0,x0)) of a scene whose two dates
@@ -509,13 +512,13 @@ class BiDateEngine:
             return None, ws
         return self._forward_packed(ws, P, False, reuse_eval_bn), ws
 
-    def _forward_packed(self, ws, P, training, reuse_eval_bn=False):
-        """The network on the packed input already in ws.x0."""
+    def _forward_packed(self, ws, P, training, reuse_eval_bn=False, frozen=False):
+        """The network on the packed input already in ws.x0.  frozen: see forward()."""
         B, H, W = ws.B, ws.H, ws.W
         dev = ws.x0.device
         st = _lib.stream_ptr()
         _lib.PHASE = 'fwd'
-        if not training and self._use_eval_schedule():
+        if not training and not frozen and self._use_eval_schedule():
             return self._forward_eval(ws, P, reuse_tables=reuse_eval_bn)
         self._check_packed(P)
         by = {L.name: L for L in self.layers}
@@ -524,11 +527,11 @@ class BiDateEngine:
         for k in range(1, 6):
             hk, wk = ws.dims[k - 1]
             La, Lb = by[f'e{k}a'], by[f'e{k}b']
-            pre = self.x3 and training                      # bf16x3 training: pooled maps, skips and upsampled maps are stored as split operands
+            pre = self.x3 and (training or frozen)          # bf16x3 training: pooled maps, skips and upsampled maps are stored as split operands
             src = ws.x0 if k == 1 else (None if pre else ws.pool[k])   # pool[k] was written together with the skip of level k-1
             za, bna = self._conv(ws, La, P, src, La.cin, None, 0, IN_PLAIN, None, 2 * B, B, training, st, rb,
-                                 presplit=(pre and k > 1) or (k == 1 and ws.x0_split))
-            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, 2 * B, B, training, st, rb)
+                                 presplit=(pre and k > 1) or (k == 1 and ws.x0_split), frozen=frozen)
+            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, 2 * B, B, training, st, rb, frozen=frozen)
             if k < 5 and pre:
                 Ld, Ln = by[f'd{5 - k}a'], by[f'e{k + 1}a']
                 hn, wn = ws.dims[k]
@@ -545,7 +548,7 @@ class BiDateEngine:
             hk, wk = ws.dims[k - 1]
             hs, wsrc = ws.dims[k]
             La, Lb = by[f'd{j}a'], by[f'd{j}b']
-            pre = self.x3 and training
+            pre = self.x3 and (training or frozen)
             if pre:
                 call('bdn_upsample2x_split', ptr(prev), prev_mode, ptr(prev_bn), ptr(ws.split_buf(('a', La.name), B * hk * wk * 2 * La.cin)),
                      2 * La.cin, ENC_CH[k - 1], La.cin, B, hs, wsrc, hk, wk, cprev, st)
@@ -553,8 +556,8 @@ class BiDateEngine:
                 call('bdn_upsample2x', self.dt, ptr(prev), prev_mode, ptr(prev_bn), ptr(ws.U[j]),
                      B, hs, wsrc, hk, wk, cprev, st)
             za, bna = self._conv(ws, La, P, None if pre else ws.f[k], ENC_CH[k - 1], None if pre else ws.U[j], cprev, IN_PLAIN, None, B, B,
-                                 training, st, rb, presplit=pre)
-            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, B, B, training, st, rb)
+                                 training, st, rb, presplit=pre, frozen=frozen)
+            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, B, B, training, st, rb, frozen=frozen)
             prev, prev_bn, prev_mode, cprev = zb, bnb, IN_BNRELU, Lb.cout
         logits = torch.empty(B, self.n_classes, H, W, dtype=torch.float32, device=dev)
         call('bdn_outc_fwd', self.dt, ptr(prev), ptr(prev_bn), ptr(P['outc.conv.weight']), ptr(P['outc.conv.bias']),
@@ -712,8 +715,11 @@ class BiDateEngine:
                 f'{"true" if c0 + c1 <= 32 else "false"}>')
 
     # ------------------------------------------------------------------ backward
-    def backward(self, ws, dlogits, P, grads, on_ready=None, zero_bias_grads=True, wgrad_stream=True):
-        """Gradient of the last training-mode forward on `ws`.
+    def backward(self, ws, dlogits, P, grads, on_ready=None, zero_bias_grads=True, wgrad_stream=True, dx=None, bn_mode='batch',
+                 need=None):
+        """Gradient of the last training-mode forward on `ws` (bn_mode='batch'), or of the last forward(frozen=True) on it
+        (bn_mode='running': BatchNorm on running statistics, which are constants -- dz = scale * g, the conv biases get
+        scale * dbeta).
 
         dlogits: [B,n_classes,H,W] float32.  grads: dict key -> preallocated float32 tensor (reference
         parameter shapes) that is OVERWRITTEN.  on_ready(keys) is called after the kernels producing
@@ -722,7 +728,14 @@ class BiDateEngine:
         ever writes them), which saves 18 fill launches per step.
         wgrad_stream=True: the weight-gradient GEMMs (off the critical dz -> dgrad -> dz chain, MFMA-bound) are
         enqueued on a second HIP stream so they overlap the HBM-bound BatchNorm-backward / unpool / upsample
-        kernels of the chain; the main stream joins it before returning."""
+        kernels of the chain; the main stream joins it before returning.
+        dx: None, or (dx1, dx2) float32 [B,n_channels,H,W] tensors that receive the gradient on the two input images
+        (bdn_conv3x3_dgrad_first after the first layer's BatchNorm backward).
+        need: None (every parameter), or the set of state-dict keys whose gradient is wanted: a layer whose conv weight is not in it
+        launches no weight-gradient GEMM (its grads entries are left as they are)."""
+        if bn_mode not in ('batch', 'running'):
+            raise ValueError(f"bn_mode must be 'batch' or 'running', got {bn_mode!r}")
+        frozen = bn_mode == 'running'
         B, H, W = ws.B, ws.H, ws.W
         dev = dlogits.device
         dlogits = dlogits.contiguous().float()
@@ -751,15 +764,36 @@ class BiDateEngine:
             ho.wait(dst)
 
         def bn_bwd_finalize(L, n, ipg, rows):
-            """Sums, dgamma and dbeta of layer L's BatchNorm backward from the `rows` per-tile partial sums per group in ws.stats."""
+            """Sums, dgamma and dbeta of layer L's BatchNorm backward from the `rows` per-tile partial sums per group in ws.stats
+            (frozen: the conv-bias gradient too, and zeroed sums)."""
+            if frozen:
+                call('bdn_bn_bwd_finalize_frozen', ptr(ws.bn[L.name]), n // ipg, L.cout, ptr(ws.stats), rows, 1, ptr(sc['sums']),
+                     ptr(grads[f'{L.bn}.weight']), ptr(grads[f'{L.bn}.bias']), ptr(grads[f'{L.conv}.bias']), ptr(ws.bnws), st)
+                return
             call('bdn_bn_bwd_finalize', ptr(ws.bn[L.name]), n // ipg, L.cout, ptr(ws.stats), rows, 1, ptr(sc['sums']),
                  ptr(grads[f'{L.bn}.weight']), ptr(grads[f'{L.bn}.bias']), ptr(ws.bnws), st)
 
-        def bn_bwd(L, dA, ldA, n, ipg, fused_rows):
+        def bn_bwd(L, dA, ldA, n, ipg, fused_rows, plain=False):
             """BatchNorm+ReLU backward of layer L: its dz, or None when bf16x3 left it split already.  fused_rows > 0: the kernel that
-            produced dA already left the per-tile partial sums (sum g, sum g*z) in ws.stats, fused_rows rows per statistic group."""
+            produced dA already left the per-tile partial sums (sum g, sum g*z) in ws.stats, fused_rows rows per statistic group.
+            plain: a float32 dz is stored in bf16x3 too (the first layer's input gradient reads it)."""
             hk, wk = ws.dims[L.level - 1]
-            if fused_rows and self.x3:
+            if frozen:
+                gb = (ptr(grads[f'{L.bn}.weight']), ptr(grads[f'{L.bn}.bias']), ptr(grads[f'{L.conv}.bias']))
+                if fused_rows and self.x3 and not plain:
+                    sp = ws.split_buf(('d', L.name), n * hk * wk * 2 * L.cout)
+                    call('bdn_bn_bwd_apply_frozen', BDN_BF16X3, dA, ldA, ptr(ws.z[L.name]), ptr(ws.bn[L.name]), ipg, n, hk, wk, L.cout,
+                         ptr(ws.stats), fused_rows, 1, ptr(sc['sums']), *gb, ptr(sp), ptr(ws.bnws), st)
+                    return None
+                dz = e(n, hk, wk, L.cout)
+                if fused_rows:
+                    call('bdn_bn_bwd_apply_frozen', self.dt, dA, ldA, ptr(ws.z[L.name]), ptr(ws.bn[L.name]), ipg, n, hk, wk, L.cout,
+                         ptr(ws.stats), fused_rows, 1, ptr(sc['sums']), *gb, ptr(dz), ptr(ws.bnws), st)
+                else:
+                    call('bdn_bn_bwd_frozen', self.dt, dA, ldA, ptr(ws.z[L.name]), ptr(ws.bn[L.name]), ipg, n, hk, wk, L.cout,
+                         ptr(sc['bnb']), ptr(sc['sums']), *gb, ptr(dz), st)
+                return dz
+            if fused_rows and self.x3 and not plain:
                 # bf16x3: dz leaves the pass as the [hi | lo] operand of its two consumers (per-layer buffer: the weight-gradient stream may
                 # lag a layer behind); there is no float32 dz and no split pass over it
                 sp = ws.split_buf(('d', L.name), n * hk * wk * 2 * L.cout)
@@ -858,16 +892,19 @@ class BiDateEngine:
             the end of the step).  The chain then joins the second queue: the bucket this ready() may release holds gradients whose GEMMs
             are still queued there.  Without a second stream everything runs on the chain's."""
             keys = [f'{L.bn}.weight', f'{L.bn}.bias', f'{L.conv}.weight', f'{L.conv}.bias']
+            if need is not None and f'{L.conv}.weight' not in need:
+                launch = lambda stp, role: None        # noqa: E731  (frozen layer: no weight-gradient GEMM)
+            zero_bias = zero_bias_grads and not frozen   # on running statistics the conv-bias gradient is scale * dbeta (bn_bwd_finalize)
             if side is not None and not last:
                 handoff(main, side)
                 with torch.cuda.stream(side):
                     launch(side.cuda_stream, 'wgrad')
-                    if zero_bias_grads:
+                    if zero_bias:
                         grads[f'{L.conv}.bias'].zero_()
                     ready(keys)                      # a bucket all-reduce launched here is ordered behind this wgrad
                 return
             launch(st, 'chain' if side is not None else 'wgrad')
-            if zero_bias_grads:
+            if zero_bias:
                 grads[f'{L.conv}.bias'].zero_()
             if side is not None:
                 handoff(side, main)
@@ -878,7 +915,8 @@ class BiDateEngine:
             dA (pointer, leading dimension ldA): the gradient on relu(bn(z)) of L; rows: rows per statistic group of the BatchNorm-backward
             partial sums its producer left in ws.stats (0: none).  dA None: the last layer, whose dz comes from the classifier's backward.
             operand = (in0, c0, in1, c1, mode, in_bn): the weight gradient's input operand; prev as in dgrad().  Returns (gradient on
-            L's input, rows of prev's partial sums); (None, 0) for the first layer, which has no data gradient."""
+            L's input, rows of prev's partial sums); (None, 0) for the first layer, whose data gradient (the input gradient) is
+            written to dx when it is asked for."""
             hk, wk = ws.dims[L.level - 1]
             first = L is self.layers[0]
             fdt = self.first_wgrad_dtype(n, hk, wk, B) if first else None
@@ -888,6 +926,9 @@ class BiDateEngine:
                 # its staging and takes the input's split operand the forward left
                 bn_bwd_finalize(L, n, B, rows)
                 fin = ws.split_buf(('a', L.name), n * hk * wk * 2 * L.cin) if self.x3 else ws.x0
+                if dx is not None:                   # the input gradient reads the same dA, z and sums, before the weight gradient
+                    call('bdn_conv3x3_dgrad_first', self.dt, dA, L.cout, ptr(ws.z[L.name]), ptr(ws.bn[L.name]), ptr(sc['sums']), B,
+                         ptr(P[f'{L.conv}.weight']), L.cin_real, ptr(dx[0]), ptr(dx[1]), B, hk, wk, st)
 
                 def launch(stp, role):               # always on the chain's stream (last=True): the 'chain' scratch
                     part = ws.wgrad_scratch('chain', 'bdn_wgrad_workspace_bytes', n, hk, wk, L.cout, L.cin, B)
@@ -902,7 +943,10 @@ class BiDateEngine:
             elif rows and self.folds_bn_bwd(L, hk, wk):      # folding finalizes the producer's partial sums: they must exist
                 dz, out, rows_out = fold_dgrad(L, dA, n, B, rows, prev)
             else:
-                dz = bn_bwd(L, dA, ldA, n, B, rows)
+                dz = bn_bwd(L, dA, ldA, n, B, rows, plain=first and dx is not None)
+            if first and dx is not None:             # dz was stored (bn_bwd): the input gradient on the plain form
+                call('bdn_conv3x3_dgrad_first', self.dt, ptr(dz), L.cout, None, None, None, B,
+                     ptr(P[f'{L.conv}.weight']), L.cin_real, ptr(dx[0]), ptr(dx[1]), B, hk, wk, st)
             if self.x3 and dz is not None:
                 split_dz(L, dz, n, B)                # on the chain's stream, before the hand-off of the release
             release(L, lambda stp, role: wgrad_call(L, dz, *operand, n, B, stp, role), last=first)

@@ -38,7 +38,13 @@ class _Lease:
 
 class _BiDateFunction(torch.autograd.Function):
     """One autograd node for the whole network: forward enqueues the fused HIP schedule, backward the
-    hand-written backward schedule (no autograd tape through individual ops)."""
+    hand-written backward schedule (no autograd tape through individual ops).
+
+    Training mode: backward reads the activations the forward left in its (leased) workspace.  Eval mode: the forward is the
+    ordinary eval forward; backward RECOMPUTES the training-layout forward on the running statistics the forward saw (copied at
+    forward time: a training forward in between moves the buffers in place) and runs the frozen-BatchNorm backward on it.  The
+    gradient on an input image is returned only when that input requires grad, a parameter's only when it requires grad (a
+    layer whose conv weight does not launches no weight-gradient GEMM)."""
 
     @staticmethod
     def forward(ctx, module, x_d1, x_d2, *params):
@@ -50,26 +56,51 @@ class _BiDateFunction(torch.autograd.Function):
         ctx.n_params = len(params)
         if training and any(ctx.needs_input_grad):
             ctx.lease = _Lease(ws)            # nobody else may run a forward on these buffers while this graph lives
+        elif any(ctx.needs_input_grad):
+            # eval graph: backward recomputes the forward from these (autograd's version check refuses an in-place change of any of them)
+            ctx.save_for_backward(x_d1, x_d2, *params)
+            ctx.running = torch.cat([P[f'{L.bn}.{b}'].detach() for L in eng.layers for b in ('running_mean', 'running_var')])
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         module = ctx.module
-        if not ctx.training:
-            raise RuntimeError('fabric_amd: backward through an eval-mode forward is not supported '
-                               '(BatchNorm used running statistics); call model.train() first')
         eng = module.engine()
         named = list(module.named_parameters())
+        needs = ctx.needs_input_grad
         P = {k: v.detach() for k, v in module.state_dict(keep_vars=True).items()}
         grads = {k: torch.empty_like(p, dtype=torch.float32) for k, p in named}
-        lease = getattr(ctx, 'lease', None)
-        if lease is not None and ctx.ws.generation != lease.generation:
-            raise RuntimeError('fabric_amd: this graph\'s activations were overwritten by a later forward (second backward with '
-                               'retain_graph=True after another forward of the same shape): re-run the forward')
-        eng.backward(ctx.ws, dlogits, P, grads)
-        if lease is not None:
-            lease.release()                   # the activations are dead: the next forward of this shape reuses the workspace
-        return (None, None, None) + tuple(grads[k] for k, _ in named)
+        need = {k for i, (k, _) in enumerate(named) if needs[3 + i]}
+        dx = None
+        if needs[1] or needs[2]:
+            x = dlogits
+            B, _, H, W = x.shape
+            dx = tuple(torch.empty(B, eng.n_channels, H, W, dtype=torch.float32, device=x.device) for _ in range(2))
+        if ctx.training:
+            lease = getattr(ctx, 'lease', None)
+            if lease is not None and ctx.ws.generation != lease.generation:
+                raise RuntimeError('fabric_amd: this graph\'s activations were overwritten by a later forward (second backward with '
+                                   'retain_graph=True after another forward of the same shape): re-run the forward')
+            eng.backward(ctx.ws, dlogits, P, grads, dx=dx, need=need)
+            if lease is not None:
+                lease.release()               # the activations are dead: the next forward of this shape reuses the workspace
+        else:
+            x_d1, x_d2 = ctx.saved_tensors[:2]
+            off = 0
+            for L in eng.layers:              # the running statistics as the forward saw them
+                for b in ('running_mean', 'running_var'):
+                    P[f'{L.bn}.{b}'] = ctx.running[off:off + L.cout]
+                    off += L.cout
+            _, ws = eng.forward(x_d1.detach(), x_d2.detach(), P, training=False, frozen=True)
+            lease = _Lease(ws)                # a forward of this shape in a hook would otherwise take these buffers
+            try:
+                eng.backward(ws, dlogits, P, grads, dx=dx, bn_mode='running', need=need)
+            finally:
+                lease.release()
+                if eng.x3:
+                    ws.release_split()        # the recompute's per-layer split operands (as model.train(False) drops them)
+        dxs = (dx[0] if dx is not None and needs[1] else None, dx[1] if dx is not None and needs[2] else None)
+        return (None,) + dxs + tuple(grads[k] if needs[3 + i] else None for i, (k, _) in enumerate(named))
 
 
 class BiDateNet(nn.Module):

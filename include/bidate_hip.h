@@ -214,6 +214,15 @@ int bdn_conv3x3_wgrad_bnbwd_supported(int dtype, int N, int H, int W, int Cout, 
 int bdn_conv3x3_wgrad_bnbwd(int dtype, const void* dA, int ldA, const void* z, const float* bn, const float* sums,
                             int imgs_per_group, int Cout, const void* in0, int C0,
                             float* partial, float* dw_oihw, int Cin_real, int N, int H, int W, void* stream);
+/* Data gradient of the FIRST convolution (inc.conv.conv.0, models/unet_parts.py:13 in models/bidate_model.py:22-30): the gradient on the
+ * two input images.  dA [2B,H,W,ldA >= 64], z [2B,H,W,64] of the shared encoder's 2B images (date 1 first: bdn_pack_input's order),
+ * dz formed on load with bdn_bn_bwd_apply's expression from bn [G][4][64] and sums [G][2][64] (bdn_bn_bwd_finalize: batch statistics;
+ * bdn_bn_bwd_finalize_frozen on a bdn_bn_eval table: running statistics); z == NULL: dA is dz itself (bn, sums unused).  w_oihw: the
+ * float32 master weight [64][Cin_real][3][3].  Writes dx1, dx2 float32 NCHW [B,Cin_real,H,W] (date 1, date 2) directly; nothing else.
+ * dtype BDN_BF16: bf16 dA / z, dz and filter rounded to bf16; BDN_F32: float32 dA / z, three-term split bf16 product. */
+int bdn_conv3x3_dgrad_first(int dtype, const void* dA, int ldA, const void* z, const float* bn, const float* sums,
+                            int imgs_per_group, const float* w_oihw, int Cin_real,
+                            float* dx1, float* dx2, int B, int H, int W, void* stream);
 
 /* ---- BatchNorm2d training statistics: nn.BatchNorm2d, models/unet_parts.py:14,17 ----
  * Reduces the conv's per-tile partials and produces, per group g and channel c,
@@ -297,6 +306,22 @@ int bdn_bn_bwd_apply_split(const void* dA, int ldA, const void* z, const float* 
  * for a consumer that applies the backward while it stages dz (bdn_conv3x3_wgrad_bnbwd). */
 int bdn_bn_bwd_finalize(const float* bn, int G, int C, const float* partial, int rows_per_group, int raw_moment,
                         float* sums, float* dgamma, float* dbeta, void* scratch, void* stream);
+/* ---- BatchNorm2d + ReLU backward on RUNNING statistics: autograd of models/unet_parts.py:14-15,17-18 after model.eval() ----
+ * bn is bdn_bn_eval's table {running_mean, invstd, scale, shift}; the statistics are constants, so dz = scale * g under the ReLU mask.
+ * dgamma = sum g * xhat and dbeta = sum g (xhat on the running statistics: the same reduction as the training finalize), and the conv
+ * bias in front of the BatchNorm gets dbias = scale * dbeta (NULL: not written).  `sums` is left ZEROED: every consumer that forms
+ * dz = scale * (g - s0/M - xhat * s1/M) from it (bdn_conv3x3_dgrad_bb, bdn_conv3x3_wgrad_bnbwd, bdn_outc_bn_bwd_apply,
+ * bdn_conv3x3_dgrad_first) then forms the frozen dz with unchanged arithmetic.  Arguments otherwise as bdn_bn_bwd_finalize,
+ * bdn_bn_bwd_apply (dtype BDN_BF16X3: dz leaves as bdn_bn_bwd_apply_split's [N,H,W,2 C] operand) and bdn_bn_bwd. */
+int bdn_bn_bwd_finalize_frozen(const float* bn, int G, int C, const float* partial, int rows_per_group, int raw_moment,
+                               float* sums, float* dgamma, float* dbeta, float* dbias, void* scratch, void* stream);
+int bdn_bn_bwd_apply_frozen(int dtype, const void* dA, int ldA, const void* z, const float* bn,
+                            int imgs_per_group, int N, int H, int W, int C,
+                            const float* partial, int rows_per_group, int raw_moment,
+                            float* sums, float* dgamma, float* dbeta, float* dbias, void* dz, void* scratch, void* stream);
+int bdn_bn_bwd_frozen(int dtype, const void* dA, int ldA, const void* z, const float* bn,
+                      int imgs_per_group, int N, int H, int W, int C,
+                      float* ws, float* sums, float* dgamma, float* dbeta, float* dbias, void* dz, void* stream);
 
 /* a = relu(z*scale + shift) written out (nn.BatchNorm2d + nn.ReLU, models/unet_parts.py:14-15): z, out [N,H,W,C]; bn [G][4][C].
  * Rounded exactly like the on-load application inside bdn_conv3x3 / bdn_conv3x3_wgrad; bdn_conv3d_wgrad takes plain operands only. */
