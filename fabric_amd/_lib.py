@@ -107,7 +107,15 @@ SIGNATURES = {
     'bdn_sgd_step': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
     'bdn_sgd_momentum_step': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _sz, _vp]),
     'bdn_adam_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, C.c_double, C.c_double, _f, _f, _i, _i64, _sz, _vp]),
+    'bdn_sgd_step_grouped': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _f, _sz, _vp]),
+    'bdn_sgd_momentum_step_grouped': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _i, _i, _sz, _vp]),
+    'bdn_adam_step_grouped': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _f, C.c_double, C.c_double, _f, _i, _i64, _sz, _vp]),
 }
+
+
+def floats(values):
+    """A host float array for an entry point that takes per-group hyperparameters (const float*, read during the call)."""
+    return (C.c_float * len(values))(*values)
 
 _lib = None
 

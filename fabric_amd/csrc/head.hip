@@ -1067,6 +1067,193 @@ extern "C" int bdn_adam_step(float* params, const float* grads, float* exp_avg, 
     return BDN_OK;
 }
 
+// ============================================================ the same rules with parameter groups and frozen tensors (train.py:55-56,95)
+// One launch over the flat buffers in which every float4 takes the hyperparameters of the group its tensor belongs to, or is skipped
+// (frozen: neither read nor written).  FlatLayout pads every tensor to 4 floats, so a float4 never straddles two tensors.  The layout is
+// a segment table in device memory -- sorted segment ends in float4 units and one group id per segment, OPT_FROZEN for a frozen one --
+// staged in LDS once per block; the per-group hyperparameters travel by value in the kernel arguments and are staged beside it.  A
+// block's 256 consecutive vectors almost always lie in one segment: one lookup of the first vector then serves the block (the lookup is
+// per lane otherwise).  A vector behind the last segment end or with a group id outside [0, n_groups) is skipped, so a wrong table can
+// not move an access out of the buffers.  The element formulas are sgd's p -= step*g, sgdm_elem and adam_elem above; the pass keeps
+// their shape (OPT_VEC float4s per thread, every load issued before the first store, no reductions, no atomics).
+constexpr int OPT_MAX_GROUPS = 8;
+constexpr int OPT_MAX_SEGS = 256;
+constexpr int OPT_FROZEN = -1;
+
+struct SegTable { const uint32_t* end; const int32_t* group; int n_seg, n_groups; };
+template <typename P> struct GroupArgs { P g[OPT_MAX_GROUPS]; };
+
+struct RuleSgd {                                        // plain SGD: bdn_sgd_step's p -= (lr * grad_scale) * g
+    using Params = float;
+    static constexpr int NS = 0;
+    static __device__ __forceinline__ bool reads_state(const Params&) { return false; }
+    static __device__ __forceinline__ void elem(float& p, float g, float&, float&, const Params& step) { p -= step * g; }
+};
+template <bool MOM> struct RuleSgdm {
+    using Params = SgdmParams;
+    static constexpr int NS = MOM ? 1 : 0;
+    static __device__ __forceinline__ bool reads_state(const Params& a) { return MOM && !a.first; }
+    static __device__ __forceinline__ void elem(float& p, float g, float& buf, float&, const Params& a) { sgdm_elem<MOM>(p, g, buf, a); }
+};
+struct RuleAdam {
+    using Params = AdamParams;
+    static constexpr int NS = 2;
+    static __device__ __forceinline__ bool reads_state(const Params&) { return true; }
+    static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v, const Params& a) { adam_elem(p, g, m, v, a); }
+};
+
+// One halving step of the lookup "first s with end[s] > i" over the LDS table, which is padded with UINT32_MAX to `cap` entries, a power
+// of two: branch-free, so the OPT_VEC lookups of a pass advance side by side (their LDS reads are independent) and lanes never diverge.
+__device__ __forceinline__ void seg_step(const uint32_t* s_end, int h, uint32_t i, int& s) {
+    if (s_end[s + h - 1] <= i) s += h;
+}
+
+template <typename Rule>
+__global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                      float* __restrict__ s1, SegTable t, GroupArgs<typename Rule::Params> a, size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS];
+    __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
+    int cap = 1;
+    while (cap < t.n_seg) cap <<= 1;
+    for (int k = threadIdx.x; k < cap; k += 256) {
+        s_end[k] = k < t.n_seg ? t.end[k] : 0xffffffffu;
+        s_grp[k] = k < t.n_seg ? t.group[k] : OPT_FROZEN;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < OPT_MAX_GROUPS; k++) s_par[k] = a.g[k];
+    }
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
+        int gid[OPT_VEC], seg[OPT_VEC] = {};
+        for (int h = cap >> 1; h > 0; h >>= 1) {             // the segment of each pass's first vector (clamped: a pass past the end is skipped below)
+#pragma unroll
+            for (int u = 0; u < OPT_VEC; u++) {
+                const size_t first = b0 + u * stride;
+                seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), seg[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t first = b0 + u * stride, i = first + threadIdx.x;
+            int grp = OPT_FROZEN;
+            if (i < n4) {
+                const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
+                int s = seg[u];
+                if (!(s_end[s] > last)) {                    // the block's 256 vectors span a boundary (or lie behind the table): per lane
+                    s = 0;
+                    for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+                }
+                if (s_end[s] > i) grp = s_grp[s];
+            }
+            gid[u] = (unsigned)grp < (unsigned)t.n_groups ? grp : OPT_FROZEN;
+        }
+        float4 P[OPT_VEC], G[OPT_VEC], S0[OPT_VEC] = {}, S1[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (gid[u] != OPT_FROZEN) {
+                P[u] = reinterpret_cast<const float4*>(p)[i]; G[u] = reinterpret_cast<const float4*>(g)[i];
+                if (Rule::NS > 0 && Rule::reads_state(s_par[0])) S0[u] = reinterpret_cast<const float4*>(s0)[i];
+                if (Rule::NS > 1) S1[u] = reinterpret_cast<const float4*>(s1)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (gid[u] != OPT_FROZEN) {
+                const typename Rule::Params q = s_par[gid[u]];
+                Rule::elem(P[u].x, G[u].x, S0[u].x, S1[u].x, q); Rule::elem(P[u].y, G[u].y, S0[u].y, S1[u].y, q);
+                Rule::elem(P[u].z, G[u].z, S0[u].z, S1[u].z, q); Rule::elem(P[u].w, G[u].w, S0[u].w, S1[u].w, q);
+                reinterpret_cast<float4*>(p)[i] = P[u];
+                if (Rule::NS > 0) reinterpret_cast<float4*>(s0)[i] = S0[u];
+                if (Rule::NS > 1) reinterpret_cast<float4*>(s1)[i] = S1[u];
+            }
+        }
+    }
+}
+
+static int grouped_check(const char* what, const void* params, const void* grads, const void* s0, const void* s1, const uint32_t* seg_end,
+                         const int32_t* seg_group, int n_seg, int n_groups, const float* lr, size_t n) {
+    if (!params || !grads || !seg_end || !seg_group || !lr) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (n_groups < 1 || n_groups > OPT_MAX_GROUPS)
+        BDN_FAIL(BDN_E_ARG, "%s: %d groups (1..%d: their hyperparameters travel in the kernel arguments)", what, n_groups, OPT_MAX_GROUPS);
+    if (n_seg < 1 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d segments (1..%d)", what, n_seg, OPT_MAX_SEGS);
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)s0 | (uintptr_t)s1) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
+    if (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3) BDN_FAIL(BDN_E_ARG, "%s: segment table must be 4-byte aligned", what);
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
+    return BDN_OK;
+}
+
+extern "C" int bdn_sgd_step_grouped(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg,
+                                    int n_groups, const float* lr, float grad_scale, size_t n, void* stream) {
+    if (int rc = grouped_check("sgd_step_grouped", params, grads, nullptr, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+    if (n == 0) return BDN_OK;
+    GroupArgs<float> a{};
+    for (int k = 0; k < n_groups; k++) a.g[k] = lr[k] * grad_scale;
+    const SegTable t{seg_end, seg_group, n_seg, n_groups};
+    hipLaunchKernelGGL(grouped_kernel<RuleSgd>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads, (float*)nullptr,
+                       (float*)nullptr, t, a, n / 4);
+    BDN_CHECK_LAUNCH("sgd_step_grouped");
+    return BDN_OK;
+}
+
+extern "C" int bdn_sgd_momentum_step_grouped(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                                             const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                             float grad_scale, float momentum, float dampening, int nesterov, int first_step, size_t n,
+                                             void* stream) {
+    if (int rc = grouped_check("sgd_momentum_step_grouped", params, grads, momentum_buf, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n))
+        return rc;
+    if (!weight_decay) BDN_FAIL(BDN_E_ARG, "sgd_momentum_step_grouped: null pointer");
+    if ((momentum != 0.f) != (momentum_buf != nullptr))
+        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step_grouped: momentum_buf must be given iff momentum != 0");
+    if (nesterov && (momentum <= 0.f || dampening != 0.f))
+        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step_grouped: nesterov needs momentum > 0 and zero dampening");
+    if (n == 0) return BDN_OK;
+    GroupArgs<SgdmParams> a{};
+    for (int k = 0; k < n_groups; k++)
+        a.g[k] = SgdmParams{lr[k], grad_scale, momentum, (float)(1.0 - (double)dampening), weight_decay[k], first_step ? 1 : 0, nesterov ? 1 : 0};
+    for (int k = n_groups; k < OPT_MAX_GROUPS; k++) a.g[k].first = first_step ? 1 : 0;        // reads_state() asks entry 0 only; keep all alike
+    const SegTable t{seg_end, seg_group, n_seg, n_groups};
+    if (momentum_buf)
+        hipLaunchKernelGGL(grouped_kernel<RuleSgdm<true>>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                           momentum_buf, (float*)nullptr, t, a, n / 4);
+    else
+        hipLaunchKernelGGL(grouped_kernel<RuleSgdm<false>>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                           (float*)nullptr, (float*)nullptr, t, a, n / 4);
+    BDN_CHECK_LAUNCH("sgd_momentum_step_grouped");
+    return BDN_OK;
+}
+
+extern "C" int bdn_adam_step_grouped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
+                                     const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                     float grad_scale, double beta1, double beta2, float eps, int decoupled_weight_decay, long long step,
+                                     size_t n, void* stream) {
+    if (int rc = grouped_check("adam_step_grouped", params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+    if (!exp_avg || !exp_avg_sq || !weight_decay) BDN_FAIL(BDN_E_ARG, "adam_step_grouped: null pointer");
+    if (step < 1) BDN_FAIL(BDN_E_ARG, "adam_step_grouped: step must be >= 1 (1-based, counted after the increment), got %lld", step);
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0))
+        BDN_FAIL(BDN_E_ARG, "adam_step_grouped: betas must lie in [0, 1)");
+    if (n == 0) return BDN_OK;
+    // 1 - beta and the bias corrections in double on the host, exactly as bdn_adam_step forms them
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    const float w1 = (float)(1.0 - beta1);
+    const bool dec = decoupled_weight_decay != 0;
+    GroupArgs<AdamParams> a{};
+    for (int k = 0; k < n_groups; k++)
+        a.g[k] = AdamParams{grad_scale, w1, (float)beta2, (float)(1.0 - beta2), eps, dec ? 0.f : weight_decay[k],
+                            dec ? (float)(1.0 - (double)lr[k] * (double)weight_decay[k]) : 1.f, (float)((double)lr[k] / bc1),
+                            (float)std::sqrt(bc2), w1 >= 0.5f ? 1 : 0};
+    const SegTable t{seg_end, seg_group, n_seg, n_groups};
+    hipLaunchKernelGGL(grouped_kernel<RuleAdam>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, t, a, n / 4);
+    BDN_CHECK_LAUNCH("adam_step_grouped");
+    return BDN_OK;
+}
+
 // ============================================================ misc
 static thread_local char g_err[512] = "";
 void bdn_set_error(const char* fmt, ...) {

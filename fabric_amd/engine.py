@@ -686,6 +686,21 @@ class BiDateEngine:
             return self.bwd_dtype
         return None
 
+    def chain_end(self, need, dx=None):
+        """Where backward's chain stops: None (it runs to the first layer: every parameter wanted, an input gradient wanted, or the
+        first layer itself trainable), 'outc' (no 3x3 layer wanted), or the name of the LAST layer, in backward's order d4b ... d1a,
+        e5b ... e1a, with a wanted gradient (conv weight or bias, BatchNorm weight or bias).  Nothing below that layer has a reader, so
+        its own data gradient and every enc_skip_bwd / upsample2x_bwd / BatchNorm-backward / data-gradient launch after it is not
+        enqueued.  One exception keeps a launch: a layer that forms its dz inside its data-gradient conv (folds_bn_bwd) still runs
+        that kernel when it is the last one, because the kernel is also what stores dz for the weight gradient."""
+        if need is None or dx is not None:
+            return None
+        last = 'outc'
+        for L in reversed(self.layers):
+            if any(k in need for k in (f'{L.conv}.weight', f'{L.conv}.bias', f'{L.bn}.weight', f'{L.bn}.bias')):
+                last = L.name
+        return None if last == self.layers[0].name else last
+
     def wgrad_launch(self, L, c0, c1, mode):
         """(dtype, c0, c1, mode, flags word) of layer L's weight-gradient GEMM on an operand of c0 (+ c1) channels in `mode`.  bf16x3: one
         split operand of c0 + c1 channels; the LAST GEMM on the second queue (e1b) on a grid of its own in the three-term backward."""
@@ -732,7 +747,9 @@ class BiDateEngine:
         dx: None, or (dx1, dx2) float32 [B,n_channels,H,W] tensors that receive the gradient on the two input images
         (bdn_conv3x3_dgrad_first after the first layer's BatchNorm backward).
         need: None (every parameter), or the set of state-dict keys whose gradient is wanted: a layer whose conv weight is not in it
-        launches no weight-gradient GEMM (its grads entries are left as they are)."""
+        launches no weight-gradient GEMM (its grads entries are left as they are), and the chain stops at the last layer that has a wanted
+        gradient (chain_end): the layers behind it launch nothing, their grads entries are left as they are, and on_ready reports their
+        keys once at the end, so that every gradient bucket is still released exactly once."""
         if bn_mode not in ('batch', 'running'):
             raise ValueError(f"bn_mode must be 'batch' or 'running', got {bn_mode!r}")
         frozen = bn_mode == 'running'
@@ -749,6 +766,8 @@ class BiDateEngine:
         side = self._side_stream(dev) if wgrad_stream else None
         keep = []                                    # every temporary lives to the end of the pass: the second queue may still read it
         n_hand = [0]
+        end = self.chain_end(need, dx)               # None: the whole chain (the need=None schedule, launch for launch)
+        released = set()                             # layers whose gradients were reported ready
 
         def handoff(src, dst):
             """Order what `dst` enqueues from now on behind what `src` has enqueued: a device-local event without the system-scope
@@ -892,6 +911,7 @@ class BiDateEngine:
             the end of the step).  The chain then joins the second queue: the bucket this ready() may release holds gradients whose GEMMs
             are still queued there.  Without a second stream everything runs on the chain's."""
             keys = [f'{L.bn}.weight', f'{L.bn}.bias', f'{L.conv}.weight', f'{L.conv}.bias']
+            released.add(L.name)
             if need is not None and f'{L.conv}.weight' not in need:
                 launch = lambda stp, role: None        # noqa: E731  (frozen layer: no weight-gradient GEMM)
             zero_bias = zero_bias_grads and not frozen   # on running statistics the conv-bias gradient is scale * dbeta (bn_bwd_finalize)
@@ -950,58 +970,74 @@ class BiDateEngine:
             if self.x3 and dz is not None:
                 split_dz(L, dz, n, B)                # on the chain's stream, before the hand-off of the release
             release(L, lambda stp, role: wgrad_call(L, dz, *operand, n, B, stp, role), last=first)
-            if out is None and not first:
+            if out is None and not first and L.name != end:      # the chain's last layer: its data gradient has no reader
                 out, rows_out = dgrad(L, dz, n, B, prev)
             keep.extend((dz, out))
             return out, rows_out
 
-        # ---- classifier: its data gradient is never stored -- bdn_outc_bwd leaves the BatchNorm-backward partial sums of d4b
-        L4b = by['d4b']
-        call('bdn_outc_bwd', self.dt, ptr(dlogits), ptr(ws.z['d4b']), ptr(ws.bn['d4b']), ptr(P['outc.conv.weight']),
-             None, ptr(grads['outc.conv.weight']), ptr(grads['outc.conv.bias']), ptr(ws.stats),
-             ptr(ws.outc_ws(self)), B, H, W, L4b.cout, self.n_classes, st)
-        ready(['outc.conv.weight', 'outc.conv.bias'])
-        # ---- decoder: d_j b on the gradient upsample2x_bwd(_bs) leaves (j = 4: on the classifier's), d_j a on d_j b's data gradient
-        dA, ldA, rows = None, 0, _lib.load().bdn_outc_bwd_rows(self.dt, B, H, W, L4b.cout)
-        dcat = {}
-        for j in range(4, 0, -1):
-            k = 5 - j
-            hk, wk = ws.dims[k - 1]
-            hs, wsrc = ws.dims[k]
-            La, Lb = by[f'd{j}a'], by[f'd{j}b']
-            ck = ENC_CH[k - 1]
-            cprev = La.cin - ck
-            dAa, rows = layer(Lb, B, dA, ldA, rows, (ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name]), prev=La)
-            # bf16x3: the operand is the split buffer the forward left (('a', layer)); the float32 skip / upsampled map do not exist
-            dc, _ = layer(La, B, ptr(dAa), La.cout, rows, (None if self.x3 else ws.f[k], ck, None if self.x3 else ws.U[j], cprev, IN_PLAIN, None))
-            dcat[k] = dc                             # [B,hk,wk, ck + cprev] = [dF_k | dU_j]
-            dprev = e(B, hs, wsrc, cprev)
-            keep.append(dprev)
-            rows = _lib.load().bdn_upsample2x_bwd_rows(self.dt, B, hs, wsrc, cprev) if j > 1 else 0
-            if rows:
-                # the gradient lands on relu(bn(z)) of the previous decoder stage: its BatchNorm-backward partial sums come out of the same pass
-                Lp = by[f'd{j - 1}b']
-                call('bdn_upsample2x_bwd_bs', self.dt, dc.data_ptr() + ck * self.esize, La.cin, ptr(dprev), ptr(ws.z[Lp.name]),
-                     ptr(ws.bn[Lp.name]), ptr(ws.stats), B, hs, wsrc, hk, wk, cprev, st)
-            else:
-                call('bdn_upsample2x_bwd', self.dt, dc.data_ptr() + ck * self.esize, La.cin, ptr(dprev), B, hs, wsrc, hk, wk, cprev, st)
-            dA, ldA = ptr(dprev), cprev
-        # ---- encoder (both dates at once): e_k b on the gradient enc_skip_bwd leaves, e_k a on e_k b's data gradient
-        dF, dP = dprev, None
-        for k in range(5, 0, -1):
-            hk, wk = ws.dims[k - 1]
-            La, Lb = by[f'e{k}a'], by[f'e{k}b']
-            ck = ENC_CH[k - 1]
-            if k < 5:
-                dF = dcat[k]
-            dAb = e(2 * B, hk, wk, ck)
-            keep.append(dAb)
-            call('bdn_enc_skip_bwd', self.dt, ptr(dF), dF.shape[3], ptr(ws.z[Lb.name]), ptr(ws.bn[Lb.name]),
-                 ptr(dP), ptr(dAb), ptr(ws.stats), B, hk, wk, ck, st)
-            dAa, rows = layer(Lb, 2 * B, ptr(dAb), ck, _lib.load().bdn_enc_skip_bwd_rows(self.dt, B, hk, wk, ck),
-                              (ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name]), prev=La)
-            src = ws.x0 if k == 1 else (None if self.x3 else ws.pool[k])
-            dP, _ = layer(La, 2 * B, ptr(dAa), La.cout, rows, (src, La.cin, None, 0, IN_PLAIN, None))
+        def chain():
+            """The schedule from the classifier down; returns early behind the layer chain_end() names."""
+            # ---- classifier: its data gradient is never stored -- bdn_outc_bwd leaves the BatchNorm-backward partial sums of d4b
+            L4b = by['d4b']
+            call('bdn_outc_bwd', self.dt, ptr(dlogits), ptr(ws.z['d4b']), ptr(ws.bn['d4b']), ptr(P['outc.conv.weight']),
+                 None, ptr(grads['outc.conv.weight']), ptr(grads['outc.conv.bias']), ptr(ws.stats),
+                 ptr(ws.outc_ws(self)), B, H, W, L4b.cout, self.n_classes, st)
+            ready(['outc.conv.weight', 'outc.conv.bias'])
+            if end == 'outc':
+                return
+            # ---- decoder: d_j b on the gradient upsample2x_bwd(_bs) leaves (j = 4: on the classifier's), d_j a on d_j b's data gradient
+            dA, ldA, rows = None, 0, _lib.load().bdn_outc_bwd_rows(self.dt, B, H, W, L4b.cout)
+            dcat = {}
+            for j in range(4, 0, -1):
+                k = 5 - j
+                hk, wk = ws.dims[k - 1]
+                hs, wsrc = ws.dims[k]
+                La, Lb = by[f'd{j}a'], by[f'd{j}b']
+                ck = ENC_CH[k - 1]
+                cprev = La.cin - ck
+                dAa, rows = layer(Lb, B, dA, ldA, rows, (ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name]), prev=La)
+                if end == Lb.name:
+                    return
+                # bf16x3: the operand is the split buffer the forward left (('a', layer)); the float32 skip / upsampled map do not exist
+                dc, _ = layer(La, B, ptr(dAa), La.cout, rows, (None if self.x3 else ws.f[k], ck, None if self.x3 else ws.U[j], cprev, IN_PLAIN, None))
+                if end == La.name:
+                    return
+                dcat[k] = dc                             # [B,hk,wk, ck + cprev] = [dF_k | dU_j]
+                dprev = e(B, hs, wsrc, cprev)
+                keep.append(dprev)
+                rows = _lib.load().bdn_upsample2x_bwd_rows(self.dt, B, hs, wsrc, cprev) if j > 1 else 0
+                if rows:
+                    # the gradient lands on relu(bn(z)) of the previous decoder stage: its BatchNorm-backward partial sums come out of the same pass
+                    Lp = by[f'd{j - 1}b']
+                    call('bdn_upsample2x_bwd_bs', self.dt, dc.data_ptr() + ck * self.esize, La.cin, ptr(dprev), ptr(ws.z[Lp.name]),
+                         ptr(ws.bn[Lp.name]), ptr(ws.stats), B, hs, wsrc, hk, wk, cprev, st)
+                else:
+                    call('bdn_upsample2x_bwd', self.dt, dc.data_ptr() + ck * self.esize, La.cin, ptr(dprev), B, hs, wsrc, hk, wk, cprev, st)
+                dA, ldA = ptr(dprev), cprev
+            # ---- encoder (both dates at once): e_k b on the gradient enc_skip_bwd leaves, e_k a on e_k b's data gradient
+            dF, dP = dprev, None
+            for k in range(5, 0, -1):
+                hk, wk = ws.dims[k - 1]
+                La, Lb = by[f'e{k}a'], by[f'e{k}b']
+                ck = ENC_CH[k - 1]
+                if k < 5:
+                    dF = dcat[k]
+                dAb = e(2 * B, hk, wk, ck)
+                keep.append(dAb)
+                call('bdn_enc_skip_bwd', self.dt, ptr(dF), dF.shape[3], ptr(ws.z[Lb.name]), ptr(ws.bn[Lb.name]),
+                     ptr(dP), ptr(dAb), ptr(ws.stats), B, hk, wk, ck, st)
+                dAa, rows = layer(Lb, 2 * B, ptr(dAb), ck, _lib.load().bdn_enc_skip_bwd_rows(self.dt, B, hk, wk, ck),
+                                  (ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name]), prev=La)
+                if end == Lb.name:
+                    return
+                src = ws.x0 if k == 1 else (None if self.x3 else ws.pool[k])
+                dP, _ = layer(La, 2 * B, ptr(dAa), La.cout, rows, (src, La.cin, None, 0, IN_PLAIN, None))
+                if end == La.name:
+                    return
+        chain()
         if side is not None:
             handoff(side, main)                      # every weight gradient is complete before the caller's next kernel
+        if end is not None:                          # the layers behind the chain's end: nothing was launched, their buckets are still due
+            ready([k for L in self.layers if L.name not in released
+                   for k in (f'{L.bn}.weight', f'{L.bn}.bias', f'{L.conv}.weight', f'{L.conv}.bias')])
         return grads

@@ -157,3 +157,183 @@ def torch_to_flat(sd, layout, names, device=None):
     else:
         step = 1 if present else 0
     return cfg, flat, step
+
+
+# ------------------------------------------------------------------ parameter groups and frozen parameters
+MAX_GROUPS = 8            # include/bidate_hip.h: the per-group hyperparameters travel in the kernel arguments
+FROZEN = -1               # the reserved group id of a frozen segment
+GROUP_KEYS = ('lr', 'weight_decay')
+
+
+def _number(name, v):
+    if not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
+        raise ValueError(f'invalid {name}: {v!r} (must be a finite number >= 0)')
+    return float(v)
+
+
+class ParamGroups:
+    """Validated parameter groups of the fused step over parameter NAMES (state-dict keys).
+
+    ``names``: every parameter in ``model.parameters()`` order; ``groups``: a list of dicts ``{'params': [names], 'lr': ...,
+    'weight_decay': ...}`` (a missing key takes cfg's value), or None for one group of every trainable parameter; ``frozen``: the
+    names with requires_grad=False.  A frozen parameter may be listed in a group, as torch.optim allows (it keeps its place in the
+    group's 'params' for the state exchange), but it is never updated and carries no state.  ``self.groups`` is a list of plain dicts
+    that the step reads at every update, so ``groups[i]['lr'] = x`` works as it does on a torch optimizer.
+
+    ValueError: more than MAX_GROUPS groups, an unknown name, a name listed twice, a trainable parameter in no group (torch would
+    silently leave it untrained; here that is an error, never a silent freeze), or a per-group key other than lr / weight_decay whose
+    value differs from the step's rule (momentum, dampening, nesterov, betas, eps are one per step)."""
+
+    def __init__(self, cfg, names, groups=None, frozen=()):
+        self.names = list(names)
+        self.frozen = set(frozen)
+        known = set(self.names)
+        if self.frozen - known:
+            raise ValueError(f'unknown frozen parameter(s) {sorted(self.frozen - known)}')
+        if groups is None:
+            groups = [{'params': [k for k in self.names if k not in self.frozen]}]
+        groups = list(groups)
+        if len(groups) > MAX_GROUPS:
+            raise ValueError(f'{len(groups)} param groups: the fused step takes at most {MAX_GROUPS}')
+        rule = cfg.param_group([])
+        self.groups, self.group_of = [], {}
+        for j, g in enumerate(groups):
+            if 'params' not in g:
+                raise ValueError(f"param group {j} has no 'params'")
+            out = {'params': list(g['params']), 'lr': cfg.lr, 'weight_decay': cfg.weight_decay}
+            for key, v in g.items():
+                if key == 'params':
+                    continue
+                if key in GROUP_KEYS:
+                    out[key] = _number(key, v)
+                elif key not in rule:
+                    raise ValueError(f'param group {j}: unknown key {key!r}')
+                elif (tuple(v) if key == 'betas' else v) != rule[key]:
+                    raise ValueError(f'param group {j}: per-group {key} = {v!r} differs from the step\'s {rule[key]!r}; only '
+                                     f'lr and weight_decay may differ between groups')
+            for k in out['params']:
+                if k not in known:
+                    raise ValueError(f'param group {j}: unknown parameter {k!r}')
+                if k in self.group_of:
+                    raise ValueError(f'parameter {k!r} appears in more than one param group (or twice in one)')
+                self.group_of[k] = j
+            self.groups.append(out)
+        left = [k for k in self.names if k not in self.frozen and k not in self.group_of]
+        if left:
+            raise ValueError(f'{len(left)} trainable parameter(s) in no param group (first: {left[0]!r}): list them, or set '
+                             f'requires_grad=False to freeze them')
+
+    def trainable(self):
+        """Names that are updated, in model.parameters() order."""
+        return [k for k in self.names if k not in self.frozen]
+
+    def group_id(self, name):
+        return FROZEN if name in self.frozen else self.group_of[name]
+
+    def hyper(self, key):
+        """The current per-group values of 'lr' or 'weight_decay' (read from the live dicts)."""
+        return [_number(key, g[key]) for g in self.groups]
+
+
+def segment_table(layout, groups):
+    """(ends, ids) of bdn_*_step_grouped's segment table for ``layout`` (FlatLayout: every tensor padded to a float4) and ``groups``
+    (ParamGroups): the sorted segment ends in float4 units and the group id of each segment, FROZEN for frozen tensors.  The segments
+    tile [0, layout.total / 4); adjacent tensors of one group share a segment."""
+    ends, ids = [], []
+    for i, k in enumerate(layout.order):
+        end = (layout.slices[layout.order[i + 1]][0] if i + 1 < len(layout.order) else layout.total) // 4
+        gid = groups.group_id(k)
+        if ids and ids[-1] == gid:
+            ends[-1] = end
+        else:
+            ends.append(end)
+            ids.append(gid)
+    return ends, ids
+
+
+def groups_to_torch(cfg, groups, layout, flat_state, step):
+    """torch.optim's ``state_dict()`` of a grouped step: what ``torch.optim.{SGD,Adam,AdamW}`` built with the same param groups holds.
+    One 'param_groups' entry per group with torch 2.10's keys; a parameter is identified by its index in ``model.parameters()``
+    (torch's load_state_dict matches the entries of a group by position, so any optimizer whose groups list the same parameters in
+    the same order loads it).  No state entry for a frozen parameter, as torch keeps none for a parameter whose grad is None.  Every
+    tensor is a copy."""
+    index = {k: i for i, k in enumerate(groups.names)}
+    state = {}
+    keys = cfg.state_keys()
+    if keys and step > 0:
+        for k in groups.trainable():
+            s = {key: layout.view(flat_state[key], k).clone() for key in keys}
+            if cfg.family == 'adam':
+                s = {'step': torch.tensor(float(step), dtype=torch.float32), **s}
+            state[index[k]] = s
+    out = []
+    for g in groups.groups:
+        pg = cfg.param_group([index[k] for k in g['params']])
+        pg['lr'], pg['weight_decay'] = float(g['lr']), float(g['weight_decay'])
+        out.append(pg)
+    return {'state': state, 'param_groups': out}
+
+
+def torch_to_groups(sd, groups, layout, device=None):
+    """Inverse of groups_to_torch: (cfg, per-group [{'lr', 'weight_decay'}] or None, flat_state, step) from the ``state_dict()`` of a torch
+    SGD / Adam / AdamW built with the same param groups as ``groups`` (ParamGroups), or groups_to_torch's output.  As in torch, the
+    saved entries are matched to the step's by POSITION (k-th parameter of the j-th group), whatever ids the file uses, and the saved
+    hyperparameters replace the step's.  ValueError: another number of groups or of parameters in one, hyperparameters other than lr
+    / weight_decay that differ between the saved groups, shapes that do not fit, state for only some of the trainable parameters, or
+    different step counts.  State saved for a parameter that is frozen here is dropped."""
+    saved = sd['param_groups']
+    mine = groups.groups
+    if len(saved) == 1 and len(saved[0]['params']) == len(groups.names) and [len(g['params']) for g in mine] != [len(groups.names)]:
+        # an ungrouped state over every parameter in model.parameters() order (flat_to_torch's output): the state is taken by name; one
+        # saved set of hyperparameters cannot describe the groups, which keep theirs (None is returned in their place)
+        mine = None
+    elif len(saved) != len(mine):
+        raise ValueError(f'optimizer state has {len(saved)} param groups, the step has {len(mine)}')
+    cfgs = [OptimConfig.from_param_group(g) for g in saved]
+    cfg = cfgs[0]
+    rule = {k: v for k, v in cfg.param_group([]).items() if k not in GROUP_KEYS + ('params',)}
+    name_of = {}
+    for j, (g, c) in enumerate(zip(saved, cfgs)):
+        other = {k: v for k, v in c.param_group([]).items() if k not in GROUP_KEYS + ('params',)}
+        if other != rule:
+            diff = sorted(k for k in rule if rule[k] != other[k])
+            raise ValueError(f'param group {j} differs from group 0 in {diff}: only lr and weight_decay may differ between groups')
+        listed = groups.names if mine is None else mine[j]['params']
+        if len(g['params']) != len(listed):
+            raise ValueError(f'param group {j}: the optimizer state covers {len(g["params"])} parameters, the step\'s group {len(listed)}')
+        for pid, k in zip(g['params'], listed):
+            name_of[pid] = k
+    states = sd['state']
+    keys = cfg.state_keys()
+    if device is None:
+        device = next((v.device for s in states.values() for v in s.values() if torch.is_tensor(v) and v.dim() > 0), 'cpu')
+    flat = {key: torch.zeros(layout.total, dtype=torch.float32, device=device) for key in keys}
+    train = set(groups.trainable())
+    present = [pid for pid, k in name_of.items() if k in train and states.get(pid)]
+    n_train = sum(1 for k in name_of.values() if k in train)
+    if present and len(present) != n_train:
+        raise ValueError(f'optimizer state for {len(present)} of {n_train} trainable parameters: the flat state needs all or none')
+    if present and not keys:
+        raise ValueError(f'optimizer state present, but {cfg.kind} with momentum {cfg.momentum} keeps none')
+    steps = set()
+    for pid in present:
+        name, s = name_of[pid], states[pid]
+        shape = layout.slices[name][2]
+        if set(s) - {'step'} != set(keys):
+            raise ValueError(f'parameter {pid} ({name}): state keys {sorted(s)}, expected {sorted(keys)}'
+                             + (' and step' if cfg.family == 'adam' else ''))
+        for key in keys:
+            if tuple(s[key].shape) != shape:
+                raise ValueError(f'parameter {pid} ({name}): {key} has shape {tuple(s[key].shape)}, the parameter {shape}')
+            layout.view(flat[key], name).copy_(s[key].detach().to(device=device, dtype=torch.float32))
+        if cfg.family == 'adam':
+            if s.get('step') is None:
+                raise ValueError(f'parameter {pid} ({name}): no step in the Adam state')
+            steps.add(float(s['step']))
+    if len(steps) > 1:
+        raise ValueError(f'parameters were stepped different numbers of times ({sorted(steps)}): the flat state needs one count')
+    if cfg.family == 'adam':
+        step = int(steps.pop()) if steps else 0
+    else:
+        step = 1 if present else 0
+    return cfg, None if mine is None else [{'lr': c.lr, 'weight_decay': c.weight_decay} for c in cfgs], flat, step

@@ -177,6 +177,47 @@ def make_torch_optimizer(params, lr, optimizer='sgd', momentum=0.0, nesterov=Fal
     return cls(params, lr=c.lr, betas=c.betas, eps=c.eps, weight_decay=c.weight_decay)
 
 
+def fine_tune_groups(model, lr, weight_decay, freeze=(), no_decay_norm_bias=False, lr_scale=()):
+    """--freeze / --no_decay_norm_bias / --lr_scale as TrainStep's `param_groups`.  Sets requires_grad=False on every parameter whose
+    state-dict name starts with one of the `freeze` prefixes (TrainStep freezes those), and returns the groups of the others by name --
+    one per (lr factor, decays or not) combination in use: `lr_scale` is [(prefix, factor)] (the first matching prefix counts, others
+    get factor 1), and with no_decay_norm_bias every 1-D tensor (BatchNorm weights and biases, conv biases) has weight_decay 0.  None
+    when the flags ask for nothing (no groups: the ungrouped step).  A prefix that matches no parameter, or more than 8 groups,
+    raises ValueError."""
+    freeze, lr_scale = tuple(freeze), list(lr_scale)
+    named = list(model.named_parameters())
+    for pre in freeze + tuple(q for q, _ in lr_scale):
+        if not any(k.startswith(pre) for k, _ in named):
+            raise ValueError(f'prefix {pre!r} matches no parameter (names start with inc, down1..4, up1..4, outc)')
+    for k, p in named:
+        if k.startswith(freeze):
+            p.requires_grad_(False)
+    if not (no_decay_norm_bias or lr_scale):
+        return None
+    groups = {}
+    for k, p in named:
+        if not p.requires_grad:
+            continue
+        factor = next((f for q, f in lr_scale if k.startswith(q)), 1.0)
+        decay = not (no_decay_norm_bias and p.dim() == 1)
+        g = groups.setdefault((factor, decay), {'params': [], 'lr': lr * factor})
+        if not decay:
+            g['weight_decay'] = 0.0
+        elif weight_decay is not None:
+            g['weight_decay'] = weight_decay
+        g['params'].append(k)
+    if len(groups) > 8:
+        raise ValueError(f'{len(groups)} parameter groups (lr factors x decay): the fused step takes at most 8')
+    return list(groups.values())
+
+
+def _lr_scale(text):
+    prefix, _, factor = text.partition('=')
+    if not prefix or not factor:
+        raise argparse.ArgumentTypeError(f'{text!r}: expected PREFIX=FACTOR')
+    return prefix, float(factor)
+
+
 _CKPT = re.compile(r'checkpoint_epoch_(\d+)\.state_dict\.pt$')
 
 
@@ -258,6 +299,15 @@ def main(argv=None):
     ap.add_argument('--adam_eps', type=float, default=1e-8, help='adam / adamw')
     ap.add_argument('--resume', default=None, help='DIR/checkpoint_epoch_N.state_dict.pt (and its sibling optimizer_epoch_N.pt): '
                                                    'continue at epoch N + 1 of --epochs')
+    ap.add_argument('--init_from', default=None, help='a checkpoint load_checkpoint reads (the reference\'s pickles and module.-prefixed '
+                                                      'state dicts included): weights and BatchNorm buffers only, training starts at epoch 0 '
+                                                      'with a fresh optimizer -- the fine-tuning start')
+    ap.add_argument('--freeze', nargs='+', default=[], metavar='PREFIX',
+                    help='state-dict name prefixes whose parameters are not trained, e.g. inc down1 down2 down3 down4 (the encoder)')
+    ap.add_argument('--frozen_bn', action='store_true', help='BatchNorm on its running statistics, which stay as loaded')
+    ap.add_argument('--no_decay_norm_bias', action='store_true', help='no weight decay on BatchNorm weights / biases and conv biases')
+    ap.add_argument('--lr_scale', nargs='+', default=[], type=_lr_scale, metavar='PREFIX=FACTOR',
+                    help='learning rate x FACTOR for the parameters under PREFIX, e.g. inc=0.1 down1=0.1')
     ap.add_argument('--device_patches', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=False,
                     help='cut and augment the patch pairs on the device from city stacks kept in HBM (fabric_amd.device_loader) '
                          'instead of on the host; --num_workers does not apply then')
@@ -289,6 +339,12 @@ def main(argv=None):
                     betas=opt.betas, eps=opt.adam_eps)
     except ValueError as e:
         raise SystemExit(f'--optimizer {opt.optimizer}: {e}')
+    grouped = bool(opt.freeze or opt.frozen_bn or opt.no_decay_norm_bias or opt.lr_scale)
+    if grouped and opt.loss_function != 'tversky':
+        raise SystemExit(f'--freeze / --frozen_bn / --no_decay_norm_bias / --lr_scale are built into the fused step, which runs '
+                         f'--loss_function tversky only (got {opt.loss_function})')
+    if opt.init_from and opt.resume:
+        raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
 
     # one process per GPU (launched by torch.distributed.run): RANK / LOCAL_RANK / WORLD_SIZE from the environment
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -329,6 +385,9 @@ def main(argv=None):
     opt_sd, first_epoch = None, 0
     if opt.resume:
         model, opt_sd, first_epoch = resume_from(opt.resume, dev, opt.precision)
+    elif opt.init_from:
+        from .utils.helpers import load_checkpoint
+        model = load_checkpoint(opt.init_from, device=dev, precision=opt.precision)
     fused = opt.loss_function == 'tversky'
     from .input_pipeline import DeviceFeeder
     from .utils.helpers import get_criterion
@@ -336,8 +395,12 @@ def main(argv=None):
     feeder = None if opt.device_patches else DeviceFeeder(dev)
     criterion = get_criterion(opt)                         # validation reports the criterion the run optimises (train.py:137)
     if fused:
-        step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta,
-                         **optimizer_kwargs(opt))
+        try:
+            groups = fine_tune_groups(model, opt.learning_rate, opt.weight_decay, opt.freeze, opt.no_decay_norm_bias, opt.lr_scale)
+            step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta,
+                             param_groups=groups, bn='frozen' if opt.frozen_bn else 'batch', **optimizer_kwargs(opt))
+        except ValueError as e:
+            raise SystemExit(f'parameter groups: {e}')
         if opt_sd is not None:
             step.load_optimizer_state_dict(opt_sd)
         if world > 1:

@@ -22,16 +22,33 @@ from .parallel import FlatLayout, GradBucketer
 class TrainStep:
     def __init__(self, model, lr=1e-3, tversky_alpha=0.1, tversky_beta=0.9, eps=1e-7,
                  process_group=None, n_buckets=4, distributed=True, force_collectives=False, guard=True,
-                 optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8):
+                 optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8,
+                 param_groups=None, bn='batch'):
         """optimizer: 'sgd' (torch.optim.SGD: momentum, dampening, nesterov, weight_decay), 'adam' or 'adamw' (torch.optim.Adam / AdamW:
         betas, adam_eps, weight_decay); weight_decay=None is torch's default (0 for sgd and adam, 1e-2 for adamw).  The default, plain
         SGD, is the reference's optim.SGD(lr) (train.py:55) and keeps no state; the other rules keep theirs in flat f32 buffers in the
         gradient layout (`opt_state`), with `opt_step` the number of updates applied.  `lr` may be reassigned between steps.
 
+        param_groups: None (one set of hyperparameters, today's kernels), or a list of dicts {'params': [state-dict names or the
+        nn.Parameter objects], 'lr': ..., 'weight_decay': ...} as torch.optim takes them (a missing key takes the step's value; at most 8
+        groups; momentum / betas / eps are one per step, a group that names another value is refused).  `step.param_groups` is then a
+        list of plain dicts read at every update: `step.param_groups[i]['lr'] = x` works the way a scheduler drives a torch optimizer.
+        Parameters with requires_grad=False when the step is built, or at set_param_groups(), are FROZEN: never updated or decayed, no
+        optimizer state, no weight-gradient GEMM, and backward stops at the last trainable layer (engine.chain_end).  A trainable
+        parameter that no group lists raises ValueError: it is never silently frozen.  With groups or frozen parameters the update
+        runs bdn_*_step_grouped; with neither, the ungrouped entry points as before.
+
+        bn: 'batch' (BatchNorm on batch statistics, running statistics updated: a training step) or 'frozen' (BatchNorm on its running
+        statistics, which are constants: running_mean / running_var / num_batches_tracked are not touched, and the conv biases in
+        front of a BatchNorm have real gradients, which are then reduced across ranks like every other).  The module's .training flag
+        is not consulted.
+
         guard: when the step issues collectives (world > 1, or force_collectives) and guard_collectives() has not been called, the
         first step() runs it in its measure-only form (replace_streams=False: it may defer the buckets, it never swaps a stream the
         caller may already have adopted) and reports / warns about a stream arrangement in which they slow the step down."""
-        self.model, self.lr = model, lr
+        if bn not in ('batch', 'frozen'):
+            raise ValueError(f"bn must be 'batch' or 'frozen', got {bn!r}")
+        self.model, self.lr, self.bn = model, lr, bn
         self.optim = _optim.OptimConfig(optimizer, lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
                                         weight_decay=weight_decay, betas=betas, eps=adam_eps)
         self._guard = guard
@@ -46,6 +63,9 @@ class TrainStep:
         dev = named[0][1].device
         if dev.type != 'cuda':
             raise RuntimeError('fabric_amd: TrainStep needs the model on a ROCm device (model.cuda() first)')
+        self._names = [k for k, _ in named]                  # model.parameters() order: torch.optim's state indices
+        self._by_id = {id(p): k for k, p in named}
+        self._checked_groups(param_groups)                   # a refused grouping leaves the module as it was
         order = param_order(model.n_channels)
         self.layout = FlatLayout([(k, p.shape) for k, p in named], order)
         self.flat_params = torch.zeros(self.layout.total, dtype=torch.float32, device=dev)
@@ -56,10 +76,11 @@ class TrainStep:
             p.data = v
             p.grad = self.layout.view(self.flat_grads, k)
         self.grads = {k: self.layout.view(self.flat_grads, k) for k, _ in named}
-        self._names = [k for k, _ in named]                  # model.parameters() order: torch.optim's state indices
         self.opt_state = {key: torch.zeros_like(self.flat_params) for key in self.optim.state_keys()}
         self.opt_step = 0
         bias_tail = [k for k in order if k.endswith('.bias') and k.split('.')[-2] in ('0', '3')]
+        if bn == 'frozen':
+            bias_tail = []                                   # on running statistics those biases have gradients (scale * dbeta): reduce them
         self.bucketer = GradBucketer(self.layout, self.flat_grads, n_buckets, process_group, keys_no_reduce=bias_tail,
                                      enabled=self.world > 1 or force_collectives, force=force_collectives)
         if self.world > 1:                                   # identical start on every rank (DataParallel broadcasts)
@@ -68,6 +89,51 @@ class TrainStep:
         self.last_counts = None
         # detached aliases of every parameter / buffer (same storage), built once: no per-step dict walk
         self._P = {k: v.detach() for k, v in self.model.state_dict(keep_vars=True).items()}
+        self.param_groups = self._groups = self._seg = self._need = None
+        self._implicit_group = False
+        if param_groups is not None or any(not p.requires_grad for _, p in named):
+            self.set_param_groups(param_groups)
+
+    def set_param_groups(self, groups):
+        """Install parameter groups (the constructor's `param_groups`) and re-read every parameter's requires_grad flag: rebuilds and
+        uploads the segment table of the grouped update kernels.  groups=None: one group of every trainable parameter with the step's lr
+        and weight_decay (`step.lr` keeps driving it); with nothing frozen either, the step returns to the ungrouped kernels.  The
+        optimizer state of parameters that stay trainable is kept; that of a parameter frozen now is zeroed, so it starts afresh if it
+        is released later (with the step's one update count).  Raises ValueError as fabric_amd.optim.ParamGroups does."""
+        dev = self.flat_params.device
+        pg = self._checked_groups(groups)
+        hp, cur = self.stream(dev), torch.cuda.current_stream(dev)
+        cur.wait_stream(hp)                                  # a step in flight still reads the old table and writes state and gradients
+        if pg is None:
+            self.param_groups = self._groups = self._seg = self._need = None
+            self._implicit_group = False
+            return
+        ends, ids = _optim.segment_table(self.layout, pg)
+        seg = (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev), torch.tensor(ids, dtype=torch.int32).to(dev), len(ends))
+        frozen = pg.frozen
+        for k in frozen:                                     # zero-filled once: reduced as zeros, and no stale state if released later
+            self.grads[k].zero_()
+            for t in self.opt_state.values():
+                self.layout.view(t, k).zero_()
+        hp.wait_stream(cur)
+        self._groups, self._seg = pg, seg
+        self.param_groups = pg.groups
+        self._implicit_group = groups is None
+        self._need = set(pg.trainable()) if frozen else None
+
+    def _checked_groups(self, groups):
+        """fabric_amd.optim.ParamGroups of `groups` (names or nn.Parameter objects) and the parameters' requires_grad flags as they are
+        now; None when no groups are given and nothing is frozen."""
+        frozen = {k for k, p in self.model.named_parameters() if not p.requires_grad}
+        if groups is None:
+            return _optim.ParamGroups(self.optim, self._names, None, frozen) if frozen else None
+
+        def name_of(q):
+            k = q if isinstance(q, str) else self._by_id.get(id(q))
+            if k is None:
+                raise ValueError('param group lists a tensor that is not a parameter of the model')
+            return k
+        return _optim.ParamGroups(self.optim, self._names, [dict(g, params=[name_of(q) for q in g['params']]) for g in groups], frozen)
 
     def _state(self):
         return self._P
@@ -283,7 +349,13 @@ class TrainStep:
         model = self.model
         eng = model.engine()
         P = self._state()
-        logits, ws = eng.forward(x_d1, x_d2, P, training=True)
+        frozen_bn = self.bn == 'frozen'
+        if frozen_bn:                                         # the training-layout forward on the running statistics, as an eval-mode
+            from .models.bidate_model import _Lease           # autograd graph recomputes it (_BiDateFunction.backward)
+            logits, ws = eng.forward(x_d1, x_d2, P, training=False, frozen=True)
+            lease = _Lease(ws)
+        else:
+            logits, ws = eng.forward(x_d1, x_d2, P, training=True)
         B, C, H, W = logits.shape
         dev = logits.device
         if self._tv is None or self._tv[3] != (B, C, H, W):
@@ -298,7 +370,16 @@ class TrainStep:
         st = _lib.stream_ptr()
         _lib.call('bdn_tversky', logits.data_ptr(), labels.data_ptr(), float(self.alpha), float(self.beta),
                   float(self.eps), tvws.data_ptr(), loss.data_ptr(), counts.data_ptr(), dlogits.data_ptr(), B, C, H, W, st)
-        eng.backward(ws, dlogits, P, self.grads, on_ready=self.bucketer.on_ready, zero_bias_grads=False)
+        if frozen_bn:
+            try:
+                eng.backward(ws, dlogits, P, self.grads, on_ready=self.bucketer.on_ready, zero_bias_grads=False, bn_mode='running',
+                             need=self._need)
+            finally:
+                lease.release()
+                if eng.x3:
+                    ws.release_split()
+        else:
+            eng.backward(ws, dlogits, P, self.grads, on_ready=self.bucketer.on_ready, zero_bias_grads=False, need=self._need)
         self.bucketer.finish()
         self._update(st)
         eng.invalidate_weights()                              # packed bf16/f32 GEMM images are now stale
@@ -310,6 +391,8 @@ class TrainStep:
         """The optimizer update on stream `st` with g = (sum of rank gradients) / world: per-rank loss, averaged gradients (standard DDP;
         SURVEY.md 8e).  Host-side scalars only: the step count is a Python int, nothing syncs."""
         o, n = self.optim, self.layout.total
+        if self._groups is not None:
+            return self._update_grouped(st)
         if o.plain:                                          # p -= lr * g: the reference's optim.SGD(lr)
             _lib.call('bdn_sgd_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), float(self.lr), 1.0 / self.world, n, st)
             return
@@ -324,26 +407,66 @@ class TrainStep:
                       self.opt_state['exp_avg_sq'].data_ptr(), float(self.lr), 1.0 / self.world, o.betas[0], o.betas[1], o.eps,
                       o.weight_decay, int(o.kind == 'adamw'), self.opt_step, n, st)
 
+    def _update_grouped(self, st):
+        """_update through bdn_*_step_grouped: per-group lr / weight_decay read from `param_groups` now, frozen segments skipped."""
+        o, n, pg = self.optim, self.layout.total, self._groups
+        if self._implicit_group:
+            pg.groups[0]['lr'] = float(self.lr)
+        lrs, wds = pg.hyper('lr'), pg.hyper('weight_decay')
+        ends, ids, n_seg = self._seg
+        table = (ends.data_ptr(), ids.data_ptr(), n_seg, len(lrs))
+        lr, wd = _lib.floats(lrs), _lib.floats(wds)
+        if o.kind == 'sgd' and o.momentum == 0 and not any(wds):
+            _lib.call('bdn_sgd_step_grouped', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), *table, lr, 1.0 / self.world, n, st)
+            return
+        first = self.opt_step == 0
+        self.opt_step += 1
+        if o.kind == 'sgd':
+            _lib.call('bdn_sgd_momentum_step_grouped', self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
+                      _lib.ptr(self.opt_state.get('momentum_buffer')), *table, lr, wd, 1.0 / self.world, o.momentum, o.dampening,
+                      int(o.nesterov), int(first), n, st)
+        else:
+            _lib.call('bdn_adam_step_grouped', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state['exp_avg'].data_ptr(),
+                      self.opt_state['exp_avg_sq'].data_ptr(), *table, lr, wd, 1.0 / self.world, o.betas[0], o.betas[1], o.eps,
+                      int(o.kind == 'adamw'), self.opt_step, n, st)
+
     # ------------------------------------------------------------------ optimizer state in torch.optim's format
     def optimizer_state_dict(self):
         """The optimizer state as ``torch.optim.{SGD,Adam,AdamW}(model.parameters()).state_dict()`` holds it (state keyed by the index in
         model.parameters(); param_groups with torch 2.10's keys).  The tensors are copies taken on the current stream, not views of the
-        live buffers."""
+        live buffers.  With parameter groups: one 'param_groups' entry per group and no state for a frozen parameter, which is what
+        torch.optim built with the same groups holds (fabric_amd.optim.groups_to_torch)."""
         self.optim.lr = float(self.lr)
         self.stream(self.flat_params.device)
         torch.cuda.current_stream(self.flat_params.device).wait_stream(self._hp)        # after the last step's update
+        if self._groups is not None:
+            if self._implicit_group:
+                self._groups.groups[0]['lr'] = float(self.lr)
+            return _optim.groups_to_torch(self.optim, self._groups, self.layout, self.opt_state, self.opt_step)
         return _optim.flat_to_torch(self.optim, self.layout, self._names, self.opt_state, self.opt_step)
 
     def load_optimizer_state_dict(self, sd):
         """Load a torch.optim SGD / Adam / AdamW ``state_dict()`` of ``model.parameters()`` (or optimizer_state_dict()'s output).  As
         torch does, the saved group's hyperparameters (lr included) replace the step's own.  Raises ValueError when the saved rule is
-        of the other family (SGD vs Adam), or its parameter count, shapes or per-parameter state do not fit this model."""
+        of the other family (SGD vs Adam), or its parameter count, shapes or per-parameter state do not fit this model.  With parameter
+        groups the state of an optimizer built with the same groups is expected (fabric_amd.optim.torch_to_groups; a single-group state
+        over all parameters is accepted too and leaves the groups' lr / weight_decay as they are)."""
         dev = self.flat_params.device
-        cfg, flat, step = _optim.torch_to_flat(sd, self.layout, self._names, dev)
+        if self._groups is not None:
+            cfg, hyper, flat, step = _optim.torch_to_groups(sd, self._groups, self.layout, dev)
+        else:
+            cfg, flat, step = _optim.torch_to_flat(sd, self.layout, self._names, dev)
         if cfg.family != self.optim.family:
             raise ValueError(f'optimizer state of {cfg.kind}, but this step runs {self.optim.kind}')
         hp = self.stream(dev)
         hp.wait_stream(torch.cuda.current_stream(dev))                                   # the copies above are ordered before the next step
         for t in self.opt_state.values():
             t.record_stream(hp)                                                          # a step still in flight may read the old buffers
+        if self._groups is not None:
+            if hyper is None:                                                            # an ungrouped state: the groups keep their values
+                cfg.lr, cfg.weight_decay = float(self.lr), self.optim.weight_decay
+            else:
+                for g, h in zip(self._groups.groups, hyper):
+                    g.update(h)
+                cfg.lr, cfg.weight_decay = hyper[0]['lr'], hyper[0]['weight_decay']
         self.optim, self.lr, self.opt_state, self.opt_step = cfg, cfg.lr, flat, step

@@ -502,6 +502,23 @@ int bdn_sgd_momentum_step(float* params, const float* grads, float* momentum_buf
 int bdn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float lr, float grad_scale,
                   double beta1, double beta2, float eps, float weight_decay, int decoupled_weight_decay, long long step,
                   size_t n, void* stream);
+/* ---- the three rules above with parameter groups and frozen tensors, train.py:55-56,95: one launch in which every float4 of the flat
+ * buffers takes lr / weight_decay of the group its tensor belongs to, or is skipped (a frozen vector is neither read nor written:
+ * parameter, gradient and state keep their bits).  n: a multiple of 4 (every tensor padded to a float4, as FlatLayout does).
+ * seg_end, seg_group: DEVICE arrays of n_seg (1..256) entries that tile [0, n/4): seg_end the sorted segment ends in float4 units,
+ * seg_group the group of each segment, 0..n_groups-1, or -1 = frozen.  They are read by the kernel only (nothing here waits for the
+ * device), so upload them when the groups change, not per step; a vector behind the last end or with an id outside the groups is
+ * skipped.  lr, weight_decay: HOST arrays of n_groups (1..8, else BDN_E_ARG) floats, passed on by value in the kernel arguments.
+ * Everything else (momentum, dampening, nesterov, betas, eps, the step count) is one per launch and means what it means above; the
+ * element formulas are the same device functions, so one group over the whole buffer gives the bits of the plain entry points. ---- */
+int bdn_sgd_step_grouped(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, int n_groups,
+                         const float* lr, float grad_scale, size_t n, void* stream);
+int bdn_sgd_momentum_step_grouped(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                                  const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                  float grad_scale, float momentum, float dampening, int nesterov, int first_step, size_t n, void* stream);
+int bdn_adam_step_grouped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
+                          const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay, float grad_scale,
+                          double beta1, double beta2, float eps, int decoupled_weight_decay, long long step, size_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,11 @@
       after a warm-up: us per launch and TB/s of the bytes the rule moves (plain SGD 3, momentum SGD 5, Adam / AdamW 7 buffer passes);
   (b) the bf16 B=64 128x128 train step in ms for sgd, sgd + momentum, adam and adamw, interleaved in one process like tools/ab_cfg.py
       (--rounds rounds of 5 warm-up + --steps timed steps per rule), median and difference to plain SGD.
-    python tools/bench_optim.py [--reps 200] [--rounds 4] [--steps 20] [--skip-step]
+  (c) --groups: the grouped Adam kernel (bdn_adam_step_grouped; BiDateNet(13, 2)'s real segment tables: weights / norms and biases,
+      and the same with the encoder's segments frozen) against bdn_adam_step in one process, the whole interleaving repeated --rounds
+      times (the spread between repeats of the ungrouped kernel is the margin), and the bf16 B=64 128x128 AdamW step with no groups, two
+      groups, the encoder frozen, and the encoder frozen + bn='frozen', interleaved like (b).
+    python tools/bench_optim.py [--reps 200] [--rounds 4] [--steps 20] [--skip-step] [--groups]
 Prints one JSON line at the end."""
 import argparse
 import json
@@ -99,13 +103,134 @@ def steps(rounds, n_steps, batch=64):
     return out
 
 
+ENCODER = ('inc.', 'down1.', 'down2.', 'down3.', 'down4.')
+
+
+def _two_groups(model, frozen_encoder):
+    """{weights} / {norms and biases: no decay, lr x 0.1} by name; the encoder's parameters get requires_grad=False when asked."""
+    for k, p in model.named_parameters():
+        p.requires_grad_(not (frozen_encoder and k.startswith(ENCODER)))
+    named = [(k, p) for k, p in model.named_parameters() if p.requires_grad]
+    return [{'params': [k for k, p in named if p.dim() > 1]},
+            {'params': [k for k, p in named if p.dim() == 1], 'weight_decay': 0.0, 'lr': 1e-4}]
+
+
+def grouped_kernels(reps, rounds):
+    """us per launch of bdn_adam_step and of bdn_adam_step_grouped on the real tables, interleaved, `rounds` times over."""
+    from fabric_amd import optim as O
+    from fabric_amd.engine import param_order
+    from fabric_amd.parallel import FlatLayout
+    dev = torch.device('cuda', 0)
+    model = BiDateNet(13, 2)
+    named = list(model.named_parameters())
+    names = [k for k, _ in named]
+    layout = FlatLayout([(k, p.shape) for k, p in named], param_order(13))
+    assert layout.total == N
+    cfg = O.OptimConfig('adamw', lr=1e-3)
+    tables, moved = {}, {}
+    for name, frozen_encoder in (('two_groups', False), ('two_groups_encoder_frozen', True)):
+        groups = _two_groups(model, frozen_encoder)
+        pg = O.ParamGroups(cfg, names, groups, {k for k, p in named if not p.requires_grad})
+        ends, ids = O.segment_table(layout, pg)
+        tables[name] = (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev), torch.tensor(ids, dtype=torch.int32).to(dev), len(ends))
+        starts = [0] + ends[:-1]
+        moved[name] = 7 * 16 * sum(b - a for a, b, g in zip(starts, ends, ids) if g != O.FROZEN)
+    g = torch.Generator(device='cpu').manual_seed(0)
+    p = torch.randn(N, generator=g).to(dev)
+    gr = (torch.randn(N, generator=g) * 1e-3).to(dev)
+    m, v = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+    st = _lib.stream_ptr()
+    step = [0]
+    lr, wd = _lib.floats([1e-3, 1e-4]), _lib.floats([1e-2, 0.0])
+
+    def plain():
+        step[0] += 1
+        _lib.call('bdn_adam_step', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), 1e-3, 1.0, 0.9, 0.999, 1e-8, 1e-2, 1, step[0], N, st)
+
+    def grouped(name):
+        ends, ids, n_seg = tables[name]
+
+        def f():
+            step[0] += 1
+            _lib.call('bdn_adam_step_grouped', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), ends.data_ptr(), ids.data_ptr(), n_seg,
+                      2, lr, wd, 1.0, 0.9, 0.999, 1e-8, 1, step[0], N, st)
+        return f
+    cases = [('adamw_ungrouped', 7 * 4 * N, plain)] + [(name, moved[name], grouped(name)) for name in tables]
+    res = {name: [] for name, _, _ in cases}
+    for _ in range(rounds):
+        for name, _, fn in cases:
+            for _ in range(20):
+                fn()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            res[name].append(e0.elapsed_time(e1) / reps * 1e3)
+    out = {}
+    for name, nbytes, _ in cases:
+        med = statistics.median(res[name])
+        out[name] = {'us': round(med, 2), 'MB': round(nbytes / 1e6, 1), 'TB_s': round(nbytes / med * 1e-6, 2),
+                     'segments': tables[name][2] if name in tables else None, 'rounds_us': [round(t, 2) for t in res[name]]}
+        print(f'{name:28s} median {med:8.2f} us  {nbytes / 1e6:6.1f} MB  {nbytes / med * 1e-6:5.2f} TB/s  {out[name]["rounds_us"]}', flush=True)
+    return out
+
+
+def grouped_steps(rounds, n_steps, batch=64):
+    """ms per bf16 B=64 128x128 AdamW step: no groups, two groups, encoder frozen, encoder frozen + bn='frozen'; interleaved."""
+    dev = torch.device('cuda', 0)
+    g = torch.Generator(device='cpu').manual_seed(1)
+    x1 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    x2 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    lbl = (torch.rand(batch, 128, 128, generator=g) < 0.1).to(torch.uint8).to(dev)
+    cases = [('no_groups', None, 'batch'), ('two_groups', False, 'batch'), ('encoder_frozen', True, 'batch'),
+             ('encoder_frozen_bn_frozen', True, 'frozen')]
+    ts = {}
+    for name, frozen_encoder, bn in cases:
+        torch.manual_seed(0)
+        model = BiDateNet(13, 2, precision='bf16').to(dev).train()
+        groups = None if frozen_encoder is None else _two_groups(model, frozen_encoder)
+        ts[name] = TrainStep(model, lr=1e-4, optimizer='adamw', param_groups=groups, bn=bn)
+    res = {name: [] for name, _, _ in cases}
+    with torch.cuda.stream(ts['no_groups'].stream()):
+        for _ in range(rounds):
+            for name, _, _ in cases:
+                s = ts[name]
+                for _ in range(5):
+                    s.step(x1, x2, lbl)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n_steps):
+                    s.step(x1, x2, lbl)
+                e1.record()
+                torch.cuda.synchronize()
+                res[name].append(e0.elapsed_time(e1) / n_steps)
+    base = statistics.median(res['no_groups'])
+    out = {}
+    for name, _, _ in cases:
+        med = statistics.median(res[name])
+        out[name] = {'ms': round(med, 4), 'delta_us': round((med - base) * 1e3, 1), 'rounds_ms': [round(t, 4) for t in res[name]]}
+        print(f'step {name:26s} median {med:.4f} ms  ({(med - base) * 1e3:+8.1f} us vs no_groups)  {out[name]["rounds_ms"]}', flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--rounds', type=int, default=4)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--skip-step', action='store_true')
+    ap.add_argument('--groups', action='store_true', help='(c): the grouped update kernel and the grouped / frozen steps only')
     a = ap.parse_args()
+    if a.groups:
+        res = {'n': N, 'grouped_kernels': grouped_kernels(max(a.reps, 200), a.rounds)}
+        if not a.skip_step:
+            res['grouped_step_bf16_b64'] = grouped_steps(a.rounds, a.steps)
+        print(json.dumps(res))
+        return
     res = {'n': N, 'kernels': kernels(max(a.reps, 200))}
     if not a.skip_step:
         res['step_bf16_b64'] = steps(a.rounds, a.steps)
