@@ -1,10 +1,11 @@
 """Helpers shared by the -m gpu parity tests: layout conversion between the oracle's NCHW float32
-CPU tensors and the library's NHWC device tensors, and error summaries."""
+CPU tensors and the library's NHWC device tensors (made as guard-banded buffers, tests/guard.py), and error summaries."""
 import numpy as np
 import torch
 
 from fabric_amd import _lib
 from fabric_amd._lib import BDN_BF16, BDN_F32
+from tests import guard
 
 DT = {'fp32': (BDN_F32, torch.float32), 'bf16': (BDN_BF16, torch.bfloat16)}
 
@@ -14,9 +15,9 @@ def rnd(precision, t):
     return t.to(torch.bfloat16).float() if precision == 'bf16' else t.float()
 
 
-def to_nhwc(precision, t_nchw):
-    """NCHW float32 CPU -> NHWC device tensor of the precision's storage type."""
-    return t_nchw.permute(0, 2, 3, 1).contiguous().to(DT[precision][1]).cuda()
+def to_nhwc(precision, t_nchw, device='cuda'):
+    """NCHW float32 CPU -> NHWC device tensor of the precision's storage type (guarded: tests/guard.py)."""
+    return guard.guard(t_nchw.permute(0, 2, 3, 1).contiguous().to(DT[precision][1]), device)
 
 
 def from_nhwc(t):
@@ -24,8 +25,8 @@ def from_nhwc(t):
     return t.float().cpu().permute(0, 3, 1, 2).contiguous()
 
 
-def dev(t, dtype=torch.float32):
-    return t.to(dtype).contiguous().cuda()
+def dev(t, dtype=torch.float32, device='cuda'):
+    return guard.guard(t.to(dtype).contiguous(), device)
 
 
 def st():
@@ -66,8 +67,8 @@ def pack_w(precision, w_oihw, cin_pad):
     dt, td = DT[precision]
     co, ci = w_oihw.shape[:2]
     wdev = dev(w_oihw)
-    wf = torch.empty(co, 9, cin_pad, dtype=td, device='cuda')
-    wd = torch.empty(cin_pad, 9, co, dtype=td, device='cuda') if cin_pad % 32 == 0 else None   # dgrad image: Cin_pad % 32
+    wf = guard.empty(co, 9, cin_pad, dtype=td)
+    wd = guard.empty(cin_pad, 9, co, dtype=td) if cin_pad % 32 == 0 else None   # dgrad image: Cin_pad % 32
     _lib.call('bdn_pack_weights', dt, wdev.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
               co, ci, cin_pad, st())
     return wf, wd

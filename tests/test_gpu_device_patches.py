@@ -12,6 +12,8 @@ import torch
 
 from fabric_amd import _lib
 from fabric_amd.utils.dataloaders import OneraPreloader, _apply_symmetry, synthetic_onera
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,13 +65,14 @@ def _special(r, shape):
 
 @pytest.mark.parametrize('C', [3, 13])
 @pytest.mark.parametrize('S', [1, 7, 12, 90, 128])
+@guarded
 def test_every_symmetry_through_the_abi(S, C):
     r = np.random.default_rng(S * 100 + C)
     shapes = [(S + 5, S + 9), (S + 8, S + 3)]
     cities = [{'images': _special(r, (2, C, h, w)), 'labels': r.integers(0, 256, (h, w)).astype(np.uint8)} for h, w in shapes]
-    dev = [{k: torch.from_numpy(v).cuda() for k, v in c.items()} for c in cities]
+    dev = [{k: guard.guard(torch.from_numpy(v)) for k, v in c.items()} for c in cities]
     rec = np.array([[d['images'].data_ptr(), d['labels'].data_ptr(), h | (w << 32)] for d, (h, w) in zip(dev, shapes)], np.int64)
-    table = torch.from_numpy(rec).cuda()
+    table = guard.guard(torch.from_numpy(rec))
     hw = np.array(shapes, np.int32)
     desc = []
     for city, (h, w) in enumerate(shapes):
@@ -77,10 +80,10 @@ def test_every_symmetry_through_the_abi(S, C):
             desc += [(city, row, col, sym) for sym in range(8)]
     desc = np.array(desc, np.int32)
     n = len(desc)
-    desc_dev = torch.from_numpy(desc).cuda()
-    o1 = torch.full((n, C, S, S), float('nan'), device='cuda')
-    o2 = torch.full_like(o1, float('nan'))
-    ol = torch.full((n, S, S), 77, dtype=torch.uint8, device='cuda')
+    desc_dev = guard.guard(torch.from_numpy(desc))
+    o1 = guard.full((n, C, S, S), float('nan'))
+    o2 = guard.full_like(o1, float('nan'))
+    ol = guard.full((n, S, S), 77, dtype=torch.uint8)
     _lib.call('bdn_sample_patches', table.data_ptr(), hw.ctypes.data, len(shapes), C, desc.ctypes.data, desc_dev.data_ptr(), n, S,
               o1.data_ptr(), o2.data_ptr(), ol.data_ptr(), _lib.stream_ptr())
     torch.cuda.synchronize()

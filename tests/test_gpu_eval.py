@@ -15,6 +15,8 @@ from fabric_amd.utils import inference as inf
 from oracle import bidate_oracle as O
 from oracle import filler
 from tests.gpu_util import DT, assert_close, dev, from_nhwc, pack_w, rnd, st, to_nhwc
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 TOL = {'fp32': 2e-5, 'bf16': 1e-2}
@@ -30,6 +32,7 @@ def _fold(gamma, beta, rm, rv, bias, eps=1e-5):
     return scale, bias * scale + (beta - rm * scale)
 
 
+@guarded
 def test_bn_eval_fold_multi():
     import struct
     Cs = [64, 512, 128]
@@ -38,12 +41,12 @@ def test_bn_eval_fold_multi():
         g, b, rm, rv = _rand((C,), 10 + i).abs() + 0.5, _rand((C,), 20 + i), _rand((C,), 30 + i), _rand((C,), 40 + i).abs() + 0.1
         bias = _rand((C,), 50 + i) if i != 1 else None
         d = [dev(t) for t in (g, b, rm, rv)] + [dev(bias) if bias is not None else None]
-        out = torch.full((2, C), float('nan'), device='cuda')
+        out = guard.full((2, C), float('nan'))
         keep += d + [out]
         recs += struct.pack('<QQQQQQii', *[t.data_ptr() if t is not None else 0 for t in d], out.data_ptr(), C, 0)
         sc, sh = _fold(g.double(), b.double(), rm.double(), rv.double(), bias.double() if bias is not None else torch.zeros(C).double())
         outs.append(out); refs.append((sc.float(), sh.float()))
-    desc = torch.frombuffer(bytearray(recs), dtype=torch.uint8).cuda()
+    desc = guard.guard(torch.frombuffer(bytearray(recs), dtype=torch.uint8))
     _lib.call('bdn_bn_eval_fold_multi', desc.data_ptr(), len(Cs), max(Cs), 1e-5, st())
     torch.cuda.synchronize()
     for out, (sc, sh) in zip(outs, refs):
@@ -68,6 +71,7 @@ EVAL_CASES = [
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', EVAL_CASES)
+@guarded
 def test_conv3x3_eval_stage(prec, case):
     N, H, W, c0r, C0, C1, Cout, use_mul, use_pool = case
     dt, td = DT[prec]
@@ -94,8 +98,8 @@ def test_conv3x3_eval_stage(prec, case):
     wf, _ = pack_w(prec, wp, C0 + C1)
     d0, d1 = to_nhwc(prec, x0), (to_nhwc(prec, x1) if C1 else None)
     dm = to_nhwc(prec, other) if use_mul else None
-    out = torch.full((N, H, W, Cout), float('nan'), dtype=td, device='cuda')
-    pool = torch.full((N, H // 2, W // 2, Cout), float('nan'), dtype=td, device='cuda') if use_pool else None
+    out = guard.full((N, H, W, Cout), float('nan'), dtype=td)
+    pool = guard.full((N, H // 2, W // 2, Cout), float('nan'), dtype=td) if use_pool else None
     dsc, dsh = dev(sc), dev(sh)
     _lib.call('bdn_conv3x3_eval', dt, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(),
               out.data_ptr(), dm.data_ptr() if use_mul else None, pool.data_ptr() if use_pool else None, N, H, W, Cout, st())
@@ -123,6 +127,7 @@ PAIR_CASES = [
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', PAIR_CASES)
+@guarded
 def test_conv3x3_eval_pair(prec, case):
     """Date-paired stage against the oracle, and bit for bit against the per-date form (bdn_conv3x3_eval with mul / pool)."""
     B, H, W, C, Cout, use_pool = case
@@ -135,8 +140,8 @@ def test_conv3x3_eval_pair(prec, case):
     pool_ref = O.maxpool2(act) if use_pool else None
     wf, _ = pack_w(prec, w, C)
     dx, dsc, dsh = to_nhwc(prec, x), dev(sc), dev(sh)
-    f = torch.full((B, H, W, Cout), float('nan'), dtype=td, device='cuda')
-    pool = torch.full((2 * B, H // 2, W // 2, Cout), float('nan'), dtype=td, device='cuda') if use_pool else None
+    f = guard.full((B, H, W, Cout), float('nan'), dtype=td)
+    pool = guard.full((2 * B, H // 2, W // 2, Cout), float('nan'), dtype=td) if use_pool else None
     _lib.call('bdn_conv3x3_eval_pair', dt, dx.data_ptr(), C, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), f.data_ptr(),
               pool.data_ptr() if use_pool else None, B, H, W, Cout, st())
     torch.cuda.synchronize()
@@ -144,9 +149,9 @@ def test_conv3x3_eval_pair(prec, case):
     if use_pool:
         assert_close('pooled', from_nhwc(pool), pool_ref, TOL[prec], 1e-6)
     # per-date form: date 1 stores its activation (+ pool), date 2 multiplies with it in the copy-out
-    a1 = torch.empty(B, H, W, Cout, dtype=td, device='cuda')
-    f2 = torch.empty_like(f)
-    pool2 = torch.empty_like(pool) if use_pool else None
+    a1 = guard.empty(B, H, W, Cout, dtype=td)
+    f2 = guard.empty_like(f)
+    pool2 = guard.empty_like(pool) if use_pool else None
     _lib.call('bdn_conv3x3_eval', dt, dx[:B].data_ptr(), C, None, 0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), a1.data_ptr(), None,
               pool2[:B].data_ptr() if use_pool else None, B, H, W, Cout, st())
     _lib.call('bdn_conv3x3_eval', dt, dx[B:].data_ptr(), C, None, 0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), f2.data_ptr(), a1.data_ptr(),
@@ -160,6 +165,7 @@ def test_conv3x3_eval_pair(prec, case):
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('shape', [(3, 32, 32), (2, 20, 45), (5, 16, 16)])
 @pytest.mark.parametrize('ncls', [2, 1])
+@guarded
 def test_conv3x3_eval_classifier_epilogue(prec, shape, ncls):
     """Last decoder stage with the classifier in its epilogue: logits bit-identical to bdn_outc_fwd on the stored activation,
     class map = first maximum, both against the oracle's conv1x1."""
@@ -174,32 +180,33 @@ def test_conv3x3_eval_classifier_epilogue(prec, shape, ncls):
     logit_ref = O.conv1x1(act_ref, cw, cb)
     wf, _ = pack_w(prec, w, C)
     d0, dsc, dsh, dcw, dcb = to_nhwc(prec, x), dev(sc), dev(sh), dev(cw.reshape(ncls, C)), dev(cb)
-    act = torch.full((N, H, W, C), float('nan'), dtype=td, device='cuda')
-    logits = torch.full((N, ncls, H, W), float('nan'), device='cuda')
-    mask = torch.full((N, H, W), 255, dtype=torch.uint8, device='cuda')
+    act = guard.full((N, H, W, C), float('nan'), dtype=td)
+    logits = guard.full((N, ncls, H, W), float('nan'))
+    mask = guard.full((N, H, W), 255, dtype=torch.uint8)
     _lib.call('bdn_conv3x3_eval_cls', dt, d0.data_ptr(), C, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), act.data_ptr(),
               dcw.data_ptr(), dcb.data_ptr(), ncls, logits.data_ptr(), mask.data_ptr(), None, 0, 0, N, H, W, C, st())
     torch.cuda.synchronize()
     assert_close('activation', from_nhwc(act), act_ref, TOL[prec], 1e-6)
     assert_close('logits', logits.cpu(), logit_ref, 5e-5 if prec == 'fp32' else 1e-2, 1e-5)
     # the stand-alone classifier on the stored activation (identity BatchNorm table): the same bits
-    ident = torch.zeros(1, 4, C, device='cuda'); ident[:, 1:3] = 1.0
-    l2 = torch.empty_like(logits)
+    ident = guard.zeros(1, 4, C); ident[:, 1:3] = 1.0
+    l2 = guard.empty_like(logits)
     _lib.call('bdn_outc_fwd', dt, act.data_ptr(), ident.data_ptr(), dcw.data_ptr(), dcb.data_ptr(), l2.data_ptr(), N, H, W, C, ncls, st())
     torch.cuda.synchronize()
     assert torch.equal(l2, logits)
-    want = torch.max(logits, 1)[1].to(torch.uint8) if ncls > 1 else torch.zeros(N, H, W, dtype=torch.uint8, device='cuda')
+    want = torch.max(logits, 1)[1].to(torch.uint8) if ncls > 1 else guard.zeros(N, H, W, dtype=torch.uint8)
     if ncls > 1:    # torch.max returns the first maximum on ties as well
         want = (logits[:, 1] > logits[:, 0]).to(torch.uint8)
     assert torch.equal(mask, want)
     # logits / activation are optional outputs
-    mask2 = torch.full_like(mask, 255)
+    mask2 = guard.full_like(mask, 255)
     _lib.call('bdn_conv3x3_eval_cls', dt, d0.data_ptr(), C, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), None,
               dcw.data_ptr(), dcb.data_ptr(), ncls, None, mask2.data_ptr(), None, 0, 0, N, H, W, C, st())
     torch.cuda.synchronize()
     assert torch.equal(mask2, mask)
 
 
+@guarded
 def test_conv3x3_eval_classifier_stitches_like_argmax_stitch():
     """Scene stitching from the epilogue == bdn_argmax_stitch on the same logits (ownership rule of utils/inference.py:187-236)."""
     p, Hs, Ws, C = 32, 88, 75, 64
@@ -212,21 +219,22 @@ def test_conv3x3_eval_classifier_stitches_like_argmax_stitch():
     dt, td = DT['bf16']
     wf, _ = pack_w('bf16', w, C)
     d0, dsc, dsh, dcw, dcb = to_nhwc('bf16', x), dev(sc), dev(sh), dev(cw), dev(cb)
-    origins = torch.from_numpy(o_np).cuda()
-    logits = torch.empty(n, 2, p, p, device='cuda')
-    m_fused = torch.full((Hs, Ws), 255, dtype=torch.uint8, device='cuda')
+    origins = guard.guard(torch.from_numpy(o_np))
+    logits = guard.empty(n, 2, p, p)
+    m_fused = guard.full((Hs, Ws), 255, dtype=torch.uint8)
     _lib.call('bdn_conv3x3_eval_cls', dt, d0.data_ptr(), C, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), None,
               dcw.data_ptr(), dcb.data_ptr(), 2, logits.data_ptr(), m_fused.data_ptr(), origins.data_ptr(), Hs, Ws, n, p, p, C, st())
-    m_ref = torch.full((Hs, Ws), 255, dtype=torch.uint8, device='cuda')
+    m_ref = guard.full((Hs, Ws), 255, dtype=torch.uint8)
     _lib.call('bdn_argmax_stitch', logits.data_ptr(), origins.data_ptr(), m_ref.data_ptr(), n, 2, p, Hs, Ws, st())
     torch.cuda.synchronize()
     assert int((m_ref == 255).sum()) == 0
     assert torch.equal(m_fused, m_ref)
 
 
+@guarded
 def test_eval_stage_argument_errors():
-    t = torch.zeros(1, 8, 8, 64, dtype=torch.bfloat16, device='cuda')
-    f = torch.zeros(64, device='cuda')
+    t = guard.zeros(1, 8, 8, 64, dtype=torch.bfloat16)
+    f = guard.zeros(64)
     with pytest.raises(RuntimeError, match='null pointer'):
         _lib.call('bdn_conv3x3_eval', 1, t.data_ptr(), 64, None, 0, t.data_ptr(), None, f.data_ptr(), t.data_ptr(), None, None, 1, 8, 8, 64, st())
     with pytest.raises(RuntimeError, match='multiple of 64'):

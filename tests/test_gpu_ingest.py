@@ -16,23 +16,26 @@ from fabric_amd.utils import inference as inf
 from oracle import filler
 from oracle import ingest_oracle as IO
 from gpu_util import st
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize('case', [(55, 60, 110, 120, 'u16'), (19, 21, 114, 126, 'u16'), (64, 48, 64, 48, 'u16'),
                                   (40, 40, 61, 77, 'f32'), (120, 90, 60, 45, 'u16'), (1, 1, 5, 7, 'f32')])
+@guarded
 def test_ingest_band_matches_oracle(case):
     hs, ws, H, W, kind = case
     r = np.random.default_rng(5)
     if kind == 'u16':
         band = r.integers(0, 12000, (hs, ws)).astype(np.uint16)
-        src = torch.from_numpy(band.view(np.int16)).cuda()
+        src = guard.guard(torch.from_numpy(band.view(np.int16)))
     else:
         band = (1500 + 400 * r.standard_normal((hs, ws))).astype(np.float32)
-        src = torch.from_numpy(band).cuda()
+        src = guard.guard(torch.from_numpy(band))
     mean, std = 1422.37, 456.25
-    out = torch.full((H, W), float('nan'), device='cuda')
+    out = guard.full((H, W), float('nan'))
     call('bdn_ingest_band', 0 if kind == 'u16' else 1, ptr(src), hs, ws, mean, std, ptr(out), H, W, st())
     ref = IO.ingest_band(band, mean, std, W, H)
     got = out.cpu().numpy()

@@ -9,6 +9,8 @@ import torch
 from fabric_amd import _lib
 from fabric_amd._lib import BDN_BF16, BDN_BF16X3, BDN_F32
 from tests.gpu_util import assert_close, st
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -59,10 +61,11 @@ def _run_first(prec, B, H, W, cr, form, seed=0, ldA=64):
     else:
         dz = _dz64(dA[..., :C].contiguous(), z, tab, sums, ipg)
     ref = torch.nn.grad.conv2d_input((N, cr, H, W), w.double(), dz.permute(0, 3, 1, 2), padding=1)
-    dx1 = torch.full((B, cr, H, W), float('nan'), device='cuda')
-    dx2 = torch.full((B, cr, H, W), float('nan'), device='cuda')
-    ddA, dz_ = dA.to(td).cuda(), z.to(td).cuda()
-    dtab, dsums, dw = tab.cuda(), sums.cuda(), w.cuda()
+    dx1 = guard.full((B, cr, H, W), float('nan'))
+    dx2 = guard.full((B, cr, H, W), float('nan'))
+    ddA, dz_ = guard.guard(dA.to(td)), guard.guard(z.to(td))
+    ddA[..., C:] = float('nan')                          # the foreign channels of a wider dA: a read of them poisons the result
+    dtab, dsums, dw = guard.guard(tab), guard.guard(sums), guard.guard(w)
     if form == 'plain':
         _lib.call('bdn_conv3x3_dgrad_first', dt, ddA.data_ptr(), ldA, None, None, None, ipg, dw.data_ptr(), cr,
                   dx1.data_ptr(), dx2.data_ptr(), B, H, W, st())
@@ -76,6 +79,7 @@ def _run_first(prec, B, H, W, cr, form, seed=0, ldA=64):
 @pytest.mark.parametrize('prec', ['fp32', 'bf16'])
 @pytest.mark.parametrize('form', ['batch', 'frozen', 'plain'])
 @pytest.mark.parametrize('case', [(2, 32, 32, 3), (2, 32, 32, 13), (1, 90, 90, 13), (3, 40, 72, 13), (2, 5, 5, 3)])
+@guarded
 def test_dgrad_first_matches_float64(prec, form, case):
     B, H, W, cr = case
     dx1, dx2, ref = _run_first(prec, B, H, W, cr, form)
@@ -83,6 +87,7 @@ def test_dgrad_first_matches_float64(prec, form, case):
     assert_close(f'dx2[{prec},{form}]', dx2, ref[B:], TOL[prec])
 
 
+@guarded
 def test_dgrad_first_reads_a_dA_slice():
     """dA with a leading dimension above 64 (a channel slice of a wider tensor)."""
     dx1, dx2, ref = _run_first('bf16', 2, 24, 20, 13, 'batch', seed=5, ldA=128)
@@ -91,19 +96,20 @@ def test_dgrad_first_reads_a_dA_slice():
 
 
 @pytest.mark.parametrize('prec', ['fp32', 'bf16'])
+@guarded
 def test_dgrad_first_full_size(prec):
     """B = 64, 128 x 128, 13 bands (the benchmark shape); the float64 reference on four images (both ends of both dates)."""
     B, H, W, cr, C = 64, 128, 128, 13, 64
     dt, td = DT[prec]
     N = 2 * B
     g = torch.Generator(device='cuda').manual_seed(0)
-    ddA = torch.randn(N, H, W, C, device='cuda', generator=g).to(td)
-    dz_ = torch.randn(N, H, W, C, device='cuda', generator=g).to(td)
+    ddA = guard.guard(torch.randn(N, H, W, C, device='cuda', generator=g).to(td))
+    dz_ = guard.guard(torch.randn(N, H, W, C, device='cuda', generator=g).to(td))
     w = _rand((C, cr, 3, 3), 2, 0.05)
     tab, sums = _table(2, C, 3), _rand((2, 2, C), 4, 50.0)
-    dx1 = torch.full((B, cr, H, W), float('nan'), device='cuda')
-    dx2 = torch.full((B, cr, H, W), float('nan'), device='cuda')
-    dtab, dsums, dw = tab.cuda(), sums.cuda(), w.cuda()
+    dx1 = guard.full((B, cr, H, W), float('nan'))
+    dx2 = guard.full((B, cr, H, W), float('nan'))
+    dtab, dsums, dw = guard.guard(tab), guard.guard(sums), guard.guard(w)
     _lib.call('bdn_conv3x3_dgrad_first', dt, ddA.data_ptr(), C, dz_.data_ptr(), dtab.data_ptr(), dsums.data_ptr(), B,
               dw.data_ptr(), cr, dx1.data_ptr(), dx2.data_ptr(), B, H, W, st())
     torch.cuda.synchronize()
@@ -121,22 +127,23 @@ def test_dgrad_first_full_size(prec):
 # ------------------------------------------------------------------ frozen BatchNorm backward
 def _eval_table(C, seed):
     rng = np.random.default_rng(seed)
-    gamma = torch.from_numpy(rng.uniform(0.5, 1.5, C).astype(np.float32)).cuda()
-    beta = torch.from_numpy(rng.standard_normal(C).astype(np.float32) * 0.1).cuda()
-    rm = torch.from_numpy(rng.standard_normal(C).astype(np.float32) * 0.3).cuda()
-    rv = torch.from_numpy(rng.uniform(0.3, 2.0, C).astype(np.float32)).cuda()
+    gamma = guard.guard(torch.from_numpy(rng.uniform(0.5, 1.5, C).astype(np.float32)))
+    beta = guard.guard(torch.from_numpy(rng.standard_normal(C).astype(np.float32) * 0.1))
+    rm = guard.guard(torch.from_numpy(rng.standard_normal(C).astype(np.float32) * 0.3))
+    rv = guard.guard(torch.from_numpy(rng.uniform(0.3, 2.0, C).astype(np.float32)))
     return gamma, beta, rm, rv
 
 
 @pytest.mark.parametrize('G,C,rows', [(2, 64, 37), (1, 256, 700), (2, 512, 9)])
+@guarded
 def test_frozen_finalize_matches_float64(G, C, rows):
     gamma, beta, rm, rv = _eval_table(C, G + C)
-    bn = torch.empty(G, 4, C, device='cuda')
+    bn = guard.empty(G, 4, C)
     _lib.call('bdn_bn_eval', gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(), rv.data_ptr(), 1e-5, G, C, bn.data_ptr(), st())
-    part = _rand((G * rows, 2, C), 7).cuda()
-    sums = torch.full((G, 2, C), float('nan'), device='cuda')
-    dg, db, dbias = (torch.full((C,), float('nan'), device='cuda') for _ in range(3))
-    scratch = torch.empty(_lib.load().bdn_bn_bwd_scratch_bytes(G, C) // 4, device='cuda')
+    part = guard.guard(_rand((G * rows, 2, C), 7))
+    sums = guard.full((G, 2, C), float('nan'))
+    dg, db, dbias = (guard.full((C,), float('nan')) for _ in range(3))
+    scratch = guard.empty(_lib.load().bdn_bn_bwd_scratch_bytes(G, C) // 4)
     _lib.call('bdn_bn_bwd_finalize_frozen', bn.data_ptr(), G, C, part.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(),
               db.data_ptr(), dbias.data_ptr(), scratch.data_ptr(), st())
     torch.cuda.synchronize()
@@ -151,6 +158,7 @@ def test_frozen_finalize_matches_float64(G, C, rows):
 
 
 @pytest.mark.parametrize('dtype,fused', [('bf16', True), ('fp32', True), ('split', True), ('bf16', False), ('fp32', False)])
+@guarded
 def test_frozen_dz_is_scale_times_masked_gradient(dtype, fused):
     """dz = scale * g under the ReLU mask, bit for bit, whichever frozen entry point forms it (no mean-correction terms)."""
     N, H, W, C, ipg = 4, 12, 20, 64, 2
@@ -158,22 +166,22 @@ def test_frozen_dz_is_scale_times_masked_gradient(dtype, fused):
     td = torch.bfloat16 if dtype == 'bf16' else torch.float32
     dt = {'bf16': BDN_BF16, 'fp32': BDN_F32, 'split': BDN_BF16X3}[dtype]
     gamma, beta, rm, rv = _eval_table(C, 3)
-    bn = torch.empty(G, 4, C, device='cuda')
+    bn = guard.empty(G, 4, C)
     _lib.call('bdn_bn_eval', gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(), rv.data_ptr(), 1e-5, G, C, bn.data_ptr(), st())
-    dA = _rand((N, H, W, C), 1).to(td).cuda()
-    z = _rand((N, H, W, C), 2).to(td).cuda()
-    sums = torch.empty(G, 2, C, device='cuda')
-    dg, db, dbias = (torch.empty(C, device='cuda') for _ in range(3))
-    out = torch.empty(N, H, W, 2 * C if dtype == 'split' else C, dtype=torch.bfloat16 if dtype == 'split' else td, device='cuda')
+    dA = guard.guard(_rand((N, H, W, C), 1).to(td))
+    z = guard.guard(_rand((N, H, W, C), 2).to(td))
+    sums = guard.empty(G, 2, C)
+    dg, db, dbias = (guard.empty(C) for _ in range(3))
+    out = guard.empty(N, H, W, 2 * C if dtype == 'split' else C, dtype=torch.bfloat16 if dtype == 'split' else td)
     lib = _lib.load()
     if fused:
         rows = 5
-        part = _rand((G * rows, 2, C), 3).cuda()
-        scratch = torch.empty(lib.bdn_bn_bwd_scratch_bytes(G, C) // 4 + 1, device='cuda')
+        part = guard.guard(_rand((G * rows, 2, C), 3))
+        scratch = guard.empty(lib.bdn_bn_bwd_scratch_bytes(G, C) // 4 + 1)
         _lib.call('bdn_bn_bwd_apply_frozen', dt, dA.data_ptr(), C, z.data_ptr(), bn.data_ptr(), ipg, N, H, W, C, part.data_ptr(),
                   rows, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(), dbias.data_ptr(), out.data_ptr(), scratch.data_ptr(), st())
     else:
-        ws = torch.empty(lib.bdn_bn_bwd_workspace_bytes(dt, N, H, W, C, ipg) // 4 + 1, device='cuda')
+        ws = guard.empty(lib.bdn_bn_bwd_workspace_bytes(dt, N, H, W, C, ipg) // 4 + 1)
         _lib.call('bdn_bn_bwd_frozen', dt, dA.data_ptr(), C, z.data_ptr(), bn.data_ptr(), ipg, N, H, W, C, ws.data_ptr(),
                   sums.data_ptr(), dg.data_ptr(), db.data_ptr(), dbias.data_ptr(), out.data_ptr(), st())
     torch.cuda.synchronize()

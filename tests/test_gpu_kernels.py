@@ -14,6 +14,8 @@ from fabric_amd._lib import BDN_BF16, IN_BNRELU, IN_PLAIN
 from oracle import bidate_oracle as O
 from tests.gpu_util import (DT, assert_close, assert_masked, preact, bn_table, bnrelu_ref, dev, frag_to_dense, from_nhwc, pack_w, rnd, st,
                             to_nhwc)
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 TOL = {'fp32': 2e-5, 'bf16': 1e-2}
@@ -40,6 +42,7 @@ CONV_CASES = [
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', CONV_CASES)
+@guarded
 def test_conv3x3_forward_stats_finalize(prec, case):
     N, H, W, c0r, C0, C1, Cout, bnrelu, ipg = case
     dt, td = DT[prec]
@@ -61,9 +64,9 @@ def test_conv3x3_forward_stats_finalize(prec, case):
         wp[:, C0:] = w[:, c0r:]
     wf, _ = pack_w(prec, wp, C0 + C1)
     d0, d1 = to_nhwc(prec, x0), (to_nhwc(prec, x1) if C1 else None)
-    out = torch.empty(N, H, W, Cout, dtype=td, device='cuda')
+    out = guard.empty(N, H, W, Cout, dtype=td)
     nt = _lib.load().bdn_conv3x3_num_mtiles(N, H, W, Cout, ipg)
-    stats = torch.full((nt, 2, Cout), float('nan'), device='cuda')
+    stats = guard.full((nt, 2, Cout), float('nan'))
     dbn = dev(bn_in) if bnrelu else None
     db = dev(b)
     _lib.call('bdn_conv3x3', dt, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1,
@@ -75,10 +78,10 @@ def test_conv3x3_forward_stats_finalize(prec, case):
     gamma, beta = _rand((Cout,), 6).abs() + 0.5, _rand((Cout,), 7, 0.3)
     rm0, rv0 = _rand((Cout,), 8, 0.2), _rand((Cout,), 9).abs() + 0.5
     drm, drv = dev(rm0), dev(rv0)
-    nbt = torch.zeros(1, dtype=torch.int64, device='cuda')
-    bn = torch.empty(G, 4, Cout, device='cuda')
+    nbt = guard.zeros(1, dtype=torch.int64)
+    bn = guard.empty(G, 4, Cout)
     dg, dbeta = dev(gamma), dev(beta)
-    fws = torch.empty(_lib.load().bdn_bn_finalize_workspace_bytes(nt, G, Cout) // 8, dtype=torch.float64, device='cuda')
+    fws = guard.empty(_lib.load().bdn_bn_finalize_workspace_bytes(nt, G, Cout) // 8, dtype=torch.float64)
     _lib.call('bdn_bn_finalize', stats.data_ptr(), nt, G, Cout, ipg * H * W, dg.data_ptr(), dbeta.data_ptr(),
               1e-5, 0.1, drm.data_ptr(), drv.data_ptr(), nbt.data_ptr(), bn.data_ptr(), fws.data_ptr(), st())
     torch.cuda.synchronize()
@@ -105,6 +108,7 @@ def test_conv3x3_forward_stats_finalize(prec, case):
 # ------------------------------------------------------------------ data gradient through the same kernel
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', [(2, 16, 16, 64, 128, 1), (2, 8, 8, 256, 128, 2), (1, 22, 45, 192, 64, 1)])
+@guarded
 def test_conv3x3_dgrad(prec, case):
     N, H, W, Cin, Cout, ipg = case
     dt, td = DT[prec]
@@ -113,7 +117,7 @@ def test_conv3x3_dgrad(prec, case):
     ref = torch.nn.grad.conv2d_input((N, Cin, H, W), w, dz, padding=1)
     _, wd = pack_w(prec, w, Cin)
     ddz = to_nhwc(prec, dz)
-    out = torch.empty(N, H, W, Cin, dtype=td, device='cuda')
+    out = guard.empty(N, H, W, Cin, dtype=td)
     _lib.call('bdn_conv3x3', dt, ddz.data_ptr(), Cout, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None,
               out.data_ptr(), None, N, H, W, Cin, st())
     torch.cuda.synchronize()
@@ -122,6 +126,7 @@ def test_conv3x3_dgrad(prec, case):
 
 @pytest.mark.parametrize('case', [(2, 40, 24, 64, 64, 1, True), (4, 32, 32, 64, 128, 2, False), (2, 24, 20, 64, 64, 2, False),
                                   (16, 64, 64, 64, 256, 8, True), (3, 17, 45, 64, 128, 3, True)])
+@guarded
 def test_conv3x3_dgrad_with_bn_backward_on_load(case):
     """bdn_conv3x3_dgrad_bb = bdn_bn_bwd_apply + bdn_conv3x3(_dgrad_bs) without the pass in between.  Its operand is the MASKED gradient g
     the fused producers store, and it forms dz = a g + b z + c (three per-channel constants, round 5) instead of bdn_bn_bwd_apply's
@@ -139,26 +144,26 @@ def test_conv3x3_dgrad_with_bn_backward_on_load(case):
     _, wd = pack_w('bf16', w, Cout)
     dA_d, z_d, bn_d = to_nhwc('bf16', dA), to_nhwc('bf16', z), dev(bn)
     # reference path: reduce + finalize + apply, then the plain data-gradient convolution
-    ws = torch.empty(lib.bdn_bn_bwd_workspace_bytes(BDN_BF16, N, H, W, C0, ipg) // 4, device='cuda')
-    sums = torch.empty(G, 2, C0, device='cuda')
-    dg, db = torch.empty(C0, device='cuda'), torch.empty(C0, device='cuda')
-    dz_ref = torch.empty(N, H, W, C0, dtype=torch.bfloat16, device='cuda')
+    ws = guard.empty(lib.bdn_bn_bwd_workspace_bytes(BDN_BF16, N, H, W, C0, ipg) // 4)
+    sums = guard.empty(G, 2, C0)
+    dg, db = guard.empty(C0), guard.empty(C0)
+    dz_ref = guard.empty(N, H, W, C0, dtype=torch.bfloat16)
     _lib.call('bdn_bn_bwd', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, C0,
               ws.data_ptr(), sums.data_ptr(), dg.data_ptr(), db.data_ptr(), dz_ref.data_ptr(), st())
-    out_ref = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device='cuda')
+    out_ref = guard.empty(N, H, W, Cout, dtype=torch.bfloat16)
     nt = lib.bdn_conv3x3_num_mtiles(N, H, W, Cout, ipg)
     zp = to_nhwc('bf16', rnd('bf16', _rand((N, Cout, H, W), 65)))
     bnp = dev(bn_table(G, Cout, 66))
-    part_ref = torch.full((nt, 2, Cout), float('nan'), device='cuda')
-    part = torch.full((nt, 2, Cout), float('nan'), device='cuda')
+    part_ref = guard.full((nt, 2, Cout), float('nan'))
+    part = guard.full((nt, 2, Cout), float('nan'))
     if with_bs:
         _lib.call('bdn_conv3x3_dgrad_bs', BDN_BF16, dz_ref.data_ptr(), C0, wd.data_ptr(), out_ref.data_ptr(), zp.data_ptr(), bnp.data_ptr(), ipg,
                   part_ref.data_ptr(), N, H, W, Cout, st())
     else:
         _lib.call('bdn_conv3x3', BDN_BF16, dz_ref.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None, out_ref.data_ptr(), None,
                   N, H, W, Cout, st())
-    out = torch.full((N, H, W, Cout), float('nan'), dtype=torch.bfloat16, device='cuda')
-    dz = torch.full((N, H, W, C0), float('nan'), dtype=torch.bfloat16, device='cuda')
+    out = guard.full((N, H, W, Cout), float('nan'), dtype=torch.bfloat16)
+    dz = guard.full((N, H, W, C0), float('nan'), dtype=torch.bfloat16)
     _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
               out.data_ptr(), zp.data_ptr() if with_bs else None, bnp.data_ptr() if with_bs else None, part.data_ptr() if with_bs else None,
               dz.data_ptr(), N, H, W, Cout, st())
@@ -175,7 +180,7 @@ def test_conv3x3_dgrad_with_bn_backward_on_load(case):
         assert torch.equal(out == 0, out_ref == 0) or ((out == 0) != (out_ref == 0)).float().mean() < 1e-3
         assert_close('fused statistics', part.cpu(), part_ref.cpu(), 2e-2, abs_floor=1e-3)
     # without the by-product store the data gradient is the same, bit for bit
-    out2 = torch.empty_like(out)
+    out2 = guard.empty_like(out)
     _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
               out2.data_ptr(), None, None, None, None, N, H, W, Cout, st())
     torch.cuda.synchronize()
@@ -199,6 +204,7 @@ WG_CASES = [
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', WG_CASES)
+@guarded
 def test_conv3x3_wgrad(prec, case):
     N, H, W, c0r, C0, C1, Cout, bnrelu, ipg = case
     dt, td = DT[prec]
@@ -213,9 +219,9 @@ def test_conv3x3_wgrad(prec, case):
     ref = torch.nn.grad.conv2d_weight(a.double(), (Cout, c0r + C1, 3, 3), dz.double(), padding=1).float()
     d0, d1, ddz = to_nhwc(prec, x0), (to_nhwc(prec, x1) if C1 else None), to_nhwc(prec, dz)
     nbytes = _lib.load().bdn_wgrad_workspace_bytes(N, H, W, Cout, C0 + C1, ipg)
-    part = torch.empty(nbytes // 4, device='cuda')
+    part = guard.empty(nbytes // 4)
     cin_real = c0r + C1 if not C1 else C0 + C1
-    dw = torch.full((Cout, cin_real, 3, 3), float('nan'), device='cuda')
+    dw = guard.full((Cout, cin_real, 3, 3), float('nan'))
     dbn = dev(bn_in) if bnrelu else None
     _lib.call('bdn_conv3x3_wgrad', dt, ddz.data_ptr(), Cout, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1,
               IN_BNRELU if bnrelu else IN_PLAIN, dbn.data_ptr() if bnrelu else None, ipg,
@@ -230,6 +236,7 @@ def test_conv3x3_wgrad(prec, case):
 # ------------------------------------------------------------------ BatchNorm + ReLU backward
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', [(4, 16, 16, 64, 2, 0), (2, 9, 7, 128, 1, 64), (6, 8, 8, 512, 3, 0)])
+@guarded
 def test_bn_bwd(prec, case):
     N, H, W, C, ipg, extra = case
     dt, td = DT[prec]
@@ -264,12 +271,13 @@ def test_bn_bwd(prec, case):
     xhat = torch.cat([(z[g * ipg:(g + 1) * ipg].double() - bn[g, 0].double()[None, :, None, None]) * bn[g, 1].double()[None, :, None, None] for g in range(G)])
     dgamma_ref = (gm * xhat).sum((0, 2, 3)).float()
     # ---- device
-    dz_d = torch.empty(N, H, W, C, dtype=td, device='cuda')
+    dz_d = guard.empty(N, H, W, C, dtype=td)
     dA_d = to_nhwc(prec, dA_full)
+    dA_d[..., :extra] = float('nan')                    # the foreign channels of the wider tensor: a read of them poisons the result
     z_d = to_nhwc(prec, z)
-    wsb = torch.empty(_lib.load().bdn_bn_bwd_workspace_bytes(dt, N, H, W, C, ipg) // 4, device='cuda')
-    sums = torch.empty(G, 2, C, device='cuda')
-    dgam, dbet = torch.empty(C, device='cuda'), torch.empty(C, device='cuda')
+    wsb = guard.empty(_lib.load().bdn_bn_bwd_workspace_bytes(dt, N, H, W, C, ipg) // 4)
+    sums = guard.empty(G, 2, C)
+    dgam, dbet = guard.empty(C), guard.empty(C)
     bn_d = dev(bn)
     es = 2 if prec == 'bf16' else 4
     _lib.call('bdn_bn_bwd', dt, dA_d.data_ptr() + extra * es, ld, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, C,
@@ -283,13 +291,14 @@ def test_bn_bwd(prec, case):
 # ------------------------------------------------------------------ pool / product / upsample and their backward
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('shape', [(4, 16, 16, 64, 2), (2, 45, 22, 64, 1), (2, 11, 11, 128, 1)])
+@guarded
 def test_bnrelu_pool(prec, shape):
     N, H, W, C, ipg = shape
     dt, td = DT[prec]
     z = rnd(prec, _rand((N, C, H, W), 41))
     bn = bn_table(N // ipg, C, 42)
     ref = O.maxpool2(bnrelu_ref(prec, z, bn, ipg))
-    out = torch.empty(N, H // 2, W // 2, C, dtype=td, device='cuda')
+    out = guard.empty(N, H // 2, W // 2, C, dtype=td)
     z_d, bn_d = to_nhwc(prec, z), dev(bn)
     _lib.call('bdn_bnrelu_pool', dt, z_d.data_ptr(), bn_d.data_ptr(), ipg, out.data_ptr(), N, H, W, C, st())
     torch.cuda.synchronize()
@@ -298,6 +307,7 @@ def test_bnrelu_pool(prec, shape):
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('shape', [(4, 16, 16, 64, 2), (2, 45, 22, 64, 1), (3, 7, 5, 512, 3), (2, 9, 9, 16, 1)])
+@guarded
 def test_bnrelu_materialised(prec, shape):
     """bdn_bnrelu writes exactly the tensor the 3x3 consumers derive on load (models/unet_parts.py:14-15)."""
     N, H, W, C, ipg = shape
@@ -305,7 +315,7 @@ def test_bnrelu_materialised(prec, shape):
     z = rnd(prec, _rand((N, C, H, W), 141))
     bn = bn_table(N // ipg, C, 142)
     ref = bnrelu_ref(prec, z, bn, ipg)
-    out = torch.full((N, H, W, C), float('nan'), dtype=td, device='cuda')
+    out = guard.full((N, H, W, C), float('nan'), dtype=td)
     z_d, bn_d = to_nhwc(prec, z), dev(bn)
     _lib.call('bdn_bnrelu', dt, z_d.data_ptr(), bn_d.data_ptr(), ipg, out.data_ptr(), N, H, W, C, st())
     torch.cuda.synchronize()
@@ -315,6 +325,7 @@ def test_bnrelu_materialised(prec, shape):
 
 
 @pytest.mark.parametrize('prec', PRECS)
+@guarded
 def test_fuse_product(prec):
     B, H, W, C = 3, 10, 12, 64
     dt, td = DT[prec]
@@ -322,7 +333,7 @@ def test_fuse_product(prec):
     bn = bn_table(2, C, 44)
     a = bnrelu_ref(prec, z, bn, B)
     ref = torch.relu(a[B:] * a[:B])                      # models/bidate_model.py:35
-    out = torch.empty(B, H, W, C, dtype=td, device='cuda')
+    out = guard.empty(B, H, W, C, dtype=td)
     z_d, bn_d = to_nhwc(prec, z), dev(bn)
     _lib.call('bdn_fuse_product', dt, z_d.data_ptr(), bn_d.data_ptr(), out.data_ptr(), B, H, W, C, st())
     torch.cuda.synchronize()
@@ -336,6 +347,7 @@ UP_CASES = [(2, 8, 8, 16, 16, 64), (2, 5, 5, 11, 11, 64), (1, 22, 22, 45, 45, 32
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', UP_CASES)
 @pytest.mark.parametrize('bnrelu', [False, True])
+@guarded
 def test_upsample2x_and_backward(prec, case, bnrelu):
     B, h, w, H, W, C = case
     dt, td = DT[prec]
@@ -348,7 +360,7 @@ def test_upsample2x_and_backward(prec, case, bnrelu):
     # cross-check the oracle's bilinear against torch's own
     tref = O.pad_to(F.interpolate(a.double(), scale_factor=2, mode='bilinear', align_corners=True), skip)
     assert (ref.detach() - tref).abs().max() < 1e-6
-    out = torch.empty(B, H, W, C, dtype=td, device='cuda')
+    out = guard.empty(B, H, W, C, dtype=td)
     s_d, bn_d = to_nhwc(prec, src), dev(bn)
     _lib.call('bdn_upsample2x', dt, s_d.data_ptr(), IN_BNRELU if bnrelu else IN_PLAIN, bn_d.data_ptr(),
               out.data_ptr(), B, h, w, H, W, C, st())
@@ -360,8 +372,9 @@ def test_upsample2x_and_backward(prec, case, bnrelu):
     extra = 16
     dU = rnd(prec, _rand((B, C + extra, H, W), 47))
     ref.backward(dU[:, extra:].double())
-    dsrc = torch.empty(B, h, w, C, dtype=td, device='cuda')
+    dsrc = guard.empty(B, h, w, C, dtype=td)
     dU_d = to_nhwc(prec, dU)
+    dU_d[..., :extra] = float('nan')                    # the foreign channels ([dF | dU]): a read of them poisons the result
     es = 2 if prec == 'bf16' else 4
     _lib.call('bdn_upsample2x_bwd', dt, dU_d.data_ptr() + extra * es, C + extra, dsrc.data_ptr(), B, h, w, H, W, C, st())
     torch.cuda.synchronize()
@@ -371,14 +384,14 @@ def test_upsample2x_and_backward(prec, case, bnrelu):
     rows = _lib.load().bdn_upsample2x_bwd_rows(dt, B, h, w, C)
     if rows == 0:
         with pytest.raises(RuntimeError, match='outside the tiled kernel'):
-            t = torch.zeros(16, device='cuda')
+            t = guard.zeros(16)
             _lib.call('bdn_upsample2x_bwd_bs', dt, dU_d.data_ptr() + extra * es, C + extra, dsrc.data_ptr(), t.data_ptr(), t.data_ptr(),
                       t.data_ptr(), B, h, w, H, W, C, st())
         return
     zp = rnd(prec, _rand((B, C, h, w), 48))
     bnp = bn_table(1, C, 49)
-    dsrc2 = torch.empty_like(dsrc)
-    part = torch.full((rows, 2, C), float('nan'), device='cuda')
+    dsrc2 = guard.empty_like(dsrc)
+    part = guard.full((rows, 2, C), float('nan'))
     zp_d, bnp_d = to_nhwc(prec, zp), dev(bnp)
     _lib.call('bdn_upsample2x_bwd_bs', dt, dU_d.data_ptr() + extra * es, C + extra, dsrc2.data_ptr(), zp_d.data_ptr(), bnp_d.data_ptr(),
               part.data_ptr(), B, h, w, H, W, C, st())
@@ -392,6 +405,7 @@ def test_upsample2x_and_backward(prec, case, bnrelu):
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('case', [(2, 16, 16, 64, True), (2, 11, 45, 64, True), (3, 8, 8, 128, False), (1, 5, 5, 64, True)])
+@guarded
 def test_enc_skip_bwd(prec, case):
     B, H, W, C, pooled = case
     dt, td = DT[prec]
@@ -406,14 +420,15 @@ def test_enc_skip_bwd(prec, case):
         loss = loss + (O.maxpool2(a) * dP.double()).sum()
     loss.backward()
     ref = a.grad.float()
-    out = torch.empty(2 * B, H, W, C, dtype=td, device='cuda')
+    out = guard.empty(2 * B, H, W, C, dtype=td)
     dF_d, z_d, bn_d = to_nhwc(prec, dF), to_nhwc(prec, z), dev(bn)
+    dF_d[..., C:] = float('nan')                        # the foreign channels ([dF | dU]): a read of them poisons the result
     dP_d = to_nhwc(prec, dP) if pooled else None
     rows = _lib.load().bdn_enc_skip_bwd_rows(dt, B, H, W, C)
-    part = torch.full((2, rows, 2, C), float('nan'), device='cuda')
+    part = guard.full((2, rows, 2, C), float('nan'))
     _lib.call('bdn_enc_skip_bwd', dt, dF_d.data_ptr(), C + extra, z_d.data_ptr(), bn_d.data_ptr(),
               dP_d.data_ptr() if pooled else None, out.data_ptr(), part.data_ptr(), B, H, W, C, st())
-    out2 = torch.empty_like(out)
+    out2 = guard.empty_like(out)
     _lib.call('bdn_enc_skip_bwd', dt, dF_d.data_ptr(), C + extra, z_d.data_ptr(), bn_d.data_ptr(),
               dP_d.data_ptr() if pooled else None, out2.data_ptr(), None, B, H, W, C, st())
     torch.cuda.synchronize()
@@ -434,6 +449,7 @@ def test_enc_skip_bwd(prec, case):
 # ------------------------------------------------------------------ classifier
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('shape', [(2, 16, 16, 64, 2), (1, 9, 13, 64, 3)])
+@guarded
 def test_outc_fwd_bwd(prec, shape):
     B, H, W, C, ncls = shape
     dt, td = DT[prec]
@@ -443,24 +459,24 @@ def test_outc_fwd_bwd(prec, shape):
     a = bnrelu_ref(prec, z, bn, B).double().requires_grad_(True)
     wd_, bd_ = w.double().requires_grad_(True), b.double().requires_grad_(True)
     ref = O.conv1x1(a, wd_, bd_)
-    logits = torch.empty(B, ncls, H, W, device='cuda')
+    logits = guard.empty(B, ncls, H, W)
     z_d, bn_d, w_d, b_d = to_nhwc(prec, z), dev(bn), dev(w), dev(b)
     _lib.call('bdn_outc_fwd', dt, z_d.data_ptr(), bn_d.data_ptr(), w_d.data_ptr(), b_d.data_ptr(), logits.data_ptr(), B, H, W, C, ncls, st())
     torch.cuda.synchronize()
     assert_close('logits', logits.cpu(), ref.detach().float(), 1e-5)
     dl = _rand((B, ncls, H, W), 65)
     ref.backward(dl.double())
-    dA = torch.empty(B, H, W, C, dtype=td, device='cuda')
-    dw, db = torch.empty(ncls, C, device='cuda'), torch.empty(ncls, device='cuda')
+    dA = guard.empty(B, H, W, C, dtype=td)
+    dw, db = guard.empty(ncls, C), guard.empty(ncls)
     dl_d = dev(dl)
     rows = _lib.load().bdn_outc_bwd_rows(dt, B, H, W, C)
-    part = torch.full((rows, 2, C), float('nan'), device='cuda')
+    part = guard.full((rows, 2, C), float('nan'))
     wsz = _lib.load().bdn_outc_bwd_workspace_bytes(dt, B, H, W, C, ncls) // 4
-    ows = torch.full((wsz,), float('nan'), device='cuda')
+    ows = guard.full((wsz,), float('nan'))
     _lib.call('bdn_outc_bwd', dt, dl_d.data_ptr(), z_d.data_ptr(), bn_d.data_ptr(), w_d.data_ptr(), dA.data_ptr(),
               dw.data_ptr(), db.data_ptr(), part.data_ptr(), ows.data_ptr(), B, H, W, C, ncls, st())
-    dA2 = torch.empty_like(dA)
-    dw2, db2 = torch.full_like(dw, 5.0), torch.full_like(db, 5.0)
+    dA2 = guard.empty_like(dA)
+    dw2, db2 = guard.full_like(dw, 5.0), guard.full_like(db, 5.0)
     _lib.call('bdn_outc_bwd', dt, dl_d.data_ptr(), z_d.data_ptr(), bn_d.data_ptr(), w_d.data_ptr(), dA2.data_ptr(),
               dw2.data_ptr(), db2.data_ptr(), None, ows.data_ptr(), B, H, W, C, ncls, st())
     torch.cuda.synchronize()
@@ -476,6 +492,7 @@ def test_outc_fwd_bwd(prec, shape):
 
 # ------------------------------------------------------------------ Tversky loss
 @pytest.mark.parametrize('shape', [(3, 2, 24, 20), (2, 3, 16, 300), (64, 2, 128, 128)])
+@guarded
 def test_tversky(shape):
     B, ncls, H, W = shape
     logits = _rand((B, ncls, H, W), 71)
@@ -483,11 +500,11 @@ def test_tversky(shape):
     lg = logits.double().requires_grad_(True)
     ref = O.tversky_loss(lg, labels.long(), 0.1, 0.9)
     ref.backward()
-    ws = torch.empty(_lib.load().bdn_overlap_workspace_bytes(B, ncls, H, W, 0) // 4, device='cuda')
-    loss = torch.empty(1, device='cuda')
-    counts = torch.empty(4, dtype=torch.int32, device='cuda')
-    dl = torch.empty(B, ncls, H, W, device='cuda')
-    lg_d, lb_d = dev(logits), labels.cuda()
+    ws = guard.empty(_lib.load().bdn_overlap_workspace_bytes(B, ncls, H, W, 0) // 4)
+    loss = guard.empty(1)
+    counts = guard.empty(4, dtype=torch.int32)
+    dl = guard.empty(B, ncls, H, W)
+    lg_d, lb_d = dev(logits), guard.guard(labels)
     _lib.call('bdn_tversky', lg_d.data_ptr(), lb_d.data_ptr(), 0.1, 0.9, 1e-7, ws.data_ptr(), loss.data_ptr(),
               counts.data_ptr(), dl.data_ptr(), B, ncls, H, W, st())
     torch.cuda.synchronize()
@@ -500,16 +517,17 @@ def test_tversky(shape):
     assert counts.cpu().tolist() == exp
 
 
+@guarded
 def test_tversky_golden(golden_dir):
     """utils/metrics.py:130-171 value + gradient captured from the reference itself (G5)."""
     import os
     g = np.load(os.path.join(golden_dir, 'g5_losses.npz'))
     logits, labels = torch.from_numpy(g['logits']), torch.from_numpy(g['labels'])
     B, ncls, H, W = logits.shape
-    ws = torch.empty(_lib.load().bdn_overlap_workspace_bytes(B, ncls, H, W, 0) // 4, device='cuda')
-    loss = torch.empty(1, device='cuda')
-    dl = torch.empty(B, ncls, H, W, device='cuda')
-    lg_d, lb_d = dev(logits), labels.cuda()
+    ws = guard.empty(_lib.load().bdn_overlap_workspace_bytes(B, ncls, H, W, 0) // 4)
+    loss = guard.empty(1)
+    dl = guard.empty(B, ncls, H, W)
+    lg_d, lb_d = dev(logits), guard.guard(labels)
     _lib.call('bdn_tversky', lg_d.data_ptr(), lb_d.data_ptr(), 0.1, 0.9, 1e-7, ws.data_ptr(), loss.data_ptr(),
               None, dl.data_ptr(), B, ncls, H, W, st())
     torch.cuda.synchronize()
@@ -519,11 +537,12 @@ def test_tversky_golden(golden_dir):
 
 # ------------------------------------------------------------------ converters, SGD
 @pytest.mark.parametrize('prec', PRECS)
+@guarded
 def test_pack_input_and_weights(prec):
     dt, td = DT[prec]
     B, C, H, W, Cp = 2, 13, 9, 7, 16
     x1, x2 = _rand((B, C, H, W), 81), _rand((B, C, H, W), 82)
-    out = torch.empty(2 * B, H, W, Cp, dtype=td, device='cuda')
+    out = guard.empty(2 * B, H, W, Cp, dtype=td)
     a, b = dev(x1), dev(x2)
     _lib.call('bdn_pack_input', dt, a.data_ptr(), b.data_ptr(), out.data_ptr(), B, C, H, W, Cp, st())
     torch.cuda.synchronize()
@@ -543,6 +562,7 @@ def test_pack_input_and_weights(prec):
     assert torch.equal(dense_d[:C], rot) and (dense_d[C:] == 0).all()
 
 
+@guarded
 def test_sgd_step():
     n = 1000003
     p, g = _rand((n,), 91), _rand((n,), 92)
@@ -556,6 +576,7 @@ def test_sgd_step():
 @pytest.mark.parametrize('prec', ['fp32', 'bf16'])
 @pytest.mark.parametrize('case', [(4, 16, 16, 128, 64, 2), (6, 24, 40, 64, 128, 3), (4, 8, 8, 64, 64, 2), (2, 20, 18, 256, 128, 2),
                                   (2, 33, 17, 64, 64, 1), (8, 128, 128, 64, 64, 4)])
+@guarded
 def test_dgrad_with_fused_bn_bwd_stats(prec, case):
     """bdn_conv3x3_dgrad_bs + bdn_bn_bwd_apply == bdn_conv3x3 (data gradient) + bdn_bn_bwd: the stored dA is the plain data gradient
     under the ReLU mask of the producing layer (identical where the mask is on), and dgamma / dbeta / dz equal up to the summation order
@@ -580,26 +601,26 @@ def test_dgrad_with_fused_bn_bwd_stats(prec, case):
         bn[g, 3] = (0.1 - mean * gamma * inv).float()
     bn_d = dev(bn)
     # reference path: plain data gradient, then the three-kernel BatchNorm backward
-    dA_ref = torch.empty(N, H, W, Cout, dtype=td, device='cuda')
+    dA_ref = guard.empty(N, H, W, Cout, dtype=td)
     _lib.call('bdn_conv3x3', dt, dzin.data_ptr(), Cz, None, 0, 0, None, ipg, wf.data_ptr(), None, dA_ref.data_ptr(), None,
               N, H, W, Cout, st())
-    wsb = torch.empty(lib.bdn_bn_bwd_workspace_bytes(dt, N, H, W, Cout, ipg) // 4, device='cuda')
-    sums_r = torch.empty(G, 2, Cout, device='cuda')
-    dg_r, db_r = torch.empty(Cout, device='cuda'), torch.empty(Cout, device='cuda')
-    dz_r = torch.empty(N, H, W, Cout, dtype=td, device='cuda')
+    wsb = guard.empty(lib.bdn_bn_bwd_workspace_bytes(dt, N, H, W, Cout, ipg) // 4)
+    sums_r = guard.empty(G, 2, Cout)
+    dg_r, db_r = guard.empty(Cout), guard.empty(Cout)
+    dz_r = guard.empty(N, H, W, Cout, dtype=td)
     _lib.call('bdn_bn_bwd', dt, dA_ref.data_ptr(), Cout, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, Cout,
               wsb.data_ptr(), sums_r.data_ptr(), dg_r.data_ptr(), db_r.data_ptr(), dz_r.data_ptr(), st())
     # fused path
     nt = lib.bdn_conv3x3_num_mtiles(N, H, W, Cout, ipg)
     assert nt % G == 0
-    part = torch.full((nt, 2, Cout), float('nan'), device='cuda')
-    dA = torch.empty_like(dA_ref)
+    part = guard.full((nt, 2, Cout), float('nan'))
+    dA = guard.empty_like(dA_ref)
     _lib.call('bdn_conv3x3_dgrad_bs', dt, dzin.data_ptr(), Cz, wf.data_ptr(), dA.data_ptr(), z_d.data_ptr(), bn_d.data_ptr(),
               ipg, part.data_ptr(), N, H, W, Cout, st())
-    sums = torch.empty(G, 2, Cout, device='cuda')
-    dg, db = torch.empty(Cout, device='cuda'), torch.empty(Cout, device='cuda')
-    dz = torch.empty_like(dz_r)
-    scratch = torch.empty(lib.bdn_bn_bwd_scratch_bytes(G, Cout), dtype=torch.uint8, device='cuda') if N * H * W > 1500 else None
+    sums = guard.empty(G, 2, Cout)
+    dg, db = guard.empty(Cout), guard.empty(Cout)
+    dz = guard.empty_like(dz_r)
+    scratch = guard.empty(lib.bdn_bn_bwd_scratch_bytes(G, Cout), dtype=torch.uint8) if N * H * W > 1500 else None
     _lib.call('bdn_bn_bwd_apply', dt, dA.data_ptr(), Cout, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, Cout,
               part.data_ptr(), nt // G, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(), dz.data_ptr(),
               scratch.data_ptr() if scratch is not None else None, st())
@@ -613,6 +634,7 @@ def test_dgrad_with_fused_bn_bwd_stats(prec, case):
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('shape', [(2, 16, 16, 64, 2, 1), (4, 33, 20, 64, 2, 2), (2, 24, 24, 128, 3, 2), (2, 128, 128, 64, 2, 2)])
+@guarded
 def test_head_bn_bwd_recomputed_from_dlogits(prec, shape):
     """bdn_outc_bwd(dA = NULL) + bdn_bn_bwd_finalize + bdn_outc_bn_bwd_apply == bdn_outc_bwd + bdn_bn_bwd_apply, bit for bit
     (dz, sums, dgamma, dbeta): the classifier's data gradient is re-formed and re-rounded exactly as outc_bwd stores it."""
@@ -630,16 +652,16 @@ def test_head_bn_bwd_recomputed_from_dlogits(prec, shape):
     rows = lib.bdn_outc_bwd_rows(dt, B, H, W, C)
     out = {}
     for fused in (0, 1):
-        dA = torch.empty(B, H, W, C, dtype=td, device='cuda')
-        dw, db = torch.empty(ncls, C, device='cuda'), torch.empty(ncls, device='cuda')
-        part = torch.full((rows, 2, C), float('nan'), device='cuda')
+        dA = guard.empty(B, H, W, C, dtype=td)
+        dw, db = guard.empty(ncls, C), guard.empty(ncls)
+        part = guard.full((rows, 2, C), float('nan'))
         bn_d = dev(bn1)
-        ows = torch.empty(lib.bdn_outc_bwd_workspace_bytes(dt, B, H, W, C, ncls) // 4, device='cuda')
+        ows = guard.empty(lib.bdn_outc_bwd_workspace_bytes(dt, B, H, W, C, ncls) // 4)
         _lib.call('bdn_outc_bwd', dt, dl_d.data_ptr(), z_d.data_ptr(), bn_d.data_ptr(), w_d.data_ptr(),
                   None if fused else dA.data_ptr(), dw.data_ptr(), db.data_ptr(), part.data_ptr(), ows.data_ptr(), B, H, W, C, ncls, st())
-        sums = torch.empty(1, 2, C, device='cuda')
-        dg, dbt = torch.empty(C, device='cuda'), torch.empty(C, device='cuda')
-        dz = torch.full((B, H, W, C), float('nan'), dtype=td, device='cuda')
+        sums = guard.empty(1, 2, C)
+        dg, dbt = guard.empty(C), guard.empty(C)
+        dz = guard.full((B, H, W, C), float('nan'), dtype=td)
         if fused:
             _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), 1, C, part.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(),
                       dbt.data_ptr(), None, st())
@@ -659,6 +681,7 @@ def test_head_bn_bwd_recomputed_from_dlogits(prec, shape):
 
 
 @pytest.mark.parametrize('prec', PRECS)
+@guarded
 def test_pack_weights_multi_equals_per_layer_pack(prec):
     """bdn_pack_weights_multi (one call for a list of layers; bf16 takes the LDS-tiled kernel for regular layers and the
     element-wise one for the rest) writes the same fragment-order images as bdn_pack_weights layer by layer."""
@@ -671,16 +694,16 @@ def test_pack_weights_multi_equals_per_layer_pack(prec):
         if has_wd and cip % 32:
             continue
         w = dev(_rand((co, ci, 3, 3), 400 + i))
-        wf = torch.full((co * 9 * cip,), 7.0, dtype=td, device='cuda')
-        wd = torch.full((co * 9 * cip,), 7.0, dtype=td, device='cuda') if has_wd else None
+        wf = guard.full((co * 9 * cip,), 7.0, dtype=td)
+        wd = guard.full((co * 9 * cip,), 7.0, dtype=td) if has_wd else None
         ws.append((w, co, ci, cip)); outs.append((wf, wd))
         rec += struct.pack('<QQQiiii', w.data_ptr(), wf.data_ptr(), wd.data_ptr() if has_wd else 0, co, ci, cip, 0)
-    desc = torch.frombuffer(bytearray(rec), dtype=torch.uint8).cuda()
+    desc = guard.guard(torch.frombuffer(bytearray(rec), dtype=torch.uint8))
     _lib.call('bdn_pack_weights_multi', dt, desc.data_ptr(), len(ws), st())
     torch.cuda.synchronize()
     for (w, co, ci, cip), (wf, wd) in zip(ws, outs):
-        rf = torch.empty_like(wf)
-        rd = torch.empty_like(wd) if wd is not None else None
+        rf = guard.empty_like(wf)
+        rd = guard.empty_like(wd) if wd is not None else None
         _lib.call('bdn_pack_weights', dt, w.data_ptr(), rf.data_ptr(), rd.data_ptr() if rd is not None else None, co, ci, cip, st())
         torch.cuda.synchronize()
         assert torch.equal(wf, rf), (co, ci)
@@ -688,6 +711,7 @@ def test_pack_weights_multi_equals_per_layer_pack(prec):
             assert torch.equal(wd, rd), (co, ci)
 
 
+@guarded
 def test_pack_weights_multi_bf16x3_equals_per_layer_pack():
     """BDN_BF16X3: the LDS-tiled packer of the regular layers (round 6) and the element-wise one of the rest write the same
     [w_hi | w_hi | w_lo] images as bdn_pack_weights(BDN_BF16X3) layer by layer."""
@@ -697,16 +721,16 @@ def test_pack_weights_multi_bf16x3_equals_per_layer_pack():
     ws, outs, rec = [], [], b''
     for i, (co, ci, cip, has_wd) in enumerate(layers):
         w = dev(_rand((co, ci, 3, 3), 450 + i))
-        wf = torch.full((co * 9 * 3 * cip,), 7.0, dtype=torch.bfloat16, device='cuda')
-        wd = torch.full((co * 9 * 3 * cip,), 7.0, dtype=torch.bfloat16, device='cuda') if has_wd else None
+        wf = guard.full((co * 9 * 3 * cip,), 7.0, dtype=torch.bfloat16)
+        wd = guard.full((co * 9 * 3 * cip,), 7.0, dtype=torch.bfloat16) if has_wd else None
         ws.append((w, co, ci, cip)); outs.append((wf, wd))
         rec += struct.pack('<QQQiiii', w.data_ptr(), wf.data_ptr(), wd.data_ptr() if has_wd else 0, co, ci, cip, 0)
-    desc = torch.frombuffer(bytearray(rec), dtype=torch.uint8).cuda()
+    desc = guard.guard(torch.frombuffer(bytearray(rec), dtype=torch.uint8))
     _lib.call('bdn_pack_weights_multi', X3, desc.data_ptr(), len(ws), st())
     torch.cuda.synchronize()
     for (w, co, ci, cip), (wf, wd) in zip(ws, outs):
-        rf = torch.empty_like(wf)
-        rd = torch.empty_like(wd) if wd is not None else None
+        rf = guard.empty_like(wf)
+        rd = guard.empty_like(wd) if wd is not None else None
         _lib.call('bdn_pack_weights', X3, w.data_ptr(), rf.data_ptr(), rd.data_ptr() if rd is not None else None, co, ci, cip, st())
         torch.cuda.synchronize()
         assert torch.equal(wf, rf), (co, ci)
@@ -715,6 +739,7 @@ def test_pack_weights_multi_bf16x3_equals_per_layer_pack():
 
 
 @pytest.mark.parametrize('case', [(4, 32, 32, 2, 64), (6, 37, 50, 3, 64), (2, 128, 128, 1, 64), (4, 24, 16, 2, 80)])
+@guarded
 def test_first_layer_wgrad_with_fused_bn_bwd(case):
     """bdn_bn_bwd_finalize + bdn_conv3x3_wgrad_bnbwd == bdn_bn_bwd_apply + bdn_conv3x3_wgrad (bf16, 13 real channels padded to
     16): same dgamma / dbeta / sums bit for bit, weight gradient equal up to the summation order of the partial tiles.
@@ -753,20 +778,21 @@ def test_first_layer_wgrad_with_fused_bn_bwd(case):
             part[g * rows + r, 0] = gm[sl, :, hs].double().sum((0, 2, 3)).float()
             part[g * rows + r, 1] = (gm[sl, :, hs].double() * z[sl, :, hs].double()).sum((0, 2, 3)).float()
     part_d = dev(part)
+    dA_full[..., Cout:] = float('nan')                  # the foreign channels of the wider dA: a read of them poisons the result
     wsz = lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0, ipg) // 4
     out = {}
     for fused in (0, 1):
-        sums = torch.full((G, 2, Cout), float('nan'), device='cuda')
-        dg, db = torch.empty(Cout, device='cuda'), torch.empty(Cout, device='cuda')
-        wpart = torch.empty(wsz, device='cuda')
-        dw = torch.full((Cout, Creal, 3, 3), float('nan'), device='cuda')
+        sums = guard.full((G, 2, Cout), float('nan'))
+        dg, db = guard.empty(Cout), guard.empty(Cout)
+        wpart = guard.empty(wsz)
+        dw = guard.full((Cout, Creal, 3, 3), float('nan'))
         if fused:
             _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), G, Cout, part_d.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(),
                       db.data_ptr(), None, st())
             _lib.call('bdn_conv3x3_wgrad_bnbwd', dt, dA_full.data_ptr(), ldA, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg,
                       Cout, x_d.data_ptr(), C0, wpart.data_ptr(), dw.data_ptr(), Creal, N, H, W, st())
         else:
-            dz = torch.empty(N, H, W, Cout, dtype=td, device='cuda')
+            dz = guard.empty(N, H, W, Cout, dtype=td)
             _lib.call('bdn_bn_bwd_apply', dt, dA_full.data_ptr(), ldA, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, Cout,
                       part_d.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(), dz.data_ptr(), None, st())
             _lib.call('bdn_conv3x3_wgrad', dt, dz.data_ptr(), Cout, x_d.data_ptr(), C0, None, 0, 0, None, ipg,
@@ -784,14 +810,15 @@ def test_first_layer_wgrad_with_fused_bn_bwd(case):
 
 @pytest.mark.parametrize('prec', PRECS)
 @pytest.mark.parametrize('shape', [(2, 16, 16, 64), (1, 45, 22, 64), (2, 11, 11, 128), (1, 2, 3, 256)])
+@guarded
 def test_product_pool_equals_separate_kernels(prec, shape):
     """bdn_product_pool == bdn_fuse_product + bdn_bnrelu_pool, bit for bit (odd sizes: floor-mode pooling)."""
     B, H, W, C = shape
     dt, td = DT[prec]
     z_d = to_nhwc(prec, rnd(prec, _rand((2 * B, C, H, W), 71)))
     bn_d = dev(bn_table(2, C, 72))
-    f1 = torch.empty(B, H, W, C, dtype=td, device='cuda'); f2 = torch.full_like(f1, 3.0)
-    p1 = torch.empty(2 * B, H // 2, W // 2, C, dtype=td, device='cuda'); p2 = torch.full_like(p1, 3.0)
+    f1 = guard.empty(B, H, W, C, dtype=td); f2 = guard.full_like(f1, 3.0)
+    p1 = guard.empty(2 * B, H // 2, W // 2, C, dtype=td); p2 = guard.full_like(p1, 3.0)
     _lib.call('bdn_fuse_product', dt, z_d.data_ptr(), bn_d.data_ptr(), f1.data_ptr(), B, H, W, C, st())
     _lib.call('bdn_bnrelu_pool', dt, z_d.data_ptr(), bn_d.data_ptr(), B, p1.data_ptr(), 2 * B, H, W, C, st())
     _lib.call('bdn_product_pool', dt, z_d.data_ptr(), bn_d.data_ptr(), f2.data_ptr(), p2.data_ptr(), B, H, W, C, st())
@@ -799,6 +826,7 @@ def test_product_pool_equals_separate_kernels(prec, shape):
     assert torch.equal(f1, f2) and torch.equal(p1, p2)
 
 
+@guarded
 def test_wgrad_phases_variant_and_per_call_flags():
     """bdn_conv3x3_wgrad_ex(phases 1 then 2) == bdn_conv3x3_wgrad; the per-call grid-size field changes the workspace, not the
     result beyond the summation order of the partial tiles; bdn_conv3x3_wgrad_variant names the kernel family; there is no
@@ -820,9 +848,9 @@ def test_wgrad_phases_variant_and_per_call_flags():
     for blocks in (0, 64):
         fl = wg_flags(0, 0, blocks)
         nbytes = lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, fl)
-        part = torch.empty(nbytes // 4, device='cuda')
-        a = torch.empty(Cout, C0, 3, 3, device='cuda')
-        b = torch.full_like(a, float('nan'))
+        part = guard.empty(nbytes // 4)
+        a = guard.empty(Cout, C0, 3, 3)
+        b = guard.full_like(a, float('nan'))
         _lib.call('bdn_conv3x3_wgrad_ex', dt, dz.data_ptr(), Cout, x.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg,
                   part.data_ptr(), a.data_ptr(), C0, N, H, W, fl | 3, st())
         for ph in (1, 2):
@@ -833,8 +861,8 @@ def test_wgrad_phases_variant_and_per_call_flags():
         res[blocks] = (a.cpu(), nbytes)
     assert res[64][1] < res[0][1] <= default_bytes
     assert lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0, ipg) == default_bytes        # nothing above changed what it answers
-    c = torch.empty(Cout, C0, 3, 3, device='cuda')
-    part = torch.empty(default_bytes // 4, device='cuda')
+    c = guard.empty(Cout, C0, 3, 3)
+    part = guard.empty(default_bytes // 4)
     _lib.call('bdn_conv3x3_wgrad', dt, dz.data_ptr(), Cout, x.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg,
               part.data_ptr(), c.data_ptr(), C0, N, H, W, st())
     torch.cuda.synchronize()
@@ -846,6 +874,7 @@ def test_wgrad_phases_variant_and_per_call_flags():
 
 
 @pytest.mark.parametrize('mode', ['bnrelu', 'plain', 'plain2'])
+@guarded
 def test_wgrad_kernel_variants_agree(mode):
     """Both weight-gradient kernels a shape may run give the same dW up to the summation order of the partial tiles
     (ragged map, two statistic groups / two concatenated sources).  The role-split kernel stages the patch through its
@@ -869,8 +898,8 @@ def test_wgrad_kernel_variants_agree(mode):
     for v in (WG_SIMPLE, WG_ROLE):
         fl = wg_flags(3, v, 0)
         ran[v] = lib.bdn_conv3x3_wgrad_variant(dt, N, H, W, Cout, C0, C1, ipg, in_mode, fl)
-        part = torch.empty(lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, C1, ipg, in_mode, fl) // 4, device='cuda')
-        dw = torch.full((Cout, C0 + C1, 3, 3), float('nan'), device='cuda')
+        part = guard.empty(lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, C1, ipg, in_mode, fl) // 4)
+        dw = guard.full((Cout, C0 + C1, 3, 3), float('nan'))
         _lib.call('bdn_conv3x3_wgrad_ex', dt, dz.data_ptr(), Cout, x0.data_ptr(), C0, x1.data_ptr() if x1 is not None else None, C1,
                   in_mode, bn_d.data_ptr() if bn_d is not None else None, ipg, part.data_ptr(), dw.data_ptr(), C0 + C1, N, H, W, fl, st())
         torch.cuda.synchronize()
@@ -879,11 +908,11 @@ def test_wgrad_kernel_variants_agree(mode):
     assert ran[WG_SIMPLE] == WG_SIMPLE and ran[WG_ROLE] == WG_ROLE
     assert_close('role-split vs simple', out[WG_ROLE], out[WG_SIMPLE], 2e-6)
     if mode == 'bnrelu':                                     # register path (BatchNorm on load) == LDS-DMA path on the materialised operand
-        act = torch.empty_like(x0)
+        act = guard.empty_like(x0)
         _lib.call('bdn_bnrelu', dt, x0.data_ptr(), bn_d.data_ptr(), ipg, act.data_ptr(), N, H, W, C0, st())
         fl = wg_flags(3, WG_ROLE, 0)
-        part = torch.empty(lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, fl) // 4, device='cuda')
-        dw = torch.full((Cout, C0, 3, 3), float('nan'), device='cuda')
+        part = guard.empty(lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, fl) // 4)
+        dw = guard.full((Cout, C0, 3, 3), float('nan'))
         _lib.call('bdn_conv3x3_wgrad_ex', dt, dz.data_ptr(), Cout, act.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg,
                   part.data_ptr(), dw.data_ptr(), C0, N, H, W, fl, st())
         torch.cuda.synchronize()
@@ -891,6 +920,7 @@ def test_wgrad_kernel_variants_agree(mode):
 
 @pytest.mark.parametrize('shape', [(1, 8, 16, 64, 64, 1), (1, 9, 17, 64, 64, 1), (2, 8, 16, 128, 64, 1), (3, 24, 16, 64, 192, 3), (4, 16, 32, 64, 64, 2)])
 @pytest.mark.parametrize('bn', [False, True])
+@guarded
 def test_role_split_wgrad_on_tiny_problems(shape, bn):
     """wgrad7's pipeline prologue / epilogue on problems of one to a few 128-pixel chunks per block (a block whose split holds a single
     chunk still issues its two look-ahead fetches, all masked) and on odd chunk counts: same dW as the one-chunk-at-a-time kernel."""
@@ -907,8 +937,8 @@ def test_role_split_wgrad_on_tiny_problems(shape, bn):
         for blocks in ((0, 1, 7) if v == WG_ROLE else (0,)):          # 1 block: one split holds every chunk; 7: odd chunk counts per split
             fl = wg_flags(3, v, blocks)
             assert lib.bdn_conv3x3_wgrad_variant(dt, N, H, W, Cout, C0, 0, ipg, mode, fl) == v
-            part = torch.empty(lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, 0, ipg, mode, fl) // 4, device='cuda')
-            dw = torch.full((Cout, C0, 3, 3), float('nan'), device='cuda')
+            part = guard.empty(lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, 0, ipg, mode, fl) // 4)
+            dw = guard.full((Cout, C0, 3, 3), float('nan'))
             _lib.call('bdn_conv3x3_wgrad_ex', dt, dz.data_ptr(), Cout, x0.data_ptr(), C0, None, 0, mode, bn_d.data_ptr() if bn else None, ipg,
                       part.data_ptr(), dw.data_ptr(), C0, N, H, W, fl, st())
             torch.cuda.synchronize()
@@ -927,6 +957,7 @@ def _split_ref(t_nchw):
 
 
 @pytest.mark.parametrize('case', [(2, 9, 7, 16, 0, False), (4, 16, 16, 64, 64, False), (4, 12, 20, 128, 0, True)])
+@guarded
 def test_split_pack_is_the_exact_hi_lo_split(case):
     """bdn_split_pack: hi = bf16(x), lo = bf16(x - hi) of cat(src0, src1) resp. relu(bn(src0)); hi + lo reproduces x to 2^-16."""
     N, H, W, C0, C1, use_bn = case
@@ -935,7 +966,7 @@ def test_split_pack_is_the_exact_hi_lo_split(case):
     bn = bn_table(2, C0, 303)
     a0 = bnrelu_ref('fp32', x0, bn, ipg) if use_bn else x0
     full = torch.cat([a0, x1], 1) if C1 else a0
-    out = torch.empty(N, H, W, 2 * (C0 + C1), dtype=torch.bfloat16, device='cuda')
+    out = guard.empty(N, H, W, 2 * (C0 + C1), dtype=torch.bfloat16)
     d0, d1 = to_nhwc('fp32', x0), (to_nhwc('fp32', x1) if C1 else None)
     bn_d = dev(bn)
     _lib.call('bdn_split_pack', d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1, IN_BNRELU if use_bn else IN_PLAIN,
@@ -953,6 +984,7 @@ def test_split_pack_is_the_exact_hi_lo_split(case):
 
 @pytest.mark.parametrize('case', [(2, 16, 16, 64, 64, 1), (2, 8, 8, 128, 64, 2), (1, 22, 45, 16, 64, 1), (3, 19, 33, 64, 128, 3),
                                   (2, 12, 12, 192, 64, 2), (36, 32, 32, 128, 256, 18), (2, 8, 8, 256, 128, 1)])
+@guarded
 def test_conv3x3_bf16x3_forward_dgrad_wgrad(case):
     """The bf16 kernels on split operands (three times the reduction length) against the float32 oracle: forward with
     statistics, data gradient and weight gradient all within 1e-4 of the tensor's magnitude (a plain bf16 GEMM sits at 1e-2)."""
@@ -964,16 +996,16 @@ def test_conv3x3_bf16x3_forward_dgrad_wgrad(case):
     b = _rand((Cout,), 313)
     ref = F.conv2d(x, w, b, padding=1)
     # forward
-    sp = torch.empty(N, H, W, 2 * Cin, dtype=torch.bfloat16, device='cuda')
+    sp = guard.empty(N, H, W, 2 * Cin, dtype=torch.bfloat16)
     xd = to_nhwc('fp32', x)
     _lib.call('bdn_split_pack', xd.data_ptr(), Cin, None, 0, IN_PLAIN, None, ipg, sp.data_ptr(), N, H, W, st())
-    wf = torch.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16, device='cuda')
-    wd = torch.empty(Cin, 9, 3 * Cout, dtype=torch.bfloat16, device='cuda') if Cin % 64 == 0 else None
+    wf = guard.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16)
+    wd = guard.empty(Cin, 9, 3 * Cout, dtype=torch.bfloat16) if Cin % 64 == 0 else None
     wdev = dev(w)
     _lib.call('bdn_pack_weights', X3, wdev.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None, Cout, Cin, Cin, st())
-    out = torch.full((N, H, W, Cout), float('nan'), device='cuda')
+    out = guard.full((N, H, W, Cout), float('nan'))
     nt = lib.bdn_conv3x3_num_mtiles_ex(X3, N, H, W, Cin, Cout, ipg)         # (operands of >= 64 channels: the fused-split-product kernels' own tile plan)
-    stats = torch.full((nt, 2, Cout), float('nan'), device='cuda')
+    stats = guard.full((nt, 2, Cout), float('nan'))
     bd = dev(b)
     _lib.call('bdn_conv3x3', X3, sp.data_ptr(), Cin, None, 0, IN_PLAIN, None, ipg, wf.data_ptr(), bd.data_ptr(), out.data_ptr(),
               stats.data_ptr(), N, H, W, Cout, st())
@@ -989,18 +1021,18 @@ def test_conv3x3_bf16x3_forward_dgrad_wgrad(case):
     # gradients
     dz = _rand((N, Cout, H, W), 314)
     dzd = to_nhwc('fp32', dz)
-    spd = torch.empty(N, H, W, 2 * Cout, dtype=torch.bfloat16, device='cuda')
+    spd = guard.empty(N, H, W, 2 * Cout, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', dzd.data_ptr(), Cout, None, 0, IN_PLAIN, None, ipg, spd.data_ptr(), N, H, W, st())
     if wd is not None:
-        dA = torch.full((N, H, W, Cin), float('nan'), device='cuda')
+        dA = guard.full((N, H, W, Cin), float('nan'))
         _lib.call('bdn_conv3x3', X3, spd.data_ptr(), Cout, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None, dA.data_ptr(), None,
                   N, H, W, Cin, st())
         torch.cuda.synchronize()
         assert_close('x3 dgrad', from_nhwc(dA), torch.nn.grad.conv2d_input(x.shape, w, dz, padding=1), 1e-4)
     nb = lib.bdn_wgrad_workspace_bytes_ex(X3, N, H, W, Cout, Cin, 0, ipg, IN_PLAIN, 3)
     assert nb <= lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, Cin, ipg)
-    part = torch.empty(nb // 4, device='cuda')
-    dw = torch.full((Cout, Cin, 3, 3), float('nan'), device='cuda')
+    part = guard.empty(nb // 4)
+    dw = guard.full((Cout, Cin, 3, 3), float('nan'))
     _lib.call('bdn_conv3x3_wgrad', X3, spd.data_ptr(), Cout, sp.data_ptr(), Cin, None, 0, IN_PLAIN, None, ipg,
               part.data_ptr(), dw.data_ptr(), Cin, N, H, W, st())
     torch.cuda.synchronize()
@@ -1010,6 +1042,7 @@ def test_conv3x3_bf16x3_forward_dgrad_wgrad(case):
 @pytest.mark.parametrize('dtype', ['x3', 'x2'])
 @pytest.mark.parametrize('case', [(2, 16, 16, 64, 64, 1, True), (4, 8, 8, 128, 64, 2, True), (3, 19, 33, 64, 128, 3, True), (2, 12, 12, 192, 64, 2, False),
                                   (36, 32, 32, 128, 256, 18, True), (2, 8, 8, 512, 128, 1, True), (2, 40, 72, 64, 64, 1, True)])
+@guarded
 def test_conv3x3_x3src_equals_split_pack_then_conv(case, dtype):
     """bdn_conv3x3_x3src (float32 operand; BatchNorm+ReLU and the bf16 hi / lo split inside the convolution's staging -- models/unet_parts.py:14-16)
     against the two launches it replaces, bdn_split_pack + bdn_conv3x3 on the split operand: output, statistics partials and the split operand it
@@ -1023,27 +1056,27 @@ def test_conv3x3_x3src_equals_split_pack_then_conv(case, dtype):
     bn = bn_table(N // ipg, Cin, 714)
     xd, bn_d, bd, wdev = to_nhwc('fp32', x), dev(bn), dev(b), dev(w)
     mode = IN_BNRELU if use_bn else IN_PLAIN
-    wf = torch.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16, device='cuda')
+    wf = guard.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16)
     _lib.call('bdn_pack_weights', _lib.BDN_BF16X3, wdev.data_ptr(), wf.data_ptr(), None, Cout, Cin, Cin, st())
     nt = lib.bdn_conv3x3_num_mtiles_ex(DT, N, H, W, Cin, Cout, ipg)
     # the two launches
-    sp = torch.empty(N, H, W, 2 * Cin, dtype=torch.bfloat16, device='cuda')
+    sp = guard.empty(N, H, W, 2 * Cin, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', xd.data_ptr(), Cin, None, 0, mode, bn_d.data_ptr(), ipg, sp.data_ptr(), N, H, W, st())
-    out0 = torch.full((N, H, W, Cout), float('nan'), device='cuda')
-    st0 = torch.full((nt, 2, Cout), float('nan'), device='cuda')
+    out0 = guard.full((N, H, W, Cout), float('nan'))
+    st0 = guard.full((nt, 2, Cout), float('nan'))
     _lib.call('bdn_conv3x3', DT, sp.data_ptr(), Cin, None, 0, IN_PLAIN, None, ipg, wf.data_ptr(), bd.data_ptr(), out0.data_ptr(),
               st0.data_ptr(), N, H, W, Cout, st())
     # the one launch
-    sp1 = torch.full((N, H, W, 2 * Cin), float('nan'), dtype=torch.bfloat16, device='cuda')
-    out1 = torch.full((N, H, W, Cout), float('nan'), device='cuda')
-    st1 = torch.full((nt, 2, Cout), float('nan'), device='cuda')
+    sp1 = guard.full((N, H, W, 2 * Cin), float('nan'), dtype=torch.bfloat16)
+    out1 = guard.full((N, H, W, Cout), float('nan'))
+    st1 = guard.full((nt, 2, Cout), float('nan'))
     _lib.call('bdn_conv3x3_x3src', DT, xd.data_ptr(), Cin, mode, bn_d.data_ptr(), ipg, wf.data_ptr(), bd.data_ptr(), out1.data_ptr(),
               st1.data_ptr(), sp1.data_ptr(), N, H, W, Cout, st())
     torch.cuda.synchronize()
     assert torch.equal(sp1.view(torch.int16), sp.view(torch.int16))
     assert torch.equal(out1, out0) and torch.equal(st1, st0)
     # without the by-product (eval forwards), same output
-    out2 = torch.full((N, H, W, Cout), float('nan'), device='cuda')
+    out2 = guard.full((N, H, W, Cout), float('nan'))
     _lib.call('bdn_conv3x3_x3src', DT, xd.data_ptr(), Cin, mode, bn_d.data_ptr(), ipg, wf.data_ptr(), bd.data_ptr(), out2.data_ptr(),
               None, None, N, H, W, Cout, st())
     torch.cuda.synchronize()
@@ -1057,6 +1090,7 @@ def test_conv3x3_x3src_equals_split_pack_then_conv(case, dtype):
 
 
 @pytest.mark.parametrize('case', [(2, 16, 16, 64, 64, 1), (2, 8, 8, 128, 64, 2), (3, 19, 33, 64, 128, 3), (2, 12, 12, 192, 64, 2)])
+@guarded
 def test_conv3x3_bf16x2_backward_gemms(case):
     """BDN_BF16X2, the two-term backward of the bf16x3 setting, on the operands and filter images of BDN_BF16X3: the data gradient equals
     the exact data gradient with the FILTER rounded to bf16 (dz in full), the weight gradient the exact one with DZ rounded to bf16 (the
@@ -1067,17 +1101,17 @@ def test_conv3x3_bf16x2_backward_gemms(case):
     x = _rand((N, Cin, H, W), 321)
     w = _rand((Cout, Cin, 3, 3), 322) * 0.1
     dz = _rand((N, Cout, H, W), 323)
-    sp = torch.empty(N, H, W, 2 * Cin, dtype=torch.bfloat16, device='cuda')
+    sp = guard.empty(N, H, W, 2 * Cin, dtype=torch.bfloat16)
     xd = to_nhwc('fp32', x)
     _lib.call('bdn_split_pack', xd.data_ptr(), Cin, None, 0, IN_PLAIN, None, ipg, sp.data_ptr(), N, H, W, st())
-    wf = torch.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16, device='cuda')
-    wd = torch.empty(Cin, 9, 3 * Cout, dtype=torch.bfloat16, device='cuda')
+    wf = guard.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16)
+    wd = guard.empty(Cin, 9, 3 * Cout, dtype=torch.bfloat16)
     wdev = dev(w)
     _lib.call('bdn_pack_weights', X3, wdev.data_ptr(), wf.data_ptr(), wd.data_ptr(), Cout, Cin, Cin, st())
     dzd = to_nhwc('fp32', dz)
-    spd = torch.empty(N, H, W, 2 * Cout, dtype=torch.bfloat16, device='cuda')
+    spd = guard.empty(N, H, W, 2 * Cout, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', dzd.data_ptr(), Cout, None, 0, IN_PLAIN, None, ipg, spd.data_ptr(), N, H, W, st())
-    dA = torch.full((N, H, W, Cin), float('nan'), device='cuda')
+    dA = guard.full((N, H, W, Cin), float('nan'))
     _lib.call('bdn_conv3x3', X2, spd.data_ptr(), Cout, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None, dA.data_ptr(), None,
               N, H, W, Cin, st())
     torch.cuda.synchronize()
@@ -1087,8 +1121,8 @@ def test_conv3x3_bf16x2_backward_gemms(case):
     full = torch.nn.grad.conv2d_input(x.shape, w, dz, padding=1)
     assert (from_nhwc(dA) - full).abs().max() > 3e-4 * full.abs().max()
     nb = lib.bdn_wgrad_workspace_bytes_ex(X2, N, H, W, Cout, Cin, 0, ipg, IN_PLAIN, 3)
-    part = torch.empty(nb // 4, device='cuda')
-    dw = torch.full((Cout, Cin, 3, 3), float('nan'), device='cuda')
+    part = guard.empty(nb // 4)
+    dw = guard.full((Cout, Cin, 3, 3), float('nan'))
     _lib.call('bdn_conv3x3_wgrad', X2, spd.data_ptr(), Cout, sp.data_ptr(), Cin, None, 0, IN_PLAIN, None, ipg,
               part.data_ptr(), dw.data_ptr(), Cin, N, H, W, st())
     torch.cuda.synchronize()
@@ -1097,6 +1131,7 @@ def test_conv3x3_bf16x2_backward_gemms(case):
 
 @pytest.mark.parametrize('dtype', ['x3', 'x2'])
 @pytest.mark.parametrize('case', [(4, 32, 32, 2, 64), (6, 37, 50, 3, 64), (2, 128, 128, 1, 64), (4, 24, 16, 2, 80)])
+@guarded
 def test_first_layer_wgrad_with_fused_bn_bwd_bf16x3(case, dtype):
     """bf16x3 / bf16x2 form of bdn_conv3x3_wgrad_bnbwd (round 6): float32 dA and z, BatchNorm backward + hi / lo split of dz inside the staging,
     the input's split operand from bdn_pack_input(BDN_BF16X3)'s layout, the terms of the split product summed in one accumulator.  Against
@@ -1114,7 +1149,7 @@ def test_first_layer_wgrad_with_fused_bn_bwd_bf16x3(case, dtype):
     z_d = to_nhwc('fp32', z)
     x = _rand((N, C0, H, W), 803); x[:, Creal:] = 0
     x_d = to_nhwc('fp32', x)
-    xs = torch.empty(N, H, W, 2 * C0, dtype=torch.bfloat16, device='cuda')
+    xs = guard.empty(N, H, W, 2 * C0, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', x_d.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, xs.data_ptr(), N, H, W, st())
     bn = bn_table(G, Cout, 804)
     for g in range(G):
@@ -1137,20 +1172,21 @@ def test_first_layer_wgrad_with_fused_bn_bwd_bf16x3(case, dtype):
             part[g * rows + r, 0] = gm[sl, :, hs].double().sum((0, 2, 3)).float()
             part[g * rows + r, 1] = (gm[sl, :, hs].double() * z[sl, :, hs].double()).sum((0, 2, 3)).float()
     part_d = dev(part)
+    dA_full[..., Cout:] = float('nan')                  # the foreign channels of the wider dA: a read of them poisons the result
     wsz = max(lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0, ipg), lib.bdn_wgrad_workspace_bytes_ex(DT_, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, 3)) // 4
     out = {}
     for fused in (0, 1):
-        sums = torch.full((G, 2, Cout), float('nan'), device='cuda')
-        dg, db = torch.empty(Cout, device='cuda'), torch.empty(Cout, device='cuda')
-        wpart = torch.empty(wsz, device='cuda')
-        dw = torch.full((Cout, Creal, 3, 3), float('nan'), device='cuda')
+        sums = guard.full((G, 2, Cout), float('nan'))
+        dg, db = guard.empty(Cout), guard.empty(Cout)
+        wpart = guard.empty(wsz)
+        dw = guard.full((Cout, Creal, 3, 3), float('nan'))
         if fused:
             _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), G, Cout, part_d.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(),
                       db.data_ptr(), None, st())
             _lib.call('bdn_conv3x3_wgrad_bnbwd', DT_, dA_full.data_ptr(), ldA, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg,
                       Cout, xs.data_ptr(), C0, wpart.data_ptr(), dw.data_ptr(), Creal, N, H, W, st())
         else:
-            dzs = torch.empty(N, H, W, 2 * Cout, dtype=torch.bfloat16, device='cuda')
+            dzs = guard.empty(N, H, W, 2 * Cout, dtype=torch.bfloat16)
             _lib.call('bdn_bn_bwd_apply_split', dA_full.data_ptr(), ldA, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, Cout,
                       part_d.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(), dzs.data_ptr(), None, st())
             _lib.call('bdn_conv3x3_wgrad', DT_, dzs.data_ptr(), Cout, xs.data_ptr(), C0, None, 0, 0, None, ipg,
@@ -1175,6 +1211,7 @@ def test_first_layer_wgrad_with_fused_bn_bwd_bf16x3(case, dtype):
         assert_close('x3 fused first-layer wgrad', out[1][3], ref, 2e-4)
 
 
+@guarded
 def test_pack_input_and_head_bn_bwd_store_the_split_operand_directly():
     """bf16x3 setting, round 6: bdn_pack_input(BDN_BF16X3) and bdn_outc_bn_bwd_apply(BDN_BF16X3) store what bdn_split_pack would make of their
     float32 outputs -- the first convolution's operand and d4b's dz -- bit for bit, so a bf16x3 step launches no split pass for them."""
@@ -1182,11 +1219,11 @@ def test_pack_input_and_head_bn_bwd_store_the_split_operand_directly():
     lib = _lib.load()
     B, C, H, W, Cp = 3, 13, 20, 24, 16
     a, b = dev(_rand((B, C, H, W), 91)), dev(_rand((B, C, H, W), 92))
-    x0 = torch.empty(2 * B, H, W, Cp, device='cuda')
+    x0 = guard.empty(2 * B, H, W, Cp)
     _lib.call('bdn_pack_input', BDN_F32, a.data_ptr(), b.data_ptr(), x0.data_ptr(), B, C, H, W, Cp, st())
-    ref = torch.empty(2 * B, H, W, 2 * Cp, dtype=torch.bfloat16, device='cuda')
+    ref = guard.empty(2 * B, H, W, 2 * Cp, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', x0.data_ptr(), Cp, None, 0, IN_PLAIN, None, B, ref.data_ptr(), 2 * B, H, W, st())
-    got = torch.full_like(ref, float('nan'))
+    got = guard.full_like(ref, float('nan'))
     _lib.call('bdn_pack_input', BDN_BF16X3, a.data_ptr(), b.data_ptr(), got.data_ptr(), B, C, H, W, Cp, st())
     torch.cuda.synchronize()
     assert torch.equal(got.view(torch.int16), ref.view(torch.int16))
@@ -1196,25 +1233,26 @@ def test_pack_input_and_head_bn_bwd_store_the_split_operand_directly():
     bn_d = dev(bn_table(1, C, 94))
     w_d, dl_d = dev(_rand((ncls, C), 95, 0.2)), dev(_rand((B, ncls, H, W), 96))
     rows = lib.bdn_outc_bwd_rows(BDN_F32, B, H, W, C)
-    dw, db = torch.empty(ncls, C, device='cuda'), torch.empty(ncls, device='cuda')
-    part = torch.empty(rows, 2, C, device='cuda')
-    ows = torch.empty(lib.bdn_outc_bwd_workspace_bytes(BDN_F32, B, H, W, C, ncls) // 4, device='cuda')
+    dw, db = guard.empty(ncls, C), guard.empty(ncls)
+    part = guard.empty(rows, 2, C)
+    ows = guard.empty(lib.bdn_outc_bwd_workspace_bytes(BDN_F32, B, H, W, C, ncls) // 4)
     _lib.call('bdn_outc_bwd', BDN_F32, dl_d.data_ptr(), z_d.data_ptr(), bn_d.data_ptr(), w_d.data_ptr(), None, dw.data_ptr(), db.data_ptr(),
               part.data_ptr(), ows.data_ptr(), B, H, W, C, ncls, st())
-    sums = torch.empty(1, 2, C, device='cuda'); dg, dbt = torch.empty(C, device='cuda'), torch.empty(C, device='cuda')
+    sums = guard.empty(1, 2, C); dg, dbt = guard.empty(C), guard.empty(C)
     _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), 1, C, part.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(), dbt.data_ptr(), None, st())
-    dz = torch.empty(B, H, W, C, device='cuda')
+    dz = guard.empty(B, H, W, C)
     _lib.call('bdn_outc_bn_bwd_apply', BDN_F32, dl_d.data_ptr(), w_d.data_ptr(), z_d.data_ptr(), bn_d.data_ptr(), B, sums.data_ptr(),
               dz.data_ptr(), B, H, W, C, ncls, st())
-    ref = torch.empty(B, H, W, 2 * C, dtype=torch.bfloat16, device='cuda')
+    ref = guard.empty(B, H, W, 2 * C, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', dz.data_ptr(), C, None, 0, IN_PLAIN, None, B, ref.data_ptr(), B, H, W, st())
-    got = torch.full_like(ref, float('nan'))
+    got = guard.full_like(ref, float('nan'))
     _lib.call('bdn_outc_bn_bwd_apply', BDN_BF16X3, dl_d.data_ptr(), w_d.data_ptr(), z_d.data_ptr(), bn_d.data_ptr(), B, sums.data_ptr(),
               got.data_ptr(), B, H, W, C, ncls, st())
     torch.cuda.synchronize()
     assert torch.equal(got.view(torch.int16), ref.view(torch.int16))
 
 
+@guarded
 def test_split_outputs_of_the_bf16x3_producers_equal_split_pack():
     """bf16x3 setting: bdn_product_pool_split / bdn_upsample2x_split / bdn_bn_bwd_apply_split store their float32 results directly as
     the [hi | lo] bf16 operands of the consuming GEMMs; each must equal bdn_split_pack of the float32 kernel's output bit for bit."""
@@ -1223,18 +1261,18 @@ def test_split_outputs_of_the_bf16x3_producers_equal_split_pack():
     z = _rand((2 * B, C, H, W), 81)
     bn = bn_table(2, C, 82)
     z_d, bn_d = to_nhwc('fp32', z), dev(bn)
-    f = torch.empty(B, H, W, C, device='cuda'); pool = torch.empty(2 * B, H // 2, W // 2, C, device='cuda')
+    f = guard.empty(B, H, W, C); pool = guard.empty(2 * B, H // 2, W // 2, C)
     _lib.call('bdn_product_pool', BDN_F32, z_d.data_ptr(), bn_d.data_ptr(), f.data_ptr(), pool.data_ptr(), B, H, W, C, st())
     # upsampled map of a (B, H/2, W/2, Cu) source with BatchNorm+ReLU on load: second source of the decoder operand [f | U]
     src = to_nhwc('fp32', _rand((B, Cu, H // 2, W // 2), 83)); bnu = dev(bn_table(1, Cu, 84))
-    U = torch.empty(B, H, W, Cu, device='cuda')
+    U = guard.empty(B, H, W, Cu)
     _lib.call('bdn_upsample2x', BDN_F32, src.data_ptr(), IN_BNRELU, bnu.data_ptr(), U.data_ptr(), B, H // 2, W // 2, H, W, Cu, st())
     Ct = C + Cu
-    ref_cat = torch.empty(B, H, W, 2 * Ct, dtype=torch.bfloat16, device='cuda')
+    ref_cat = guard.empty(B, H, W, 2 * Ct, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', f.data_ptr(), C, U.data_ptr(), Cu, IN_PLAIN, None, B, ref_cat.data_ptr(), B, H, W, st())
-    ref_pool = torch.empty(2 * B, H // 2, W // 2, 2 * C, dtype=torch.bfloat16, device='cuda')
+    ref_pool = guard.empty(2 * B, H // 2, W // 2, 2 * C, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', pool.data_ptr(), C, None, 0, IN_PLAIN, None, B, ref_pool.data_ptr(), 2 * B, H // 2, W // 2, st())
-    got_cat = torch.zeros_like(ref_cat); got_pool = torch.zeros_like(ref_pool)
+    got_cat = guard.zeros_like(ref_cat); got_pool = guard.zeros_like(ref_pool)
     _lib.call('bdn_product_pool_split', z_d.data_ptr(), bn_d.data_ptr(), got_cat.data_ptr(), 2 * Ct, Ct, got_pool.data_ptr(), B, H, W, C, st())
     _lib.call('bdn_upsample2x_split', src.data_ptr(), IN_BNRELU, bnu.data_ptr(), got_cat.data_ptr(), 2 * Ct, C, Ct, B, H // 2, W // 2, H, W, Cu, st())
     torch.cuda.synchronize()
@@ -1244,19 +1282,19 @@ def test_split_outputs_of_the_bf16x3_producers_equal_split_pack():
     lib = _lib.load()
     N, ipg = 2 * B, B
     dA = to_nhwc('fp32', _rand((N, C, H, W), 85))
-    ws = torch.empty(lib.bdn_bn_bwd_workspace_bytes(BDN_F32, N, H, W, C, ipg) // 4, device='cuda')
-    sums = torch.empty(2, 2, C, device='cuda'); dg, db = torch.empty(C, device='cuda'), torch.empty(C, device='cuda')
-    dz = torch.empty(N, H, W, C, device='cuda')
+    ws = guard.empty(lib.bdn_bn_bwd_workspace_bytes(BDN_F32, N, H, W, C, ipg) // 4)
+    sums = guard.empty(2, 2, C); dg, db = guard.empty(C), guard.empty(C)
+    dz = guard.empty(N, H, W, C)
     _lib.call('bdn_bn_bwd', BDN_F32, dA.data_ptr(), C, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, C, ws.data_ptr(), sums.data_ptr(), dg.data_ptr(),
               db.data_ptr(), dz.data_ptr(), st())
-    ref_dz = torch.empty(N, H, W, 2 * C, dtype=torch.bfloat16, device='cuda')
+    ref_dz = guard.empty(N, H, W, 2 * C, dtype=torch.bfloat16)
     _lib.call('bdn_split_pack', dz.data_ptr(), C, None, 0, IN_PLAIN, None, ipg, ref_dz.data_ptr(), N, H, W, st())
     # the same partial rows the fused producers would leave: one row per group holding the finalized sums is not available here, so feed
     # the reduction's own block partials (raw_moment = 0: second moment already against xhat)
     G = N // ipg
     rows = (ws.numel() * 4 - lib.bdn_bn_bwd_scratch_bytes(G, C)) // (2 * C * 4) // G
-    sums2 = torch.empty_like(sums); got_dz = torch.zeros_like(ref_dz)
-    scratch = torch.empty(max(lib.bdn_bn_bwd_scratch_bytes(G, C) // 8, 1), dtype=torch.float64, device='cuda')
+    sums2 = guard.empty_like(sums); got_dz = guard.zeros_like(ref_dz)
+    scratch = guard.empty(max(lib.bdn_bn_bwd_scratch_bytes(G, C) // 8, 1), dtype=torch.float64)
     _lib.call('bdn_bn_bwd_apply_split', dA.data_ptr(), C, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, C, ws.data_ptr(), rows, 0,
               sums2.data_ptr(), dg.data_ptr(), db.data_ptr(), got_dz.data_ptr(), scratch.data_ptr(), st())
     torch.cuda.synchronize()

@@ -23,6 +23,8 @@ from fabric_amd import _lib
 from fabric_amd._lib import BDN_BF16, BDN_BF16X3, IN_BNRELU, IN_PLAIN
 from tests import launch_cases as lc
 from tests.gpu_util import assert_masked, bn_table, bnrelu_ref, dev, from_nhwc, pack_w, preact, rnd, st, to_nhwc
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 TAU = 2e-3
@@ -95,9 +97,9 @@ def _finalize_and_check(name, stats, nt, z64, G, ipg, H, W, Cout, fp32):
     gamma, beta = _rand((Cout,), 6).abs() + 0.5, _rand((Cout,), 7, 0.3)
     rm0, rv0 = _rand((Cout,), 8, 0.2), _rand((Cout,), 9).abs() + 0.5
     drm, drv, dg, db = dev(rm0), dev(rv0), dev(gamma), dev(beta)
-    nbt = torch.zeros(1, dtype=torch.int64, device='cuda')
-    bn = torch.full((G, 4, Cout), NAN, device='cuda')
-    fws = torch.empty(lib.bdn_bn_finalize_workspace_bytes(nt, G, Cout) // 8, dtype=torch.float64, device='cuda')
+    nbt = guard.zeros(1, dtype=torch.int64)
+    bn = guard.full((G, 4, Cout), NAN)
+    fws = guard.empty(lib.bdn_bn_finalize_workspace_bytes(nt, G, Cout) // 8, dtype=torch.float64)
     _lib.call('bdn_bn_finalize', stats.data_ptr(), nt, G, Cout, ipg * H * W, dg.data_ptr(), db.data_ptr(),
               1e-5, 0.1, drm.data_ptr(), drv.data_ptr(), nbt.data_ptr(), bn.data_ptr(), fws.data_ptr(), st())
     torch.cuda.synchronize()
@@ -121,6 +123,7 @@ def _finalize_and_check(name, stats, nt, z64, G, ipg, H, W, Cout, fp32):
 
 # ------------------------------------------------------------------ forward + statistics (+ finalize)
 @pytest.mark.parametrize('r', _rows('fwd'), ids=_rid)
+@guarded
 def test_forward_and_statistics(r):
     _assert_variant(r)
     N, H, W, C0, C1, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg, r.prec
@@ -136,9 +139,9 @@ def test_forward_and_statistics(r):
     ref = F.conv2d(a.double(), w.double(), b.double(), padding=1)
     wf, _ = pack_w(p, w, C0 + C1)
     d0, d1 = to_nhwc(p, x0), (to_nhwc(p, x1) if C1 else None)
-    out = torch.full((N, H, W, Cout), NAN, dtype=td, device='cuda')
+    out = guard.full((N, H, W, Cout), NAN, dtype=td)
     nt = _lib.load().bdn_conv3x3_num_mtiles(N, H, W, Cout, ipg)
-    stats = torch.full((nt, 2, Cout), NAN, device='cuda')
+    stats = guard.full((nt, 2, Cout), NAN)
     dbn, db = (dev(bn_in) if r.bnrelu else None), dev(b)
     _lib.call('bdn_conv3x3', dt, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1, IN_BNRELU if r.bnrelu else IN_PLAIN,
               dbn.data_ptr() if r.bnrelu else None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(), stats.data_ptr(), N, H, W, Cout, st())
@@ -162,13 +165,14 @@ def _dgrad_setup(r, seed=11):
 
 
 @pytest.mark.parametrize('r', _rows('dgrad'), ids=_rid)
+@guarded
 def test_data_gradient(r):
     _assert_variant(r)
     p = r.prec
     dt, td = lc.DTYPE[p], (torch.bfloat16 if p == 'bf16' else torch.float32)
     dz, w, wd = _dgrad_setup(r)
     ref = torch.nn.grad.conv2d_input((r.N, r.Cout, r.H, r.W), w.double(), dz.double(), padding=1)
-    out = torch.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td, device='cuda')
+    out = guard.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td)
     ddz = to_nhwc(p, dz)
     _lib.call('bdn_conv3x3', dt, ddz.data_ptr(), r.C0, None, 0, IN_PLAIN, None, r.ipg, wd.data_ptr(), None, out.data_ptr(), None,
               r.N, r.H, r.W, r.Cout, st())
@@ -191,6 +195,7 @@ def _check_bs(name, part, nt, refs, G, Cout):
 
 
 @pytest.mark.parametrize('r', _rows('dgrad_bs'), ids=_rid)
+@guarded
 def test_data_gradient_with_fused_statistics(r):
     _assert_variant(r)
     p = r.prec
@@ -201,12 +206,12 @@ def test_data_gradient_with_fused_statistics(r):
     zprev = rnd(p, _rand((r.N, r.Cout, r.H, r.W), 53))
     bnp = _bn_from(zprev, G, 54)
     ddz, zp_d, bnp_d = to_nhwc(p, dz), to_nhwc(p, zprev), dev(bnp)
-    plain = torch.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td, device='cuda')
+    plain = guard.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td)
     _lib.call('bdn_conv3x3', dt, ddz.data_ptr(), r.C0, None, 0, IN_PLAIN, None, r.ipg, wd.data_ptr(), None, plain.data_ptr(), None,
               r.N, r.H, r.W, r.Cout, st())
     nt = _lib.load().bdn_conv3x3_num_mtiles(r.N, r.H, r.W, r.Cout, r.ipg)
-    part = torch.full((nt, 2, r.Cout), NAN, device='cuda')
-    dA = torch.full_like(plain, NAN)
+    part = guard.full((nt, 2, r.Cout), NAN)
+    dA = guard.full_like(plain, NAN)
     _lib.call('bdn_conv3x3_dgrad_bs', dt, ddz.data_ptr(), r.C0, wd.data_ptr(), dA.data_ptr(), zp_d.data_ptr(), bnp_d.data_ptr(), r.ipg,
               part.data_ptr(), r.N, r.H, r.W, r.Cout, st())
     torch.cuda.synchronize()
@@ -216,6 +221,7 @@ def test_data_gradient_with_fused_statistics(r):
 
 
 @pytest.mark.parametrize('r', _rows('dgrad_bb'), ids=_rid)
+@guarded
 def test_data_gradient_with_bn_backward_on_load(r):
     """bdn_conv3x3_dgrad_bb against an independent float64 computation: the BatchNorm backward dz = scale (g - s0/M - xhat s1/M) with the
     sums of g in float64, then conv2d_input of bf16(dz); and against the two-kernel path (bdn_bn_bwd + the plain data gradient)."""
@@ -242,13 +248,13 @@ def test_data_gradient_with_bn_backward_on_load(r):
         dz64[sl] = scale * (gg - s0[None, :, None, None] / M - xhat * s1[None, :, None, None] / M)
     ref = torch.nn.grad.conv2d_input((N, Cout, H, W), w.double(), dz64.to(torch.bfloat16).double(), padding=1)
     # two-kernel path: its sums feed the fused kernel
-    ws = torch.empty(lib.bdn_bn_bwd_workspace_bytes(BDN_BF16, N, H, W, C0, ipg) // 4, device='cuda')
-    sums = torch.full((G, 2, C0), NAN, device='cuda')
-    dg, db = torch.empty(C0, device='cuda'), torch.empty(C0, device='cuda')
-    dz_two = torch.full((N, H, W, C0), NAN, dtype=torch.bfloat16, device='cuda')
+    ws = guard.empty(lib.bdn_bn_bwd_workspace_bytes(BDN_BF16, N, H, W, C0, ipg) // 4)
+    sums = guard.full((G, 2, C0), NAN)
+    dg, db = guard.empty(C0), guard.empty(C0)
+    dz_two = guard.full((N, H, W, C0), NAN, dtype=torch.bfloat16)
     _lib.call('bdn_bn_bwd', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), ipg, N, H, W, C0,
               ws.data_ptr(), sums.data_ptr(), dg.data_ptr(), db.data_ptr(), dz_two.data_ptr(), st())
-    out_two = torch.full((N, H, W, Cout), NAN, dtype=torch.bfloat16, device='cuda')
+    out_two = guard.full((N, H, W, Cout), NAN, dtype=torch.bfloat16)
     _lib.call('bdn_conv3x3', BDN_BF16, dz_two.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None, out_two.data_ptr(), None,
               N, H, W, Cout, st())
     # fused: without and with the producing layer's statistics
@@ -256,12 +262,12 @@ def test_data_gradient_with_bn_backward_on_load(r):
     bnp = _bn_from(zprev, G, 66)
     zp_d, bnp_d = to_nhwc('bf16', zprev), dev(bnp)
     nt = lib.bdn_conv3x3_num_mtiles(N, H, W, Cout, ipg)
-    part = torch.full((nt, 2, Cout), NAN, device='cuda')
-    out = torch.full((N, H, W, Cout), NAN, dtype=torch.bfloat16, device='cuda')
-    dz = torch.full((N, H, W, C0), NAN, dtype=torch.bfloat16, device='cuda')
+    part = guard.full((nt, 2, Cout), NAN)
+    out = guard.full((N, H, W, Cout), NAN, dtype=torch.bfloat16)
+    dz = guard.full((N, H, W, C0), NAN, dtype=torch.bfloat16)
     _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
               out.data_ptr(), None, None, None, dz.data_ptr(), N, H, W, Cout, st())
-    outm = torch.full_like(out, NAN)
+    outm = guard.full_like(out, NAN)
     _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
               outm.data_ptr(), zp_d.data_ptr(), bnp_d.data_ptr(), part.data_ptr(), None, N, H, W, Cout, st())
     torch.cuda.synchronize()
@@ -280,7 +286,7 @@ def test_data_gradient_with_bn_backward_on_load(r):
 # ------------------------------------------------------------------ bf16x3 / bf16x2: split operand, float32 operand
 def _split(x_nchw, ipg, mode=IN_PLAIN, bn=None):
     N, C, H, W = x_nchw.shape
-    sp = torch.full((N, H, W, 2 * C), NAN, dtype=torch.bfloat16, device='cuda')
+    sp = guard.full((N, H, W, 2 * C), NAN, dtype=torch.bfloat16)
     xd, bd = to_nhwc('fp32', x_nchw), (dev(bn) if bn is not None else None)
     _lib.call('bdn_split_pack', xd.data_ptr(), C, None, 0, mode, bd.data_ptr() if bn is not None else None, ipg, sp.data_ptr(), N, H, W, st())
     torch.cuda.synchronize()
@@ -289,7 +295,7 @@ def _split(x_nchw, ipg, mode=IN_PLAIN, bn=None):
 
 def _x3_weights(w):
     Cout, Cin = w.shape[:2]
-    wf = torch.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16, device='cuda')
+    wf = guard.empty(Cout, 9, 3 * Cin, dtype=torch.bfloat16)
     wd = dev(w)
     _lib.call('bdn_pack_weights', BDN_BF16X3, wd.data_ptr(), wf.data_ptr(), None, Cout, Cin, Cin, st())
     torch.cuda.synchronize()
@@ -297,6 +303,7 @@ def _x3_weights(w):
 
 
 @pytest.mark.parametrize('r', _rows('x3', 'x3src'), ids=_rid)
+@guarded
 def test_split_product_convolution(r):
     """bf16x3 (three terms: the float32 product to ~2^-16) and bf16x2 (a_hi w_hi + a_lo w_hi = a times the filter rounded to bf16) on the
     split operand (bdn_conv3x3) and on the float32 operand (bdn_conv3x3_x3src, BatchNorm+ReLU on load), with statistics."""
@@ -313,8 +320,8 @@ def test_split_product_convolution(r):
     ref = F.conv2d(a.double(), wr.double(), b.double(), padding=1)
     wf = _x3_weights(w)
     nt = lib.bdn_conv3x3_num_mtiles_ex(dt, N, H, W, C0, Cout, ipg)
-    out = torch.full((N, H, W, Cout), NAN, device='cuda')
-    stats = torch.full((nt, 2, Cout), NAN, device='cuda') if r.stats else None
+    out = guard.full((N, H, W, Cout), NAN)
+    stats = guard.full((nt, 2, Cout), NAN) if r.stats else None
     sp_out = None
     db = dev(b)
     if r.op == 'x3':
@@ -322,7 +329,7 @@ def test_split_product_convolution(r):
         _lib.call('bdn_conv3x3', dt, xs.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
                   stats.data_ptr(), N, H, W, Cout, st())
     else:
-        sp_out = torch.full((N, H, W, 2 * C0), NAN, dtype=torch.bfloat16, device='cuda') if r.stats else None
+        sp_out = guard.full((N, H, W, 2 * C0), NAN, dtype=torch.bfloat16) if r.stats else None
         xd, dbn = to_nhwc('fp32', x), (dev(bn) if r.bnrelu else None)
         _lib.call('bdn_conv3x3_x3src', dt, xd.data_ptr(), C0, IN_BNRELU if r.bnrelu else IN_PLAIN,
                   dbn.data_ptr() if r.bnrelu else None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
@@ -357,6 +364,7 @@ def _pool64(t):
 
 
 @pytest.mark.parametrize('r', _rows('eval', 'eval_pair', 'eval_cls'), ids=_rid)
+@guarded
 def test_eval_stage(r):
     """Eval-mode launches (conv -> folded BatchNorm -> ReLU in the epilogue): the stored activation / date product / pooled maps / logits."""
     _assert_variant(r)
@@ -367,8 +375,8 @@ def test_eval_stage(r):
     d0, d1 = to_nhwc(p, x0), (to_nhwc(p, x1) if r.C1 else None)
     name = _rid(r)
     if r.op == 'eval':
-        out = torch.full((N, H, W, Cout), NAN, dtype=td, device='cuda')
-        pool = torch.full((N, H // 2, W // 2, Cout), NAN, dtype=td, device='cuda')
+        out = guard.full((N, H, W, Cout), NAN, dtype=td)
+        pool = guard.full((N, H // 2, W // 2, Cout), NAN, dtype=td)
         _lib.call('bdn_conv3x3_eval', dt, d0.data_ptr(), r.C0, d1.data_ptr() if r.C1 else None, r.C1, wf.data_ptr(),
                   dsc.data_ptr(), dsh.data_ptr(), out.data_ptr(), None, pool.data_ptr(), N, H, W, Cout, st())
         torch.cuda.synchronize()
@@ -376,8 +384,8 @@ def test_eval_stage(r):
         check(f'{name} pooled', from_nhwc(pool), _pool64(act), p)
     elif r.op == 'eval_pair':
         B = N
-        f = torch.full((B, H, W, Cout), NAN, dtype=td, device='cuda')
-        pool = torch.full((2 * B, H // 2, W // 2, Cout), NAN, dtype=td, device='cuda')
+        f = guard.full((B, H, W, Cout), NAN, dtype=td)
+        pool = guard.full((2 * B, H // 2, W // 2, Cout), NAN, dtype=td)
         _lib.call('bdn_conv3x3_eval_pair', dt, d0.data_ptr(), r.C0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), f.data_ptr(),
                   pool.data_ptr(), B, H, W, Cout, st())
         torch.cuda.synchronize()
@@ -388,9 +396,9 @@ def test_eval_stage(r):
         ncls = 2
         cw, cb = _rand((ncls, Cout), 409, 0.2), _rand((ncls,), 410, 0.1)
         dcw, dcb = dev(cw), dev(cb)
-        a_out = torch.full((N, H, W, Cout), NAN, dtype=td, device='cuda')
-        logits = torch.full((N, ncls, H, W), NAN, device='cuda')
-        mask = torch.full((N, H, W), 255, dtype=torch.uint8, device='cuda')
+        a_out = guard.full((N, H, W, Cout), NAN, dtype=td)
+        logits = guard.full((N, ncls, H, W), NAN)
+        mask = guard.full((N, H, W), 255, dtype=torch.uint8)
         _lib.call('bdn_conv3x3_eval_cls', dt, d0.data_ptr(), r.C0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), a_out.data_ptr(),
                   dcw.data_ptr(), dcb.data_ptr(), ncls, logits.data_ptr(), mask.data_ptr(), None, 0, 0, N, H, W, Cout, st())
         torch.cuda.synchronize()
@@ -403,9 +411,15 @@ def test_eval_stage(r):
 
 # ------------------------------------------------------------------ weight gradient at the production plan
 @pytest.mark.parametrize('r', _rows('wgrad'), ids=_rid)
+@guarded
 def test_weight_gradient(r):
     _assert_variant(r)
     assert lc.reduce_lanes(r) == r.lanes
+    run_weight_gradient(r)
+
+
+def run_weight_gradient(r, flags=3):
+    """The body of test_weight_gradient at plan flags `flags` (tests/test_gpu_bounds.py runs it at other plans and kernels)."""
     lib = _lib.load()
     N, H, W, C0, C1, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg, r.prec
     dt, G = lc.DTYPE[p], N // ipg
@@ -419,26 +433,27 @@ def test_weight_gradient(r):
     a = torch.cat([a0, x1], 1) if C1 else a0
     dzr = dz.to(torch.bfloat16).float() if p == 'bf16x2' else dz          # two terms: dz_hi x [a_hi | a_lo]
     ref = torch.nn.grad.conv2d_weight(a.double(), (Cout, C0 + C1, 3, 3), dzr.double(), padding=1)
-    nb = lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, C1, ipg, IN_BNRELU if r.bnrelu else IN_PLAIN, 3)
-    assert nb <= lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0 + C1, ipg)
-    part = torch.empty(nb // 4, device='cuda')
-    dw = torch.full((Cout, C0 + C1, 3, 3), NAN, device='cuda')
+    nb = lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, C1, ipg, IN_BNRELU if r.bnrelu else IN_PLAIN, flags)
+    assert flags != 3 or nb <= lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0 + C1, ipg)
+    part = guard.empty(nb // 4)
+    dw = guard.full((Cout, C0 + C1, 3, 3), NAN)
     if x3:
         assert not r.bnrelu and not C1
         sdz, sx = _split(dz, ipg), _split(x0, ipg)
         _lib.call('bdn_conv3x3_wgrad_ex', dt, sdz.data_ptr(), Cout, sx.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg,
-                  part.data_ptr(), dw.data_ptr(), C0, N, H, W, 3, st())
+                  part.data_ptr(), dw.data_ptr(), C0, N, H, W, flags, st())
     else:
         ddz, d0, d1 = to_nhwc(p, dz), to_nhwc(p, x0), (to_nhwc(p, x1) if C1 else None)
         dbn = dev(bn_in) if r.bnrelu else None
         _lib.call('bdn_conv3x3_wgrad_ex', dt, ddz.data_ptr(), Cout, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1,
                   IN_BNRELU if r.bnrelu else IN_PLAIN, dbn.data_ptr() if r.bnrelu else None, ipg, part.data_ptr(), dw.data_ptr(), C0 + C1,
-                  N, H, W, 3, st())
+                  N, H, W, flags, st())
     torch.cuda.synchronize()
     check(f'{_rid(r)} dW', dw, ref, 'x3' if x3 else 'fp32')
 
 
 @pytest.mark.parametrize('r', _rows('wgrad_bnbwd'), ids=_rid)
+@guarded
 def test_first_layer_weight_gradient(r):
     """bdn_bn_bwd_finalize + bdn_conv3x3_wgrad_bnbwd (256-block plan, 16 split lanes) against float64: dz = scale (g - s0/M - xhat s1/M)
     from the float64 sums (bf16: rounded to bf16 like the kernel's staging; bf16x2: dz rounded, x in full), then conv2d_weight."""
@@ -474,16 +489,17 @@ def test_first_layer_weight_gradient(r):
         dz64[sl] = scale * (gm[sl] - s0[None, :, None, None] / M - xhat * s1[None, :, None, None] / M)
     dzr = dz64 if p == 'bf16x3' else dz64.to(torch.bfloat16).double()
     ref = torch.nn.grad.conv2d_weight(x[:, :Creal].double(), (Cout, Creal, 3, 3), dzr, padding=1)
-    sums = torch.full((G, 2, Cout), NAN, device='cuda')
-    dg, db = torch.empty(Cout, device='cuda'), torch.empty(Cout, device='cuda')
+    sums = guard.full((G, 2, Cout), NAN)
+    dg, db = guard.empty(Cout), guard.empty(Cout)
     bn_d, part_d = dev(bn), dev(part)
     _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), G, Cout, part_d.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(),
               None, st())
     xin = _split(x, ipg) if x3 else to_nhwc('bf16', x)
     wsz = max(lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0, ipg), lib.bdn_wgrad_workspace_bytes_ex(lc.DTYPE[p], N, H, W, Cout, C0, 0, ipg, IN_PLAIN, 3))
-    wpart = torch.empty(wsz // 4, device='cuda')
-    dw = torch.full((Cout, Creal, 3, 3), NAN, device='cuda')
+    wpart = guard.empty(wsz // 4)
+    dw = guard.full((Cout, Creal, 3, 3), NAN)
     dA_d, z_d = to_nhwc(sp, dA_full), to_nhwc(sp, z)
+    dA_d[..., Cout:] = NAN                               # the foreign channels of the wider dA: a read of them poisons the result
     _lib.call('bdn_conv3x3_wgrad_bnbwd', lc.DTYPE[p], dA_d.data_ptr(), ldA, z_d.data_ptr(), bn_d.data_ptr(),
               sums.data_ptr(), ipg, Cout, xin.data_ptr(), C0, wpart.data_ptr(), dw.data_ptr(), Creal, N, H, W, st())
     torch.cuda.synchronize()
@@ -492,6 +508,7 @@ def test_first_layer_weight_gradient(r):
 
 # ------------------------------------------------------------------ statistics reductions on synthetic partials
 @pytest.mark.parametrize('case', lc.STATS_CASES, ids=lambda c: f'rows{c[0]}-G{c[1]}')
+@guarded
 def test_bn_finalize_reduction(case):
     """bdn_bn_finalize: one launch up to 512 rows per group, reduce_rows_kernel + bn_finalize_kernel above (RS capped at 64)."""
     rpg, G = case
@@ -505,9 +522,9 @@ def test_bn_finalize_reduction(case):
     gamma, beta = _rand((C,), 6).abs() + 0.5, _rand((C,), 7, 0.3)
     rm0, rv0 = _rand((C,), 8, 0.2), _rand((C,), 9).abs() + 0.5
     drm, drv, dgam, dbet, part_d = dev(rm0), dev(rv0), dev(gamma), dev(beta), dev(part)
-    nbt = torch.full((1,), 5, dtype=torch.int64, device='cuda')
-    bn = torch.full((G, 4, C), NAN, device='cuda')
-    fws = torch.full((lib.bdn_bn_finalize_workspace_bytes(G * rpg, G, C) // 8,), NAN, dtype=torch.float64, device='cuda')
+    nbt = guard.full((1,), 5, dtype=torch.int64)
+    bn = guard.full((G, 4, C), NAN)
+    fws = guard.full((lib.bdn_bn_finalize_workspace_bytes(G * rpg, G, C) // 8,), NAN, dtype=torch.float64)
     _lib.call('bdn_bn_finalize', part_d.data_ptr(), G * rpg, G, C, count, dgam.data_ptr(), dbet.data_ptr(), 1e-5, 0.1,
               drm.data_ptr(), drv.data_ptr(), nbt.data_ptr(), bn.data_ptr(), fws.data_ptr(), st())
     torch.cuda.synchronize()
@@ -529,6 +546,7 @@ def test_bn_finalize_reduction(case):
 
 
 @pytest.mark.parametrize('case', lc.STATS_CASES, ids=lambda c: f'rows{c[0]}-G{c[1]}')
+@guarded
 def test_bn_bwd_finalize_reduction(case):
     """bdn_bn_bwd_finalize with its scratch (the two-stage row plan above 512 rows per group): sums of g and g xhat (from the raw moment
     sum g z), dgamma and dbeta accumulated over the groups, against float64."""
@@ -538,9 +556,9 @@ def test_bn_bwd_finalize_reduction(case):
     bn = bn_table(G, C, rpg)
     r = np.random.default_rng(rpg * 3 + G)
     part = torch.from_numpy(r.standard_normal((G * rpg, 2, C)).astype(np.float32) * 4)
-    sums = torch.full((G, 2, C), NAN, device='cuda')
-    dg, db = torch.full((C,), NAN, device='cuda'), torch.full((C,), NAN, device='cuda')
-    scratch = torch.full((lib.bdn_bn_bwd_scratch_bytes(G, C) // 8,), NAN, dtype=torch.float64, device='cuda')
+    sums = guard.full((G, 2, C), NAN)
+    dg, db = guard.full((C,), NAN), guard.full((C,), NAN)
+    scratch = guard.full((lib.bdn_bn_bwd_scratch_bytes(G, C) // 8,), NAN, dtype=torch.float64)
     bn_d, part_d = dev(bn), dev(part)
     _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), G, C, part_d.data_ptr(), rpg, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(),
               scratch.data_ptr(), st())

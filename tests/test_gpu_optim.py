@@ -15,6 +15,8 @@ from fabric_amd.train_step import TrainStep
 from fabric_amd.utils.metrics import TverskyLoss
 from oracle import filler
 from tests import optim_ref as R
+from tests import guard
+from tests.guard import guarded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -59,22 +61,23 @@ def _run_kernel(case, gs, p, grads, state):
 
 @pytest.mark.parametrize('n', _SIZES)
 @pytest.mark.parametrize('name,case,gs', _KERNEL_CASES, ids=[c[0] for c in _KERNEL_CASES])
+@guarded
 def test_update_kernel_matches_float64_restatement(name, case, gs, n):
     """Three steps (the first-step momentum branch and two after it), each checked from the kernel's own float32 inputs: every element
     of the parameters and the state within R.ULPS float32 epsilons of the magnitude R computes (at least max(|p|, |dp|)).  A repeat of the
     whole run from the same inputs is bit-identical."""
     gen = torch.Generator(device='cpu').manual_seed(n * 31 + len(name))
-    p0 = torch.randn(n, generator=gen).to(dev)
+    p0 = guard.guard(torch.randn(n, generator=gen), dev)
     p0[::7] *= 1e-3                                           # parameters much smaller than their update
-    grads = [(torch.randn(n, generator=gen) * (0.3 + it)).to(dev) for it in range(3)]
+    grads = [guard.guard(torch.randn(n, generator=gen) * (0.3 + it), dev) for it in range(3)]
     grads[1][::5] = 0.0                                       # zero gradients: Adam's m / (sqrt(v) + eps) with a decayed m
     runs = []
     for _ in range(2):
-        p = p0.clone()
+        p = guard.clone(p0)
         if case['kind'] == 'sgd':
-            state = {'buf': torch.full((n,), float('nan'), device=dev)} if case.get('momentum', 0.0) else {}   # first step must not read it
+            state = {'buf': guard.full((n,), float('nan'), device=dev)} if case.get('momentum', 0.0) else {}   # first step must not read it
         else:
-            state = {'m': torch.zeros(n, device=dev), 'v': torch.zeros(n, device=dev)}
+            state = {'m': guard.zeros(n, device=dev), 'v': guard.zeros(n, device=dev)}
         runs.append(_run_kernel(case, gs, p, grads, state))
     torch.cuda.synchronize()
     for it, ((p_in, s_in), p_out, s_out) in enumerate(runs[0]):

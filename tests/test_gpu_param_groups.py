@@ -20,6 +20,8 @@ from fabric_amd.utils.metrics import TverskyLoss
 from oracle import filler
 from tests import optim_ref as R
 from tests.param_groups_ref import grouped_reference
+from tests import guard
+from tests.guard import guarded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -48,7 +50,7 @@ def _table(n, n_groups, frozen_every=0, seed=0):
 
 
 def _dev_table(ends, ids):
-    return (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev), torch.tensor(ids, dtype=torch.int32).to(dev))
+    return (guard.guard(torch.tensor(ends, dtype=torch.int64).to(torch.int32), dev), guard.guard(torch.tensor(ids, dtype=torch.int32), dev))
 
 
 def _call_grouped(kind, rule, p, g, state, tab, hyper, gs, step):
@@ -81,15 +83,16 @@ _HYPER = [(0.01, 1e-2), (0.001, 0.0), (0.02, 1e-3), (0.005, 5e-2), (0.01, 0.0), 
 
 def _state(kind, rule, n, fill=0.0):
     if kind in ('adam', 'adamw'):
-        return {'m': torch.full((n,), fill, device=dev), 'v': torch.full((n,), abs(fill), device=dev)}
+        return {'m': guard.full((n,), fill, device=dev), 'v': guard.full((n,), abs(fill), device=dev)}
     if rule.get('momentum', 0.0):
-        return {'buf': torch.full((n,), float('nan'), device=dev)}           # the first step must not read it
+        return {'buf': guard.full((n,), float('nan'), device=dev)}           # the first step must not read it
     return {}
 
 
 @pytest.mark.parametrize('n', [4, 1028, 4_000_004])
 @pytest.mark.parametrize('n_groups', [1, 2, 8])
 @pytest.mark.parametrize('name,kind,rule,gs', _KERNEL_CASES, ids=[c[0] for c in _KERNEL_CASES])
+@guarded
 def test_grouped_kernel_matches_float64_restatement(name, kind, rule, gs, n_groups, n):
     """Three steps on sizes that are no multiple of a block's 1024 vectors, 1 / 2 / 8 groups with their own lr and weight decay, some
     segments frozen: every element within R.ULPS of the restatement (frozen ones exactly as they were), from the kernel's own inputs."""
@@ -99,9 +102,9 @@ def test_grouped_kernel_matches_float64_restatement(name, kind, rule, gs, n_grou
     ends, ids, segs = _table(n, n_groups, frozen_every=4, seed=n + n_groups)
     tab = _dev_table(ends, ids)
     gen = torch.Generator(device='cpu').manual_seed(n * 31 + len(name))
-    p = torch.randn(n, generator=gen).to(dev)
+    p = guard.guard(torch.randn(n, generator=gen), dev)
     p[::7] *= 1e-3
-    grads = [(torch.randn(n, generator=gen) * (0.3 + it)).to(dev) for it in range(3)]
+    grads = [guard.guard(torch.randn(n, generator=gen) * (0.3 + it), dev) for it in range(3)]
     grads[1][::5] = 0.0
     state = _state(kind, rule, n)
     rkind = 'sgd' if kind == 'sgd_plain' else kind
@@ -123,9 +126,10 @@ def test_grouped_kernel_matches_float64_restatement(name, kind, rule, gs, n_grou
         assert bool((p != p_in).any()), 'the step changed nothing'
 
 
+@guarded
 def test_nine_groups_are_refused():
     n = 64
-    p, g, m, v = (torch.zeros(n, device=dev) for _ in range(4))
+    p, g, m, v = (guard.zeros(n, device=dev) for _ in range(4))
     tab = _dev_table([16], [0])
     nine = [(0.01, 0.0)] * 9
     for kind, rule in (('sgd_plain', {}), ('sgd', dict(momentum=0.9)), ('adam', {})):
@@ -134,17 +138,18 @@ def test_nine_groups_are_refused():
 
 
 @pytest.mark.parametrize('n', [1028, 13_401_156])
+@guarded
 def test_one_group_gives_the_bits_of_the_ungrouped_kernels(n):
     """One group over the whole buffer: the same device functions on the same inputs, so equality, not a tolerance."""
     st = _lib.stream_ptr()
     gen = torch.Generator(device='cpu').manual_seed(n)
-    p0 = torch.randn(n, generator=gen).to(dev)
-    grads = [(torch.randn(n, generator=gen) * (0.3 + it)).to(dev) for it in range(3)]
+    p0 = guard.guard(torch.randn(n, generator=gen), dev)
+    grads = [guard.guard(torch.randn(n, generator=gen) * (0.3 + it), dev) for it in range(3)]
     tab = _dev_table([n // 4], [0])
     lr, wd, gs = 0.013, 1e-2, 0.5
 
     def run(grouped, kind, rule):
-        p = p0.clone()
+        p = guard.clone(p0)
         state = _state(kind, rule, n)
         for it, g in enumerate(grads):
             if grouped:
@@ -169,6 +174,7 @@ def test_one_group_gives_the_bits_of_the_ungrouped_kernels(n):
 
 
 @pytest.mark.parametrize('kind,rule', [('sgd_plain', {}), ('sgd', dict(momentum=0.9)), ('adamw', {})], ids=['sgd', 'sgd_momentum', 'adamw'])
+@guarded
 def test_frozen_segments_are_neither_read_nor_written(kind, rule):
     """Frozen segments: parameters and state bit-identical after three steps, with their gradients NaN (a read would spread it) and,
     for the state, NaN placeholders of their own."""
@@ -181,7 +187,7 @@ def test_frozen_segments_are_neither_read_nor_written(kind, rule):
     mask = mask.to(dev)
     assert bool(mask.any()) and not bool(mask.all())
     gen = torch.Generator(device='cpu').manual_seed(1)
-    p = torch.randn(n, generator=gen).to(dev)
+    p = guard.guard(torch.randn(n, generator=gen), dev)
     state = _state(kind, rule, n)
     for t in state.values():
         t[~mask] = 0.0
@@ -189,7 +195,7 @@ def test_frozen_segments_are_neither_read_nor_written(kind, rule):
     p0, s0 = p.clone(), {k: v.clone() for k, v in state.items()}
     hyper = [(0.01, 0.0), (0.02, 0.0), (0.03, 0.0)] if kind == 'sgd_plain' else _HYPER[:3]
     for it in range(3):
-        g = torch.randn(n, generator=gen).to(dev)
+        g = guard.guard(torch.randn(n, generator=gen), dev)
         g[mask] = float('nan')
         _call_grouped(kind, rule, p, g, state, tab, hyper, 1.0, it + 1)
     torch.cuda.synchronize()

@@ -15,6 +15,8 @@ from fabric_amd.utils import inference as inf
 from oracle import bidate_oracle as O
 from oracle import filler
 from gpu_util import DT, st, rnd
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -29,6 +31,7 @@ def _scene(c, h, w, seed):
 
 @pytest.mark.parametrize('prec', ['fp32', 'bf16'])
 @pytest.mark.parametrize('shape', [(13, 150, 141, 32), (3, 96, 64, 32), (5, 40, 40, 40), (13, 33, 70, 16)])
+@guarded
 def test_gather_tiles_matches_oracle_tiler(prec, shape):
     c, h, w, p = shape
     d1, d2 = _scene(c, h, w, 1)
@@ -38,8 +41,8 @@ def test_gather_tiles_matches_oracle_tiler(prec, shape):
     assert (hs, ws, lc, lr) == (hs2, ws2, lc2, lr2) and len(o) == ref1.shape[0]
     n, cp = len(o), 16
     dt, td = DT[prec]
-    out = torch.full((2 * n, p, p, cp), 7.0, dtype=td, device='cuda')
-    g1, g2, go = torch.from_numpy(d1).cuda(), torch.from_numpy(d2).cuda(), torch.from_numpy(o).cuda()
+    out = guard.full((2 * n, p, p, cp), 7.0, dtype=td)
+    g1, g2, go = guard.guard(torch.from_numpy(d1)), guard.guard(torch.from_numpy(d2)), guard.guard(torch.from_numpy(o))
     call('bdn_gather_tiles', dt, ptr(g1), ptr(g2), ptr(go), ptr(out), n, c, h, w, p, cp, st())
     got = out.float().cpu()
     ref = rnd(prec, torch.from_numpy(np.concatenate([ref1, ref2])))
@@ -48,6 +51,7 @@ def test_gather_tiles_matches_oracle_tiler(prec, shape):
 
 
 @pytest.mark.parametrize('shape', [(2, 150, 141, 32), (2, 96, 64, 32), (5, 64, 100, 64), (2, 40, 40, 40)])
+@guarded
 def test_argmax_stitch_matches_oracle_stitcher(shape):
     ncls, h, w, p = shape
     o, hs, ws, lc, lr = inf.tile_origins(h, w, p)
@@ -58,8 +62,8 @@ def test_argmax_stitch_matches_oracle_stitcher(shape):
     lt = torch.from_numpy(logits)
     pred = torch.max(lt, 1)[1].numpy()
     ref = O.stitch_scene(pred.astype(np.float64), hs, ws, lc, lr, h, w, p).astype(np.uint8)
-    mask = torch.full((h, w), 255, dtype=torch.uint8, device='cuda')
-    lg, go = lt.cuda(), torch.from_numpy(o).cuda()
+    mask = guard.full((h, w), 255, dtype=torch.uint8)
+    lg, go = guard.guard(lt), guard.guard(torch.from_numpy(o))
     call('bdn_argmax_stitch', ptr(lg), ptr(go), ptr(mask), n, ncls, p, h, w, st())
     if h % p and w % p:
         assert np.array_equal(mask.cpu().numpy(), ref)
@@ -73,7 +77,7 @@ def test_argmax_stitch_matches_oracle_stitcher(shape):
                 cover[y:y + p, x:x + p] += 1
         ok = cover == 0
         assert np.array_equal(mask.cpu().numpy()[ok], ref[ok])
-    dense = torch.empty(n, p, p, dtype=torch.uint8, device='cuda')
+    dense = guard.empty(n, p, p, dtype=torch.uint8)
     call('bdn_argmax', ptr(lg), ptr(dense), n, ncls, p, p, st())
     assert np.array_equal(dense.cpu().numpy(), pred.astype(np.uint8))
 
@@ -213,13 +217,14 @@ def test_predict_scene_at_the_full_baseline_size():
     parts = [inf.predict_scene(model, d1, d2, patch_size=p, batch_size=64, shard=(r, 2), merge=False) for r in range(2)]
     assert torch.equal(torch.maximum(parts[0], parts[1]), a)
     del parts, b
-    full = torch.full((h, w), 255, dtype=torch.uint8, device='cuda')
-    from fabric_amd._lib import call, ptr, stream_ptr
-    origins = torch.from_numpy(o).cuda()
-    logits = torch.zeros(64, 2, p, p, device='cuda')
-    for i in range(0, len(o), 64):
-        oo = origins[i:i + 64]
-        call('bdn_argmax_stitch', ptr(logits), ptr(oo), ptr(full), oo.shape[0], 2, p, h, w, stream_ptr())
+    from fabric_amd._lib import ptr, stream_ptr
+    with guard.checked(name='stitch loop'):                       # the scans above allocate for themselves; the direct calls run on guarded buffers
+        full = guard.full((h, w), 255, dtype=torch.uint8)
+        origins = guard.guard(torch.from_numpy(o))
+        logits = guard.zeros(64, 2, p, p)
+        for i in range(0, len(o), 64):
+            oo = origins[i:i + 64]
+            _lib.call('bdn_argmax_stitch', ptr(logits), ptr(oo), ptr(full), oo.shape[0], 2, p, h, w, stream_ptr())
     assert int(full.max()) == 0                                   # every pixel of the scene is owned by some tile
 
 

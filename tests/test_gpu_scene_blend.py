@@ -14,6 +14,8 @@ from fabric_amd.utils import inference as inf
 from fabric_amd.utils.dataloaders import _apply_symmetry
 from oracle import filler
 from gpu_util import DT, st, rnd
+from tests import guard
+from tests.guard import guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +53,7 @@ def _restate(logits, table, win, h, w):
 # ---------------------------------------------------------------- 1. symmetric gather
 @pytest.mark.parametrize('prec', ['fp32', 'bf16'])
 @pytest.mark.parametrize('shape', [(3, 150, 141, 40), (5, 96, 64, 32), (13, 70, 80, 64)])
+@guarded
 def test_gather_tiles_sym_matches_host(prec, shape):
     c, h, w, p = shape
     d1, d2 = _scene(c, h, w, 1)
@@ -61,9 +64,9 @@ def test_gather_tiles_sym_matches_host(prec, shape):
     table = np.concatenate([o, (np.arange(n) % 8)[:, None]], 1).astype(np.int32)
     cp = 16
     dt, td = DT[prec]
-    g1, g2 = torch.from_numpy(d1).cuda(), torch.from_numpy(d2).cuda()
-    out = torch.full((2 * n, p, p, cp), 7.0, dtype=td, device='cuda')
-    call('bdn_gather_tiles_sym', dt, ptr(g1), ptr(g2), ptr(torch.from_numpy(table).cuda()), ptr(out), n, c, h, w, p, cp, st())
+    g1, g2 = guard.guard(torch.from_numpy(d1)), guard.guard(torch.from_numpy(d2))
+    out = guard.full((2 * n, p, p, cp), 7.0, dtype=td)
+    call('bdn_gather_tiles_sym', dt, ptr(g1), ptr(g2), ptr(guard.guard(torch.from_numpy(table))), ptr(out), n, c, h, w, p, cp, st())
     got = out.float().cpu()
     ref = np.stack([np.ascontiguousarray(_sym(d[:, y:y + p, x:x + p], s).transpose(1, 2, 0))
                     for d in (d1, d2) for y, x, s in table])
@@ -72,10 +75,10 @@ def test_gather_tiles_sym_matches_host(prec, shape):
     # symmetry 0 is bdn_gather_tiles
     t0 = table.copy()
     t0[:, 2] = 0
-    a = torch.full_like(out, 3.0)
-    b = torch.full_like(out, 5.0)
-    call('bdn_gather_tiles_sym', dt, ptr(g1), ptr(g2), ptr(torch.from_numpy(t0).cuda()), ptr(a), n, c, h, w, p, cp, st())
-    call('bdn_gather_tiles', dt, ptr(g1), ptr(g2), ptr(torch.from_numpy(np.ascontiguousarray(o)).cuda()), ptr(b), n, c, h, w, p, cp, st())
+    a = guard.full_like(out, 3.0)
+    b = guard.full_like(out, 5.0)
+    call('bdn_gather_tiles_sym', dt, ptr(g1), ptr(g2), ptr(guard.guard(torch.from_numpy(t0))), ptr(a), n, c, h, w, p, cp, st())
+    call('bdn_gather_tiles', dt, ptr(g1), ptr(g2), ptr(guard.guard(torch.from_numpy(np.ascontiguousarray(o)))), ptr(b), n, c, h, w, p, cp, st())
     assert torch.equal(a, b)
 
 
@@ -83,10 +86,10 @@ def test_gather_tiles_sym_matches_host(prec, shape):
 def _blend_kernels(logits, table, win, h, w, p, stride, S, batch):
     """fold + stitch per batch of `batch` images (in order, one stream), then finalize: what predict_scene_blended launches."""
     n, ncls = logits.shape[0], logits.shape[1]
-    proba = torch.zeros(ncls, h, w, device='cuda')
-    wsum = torch.zeros(h, w, device='cuda')
-    mask = torch.empty(h, w, dtype=torch.uint8, device='cuda')
-    fold = torch.empty(min(batch, n), ncls, p, p, device='cuda')
+    proba = guard.zeros(ncls, h, w)
+    wsum = guard.zeros(h, w)
+    mask = guard.empty(h, w, dtype=torch.uint8)
+    fold = guard.empty(min(batch, n), ncls, p, p)
     for i in range(0, n, batch):
         nb = min(n, i + batch) - i
         call('bdn_blend_fold', ptr(logits[i:i + nb]), ptr(table[i:i + nb]), ptr(win), ptr(fold), nb, ncls, p, st())
@@ -107,6 +110,7 @@ def _custom_window(p):
     (100, 90, 32, 12, 'custom', tuple(range(8))),
     (77, 70, 40, 25, 'gaussian', (6, 1, 4)),
 ])
+@guarded
 def test_blend_kernels_match_float64(ncls, h, w, p, stride, window, syms):
     o, _, _ = inf.blend_tile_origins(h, w, p, stride)
     table = _table(o, syms)
@@ -116,7 +120,7 @@ def test_blend_kernels_match_float64(ncls, h, w, p, stride, window, syms):
     big = r.uniform(0, 1, (n, 1, p, p)) < 0.2
     logits = np.where(big, r.uniform(-80, 80, (n, ncls, p, p)).astype(np.float32), logits)
     win = _custom_window(p) if window == 'custom' else inf.blend_window(p, window)
-    lg, tb, wd = torch.from_numpy(logits).cuda(), torch.from_numpy(table).cuda(), win.cuda()
+    lg, tb, wd = guard.guard(torch.from_numpy(logits)), guard.guard(torch.from_numpy(table)), guard.guard(win)
     proba, mask = _blend_kernels(lg, tb, wd, h, w, p, stride, len(syms), 64)
     ref = _restate(logits, table, win.numpy(), h, w)
     got = proba.double().cpu().numpy()
