@@ -1,0 +1,103 @@
+"""The criterion of a run as one object: L = w_overlap * Overlap(alpha, beta, eps, reduce) + w_focal * Focal(gamma, class_alpha,
+size_average) behind ``bdn_criterion`` (include/bidate_hip.h; reference utils/helpers.py:303-312 over utils/metrics.py:8-171).
+
+Overlap is the TP / (TP + alpha FP + beta FN + eps) family: Tversky as given, jaccard = (1, 1, eps), dice = (0.5, 0.5, eps / 2).
+Focal is FocalLoss with the modulating factor a constant for the gradient.  The compound forms (focal + an overlap term, what change
+detection trains with on imbalanced data) run as one three-launch kernel sequence.  Importable without a GPU; evaluate() needs one.
+"""
+
+NAMES = ('tversky', 'dice', 'jaccard', 'focal', 'focal+tversky', 'focal+dice', 'focal+jaccard')
+COMPOUND = tuple(n for n in NAMES if '+' in n)
+REDUCE = {'columns': 0, 'image': 1}
+
+
+class Criterion:
+    def __init__(self, w_overlap=1.0, alpha=0.5, beta=0.5, eps=1e-7, reduce='columns', w_focal=0.0, gamma=0.0, class_alpha=None,
+                 size_average=True):
+        """reduce: 'columns' -- what the reference's train.py gets from [B,H,W] labels, sums over dims (0,2), one ratio per (class,
+        column) -- or 'image', dims (0,2,3), one ratio per class ([B,1,H,W] labels there).  class_alpha: None, a float a (class
+        weights [a, 1 - a], utils/metrics.py:13-14) or a sequence of ncls class weights."""
+        w_overlap, w_focal = float(w_overlap), float(w_focal)
+        if not (w_overlap >= 0.0 and w_focal >= 0.0):
+            raise ValueError(f'criterion weights must be >= 0, got w_overlap={w_overlap}, w_focal={w_focal}')
+        if w_overlap == 0.0 and w_focal == 0.0:
+            raise ValueError('criterion weights are both zero')
+        if reduce not in REDUCE:
+            raise ValueError(f"reduce must be 'columns' or 'image', got {reduce!r}")
+        if not float(gamma) >= 0.0:
+            raise ValueError(f'focal gamma must be >= 0, got {gamma}')
+        self.w_overlap, self.alpha, self.beta, self.eps, self.reduce = w_overlap, float(alpha), float(beta), float(eps), reduce
+        self.w_focal, self.gamma, self.size_average = w_focal, float(gamma), bool(size_average)
+        if isinstance(class_alpha, (float, int)):
+            class_alpha = [float(class_alpha), 1.0 - float(class_alpha)]
+        self.class_alpha = None if class_alpha is None else tuple(float(v) for v in class_alpha)
+        self._alpha_dev = {}
+
+    @classmethod
+    def parse(cls, name, tversky_alpha=0.5, tversky_beta=0.5, focal_gamma=None, focal_alpha=None, weights=(1, 1), eps=1e-7,
+              reduce='columns'):
+        """The criterion of a --loss_function name.  weights = (w_focal, w_overlap), used by the compound names only."""
+        if name not in NAMES:
+            raise ValueError(f'unknown criterion {name!r}: one of {", ".join(NAMES)}')
+        parts = name.split('+')
+        focal, overlap = 'focal' in parts, parts[-1] if parts[-1] != 'focal' else None
+        if focal and focal_gamma is None:
+            raise ValueError(f'criterion {name!r} needs a focal gamma')
+        w_focal, w_overlap = (float(weights[0]), float(weights[1])) if focal and overlap else (float(focal), float(overlap is not None))
+        coef = {'tversky': (tversky_alpha, tversky_beta, eps), 'dice': (0.5, 0.5, 0.5 * eps), 'jaccard': (1.0, 1.0, eps),
+                None: (0.5, 0.5, eps)}[overlap]
+        return cls(w_overlap, *coef, reduce=reduce, w_focal=w_focal, gamma=focal_gamma if focal else 0.0,
+                   class_alpha=focal_alpha if focal else None)
+
+    def __repr__(self):
+        return (f'Criterion(w_overlap={self.w_overlap}, alpha={self.alpha}, beta={self.beta}, eps={self.eps}, reduce={self.reduce!r}, '
+                f'w_focal={self.w_focal}, gamma={self.gamma}, class_alpha={self.class_alpha}, size_average={self.size_average})')
+
+    # ------------------------------------------------------------------ device side
+    def _class_alpha(self, device, ncls):
+        if self.class_alpha is None:
+            return None
+        if len(self.class_alpha) < ncls:
+            raise RuntimeError(f'class_alpha holds {len(self.class_alpha)} class weights for {ncls} classes')
+        import torch
+        t = self._alpha_dev.get(device)
+        if t is None:
+            t = self._alpha_dev[device] = torch.tensor(self.class_alpha, dtype=torch.float32).to(device)
+        return t
+
+    def buffers(self, shape, device):
+        """Persistent outputs for logits of `shape`: (workspace, loss, terms, counts), the `out` of evaluate()."""
+        import torch
+        from . import _lib
+        B, C, H, W = shape
+        n = _lib.load().bdn_criterion_workspace_bytes(B, C, H, W, REDUCE[self.reduce])
+        if n == 0:
+            raise RuntimeError(f'fabric_amd: the criterion takes logits [B, 2..8, H, W] with B*H*W < 2^31, got {tuple(shape)}')
+        return (torch.empty((n + 15) // 16 * 16, dtype=torch.uint8, device=device), torch.empty((), dtype=torch.float32, device=device),
+                torch.empty(2, dtype=torch.float32, device=device), torch.empty(4, dtype=torch.int32, device=device))
+
+    def evaluate(self, logits, labels, want_grad=True, out=None):
+        """-> (loss, terms, counts, dlogits) of float32 [B,C,H,W] logits and [B,H,W] or [B,1,H,W] class-index labels, on the current
+        stream: loss a 0-dim tensor, terms f32[2] = the unweighted overlap and focal values, counts int32[4] = {TP, FP, FN, correct} of
+        argmax(logits), dlogits = d loss / d logits (None without want_grad: no gradient pass is launched).  `out`: buffers() of this
+        shape, overwritten by every call that is given them; fresh ones otherwise.  The reduction is the criterion's `reduce`,
+        whichever rank the labels have."""
+        import torch
+        from . import _lib
+        if not logits.is_cuda:
+            raise RuntimeError('fabric_amd: the losses run only on a ROCm device -- there is no CPU path')
+        if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
+            raise RuntimeError('fabric_amd: the criterion takes contiguous float32 [B,C,H,W] logits')
+        B, C, H, W = logits.shape
+        if labels.numel() != B * H * W or tuple(labels.shape) not in ((B, H, W), (B, 1, H, W)):
+            raise RuntimeError(f'labels must be [B,H,W] or [B,1,H,W] for logits {tuple(logits.shape)}, got {tuple(labels.shape)}')
+        if labels.dtype != torch.uint8:
+            labels = labels.to(torch.uint8)
+        labels = labels.contiguous()
+        ws, loss, terms, counts = out if out is not None else self.buffers(logits.shape, logits.device)
+        dlogits = torch.empty_like(logits) if want_grad else None
+        ca = self._class_alpha(logits.device, C)
+        _lib.call('bdn_criterion', logits.data_ptr(), labels.data_ptr(), self.w_overlap, self.alpha, self.beta, self.eps,
+                  REDUCE[self.reduce], self.w_focal, self.gamma, _lib.ptr(ca), int(self.size_average), ws.data_ptr(), loss.data_ptr(),
+                  terms.data_ptr(), counts.data_ptr(), _lib.ptr(dlogits), B, C, H, W, _lib.stream_ptr())
+        return loss, terms, counts, dlogits

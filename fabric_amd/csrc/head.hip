@@ -586,10 +586,16 @@ extern "C" int bdn_outc_bn_bwd_apply(int dtype, const float* dlogits, const floa
 // sums[k][c][w], k = 0 TP, 1 FP, 2 FN, reduced over batch and H for every (class, column w).
 // pass 1: grid (column blocks x row blocks) -> per-block partial sums;  pass 2: single block adds the blocks in a fixed
 // order (no float atomics: the loss and dlogits are the same bits every run), then loss + coefficient tables;  pass 3: dlogits.
-template <int NC>
+// FOCAL (bdn_criterion's compound loss, below): the same three passes also carry a focal term -- the statistics pass adds every pixel's
+// focal loss from the softmax it has already formed (double per lane, block partials in a fixed order), the finish adds the blocks'
+// partials and forms the weighted sum, the gradient pass writes w_overlap dO + w_focal dF.  FOCAL = false is the code as it was.
+struct FocalStats { const float* calpha; float gamma; double* part; };                    // class weights or NULL; partial [gx*gy]
+__device__ __forceinline__ float focal_mod(float pt, float gamma) { return gamma == 0.f ? 1.f : powf(fmaxf(1.f - pt, 0.f), gamma); }
+
+template <int NC, bool FOCAL = false>
 __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                     float* __restrict__ part, int32_t* __restrict__ pcounts, int B, int ncls, int H, int W,
-                                    int rows_per_block, int We, FastDiv dH) {
+                                    int rows_per_block, int We, FastDiv dH, FocalStats fs = {}) {
     // block = 256 threads = RL row lanes x CW columns (CW = min(W rounded up to a power of two, 256));
     // grid.x = column blocks, grid.y = row blocks
     extern __shared__ float sm[];                         // [RL][3*NC][CW]
@@ -601,6 +607,7 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
 #pragma unroll
     for (int k = 0; k < NC; k++) { tp[k] = 0.f; fp[k] = 0.f; fn[k] = 0.f; }
     int c_tp = 0, c_fp = 0, c_fn = 0, c_ok = 0;
+    double facc = 0.0;
     const int rows = B * H, r_end = min(rows, (int)(blockIdx.y + 1) * rows_per_block);
     if (x < W)
         // four rows of a lane are requested before the first is used (a lane walks 16 rows at B = 64: one dependent HBM round trip
@@ -628,10 +635,18 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
                 for (int k = 0; k < NC; k++) { l[k] = k < ncls ? expf(l[k] - m) : 0.f; den += l[k]; }
                 const int t = tv[u];
                 const float inv = 1.f / den;
+                float pt = 0.f;
 #pragma unroll
                 for (int k = 0; k < NC; k++) {
                     const float p = l[k] * inv;
-                    if (t == k) { tp[k] += p; fn[k] += 1.f - p; } else fp[k] += p;
+                    if (t == k) { tp[k] += p; fn[k] += 1.f - p; pt = p; } else fp[k] += p;
+                }
+                if constexpr (FOCAL) {                     // -(1 - pt)^gamma a[t] log pt on the softmax above (focal_kernel's expression)
+                    float ltm = 0.f;                       // l[t] - max
+#pragma unroll
+                    for (int k = 0; k < NC; k++) if (t == k) ltm = lv[u][k] - m;
+                    const float a = fs.calpha ? (t < ncls ? fs.calpha[t] : 0.f) : 1.f;
+                    facc += (double)(-focal_mod(pt, fs.gamma) * a * (ltm - logf(den)));
                 }
                 c_tp += (am == 1 && t == 1); c_fp += (am == 1 && t != 1); c_fn += (am != 1 && t == 1); c_ok += (am == t);
             }
@@ -675,14 +690,26 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
         ism[tid * 4 + 0] = c_tp; ism[tid * 4 + 1] = c_fp; ism[tid * 4 + 2] = c_fn; ism[tid * 4 + 3] = c_ok;
         __syncthreads();
         if (tid < 4) { int v = 0; for (int i = 0; i < 256; i++) v += ism[i * 4 + tid]; pcounts[nblk_lin * 4 + tid] = v; }
+        if constexpr (FOCAL) {                             // the block's focal partial: LDS tree over the 256 lanes, a fixed order
+            double* dsm = reinterpret_cast<double*>(sm);
+            __syncthreads();
+            dsm[tid] = facc;
+            __syncthreads();
+            for (int s = 128; s > 0; s >>= 1) { if (tid < s) dsm[tid] += dsm[tid + s]; __syncthreads(); }
+            if (tid == 0) fs.part[nblk_lin] = dsm[0];
+        }
     }
 }
 
 // sums[cell] = sum over the nblk block partials (cell-major rows of `part`), fixed order: thread = (float4 of cells or one
 // cell, block lane); then loss = 1 - mean_{c,w} TP/(TP + a FP + b FN + eps).  Overwrites sums[0] with 1/D and sums[1] with TP/D^2.
+// FOCAL: also adds the nfp focal block partials (fixed order), loss = w_o overlap + w_f focal, terms = the two unweighted values.
+struct FocalFinish { const double* part; int nfp; double scale; float w_o, w_f; float* terms; };
+template <bool FOCAL = false>
 __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict__ sums, const float* __restrict__ part, int nblk,
                                       const int32_t* __restrict__ pcounts, int ncblk, int32_t* __restrict__ counts,
-                                      float alpha, float beta, float eps, int ncls, int W, float* __restrict__ loss) {   // W = effective width (1 when the columns are reduced too)
+                                      float alpha, float beta, float eps, int ncls, int W, float* __restrict__ loss,    // W = effective width (1 when the columns are reduced too)
+                                      FocalFinish ff = {}) {
     __shared__ double red[256];
     __shared__ float4 lane_sums[1024];
     const int n = 3 * ncls * W, tid = threadIdx.x;
@@ -734,12 +761,28 @@ __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict_
     if (tid < 256) red[tid] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+    if constexpr (FOCAL) {
+        const float ov = (float)(1.0 - red[0] / nc);
+        __syncthreads();                                   // red[0] is read by every thread before it is reused
+        double f = 0.0;
+        if (tid < 256) { for (int i = tid; i < ff.nfp; i += 256) f += ff.part[i]; red[tid] = f; }
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+        if (tid == 0) {
+            const float fo = (float)(red[0] * ff.scale);
+            *loss = ff.w_o * ov + ff.w_f * fo;
+            if (ff.terms) { ff.terms[0] = ov; ff.terms[1] = fo; }
+        }
+    } else
     if (tid == 0) *loss = (float)(1.0 - red[0] / nc);
 }
 
+// FOCAL: dlogits = w_o dO + w_f dF with dF_k = -(1 - pt)^gamma a[t] gscale ([k == t] - p_k), the factor a constant (focal_kernel)
+struct FocalBwd { const float* calpha; float gamma, gscale, w_o, w_f; };
+template <bool FOCAL = false>
 __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                    const float* __restrict__ coef, float alpha, float beta, float* __restrict__ dlogits,
-                                   int B, int ncls, int H, int Wimg, int W, FastDiv dhw, FastDiv dWimg) {
+                                   int B, int ncls, int H, int Wimg, int W, FastDiv dhw, FastDiv dWimg, FocalBwd fb = {}) {
     const size_t hw = (size_t)H * Wimg, npix = (size_t)B * hw;
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npix) return;
@@ -764,8 +807,19 @@ __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8
         dp[k] = norm * (tk * invD - tpD2 * (tk + alpha * (1.f - tk) - beta * tk));
         dot += l[k] * dp[k];
     }
+    if constexpr (FOCAL) {
+        float pt = 0.f;
+#pragma unroll
+        for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls && k == t) pt = l[k];
+        const float a = fb.calpha ? (t < ncls ? fb.calpha[t] : 0.f) : 1.f;
+        const float c = -focal_mod(pt, fb.gamma) * a * fb.gscale;
+#pragma unroll
+        for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls)
+            dlogits[(b * ncls + k) * hw + q] = fb.w_o * (l[k] * (dp[k] - dot)) + fb.w_f * (c * ((k == t ? 1.f : 0.f) - l[k]));
+    } else {
 #pragma unroll
     for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls) dlogits[(b * ncls + k) * hw + q] = l[k] * (dp[k] - dot);
+    }
 }
 
 struct OverlapPlan { int We, CW, RL, rpb, gx, gy, nblk, n; };
@@ -799,13 +853,13 @@ extern "C" int bdn_overlap_loss(const float* logits, const uint8_t* labels, floa
     float* part = ws + p.n;                                                    // [nblk][n] block partials behind the n final sums
     int32_t* pcounts = reinterpret_cast<int32_t*>(part + (size_t)p.nblk * p.n);  // [gx*gy][4]
     dim3 grid(p.gx, p.gy), block(p.RL, p.CW);
-    if (ncls <= 2) hipLaunchKernelGGL(tversky_sums_kernel<2>, grid, block, sizeof(float) * 256 * 3 * 2, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, We, FastDiv(H));
-    else hipLaunchKernelGGL(tversky_sums_kernel<OUTC_MAXCLS>, grid, block, sizeof(float) * 256 * 3 * OUTC_MAXCLS, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, We, FastDiv(H));
+    if (ncls <= 2) hipLaunchKernelGGL((tversky_sums_kernel<2, false>), grid, block, sizeof(float) * 256 * 3 * 2, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, We, FastDiv(H), FocalStats{});
+    else hipLaunchKernelGGL((tversky_sums_kernel<OUTC_MAXCLS, false>), grid, block, sizeof(float) * 256 * 3 * OUTC_MAXCLS, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, We, FastDiv(H), FocalStats{});
     BDN_CHECK_LAUNCH("tversky_sums");
-    hipLaunchKernelGGL(tversky_finish_kernel, dim3(1), dim3(1024), 0, st, ws, part, p.nblk, pcounts, p.gx * p.gy, counts, alpha, beta, eps, ncls, We, loss);
+    hipLaunchKernelGGL(tversky_finish_kernel<false>, dim3(1), dim3(1024), 0, st, ws, part, p.nblk, pcounts, p.gx * p.gy, counts, alpha, beta, eps, ncls, We, loss, FocalFinish{});
     BDN_CHECK_LAUNCH("tversky_finish");
     if (dlogits) {
-        hipLaunchKernelGGL(tversky_bwd_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, logits, labels, ws, alpha, beta, dlogits, B, ncls, H, W, We, FastDiv(H * W), FastDiv(W));
+        hipLaunchKernelGGL(tversky_bwd_kernel<false>, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, logits, labels, ws, alpha, beta, dlogits, B, ncls, H, W, We, FastDiv(H * W), FastDiv(W), FocalBwd{});
         BDN_CHECK_LAUNCH("tversky_bwd");
     }
     return BDN_OK;
@@ -891,6 +945,66 @@ extern "C" int bdn_focal(const float* logits, const uint8_t* labels, float gamma
     BDN_CHECK_LAUNCH("focal");
     hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nblk, inv, loss);
     BDN_CHECK_LAUNCH("focal_finish");
+    return BDN_OK;
+}
+
+// ============================================================ criterion: w_overlap Overlap + w_focal Focal (utils/helpers.py:303-312)
+// One term with weight 1 is the existing entry point, launch for launch (same bits).  Anything else -- the compound losses -- runs the
+// overlap loss's three passes in their FOCAL form: statistics (softmax once per pixel -> overlap partial sums, focal partial sums in
+// double, argmax counts), the fixed-order finish, and one gradient pass that writes w_overlap dO + w_focal dF.  No atomics, no memset.
+// ws: [focal block partials, double, padded to 16 bytes][bdn_overlap_loss's workspace].
+__global__ void criterion_terms_kernel(const float* __restrict__ loss, float* __restrict__ terms, int slot) {
+    terms[slot] = *loss; terms[1 - slot] = 0.f;
+}
+
+static inline size_t criterion_focal_part_bytes(const OverlapPlan& p) { return (sizeof(double) * p.gx * p.gy + 15) / 16 * 16; }
+
+extern "C" size_t bdn_criterion_workspace_bytes(int B, int ncls, int H, int W, int reduce_w) {
+    const size_t ov = bdn_overlap_workspace_bytes(B, ncls, H, W, reduce_w);
+    if (ov == 0 || (size_t)B * H * W >= ((size_t)1 << 31)) return 0;
+    const size_t compound = criterion_focal_part_bytes(overlap_plan(B, ncls, H, W, reduce_w)) + ov, focal = bdn_focal_workspace_bytes();
+    return compound > focal ? compound : focal;
+}
+
+extern "C" int bdn_criterion(const float* logits, const uint8_t* labels, float w_overlap, float alpha, float beta, float eps, int reduce_w,
+                             float w_focal, float gamma, const float* class_alpha, int size_average, void* ws, float* loss, float* terms,
+                             int32_t* counts, float* dlogits, int B, int ncls, int H, int W, void* stream) {
+    if (!logits || !labels || !ws || !loss) BDN_FAIL(BDN_E_ARG, "criterion: null pointer");
+    if (!(w_overlap >= 0.f) || !(w_focal >= 0.f)) BDN_FAIL(BDN_E_ARG, "criterion: negative weight (w_overlap=%g, w_focal=%g)", w_overlap, w_focal);
+    if (w_overlap == 0.f && w_focal == 0.f) BDN_FAIL(BDN_E_ARG, "criterion: both weights are zero");
+    if (!(gamma >= 0.f)) BDN_FAIL(BDN_E_ARG, "criterion: negative gamma");
+    if (ncls < 2 || ncls > OUTC_MAXCLS) BDN_FAIL(BDN_E_SHAPE, "criterion: ncls=%d unsupported (2..%d)", ncls, OUTC_MAXCLS);
+    if (B <= 0 || H <= 0 || W <= 0 || (size_t)B * H * W >= ((size_t)1 << 31)) BDN_FAIL(BDN_E_SHAPE, "criterion: bad shape (B*H*W must stay below 2^31)");
+    if ((uintptr_t)ws & 15) BDN_FAIL(BDN_E_ARG, "criterion: ws must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if ((w_focal == 0.f && w_overlap == 1.f) || (w_overlap == 0.f && w_focal == 1.f)) {
+        const int focal = w_overlap == 0.f;
+        const int rc = focal ? bdn_focal(logits, labels, gamma, class_alpha, size_average, ws, loss, counts, dlogits, B, ncls, H, W, stream)
+                             : bdn_overlap_loss(logits, labels, alpha, beta, eps, reduce_w, (float*)ws, loss, counts, dlogits, B, ncls, H, W, stream);
+        if (rc != BDN_OK || !terms) return rc;
+        hipLaunchKernelGGL(criterion_terms_kernel, dim3(1), dim3(1), 0, st, loss, terms, focal);
+        BDN_CHECK_LAUNCH("criterion_terms");
+        return BDN_OK;
+    }
+    const OverlapPlan p = overlap_plan(B, ncls, H, W, reduce_w);
+    double* fpart = (double*)ws;                                               // [gx*gy]
+    float* sums = (float*)((char*)ws + criterion_focal_part_bytes(p));         // bdn_overlap_loss's layout from here on
+    float* part = sums + p.n;
+    int32_t* pcounts = reinterpret_cast<int32_t*>(part + (size_t)p.nblk * p.n);
+    const double inv = size_average ? 1.0 / (double)((size_t)B * H * W) : 1.0;
+    const FocalStats fs{class_alpha, gamma, fpart};
+    dim3 grid(p.gx, p.gy), block(p.RL, p.CW);
+    if (ncls <= 2) hipLaunchKernelGGL((tversky_sums_kernel<2, true>), grid, block, sizeof(float) * 256 * 3 * 2, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, p.We, FastDiv(H), fs);
+    else hipLaunchKernelGGL((tversky_sums_kernel<OUTC_MAXCLS, true>), grid, block, sizeof(float) * 256 * 3 * OUTC_MAXCLS, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, p.We, FastDiv(H), fs);
+    BDN_CHECK_LAUNCH("criterion_stats");
+    hipLaunchKernelGGL(tversky_finish_kernel<true>, dim3(1), dim3(1024), 0, st, sums, part, p.nblk, pcounts, p.gx * p.gy, counts, alpha, beta, eps, ncls, p.We, loss,
+                       FocalFinish{fpart, p.gx * p.gy, inv, w_overlap, w_focal, terms});
+    BDN_CHECK_LAUNCH("criterion_finish");
+    if (dlogits) {
+        hipLaunchKernelGGL(tversky_bwd_kernel<true>, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, logits, labels, sums, alpha, beta, dlogits, B, ncls, H, W, p.We,
+                           FastDiv(H * W), FastDiv(W), FocalBwd{class_alpha, gamma, (float)inv, w_overlap, w_focal});
+        BDN_CHECK_LAUNCH("criterion_bwd");
+    }
     return BDN_OK;
 }
 

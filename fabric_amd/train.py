@@ -6,6 +6,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --epochs 1                                   # needs an MI355X
     python -m fabric_amd.train --metadata metadata.json --dataset_dir ./onera/          # an OSCD directory tree
     python -m fabric_amd.train --synthetic --epochs 4 --optimizer adamw --resume ./log/checkpoint_epoch_1.state_dict.pt
+    python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --freeze inc --optimizer adamw
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
 predicted tile by tile (utils/inference.py) -- here on the device-resident city stacks -- and written as PNG masks.
@@ -139,7 +140,7 @@ def validate(model, loader, dev, patch_size, criterion, feeder=None):
 
 
 def train_epoch_autograd(model, criterion, optimizer, loader, dev, patch_size, world=1, feeder=None):
-    """The reference loop itself (train.py:83-101) for the criteria the fused step does not cover (dice / jaccard / focal):
+    """The reference loop itself (train.py:83-101) for dice / jaccard / focal without --fused_step true (the routing as it always was):
     autograd through the one-node BiDateNet function, a torch.optim optimizer (make_torch_optimizer), gradients averaged over the
     ranks after backward."""
     from .parallel import allreduce_mean_grads
@@ -290,6 +291,13 @@ def main(argv=None):
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'bf16x3', 'bf16x3-fast', 'fp32'])
     ap.add_argument('--seed', type=int, default=0, help='seeds the shard permutation, the augmentation draws and the initial weights identically on every rank')
     ap.add_argument('--focal_gamma', type=float, default=None, help='required by --loss_function focal (utils/helpers.py:291)')
+    ap.add_argument('--focal_alpha', type=float, default=None, help='focal class weights [a, 1 - a] (utils/metrics.py:13-14); --fused_step true only')
+    ap.add_argument('--fused_step', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=False,
+                    help='true: every --loss_function trains on the fused step (and --freeze / --frozen_bn / --no_decay_norm_bias / --lr_scale '
+                         'work with all of them), and the compound criteria focal+dice / focal+jaccard / focal+tversky are available; '
+                         'false: tversky on the fused step, dice / jaccard / focal on the autograd route')
+    ap.add_argument('--loss_weights', type=float, nargs=2, default=[1.0, 1.0], metavar=('W_FOCAL', 'W_OVERLAP'),
+                    help='weights of the two terms of a compound --loss_function')
     ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam', 'adamw'],
                     help='sgd is train.py:55 (optim.SGD); adam / adamw the torch.optim rules (train.py:56 is a commented-out Adam)')
     ap.add_argument('--momentum', type=float, default=0.0, help='sgd only')
@@ -328,11 +336,21 @@ def main(argv=None):
     opt = ap.parse_args(argv)
     for k in ('band_ids', 'band_means', 'band_stds'):
         setattr(opt, k, meta.get(k))
-    if opt.loss_function not in ('tversky', 'dice', 'jaccard', 'focal'):
+    from .criterion import COMPOUND
+    if opt.loss_function in COMPOUND and not opt.fused_step:
+        raise SystemExit(f'--loss_function {opt.loss_function} is a compound criterion of the fused step: add --fused_step true')
+    if opt.loss_function not in ('tversky', 'dice', 'jaccard', 'focal') + COMPOUND:
         raise SystemExit(f'--loss_function {opt.loss_function}: the reference offers bce / focal / dice / jaccard / tversky '
                          f"(utils/helpers.py:288-314); its bce branch cannot run on BiDateNet's logits and is not built")
-    if opt.loss_function == 'focal' and opt.focal_gamma is None:
-        raise SystemExit('--loss_function focal needs --focal_gamma')
+    if 'focal' in opt.loss_function.split('+') and opt.focal_gamma is None:
+        raise SystemExit(f'--loss_function {opt.loss_function} needs --focal_gamma')
+    step_criterion = None                                  # --fused_step true: ONE Criterion for the step and for validation
+    if opt.fused_step:
+        from .utils.helpers import criterion_from_opt
+        try:
+            step_criterion = criterion_from_opt(opt)
+        except ValueError as e:
+            raise SystemExit(f'--loss_function {opt.loss_function}: {e}')
     from .optim import OptimConfig
     try:
         OptimConfig(opt.optimizer, lr=opt.learning_rate, momentum=opt.momentum, nesterov=opt.nesterov, weight_decay=opt.weight_decay,
@@ -340,9 +358,9 @@ def main(argv=None):
     except ValueError as e:
         raise SystemExit(f'--optimizer {opt.optimizer}: {e}')
     grouped = bool(opt.freeze or opt.frozen_bn or opt.no_decay_norm_bias or opt.lr_scale)
-    if grouped and opt.loss_function != 'tversky':
+    if grouped and opt.loss_function != 'tversky' and not opt.fused_step:
         raise SystemExit(f'--freeze / --frozen_bn / --no_decay_norm_bias / --lr_scale are built into the fused step, which runs '
-                         f'--loss_function tversky only (got {opt.loss_function})')
+                         f'--loss_function tversky only (got {opt.loss_function}) unless --fused_step true is given')
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
 
@@ -388,17 +406,22 @@ def main(argv=None):
     elif opt.init_from:
         from .utils.helpers import load_checkpoint
         model = load_checkpoint(opt.init_from, device=dev, precision=opt.precision)
-    fused = opt.loss_function == 'tversky'
+    fused = opt.fused_step or opt.loss_function == 'tversky'
     from .input_pipeline import DeviceFeeder
     from .utils.helpers import get_criterion
     # ONE feeder (copy stream, staging threads, device slots) for the whole run; device-sampled batches need none
     feeder = None if opt.device_patches else DeviceFeeder(dev)
-    criterion = get_criterion(opt)                         # validation reports the criterion the run optimises (train.py:137)
+    if step_criterion is not None:
+        from .utils.metrics import CompoundLoss
+        criterion = CompoundLoss(step_criterion)           # the step's own Criterion, through its autograd module
+    else:
+        criterion = get_criterion(opt)                     # validation reports the criterion the run optimises (train.py:137)
     if fused:
         try:
             groups = fine_tune_groups(model, opt.learning_rate, opt.weight_decay, opt.freeze, opt.no_decay_norm_bias, opt.lr_scale)
             step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta,
-                             param_groups=groups, bn='frozen' if opt.frozen_bn else 'batch', **optimizer_kwargs(opt))
+                             param_groups=groups, bn='frozen' if opt.frozen_bn else 'batch', criterion=step_criterion,
+                             **optimizer_kwargs(opt))
         except ValueError as e:
             raise SystemExit(f'parameter groups: {e}')
         if opt_sd is not None:

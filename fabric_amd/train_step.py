@@ -1,6 +1,6 @@
 """The train.py step (reference train.py:83-101 + optim.SGD, train.py:55) as one fused schedule:
 
-    to-device tensors -> forward -> Tversky loss (+ argmax TP/FP/FN counts) -> backward
+    to-device tensors -> forward -> Tversky loss, or the `criterion` given (+ argmax TP/FP/FN counts) -> backward
     -> bucketed gradient all-reduce overlapped with backward -> SGD (or momentum SGD / Adam / AdamW: fabric_amd/optim.py)
 
 with no host synchronisation inside the step (the reference syncs every step for sklearn
@@ -23,7 +23,7 @@ class TrainStep:
     def __init__(self, model, lr=1e-3, tversky_alpha=0.1, tversky_beta=0.9, eps=1e-7,
                  process_group=None, n_buckets=4, distributed=True, force_collectives=False, guard=True,
                  optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8,
-                 param_groups=None, bn='batch'):
+                 param_groups=None, bn='batch', criterion=None):
         """optimizer: 'sgd' (torch.optim.SGD: momentum, dampening, nesterov, weight_decay), 'adam' or 'adamw' (torch.optim.Adam / AdamW:
         betas, adam_eps, weight_decay); weight_decay=None is torch's default (0 for sgd and adam, 1e-2 for adamw).  The default, plain
         SGD, is the reference's optim.SGD(lr) (train.py:55) and keeps no state; the other rules keep theirs in flat f32 buffers in the
@@ -37,6 +37,12 @@ class TrainStep:
         optimizer state, no weight-gradient GEMM, and backward stops at the last trainable layer (engine.chain_end).  A trainable
         parameter that no group lists raises ValueError: it is never silently frozen.  With groups or frozen parameters the update
         runs bdn_*_step_grouped; with neither, the ungrouped entry points as before.
+
+        criterion: None (the reference's default, TverskyLoss(tversky_alpha, tversky_beta, eps) on [B,H,W] labels through bdn_tversky:
+        the step as it always was), a fabric_amd.criterion.Criterion, or one of its names ('tversky', 'dice', 'jaccard', 'focal+dice',
+        ...: Criterion.parse with this step's tversky_alpha / tversky_beta / eps; a focal term needs a gamma, so build the Criterion).
+        With a criterion the loss runs bdn_criterion, labels may be [B,H,W] or [B,1,H,W] (the criterion's `reduce` decides the overlap
+        reduction), `last_terms` holds the unweighted overlap and focal values beside `last_counts`, and `last_dlogits` the loss gradient.
 
         bn: 'batch' (BatchNorm on batch statistics, running statistics updated: a training step) or 'frozen' (BatchNorm on its running
         statistics, which are constants: running_mean / running_var / num_batches_tracked are not touched, and the conv biases in
@@ -54,6 +60,10 @@ class TrainStep:
         self._guard = guard
         self.collectives_report = None
         self.alpha, self.beta, self.eps = tversky_alpha, tversky_beta, eps
+        if isinstance(criterion, str):
+            from .criterion import Criterion
+            criterion = Criterion.parse(criterion, tversky_alpha=tversky_alpha, tversky_beta=tversky_beta, eps=eps)
+        self.criterion = criterion
         self.group = process_group
         self.high_priority_chain = True
         self._hp = None
@@ -86,7 +96,7 @@ class TrainStep:
         if self.world > 1:                                   # identical start on every rank (DataParallel broadcasts)
             dist.broadcast(self.flat_params, src=0, group=process_group)
         self._tv = None
-        self.last_counts = None
+        self.last_counts = self.last_terms = self.last_dlogits = None
         # detached aliases of every parameter / buffer (same storage), built once: no per-step dict walk
         self._P = {k: v.detach() for k, v in self.model.state_dict(keep_vars=True).items()}
         self.param_groups = self._groups = self._seg = self._need = None
@@ -160,8 +170,9 @@ class TrainStep:
         with torch.cuda.stream(self._hp):
             loss = self._step(x_d1, x_d2, labels)
         cur.wait_stream(self._hp)
-        for t in (loss, self.last_logits, self.last_counts):
-            t.record_stream(cur)
+        for t in (loss, self.last_logits, self.last_counts, self.last_terms, self.last_dlogits):
+            if t is not None:
+                t.record_stream(cur)
         return loss
 
     def stream(self, device=None):
@@ -356,20 +367,11 @@ class TrainStep:
             lease = _Lease(ws)
         else:
             logits, ws = eng.forward(x_d1, x_d2, P, training=True)
-        B, C, H, W = logits.shape
-        dev = logits.device
-        if self._tv is None or self._tv[3] != (B, C, H, W):
-            n = _lib.load().bdn_overlap_workspace_bytes(B, C, H, W, 0) // 4
-            self._tv = (torch.empty(n, dtype=torch.float32, device=dev), torch.empty((), dtype=torch.float32, device=dev),
-                        torch.empty(4, dtype=torch.int32, device=dev), (B, C, H, W))
-        tvws, loss, counts, _ = self._tv
-        if labels.dtype != torch.uint8:
-            labels = labels.to(torch.uint8)
-        labels = labels.contiguous()
-        dlogits = torch.empty_like(logits)
         st = _lib.stream_ptr()
-        _lib.call('bdn_tversky', logits.data_ptr(), labels.data_ptr(), float(self.alpha), float(self.beta),
-                  float(self.eps), tvws.data_ptr(), loss.data_ptr(), counts.data_ptr(), dlogits.data_ptr(), B, C, H, W, st)
+        if self.criterion is not None:
+            loss, counts, dlogits = self._criterion_loss(logits, labels)
+        else:
+            loss, counts, dlogits = self._tversky_loss(logits, labels, st)
         if frozen_bn:
             try:
                 eng.backward(ws, dlogits, P, self.grads, on_ready=self.bucketer.on_ready, zero_bias_grads=False, bn_mode='running',
@@ -386,6 +388,33 @@ class TrainStep:
         self.last_counts = counts
         self.last_logits = logits
         return loss.clone()
+
+    def _tversky_loss(self, logits, labels, st):
+        """The default criterion: bdn_tversky on persistent buffers -> (loss, counts, dlogits)."""
+        B, C, H, W = logits.shape
+        dev = logits.device
+        if self._tv is None or self._tv[3] != (B, C, H, W):
+            n = _lib.load().bdn_overlap_workspace_bytes(B, C, H, W, 0) // 4
+            self._tv = (torch.empty(n, dtype=torch.float32, device=dev), torch.empty((), dtype=torch.float32, device=dev),
+                        torch.empty(4, dtype=torch.int32, device=dev), (B, C, H, W))
+        tvws, loss, counts, _ = self._tv
+        if labels.dtype != torch.uint8:
+            labels = labels.to(torch.uint8)
+        labels = labels.contiguous()
+        dlogits = torch.empty_like(logits)
+        _lib.call('bdn_tversky', logits.data_ptr(), labels.data_ptr(), float(self.alpha), float(self.beta),
+                  float(self.eps), tvws.data_ptr(), loss.data_ptr(), counts.data_ptr(), dlogits.data_ptr(), B, C, H, W, st)
+        return loss, counts, dlogits
+
+    def _criterion_loss(self, logits, labels):
+        """An explicit criterion: bdn_criterion on persistent buffers sized once per shape -> (loss, counts, dlogits); sets last_terms
+        and last_dlogits (the gradient this step's backward starts from)."""
+        shape = tuple(logits.shape)
+        if self._tv is None or self._tv[1] != shape:
+            self._tv = (self.criterion.buffers(shape, logits.device), shape)
+        loss, terms, counts, dlogits = self.criterion.evaluate(logits, labels, out=self._tv[0])
+        self.last_terms, self.last_dlogits = terms, dlogits
+        return loss, counts, dlogits
 
     def _update(self, st):
         """The optimizer update on stream `st` with g = (sum of rank gradients) / world: per-rank loss, averaged gradients (standard DDP;

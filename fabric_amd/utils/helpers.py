@@ -4,7 +4,7 @@ import numpy as np
 import torch
 
 from ..models.bidate_model import BiDateNet
-from .metrics import FocalLoss, TverskyLoss, dice_loss, jaccard_loss
+from .metrics import CompoundLoss, FocalLoss, TverskyLoss, dice_loss, jaccard_loss
 
 
 def initialize_metrics():
@@ -31,6 +31,8 @@ def get_criterion(opt):
     """reference utils/helpers.py:288-314.  `focal` reads opt.focal_gamma exactly like the reference (absent from
     metadata.json there, so it raises AttributeError unless the caller adds it); `bce` cannot run on BiDateNet's
     [B,2,H,W] logits with [B,H,W] labels in the reference either (shape mismatch inside BCEWithLogitsLoss)."""
+    if '+' in str(opt.loss_function):                        # focal+dice / focal+jaccard / focal+tversky: one compound criterion
+        return CompoundLoss(criterion_from_opt(opt))
     if opt.loss_function == 'focal':
         return FocalLoss(opt.focal_gamma)
     if opt.loss_function == 'dice':
@@ -41,6 +43,15 @@ def get_criterion(opt):
         return TverskyLoss(alpha=opt.tversky_alpha, beta=opt.tversky_beta)
     raise NotImplementedError(f'fabric_amd: loss_function={opt.loss_function!r}: the reference\'s BCEWithLogitsLoss '
                               f'branch fails on [B,2,H,W] logits vs [B,H,W] labels and is not built')
+
+
+def criterion_from_opt(opt):
+    """fabric_amd.criterion.Criterion of the --loss_function / --tversky_alpha / --tversky_beta / --focal_gamma / --focal_alpha /
+    --loss_weights (W_FOCAL W_OVERLAP) options; ValueError as Criterion.parse raises it."""
+    from ..criterion import Criterion
+    return Criterion.parse(opt.loss_function, tversky_alpha=getattr(opt, 'tversky_alpha', 0.5), tversky_beta=getattr(opt, 'tversky_beta', 0.5),
+                           focal_gamma=getattr(opt, 'focal_gamma', None), focal_alpha=getattr(opt, 'focal_alpha', None),
+                           weights=tuple(getattr(opt, 'loss_weights', None) or (1, 1)))
 
 
 def get_loaders(opt):

@@ -3,7 +3,9 @@
 TverskyLoss (the default criterion, metadata.json:42-44) is a fused HIP kernel
 (softmax + the reference's TP/FP/FN sums + loss + d loss / d logits + argmax
 TP/FP/FN counts for F1) behind ``bdn_overlap_loss``; dice_loss and jaccard_loss
-are the same kernel with other coefficients, FocalLoss is ``bdn_focal``.  Both
+are the same kernel with other coefficients, FocalLoss is ``bdn_focal``;
+CompoundLoss is a weighted focal + overlap sum as one criterion (``bdn_criterion``,
+fabric_amd/criterion.py).  Both
 label ranks of the reference are supported ([B,H,W] -> dims (0,2), [B,1,H,W] ->
 dims (0,2,3)).  The sigmoid single-class branch (utils/metrics.py:65-72,
 100-107, 149-157) is never reached by BiDateNet(13, 2) and is not built.
@@ -140,6 +142,48 @@ class TverskyLoss(nn.Module):
     def last_counts(self):
         """int32[4] device tensor {TP, FP, FN, correct} of argmax(logits) vs labels for the last call."""
         return self._holder.get('counts')
+
+
+class _CriterionFunction(torch.autograd.Function):
+    """fabric_amd.criterion.Criterion.evaluate as one autograd node; without a gradient to compute no gradient pass is launched."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, criterion, holder):
+        want = ctx.needs_input_grad[0]
+        loss, terms, counts, dl = criterion.evaluate(logits.detach().contiguous().float(), labels.detach(), want_grad=want)
+        if want:
+            ctx.save_for_backward(dl)
+        holder['counts'], holder['terms'] = counts, terms
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return dl * g, None, None, None
+
+
+class CompoundLoss(nn.Module):
+    """w_overlap * (dice | jaccard | Tversky) + w_focal * FocalLoss as one criterion (fabric_amd.criterion.Criterion, bdn_criterion):
+    the module form for validation and the autograd route.  The criterion's `reduce` decides the overlap reduction, not the label
+    rank."""
+
+    def __init__(self, criterion):
+        super(CompoundLoss, self).__init__()
+        self.criterion = criterion
+        self._holder = {}
+
+    def forward(self, logits, true):
+        return _CriterionFunction.apply(logits, true, self.criterion, self._holder)
+
+    @property
+    def last_counts(self):
+        """int32[4] device tensor {TP, FP, FN, correct} of argmax(logits) vs labels for the last call."""
+        return self._holder.get('counts')
+
+    @property
+    def last_terms(self):
+        """f32[2] device tensor: the unweighted overlap and focal values of the last call."""
+        return self._holder.get('terms')
 
 
 def confusion_counts(logits, labels):

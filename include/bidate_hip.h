@@ -429,6 +429,21 @@ int bdn_focal(const float* logits, const uint8_t* labels, float gamma, const flo
               void* ws, float* loss, int32_t* counts, float* dlogits,
               int B, int ncls, int H, int W, void* stream);
 
+/* ---- the criterion of a run, utils/helpers.py:303-312 over utils/metrics.py:8-48 (FocalLoss) and :51-171 (dice / jaccard / Tversky) ----
+ *   L = w_overlap * Overlap(alpha, beta, eps, reduce_w) + w_focal * Focal(gamma, class_alpha, size_average)
+ * with Overlap exactly bdn_overlap_loss's function and Focal exactly bdn_focal's (the modulating factor a constant for the gradient);
+ * w_overlap, w_focal >= 0 and not both zero.  One term with weight 1 and the other with weight 0 runs that entry point's own launches
+ * (its bits).  Every other case -- the compound losses focal + dice / jaccard / Tversky -- is three launches: a statistics pass that forms
+ * softmax once per pixel (overlap partial sums, focal partial sums in double, argmax counts), a fixed-order finish, and a gradient pass
+ * that writes w_overlap dO + w_focal dF once; no float atomics, no memset: loss, terms, counts and dlogits are the same bits every run.
+ * Every pointer is device memory.  class_alpha: NULL or f32[ncls].  ws: bdn_criterion_workspace_bytes() bytes, 16-byte aligned.
+ * terms: NULL or f32[2] = the unweighted overlap and focal values (0 for a term that did not run).  counts, dlogits: NULL or as
+ * bdn_tversky; dlogits == NULL launches no gradient pass (validation). */
+size_t bdn_criterion_workspace_bytes(int B, int ncls, int H, int W, int reduce_w);
+int bdn_criterion(const float* logits, const uint8_t* labels, float w_overlap, float alpha, float beta, float eps, int reduce_w,
+                  float w_focal, float gamma, const float* class_alpha, int size_average, void* ws, float* loss, float* terms,
+                  int32_t* counts, float* dlogits, int B, int ncls, int H, int W, void* stream);
+
 /* ---- OSCD ingest: utils/dataloaders.py:86-111 city_loader, per band ----
  * dst [H][W] f32 (one plane of a [C][H][W] scene) = cv2.resize((src - mean) / std, (W, H)) with cv2's default float
  * INTER_LINEAR sampling (half-pixel centres, border weights (1,0)).  src: [hs][ws] uint16 (src_is_f32 = 0) or f32, on

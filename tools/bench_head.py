@@ -46,6 +46,22 @@ if True:
     timeit('outc_fwd', lambda: _lib.call('bdn_outc_fwd', dt, P(z), P(bn), P(w), P(b), P(logits), B, H, W, C, NC, st), zb + logits.numel() * 4)
     timeit('tversky (3 launches)', lambda: _lib.call('bdn_tversky', P(logits), P(labels), 0.1, 0.9, 1e-7, P(ws_t), P(loss), P(counts), P(dlogits), B, NC, H, W, st),
            2 * logits.numel() * 4 + 2 * labels.numel() + dlogits.numel() * 4)
+    # the criterion entry point: one term (the existing launches), the compound loss, and what the compound loss cost as two calls
+    lb = 2 * logits.numel() * 4 + 2 * labels.numel() + dlogits.numel() * 4
+    ws_c = torch.empty(lib.bdn_criterion_workspace_bytes(B, NC, H, W, 0) + 16, dtype=torch.uint8, device=dev)
+    ws_f = torch.empty(lib.bdn_focal_workspace_bytes(), dtype=torch.uint8, device=dev)
+    terms = torch.empty(2, device=dev); dl2 = torch.empty_like(dlogits)
+    crit = lambda wo, wf: _lib.call('bdn_criterion', P(logits), P(labels), wo, 0.5, 0.5, 5e-8, 0, wf, 2.0, None, 1, P(ws_c), P(loss), P(terms),
+                                    P(counts), P(dlogits), B, NC, H, W, st)
+
+    def two_calls():
+        _lib.call('bdn_focal', P(logits), P(labels), 2.0, None, 1, P(ws_f), P(loss), P(counts), P(dl2), B, NC, H, W, st)
+        _lib.call('bdn_overlap_loss', P(logits), P(labels), 0.5, 0.5, 5e-8, 0, P(ws_t), P(loss), P(counts), P(dlogits), B, NC, H, W, st)
+        dlogits.add_(dl2)
+    timeit('criterion dice', lambda: crit(1.0, 0.0), lb)
+    timeit('criterion focal', lambda: crit(0.0, 1.0), lb)
+    timeit('criterion focal+dice', lambda: crit(1.0, 1.0), lb)
+    timeit('focal + dice, two calls', two_calls, lb)
     timeit('outc_bwd (+dw reduce)', lambda: _lib.call('bdn_outc_bwd', dt, P(dlogits), P(z), P(bn), P(w), None, P(dw), P(db), P(stats), P(ows), B, H, W, C, NC, st),
            zb + dlogits.numel() * 4)
     timeit('outc_bn_bwd_apply', lambda: _lib.call('bdn_outc_bn_bwd_apply', dt, P(dlogits), P(w), P(z), P(bn), B, P(sums), P(dz), B, H, W, C, NC, st),
