@@ -644,8 +644,8 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
                 if constexpr (FOCAL) {                     // -(1 - pt)^gamma a[t] log pt on the softmax above (focal_kernel's expression)
                     float ltm = 0.f;                       // l[t] - max
 #pragma unroll
-                    for (int k = 0; k < NC; k++) if (t == k) ltm = lv[u][k] - m;
-                    const float a = fs.calpha ? (t < ncls ? fs.calpha[t] : 0.f) : 1.f;
+                    for (int k = 0; k < NC; k++) if (k < ncls && t == k) ltm = lv[u][k] - m;      // (lv is -inf for k >= ncls: 0 * inf otherwise)
+                    const float a = t < ncls ? (fs.calpha ? fs.calpha[t] : 1.f) : 0.f;       // a label >= ncls has no true class: no focal term
                     facc += (double)(-focal_mod(pt, fs.gamma) * a * (ltm - logf(den)));
                 }
                 c_tp += (am == 1 && t == 1); c_fp += (am == 1 && t != 1); c_fn += (am != 1 && t == 1); c_ok += (am == t);
@@ -811,7 +811,7 @@ __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8
         float pt = 0.f;
 #pragma unroll
         for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls && k == t) pt = l[k];
-        const float a = fb.calpha ? (t < ncls ? fb.calpha[t] : 0.f) : 1.f;
+        const float a = t < ncls ? (fb.calpha ? fb.calpha[t] : 1.f) : 0.f;                   // a label >= ncls: no focal gradient
         const float c = -focal_mod(pt, fb.gamma) * a * fb.gscale;
 #pragma unroll
         for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls)
@@ -894,19 +894,21 @@ __global__ void focal_kernel(const float* __restrict__ logits, const uint8_t* __
 #pragma unroll
         for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls) den += expf(l[k] - m);
         const int t = labels[p];
-        const float lse = m + logf(den);
-        float lt = 0.f;
+        // log-softmax on the maximum-subtracted logits, (l - m) - log(den): forming lse = m + log(den) first rounds log(den) to an ulp of m
+        // and makes the loss depend on a common shift of the logits (1e-3 at |l| ~ 8192)
+        const float logden = logf(den);
+        float ltm = 0.f;
 #pragma unroll
-        for (int k = 0; k < OUTC_MAXCLS; k++) if (k == t) lt = l[k];
-        const float logpt = lt - lse, pt = expf(logpt);
-        const float a = alpha ? alpha[t] : 1.f;
+        for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls && k == t) ltm = l[k] - m;      // (l[k] is not loaded for k >= ncls)
+        const float logpt = ltm - logden, pt = expf(logpt);
+        const float a = t < ncls ? (alpha ? alpha[t] : 1.f) : 0.f;     // a label >= ncls has no true class: term and gradient are 0, alpha is not indexed
         const float mod = gamma == 0.f ? 1.f : powf(fmaxf(1.f - pt, 0.f), gamma);
         acc += (double)(-mod * a * logpt);
         if (dlogits) {
             const float c = -mod * a * gscale;
 #pragma unroll
             for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls)
-                dlogits[(b * ncls + k) * hw + q] = c * ((k == t ? 1.f : 0.f) - expf(l[k] - lse));
+                dlogits[(b * ncls + k) * hw + q] = c * ((k == t ? 1.f : 0.f) - expf((l[k] - m) - logden));
         }
         c_tp += (am == 1 && t == 1); c_fp += (am == 1 && t != 1); c_fn += (am != 1 && t == 1); c_ok += (am == t);
     }

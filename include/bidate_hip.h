@@ -164,7 +164,11 @@ int bdn_conv3d_wgrad(int dtype, const void* dz, int Cout, const void* in, int C,
  * src1 may be NULL) with relu(bn(.)) applied to src0 when in_mode == BDN_IN_BNRELU (models/unet_parts.py:14-15,78).
  * With BDN_BF16X3: bdn_conv3x3 takes in0 = that tensor, C0 = the logical channel count, in1 = NULL, in_mode PLAIN, w from
  * bdn_pack_weights(BDN_BF16X3) (wf: [Cout][9][3 Cin_pad] bf16, wd: [Cin_pad][9][3 Cout]), and writes float32 out / statistics;
- * bdn_conv3x3_wgrad* take dz and in0 both split-packed and write the float32 OIHW gradient. */
+ * bdn_conv3x3_wgrad* take dz and in0 both split-packed and write the float32 OIHW gradient.
+ * Rounding: hi and lo are round-to-nearest-even conversions (ties to the even bf16 mantissa, carries into the next binade included);
+ * float32 subnormals are NOT flushed -- they convert to bf16 subnormals and x - hi is formed with subnormals kept -- and the sign of a
+ * zero survives: the output equals torch's CPU conversion bit for bit on every finite input (tests/test_gpu_conditioning.py, E).  The
+ * same holds for bdn_pack_input and bdn_pack_weights.  With BDN_IN_BNRELU an input that is off is stored as +0.0. */
 int bdn_split_pack(const float* src0, int C0, const float* src1, int C1, int in_mode, const float* in_bn,
                    int imgs_per_group, void* out, int N, int H, int W, void* stream);
 
@@ -229,7 +233,15 @@ int bdn_conv3x3_dgrad_first(int dtype, const void* dA, int ldA, const void* z, c
  * bn[g][0..3][c] = {mean, invstd, scale = gamma*invstd, shift = beta - mean*scale}  (layout [G][4][C]),
  * then updates running_mean/var (momentum 0.1, unbiased variance) once per group in order g=0,1,..
  * and adds G to num_batches_tracked -- the reference calls the module once per date.
- * ws: scratch of bdn_bn_finalize_workspace_bytes() (double partial sums of the two-stage reduction). */
+ * ws: scratch of bdn_bn_finalize_workspace_bytes() (double partial sums of the two-stage reduction).
+ * Limit of the one-pass statistic.  The partials are per-tile float32 sums of z and z*z (bdn_conv3x3: stats_partial); they are added
+ * in double and var = s1/count - mean^2, clamped at 0, so invstd <= 1/sqrt(eps) and a constant channel gives invstd = 1/sqrt(eps) or
+ * whatever the rounding of its sum of squares leaves above 0.  The subtraction loses (mean/std)^2 of the float32 sums' precision:
+ * error of the normalised output about 3e-6 of its magnitude at |mean|/std = 4, 4e-5 at 16, 8e-4 at 64, 1.5e-2 at 256 (measured; DESIGN.md
+ * 12), where torch.native_batch_norm in float32 stays below 1.3e-5.  The reference network stays below |mean|/std = 4.1 in every layer; the suite
+ * requires the float32 bar (5e-5) up to twice that.  The raw-moment backward half (bdn_bn_bwd_apply, raw_moment = 1: sum g*z converted
+ * to sum g*xhat; bdn_conv3x3_dgrad_bb: dz = a g + b z + c) cancels in the same way but only linearly in mean/std: dgamma is off by
+ * 2e-5 of its magnitude at 256 and dz stays at its storage rounding. */
 size_t bdn_bn_finalize_workspace_bytes(int n_mtiles, int G, int C);
 int bdn_bn_finalize(const float* stats_partial, int n_mtiles, int G, int C, int count_per_group,
                     const float* gamma, const float* beta, float eps, float momentum,
@@ -403,7 +415,11 @@ int bdn_outc_bwd_rows(int dtype, int B, int H, int W, int C);
  * labels: uint8 [B,H,W].  ws: bdn_overlap_workspace_bytes(B, ncls, H, W, 0) bytes of f32 scratch (16-byte aligned): the
  * blocks' partial sums are added in a fixed order, no float atomics -- loss and dlogits are the same bits on every run.
  * loss: f32 scalar.  counts: NULL or int32[4] = {TP, FP, FN, correct} of argmax(logits) vs labels
- * (class 1 positive; train.py:96-106).  dlogits: NULL or [B,ncls,H,W] = d loss / d logits. */
+ * (class 1 positive, first maximum wins; train.py:96-106).  dlogits: NULL or [B,ncls,H,W] = d loss / d logits.
+ * Labels outside the classes (label >= ncls, e.g. the 255 of a {0, 255} mask; the reference raises on them): such a pixel has no true
+ * class.  In every loss entry point (bdn_tversky, bdn_overlap_loss, bdn_focal, bdn_criterion) its probabilities add to FP of every
+ * class and to nothing else; its focal term and focal gradient are exactly 0 while it still counts in the size_average denominator; it
+ * is never a correct prediction in `counts` (it is an FP when class 1 is predicted); the class weights are never indexed with it. */
 size_t bdn_overlap_workspace_bytes(int B, int ncls, int H, int W, int reduce_w);
 int bdn_tversky(const float* logits, const uint8_t* labels, float alpha, float beta, float eps,
                 float* ws, float* loss, int32_t* counts, float* dlogits,
@@ -423,6 +439,8 @@ int bdn_overlap_loss(const float* logits, const uint8_t* labels, float alpha, fl
 /* ---- FocalLoss(gamma, alpha, size_average).forward, utils/metrics.py:8-48 (criterion 'focal', utils/helpers.py:305) ----
  * labels uint8 [B,H,W] (or [B,1,H,W], same memory).  alpha: NULL or f32[ncls] class weights (device).
  * The modulating factor (1-pt)^gamma is a constant for the gradient exactly as in the reference (:35).
+ * log pt is formed on the maximum-subtracted logits, (l_t - max) - log sum exp(l - max): loss and gradient do not depend on a common
+ * shift of the logits.  A label >= ncls: term and gradient 0, alpha not read (bdn_tversky, "labels outside the classes").
  * ws: bdn_focal_workspace_bytes() bytes.  loss, counts, dlogits as bdn_tversky. */
 size_t bdn_focal_workspace_bytes(void);
 int bdn_focal(const float* logits, const uint8_t* labels, float gamma, const float* alpha, int size_average,
