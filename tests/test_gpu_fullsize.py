@@ -5,7 +5,9 @@ gradients, the fused first / last layer paths, the side stream):
 
 * backward is LINEAR in dlogits, and scaling by a power of two is exact in bf16 and f32: grads(4 * dlogits) == 4 * grads(dlogits)
   bit for bit, for every parameter the deterministic kernels produce;
-* two identical runs of three steps give the same bits (fixed-order reductions everywhere, no races between the two streams);
+* two identical runs of three steps give the same bits: determinism (fixed-order reductions everywhere).  Both runs have the same natural
+  timing, so this says nothing about races between the two streams -- a missing wait that the timing happens to hide passes both runs
+  identically; tests/test_gpu_sched_stress.py moves the timing and is the test for that;
 * swapping the dates leaves the train-mode logits unchanged (shared encoder, commutative fusion, per-date BatchNorm groups);
 * eval-mode images are independent: the batch of 64 equals its two halves run separately;
 * SGD on a fixed batch lowers the Tversky loss, and the gradients are finite and non-trivial everywhere.
