@@ -20,6 +20,7 @@ def wg_flags(phases=3, kernel=0, blocks=0):
     return phases | (kernel << 8) | (blocks << 16)
 
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
+_hf = C.POINTER(C.c_float)          # a HOST float array (floats() below), where a void* would be taken for a device pointer
 
 # name -> (restype, argtypes); mirrors include/bidate_hip.h one to one
 SIGNATURES = {
@@ -112,6 +113,13 @@ SIGNATURES = {
     'bdn_sgd_step_grouped': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _f, _sz, _vp]),
     'bdn_sgd_momentum_step_grouped': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _f, _f, _f, _i, _i, _sz, _vp]),
     'bdn_adam_step_grouped': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _f, C.c_double, C.c_double, _f, _i, _i64, _sz, _vp]),
+    'bdn_sgd_step_grouped_ex': (_i, [_vp, _vp, _vp, _vp, _i, _i, _hf, _f, _vp, _sz, _vp]),
+    'bdn_sgd_momentum_step_grouped_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _hf, _hf, _f, _vp, _f, _f, _i, _i, _sz, _vp]),
+    'bdn_adam_step_grouped_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _hf, _hf, _f, _vp, C.c_double, C.c_double, _f, _i, _i64, _sz,
+                                      _vp]),
+    'bdn_grad_accumulate': (_i, [_vp, _vp, _sz, _i, _vp]),
+    'bdn_grad_norm_workspace_bytes': (_sz, [_sz]),
+    'bdn_grad_norm': (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp, _sz, _vp]),
 }
 
 

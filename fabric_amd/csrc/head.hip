@@ -1202,18 +1202,21 @@ template <typename P> struct GroupArgs { P g[OPT_MAX_GROUPS]; };
 struct RuleSgd {                                        // plain SGD: bdn_sgd_step's p -= (lr * grad_scale) * g
     using Params = float;
     static constexpr int NS = 0;
+    static __device__ __forceinline__ void scale(Params& step, float s) { step *= s; }
     static __device__ __forceinline__ bool reads_state(const Params&) { return false; }
     static __device__ __forceinline__ void elem(float& p, float g, float&, float&, const Params& step) { p -= step * g; }
 };
 template <bool MOM> struct RuleSgdm {
     using Params = SgdmParams;
     static constexpr int NS = MOM ? 1 : 0;
+    static __device__ __forceinline__ void scale(Params& a, float s) { a.grad_scale *= s; }
     static __device__ __forceinline__ bool reads_state(const Params& a) { return MOM && !a.first; }
     static __device__ __forceinline__ void elem(float& p, float g, float& buf, float&, const Params& a) { sgdm_elem<MOM>(p, g, buf, a); }
 };
 struct RuleAdam {
     using Params = AdamParams;
     static constexpr int NS = 2;
+    static __device__ __forceinline__ void scale(Params& a, float s) { a.grad_scale *= s; }
     static __device__ __forceinline__ bool reads_state(const Params&) { return true; }
     static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v, const Params& a) { adam_elem(p, g, m, v, a); }
 };
@@ -1226,7 +1229,8 @@ __device__ __forceinline__ void seg_step(const uint32_t* s_end, int h, uint32_t 
 
 template <typename Rule>
 __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
-                                                      float* __restrict__ s1, SegTable t, GroupArgs<typename Rule::Params> a, size_t n4) {
+                                                      float* __restrict__ s1, SegTable t, GroupArgs<typename Rule::Params> a,
+                                                      const float* __restrict__ dev_scale, size_t n4) {
     __shared__ uint32_t s_end[OPT_MAX_SEGS];
     __shared__ int s_grp[OPT_MAX_SEGS];
     __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
@@ -1239,6 +1243,11 @@ __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, con
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < OPT_MAX_GROUPS; k++) s_par[k] = a.g[k];
+        if (dev_scale) {                                     // the _ex entry points: grad_scale * *dev_scale, formed once per block
+            const float ds = *dev_scale;
+#pragma unroll
+            for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
+        }
     }
     __syncthreads();
     const size_t stride = (size_t)gridDim.x * 256;
@@ -1304,30 +1313,46 @@ static int grouped_check(const char* what, const void* params, const void* grads
     return BDN_OK;
 }
 
-extern "C" int bdn_sgd_step_grouped(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg,
-                                    int n_groups, const float* lr, float grad_scale, size_t n, void* stream) {
-    if (int rc = grouped_check("sgd_step_grouped", params, grads, nullptr, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+// The grouped entry points and their _ex forms share one launcher each: dev_scale == nullptr is the plain form (the kernel then never
+// touches the staged parameters, so its bits are those it always gave), a device pointer the _ex form.
+static int ex_check(const char* what, const float* dev_scale) {
+    if (!dev_scale) BDN_FAIL(BDN_E_ARG, "%s: null pointer (dev_scale)", what);
+    if ((uintptr_t)dev_scale & 3) BDN_FAIL(BDN_E_ARG, "%s: dev_scale must be 4-byte aligned", what);
+    return BDN_OK;
+}
+
+static int sgd_grouped_launch(const char* what, float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group,
+                              int n_seg, int n_groups, const float* lr, float grad_scale, const float* dev_scale, size_t n, void* stream) {
+    if (int rc = grouped_check(what, params, grads, nullptr, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
     if (n == 0) return BDN_OK;
     GroupArgs<float> a{};
     for (int k = 0; k < n_groups; k++) a.g[k] = lr[k] * grad_scale;
     const SegTable t{seg_end, seg_group, n_seg, n_groups};
     hipLaunchKernelGGL(grouped_kernel<RuleSgd>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads, (float*)nullptr,
-                       (float*)nullptr, t, a, n / 4);
-    BDN_CHECK_LAUNCH("sgd_step_grouped");
+                       (float*)nullptr, t, a, dev_scale, n / 4);
+    BDN_CHECK_LAUNCH(what);
     return BDN_OK;
 }
 
-extern "C" int bdn_sgd_momentum_step_grouped(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
-                                             const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
-                                             float grad_scale, float momentum, float dampening, int nesterov, int first_step, size_t n,
-                                             void* stream) {
-    if (int rc = grouped_check("sgd_momentum_step_grouped", params, grads, momentum_buf, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n))
-        return rc;
-    if (!weight_decay) BDN_FAIL(BDN_E_ARG, "sgd_momentum_step_grouped: null pointer");
-    if ((momentum != 0.f) != (momentum_buf != nullptr))
-        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step_grouped: momentum_buf must be given iff momentum != 0");
-    if (nesterov && (momentum <= 0.f || dampening != 0.f))
-        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step_grouped: nesterov needs momentum > 0 and zero dampening");
+extern "C" int bdn_sgd_step_grouped(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg,
+                                    int n_groups, const float* lr, float grad_scale, size_t n, void* stream) {
+    return sgd_grouped_launch("sgd_step_grouped", params, grads, seg_end, seg_group, n_seg, n_groups, lr, grad_scale, nullptr, n, stream);
+}
+
+extern "C" int bdn_sgd_step_grouped_ex(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg,
+                                       int n_groups, const float* lr, float grad_scale, const float* dev_scale, size_t n, void* stream) {
+    if (int rc = ex_check("sgd_step_grouped_ex", dev_scale)) return rc;
+    return sgd_grouped_launch("sgd_step_grouped_ex", params, grads, seg_end, seg_group, n_seg, n_groups, lr, grad_scale, dev_scale, n, stream);
+}
+
+static int sgdm_grouped_launch(const char* what, float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                               const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                               float grad_scale, const float* dev_scale, float momentum, float dampening, int nesterov, int first_step,
+                               size_t n, void* stream) {
+    if (int rc = grouped_check(what, params, grads, momentum_buf, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+    if (!weight_decay) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if ((momentum != 0.f) != (momentum_buf != nullptr)) BDN_FAIL(BDN_E_ARG, "%s: momentum_buf must be given iff momentum != 0", what);
+    if (nesterov && (momentum <= 0.f || dampening != 0.f)) BDN_FAIL(BDN_E_ARG, "%s: nesterov needs momentum > 0 and zero dampening", what);
     if (n == 0) return BDN_OK;
     GroupArgs<SgdmParams> a{};
     for (int k = 0; k < n_groups; k++)
@@ -1336,23 +1361,39 @@ extern "C" int bdn_sgd_momentum_step_grouped(float* params, const float* grads, 
     const SegTable t{seg_end, seg_group, n_seg, n_groups};
     if (momentum_buf)
         hipLaunchKernelGGL(grouped_kernel<RuleSgdm<true>>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads,
-                           momentum_buf, (float*)nullptr, t, a, n / 4);
+                           momentum_buf, (float*)nullptr, t, a, dev_scale, n / 4);
     else
         hipLaunchKernelGGL(grouped_kernel<RuleSgdm<false>>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads,
-                           (float*)nullptr, (float*)nullptr, t, a, n / 4);
-    BDN_CHECK_LAUNCH("sgd_momentum_step_grouped");
+                           (float*)nullptr, (float*)nullptr, t, a, dev_scale, n / 4);
+    BDN_CHECK_LAUNCH(what);
     return BDN_OK;
 }
 
-extern "C" int bdn_adam_step_grouped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
-                                     const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
-                                     float grad_scale, double beta1, double beta2, float eps, int decoupled_weight_decay, long long step,
-                                     size_t n, void* stream) {
-    if (int rc = grouped_check("adam_step_grouped", params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
-    if (!exp_avg || !exp_avg_sq || !weight_decay) BDN_FAIL(BDN_E_ARG, "adam_step_grouped: null pointer");
-    if (step < 1) BDN_FAIL(BDN_E_ARG, "adam_step_grouped: step must be >= 1 (1-based, counted after the increment), got %lld", step);
-    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0))
-        BDN_FAIL(BDN_E_ARG, "adam_step_grouped: betas must lie in [0, 1)");
+extern "C" int bdn_sgd_momentum_step_grouped(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                                             const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                             float grad_scale, float momentum, float dampening, int nesterov, int first_step, size_t n,
+                                             void* stream) {
+    return sgdm_grouped_launch("sgd_momentum_step_grouped", params, grads, momentum_buf, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, nullptr, momentum, dampening, nesterov, first_step, n, stream);
+}
+
+extern "C" int bdn_sgd_momentum_step_grouped_ex(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                                                const int32_t* seg_group, int n_seg, int n_groups, const float* lr,
+                                                const float* weight_decay, float grad_scale, const float* dev_scale, float momentum,
+                                                float dampening, int nesterov, int first_step, size_t n, void* stream) {
+    if (int rc = ex_check("sgd_momentum_step_grouped_ex", dev_scale)) return rc;
+    return sgdm_grouped_launch("sgd_momentum_step_grouped_ex", params, grads, momentum_buf, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, dev_scale, momentum, dampening, nesterov, first_step, n, stream);
+}
+
+static int adam_grouped_launch(const char* what, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                               const uint32_t* seg_end, const int32_t* seg_group, int n_seg, int n_groups, const float* lr,
+                               const float* weight_decay, float grad_scale, const float* dev_scale, double beta1, double beta2, float eps,
+                               int decoupled_weight_decay, long long step, size_t n, void* stream) {
+    if (int rc = grouped_check(what, params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+    if (!exp_avg || !exp_avg_sq || !weight_decay) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (step < 1) BDN_FAIL(BDN_E_ARG, "%s: step must be >= 1 (1-based, counted after the increment), got %lld", what, step);
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) BDN_FAIL(BDN_E_ARG, "%s: betas must lie in [0, 1)", what);
     if (n == 0) return BDN_OK;
     // 1 - beta and the bias corrections in double on the host, exactly as bdn_adam_step forms them
     const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
@@ -1365,8 +1406,199 @@ extern "C" int bdn_adam_step_grouped(float* params, const float* grads, float* e
                             (float)std::sqrt(bc2), w1 >= 0.5f ? 1 : 0};
     const SegTable t{seg_end, seg_group, n_seg, n_groups};
     hipLaunchKernelGGL(grouped_kernel<RuleAdam>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                       exp_avg_sq, t, a, n / 4);
-    BDN_CHECK_LAUNCH("adam_step_grouped");
+                       exp_avg_sq, t, a, dev_scale, n / 4);
+    BDN_CHECK_LAUNCH(what);
+    return BDN_OK;
+}
+
+extern "C" int bdn_adam_step_grouped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
+                                     const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                     float grad_scale, double beta1, double beta2, float eps, int decoupled_weight_decay, long long step,
+                                     size_t n, void* stream) {
+    return adam_grouped_launch("adam_step_grouped", params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, nullptr, beta1, beta2, eps, decoupled_weight_decay, step, n, stream);
+}
+
+extern "C" int bdn_adam_step_grouped_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
+                                        const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                        float grad_scale, const float* dev_scale, double beta1, double beta2, float eps,
+                                        int decoupled_weight_decay, long long step, size_t n, void* stream) {
+    if (int rc = ex_check("adam_step_grouped_ex", dev_scale)) return rc;
+    return adam_grouped_launch("adam_step_grouped_ex", params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, dev_scale, beta1, beta2, eps, decoupled_weight_decay, step, n, stream);
+}
+
+// ============================================================ gradient accumulation and the global gradient norm (clip_grad_norm_)
+// Two memory-bound passes on the path between backward and the update, in the update kernels' shape (float4, OPT_VEC loads in flight).
+//
+// bdn_grad_accumulate: dst = src (add = 0) or dst = dst + src (add = 1), one IEEE float32 add per element; a micro-step's gradients go
+// into the accumulator, the last micro-step's come out of it, and no zero-fill is ever needed.
+//
+// bdn_grad_norm: out[0] = grad_scale * sqrt(sum g^2) over the vectors that count, out[1] = torch's clip coefficient of it.  Every float32
+// is converted to double before it is squared and everything is accumulated in double (a square neither overflows nor underflows; the
+// sum of 2^32 vectors errs by ~n 2^-53).  Stage 1: block b owns the NORM_CHUNK consecutive vectors [b NORM_CHUNK, (b + 1) NORM_CHUNK) --
+// the block count is a function of n alone -- each lane sums its vectors in index order, a wave64 butterfly (__shfl_xor, the same tree in
+// every wave) sums the lanes, thread 0 adds the four wave sums in wave order and writes ONE double.  Stage 2: one thread adds the partials
+// in index order (staged through LDS 1024 at a time) and forms norm and coefficient.  No atomics, no memset, the same bits on any device.
+// With a segment table (the update kernels') a vector of a frozen segment, or behind the table's end, is not read.
+__device__ __forceinline__ float4 add4(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// A pass whose OPT_VEC vectors are all in range issues its loads without a bounds test (named registers: hipcc moved a conditionally
+// loaded float4[OPT_VEC] of the copy form into LDS and waited for every load in turn); the last, partial pass goes vector by vector.
+template <bool ADD>
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n4, size_t n) {
+    static_assert(OPT_VEC == 4, "four loads in flight, written out");
+    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(dst);
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t base = (size_t)blockIdx.x * 256 + threadIdx.x; base < n4; base += stride * OPT_VEC) {
+        if (base + 3 * stride < n4) {
+            float4 a0 = s4[base], a1 = s4[base + stride], a2 = s4[base + 2 * stride], a3 = s4[base + 3 * stride];
+            if (ADD) {
+                const float4 c0 = d4[base], c1 = d4[base + stride], c2 = d4[base + 2 * stride], c3 = d4[base + 3 * stride];
+                a0 = add4(c0, a0); a1 = add4(c1, a1); a2 = add4(c2, a2); a3 = add4(c3, a3);
+            }
+            d4[base] = a0; d4[base + stride] = a1; d4[base + 2 * stride] = a2; d4[base + 3 * stride] = a3;
+        } else {
+            for (size_t i = base; i < n4; i += stride) {
+                float4 v = s4[i];
+                if (ADD) v = add4(d4[i], v);
+                d4[i] = v;
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {       // the n % 4 trailing elements
+        const size_t k = n4 * 4 + threadIdx.x;
+        dst[k] = ADD ? dst[k] + src[k] : src[k];
+    }
+}
+
+extern "C" int bdn_grad_accumulate(float* dst, const float* src, size_t n, int add, void* stream) {
+    if (!dst || !src) BDN_FAIL(BDN_E_ARG, "grad_accumulate: null pointer");
+    if (((uintptr_t)dst | (uintptr_t)src) & 15) BDN_FAIL(BDN_E_ARG, "grad_accumulate: buffers must be 16-byte aligned");
+    if (add != 0 && add != 1) BDN_FAIL(BDN_E_ARG, "grad_accumulate: add must be 0 or 1, got %d", add);
+    if (n == 0) return BDN_OK;
+    const size_t n4 = n / 4;
+    if (add) hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, dst, src, n4, n);
+    else hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, dst, src, n4, n);
+    BDN_CHECK_LAUNCH("grad_accumulate");
+    return BDN_OK;
+}
+
+constexpr int NORM_ROUNDS = 4;                                   // passes of OPT_VEC float4s per thread
+constexpr size_t NORM_CHUNK = (size_t)256 * OPT_VEC * NORM_ROUNDS;   // vectors per block and per partial: 4096 (64 KiB of gradients)
+
+static inline size_t norm_blocks(size_t n4) { return (n4 + NORM_CHUNK - 1) / NORM_CHUNK; }
+
+__device__ __forceinline__ double sq_acc(double acc, const float4& v) {
+    const double x = (double)v.x, y = (double)v.y, z = (double)v.z, w = (double)v.w;
+    acc = fma(x, x, acc); acc = fma(y, y, acc); acc = fma(z, z, acc); acc = fma(w, w, acc);
+    return acc;
+}
+
+__global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float* __restrict__ g, const uint32_t* __restrict__ seg_end,
+                                                                const int32_t* __restrict__ seg_group, int n_seg,
+                                                                double* __restrict__ part, size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS];
+    __shared__ double s_wave[4];
+    int cap = 1;
+    if (n_seg > 0) {
+        while (cap < n_seg) cap <<= 1;
+        for (int k = threadIdx.x; k < cap; k += 256) {
+            s_end[k] = k < n_seg ? seg_end[k] : 0xffffffffu;
+            s_grp[k] = k < n_seg ? seg_group[k] : OPT_FROZEN;
+        }
+        __syncthreads();
+    }
+    const size_t c0 = (size_t)blockIdx.x * NORM_CHUNK;
+    // A block's 4096 consecutive vectors almost always lie in one segment: one lookup of its first and of its last vector then serves the
+    // block (a frozen block reads nothing at all); a block that spans a boundary looks every vector up.  The sums are the same either way.
+    bool per_lane = false, whole = true;
+    if (n_seg > 0) {
+        const size_t last = (c0 + NORM_CHUNK < n4 ? c0 + NORM_CHUNK : n4) - 1;
+        int s_lo = 0, s_hi = 0;
+        for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)c0, s_lo); seg_step(s_end, h, (uint32_t)last, s_hi); }
+        per_lane = s_lo != s_hi;
+        whole = s_end[s_lo] > last && s_grp[s_lo] != OPT_FROZEN;
+    }
+    double acc = 0.0;
+    for (int r = 0; r < NORM_ROUNDS; r++) {
+        bool take[OPT_VEC];
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+            take[u] = i < n4 && (per_lane || whole);
+            if (take[u] && per_lane) {                       // first segment whose end lies behind i
+                int s = 0;
+                for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+                take[u] = s_end[s] > i && s_grp[s] != OPT_FROZEN;
+            }
+        }
+        float4 G[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+            if (take[u]) G[u] = reinterpret_cast<const float4*>(g)[i];
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) acc = sq_acc(acc, G[u]);           // a vector not taken adds +0.0: the sum is unchanged
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+__global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __restrict__ part, size_t nblk, float grad_scale, float max_norm,
+                                                               float* __restrict__ out) {
+    __shared__ double s_part[1024];
+    double sum = 0.0;
+    for (size_t b0 = 0; b0 < nblk; b0 += 1024) {
+        const size_t m = nblk - b0 < 1024 ? nblk - b0 : 1024;
+        for (size_t k = threadIdx.x; k < m; k += 256) s_part[k] = part[b0 + k];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (size_t k = 0; k < m; k++) sum += s_part[k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm32 = (float)((double)grad_scale * sqrt(sum));
+        // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1), the quotient as torch evaluates a Python float over a
+        // tensor (Tensor.__rtruediv__): reciprocal, then product
+        float coef = (1.0f / (norm32 + 1e-6f)) * max_norm;
+        if (coef > 1.0f) coef = 1.0f;                        // a comparison, not fminf: a NaN norm keeps its NaN coefficient
+        out[0] = norm32;
+        out[1] = coef;
+    }
+}
+
+extern "C" size_t bdn_grad_norm_workspace_bytes(size_t n) {
+    const size_t nb = norm_blocks(n / 4);
+    return ((nb ? nb : 1) * sizeof(double) + 15) / 16 * 16;
+}
+
+extern "C" int bdn_grad_norm(const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float grad_scale,
+                             float max_norm, void* workspace, float* out, size_t n, void* stream) {
+    if (!grads || !workspace || !out) BDN_FAIL(BDN_E_ARG, "grad_norm: null pointer");
+    if (n_seg < 0 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "grad_norm: %d segments (0..%d; 0: no table, every element counts)", n_seg, OPT_MAX_SEGS);
+    if (n_seg > 0 && (!seg_end || !seg_group)) BDN_FAIL(BDN_E_ARG, "grad_norm: null pointer (segment table of %d segments)", n_seg);
+    if ((uintptr_t)grads & 15) BDN_FAIL(BDN_E_ARG, "grad_norm: buffers must be 16-byte aligned");
+    if ((uintptr_t)workspace & 7) BDN_FAIL(BDN_E_ARG, "grad_norm: workspace must be 8-byte aligned");
+    if ((uintptr_t)out & 3) BDN_FAIL(BDN_E_ARG, "grad_norm: out must be 4-byte aligned");
+    if (n_seg > 0 && (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3)) BDN_FAIL(BDN_E_ARG, "grad_norm: segment table must be 4-byte aligned");
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "grad_norm: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", n);
+    if (!(max_norm >= 0.f)) BDN_FAIL(BDN_E_ARG, "grad_norm: max_norm = %g must be >= 0 (+inf: measure only)", (double)max_norm);
+    const size_t n4 = n / 4, nblk = norm_blocks(n4);
+    if (nblk) {
+        hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, grads, seg_end, seg_group, n_seg,
+                           (double*)workspace, n4);
+        BDN_CHECK_LAUNCH("grad_norm");
+    }
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, nblk, grad_scale, max_norm, out);
+    BDN_CHECK_LAUNCH("grad_norm_finish");
     return BDN_OK;
 }
 

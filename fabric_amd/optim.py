@@ -94,6 +94,22 @@ class OptimConfig:
         return 'OptimConfig(' + ', '.join(f'{k}={v!r}' for k, v in vars(self).items()) + ')'
 
 
+def check_accumulate(k):
+    """The fused step's `accumulate`: an int >= 1 (bool is refused: it is an int to Python only)."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f'invalid accumulate: {k!r} (must be an integer >= 1)')
+    return k
+
+
+def check_max_grad_norm(x):
+    """The fused step's `max_grad_norm`: None (no clipping, nothing measured), a number > 0, or float('inf') (measure only)."""
+    if x is None:
+        return None
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or math.isnan(x) or x <= 0:
+        raise ValueError(f"invalid max_grad_norm: {x!r} (must be a number > 0, float('inf') to measure without clipping, or None)")
+    return float(x)
+
+
 def flat_to_torch(cfg, layout, names, flat_state, step):
     """torch.optim's ``state_dict()`` of the flat state: ``flat_state`` maps cfg.state_keys() to flat buffers in ``layout``, ``names``
     lists the parameter names in ``model.parameters()`` order, ``step`` is the number of updates applied.  Every tensor is a copy.

@@ -78,12 +78,16 @@ class GradBucketer:
     BatchNorm) -- they sit at the tail of the layout and are never communicated."""
 
     def __init__(self, layout, flat_grads, n_buckets=4, group=None, keys_no_reduce=(), enabled=True, tail_bytes=1 << 20,
-                 force=False):
-        """n_buckets equal slices by bytes, plus one more cut in front of the last `tail_bytes` of gradients: the final
+                 force=False, before_reduce=None):
+        """before_reduce: None, or a callable (a, b) invoked once per bucket on the current stream immediately before the all-reduce of
+        flat_grads[a:b] is issued, from on_ready and from finish alike (gradient accumulation adds the pending sum there).
+
+        n_buckets equal slices by bytes, plus one more cut in front of the last `tail_bytes` of gradients: the final
         bucket cannot start before the very last weight gradient of backward exists, so its all-reduce is the one piece of
         communication nothing can hide -- in BiDateNet the last megabyte is the four shallow encoder convs, while an equal
         quarter (13 MB) would also have held back three deep layers that were ready a millisecond earlier."""
         self.layout, self.flat, self.group = layout, flat_grads, group
+        self.before_reduce = before_reduce
         self.enabled = enabled                      # False: purely local step even inside an initialised process group
         self.force = force                          # True: issue the bucket all-reduces even in a world of one rank (a way to run the
                                                     # RCCL launches, their stream ordering and their cost on a single GPU)
@@ -150,17 +154,21 @@ class GradBucketer:
                 continue
             self.pending[i].discard(k)
             if not self.pending[i] and not self.launched[i]:
-                a, b, _ = self.buckets[i]
-                self.works.append(dist.all_reduce(self.flat[a:b], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
-                self.launched[i] = True
+                self._reduce(i)
+
+    def _reduce(self, i):
+        a, b, _ = self.buckets[i]
+        if self.before_reduce is not None:
+            self.before_reduce(a, b)
+        self.works.append(dist.all_reduce(self.flat[a:b], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+        self.launched[i] = True
 
     def finish(self):
         """Launch whatever is left and make the current stream wait for every bucket."""
         if self.active():
-            for i, (a, b, _) in enumerate(self.buckets):
+            for i in range(len(self.buckets)):
                 if not self.launched[i]:
-                    self.works.append(dist.all_reduce(self.flat[a:b], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
-                    self.launched[i] = True
+                    self._reduce(i)
             for w in self.works:
                 w.wait()
         self.reset()

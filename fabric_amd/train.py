@@ -7,6 +7,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --metadata metadata.json --dataset_dir ./onera/          # an OSCD directory tree
     python -m fabric_amd.train --synthetic --epochs 4 --optimizer adamw --resume ./log/checkpoint_epoch_1.state_dict.pt
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --freeze inc --optimizer adamw
+    python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --accumulate 4 --max_grad_norm 1.0
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
 predicted tile by tile (utils/inference.py) -- here on the device-resident city stacks -- and written as PNG masks.
@@ -108,19 +109,28 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
     from .device_loader import DevicePatchLoader
     from .input_pipeline import DeviceFeeder
     step.model.train()
-    recs = []
+    recs, norms = [], []
+    clip = step.max_grad_norm is not None
     if not isinstance(loader, DevicePatchLoader):
         feeder = feeder or DeviceFeeder(dev)
     with torch.cuda.stream(step.stream()):                # the loop lives on the step's own stream: no joins per step
         for b1, b2, labels in _device_batches(loader, dev, feeder):
             loss = step.step(b1, b2, labels)
             recs.append((loss, step.last_counts.clone(), labels.shape[0]))
+            if clip and step.micro == 0:                  # this call ended with an update
+                norms.append((step.last_grad_norm.clone(), step.last_clip_coef.clone()))
+        if step.flush() and clip:                         # --accumulate: the batches left over at the end of the epoch
+            norms.append((step.last_grad_norm.clone(), step.last_clip_coef.clone()))
     torch.cuda.current_stream(dev).wait_stream(step.stream())
     metrics = initialize_metrics()
     for loss, counts, n in recs:
         c = counts.cpu()
         metrics = set_metrics(metrics, loss.item(), 100.0 * int(c[3]) / (n * patch_size ** 2), batch_prf_from_counts(c))
-    return get_mean_metrics(metrics) if recs else {}
+    out = get_mean_metrics(metrics) if recs else {}
+    if norms:                                             # --max_grad_norm: read back once per epoch, beside the losses
+        nc = torch.stack([torch.stack(v) for v in norms]).cpu()
+        out.update(grad_norm_mean=float(nc[:, 0].mean()), grad_norm_max=float(nc[:, 0].max()), clipped_frac=float((nc[:, 1] < 1).float().mean()))
+    return out
 
 
 @torch.no_grad()
@@ -305,6 +315,10 @@ def main(argv=None):
     ap.add_argument('--weight_decay', type=float, default=None, help="default: torch's (0 for sgd and adam, 1e-2 for adamw)")
     ap.add_argument('--betas', type=float, nargs=2, default=[0.9, 0.999], help='adam / adamw')
     ap.add_argument('--adam_eps', type=float, default=1e-8, help='adam / adamw')
+    ap.add_argument('--accumulate', type=int, default=1, metavar='K',
+                    help='fused step: update on every K-th batch with the mean gradient of the K batches (one gradient exchange per update)')
+    ap.add_argument('--max_grad_norm', type=float, default=None, metavar='X',
+                    help='fused step: clip the gradients to a global L2 norm of X (torch.nn.utils.clip_grad_norm_); inf: measure only')
     ap.add_argument('--resume', default=None, help='DIR/checkpoint_epoch_N.state_dict.pt (and its sibling optimizer_epoch_N.pt): '
                                                    'continue at epoch N + 1 of --epochs')
     ap.add_argument('--init_from', default=None, help='a checkpoint load_checkpoint reads (the reference\'s pickles and module.-prefixed '
@@ -361,6 +375,15 @@ def main(argv=None):
     if grouped and opt.loss_function != 'tversky' and not opt.fused_step:
         raise SystemExit(f'--freeze / --frozen_bn / --no_decay_norm_bias / --lr_scale are built into the fused step, which runs '
                          f'--loss_function tversky only (got {opt.loss_function}) unless --fused_step true is given')
+    from .optim import check_accumulate, check_max_grad_norm
+    try:
+        check_accumulate(opt.accumulate)
+        check_max_grad_norm(opt.max_grad_norm)
+    except ValueError as e:
+        raise SystemExit(f'--accumulate / --max_grad_norm: {e}')
+    if (opt.accumulate != 1 or opt.max_grad_norm is not None) and opt.loss_function != 'tversky' and not opt.fused_step:
+        raise SystemExit(f'--accumulate / --max_grad_norm are built into the fused step, which runs --loss_function tversky only '
+                         f'(got {opt.loss_function}) unless --fused_step true is given')
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
 
@@ -421,7 +444,7 @@ def main(argv=None):
             groups = fine_tune_groups(model, opt.learning_rate, opt.weight_decay, opt.freeze, opt.no_decay_norm_bias, opt.lr_scale)
             step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta,
                              param_groups=groups, bn='frozen' if opt.frozen_bn else 'batch', criterion=step_criterion,
-                             **optimizer_kwargs(opt))
+                             accumulate=opt.accumulate, max_grad_norm=opt.max_grad_norm, **optimizer_kwargs(opt))
         except ValueError as e:
             raise SystemExit(f'parameter groups: {e}')
         if opt_sd is not None:

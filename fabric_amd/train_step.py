@@ -23,7 +23,7 @@ class TrainStep:
     def __init__(self, model, lr=1e-3, tversky_alpha=0.1, tversky_beta=0.9, eps=1e-7,
                  process_group=None, n_buckets=4, distributed=True, force_collectives=False, guard=True,
                  optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8,
-                 param_groups=None, bn='batch', criterion=None):
+                 param_groups=None, bn='batch', criterion=None, accumulate=1, max_grad_norm=None):
         """optimizer: 'sgd' (torch.optim.SGD: momentum, dampening, nesterov, weight_decay), 'adam' or 'adamw' (torch.optim.Adam / AdamW:
         betas, adam_eps, weight_decay); weight_decay=None is torch's default (0 for sgd and adam, 1e-2 for adamw).  The default, plain
         SGD, is the reference's optim.SGD(lr) (train.py:55) and keeps no state; the other rules keep theirs in flat f32 buffers in the
@@ -49,11 +49,31 @@ class TrainStep:
         front of a BatchNorm have real gradients, which are then reduced across ranks like every other).  The module's .training flag
         is not consulted.
 
+        accumulate: K >= 1.  Every step() is a micro-step (forward, loss, backward; BatchNorm running statistics update as in torch; the
+        micro-batch's own unscaled loss is returned); the update runs on every K-th call with the MEAN of the K micro-batch gradients
+        (grad_scale = 1 / (world * K)).  `micro` counts the pending micro-steps (0..K-1), `opt_step` counts updates.  The sum is kept in
+        one flat float32 buffer in the gradient layout, `flat_accum`, in a fixed order: micro-step 1 acc = g1; micro-steps 2..K-1
+        acc += g; micro-step K flat_grads = gK + acc (bdn_grad_accumulate, one float32 add per element each).  Micro-steps 1..K-1 issue
+        no collective and leave the engine's packed weights valid; on micro-step K the pending sum is added bucket by bucket right before
+        each bucket's all-reduce (GradBucketer.before_reduce), so there is one exchange per UPDATE and it still overlaps backward.
+        flush() applies (or drops) an incomplete accumulation, e.g. at the end of an epoch.
+
+        max_grad_norm: None, x > 0, or float('inf') (measure only).  torch.nn.utils.clip_grad_norm_(parameters, x) between backward and
+        the update: bdn_grad_norm leaves the norm of the averaged gradients of the trainable parameters and the clip coefficient in a
+        persistent device buffer (`last_grad_norm`, `last_clip_coef`: 0-dim views that the next update overwrites; clone them to keep
+        them), and the update reads the coefficient from there (bdn_*_step_grouped_ex): no host synchronisation, no pass that rescales
+        the gradients.  flat_grads, and with it p.grad, therefore keeps the UNCLIPPED (and unaveraged) sum.
+
         guard: when the step issues collectives (world > 1, or force_collectives) and guard_collectives() has not been called, the
         first step() runs it in its measure-only form (replace_streams=False: it may defer the buckets, it never swaps a stream the
         caller may already have adopted) and reports / warns about a stream arrangement in which they slow the step down."""
         if bn not in ('batch', 'frozen'):
             raise ValueError(f"bn must be 'batch' or 'frozen', got {bn!r}")
+        self.accumulate = _optim.check_accumulate(accumulate)
+        self.max_grad_norm = _optim.check_max_grad_norm(max_grad_norm)
+        self.micro = 0
+        self.flat_accum = self._norm = self._clip_table = None
+        self.last_grad_norm = self.last_clip_coef = None
         self.model, self.lr, self.bn = model, lr, bn
         self.optim = _optim.OptimConfig(optimizer, lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
                                         weight_decay=weight_decay, betas=betas, eps=adam_eps)
@@ -103,6 +123,33 @@ class TrainStep:
         self._implicit_group = False
         if param_groups is not None or any(not p.requires_grad for _, p in named):
             self.set_param_groups(param_groups)
+        if self.accumulate > 1:
+            self.flat_accum = torch.empty_like(self.flat_grads)             # written (add = 0) before it is ever read: no zero-fill
+            self.bucketer.before_reduce = self._add_pending
+        self._adding = False
+        if self.max_grad_norm is not None:
+            ws = torch.empty(_lib.load().bdn_grad_norm_workspace_bytes(self.layout.total) // 8, dtype=torch.float64, device=dev)
+            out = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._norm = (ws, out)
+            self.last_grad_norm, self.last_clip_coef = out[0], out[1]
+            if self._groups is None:
+                self._implicit_table()                       # uploaded now: the step itself never waits for the device
+
+    def _implicit_table(self):
+        """The clipped update runs the grouped (_ex) entry points; without groups or frozen parameters, on one implicit group of every
+        parameter.  Built when the step is, unless groups or frozen parameters give it a table already; after a set_param_groups(None) that
+        returns to no groups, at the next update.  The group's lr and weight_decay follow the step's at every update."""
+        if self._clip_table is None:
+            dev = self.flat_params.device
+            pg = _optim.ParamGroups(self.optim, self._names, None, ())
+            ends, ids = _optim.segment_table(self.layout, pg)
+            self._clip_table = (pg, (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev),
+                                     torch.tensor(ids, dtype=torch.int32).to(dev), len(ends)))
+        return self._clip_table
+
+    def _no_pending(self, what):
+        if self.micro != 0:
+            raise RuntimeError(f'{what}: {self.micro} of {self.accumulate} micro-steps are pending; call flush() (or flush(apply=False)) first')
 
     def set_param_groups(self, groups):
         """Install parameter groups (the constructor's `param_groups`) and re-read every parameter's requires_grad flag: rebuilds and
@@ -110,6 +157,7 @@ class TrainStep:
         and weight_decay (`step.lr` keeps driving it); with nothing frozen either, the step returns to the ungrouped kernels.  The
         optimizer state of parameters that stay trainable is kept; that of a parameter frozen now is zeroed, so it starts afresh if it
         is released later (with the step's one update count).  Raises ValueError as fabric_amd.optim.ParamGroups does."""
+        self._no_pending('set_param_groups()')
         dev = self.flat_params.device
         pg = self._checked_groups(groups)
         hp, cur = self.stream(dev), torch.cuda.current_stream(dev)
@@ -170,10 +218,42 @@ class TrainStep:
         with torch.cuda.stream(self._hp):
             loss = self._step(x_d1, x_d2, labels)
         cur.wait_stream(self._hp)
-        for t in (loss, self.last_logits, self.last_counts, self.last_terms, self.last_dlogits):
+        for t in (loss, self.last_logits, self.last_counts, self.last_terms, self.last_dlogits, self.last_grad_norm):
             if t is not None:
-                t.record_stream(cur)
+                t.record_stream(cur)                          # (last_clip_coef shares last_grad_norm's buffer)
         return loss
+
+    def flush(self, apply=True):
+        """End an incomplete accumulation.  With m = `micro` > 0 pending micro-steps and apply=True: flat_grads = the pending sum, one
+        set of bucket all-reduces, the norm if clipping is on, and the update with the mean of the m gradients (grad_scale =
+        1 / (world * m)); returns True.  apply=False drops the pending gradients (returns False).  With nothing pending nothing is
+        launched and False is returned.  Every rank must call it alike (it issues collectives)."""
+        m = self.micro
+        if m == 0:
+            return False
+        if not apply:
+            self.micro = 0
+            return False
+        dev = self.flat_params.device
+
+        def run():
+            st = _lib.stream_ptr()
+            _lib.call('bdn_grad_accumulate', self.flat_grads.data_ptr(), self.flat_accum.data_ptr(), self.layout.total, 0, st)
+            self.micro = 0
+            self.bucketer.finish()
+            self._apply(st, 1.0 / (self.world * m))
+            self.model.engine().invalidate_weights()
+        cur, hp = torch.cuda.current_stream(dev), self.stream(dev)
+        if not self.high_priority_chain or cur.cuda_stream == hp.cuda_stream:
+            run()
+            return True
+        hp.wait_stream(cur)
+        with torch.cuda.stream(hp):
+            run()
+        cur.wait_stream(hp)
+        if self.last_grad_norm is not None:
+            self.last_grad_norm.record_stream(cur)
+        return True
 
     def stream(self, device=None):
         """The high-priority stream the step's chain runs on: the process-wide 'chain' stream of the device (fabric_amd/streams.py;
@@ -256,7 +336,7 @@ class TrainStep:
         self.collectives_report = {'running': True}                     # re-entrancy: _step below must not call the guard again
         ok = False
         eng = self.model.engine()
-        saved = saved_flat = saved_opt = None
+        saved = saved_flat = saved_opt = saved_acc = None
         tried = []
         from . import streams as _streams
         orig_streams = (_streams.get('chain', dev), _streams.get('wgrad', dev))     # put back if a measurement raises half-way
@@ -269,6 +349,10 @@ class TrainStep:
             saved = {k: v.clone() for k, v in self._P.items()}
             saved_flat = self.flat_params.clone()
             saved_opt = ({k: v.clone() for k, v in self.opt_state.items()}, self.opt_step)
+            # every timed step exchanges: accumulation is switched to 1 for the measurement and put back with what it had pending
+            saved_acc = (self.accumulate, self.micro, None if self.flat_accum is None else self.flat_accum.clone(),
+                         None if self._norm is None else self._norm[1].clone())
+            self.accumulate, self.micro = 1, 0
 
             def timed(collectives, defer=False):
                 self.bucketer.enabled, self.bucketer.defer = collectives, defer
@@ -349,6 +433,12 @@ class TrainStep:
                 for k, v in saved_opt[0].items():
                     self.opt_state[k].copy_(v)
                 self.opt_step = saved_opt[1]
+            if saved_acc is not None:
+                self.accumulate, self.micro = saved_acc[0], saved_acc[1]
+                if saved_acc[2] is not None:
+                    self.flat_accum.copy_(saved_acc[2])
+                if saved_acc[3] is not None:
+                    self._norm[1].copy_(saved_acc[3])
             eng.invalidate_weights()
             torch.cuda.synchronize(dev)
             if not ok:
@@ -372,22 +462,54 @@ class TrainStep:
             loss, counts, dlogits = self._criterion_loss(logits, labels)
         else:
             loss, counts, dlogits = self._tversky_loss(logits, labels, st)
-        if frozen_bn:
-            try:
-                eng.backward(ws, dlogits, P, self.grads, on_ready=self.bucketer.on_ready, zero_bias_grads=False, bn_mode='running',
-                             need=self._need)
-            finally:
-                lease.release()
-                if eng.x3:
-                    ws.release_split()
-        else:
-            eng.backward(ws, dlogits, P, self.grads, on_ready=self.bucketer.on_ready, zero_bias_grads=False, need=self._need)
-        self.bucketer.finish()
-        self._update(st)
+        pending = self.micro                                  # micro-steps already in flat_accum
+        closing = pending + 1 >= self.accumulate              # this call ends with the update (always, without accumulation)
+        on_ready = self.bucketer.on_ready if closing else None
+        self._adding = pending > 0                            # closing: the buckets take the pending sum in right before their all-reduce
+        try:
+            if frozen_bn:
+                try:
+                    eng.backward(ws, dlogits, P, self.grads, on_ready=on_ready, zero_bias_grads=False, bn_mode='running', need=self._need)
+                finally:
+                    lease.release()
+                    if eng.x3:
+                        ws.release_split()
+            else:
+                eng.backward(ws, dlogits, P, self.grads, on_ready=on_ready, zero_bias_grads=False, need=self._need)
+            self.last_counts = counts
+            self.last_logits = logits
+            if not closing:                                   # acc = g1, then acc += g: no collective, no update, the packed weights stay valid
+                _lib.call('bdn_grad_accumulate', self.flat_accum.data_ptr(), self.flat_grads.data_ptr(), self.layout.total, int(pending > 0), st)
+                self.micro = pending + 1
+                return loss.clone()
+            if pending:                                       # flat_grads = gK + acc
+                if self.bucketer.active():
+                    self._add_pending(self.bucketer.reduce_end, self.layout.total)       # the tail that is not exchanged
+                else:
+                    self._add_pending(0, self.layout.total)
+            self.bucketer.finish()
+        finally:
+            self._adding = False
+        self.micro = 0
+        self._apply(st, 1.0 / (self.world * (pending + 1)))
         eng.invalidate_weights()                              # packed bf16/f32 GEMM images are now stale
-        self.last_counts = counts
-        self.last_logits = logits
         return loss.clone()
+
+    def _add_pending(self, a, b):
+        """flat_grads[a:b] += flat_accum[a:b] on the current stream (GradBucketer.before_reduce: a bucket, right before its all-reduce)."""
+        if self._adding and b > a:
+            _lib.call('bdn_grad_accumulate', self.flat_grads.data_ptr() + 4 * a, self.flat_accum.data_ptr() + 4 * a, b - a, 1,
+                      _lib.stream_ptr())
+
+    def _apply(self, st, grad_scale):
+        """The norm (when clipping is on) and the update, with g = grad_scale * flat_grads."""
+        if self._norm is None:
+            return self._update(st, grad_scale)
+        ws, out = self._norm
+        pg, (ends, ids, n_seg) = (self._groups, self._seg) if self._groups is not None else self._implicit_table()
+        _lib.call('bdn_grad_norm', self.flat_grads.data_ptr(), ends.data_ptr(), ids.data_ptr(), n_seg, grad_scale, self.max_grad_norm,
+                  ws.data_ptr(), out.data_ptr(), self.layout.total, st)
+        self._update_grouped(st, grad_scale, out.data_ptr() + 4)
 
     def _tversky_loss(self, logits, labels, st):
         """The default criterion: bdn_tversky on persistent buffers -> (loss, counts, dlogits)."""
@@ -416,47 +538,55 @@ class TrainStep:
         self.last_terms, self.last_dlogits = terms, dlogits
         return loss, counts, dlogits
 
-    def _update(self, st):
-        """The optimizer update on stream `st` with g = (sum of rank gradients) / world: per-rank loss, averaged gradients (standard DDP;
-        SURVEY.md 8e).  Host-side scalars only: the step count is a Python int, nothing syncs."""
+    def _update(self, st, grad_scale):
+        """The optimizer update on stream `st` with g = grad_scale * (sum of rank gradients), grad_scale = 1 / world (times 1 / the number
+        of accumulated micro-steps): per-rank loss, averaged gradients (standard DDP).  Host-side scalars only: the step
+        count is a Python int, nothing syncs."""
         o, n = self.optim, self.layout.total
         if self._groups is not None:
-            return self._update_grouped(st)
+            return self._update_grouped(st, grad_scale)
         if o.plain:                                          # p -= lr * g: the reference's optim.SGD(lr)
-            _lib.call('bdn_sgd_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), float(self.lr), 1.0 / self.world, n, st)
+            _lib.call('bdn_sgd_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), float(self.lr), grad_scale, n, st)
             return
         first = self.opt_step == 0
         self.opt_step += 1
         if o.kind == 'sgd':
             buf = self.opt_state.get('momentum_buffer')
             _lib.call('bdn_sgd_momentum_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), _lib.ptr(buf), float(self.lr),
-                      1.0 / self.world, o.momentum, o.dampening, o.weight_decay, int(o.nesterov), int(first), n, st)
+                      grad_scale, o.momentum, o.dampening, o.weight_decay, int(o.nesterov), int(first), n, st)
         else:
             _lib.call('bdn_adam_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state['exp_avg'].data_ptr(),
-                      self.opt_state['exp_avg_sq'].data_ptr(), float(self.lr), 1.0 / self.world, o.betas[0], o.betas[1], o.eps,
+                      self.opt_state['exp_avg_sq'].data_ptr(), float(self.lr), grad_scale, o.betas[0], o.betas[1], o.eps,
                       o.weight_decay, int(o.kind == 'adamw'), self.opt_step, n, st)
 
-    def _update_grouped(self, st):
-        """_update through bdn_*_step_grouped: per-group lr / weight_decay read from `param_groups` now, frozen segments skipped."""
-        o, n, pg = self.optim, self.layout.total, self._groups
-        if self._implicit_group:
-            pg.groups[0]['lr'] = float(self.lr)
+    def _update_grouped(self, st, grad_scale, dev_scale=None):
+        """_update through bdn_*_step_grouped: per-group lr / weight_decay read from `param_groups` now, frozen segments skipped.
+        dev_scale: None, or the device address of the clip coefficient: the _ex entry points, g = (grad_scale * coefficient) * grad."""
+        o, n = self.optim, self.layout.total
+        if self._groups is not None:
+            pg, seg = self._groups, self._seg
+            if self._implicit_group:
+                pg.groups[0]['lr'] = float(self.lr)
+        else:                                                # clipping without groups: the one implicit group follows the step's values
+            pg, seg = self._implicit_table()
+            pg.groups[0]['lr'], pg.groups[0]['weight_decay'] = float(self.lr), o.weight_decay
         lrs, wds = pg.hyper('lr'), pg.hyper('weight_decay')
-        ends, ids, n_seg = self._seg
+        ends, ids, n_seg = seg
         table = (ends.data_ptr(), ids.data_ptr(), n_seg, len(lrs))
         lr, wd = _lib.floats(lrs), _lib.floats(wds)
+        ex, ds = ('', ()) if dev_scale is None else ('_ex', (dev_scale,))
         if o.kind == 'sgd' and o.momentum == 0 and not any(wds):
-            _lib.call('bdn_sgd_step_grouped', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), *table, lr, 1.0 / self.world, n, st)
+            _lib.call('bdn_sgd_step_grouped' + ex, self.flat_params.data_ptr(), self.flat_grads.data_ptr(), *table, lr, grad_scale, *ds, n, st)
             return
         first = self.opt_step == 0
         self.opt_step += 1
         if o.kind == 'sgd':
-            _lib.call('bdn_sgd_momentum_step_grouped', self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
-                      _lib.ptr(self.opt_state.get('momentum_buffer')), *table, lr, wd, 1.0 / self.world, o.momentum, o.dampening,
+            _lib.call('bdn_sgd_momentum_step_grouped' + ex, self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
+                      _lib.ptr(self.opt_state.get('momentum_buffer')), *table, lr, wd, grad_scale, *ds, o.momentum, o.dampening,
                       int(o.nesterov), int(first), n, st)
         else:
-            _lib.call('bdn_adam_step_grouped', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state['exp_avg'].data_ptr(),
-                      self.opt_state['exp_avg_sq'].data_ptr(), *table, lr, wd, 1.0 / self.world, o.betas[0], o.betas[1], o.eps,
+            _lib.call('bdn_adam_step_grouped' + ex, self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state['exp_avg'].data_ptr(),
+                      self.opt_state['exp_avg_sq'].data_ptr(), *table, lr, wd, grad_scale, *ds, o.betas[0], o.betas[1], o.eps,
                       int(o.kind == 'adamw'), self.opt_step, n, st)
 
     # ------------------------------------------------------------------ optimizer state in torch.optim's format
@@ -465,6 +595,7 @@ class TrainStep:
         model.parameters(); param_groups with torch 2.10's keys).  The tensors are copies taken on the current stream, not views of the
         live buffers.  With parameter groups: one 'param_groups' entry per group and no state for a frozen parameter, which is what
         torch.optim built with the same groups holds (fabric_amd.optim.groups_to_torch)."""
+        self._no_pending('optimizer_state_dict()')
         self.optim.lr = float(self.lr)
         self.stream(self.flat_params.device)
         torch.cuda.current_stream(self.flat_params.device).wait_stream(self._hp)        # after the last step's update
@@ -480,6 +611,7 @@ class TrainStep:
         of the other family (SGD vs Adam), or its parameter count, shapes or per-parameter state do not fit this model.  With parameter
         groups the state of an optimizer built with the same groups is expected (fabric_amd.optim.torch_to_groups; a single-group state
         over all parameters is accepted too and leaves the groups' lr / weight_decay as they are)."""
+        self._no_pending('load_optimizer_state_dict()')
         dev = self.flat_params.device
         if self._groups is not None:
             cfg, hyper, flat, step = _optim.torch_to_groups(sd, self._groups, self.layout, dev)

@@ -553,6 +553,40 @@ int bdn_adam_step_grouped(float* params, const float* grads, float* exp_avg, flo
                           const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay, float grad_scale,
                           double beta1, double beta2, float eps, int decoupled_weight_decay, long long step, size_t n, void* stream);
 
+/* ---- the three grouped rules with one more factor on the gradient, read from DEVICE memory: g = (grad_scale * *dev_scale) * grads.
+ * dev_scale (not NULL, 4-byte aligned) is read by the kernel, once per block when the per-group parameters are staged (plain SGD: the
+ * host-formed lr * grad_scale is multiplied there), so a clip coefficient that bdn_grad_norm has just written reaches the update
+ * without a host round trip and without a scaling pass over the gradients.  Everything else as above; with *dev_scale == 1.0f the
+ * bits are those of the plain grouped entry points. ---- */
+int bdn_sgd_step_grouped_ex(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, int n_groups,
+                            const float* lr, float grad_scale, const float* dev_scale, size_t n, void* stream);
+int bdn_sgd_momentum_step_grouped_ex(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                                     const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                     float grad_scale, const float* dev_scale, float momentum, float dampening, int nesterov,
+                                     int first_step, size_t n, void* stream);
+int bdn_adam_step_grouped_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
+                             const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                             float grad_scale, const float* dev_scale, double beta1, double beta2, float eps,
+                             int decoupled_weight_decay, long long step, size_t n, void* stream);
+
+/* ---- gradient accumulation: dst = src (add = 0) or dst = dst + src (add = 1, one IEEE float32 add per element) over n floats; both
+ * 16-byte aligned, n arbitrary (float4 body, scalar tail).  Called on sub-ranges (dst + a, src + a, b - a) with a, b multiples of 4. ---- */
+int bdn_grad_accumulate(float* dst, const float* src, size_t n, int add, void* stream);
+
+/* ---- the global L2 norm of the gradients and torch.nn.utils.clip_grad_norm_'s coefficient, both left on the device:
+ *   out[0] = (float)(grad_scale * sqrt(sum g^2)),  out[1] = clamp(max_norm / (out[0] + 1e-6f), max = 1.0f)   (float32, torch's formula, the
+ *   quotient formed as torch forms a float over a tensor: (1 / (out[0] + 1e-6f)) * max_norm; a NaN norm gives a NaN coefficient;
+ *   max_norm = +inf gives 1: measure only).
+ * n: a multiple of 4.  n_seg = 0: every element counts.  n_seg in 1..256: seg_end / seg_group are the DEVICE segment table of the grouped
+ * update rules, and a vector of a segment with group id -1 (frozen), or behind the last end, is NOT READ (torch skips parameters
+ * without a gradient).  Each float32 is converted to double before it is squared; sums are double.  Two launches, no atomics, no memset:
+ * one double per block of 4096 vectors (16384 floats) into `workspace` (bdn_grad_norm_workspace_bytes(n) bytes, 8-byte aligned; the
+ * block count depends on n only, reductions run in a fixed order: bit-identical on any device), then one thread adds them in index
+ * order.  max_norm negative or NaN: BDN_E_ARG. ---- */
+size_t bdn_grad_norm_workspace_bytes(size_t n);
+int bdn_grad_norm(const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float grad_scale, float max_norm,
+                  void* workspace, float* out, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,12 @@
       and the same with the encoder's segments frozen) against bdn_adam_step in one process, the whole interleaving repeated --rounds
       times (the spread between repeats of the ungrouped kernel is the margin), and the bf16 B=64 128x128 AdamW step with no groups, two
       groups, the encoder frozen, and the encoder frozen + bn='frozen', interleaved like (b).
-    python tools/bench_optim.py [--reps 200] [--rounds 4] [--steps 20] [--skip-step] [--groups]
+  (d) --clip: bdn_grad_norm (no table; the model's two-group table; the same with the encoder frozen) and bdn_grad_accumulate (add = 0,
+      add = 1) at the model's size beside launches that move the same bytes on the same card in the same process (torch's vector_norm:
+      one read; torch's copy_: read + write; torch's add_: two reads + write), bdn_adam_step_grouped_ex beside bdn_adam_step_grouped, and
+      the bf16 B=64 128x128 AdamW step plain / with max_grad_norm=1.0 / with accumulate=4 (per update of four micro-steps, against
+      four plain steps), interleaved like (b).
+    python tools/bench_optim.py [--reps 200] [--rounds 4] [--steps 20] [--skip-step] [--groups | --clip]
 Prints one JSON line at the end."""
 import argparse
 import json
@@ -217,6 +222,132 @@ def grouped_steps(rounds, n_steps, batch=64):
     return out
 
 
+def clip_kernels(reps, rounds):
+    """us per launch (median of `rounds` interleaved repeats) of the norm, accumulate and _ex kernels and of their byte-for-byte
+    references."""
+    from fabric_amd import optim as O
+    from fabric_amd.engine import param_order
+    from fabric_amd.parallel import FlatLayout
+    dev = torch.device('cuda', 0)
+    model = BiDateNet(13, 2)
+    named = list(model.named_parameters())
+    names = [k for k, _ in named]
+    layout = FlatLayout([(k, p.shape) for k, p in named], param_order(13))
+    assert layout.total == N
+    cfg = O.OptimConfig('adamw', lr=1e-3)
+    tables, counted = {}, {}
+    for name, frozen_encoder in (('two_groups', False), ('two_groups_encoder_frozen', True)):
+        groups = _two_groups(model, frozen_encoder)
+        pg = O.ParamGroups(cfg, names, groups, {k for k, p in named if not p.requires_grad})
+        ends, ids = O.segment_table(layout, pg)
+        tables[name] = (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev), torch.tensor(ids, dtype=torch.int32).to(dev), len(ends))
+        counted[name] = 16 * sum(b - a for a, b, g in zip([0] + ends[:-1], ends, ids) if g != O.FROZEN)
+    g = torch.Generator(device='cpu').manual_seed(0)
+    p = torch.randn(N, generator=g).to(dev)
+    gr = (torch.randn(N, generator=g) * 1e-3).to(dev)
+    acc, m, v = torch.zeros(N, device=dev), torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+    ws = torch.empty(_lib.load().bdn_grad_norm_workspace_bytes(N) // 8, dtype=torch.float64, device=dev)
+    out2 = torch.ones(2, device=dev)
+    one = torch.ones(1, device=dev)
+    st = _lib.stream_ptr()
+    step = [0]
+    lr, wd = _lib.floats([1e-3, 1e-4]), _lib.floats([1e-2, 0.0])
+
+    def norm(name):
+        t = (None, None, 0) if name is None else (tables[name][0].data_ptr(), tables[name][1].data_ptr(), tables[name][2])
+        return lambda: _lib.call('bdn_grad_norm', gr.data_ptr(), *t, 1.0, 1.0, ws.data_ptr(), out2.data_ptr(), N, st)
+
+    def adam(ex):
+        ends, ids, n_seg = tables['two_groups']
+
+        def f():
+            step[0] += 1
+            if ex:
+                _lib.call('bdn_adam_step_grouped_ex', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), ends.data_ptr(), ids.data_ptr(),
+                          n_seg, 2, lr, wd, 1.0, one.data_ptr(), 0.9, 0.999, 1e-8, 1, step[0], N, st)
+            else:
+                _lib.call('bdn_adam_step_grouped', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), ends.data_ptr(), ids.data_ptr(),
+                          n_seg, 2, lr, wd, 1.0, 0.9, 0.999, 1e-8, 1, step[0], N, st)
+        return f
+    cases = [
+        ('ref_read_torch_vector_norm', 4 * N, lambda: torch.linalg.vector_norm(gr)),
+        ('grad_norm', 4 * N, norm(None)),
+        ('grad_norm_two_groups', counted['two_groups'], norm('two_groups')),
+        ('grad_norm_encoder_frozen', counted['two_groups_encoder_frozen'], norm('two_groups_encoder_frozen')),
+        ('ref_read_write_torch_copy', 8 * N, lambda: acc.copy_(gr)),
+        ('grad_accumulate_copy', 8 * N, lambda: _lib.call('bdn_grad_accumulate', acc.data_ptr(), gr.data_ptr(), N, 0, st)),
+        ('ref_2read_write_torch_add', 12 * N, lambda: acc.add_(gr)),
+        ('grad_accumulate_add', 12 * N, lambda: _lib.call('bdn_grad_accumulate', acc.data_ptr(), gr.data_ptr(), N, 1, st)),
+        ('adamw_grouped', 28 * N, adam(False)),
+        ('adamw_grouped_ex', 28 * N, adam(True)),
+    ]
+    res = {name: [] for name, _, _ in cases}
+    for _ in range(rounds):
+        for name, _, fn in cases:
+            for _ in range(20):
+                fn()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            res[name].append(e0.elapsed_time(e1) / reps * 1e3)
+    out = {}
+    for name, nbytes, _ in cases:
+        med = statistics.median(res[name])
+        out[name] = {'us': round(med, 2), 'MB': round(nbytes / 1e6, 1), 'TB_s': round(nbytes / med * 1e-6, 2), 'rounds_us': [round(t, 2) for t in res[name]]}
+        print(f'{name:30s} median {med:8.2f} us  {nbytes / 1e6:6.1f} MB  {nbytes / med * 1e-6:5.2f} TB/s  {out[name]["rounds_us"]}', flush=True)
+    for a, b in (('grad_norm', 'ref_read_torch_vector_norm'), ('grad_accumulate_copy', 'ref_read_write_torch_copy'),
+                 ('grad_accumulate_add', 'ref_2read_write_torch_add'), ('adamw_grouped_ex', 'adamw_grouped')):
+        out[f'{a}/{b}'] = round(out[a]['us'] / out[b]['us'], 3)
+        print(f'{a} / {b} = {out[f"{a}/{b}"]}', flush=True)
+    return out
+
+
+def clip_steps(rounds, n_steps, batch=64):
+    """ms per bf16 B=64 128x128 AdamW step: plain, with max_grad_norm=1.0, and with accumulate=4 (n_steps is rounded to a multiple of 4;
+    reported per micro-step and per update); interleaved."""
+    dev = torch.device('cuda', 0)
+    g = torch.Generator(device='cpu').manual_seed(1)
+    x1 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    x2 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    lbl = (torch.rand(batch, 128, 128, generator=g) < 0.1).to(torch.uint8).to(dev)
+    n_steps = max(4, n_steps // 4 * 4)
+    cases = [('plain', {}), ('max_grad_norm_1', dict(max_grad_norm=1.0)), ('accumulate_4', dict(accumulate=4)),
+             ('accumulate_4_max_grad_norm_1', dict(accumulate=4, max_grad_norm=1.0))]
+    ts = {}
+    for name, kw in cases:
+        torch.manual_seed(0)
+        ts[name] = TrainStep(BiDateNet(13, 2, precision='bf16').to(dev).train(), lr=1e-4, optimizer='adamw', **kw)
+    res = {name: [] for name, _ in cases}
+    with torch.cuda.stream(ts['plain'].stream()):
+        for _ in range(rounds):
+            for name, _ in cases:
+                s = ts[name]
+                for _ in range(8):
+                    s.step(x1, x2, lbl)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n_steps):
+                    s.step(x1, x2, lbl)
+                e1.record()
+                torch.cuda.synchronize()
+                res[name].append(e0.elapsed_time(e1) / n_steps)
+    base = statistics.median(res['plain'])
+    out = {}
+    for name, kw in cases:
+        med = statistics.median(res[name])
+        k = kw.get('accumulate', 1)
+        out[name] = {'ms_per_call': round(med, 4), 'delta_us_per_call': round((med - base) * 1e3, 1), 'ms_per_update': round(med * k, 4),
+                     'delta_us_per_update_vs_plain_steps': round((med - base) * k * 1e3, 1), 'rounds_ms': [round(t, 4) for t in res[name]]}
+        print(f'step {name:30s} median {med:.4f} ms/call  ({(med - base) * 1e3:+7.1f} us vs plain; per update of {k}: '
+              f'{(med - base) * k * 1e3:+7.1f} us)  {out[name]["rounds_ms"]}', flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=200)
@@ -224,7 +355,14 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--skip-step', action='store_true')
     ap.add_argument('--groups', action='store_true', help='(c): the grouped update kernel and the grouped / frozen steps only')
+    ap.add_argument('--clip', action='store_true', help='(d): the norm / accumulate / _ex kernels and the clipped / accumulating steps only')
     a = ap.parse_args()
+    if a.clip:
+        res = {'n': N, 'clip_kernels': clip_kernels(max(a.reps, 200), a.rounds)}
+        if not a.skip_step:
+            res['clip_step_bf16_b64'] = clip_steps(a.rounds, a.steps)
+        print(json.dumps(res))
+        return
     if a.groups:
         res = {'n': N, 'grouped_kernels': grouped_kernels(max(a.reps, 200), a.rounds)}
         if not a.skip_step:
