@@ -4,6 +4,14 @@ size_average) behind ``bdn_criterion`` (include/bidate_hip.h; reference utils/he
 Overlap is the TP / (TP + alpha FP + beta FN + eps) family: Tversky as given, jaccard = (1, 1, eps), dice = (0.5, 0.5, eps / 2).
 Focal is FocalLoss with the modulating factor a constant for the gradient.  The compound forms (focal + an overlap term, what change
 detection trains with on imbalanced data) run as one three-launch kernel sequence.  Importable without a GPU; evaluate() needs one.
+
+ignore_index (None or a label byte 0..255, torch's name for it): pixels with that label are left out of the loss -- ``bdn_criterion_masked``.
+The overlap sums TP / FP / FN run over the other (valid) pixels only, the focal mean divides by the number of valid pixels, dlogits is
+exactly 0 at an ignored pixel, the counts become {TP, FP, FN, correct, valid} over valid pixels, and the logits of an ignored pixel (inf
+and NaN included) reach no output.  A valid label >= ncls keeps the library's "labels outside the classes" rule.  A batch without a valid
+pixel gives overlap = 1, focal = 0 and an all-zero gradient (counts[4] = 0): a train step on it still runs and weight decay still
+applies; nothing checks for it on the host.  Data-parallel: each rank normalises by its own valid count and the ranks' gradients are
+averaged with equal weight, as torch's DistributedDataParallel does with ignore_index.
 """
 
 NAMES = ('tversky', 'dice', 'jaccard', 'focal', 'focal+tversky', 'focal+dice', 'focal+jaccard')
@@ -13,10 +21,11 @@ REDUCE = {'columns': 0, 'image': 1}
 
 class Criterion:
     def __init__(self, w_overlap=1.0, alpha=0.5, beta=0.5, eps=1e-7, reduce='columns', w_focal=0.0, gamma=0.0, class_alpha=None,
-                 size_average=True):
+                 size_average=True, ignore_index=None):
         """reduce: 'columns' -- what the reference's train.py gets from [B,H,W] labels, sums over dims (0,2), one ratio per (class,
         column) -- or 'image', dims (0,2,3), one ratio per class ([B,1,H,W] labels there).  class_alpha: None, a float a (class
-        weights [a, 1 - a], utils/metrics.py:13-14) or a sequence of ncls class weights."""
+        weights [a, 1 - a], utils/metrics.py:13-14) or a sequence of ncls class weights.  ignore_index: None -- every pixel carries a label,
+        bdn_criterion -- or the label byte (0..255) of the pixels to leave out (module docstring), bdn_criterion_masked."""
         w_overlap, w_focal = float(w_overlap), float(w_focal)
         if not (w_overlap >= 0.0 and w_focal >= 0.0):
             raise ValueError(f'criterion weights must be >= 0, got w_overlap={w_overlap}, w_focal={w_focal}')
@@ -26,6 +35,11 @@ class Criterion:
             raise ValueError(f"reduce must be 'columns' or 'image', got {reduce!r}")
         if not float(gamma) >= 0.0:
             raise ValueError(f'focal gamma must be >= 0, got {gamma}')
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not 0 <= int(ignore_index) <= 255:
+                raise ValueError(f'ignore_index must be None or a label byte 0..255, got {ignore_index!r}')
+            ignore_index = int(ignore_index)
+        self.ignore_index = ignore_index
         self.w_overlap, self.alpha, self.beta, self.eps, self.reduce = w_overlap, float(alpha), float(beta), float(eps), reduce
         self.w_focal, self.gamma, self.size_average = w_focal, float(gamma), bool(size_average)
         if isinstance(class_alpha, (float, int)):
@@ -35,7 +49,7 @@ class Criterion:
 
     @classmethod
     def parse(cls, name, tversky_alpha=0.5, tversky_beta=0.5, focal_gamma=None, focal_alpha=None, weights=(1, 1), eps=1e-7,
-              reduce='columns'):
+              reduce='columns', ignore_index=None):
         """The criterion of a --loss_function name.  weights = (w_focal, w_overlap), used by the compound names only."""
         if name not in NAMES:
             raise ValueError(f'unknown criterion {name!r}: one of {", ".join(NAMES)}')
@@ -47,11 +61,12 @@ class Criterion:
         coef = {'tversky': (tversky_alpha, tversky_beta, eps), 'dice': (0.5, 0.5, 0.5 * eps), 'jaccard': (1.0, 1.0, eps),
                 None: (0.5, 0.5, eps)}[overlap]
         return cls(w_overlap, *coef, reduce=reduce, w_focal=w_focal, gamma=focal_gamma if focal else 0.0,
-                   class_alpha=focal_alpha if focal else None)
+                   class_alpha=focal_alpha if focal else None, ignore_index=ignore_index)
 
     def __repr__(self):
         return (f'Criterion(w_overlap={self.w_overlap}, alpha={self.alpha}, beta={self.beta}, eps={self.eps}, reduce={self.reduce!r}, '
-                f'w_focal={self.w_focal}, gamma={self.gamma}, class_alpha={self.class_alpha}, size_average={self.size_average})')
+                f'w_focal={self.w_focal}, gamma={self.gamma}, class_alpha={self.class_alpha}, size_average={self.size_average}'
+                + (f', ignore_index={self.ignore_index}' if self.ignore_index is not None else '') + ')')
 
     # ------------------------------------------------------------------ device side
     def _class_alpha(self, device, ncls):
@@ -66,22 +81,26 @@ class Criterion:
         return t
 
     def buffers(self, shape, device):
-        """Persistent outputs for logits of `shape`: (workspace, loss, terms, counts), the `out` of evaluate()."""
+        """Persistent outputs for logits of `shape`: (workspace, loss, terms, counts), the `out` of evaluate().  counts is int32[4], or
+        int32[5] with an ignore_index."""
         import torch
         from . import _lib
         B, C, H, W = shape
-        n = _lib.load().bdn_criterion_workspace_bytes(B, C, H, W, REDUCE[self.reduce])
+        masked = self.ignore_index is not None
+        query = _lib.load().bdn_criterion_masked_workspace_bytes if masked else _lib.load().bdn_criterion_workspace_bytes
+        n = query(B, C, H, W, REDUCE[self.reduce])
         if n == 0:
             raise RuntimeError(f'fabric_amd: the criterion takes logits [B, 2..8, H, W] with B*H*W < 2^31, got {tuple(shape)}')
         return (torch.empty((n + 15) // 16 * 16, dtype=torch.uint8, device=device), torch.empty((), dtype=torch.float32, device=device),
-                torch.empty(2, dtype=torch.float32, device=device), torch.empty(4, dtype=torch.int32, device=device))
+                torch.empty(2, dtype=torch.float32, device=device), torch.empty(5 if masked else 4, dtype=torch.int32, device=device))
 
     def evaluate(self, logits, labels, want_grad=True, out=None):
         """-> (loss, terms, counts, dlogits) of float32 [B,C,H,W] logits and [B,H,W] or [B,1,H,W] class-index labels, on the current
         stream: loss a 0-dim tensor, terms f32[2] = the unweighted overlap and focal values, counts int32[4] = {TP, FP, FN, correct} of
         argmax(logits), dlogits = d loss / d logits (None without want_grad: no gradient pass is launched).  `out`: buffers() of this
         shape, overwritten by every call that is given them; fresh ones otherwise.  The reduction is the criterion's `reduce`,
-        whichever rank the labels have."""
+        whichever rank the labels have.  With an ignore_index: counts int32[5] = {TP, FP, FN, correct, valid} over the valid pixels and
+        dlogits exactly 0 at the ignored ones (module docstring)."""
         import torch
         from . import _lib
         if not logits.is_cuda:
@@ -97,6 +116,11 @@ class Criterion:
         ws, loss, terms, counts = out if out is not None else self.buffers(logits.shape, logits.device)
         dlogits = torch.empty_like(logits) if want_grad else None
         ca = self._class_alpha(logits.device, C)
+        if self.ignore_index is not None:
+            _lib.call('bdn_criterion_masked', logits.data_ptr(), labels.data_ptr(), self.ignore_index, self.w_overlap, self.alpha, self.beta,
+                      self.eps, REDUCE[self.reduce], self.w_focal, self.gamma, _lib.ptr(ca), int(self.size_average), ws.data_ptr(),
+                      loss.data_ptr(), terms.data_ptr(), counts.data_ptr(), _lib.ptr(dlogits), B, C, H, W, _lib.stream_ptr())
+            return loss, terms, counts, dlogits
         _lib.call('bdn_criterion', logits.data_ptr(), labels.data_ptr(), self.w_overlap, self.alpha, self.beta, self.eps,
                   REDUCE[self.reduce], self.w_focal, self.gamma, _lib.ptr(ca), int(self.size_average), ws.data_ptr(), loss.data_ptr(),
                   terms.data_ptr(), counts.data_ptr(), _lib.ptr(dlogits), B, C, H, W, _lib.stream_ptr())

@@ -589,10 +589,15 @@ extern "C" int bdn_outc_bn_bwd_apply(int dtype, const float* dlogits, const floa
 // FOCAL (bdn_criterion's compound loss, below): the same three passes also carry a focal term -- the statistics pass adds every pixel's
 // focal loss from the softmax it has already formed (double per lane, block partials in a fixed order), the finish adds the blocks'
 // partials and forms the weighted sum, the gradient pass writes w_overlap dO + w_focal dF.  FOCAL = false is the code as it was.
-struct FocalStats { const float* calpha; float gamma; double* part; };                    // class weights or NULL; partial [gx*gy]
+// MASKED (bdn_criterion_masked, with FOCAL): a pixel whose label equals `ignore` is skipped by a branch before any of its logits is
+// used -- it adds to no sum and to no count, so whatever its logits hold (inf, NaN) reaches no output; the statistics pass also counts
+// the valid pixels (pcounts[block][5]), the finish forms the focal scale 1/valid from that count and leaves it in device memory for
+// the gradient pass, which writes 0.0f at an ignored pixel.  A term with weight 0 contributes nothing (it is selected out, not
+// multiplied by 0).  MASKED = false is the code as it was.
+struct FocalStats { const float* calpha; float gamma; double* part; int ignore; };        // class weights or NULL; partial [gx*gy]
 __device__ __forceinline__ float focal_mod(float pt, float gamma) { return gamma == 0.f ? 1.f : powf(fmaxf(1.f - pt, 0.f), gamma); }
 
-template <int NC, bool FOCAL = false>
+template <int NC, bool FOCAL = false, bool MASKED = false>
 __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                     float* __restrict__ part, int32_t* __restrict__ pcounts, int B, int ncls, int H, int W,
                                     int rows_per_block, int We, FastDiv dH, FocalStats fs = {}) {
@@ -606,7 +611,7 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
     float tp[NC], fp[NC], fn[NC];
 #pragma unroll
     for (int k = 0; k < NC; k++) { tp[k] = 0.f; fp[k] = 0.f; fn[k] = 0.f; }
-    int c_tp = 0, c_fp = 0, c_fn = 0, c_ok = 0;
+    int c_tp = 0, c_fp = 0, c_fn = 0, c_ok = 0, c_valid = 0;
     double facc = 0.0;
     const int rows = B * H, r_end = min(rows, (int)(blockIdx.y + 1) * rows_per_block);
     if (x < W)
@@ -627,6 +632,7 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (r0 + u * RL >= r_end) break;
+                if constexpr (MASKED) { if (tv[u] == fs.ignore) continue; c_valid++; }      // an ignored pixel: nothing of it is used
                 float l[NC]; float m = -INFINITY; int am = 0;
 #pragma unroll
                 for (int k = 0; k < NC; k++) { l[k] = lv[u][k]; if (l[k] > m) { m = l[k]; am = k; } }
@@ -659,7 +665,7 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
     }
     __syncthreads();
     // block partials, no atomics: part[row block][cell] (cells [3][ncls][W]) or part[block][3*NC] when the columns are
-    // reduced too; tversky_finish_kernel adds the blocks in a fixed order.  pcounts[block][4] likewise.
+    // reduced too; tversky_finish_kernel adds the blocks in a fixed order.  pcounts[block][4] likewise ([5] MASKED: + valid pixels).
     const int nblk_lin = blockIdx.y * gridDim.x + blockIdx.x;
     if (We == W) {
         if (rl == 0 && x < W)
@@ -687,9 +693,11 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
         int* ism = reinterpret_cast<int*>(sm);
         __syncthreads();
         const int tid = rl * CW + cl;
-        ism[tid * 4 + 0] = c_tp; ism[tid * 4 + 1] = c_fp; ism[tid * 4 + 2] = c_fn; ism[tid * 4 + 3] = c_ok;
+        constexpr int NCNT = MASKED ? 5 : 4;             // (256 * 5 ints fit in the 256 * 3 * NC floats of sm)
+        ism[tid * NCNT + 0] = c_tp; ism[tid * NCNT + 1] = c_fp; ism[tid * NCNT + 2] = c_fn; ism[tid * NCNT + 3] = c_ok;
+        if constexpr (MASKED) ism[tid * NCNT + 4] = c_valid;
         __syncthreads();
-        if (tid < 4) { int v = 0; for (int i = 0; i < 256; i++) v += ism[i * 4 + tid]; pcounts[nblk_lin * 4 + tid] = v; }
+        if (tid < NCNT) { int v = 0; for (int i = 0; i < 256; i++) v += ism[i * NCNT + tid]; pcounts[nblk_lin * NCNT + tid] = v; }
         if constexpr (FOCAL) {                             // the block's focal partial: LDS tree over the 256 lanes, a fixed order
             double* dsm = reinterpret_cast<double*>(sm);
             __syncthreads();
@@ -704,8 +712,10 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
 // sums[cell] = sum over the nblk block partials (cell-major rows of `part`), fixed order: thread = (float4 of cells or one
 // cell, block lane); then loss = 1 - mean_{c,w} TP/(TP + a FP + b FN + eps).  Overwrites sums[0] with 1/D and sums[1] with TP/D^2.
 // FOCAL: also adds the nfp focal block partials (fixed order), loss = w_o overlap + w_f focal, terms = the two unweighted values.
-struct FocalFinish { const double* part; int nfp; double scale; float w_o, w_f; float* terms; };
-template <bool FOCAL = false>
+// MASKED: five counters per block; the focal scale is formed here from the valid count (size_average: 1/valid, 1 with no valid pixel --
+// the sum is then 0 --; else 1) and left in *gscale for the gradient pass; a term with weight 0 is reported as 0 and adds nothing.
+struct FocalFinish { const double* part; int nfp; double scale; float w_o, w_f; float* terms; int size_average; float* gscale; };
+template <bool FOCAL = false, bool MASKED = false>
 __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict__ sums, const float* __restrict__ part, int nblk,
                                       const int32_t* __restrict__ pcounts, int ncblk, int32_t* __restrict__ counts,
                                       float alpha, float beta, float eps, int ncls, int W, float* __restrict__ loss,    // W = effective width (1 when the columns are reduced too)
@@ -737,6 +747,21 @@ __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict_
             sums[i] = a;
         }
     }
+    __shared__ int nvalid;                                 // MASKED: the number of valid pixels
+    if constexpr (MASKED) {                                // TP / FP / FN / correct / valid: 5 counters x 128 block lanes, LDS tree per counter
+        int* ired = reinterpret_cast<int*>(lane_sums);
+        __syncthreads();                                   // lane_sums is free again
+        const int j = tid >> 7, l = tid & 127;
+        if (tid < 640) {
+            int v = 0;
+            for (int b = l; b < ncblk; b += 128) v += pcounts[b * 5 + j];
+            ired[tid] = v;
+        }
+        __syncthreads();
+        for (int s2 = 64; s2 >= 1; s2 >>= 1) { if (tid < 640 && l < s2) ired[tid] += ired[tid + s2]; __syncthreads(); }
+        if (tid < 5 && counts) counts[tid] = ired[tid * 128];
+        if (tid == 0) nvalid = ired[4 * 128];
+    } else
     if (counts) {                                          // TP / FP / FN / correct counts: 256 block lanes x 4 counters, LDS tree (integers: any order)
         int* ired = reinterpret_cast<int*>(lane_sums);
         __syncthreads();                                   // lane_sums is free again
@@ -768,6 +793,16 @@ __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict_
         if (tid < 256) { for (int i = tid; i < ff.nfp; i += 256) f += ff.part[i]; red[tid] = f; }
         __syncthreads();
         for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+        if constexpr (MASKED) {
+            if (tid == 0) {
+                const double scale = ff.size_average && nvalid > 0 ? 1.0 / (double)nvalid : 1.0;
+                const float fo = (float)(red[0] * scale);
+                const float lo = ff.w_o != 0.f ? ff.w_o * ov : 0.f, lf = ff.w_f != 0.f ? ff.w_f * fo : 0.f;
+                *loss = lo + lf;
+                if (ff.terms) { ff.terms[0] = ff.w_o != 0.f ? ov : 0.f; ff.terms[1] = ff.w_f != 0.f ? fo : 0.f; }
+                *ff.gscale = (float)scale;
+            }
+        } else
         if (tid == 0) {
             const float fo = (float)(red[0] * ff.scale);
             *loss = ff.w_o * ov + ff.w_f * fo;
@@ -778,8 +813,9 @@ __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict_
 }
 
 // FOCAL: dlogits = w_o dO + w_f dF with dF_k = -(1 - pt)^gamma a[t] gscale ([k == t] - p_k), the factor a constant (focal_kernel)
-struct FocalBwd { const float* calpha; float gamma, gscale, w_o, w_f; };
-template <bool FOCAL = false>
+// MASKED: 0.0f for every class at an ignored pixel (written: the buffer is uninitialised), the focal scale read from *gscale_dev
+struct FocalBwd { const float* calpha; float gamma, gscale, w_o, w_f; const float* gscale_dev; int ignore; };
+template <bool FOCAL = false, bool MASKED = false>
 __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                    const float* __restrict__ coef, float alpha, float beta, float* __restrict__ dlogits,
                                    int B, int ncls, int H, int Wimg, int W, FastDiv dhw, FastDiv dWimg, FocalBwd fb = {}) {
@@ -789,6 +825,13 @@ __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8
     int bi, qi, yi, xi; dhw.divmod((int)p, bi, qi); dWimg.divmod(qi, yi, xi);      // (the entry point keeps B*H*W below 2^31)
     const size_t b = bi, q = qi; const int x = W == 1 ? 0 : xi;
     const int n = ncls * W;
+    if constexpr (MASKED) {
+        if (labels[p] == fb.ignore) {                      // nothing of this pixel's logits is read
+#pragma unroll
+            for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls) dlogits[(b * ncls + k) * hw + q] = 0.f;
+            return;
+        }
+    }
     float l[OUTC_MAXCLS], dp[OUTC_MAXCLS]; float m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls) { l[k] = logits[(b * ncls + k) * hw + q]; m = fmaxf(m, l[k]); }
@@ -812,10 +855,20 @@ __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8
 #pragma unroll
         for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls && k == t) pt = l[k];
         const float a = t < ncls ? (fb.calpha ? fb.calpha[t] : 1.f) : 0.f;                   // a label >= ncls: no focal gradient
+        if constexpr (MASKED) {
+            const float c = -focal_mod(pt, fb.gamma) * a * fb.gscale_dev[0];
+#pragma unroll
+            for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls) {
+                const float go = fb.w_o != 0.f ? fb.w_o * (l[k] * (dp[k] - dot)) : 0.f;
+                const float gf = fb.w_f != 0.f ? fb.w_f * (c * ((k == t ? 1.f : 0.f) - l[k])) : 0.f;
+                dlogits[(b * ncls + k) * hw + q] = go + gf;
+            }
+        } else {
         const float c = -focal_mod(pt, fb.gamma) * a * fb.gscale;
 #pragma unroll
         for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls)
             dlogits[(b * ncls + k) * hw + q] = fb.w_o * (l[k] * (dp[k] - dot)) + fb.w_f * (c * ((k == t ? 1.f : 0.f) - l[k]));
+        }
     } else {
 #pragma unroll
     for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls) dlogits[(b * ncls + k) * hw + q] = l[k] * (dp[k] - dot);
@@ -1006,6 +1059,50 @@ extern "C" int bdn_criterion(const float* logits, const uint8_t* labels, float w
         hipLaunchKernelGGL(tversky_bwd_kernel<true>, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, logits, labels, sums, alpha, beta, dlogits, B, ncls, H, W, p.We,
                            FastDiv(H * W), FastDiv(W), FocalBwd{class_alpha, gamma, (float)inv, w_overlap, w_focal});
         BDN_CHECK_LAUNCH("criterion_bwd");
+    }
+    return BDN_OK;
+}
+
+// ============================================================ criterion with an ignore label
+// bdn_criterion's function over the VALID pixels (label != ignore_label): always the three MASKED launches above, whatever the weights.
+// ws: [focal block partials, double, padded to 16 bytes][sums n][part nblk*n][pcounts gx*gy*5][focal gradient scale, padded to 16 bytes].
+extern "C" size_t bdn_criterion_masked_workspace_bytes(int B, int ncls, int H, int W, int reduce_w) {
+    if (B <= 0 || H <= 0 || W <= 0 || ncls < 2 || ncls > OUTC_MAXCLS || (size_t)B * H * W >= ((size_t)1 << 31)) return 0;
+    const OverlapPlan p = overlap_plan(B, ncls, H, W, reduce_w);
+    return criterion_focal_part_bytes(p) + sizeof(float) * (size_t)p.n * (p.nblk + 1) + sizeof(int32_t) * 5 * p.gx * p.gy + 16;
+}
+
+extern "C" int bdn_criterion_masked(const float* logits, const uint8_t* labels, int ignore_label, float w_overlap, float alpha, float beta,
+                                    float eps, int reduce_w, float w_focal, float gamma, const float* class_alpha, int size_average,
+                                    void* ws, float* loss, float* terms, int32_t* counts, float* dlogits, int B, int ncls, int H, int W,
+                                    void* stream) {
+    if (!logits || !labels || !ws || !loss) BDN_FAIL(BDN_E_ARG, "criterion_masked: null pointer");
+    if (ignore_label < 0 || ignore_label > 255) BDN_FAIL(BDN_E_ARG, "criterion_masked: ignore_label=%d is not a byte value (0..255)", ignore_label);
+    if (!(w_overlap >= 0.f) || !(w_focal >= 0.f)) BDN_FAIL(BDN_E_ARG, "criterion_masked: negative weight (w_overlap=%g, w_focal=%g)", w_overlap, w_focal);
+    if (w_overlap == 0.f && w_focal == 0.f) BDN_FAIL(BDN_E_ARG, "criterion_masked: both weights are zero");
+    if (!(gamma >= 0.f)) BDN_FAIL(BDN_E_ARG, "criterion_masked: negative gamma");
+    if (ncls < 2 || ncls > OUTC_MAXCLS) BDN_FAIL(BDN_E_SHAPE, "criterion_masked: ncls=%d unsupported (2..%d)", ncls, OUTC_MAXCLS);
+    if (B <= 0 || H <= 0 || W <= 0 || (size_t)B * H * W >= ((size_t)1 << 31)) BDN_FAIL(BDN_E_SHAPE, "criterion_masked: bad shape (B*H*W must stay below 2^31)");
+    if ((uintptr_t)ws & 15) BDN_FAIL(BDN_E_ARG, "criterion_masked: ws must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const OverlapPlan p = overlap_plan(B, ncls, H, W, reduce_w);
+    double* fpart = (double*)ws;                                               // [gx*gy]
+    float* sums = (float*)((char*)ws + criterion_focal_part_bytes(p));         // [n], then the coefficient tables
+    float* part = sums + p.n;                                                  // [nblk][n]
+    int32_t* pcounts = reinterpret_cast<int32_t*>(part + (size_t)p.nblk * p.n);  // [gx*gy][5]
+    float* gscale = reinterpret_cast<float*>(pcounts + (size_t)5 * p.gx * p.gy); // the finish writes it, the gradient pass reads it
+    const FocalStats fs{class_alpha, gamma, fpart, ignore_label};
+    dim3 grid(p.gx, p.gy), block(p.RL, p.CW);
+    if (ncls <= 2) hipLaunchKernelGGL((tversky_sums_kernel<2, true, true>), grid, block, sizeof(float) * 256 * 3 * 2, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, p.We, FastDiv(H), fs);
+    else hipLaunchKernelGGL((tversky_sums_kernel<OUTC_MAXCLS, true, true>), grid, block, sizeof(float) * 256 * 3 * OUTC_MAXCLS, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, p.We, FastDiv(H), fs);
+    BDN_CHECK_LAUNCH("criterion_masked_stats");
+    hipLaunchKernelGGL((tversky_finish_kernel<true, true>), dim3(1), dim3(1024), 0, st, sums, part, p.nblk, pcounts, p.gx * p.gy, counts, alpha, beta, eps, ncls, p.We, loss,
+                       FocalFinish{fpart, p.gx * p.gy, 1.0, w_overlap, w_focal, terms, size_average, gscale});
+    BDN_CHECK_LAUNCH("criterion_masked_finish");
+    if (dlogits) {
+        hipLaunchKernelGGL((tversky_bwd_kernel<true, true>), dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, logits, labels, sums, alpha, beta, dlogits, B, ncls, H, W, p.We,
+                           FastDiv(H * W), FastDiv(W), FocalBwd{class_alpha, gamma, 1.f, w_overlap, w_focal, gscale, ignore_label});
+        BDN_CHECK_LAUNCH("criterion_masked_bwd");
     }
     return BDN_OK;
 }

@@ -8,6 +8,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --epochs 4 --optimizer adamw --resume ./log/checkpoint_epoch_1.state_dict.pt
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --freeze inc --optimizer adamw
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --accumulate 4 --max_grad_norm 1.0
+    python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --ignore_label 255
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
 predicted tile by tile (utils/inference.py) -- here on the device-resident city stacks -- and written as PNG masks.
@@ -103,6 +104,13 @@ class _RankWorkerSeed:
         random.seed((self.seed * 7919 + self.rank) * 1000003 + worker_id * 65537 + torch.initial_seed() % 65521)
 
 
+def batch_accuracy(counts, n_pixels):
+    """Per-batch accuracy in percent from a criterion's counts: correct / all pixels, or, with the five counts of a criterion that has
+    an ignore label, correct / valid pixels -- 0 for a batch without a valid pixel, like the zero-division default of the P / R / F1."""
+    n = int(counts[4]) if len(counts) > 4 else n_pixels
+    return 100.0 * int(counts[3]) / n if n else 0.0
+
+
 def train_epoch(step, loader, dev, patch_size, feeder=None):
     """train.py:73-118 without the per-step host round trip: losses / counts are read back once per epoch, and the
     host -> device copies of batch k+1 (train.py:83-85) run on a copy stream under the step of batch k."""
@@ -125,7 +133,7 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
     metrics = initialize_metrics()
     for loss, counts, n in recs:
         c = counts.cpu()
-        metrics = set_metrics(metrics, loss.item(), 100.0 * int(c[3]) / (n * patch_size ** 2), batch_prf_from_counts(c))
+        metrics = set_metrics(metrics, loss.item(), batch_accuracy(c, n * patch_size ** 2), batch_prf_from_counts(c))
     out = get_mean_metrics(metrics) if recs else {}
     if norms:                                             # --max_grad_norm: read back once per epoch, beside the losses
         nc = torch.stack([torch.stack(v) for v in norms]).cpu()
@@ -134,18 +142,18 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
 
 
 @torch.no_grad()
-def validate(model, loader, dev, patch_size, criterion, feeder=None):
+def validate(model, loader, dev, patch_size, criterion, feeder=None, ignore_index=None):
     """train.py:125-172: eval-mode forward, the SAME criterion the run optimises (train.py:137), per-batch accuracy / P / R / F1,
-    mean over batches.  Batches arrive through the feeder's copy stream when one is given."""
+    mean over batches.  Batches arrive through the feeder's copy stream when one is given.  ignore_index: the run's ignore label --
+    the counts, and with them accuracy / P / R / F1, are taken over the other pixels."""
     from .utils.metrics import confusion_counts
     model.eval()
     metrics = initialize_metrics()
     for b1, b2, labels in _device_batches(loader, dev, feeder):
         logits = model(b1, b2)
         loss = criterion(logits, labels.long())
-        c = confusion_counts(logits, labels).cpu()
-        metrics = set_metrics(metrics, loss.item(), 100.0 * int(c[3]) / (labels.shape[0] * patch_size ** 2),
-                              batch_prf_from_counts(c))
+        c = confusion_counts(logits, labels, ignore_index).cpu()
+        metrics = set_metrics(metrics, loss.item(), batch_accuracy(c, labels.shape[0] * patch_size ** 2), batch_prf_from_counts(c))
     return get_mean_metrics(metrics)
 
 
@@ -308,6 +316,11 @@ def main(argv=None):
                          'false: tversky on the fused step, dice / jaccard / focal on the autograd route')
     ap.add_argument('--loss_weights', type=float, nargs=2, default=[1.0, 1.0], metavar=('W_FOCAL', 'W_OVERLAP'),
                     help='weights of the two terms of a compound --loss_function')
+    ap.add_argument('--ignore_label', type=int, default=None, metavar='V',
+                    help='--fused_step true only: pixels labelled V (0..255, e.g. 255 for nodata / unlabelled) are left out of the loss, '
+                         'its gradient and the accuracy / precision / recall / F1 (Criterion(ignore_index=V))')
+    ap.add_argument('--synthetic_ignore_frac', type=float, default=0.1,
+                    help='--synthetic with --ignore_label V: the fraction of every label raster painted with V')
     ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam', 'adamw'],
                     help='sgd is train.py:55 (optim.SGD); adam / adamw the torch.optim rules (train.py:56 is a commented-out Adam)')
     ap.add_argument('--momentum', type=float, default=0.0, help='sgd only')
@@ -358,6 +371,13 @@ def main(argv=None):
                          f"(utils/helpers.py:288-314); its bce branch cannot run on BiDateNet's logits and is not built")
     if 'focal' in opt.loss_function.split('+') and opt.focal_gamma is None:
         raise SystemExit(f'--loss_function {opt.loss_function} needs --focal_gamma')
+    if opt.ignore_label is not None:
+        if not opt.fused_step:
+            raise SystemExit(f'--ignore_label {opt.ignore_label} is built into the criterion of the fused step: add --fused_step true')
+        if not 0 <= opt.ignore_label <= 255:
+            raise SystemExit(f'--ignore_label {opt.ignore_label}: a label byte 0..255')
+        if not 0.0 <= opt.synthetic_ignore_frac < 1.0:
+            raise SystemExit(f'--synthetic_ignore_frac {opt.synthetic_ignore_frac}: a fraction in [0, 1)')
     step_criterion = None                                  # --fused_step true: ONE Criterion for the step and for validation
     if opt.fused_step:
         from .utils.helpers import criterion_from_opt
@@ -401,7 +421,8 @@ def main(argv=None):
     torch.manual_seed(opt.seed)                            # (global `random`, utils/dataloaders.py:150-156) are re-seeded per rank below
     scenes = None
     if opt.synthetic:
-        data = synthetic_onera(n_cities=6, bands=13, size=(360, 360))
+        data = synthetic_onera(n_cities=6, bands=13, size=(360, 360), **(
+            {} if opt.ignore_label is None else dict(ignore_frac=opt.synthetic_ignore_frac, ignore_value=opt.ignore_label)))
         val_cities = ['city4', 'city5']
     else:
         if not opt.band_ids:
@@ -469,7 +490,7 @@ def main(argv=None):
             tr = train_epoch(step, train_loader, dev, opt.patch_size, feeder)
         else:
             tr = train_epoch_autograd(model, criterion, optimizer, train_loader, dev, opt.patch_size, world, feeder)
-        va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder)
+        va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder, ignore_index=opt.ignore_label)
         if rank == 0:
             print(json.dumps({'epoch': epoch, **{'train_' + k: float(v) for k, v in tr.items()},
                               **{'validate_' + k: float(v) for k, v in va.items()}}), flush=True)

@@ -43,6 +43,10 @@ class TrainStep:
         ...: Criterion.parse with this step's tversky_alpha / tversky_beta / eps; a focal term needs a gamma, so build the Criterion).
         With a criterion the loss runs bdn_criterion, labels may be [B,H,W] or [B,1,H,W] (the criterion's `reduce` decides the overlap
         reduction), `last_terms` holds the unweighted overlap and focal values beside `last_counts`, and `last_dlogits` the loss gradient.
+        A Criterion with an ignore_index (bdn_criterion_masked) leaves the pixels with that label out: `last_counts` then has five entries,
+        {TP, FP, FN, correct, valid}, `last_dlogits` is exactly 0 at the ignored pixels, and a batch without a valid pixel is a step with
+        a zero gradient (weight decay still applies).  Data-parallel, every rank normalises by its own valid count and the gradients are
+        averaged over the ranks with equal weight, as torch's DistributedDataParallel does with ignore_index.
 
         bn: 'batch' (BatchNorm on batch statistics, running statistics updated: a training step) or 'frozen' (BatchNorm on its running
         statistics, which are constants: running_mean / running_var / num_batches_tracked are not touched, and the conv biases in

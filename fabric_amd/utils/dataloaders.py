@@ -86,11 +86,15 @@ def metadata_from_shapes(shapes, val_cities, patch_size, stride):
     return train, val
 
 
-def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fraction=0.05):
+def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fraction=0.05, ignore_frac=0.0, ignore_value=255):
     """A `full_load` dict of the reference's schema ({city: {'images': f32[2,C,H,W], 'labels': u8[H,W]}},
     utils/dataloaders.py:138-145) filled with z-scored noise; date 2 = date 1 + small noise + blobs of
-    change where the label is 1."""
+    change where the label is 1.  ignore_frac > 0: rectangles of the label raster (nodata borders, unlabelled stretches) are painted
+    with `ignore_value` (255) until about that fraction of it is covered, for runs with an ignore label (train.py --ignore_label).
+    The rectangles come from a generator of their own and are painted last: the images, and with ignore_frac = 0 the labels, are
+    the arrays this function always returned."""
     r = np.random.default_rng(seed)
+    ri = np.random.default_rng([seed, 255]) if ignore_frac > 0 else None
     out = {}
     for c in range(n_cities):
         h, w = size
@@ -100,6 +104,12 @@ def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fracti
             cy, cx = r.integers(0, h), r.integers(0, w)
             lbl[max(0, cy - 10):cy + 10, max(0, cx - 10):cx + 10] = 1
         d2 = d1 + 0.3 * r.standard_normal(d1.shape).astype(np.float32) + 1.5 * lbl[None].astype(np.float32)
+        if ri is not None:
+            lbl[:, :max(1, int(0.25 * ignore_frac * w))] = ignore_value            # a nodata border: a quarter of the budget
+            while (lbl == ignore_value).mean() < ignore_frac:
+                rh, rw = int(ri.integers(h // 16 + 1, h // 4 + 2)), int(ri.integers(w // 16 + 1, w // 4 + 2))
+                y0, x0 = int(ri.integers(0, h - rh + 1)), int(ri.integers(0, w - rw + 1))
+                lbl[y0:y0 + rh, x0:x0 + rw] = ignore_value
         out[f'city{c}'] = {'images': np.stack([d1, d2]).astype(np.float32), 'labels': lbl}
     return out
 

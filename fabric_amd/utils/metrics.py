@@ -177,7 +177,8 @@ class CompoundLoss(nn.Module):
 
     @property
     def last_counts(self):
-        """int32[4] device tensor {TP, FP, FN, correct} of argmax(logits) vs labels for the last call."""
+        """int32[4] device tensor {TP, FP, FN, correct} of argmax(logits) vs labels for the last call; int32[5] = {.., valid}, over the
+        valid pixels, when the criterion has an ignore_index."""
         return self._holder.get('counts')
 
     @property
@@ -186,9 +187,15 @@ class CompoundLoss(nn.Module):
         return self._holder.get('terms')
 
 
-def confusion_counts(logits, labels):
+def confusion_counts(logits, labels, ignore_index=None):
     """int32[4] device tensor {TP, FP, FN, correct} of argmax(logits, 1) vs labels (what train.py:96-106 hands to sklearn),
-    for criteria that do not report it themselves: one pass of the overlap-loss kernel, loss and gradient discarded."""
+    for criteria that do not report it themselves: one pass of the overlap-loss kernel, loss and gradient discarded.
+    ignore_index: a label byte 0..255 -> int32[5] = {TP, FP, FN, correct, valid} over the pixels whose label is not ignore_index
+    (the statistics and finish passes of bdn_criterion_masked)."""
+    if ignore_index is not None:
+        from ..criterion import Criterion
+        lg = logits.detach().contiguous().float()
+        return Criterion(ignore_index=ignore_index).evaluate(lg, labels.detach(), want_grad=False)[2]
     holder = {}
     with torch.no_grad():
         _OverlapFunction.apply(logits.detach(), labels, 0.5, 0.5, 1e-7, holder)

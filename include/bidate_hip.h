@@ -462,6 +462,31 @@ int bdn_criterion(const float* logits, const uint8_t* labels, float w_overlap, f
                   float w_focal, float gamma, const float* class_alpha, int size_average, void* ws, float* loss, float* terms,
                   int32_t* counts, float* dlogits, int B, int ncls, int H, int W, void* stream);
 
+/* ---- the same criterion over the labelled pixels only: an ignore label (torch's ignore_index; the reference has none) ----
+ * A pixel whose label byte equals ignore_label (0..255) is IGNORED; every other pixel is VALID and treated exactly as by bdn_criterion,
+ * the "labels outside the classes" rule (bdn_tversky) for a valid label >= ncls included.  With v = 1 at valid pixels and 0 elsewhere:
+ *   Overlap: TP = sum p onehot v, FP = sum p (1 - onehot) v, FN = sum (1 - p) onehot v over the same dims, the mean over the same
+ *            (class, column) or (class) cells; a cell without a valid pixel has the ratio 0 / (0 + eps) = 0 (no special case).
+ *   Focal:   the per-pixel term summed over the valid pixels; size_average divides by the NUMBER OF VALID PIXELS (0 with none); the
+ *            modulating factor stays a constant for the gradient.
+ *   dlogits: exactly 0.0f for every class at an ignored pixel (written, not skipped), the gradient of the masked loss elsewhere.
+ *   counts:  NULL or int32[5] = {TP, FP, FN, correct, valid}, all over the valid pixels.
+ * The logits of an ignored pixel reach no output, whatever they hold (+-inf and NaN included): the kernels branch on the label before
+ * they use them.  A batch without a valid pixel gives overlap = 1, focal = 0, loss = w_overlap, an all-zero dlogits and counts[4] = 0;
+ * it is not an error and nothing checks for it on the host.
+ * Always three launches, whatever the weights (one term with weight 1 included): the statistics pass (softmax once per pixel, overlap
+ * block partials, focal block partials in double, argmax counts and the valid count), the fixed-order finish (loss, terms, counts,
+ * coefficient tables, and the focal gradient scale 1 / valid -- or 1 -- left in the workspace), and the gradient pass, which reads that
+ * scale from device memory.  No atomics, no memset, no host read-back: the same bits on every run.  A term with weight 0 contributes
+ * nothing to loss and dlogits and is reported as 0 in `terms`.
+ * Arguments and their checks as bdn_criterion, plus ignore_label in 0..255.  ws: bdn_criterion_masked_workspace_bytes() bytes,
+ * 16-byte aligned.  Data-parallel training: each rank normalises by its own valid count and the ranks' gradients are averaged with
+ * equal weight (torch DistributedDataParallel with ignore_index does the same). */
+size_t bdn_criterion_masked_workspace_bytes(int B, int ncls, int H, int W, int reduce_w);
+int bdn_criterion_masked(const float* logits, const uint8_t* labels, int ignore_label, float w_overlap, float alpha, float beta, float eps,
+                         int reduce_w, float w_focal, float gamma, const float* class_alpha, int size_average, void* ws, float* loss,
+                         float* terms, int32_t* counts, float* dlogits, int B, int ncls, int H, int W, void* stream);
+
 /* ---- OSCD ingest: utils/dataloaders.py:86-111 city_loader, per band ----
  * dst [H][W] f32 (one plane of a [C][H][W] scene) = cv2.resize((src - mean) / std, (W, H)) with cv2's default float
  * INTER_LINEAR sampling (half-pixel centres, border weights (1,0)).  src: [hs][ws] uint16 (src_is_f32 = 0) or f32, on
