@@ -122,6 +122,9 @@ SIGNATURES = {
     'bdn_grad_accumulate': (_i, [_vp, _vp, _sz, _i, _vp]),
     'bdn_grad_norm_workspace_bytes': (_sz, [_sz]),
     'bdn_grad_norm': (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp, _sz, _vp]),
+    'bdn_ema_update': (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _sz, _vp]),
+    'bdn_ema_update_multi': (_i, [_vp, _i, _i, _f, _i, _vp]),
+    'bdn_swap_segments': (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp]),
 }
 
 

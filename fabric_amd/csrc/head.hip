@@ -1299,6 +1299,7 @@ template <typename P> struct GroupArgs { P g[OPT_MAX_GROUPS]; };
 struct RuleSgd {                                        // plain SGD: bdn_sgd_step's p -= (lr * grad_scale) * g
     using Params = float;
     static constexpr int NS = 0;
+    static constexpr bool GRAD = true;
     static __device__ __forceinline__ void scale(Params& step, float s) { step *= s; }
     static __device__ __forceinline__ bool reads_state(const Params&) { return false; }
     static __device__ __forceinline__ void elem(float& p, float g, float&, float&, const Params& step) { p -= step * g; }
@@ -1306,6 +1307,7 @@ struct RuleSgd {                                        // plain SGD: bdn_sgd_st
 template <bool MOM> struct RuleSgdm {
     using Params = SgdmParams;
     static constexpr int NS = MOM ? 1 : 0;
+    static constexpr bool GRAD = true;
     static __device__ __forceinline__ void scale(Params& a, float s) { a.grad_scale *= s; }
     static __device__ __forceinline__ bool reads_state(const Params& a) { return MOM && !a.first; }
     static __device__ __forceinline__ void elem(float& p, float g, float& buf, float&, const Params& a) { sgdm_elem<MOM>(p, g, buf, a); }
@@ -1313,6 +1315,7 @@ template <bool MOM> struct RuleSgdm {
 struct RuleAdam {
     using Params = AdamParams;
     static constexpr int NS = 2;
+    static constexpr bool GRAD = true;
     static __device__ __forceinline__ void scale(Params& a, float s) { a.grad_scale *= s; }
     static __device__ __forceinline__ bool reads_state(const Params&) { return true; }
     static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v, const Params& a) { adam_elem(p, g, m, v, a); }
@@ -1335,7 +1338,7 @@ __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, con
     while (cap < t.n_seg) cap <<= 1;
     for (int k = threadIdx.x; k < cap; k += 256) {
         s_end[k] = k < t.n_seg ? t.end[k] : 0xffffffffu;
-        s_grp[k] = k < t.n_seg ? t.group[k] : OPT_FROZEN;
+        s_grp[k] = k < t.n_seg ? t.group[k] : (t.n_seg == 0 ? 0 : OPT_FROZEN);      // no table (bdn_ema_update): one segment of group 0
     }
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -1377,7 +1380,8 @@ __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, con
         for (int u = 0; u < OPT_VEC; u++) {
             const size_t i = b0 + u * stride + threadIdx.x;
             if (gid[u] != OPT_FROZEN) {
-                P[u] = reinterpret_cast<const float4*>(p)[i]; G[u] = reinterpret_cast<const float4*>(g)[i];
+                P[u] = reinterpret_cast<const float4*>(p)[i];
+                if (Rule::GRAD) G[u] = reinterpret_cast<const float4*>(g)[i];
                 if (Rule::NS > 0 && Rule::reads_state(s_par[0])) S0[u] = reinterpret_cast<const float4*>(s0)[i];
                 if (Rule::NS > 1) S1[u] = reinterpret_cast<const float4*>(s1)[i];
             }
@@ -1387,8 +1391,10 @@ __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, con
             const size_t i = b0 + u * stride + threadIdx.x;
             if (gid[u] != OPT_FROZEN) {
                 const typename Rule::Params q = s_par[gid[u]];
-                Rule::elem(P[u].x, G[u].x, S0[u].x, S1[u].x, q); Rule::elem(P[u].y, G[u].y, S0[u].y, S1[u].y, q);
-                Rule::elem(P[u].z, G[u].z, S0[u].z, S1[u].z, q); Rule::elem(P[u].w, G[u].w, S0[u].w, S1[u].w, q);
+                float4 g4 = {};                              // a rule without `g` never loaded G[u]: it is not read either
+                if constexpr (Rule::GRAD) g4 = G[u];
+                Rule::elem(P[u].x, g4.x, S0[u].x, S1[u].x, q); Rule::elem(P[u].y, g4.y, S0[u].y, S1[u].y, q);
+                Rule::elem(P[u].z, g4.z, S0[u].z, S1[u].z, q); Rule::elem(P[u].w, g4.w, S0[u].w, S1[u].w, q);
                 reinterpret_cast<float4*>(p)[i] = P[u];
                 if (Rule::NS > 0) reinterpret_cast<float4*>(s0)[i] = S0[u];
                 if (Rule::NS > 1) reinterpret_cast<float4*>(s1)[i] = S1[u];
@@ -1523,6 +1529,116 @@ extern "C" int bdn_adam_step_grouped_ex(float* params, const float* grads, float
     if (int rc = ex_check("adam_step_grouped_ex", dev_scale)) return rc;
     return adam_grouped_launch("adam_step_grouped_ex", params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr,
                                weight_decay, grad_scale, dev_scale, beta1, beta2, eps, decoupled_weight_decay, step, n, stream);
+}
+
+// ============================================================ averaged weights: EMA / SWA (torch.optim.swa_utils.AveragedModel)
+// avg = lerp(avg, p, w) as torch evaluates it (ATen lerp: w < 0.5 ? avg + w*(p - avg) : p - (p - avg)*(1 - w)), or avg = p for the first
+// update, and the in-place exchange of two flat buffers.  Both are rules of grouped_kernel above -- its LDS-staged segment lookup, its pass
+// shape (one float4 per lane, OPT_VEC in flight, every load issued before the first store), no atomics -- in which `p` is the average and
+// `g` the parameters (RuleEma), or `p` and `s0` the two buffers and no `g` at all (RuleSwap).  Every group id 0..7 counts alike: only
+// frozen vectors and vectors behind the table's end are skipped, in every buffer.
+struct EmaParams { float w; int copy, hi; };
+
+__device__ __forceinline__ void ema_elem(float& a, float p, const EmaParams& q) {
+    if (q.copy) a = p;
+    else a = q.hi ? p - (p - a) * (1.f - q.w) : a + q.w * (p - a);
+}
+
+struct RuleEma {
+    using Params = EmaParams;
+    static constexpr int NS = 0;
+    static constexpr bool GRAD = true;
+    static __device__ __forceinline__ void scale(Params&, float) {}
+    static __device__ __forceinline__ bool reads_state(const Params&) { return false; }
+    static __device__ __forceinline__ void elem(float& a, float p, float&, float&, const Params& q) { ema_elem(a, p, q); }
+};
+struct RuleSwap {                                       // bits are moved, never computed
+    using Params = int;
+    static constexpr int NS = 1;
+    static constexpr bool GRAD = false;
+    static __device__ __forceinline__ void scale(Params&, float) {}
+    static __device__ __forceinline__ bool reads_state(const Params&) { return true; }
+    static __device__ __forceinline__ void elem(float& a, float, float& b, float&, const Params&) { const float t = a; a = b; b = t; }
+};
+
+static int segments_check(const char* what, const void* a, const void* b, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, size_t n) {
+    if (!a || !b) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (n_seg < 0 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d segments (0..%d; 0: no table, every vector counts)", what, n_seg, OPT_MAX_SEGS);
+    if (n_seg > 0 && (!seg_end || !seg_group)) BDN_FAIL(BDN_E_ARG, "%s: null pointer (segment table of %d segments)", what, n_seg);
+    if (((uintptr_t)a | (uintptr_t)b) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
+    if (n_seg > 0 && (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3)) BDN_FAIL(BDN_E_ARG, "%s: segment table must be 4-byte aligned", what);
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
+    return BDN_OK;
+}
+
+static int ema_params(const char* what, float weight, int copy, EmaParams& q) {
+    if (!(weight >= 0.f && weight <= 1.f)) BDN_FAIL(BDN_E_ARG, "%s: weight = %g must lie in [0, 1]", what, (double)weight);
+    if (copy != 0 && copy != 1) BDN_FAIL(BDN_E_ARG, "%s: copy must be 0 or 1, got %d", what, copy);
+    q = EmaParams{weight, copy, weight >= 0.5f ? 1 : 0};
+    return BDN_OK;
+}
+
+extern "C" int bdn_ema_update(float* avg, const float* params, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float weight,
+                              int copy, size_t n, void* stream) {
+    if (int rc = segments_check("ema_update", avg, params, seg_end, seg_group, n_seg, n)) return rc;
+    EmaParams q;
+    if (int rc = ema_params("ema_update", weight, copy, q)) return rc;
+    if (n == 0) return BDN_OK;
+    GroupArgs<EmaParams> a{};
+    for (int k = 0; k < OPT_MAX_GROUPS; k++) a.g[k] = q;
+    const SegTable t{seg_end, seg_group, n_seg, OPT_MAX_GROUPS};
+    hipLaunchKernelGGL(grouped_kernel<RuleEma>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, avg, params, (float*)nullptr,
+                       (float*)nullptr, t, a, (const float*)nullptr, n / 4);
+    BDN_CHECK_LAUNCH("ema_update");
+    return BDN_OK;
+}
+
+extern "C" int bdn_swap_segments(float* a, float* b, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, size_t n, void* stream) {
+    if (int rc = segments_check("swap_segments", a, b, seg_end, seg_group, n_seg, n)) return rc;
+    if (a == b) BDN_FAIL(BDN_E_ARG, "swap_segments: a and b are the same buffer");
+    if (n == 0) return BDN_OK;
+    const SegTable t{seg_end, seg_group, n_seg, OPT_MAX_GROUPS};
+    hipLaunchKernelGGL(grouped_kernel<RuleSwap>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, a, (const float*)nullptr, b,
+                       (float*)nullptr, t, GroupArgs<int>{}, (const float*)nullptr, n / 4);
+    BDN_CHECK_LAUNCH("swap_segments");
+    return BDN_OK;
+}
+
+// The same rule over a device table of small tensors (the BatchNorm running statistics) in one launch: block row y owns tensor y and
+// grid-strides it, a float4 body where both pointers are 16-byte aligned and one element per lane for the rest.
+struct EmaDesc { float* avg; const float* src; int len, pad_; };
+constexpr int EMA_MULTI_MAX_BLOCKS = 64;
+
+__global__ void __launch_bounds__(256) ema_multi_kernel(const EmaDesc* __restrict__ desc, EmaParams q) {
+    const EmaDesc d = desc[blockIdx.y];
+    const int stride = gridDim.x * 256, tid = blockIdx.x * 256 + threadIdx.x;
+    const int n4 = ((((uintptr_t)d.avg | (uintptr_t)d.src) & 15) == 0 && d.len > 0) ? d.len / 4 : 0;
+    for (int i = tid; i < n4; i += stride) {
+        float4 a = reinterpret_cast<float4*>(d.avg)[i];
+        const float4 p = reinterpret_cast<const float4*>(d.src)[i];
+        ema_elem(a.x, p.x, q); ema_elem(a.y, p.y, q); ema_elem(a.z, p.z, q); ema_elem(a.w, p.w, q);
+        reinterpret_cast<float4*>(d.avg)[i] = a;
+    }
+    for (int i = n4 * 4 + tid; i < d.len; i += stride) {
+        float a = d.avg[i];
+        ema_elem(a, d.src[i], q);
+        d.avg[i] = a;
+    }
+}
+
+extern "C" int bdn_ema_update_multi(const void* desc_dev, int n_tensors, int max_len, float weight, int copy, void* stream) {
+    if (!desc_dev) BDN_FAIL(BDN_E_ARG, "ema_update_multi: null pointer");
+    if ((uintptr_t)desc_dev & 7) BDN_FAIL(BDN_E_ARG, "ema_update_multi: the descriptor table must be 8-byte aligned");
+    if (n_tensors < 0 || n_tensors > 65535 || max_len < 0) BDN_FAIL(BDN_E_SHAPE, "ema_update_multi: n_tensors=%d (0..65535) max_len=%d", n_tensors, max_len);
+    EmaParams q;
+    if (int rc = ema_params("ema_update_multi", weight, copy, q)) return rc;
+    if (n_tensors == 0 || max_len == 0) return BDN_OK;
+    const int want = (max_len + 1023) / 1024;
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(want < EMA_MULTI_MAX_BLOCKS ? want : EMA_MULTI_MAX_BLOCKS, n_tensors), dim3(256), 0,
+                       (hipStream_t)stream, static_cast<const EmaDesc*>(desc_dev), q);
+    BDN_CHECK_LAUNCH("ema_update_multi");
+    return BDN_OK;
 }
 
 // ============================================================ gradient accumulation and the global gradient norm (clip_grad_norm_)

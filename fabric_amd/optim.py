@@ -110,6 +110,35 @@ def check_max_grad_norm(x):
     return float(x)
 
 
+AVERAGES = ('ema', 'swa')
+
+
+def check_ema(ema_decay=None, average='ema', ema_every=1, ema_start=0):
+    """The fused step's weight-averaging keywords -> (on, decay or None, average, every, start).  The average is on when `ema_decay` is a
+    number (average='ema': an exponential moving average, weight 1 - decay) or average='swa' (the equal-weight running mean, weight
+    1 / (n_averaged + 1); it takes no decay).  ValueError: a decay outside [0, 1), ema_every < 1, ema_start < 0, an unknown average, or
+    'swa' together with a decay (bools are refused everywhere: they are numbers to Python only)."""
+    if average not in AVERAGES:
+        raise ValueError(f'average {average!r}: expected one of {AVERAGES}')
+    if ema_decay is not None:
+        if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay < 1.0:       # NaN fails both
+            raise ValueError(f'invalid ema_decay: {ema_decay!r} (must be a number in [0, 1), or None)')
+        if average == 'swa':
+            raise ValueError(f"average='swa' is the equal-weight mean and takes no ema_decay (got {ema_decay!r})")
+        ema_decay = float(ema_decay)
+    if isinstance(ema_every, bool) or not isinstance(ema_every, int) or ema_every < 1:
+        raise ValueError(f'invalid ema_every: {ema_every!r} (must be an integer >= 1)')
+    if isinstance(ema_start, bool) or not isinstance(ema_start, int) or ema_start < 0:
+        raise ValueError(f'invalid ema_start: {ema_start!r} (must be an integer >= 0)')
+    return ema_decay is not None or average == 'swa', ema_decay, average, ema_every, ema_start
+
+
+def average_weight(average, decay, n_averaged):
+    """The lerp weight of the next averaging update, in double: 1 - decay (EMA) or 1 / (n_averaged + 1) (SWA), as
+    torch.optim.swa_utils forms it; the kernels take it rounded to float32."""
+    return 1.0 - decay if average == 'ema' else 1.0 / (n_averaged + 1)
+
+
 def flat_to_torch(cfg, layout, names, flat_state, step):
     """torch.optim's ``state_dict()`` of the flat state: ``flat_state`` maps cfg.state_keys() to flat buffers in ``layout``, ``names``
     lists the parameter names in ``model.parameters()`` order, ``step`` is the number of updates applied.  Every tensor is a copy.
@@ -353,3 +382,54 @@ def torch_to_groups(sd, groups, layout, device=None):
     else:
         step = 1 if present else 0
     return cfg, None if mine is None else [{'lr': c.lr, 'weight_decay': c.weight_decay} for c in cfgs], flat, step
+
+
+# ------------------------------------------------------------------ averaged weights in torch.optim.swa_utils.AveragedModel's format
+AVG_COUNT = 'n_averaged'
+AVG_PREFIX = 'module.'
+
+
+def avg_to_torch(layout, keys, flat_avg, buffers, n_averaged):
+    """``AveragedModel(model).state_dict()`` of the flat average: 'n_averaged' (int64 scalar, on the CPU, where AveragedModel(model)
+    keeps its count) and 'module.<key>' for every key of ``keys`` (the model's state_dict() order) -- a view of ``flat_avg`` in
+    ``layout`` for a parameter, ``buffers[key]`` for a buffer.  Every tensor is a copy."""
+    out = {AVG_COUNT: torch.tensor(int(n_averaged), dtype=torch.int64)}
+    for k in keys:
+        out[AVG_PREFIX + k] = (layout.view(flat_avg, k) if k in layout.slices else buffers[k]).clone()
+    return out
+
+
+def torch_to_avg(sd, layout, keys, buffers):
+    """Inverse of avg_to_torch, checked before anything is written: (n_averaged, {key: tensor of sd}) for every key of ``keys``.
+    ``buffers``: {key: a tensor of the expected shape} for the keys that are not parameters.  ValueError: no integer scalar
+    'n_averaged', missing or unexpected keys, a wrong shape."""
+    n = sd.get(AVG_COUNT)
+    if not (torch.is_tensor(n) and n.numel() == 1 and not n.dtype.is_floating_point and n.dtype != torch.bool) and \
+            not (isinstance(n, int) and not isinstance(n, bool)):
+        raise ValueError(f"averaged state: {AVG_COUNT!r} must be an integer scalar (AveragedModel's update count)")
+    if int(n) < 0:
+        raise ValueError(f'averaged state: {AVG_COUNT} = {int(n)}')
+    want = [AVG_PREFIX + k for k in keys]
+    missing = [k for k in want if k not in sd]
+    known = set(want)
+    extra = [k for k in sd if k != AVG_COUNT and k not in known]
+    if missing or extra:
+        raise ValueError(f'averaged state: {len(missing)} missing key(s) {missing[:3]}, {len(extra)} unexpected key(s) {extra[:3]}')
+    out = {}
+    for k in keys:
+        shape = layout.slices[k][2] if k in layout.slices else tuple(buffers[k].shape)
+        v = sd[AVG_PREFIX + k]
+        if not torch.is_tensor(v) or tuple(v.shape) != tuple(shape):
+            raise ValueError(f'averaged state: {k} has shape {tuple(getattr(v, "shape", ()))}, the model {tuple(shape)}')
+        out[k] = v.detach()
+    return int(n), out
+
+
+def is_averaged_state(sd):
+    """An AveragedModel state dict: every key 'module.'-prefixed except an integer scalar 'n_averaged'."""
+    if not isinstance(sd, dict) or AVG_COUNT not in sd or len(sd) < 2:
+        return False
+    n = sd[AVG_COUNT]
+    if not (torch.is_tensor(n) and n.numel() == 1 and not n.dtype.is_floating_point and n.dtype != torch.bool):
+        return False
+    return all(isinstance(k, str) and k.startswith(AVG_PREFIX) for k in sd if k != AVG_COUNT)

@@ -9,11 +9,13 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --freeze inc --optimizer adamw
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --accumulate 4 --max_grad_norm 1.0
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --ignore_label 255
+    python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --ema_decay 0.999        # validate and save the averaged weights
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
 predicted tile by tile (utils/inference.py) -- here on the device-resident city stacks -- and written as PNG masks.
 """
 import argparse
+import contextlib
 import json
 import os
 import re
@@ -255,11 +257,14 @@ def resume_from(path, device=None, precision=None):
     return model, opt_sd, epoch + 1
 
 
-def save_if_better(model, mean_val_metrics, best_metrics, metadata, epoch, out_dir, optimizer_state=None):
+def save_if_better(model, mean_val_metrics, best_metrics, metadata, epoch, out_dir, optimizer_state=None, ema_state=None):
     """train.py:207-227: when validation precision, recall OR F1 improved, write `checkpoint_epoch_N.pt` (the pickled
     module, as the reference does with torch.save(model, ...)) and `metadata_epoch_N.json` (the run's metadata plus
-    `validation_metrics`), and, when `optimizer_state` (torch.optim's state_dict() format) holds any state, `optimizer_epoch_N.pt`.
-    The upload to the outputs store / comet is out of scope.  Returns the new best metrics."""
+    `validation_metrics`), and, when `optimizer_state` (torch.optim's state_dict() format) holds any state, `optimizer_epoch_N.pt`,
+    and, when `ema_state` (TrainStep.ema_state_dict()'s output, torch.optim.swa_utils.AveragedModel's format, or a callable that returns
+    it, called only when something is written) is given, `ema_epoch_N.pt`, which
+    load_checkpoint reads as a BiDateNet on the averaged weights.  The upload to the outputs store / comet is out of scope.  Returns the
+    new best metrics."""
     keys = ('cd_precisions', 'cd_recalls', 'cd_f1scores')
     if not any(mean_val_metrics[k] > best_metrics[k] for k in keys):
         return best_metrics
@@ -276,6 +281,9 @@ def save_if_better(model, mean_val_metrics, best_metrics, metadata, epoch, out_d
                os.path.join(out_dir, f'checkpoint_epoch_{epoch}.state_dict.pt'))
     if optimizer_state is not None and optimizer_state['state']:
         torch.save(_to_cpu(optimizer_state), os.path.join(out_dir, f'optimizer_epoch_{epoch}.pt'))
+    if ema_state is not None:
+        ema_state = ema_state() if callable(ema_state) else ema_state
+        torch.save(_to_cpu(ema_state), os.path.join(out_dir, f'ema_epoch_{epoch}.pt'))
     return mean_val_metrics
 
 
@@ -332,8 +340,16 @@ def main(argv=None):
                     help='fused step: update on every K-th batch with the mean gradient of the K batches (one gradient exchange per update)')
     ap.add_argument('--max_grad_norm', type=float, default=None, metavar='X',
                     help='fused step: clip the gradients to a global L2 norm of X (torch.nn.utils.clip_grad_norm_); inf: measure only')
-    ap.add_argument('--resume', default=None, help='DIR/checkpoint_epoch_N.state_dict.pt (and its sibling optimizer_epoch_N.pt): '
-                                                   'continue at epoch N + 1 of --epochs')
+    ap.add_argument('--ema_decay', type=float, default=None, metavar='D',
+                    help='--fused_step true only: keep an exponential moving average of the weights (decay D in [0, 1), '
+                         'torch.optim.swa_utils.AveragedModel); validation and the full scenes run on it, and ema_epoch_N.pt is written')
+    ap.add_argument('--swa', action='store_true', help='--fused_step true only: the equal-weight running mean of the weights (SWA) instead; no --ema_decay')
+    ap.add_argument('--ema_every', type=int, default=1, metavar='N', help='average on every N-th update')
+    ap.add_argument('--ema_start', type=int, default=0, metavar='N', help='start averaging after the first N updates of the run (a --resume that loads a running average does not wait again)')
+    ap.add_argument('--ema_buffers', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=True,
+                    help='true: running_mean / running_var are averaged too (use_buffers=True); false: the averaged model uses the live ones')
+    ap.add_argument('--resume', default=None, help='DIR/checkpoint_epoch_N.state_dict.pt (and its siblings optimizer_epoch_N.pt, '
+                                                   'ema_epoch_N.pt): continue at epoch N + 1 of --epochs')
     ap.add_argument('--init_from', default=None, help='a checkpoint load_checkpoint reads (the reference\'s pickles and module.-prefixed '
                                                       'state dicts included): weights and BatchNorm buffers only, training starts at epoch 0 '
                                                       'with a fresh optimizer -- the fine-tuning start')
@@ -404,6 +420,15 @@ def main(argv=None):
     if (opt.accumulate != 1 or opt.max_grad_norm is not None) and opt.loss_function != 'tversky' and not opt.fused_step:
         raise SystemExit(f'--accumulate / --max_grad_norm are built into the fused step, which runs --loss_function tversky only '
                          f'(got {opt.loss_function}) unless --fused_step true is given')
+    from .optim import check_ema
+    try:
+        averaging = check_ema(opt.ema_decay, 'swa' if opt.swa else 'ema', opt.ema_every, opt.ema_start)[0]
+    except ValueError as e:
+        raise SystemExit(f'--ema_decay / --swa / --ema_every / --ema_start: {e}')
+    if (averaging or opt.ema_every != 1 or opt.ema_start != 0 or not opt.ema_buffers) and not opt.fused_step:
+        raise SystemExit('--ema_decay / --swa / --ema_every / --ema_start / --ema_buffers are built into the fused step: add --fused_step true')
+    if not averaging and (opt.ema_every != 1 or opt.ema_start != 0 or not opt.ema_buffers):
+        raise SystemExit('--ema_every / --ema_start / --ema_buffers shape an average that is not on: add --ema_decay D or --swa')
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
 
@@ -465,11 +490,17 @@ def main(argv=None):
             groups = fine_tune_groups(model, opt.learning_rate, opt.weight_decay, opt.freeze, opt.no_decay_norm_bias, opt.lr_scale)
             step = TrainStep(model, lr=opt.learning_rate, tversky_alpha=opt.tversky_alpha, tversky_beta=opt.tversky_beta,
                              param_groups=groups, bn='frozen' if opt.frozen_bn else 'batch', criterion=step_criterion,
-                             accumulate=opt.accumulate, max_grad_norm=opt.max_grad_norm, **optimizer_kwargs(opt))
+                             accumulate=opt.accumulate, max_grad_norm=opt.max_grad_norm, ema_decay=opt.ema_decay,
+                             average='swa' if opt.swa else 'ema', ema_every=opt.ema_every, ema_start=opt.ema_start,
+                             ema_buffers=opt.ema_buffers, **optimizer_kwargs(opt))
         except ValueError as e:
             raise SystemExit(f'parameter groups: {e}')
         if opt_sd is not None:
             step.load_optimizer_state_dict(opt_sd)
+        if averaging and opt.resume:                       # the averaged weights of the epoch resumed from, when that run kept them
+            ema_path = os.path.join(os.path.dirname(opt.resume), f'ema_epoch_{first_epoch - 1}.pt')
+            if os.path.exists(ema_path):
+                step.load_ema_state_dict(torch.load(ema_path, map_location='cpu', weights_only=True))
         if world > 1:
             # measure (and, if it is the slow one, repair) the placement of RCCL's collective stream BEFORE the loop adopts the chain's stream
             rep = step.guard_collectives(opt.batch_size, opt.patch_size, opt.patch_size)
@@ -490,37 +521,45 @@ def main(argv=None):
             tr = train_epoch(step, train_loader, dev, opt.patch_size, feeder)
         else:
             tr = train_epoch_autograd(model, criterion, optimizer, train_loader, dev, opt.patch_size, world, feeder)
-        va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder, ignore_index=opt.ignore_label)
-        if rank == 0:
-            print(json.dumps({'epoch': epoch, **{'train_' + k: float(v) for k, v in tr.items()},
-                              **{'validate_' + k: float(v) for k, v in va.items()}}), flush=True)
-        if scenes is not None and rank == 0:                   # train.py:182-205: full validation images
-            from .utils import ingest
-            from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
-            os.makedirs(opt.log_dir, exist_ok=True)
-            model.eval()
-            scene_counts = {}
-            for city in val_cities:
-                st = scenes[city]['images']
-                if opt.scene_stride > 0:
-                    proba, mask = predict_scene_blended(model, st[0], st[1], patch_size=opt.patch_size, stride=opt.scene_stride,
-                                                        window=opt.scene_window, symmetries=TTA_SYMMETRIES[opt.scene_tta],
-                                                        batch_size=opt.batch_size)
-                    ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}_proba.png'),
-                                          torch.round(proba[1] * 255).to(torch.uint8).cpu().numpy())
-                    scene_counts[city] = scene_scores(mask.cpu().numpy(), scenes[city]['labels'])
-                else:
-                    mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
-                ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}.png'), (mask * 255).cpu().numpy())
-            if opt.scene_stride > 0:
-                print(json.dumps({'epoch': epoch, 'scene': scene_counts}), flush=True)
+        with step.ema_weights() if averaging else contextlib.nullcontext():       # --ema_decay / --swa: evaluate the averaged weights
+            va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder, ignore_index=opt.ignore_label)
+            if rank == 0:
+                print(json.dumps({'epoch': epoch, **{'train_' + k: float(v) for k, v in tr.items()},
+                                  **{'validate_' + k: float(v) for k, v in va.items()},
+                                  **({'ema_n_averaged': step.n_averaged} if averaging else {})}), flush=True)
+            if scenes is not None and rank == 0:               # train.py:182-205: full validation images
+                _predict_scenes(model, scenes, val_cities, opt, epoch)
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
-                                  step.optimizer_state_dict() if fused else optimizer.state_dict())
+                                  step.optimizer_state_dict() if fused else optimizer.state_dict(),
+                                  step.ema_state_dict if averaging else None)
     if feeder is not None:
         feeder.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def _predict_scenes(model, scenes, val_cities, opt, epoch):
+    """train.py:182-205: the full validation scenes of one epoch, written as PNG masks (and, blended, as probabilities with a scene F1 line)."""
+    from .utils import ingest
+    from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
+    os.makedirs(opt.log_dir, exist_ok=True)
+    model.eval()
+    scene_counts = {}
+    for city in val_cities:
+        st = scenes[city]['images']
+        if opt.scene_stride > 0:
+            proba, mask = predict_scene_blended(model, st[0], st[1], patch_size=opt.patch_size, stride=opt.scene_stride,
+                                                window=opt.scene_window, symmetries=TTA_SYMMETRIES[opt.scene_tta],
+                                                batch_size=opt.batch_size)
+            ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}_proba.png'),
+                                  torch.round(proba[1] * 255).to(torch.uint8).cpu().numpy())
+            scene_counts[city] = scene_scores(mask.cpu().numpy(), scenes[city]['labels'])
+        else:
+            mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
+        ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}.png'), (mask * 255).cpu().numpy())
+    if opt.scene_stride > 0:
+        print(json.dumps({'epoch': epoch, 'scene': scene_counts}), flush=True)
 
 
 if __name__ == '__main__':

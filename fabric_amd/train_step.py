@@ -10,6 +10,8 @@ module's nn.Parameters are re-pointed at views of them, so ``model.state_dict()`
 ``model.parameters()`` and ``p.grad`` keep working for callers that expect the reference's
 surface.
 """
+import contextlib
+
 import torch
 import torch.distributed as dist
 
@@ -23,7 +25,8 @@ class TrainStep:
     def __init__(self, model, lr=1e-3, tversky_alpha=0.1, tversky_beta=0.9, eps=1e-7,
                  process_group=None, n_buckets=4, distributed=True, force_collectives=False, guard=True,
                  optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8,
-                 param_groups=None, bn='batch', criterion=None, accumulate=1, max_grad_norm=None):
+                 param_groups=None, bn='batch', criterion=None, accumulate=1, max_grad_norm=None,
+                 ema_decay=None, average='ema', ema_every=1, ema_start=0, ema_buffers=True):
         """optimizer: 'sgd' (torch.optim.SGD: momentum, dampening, nesterov, weight_decay), 'adam' or 'adamw' (torch.optim.Adam / AdamW:
         betas, adam_eps, weight_decay); weight_decay=None is torch's default (0 for sgd and adam, 1e-2 for adamw).  The default, plain
         SGD, is the reference's optim.SGD(lr) (train.py:55) and keeps no state; the other rules keep theirs in flat f32 buffers in the
@@ -68,12 +71,37 @@ class TrainStep:
         them), and the update reads the coefficient from there (bdn_*_step_grouped_ex): no host synchronisation, no pass that rescales
         the gradients.  flat_grads, and with it p.grad, therefore keeps the UNCLIPPED (and unaveraged) sum.
 
+        ema_decay, average, ema_every, ema_start, ema_buffers: an averaged copy of the weights, torch.optim.swa_utils.AveragedModel's.
+        On when ema_decay is a number in [0, 1) (average='ema': avg = lerp(avg, p, 1 - ema_decay)) or average='swa' (the equal-weight
+        running mean, avg = lerp(avg, p, 1 / (n_averaged + 1)); no decay); off, the default, nothing is allocated or launched and
+        `flat_avg` is None.  `flat_avg` is one more flat buffer in `layout` (it starts as a clone of flat_params), `avg_buffers` holds one
+        tensor per averaged BatchNorm buffer by state-dict key, `n_averaged` is a host int.  The averaging update is ONE launch
+        (bdn_ema_update) on the step's stream right after the optimizer update of an updating call -- never on a micro-step of
+        accumulate=K, also after flush() -- of the u-th update of this step object when u > ema_start and (u - ema_start) is a multiple
+        of ema_every.  The first averaging update is a copy, as AveragedModel's is; the weight is formed in double on the host and
+        passed as float32.  Frozen parameters are skipped through the step's segment table, and a frozen tensor's average is its value:
+        set_param_groups() re-reads the table and sets the average of every tensor that is frozen then to the tensor's value (its
+        history is dropped: the value is constant from there on, and ema_weights() and ema_state_dict() keep describing one model).
+        ema_start counts the updates of this step object; load_ema_state_dict() of a state with n_averaged > 0 ends the delay (a
+        resumed run goes on averaging at once, the ema_every phase starting at the load).  ema_buffers=True (AveragedModel(use_buffers=True)): running_mean / running_var are
+        averaged with the same weight in one more launch (bdn_ema_update_multi, its descriptor uploaded once); False
+        (use_buffers=False): the averaged model uses the live buffers.  num_batches_tracked is NEVER averaged, the averaged model
+        carries the live count: a deliberate departure from AveragedModel(use_buffers=True), which pushes the int64 count through the
+        float formula.  Data-parallel: every rank holds bit-identical parameters after the update, so every rank computes the same
+        average and nothing is communicated (the BatchNorm buffers are per rank, as they always were; rank 0's are saved).
+        ema_state_dict() / load_ema_state_dict() exchange the state in AveragedModel's format; `with step.ema_weights():` evaluates
+        on the averaged weights.
+
         guard: when the step issues collectives (world > 1, or force_collectives) and guard_collectives() has not been called, the
         first step() runs it in its measure-only form (replace_streams=False: it may defer the buckets, it never swaps a stream the
         caller may already have adopted) and reports / warns about a stream arrangement in which they slow the step down."""
         if bn not in ('batch', 'frozen'):
             raise ValueError(f"bn must be 'batch' or 'frozen', got {bn!r}")
         self.accumulate = _optim.check_accumulate(accumulate)
+        ema_on, self.ema_decay, self.average, self.ema_every, self.ema_start = _optim.check_ema(ema_decay, average, ema_every, ema_start)
+        self.ema_buffers = bool(ema_buffers)
+        self.flat_avg, self.avg_buffers, self.n_averaged = None, {}, 0
+        self._updates, self._ema_hold, self._swapped, self._avg_desc = 0, False, False, None
         self.max_grad_norm = _optim.check_max_grad_norm(max_grad_norm)
         self.micro = 0
         self.flat_accum = self._norm = self._clip_table = None
@@ -138,6 +166,8 @@ class TrainStep:
             self.last_grad_norm, self.last_clip_coef = out[0], out[1]
             if self._groups is None:
                 self._implicit_table()                       # uploaded now: the step itself never waits for the device
+        if ema_on:
+            self._init_average()
 
     def _implicit_table(self):
         """The clipped update runs the grouped (_ex) entry points; without groups or frozen parameters, on one implicit group of every
@@ -151,6 +181,68 @@ class TrainStep:
                                      torch.tensor(ids, dtype=torch.int32).to(dev), len(ends)))
         return self._clip_table
 
+    def _init_average(self):
+        """flat_avg (a clone of flat_params), and with ema_buffers the averaged running statistics: views of one flat buffer, a scratch
+        copy of it for the exchange, and the two descriptor tables of bdn_ema_update_multi ({average <- live}, {live <- scratch})."""
+        import struct
+        dev = self.flat_params.device
+        self.flat_avg = self.flat_params.clone()
+        if not self.ema_buffers:
+            return
+        keys = [k for k in self._P if k.endswith(('.running_mean', '.running_var'))]
+        if not keys:
+            return
+        offs, total = {}, 0
+        for k in keys:
+            offs[k] = total
+            total += (self._P[k].numel() + 3) // 4 * 4            # every view starts on a float4
+        flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        tmp = torch.empty_like(flat)
+        upd = back = b''
+        for k in keys:
+            live = self._P[k]
+            if live.dtype != torch.float32 or not live.is_contiguous():
+                raise RuntimeError(f'fabric_amd: BatchNorm buffer {k} must be contiguous float32')
+            n = live.numel()
+            v = flat[offs[k]:offs[k] + n].view(live.shape)
+            v.copy_(live)
+            self.avg_buffers[k] = v
+            upd += struct.pack('<QQii', v.data_ptr(), live.data_ptr(), n, 0)
+            back += struct.pack('<QQii', live.data_ptr(), tmp.data_ptr() + 4 * offs[k], n, 0)
+        up = lambda rec: torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(dev)
+        self._avg_desc = (up(upd), up(back), len(keys), max(self._P[k].numel() for k in keys), flat, tmp)
+
+    def _table(self):
+        """(seg_end, seg_group, n_seg) device addresses of the step's segment table for the averaging kernels; n_seg = 0 without groups
+        or frozen parameters: every vector counts."""
+        if self._groups is None:
+            return None, None, 0
+        ends, ids, n_seg = self._seg
+        return ends.data_ptr(), ids.data_ptr(), n_seg
+
+    def _average(self, st):
+        """Count one optimizer update and, when it is due, fold the new parameters (and running statistics) into the average on `st`."""
+        if self.flat_avg is None or self._ema_hold:
+            return
+        self._updates += 1
+        u = self._updates - self.ema_start
+        if u <= 0 or u % self.ema_every:
+            return
+        copy = int(self.n_averaged == 0)
+        w = 0.0 if copy else _optim.average_weight(self.average, self.ema_decay, self.n_averaged)
+        _lib.call('bdn_ema_update', self.flat_avg.data_ptr(), self.flat_params.data_ptr(), *self._table(), w, copy, self.layout.total, st)
+        if self._avg_desc is not None:
+            _lib.call('bdn_ema_update_multi', self._avg_desc[0].data_ptr(), self._avg_desc[2], self._avg_desc[3], w, copy, st)
+        self.n_averaged += 1
+
+    def _need_average(self, what):
+        if self.flat_avg is None:
+            raise RuntimeError(f"{what}: this step keeps no averaged weights (build it with ema_decay=... or average='swa')")
+
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f'{what}: not inside `with step.ema_weights()`, where the live and the averaged weights are exchanged')
+
     def _no_pending(self, what):
         if self.micro != 0:
             raise RuntimeError(f'{what}: {self.micro} of {self.accumulate} micro-steps are pending; call flush() (or flush(apply=False)) first')
@@ -162,6 +254,7 @@ class TrainStep:
         optimizer state of parameters that stay trainable is kept; that of a parameter frozen now is zeroed, so it starts afresh if it
         is released later (with the step's one update count).  Raises ValueError as fabric_amd.optim.ParamGroups does."""
         self._no_pending('set_param_groups()')
+        self._not_swapped('set_param_groups()')
         dev = self.flat_params.device
         pg = self._checked_groups(groups)
         hp, cur = self.stream(dev), torch.cuda.current_stream(dev)
@@ -177,6 +270,11 @@ class TrainStep:
             self.grads[k].zero_()
             for t in self.opt_state.values():
                 self.layout.view(t, k).zero_()
+            if self.flat_avg is not None:
+                # a frozen tensor's average is its value: the exchange of ema_weights() skips frozen vectors, so an average left behind
+                # its (now constant) tensor would make the model inside the block differ from ema_state_dict(); the value is also what
+                # an average of the constant converges to
+                self.layout.view(self.flat_avg, k).copy_(self.layout.view(self.flat_params, k))
         hp.wait_stream(cur)
         self._groups, self._seg = pg, seg
         self.param_groups = pg.groups
@@ -209,6 +307,7 @@ class TrainStep:
         weight-gradient GEMMs run beside it on a normal-priority stream (engine.backward), so the chain's kernels get
         compute units first (A/B tools/archive/ab_prio.py: -0.8 % step time).  The caller's current stream is joined on both
         sides, so the usual stream semantics hold for inputs and outputs."""
+        self._not_swapped('step()')
         if self._guard and self.collectives_report is None and self.bucketer.active():
             # measure only: the caller may already run its loop on step.stream(), which must not be swapped under it
             self.guard_collectives(*[int(v) for v in (x_d1.shape[0], x_d1.shape[2], x_d1.shape[3])], replace_streams=False)
@@ -232,6 +331,7 @@ class TrainStep:
         set of bucket all-reduces, the norm if clipping is on, and the update with the mean of the m gradients (grad_scale =
         1 / (world * m)); returns True.  apply=False drops the pending gradients (returns False).  With nothing pending nothing is
         launched and False is returned.  Every rank must call it alike (it issues collectives)."""
+        self._not_swapped('flush()')
         m = self.micro
         if m == 0:
             return False
@@ -357,6 +457,7 @@ class TrainStep:
             saved_acc = (self.accumulate, self.micro, None if self.flat_accum is None else self.flat_accum.clone(),
                          None if self._norm is None else self._norm[1].clone())
             self.accumulate, self.micro = 1, 0
+            self._ema_hold = True                                       # the timed steps are not updates of the run: not averaged
 
             def timed(collectives, defer=False):
                 self.bucketer.enabled, self.bucketer.defer = collectives, defer
@@ -421,6 +522,7 @@ class TrainStep:
             ok = True
         finally:
             self.bucketer.enabled = True
+            self._ema_hold = False
             if not ok:
                 self.bucketer.defer = False
                 # a measurement raised (OOM, RCCL error) while a remedy's stream was in place: back to the arrangement the guard started
@@ -506,14 +608,16 @@ class TrainStep:
                       _lib.stream_ptr())
 
     def _apply(self, st, grad_scale):
-        """The norm (when clipping is on) and the update, with g = grad_scale * flat_grads."""
+        """The norm (when clipping is on), the update with g = grad_scale * flat_grads, and the averaging update when one is due."""
         if self._norm is None:
-            return self._update(st, grad_scale)
+            self._update(st, grad_scale)
+            return self._average(st)
         ws, out = self._norm
         pg, (ends, ids, n_seg) = (self._groups, self._seg) if self._groups is not None else self._implicit_table()
         _lib.call('bdn_grad_norm', self.flat_grads.data_ptr(), ends.data_ptr(), ids.data_ptr(), n_seg, grad_scale, self.max_grad_norm,
                   ws.data_ptr(), out.data_ptr(), self.layout.total, st)
         self._update_grouped(st, grad_scale, out.data_ptr() + 4)
+        self._average(st)
 
     def _tversky_loss(self, logits, labels, st):
         """The default criterion: bdn_tversky on persistent buffers -> (loss, counts, dlogits)."""
@@ -600,6 +704,7 @@ class TrainStep:
         live buffers.  With parameter groups: one 'param_groups' entry per group and no state for a frozen parameter, which is what
         torch.optim built with the same groups holds (fabric_amd.optim.groups_to_torch)."""
         self._no_pending('optimizer_state_dict()')
+        self._not_swapped('optimizer_state_dict()')
         self.optim.lr = float(self.lr)
         self.stream(self.flat_params.device)
         torch.cuda.current_stream(self.flat_params.device).wait_stream(self._hp)        # after the last step's update
@@ -616,6 +721,7 @@ class TrainStep:
         groups the state of an optimizer built with the same groups is expected (fabric_amd.optim.torch_to_groups; a single-group state
         over all parameters is accepted too and leaves the groups' lr / weight_decay as they are)."""
         self._no_pending('load_optimizer_state_dict()')
+        self._not_swapped('load_optimizer_state_dict()')
         dev = self.flat_params.device
         if self._groups is not None:
             cfg, hyper, flat, step = _optim.torch_to_groups(sd, self._groups, self.layout, dev)
@@ -635,3 +741,93 @@ class TrainStep:
                     g.update(h)
                 cfg.lr, cfg.weight_decay = hyper[0]['lr'], hyper[0]['weight_decay']
         self.optim, self.lr, self.opt_state, self.opt_step = cfg, cfg.lr, flat, step
+
+    # ------------------------------------------------------------------ averaged weights in torch.optim.swa_utils.AveragedModel's format
+    def _avg_entries(self):
+        """{state-dict key: the tensor the averaged model holds for a buffer}: the averaged running statistics with ema_buffers, the live
+        ones without, and always the live num_batches_tracked."""
+        return {k: self.avg_buffers.get(k, v) for k, v in self._P.items() if k not in self.layout.slices}
+
+    def ema_state_dict(self):
+        """The averaged model as ``torch.optim.swa_utils.AveragedModel(model, use_buffers=ema_buffers).state_dict()`` holds it:
+        'n_averaged' (int64 scalar) and 'module.<key>' for every parameter and buffer (with ema_buffers=False the live buffers, as torch
+        keeps them in sync; num_batches_tracked is always the live count).  It loads into an AveragedModel with
+        load_state_dict(strict=True) and, through fabric_amd.utils.helpers.load_checkpoint, gives a BiDateNet on the averaged weights.
+        Until the first averaging update (n_averaged == 0) the average IS the live model.  The tensors are copies taken on the current
+        stream after the step's stream."""
+        self._need_average('ema_state_dict()')
+        self._no_pending('ema_state_dict()')
+        self._not_swapped('ema_state_dict()')
+        dev = self.flat_params.device
+        torch.cuda.current_stream(dev).wait_stream(self.stream(dev))                     # after the last step's averaging update
+        if self.n_averaged == 0:
+            return _optim.avg_to_torch(self.layout, list(self._P), self.flat_params, self._P, 0)
+        return _optim.avg_to_torch(self.layout, list(self._P), self.flat_avg, self._avg_entries(), self.n_averaged)
+
+    def load_ema_state_dict(self, sd):
+        """Load an AveragedModel ``state_dict()`` of this model (or ema_state_dict()'s output): the averaged parameters, with
+        ema_buffers the averaged running_mean / running_var, and n_averaged.  The saved num_batches_tracked (and, with
+        ema_buffers=False, the saved running statistics) are checked for their shape and otherwise ignored: the averaged model uses the
+        live ones.  With n_averaged > 0 the ema_start delay is over: the next update is averaged (then every ema_every-th).  Raises ValueError on missing or unexpected keys or wrong shapes, before anything is written."""
+        self._need_average('load_ema_state_dict()')
+        self._no_pending('load_ema_state_dict()')
+        self._not_swapped('load_ema_state_dict()')
+        dev = self.flat_params.device
+        n, vals = _optim.torch_to_avg(sd, self.layout, list(self._P), self._avg_entries())
+        hp, cur = self.stream(dev), torch.cuda.current_stream(dev)
+        cur.wait_stream(hp)                                                              # a step in flight still writes the average
+        for k, v in vals.items():
+            dst = self.layout.view(self.flat_avg, k) if k in self.layout.slices else self.avg_buffers.get(k)
+            if dst is not None:
+                dst.copy_(v.to(device=dev, dtype=torch.float32))
+        hp.wait_stream(cur)                                                              # ordered before the next step
+        self.n_averaged = n
+        if n > 0:                                            # the average was running already: no second start delay
+            self._updates = max(self._updates, self.ema_start)
+
+    def _exchange(self):
+        """Exchange the live and the averaged parameters (and running statistics) in place on the step's stream, ordered against the
+        caller's current stream on both sides, and re-derive what the engine keeps of their values: the packed GEMM images and the
+        folded eval-mode BatchNorm tables."""
+        dev = self.flat_params.device
+        eng = self.model.engine()
+        hp, cur = self.stream(dev), torch.cuda.current_stream(dev)
+        hp.wait_stream(cur)
+        if self.n_averaged == 0:
+            # The average is the live model still (ema_state_dict() says the same): nothing is exchanged, and nothing is repacked or
+            # refolded either.  That relies on no VALUE having changed; if a state with n_averaged == 0 ever comes to carry other
+            # weights than the live ones, this branch has to exchange and refresh like the other.
+            return cur.wait_stream(hp)
+        with torch.cuda.stream(hp):
+            st = _lib.stream_ptr()
+            _lib.call('bdn_swap_segments', self.flat_params.data_ptr(), self.flat_avg.data_ptr(), *self._table(), self.layout.total, st)
+            if self._avg_desc is not None:                   # scratch = average; average = live; live = scratch
+                upd, back, n, max_len, flat, tmp = self._avg_desc
+                tmp.copy_(flat)
+                _lib.call('bdn_ema_update_multi', upd.data_ptr(), n, max_len, 0.0, 1, st)
+                _lib.call('bdn_ema_update_multi', back.data_ptr(), n, max_len, 0.0, 1, st)
+            eng.invalidate_weights()                         # in-place writes bump no version counter (BiDateEngine._check_packed)
+            eng._weights(eng.layers[0], self._P, False)
+            if eng._use_eval_schedule():
+                eng.eval_tables(self._P)
+        cur.wait_stream(hp)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with step.ema_weights():`` -- the model carries the averaged weights (and, with ema_buffers, the averaged running
+        statistics) inside the block: validate, predict or model.state_dict() there.  The live and the averaged values are exchanged
+        in place (bdn_swap_segments: the parameters stay views of flat_params, frozen tensors are not touched, no third buffer), the
+        engine's packed weight images and eval-mode BatchNorm tables are rebuilt, and on exit -- also when the body raises --
+        everything is exchanged back and rebuilt again.  Entry and exit order the caller's current stream against the step's stream in
+        both directions.  Inside the block step(), flush(), set_param_groups() and the state-dict methods raise RuntimeError.  Before
+        any averaging update has run (n_averaged == 0) the average is the live model, so nothing is exchanged; it does not raise."""
+        self._need_average('ema_weights()')
+        self._no_pending('ema_weights()')
+        self._not_swapped('ema_weights()')
+        self._exchange()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swapped = False
+            self._exchange()

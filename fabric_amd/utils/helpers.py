@@ -91,7 +91,10 @@ def load_checkpoint(src, device=None, precision=None, allow_pickle=True):
       * the whole-module pickle of train.py:222 -- nn.DataParallel(BiDateNet) or a bare BiDateNet (the class paths
         `models.bidate_model.BiDateNet`, `models.unet_parts.*` resolve through the repo-root shims; run with the repo root on
         sys.path).  The DataParallel wrapper is dropped: here one process drives one GPU (fabric_amd.parallel);
-      * a state dict, with or without the `module.` prefix of a DataParallel save, optionally nested under 'state_dict' / 'model'.
+      * a state dict, with or without the `module.` prefix of a DataParallel save, optionally nested under 'state_dict' / 'model';
+      * the state dict of a torch.optim.swa_utils.AveragedModel of a BiDateNet (TrainStep.ema_state_dict(), the `ema_epoch_N.pt`
+        fabric_amd.train writes): a dict whose keys are all `module.`-prefixed except an integer scalar `n_averaged`, which is dropped
+        -- the result is a BiDateNet on the averaged weights.
     The result is always a fresh fabric_amd BiDateNet carrying the checkpoint's parameters AND BatchNorm buffers; the channel
     counts come from the tensors.  Mismatched / missing / unexpected keys raise (load_state_dict(strict=True)).
 
@@ -127,6 +130,9 @@ def load_checkpoint(src, device=None, precision=None, allow_pickle=True):
                 return load_checkpoint(sd[nest], device, precision, allow_pickle)
     else:
         raise TypeError(f'fabric_amd: cannot load a checkpoint from {type(obj).__name__}')
+    from ..optim import AVG_COUNT, is_averaged_state
+    if is_averaged_state(sd):
+        sd = {k: v for k, v in sd.items() if k != AVG_COUNT}
     sd = strip_module_prefix(sd)
     try:
         n_channels = int(sd['inc.conv.conv.0.weight'].shape[1])

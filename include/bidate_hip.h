@@ -612,6 +612,26 @@ size_t bdn_grad_norm_workspace_bytes(size_t n);
 int bdn_grad_norm(const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float grad_scale, float max_norm,
                   void* workspace, float* out, size_t n, void* stream);
 
+/* ---- averaged weights (torch.optim.swa_utils.AveragedModel's EMA / SWA) over the flat f32 buffers of the fused step.
+ * bdn_ema_update: copy = 1: avg = params bit for bit (AveragedModel's first update); copy = 0: avg = lerp(avg, params, weight) by torch's
+ *   element formula in float32, weight < 0.5: avg + weight * (p - avg), otherwise p - (p - avg) * (1 - weight) -- so weight 0 keeps avg's
+ *   bits and weight 1 gives p's (for finite values other than -0).  EMA: weight = 1 - decay; SWA: weight = 1 / (n_averaged + 1).  weight
+ *   outside [0, 1] or NaN, or copy other than 0 / 1: BDN_E_ARG.
+ * bdn_swap_segments: exchanges a and b in place (bits are moved, not computed); a == b: BDN_E_ARG.
+ * Both: n a multiple of 4, buffers 16-byte aligned.  n_seg = 0: every vector counts.  n_seg in 1..256: seg_end / seg_group are the DEVICE
+ *   segment table of the grouped update rules above; a vector of a segment with group id -1 (frozen) or an id outside 0..7, or behind the
+ *   last end, is neither read nor written in either buffer, every other group id counts alike.  One launch of the grouped rules' kernel
+ *   (the same LDS-staged lookup, one float4 per lane, every load of a pass issued before the first store, no atomics: bit-reproducible).
+ * bdn_ema_update_multi: the same rule (weight, copy) over n_tensors (0..65535) small tensors in ONE launch.  desc_dev: DEVICE array of
+ *   n_tensors records { float* avg; const float* src; int32 len; int32 pad; } (24 bytes each, 8-byte aligned); the pointers need 4-byte
+ *   alignment only (a float4 body where both are 16-byte aligned, one element per lane otherwise and for the len % 4 tail).  max_len:
+ *   the largest len, sizes the grid only (every tensor is grid-strided to its own len; len <= 0 is skipped).
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+int bdn_ema_update(float* avg, const float* params, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float weight, int copy,
+                   size_t n, void* stream);
+int bdn_ema_update_multi(const void* desc_dev, int n_tensors, int max_len, float weight, int copy, void* stream);
+int bdn_swap_segments(float* a, float* b, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,11 @@
       one read; torch's copy_: read + write; torch's add_: two reads + write), bdn_adam_step_grouped_ex beside bdn_adam_step_grouped, and
       the bf16 B=64 128x128 AdamW step plain / with max_grad_norm=1.0 / with accumulate=4 (per update of four micro-steps, against
       four plain steps), interleaved like (b).
-    python tools/bench_optim.py [--reps 200] [--rounds 4] [--steps 20] [--skip-step] [--groups | --clip]
+  (e) --ema: bdn_ema_update (no table; the model's two-group table; the same with the encoder frozen: 3 buffer passes over the vectors
+      that count) and bdn_swap_segments (4 passes) at the model's size, with bdn_adam_step and bdn_adam_step_grouped (7 passes) from
+      the same library interleaved in the same run as the bandwidth yardstick, the whole interleaving repeated --rounds times; and the
+      bf16 B=64 128x128 AdamW step with averaging off, on (ema_decay=0.999) and on with ema_every=4, interleaved like (b).
+    python tools/bench_optim.py [--reps 200] [--rounds 4] [--steps 20] [--skip-step] [--groups | --clip | --ema]
 Prints one JSON line at the end."""
 import argparse
 import json
@@ -348,6 +352,123 @@ def clip_steps(rounds, n_steps, batch=64):
     return out
 
 
+def _tables(dev):
+    """BiDateNet(13, 2)'s layout and its real segment tables: {name: (ends, ids, n_seg, vectors that count)}."""
+    from fabric_amd import optim as O
+    from fabric_amd.engine import param_order
+    from fabric_amd.parallel import FlatLayout
+    model = BiDateNet(13, 2)
+    named = list(model.named_parameters())
+    names = [k for k, _ in named]
+    layout = FlatLayout([(k, p.shape) for k, p in named], param_order(13))
+    assert layout.total == N
+    cfg = O.OptimConfig('adamw', lr=1e-3)
+    tables = {}
+    for name, frozen_encoder in (('two_groups', False), ('encoder_frozen', True)):
+        groups = _two_groups(model, frozen_encoder)
+        pg = O.ParamGroups(cfg, names, groups, {k for k, p in named if not p.requires_grad})
+        ends, ids = O.segment_table(layout, pg)
+        count = sum(b - a for a, b, g in zip([0] + ends[:-1], ends, ids) if g != O.FROZEN)
+        tables[name] = (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev), torch.tensor(ids, dtype=torch.int32).to(dev), len(ends), count)
+    return tables
+
+
+def ema_kernels(reps, rounds):
+    """us per launch, bytes moved and TB/s of bdn_ema_update and bdn_swap_segments beside bdn_adam_step / bdn_adam_step_grouped,
+    interleaved, `rounds` times over."""
+    dev = torch.device('cuda', 0)
+    tables = _tables(dev)
+    g = torch.Generator(device='cpu').manual_seed(0)
+    p = torch.randn(N, generator=g).to(dev)
+    gr = (torch.randn(N, generator=g) * 1e-3).to(dev)
+    m, v, avg = torch.zeros(N, device=dev), torch.zeros(N, device=dev), p.clone()
+    st = _lib.stream_ptr()
+    step = [0]
+    lr, wd = _lib.floats([1e-3, 1e-4]), _lib.floats([1e-2, 0.0])
+
+    def table(name):
+        if name is None:
+            return None, None, 0
+        ends, ids, n_seg, _ = tables[name]
+        return ends.data_ptr(), ids.data_ptr(), n_seg
+
+    def adam():
+        step[0] += 1
+        _lib.call('bdn_adam_step', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), 1e-3, 1.0, 0.9, 0.999, 1e-8, 1e-2, 1, step[0], N, st)
+
+    def adam_grouped():
+        step[0] += 1
+        _lib.call('bdn_adam_step_grouped', p.data_ptr(), gr.data_ptr(), m.data_ptr(), v.data_ptr(), *table('two_groups'), 2, lr, wd, 1.0,
+                  0.9, 0.999, 1e-8, 1, step[0], N, st)
+
+    def ema(name):
+        return lambda: _lib.call('bdn_ema_update', avg.data_ptr(), p.data_ptr(), *table(name), 1e-3, 0, N, st)
+
+    def swap(name):
+        return lambda: _lib.call('bdn_swap_segments', p.data_ptr(), avg.data_ptr(), *table(name), N, st)
+    vec = lambda name: N // 4 if name is None else tables[name][3]          # noqa: E731
+    cases = [('adamw_ungrouped', 7 * 4 * N, adam), ('adamw_two_groups', 7 * 16 * vec('two_groups'), adam_grouped),
+             ('ema_no_table', 3 * 4 * N, ema(None)), ('ema_two_groups', 3 * 16 * vec('two_groups'), ema('two_groups')),
+             ('ema_encoder_frozen', 3 * 16 * vec('encoder_frozen'), ema('encoder_frozen')),
+             ('swap_no_table', 4 * 4 * N, swap(None)), ('swap_two_groups', 4 * 16 * vec('two_groups'), swap('two_groups'))]
+    res = {name: [] for name, _, _ in cases}
+    for _ in range(rounds):
+        for name, _, fn in cases:
+            for _ in range(20):
+                fn()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            res[name].append(e0.elapsed_time(e1) / reps * 1e3)
+    out = {}
+    for name, nbytes, _ in cases:
+        med = statistics.median(res[name])
+        out[name] = {'us': round(med, 2), 'MB': round(nbytes / 1e6, 1), 'TB_s': round(nbytes / med * 1e-6, 2),
+                     'TB_s_rounds': [round(nbytes / t * 1e-6, 2) for t in res[name]], 'rounds_us': [round(t, 2) for t in res[name]]}
+        print(f'{name:22s} median {med:8.2f} us  {nbytes / 1e6:6.1f} MB  {nbytes / med * 1e-6:5.2f} TB/s  {out[name]["rounds_us"]}', flush=True)
+    return out
+
+
+def ema_steps(rounds, n_steps, batch=64):
+    """ms per bf16 B=64 128x128 AdamW step with averaging off, on, and on with ema_every=4; interleaved."""
+    dev = torch.device('cuda', 0)
+    g = torch.Generator(device='cpu').manual_seed(1)
+    x1 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    x2 = torch.randn(batch, 13, 128, 128, generator=g).to(dev)
+    lbl = (torch.rand(batch, 128, 128, generator=g) < 0.1).to(torch.uint8).to(dev)
+    cases = [('off', {}), ('ema', dict(ema_decay=0.999)), ('ema_every_4', dict(ema_decay=0.999, ema_every=4))]
+    ts = {}
+    for name, kw in cases:
+        torch.manual_seed(0)
+        ts[name] = TrainStep(BiDateNet(13, 2, precision='bf16').to(dev).train(), lr=1e-4, optimizer='adamw', **kw)
+    res = {name: [] for name, _ in cases}
+    with torch.cuda.stream(ts['off'].stream()):
+        for _ in range(rounds):
+            for name, _ in cases:
+                s = ts[name]
+                for _ in range(5):
+                    s.step(x1, x2, lbl)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n_steps):
+                    s.step(x1, x2, lbl)
+                e1.record()
+                torch.cuda.synchronize()
+                res[name].append(e0.elapsed_time(e1) / n_steps)
+    base = statistics.median(res['off'])
+    out = {}
+    for name, _ in cases:
+        med = statistics.median(res[name])
+        out[name] = {'ms': round(med, 4), 'delta_us': round((med - base) * 1e3, 1), 'rounds_ms': [round(t, 4) for t in res[name]]}
+        print(f'step {name:12s} median {med:.4f} ms  ({(med - base) * 1e3:+8.1f} us vs off)  {out[name]["rounds_ms"]}', flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=200)
@@ -356,7 +477,14 @@ def main():
     ap.add_argument('--skip-step', action='store_true')
     ap.add_argument('--groups', action='store_true', help='(c): the grouped update kernel and the grouped / frozen steps only')
     ap.add_argument('--clip', action='store_true', help='(d): the norm / accumulate / _ex kernels and the clipped / accumulating steps only')
+    ap.add_argument('--ema', action='store_true', help='(e): the averaging / exchange kernels beside the Adam kernels, and the step with averaging off / on')
     a = ap.parse_args()
+    if a.ema:
+        res = {'n': N, 'ema_kernels': ema_kernels(max(a.reps, 200), a.rounds)}
+        if not a.skip_step:
+            res['ema_step_bf16_b64'] = ema_steps(a.rounds, a.steps)
+        print(json.dumps(res))
+        return
     if a.clip:
         res = {'n': N, 'clip_kernels': clip_kernels(max(a.reps, 200), a.rounds)}
         if not a.skip_step:
