@@ -143,6 +143,10 @@ class TrainStep:
         bias_tail = [k for k in order if k.endswith('.bias') and k.split('.')[-2] in ('0', '3')]
         if bn == 'frozen':
             bias_tail = []                                   # on running statistics those biases have gradients (scale * dbeta): reduce them
+        # bn='batch': backward never writes those bias gradients (zero_bias_grads=False), it relies on the zeros they were born with.
+        # p.grad is a view of flat_grads, so an eager backward on the module adds into them -- an eval-mode graph adds real values.
+        # Such a write moves flat_grads' version counter (the library's own kernels do not): _step() zeroes the slices again only then
+        self._zero_tail = [(k, self.layout.view(self.flat_grads, k)) for k in bias_tail]
         self.bucketer = GradBucketer(self.layout, self.flat_grads, n_buckets, process_group, keys_no_reduce=bias_tail,
                                      enabled=self.world > 1 or force_collectives, force=force_collectives)
         if self.world > 1:                                   # identical start on every rank (DataParallel broadcasts)
@@ -151,6 +155,7 @@ class TrainStep:
         self.last_counts = self.last_terms = self.last_dlogits = None
         # detached aliases of every parameter / buffer (same storage), built once: no per-step dict walk
         self._P = {k: v.detach() for k, v in self.model.state_dict(keep_vars=True).items()}
+        self._bound = self._bindings()
         self.param_groups = self._groups = self._seg = self._need = None
         self._implicit_group = False
         if param_groups is not None or any(not p.requires_grad for _, p in named):
@@ -168,6 +173,7 @@ class TrainStep:
                 self._implicit_table()                       # uploaded now: the step itself never waits for the device
         if ema_on:
             self._init_average()
+        self._grads_version = self.flat_grads._version
 
     def _implicit_table(self):
         """The clipped update runs the grouped (_ex) entry points; without groups or frozen parameters, on one implicit group of every
@@ -181,12 +187,14 @@ class TrainStep:
                                      torch.tensor(ids, dtype=torch.int32).to(dev), len(ends)))
         return self._clip_table
 
-    def _init_average(self):
+    def _init_average(self, rebind=False):
         """flat_avg (a clone of flat_params), and with ema_buffers the averaged running statistics: views of one flat buffer, a scratch
-        copy of it for the exchange, and the two descriptor tables of bdn_ema_update_multi ({average <- live}, {live <- scratch})."""
+        copy of it for the exchange, and the two descriptor tables of bdn_ema_update_multi ({average <- live}, {live <- scratch}).
+        rebind: the live buffers moved (_rebind): only the two tables are rebuilt, every average keeps its value."""
         import struct
         dev = self.flat_params.device
-        self.flat_avg = self.flat_params.clone()
+        if not rebind:
+            self.flat_avg = self.flat_params.clone()
         if not self.ema_buffers:
             return
         keys = [k for k in self._P if k.endswith(('.running_mean', '.running_var'))]
@@ -196,8 +204,12 @@ class TrainStep:
         for k in keys:
             offs[k] = total
             total += (self._P[k].numel() + 3) // 4 * 4            # every view starts on a float4
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        tmp = torch.empty_like(flat)
+        if rebind and self._avg_desc is not None:
+            flat, tmp = self._avg_desc[4], self._avg_desc[5]
+        else:
+            rebind = False
+            flat = torch.zeros(total, dtype=torch.float32, device=dev)
+            tmp = torch.empty_like(flat)
         upd = back = b''
         for k in keys:
             live = self._P[k]
@@ -205,7 +217,8 @@ class TrainStep:
                 raise RuntimeError(f'fabric_amd: BatchNorm buffer {k} must be contiguous float32')
             n = live.numel()
             v = flat[offs[k]:offs[k] + n].view(live.shape)
-            v.copy_(live)
+            if not rebind:
+                v.copy_(live)
             self.avg_buffers[k] = v
             upd += struct.pack('<QQii', v.data_ptr(), live.data_ptr(), n, 0)
             back += struct.pack('<QQii', live.data_ptr(), tmp.data_ptr() + 4 * offs[k], n, 0)
@@ -298,6 +311,53 @@ class TrainStep:
     def _state(self):
         return self._P
 
+    def _bindings(self):
+        """(owning dict, attribute, state-dict key, device address) of every parameter and buffer of the module as the step bound it: the
+        flat buffers, `_P` and the descriptor tables all hold these addresses."""
+        out = []
+        for prefix, mod in self.model.named_modules():
+            for d in (mod._parameters, mod._buffers):
+                out += [(d, name, f'{prefix}.{name}' if prefix else name, t.data_ptr()) for name, t in d.items() if t is not None]
+        return out
+
+    def _check_bound(self):
+        """The step trains flat_params through aliases built once.  When a parameter or buffer of the module was re-pointed since
+        (load_state_dict(assign=True), p.data = t, a second TrainStep built on the same module) the module is the truth: the step
+        binds it again (_rebind) and goes on exactly as a step built on the module as it now is, with the optimizer state and
+        averages it has.  Host-side address comparisons only: no device synchronisation."""
+        for d, name, key, addr in self._bound:
+            t = d.get(name)
+            if t is None or t.data_ptr() != addr:
+                return self._rebind(key)
+
+    def _rebind(self, key):
+        """Take the module's tensors over again, as the constructor did: the values of every re-pointed parameter are copied into
+        its view of flat_params and p.data / p.grad are pointed back at the flat buffers; re-pointed buffers are adopted where they
+        are.  The aliases `_P`, the averaging tables (which hold buffer addresses) and the engine's packed images are re-derived.
+        Raises RuntimeError naming `key` when the module can no longer be bound: other parameter names or shapes, another device."""
+        dev = self.flat_params.device
+        named = list(self.model.named_parameters())
+        state = self.model.state_dict(keep_vars=True)
+        if [k for k, _ in named] != self._names or any(tuple(p.shape) != tuple(self.layout.slices[k][2]) for k, p in named) \
+                or any(t.device != dev for t in state.values()):
+            raise RuntimeError(f'fabric_amd: {key} was re-pointed at other storage after this TrainStep was built and the module no '
+                               f'longer fits the step (a device move, or other parameter names or shapes): build a new TrainStep')
+        hp, cur = self.stream(dev), torch.cuda.current_stream(dev)
+        cur.wait_stream(hp)                                  # a step in flight still reads and writes the flat buffers
+        for k, p in named:
+            v = self.layout.view(self.flat_params, k)
+            if p.data_ptr() != v.data_ptr():
+                v.copy_(p.data)
+                p.data = v
+            p.grad = self.layout.view(self.flat_grads, k)
+        hp.wait_stream(cur)
+        self._by_id = {id(p): k for k, p in named}
+        self._P = {k: v.detach() for k, v in self.model.state_dict(keep_vars=True).items()}
+        if self.flat_avg is not None:
+            self._init_average(rebind=True)
+        self.model.engine().invalidate_weights()
+        self._bound = self._bindings()
+
     def step(self, x_d1, x_d2, labels):
         """One optimisation step.  Returns the loss as a fresh 0-dim device tensor (no sync; safe to keep in a list like
         the reference loop does with `cd_loss`).  `last_counts` / `last_logits` are persistent buffers that the NEXT step
@@ -308,6 +368,7 @@ class TrainStep:
         compute units first (A/B tools/archive/ab_prio.py: -0.8 % step time).  The caller's current stream is joined on both
         sides, so the usual stream semantics hold for inputs and outputs."""
         self._not_swapped('step()')
+        self._check_bound()
         if self._guard and self.collectives_report is None and self.bucketer.active():
             # measure only: the caller may already run its loop on step.stream(), which must not be swapped under it
             self.guard_collectives(*[int(v) for v in (x_d1.shape[0], x_d1.shape[2], x_d1.shape[3])], replace_streams=False)
@@ -338,6 +399,7 @@ class TrainStep:
         if not apply:
             self.micro = 0
             return False
+        self._check_bound()
         dev = self.flat_params.device
 
         def run():
@@ -557,6 +619,12 @@ class TrainStep:
         eng = model.engine()
         P = self._state()
         frozen_bn = self.bn == 'frozen'
+        if self.flat_grads._version != self._grads_version:   # somebody wrote p.grad since the last step (host-side check, no launch otherwise)
+            skip = self._groups.frozen if self._groups is not None else ()
+            for k, g in self._zero_tail:
+                if k not in skip:                             # a frozen tensor's gradient has no reader: left as it is
+                    g.zero_()
+            self._grads_version = self.flat_grads._version
         if frozen_bn:                                         # the training-layout forward on the running statistics, as an eval-mode
             from .models.bidate_model import _Lease           # autograd graph recomputes it (_BiDateFunction.backward)
             logits, ws = eng.forward(x_d1, x_d2, P, training=False, frozen=True)
@@ -587,6 +655,7 @@ class TrainStep:
             if not closing:                                   # acc = g1, then acc += g: no collective, no update, the packed weights stay valid
                 _lib.call('bdn_grad_accumulate', self.flat_accum.data_ptr(), self.flat_grads.data_ptr(), self.layout.total, int(pending > 0), st)
                 self.micro = pending + 1
+                self._grads_version = self.flat_grads._version
                 return loss.clone()
             if pending:                                       # flat_grads = gK + acc
                 if self.bucketer.active():
@@ -599,6 +668,7 @@ class TrainStep:
         self.micro = 0
         self._apply(st, 1.0 / (self.world * (pending + 1)))
         eng.invalidate_weights()                              # packed bf16/f32 GEMM images are now stale
+        self._grads_version = self.flat_grads._version        # whatever the step itself moved it by (the buckets' all-reduces)
         return loss.clone()
 
     def _add_pending(self, a, b):

@@ -364,7 +364,11 @@ def _open_lanes(eng, P, dev, n, batch_size, patch_size, two_streams):
     lanes = [cur, _streams.get('wgrad', dev)] if want_two else [cur]
     seen = [set() for _ in lanes]
     if len(lanes) > 1:
-        eng._weights(eng.layers[0], P, False)            # the filter images are packed once, on the caller's stream, before the fork
+        # the filter images are packed once, on the caller's stream, before the fork.  The staleness check comes first: after an
+        # optimizer step with no forward since, the images are old but still marked valid, and the repack would otherwise happen
+        # inside lane 0's first batch, on lane 0's stream, while lane 1 (ordered only behind the fork) reads them
+        eng._check_packed(P)
+        eng._weights(eng.layers[0], P, False)
         if eng._use_eval_schedule():
             eng.eval_tables(P)                           # and so are the folded BatchNorm tables both lanes read
             seen = [{min(batch_size, n), n % batch_size or batch_size} for _ in lanes]
