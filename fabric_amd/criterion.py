@@ -12,6 +12,15 @@ and NaN included) reach no output.  A valid label >= ncls keeps the library's "l
 pixel gives overlap = 1, focal = 0 and an all-zero gradient (counts[4] = 0): a train step on it still runs and weight decay still
 applies; nothing checks for it on the host.  Data-parallel: each rank normalises by its own valid count and the ranks' gradients are
 averaged with equal weight, as torch's DistributedDataParallel does with ignore_index.
+
+topk (None or a fraction 0 < f <= 1): hard-pixel mining -- nnU-Net's TopKLoss, "bootstrapped cross-entropy", OHEM -- ``bdn_criterion_topk``.
+The focal term is averaged over the K hardest valid pixels of the batch only: ppm = round(f * 1e6), K = max(1, n_valid * ppm // 1e6) (0
+without a valid pixel), the pixels ranked by their float32 focal term (ties: the lower pixel index first) by an exact select on the device.
+The focal gradient is exactly 0 at a valid pixel that is not kept; the selection is a constant for the gradient, as torch.topk is under
+autograd.  The overlap term still runs over all valid pixels.  terms becomes f32[3] = overlap, focal, the K-th largest term (the
+threshold), counts int32[6] = {TP, FP, FN, correct, valid, K}.  It needs a focal weight (gamma = 0 is top-k cross-entropy) and class
+weights >= 0, and composes with ignore_index.  Data-parallel: each rank selects its own K from its own batch; with gradient accumulation
+the selection is per micro-step.  topk=None is the criterion as it was, call for call.
 """
 
 NAMES = ('tversky', 'dice', 'jaccard', 'focal', 'focal+tversky', 'focal+dice', 'focal+jaccard')
@@ -21,11 +30,12 @@ REDUCE = {'columns': 0, 'image': 1}
 
 class Criterion:
     def __init__(self, w_overlap=1.0, alpha=0.5, beta=0.5, eps=1e-7, reduce='columns', w_focal=0.0, gamma=0.0, class_alpha=None,
-                 size_average=True, ignore_index=None):
+                 size_average=True, ignore_index=None, topk=None):
         """reduce: 'columns' -- what the reference's train.py gets from [B,H,W] labels, sums over dims (0,2), one ratio per (class,
         column) -- or 'image', dims (0,2,3), one ratio per class ([B,1,H,W] labels there).  class_alpha: None, a float a (class
         weights [a, 1 - a], utils/metrics.py:13-14) or a sequence of ncls class weights.  ignore_index: None -- every pixel carries a label,
-        bdn_criterion -- or the label byte (0..255) of the pixels to leave out (module docstring), bdn_criterion_masked."""
+        bdn_criterion -- or the label byte (0..255) of the pixels to leave out (module docstring), bdn_criterion_masked.  topk: None, or the fraction 0 < f <= 1 of the valid pixels the
+        focal term is averaged over, the hardest first (module docstring), bdn_criterion_topk."""
         w_overlap, w_focal = float(w_overlap), float(w_focal)
         if not (w_overlap >= 0.0 and w_focal >= 0.0):
             raise ValueError(f'criterion weights must be >= 0, got w_overlap={w_overlap}, w_focal={w_focal}')
@@ -45,12 +55,26 @@ class Criterion:
         if isinstance(class_alpha, (float, int)):
             class_alpha = [float(class_alpha), 1.0 - float(class_alpha)]
         self.class_alpha = None if class_alpha is None else tuple(float(v) for v in class_alpha)
+        self.topk_ppm = None
+        if topk is not None:
+            if isinstance(topk, bool) or not isinstance(topk, (float, int)) or not 0.0 < float(topk) <= 1.0:
+                raise ValueError(f'topk must be None or a fraction 0 < f <= 1, got {topk!r}')
+            ppm = int(round(float(topk) * 1e6))
+            if not 1 <= ppm <= 1_000_000:
+                raise ValueError(f'topk={topk!r} is {ppm} parts per million: it must lie in 1..1000000')
+            if not w_focal > 0.0:
+                raise ValueError('topk ranks the focal term: the criterion needs a focal weight (gamma = 0 is top-k cross-entropy)')
+            if self.class_alpha is not None and not all(v >= 0.0 for v in self.class_alpha):
+                raise ValueError(f'topk needs class weights >= 0, got class_alpha={self.class_alpha}')
+            topk, self.topk_ppm = float(topk), ppm
+        self.topk = topk
         self._alpha_dev = {}
 
     @classmethod
     def parse(cls, name, tversky_alpha=0.5, tversky_beta=0.5, focal_gamma=None, focal_alpha=None, weights=(1, 1), eps=1e-7,
-              reduce='columns', ignore_index=None):
-        """The criterion of a --loss_function name.  weights = (w_focal, w_overlap), used by the compound names only."""
+              reduce='columns', ignore_index=None, topk=None):
+        """The criterion of a --loss_function name.  weights = (w_focal, w_overlap), used by the compound names only.  topk: a name with a
+        focal term only (Criterion raises ValueError otherwise)."""
         if name not in NAMES:
             raise ValueError(f'unknown criterion {name!r}: one of {", ".join(NAMES)}')
         parts = name.split('+')
@@ -61,12 +85,13 @@ class Criterion:
         coef = {'tversky': (tversky_alpha, tversky_beta, eps), 'dice': (0.5, 0.5, 0.5 * eps), 'jaccard': (1.0, 1.0, eps),
                 None: (0.5, 0.5, eps)}[overlap]
         return cls(w_overlap, *coef, reduce=reduce, w_focal=w_focal, gamma=focal_gamma if focal else 0.0,
-                   class_alpha=focal_alpha if focal else None, ignore_index=ignore_index)
+                   class_alpha=focal_alpha if focal else None, ignore_index=ignore_index, topk=topk)
 
     def __repr__(self):
         return (f'Criterion(w_overlap={self.w_overlap}, alpha={self.alpha}, beta={self.beta}, eps={self.eps}, reduce={self.reduce!r}, '
                 f'w_focal={self.w_focal}, gamma={self.gamma}, class_alpha={self.class_alpha}, size_average={self.size_average}'
-                + (f', ignore_index={self.ignore_index}' if self.ignore_index is not None else '') + ')')
+                + (f', ignore_index={self.ignore_index}' if self.ignore_index is not None else '')
+                + (f', topk={self.topk}' if self.topk is not None else '') + ')')
 
     # ------------------------------------------------------------------ device side
     def _class_alpha(self, device, ncls):
@@ -82,25 +107,30 @@ class Criterion:
 
     def buffers(self, shape, device):
         """Persistent outputs for logits of `shape`: (workspace, loss, terms, counts), the `out` of evaluate().  counts is int32[4], or
-        int32[5] with an ignore_index."""
+        int32[5] with an ignore_index; with topk, terms is f32[3] and counts int32[6]."""
         import torch
         from . import _lib
         B, C, H, W = shape
         masked = self.ignore_index is not None
         query = _lib.load().bdn_criterion_masked_workspace_bytes if masked else _lib.load().bdn_criterion_workspace_bytes
+        if self.topk is not None:
+            query = _lib.load().bdn_criterion_topk_workspace_bytes
         n = query(B, C, H, W, REDUCE[self.reduce])
         if n == 0:
             raise RuntimeError(f'fabric_amd: the criterion takes logits [B, 2..8, H, W] with B*H*W < 2^31, got {tuple(shape)}')
         return (torch.empty((n + 15) // 16 * 16, dtype=torch.uint8, device=device), torch.empty((), dtype=torch.float32, device=device),
-                torch.empty(2, dtype=torch.float32, device=device), torch.empty(5 if masked else 4, dtype=torch.int32, device=device))
+                torch.empty(3 if self.topk is not None else 2, dtype=torch.float32, device=device),
+                torch.empty(6 if self.topk is not None else 5 if masked else 4, dtype=torch.int32, device=device))
 
-    def evaluate(self, logits, labels, want_grad=True, out=None):
+    def evaluate(self, logits, labels, want_grad=True, out=None, pixel_terms=None, kept=None):
         """-> (loss, terms, counts, dlogits) of float32 [B,C,H,W] logits and [B,H,W] or [B,1,H,W] class-index labels, on the current
         stream: loss a 0-dim tensor, terms f32[2] = the unweighted overlap and focal values, counts int32[4] = {TP, FP, FN, correct} of
         argmax(logits), dlogits = d loss / d logits (None without want_grad: no gradient pass is launched).  `out`: buffers() of this
         shape, overwritten by every call that is given them; fresh ones otherwise.  The reduction is the criterion's `reduce`,
         whichever rank the labels have.  With an ignore_index: counts int32[5] = {TP, FP, FN, correct, valid} over the valid pixels and
-        dlogits exactly 0 at the ignored ones (module docstring)."""
+        dlogits exactly 0 at the ignored ones (module docstring).  With topk: terms f32[3] = overlap, focal, threshold and counts int32[6]
+        = {.., valid, K}; `pixel_terms` (contiguous float32, B*H*W elements) and `kept` (contiguous uint8, B*H*W) are optional caller
+        tensors that receive every pixel's ranked term (unspecified at ignored pixels) and its 0 / 1 kept flag."""
         import torch
         from . import _lib
         if not logits.is_cuda:
@@ -116,6 +146,18 @@ class Criterion:
         ws, loss, terms, counts = out if out is not None else self.buffers(logits.shape, logits.device)
         dlogits = torch.empty_like(logits) if want_grad else None
         ca = self._class_alpha(logits.device, C)
+        if self.topk is None:
+            if pixel_terms is not None or kept is not None:
+                raise RuntimeError('fabric_amd: pixel_terms / kept are outputs of a criterion with topk')
+        else:
+            for t, dt, what in ((pixel_terms, torch.float32, 'pixel_terms'), (kept, torch.uint8, 'kept')):
+                if t is not None and (t.device != logits.device or t.dtype != dt or t.numel() != B * H * W or not t.is_contiguous()):
+                    raise RuntimeError(f'fabric_amd: {what} must be a contiguous {dt} tensor of {B * H * W} elements on {logits.device}')
+            _lib.call('bdn_criterion_topk', logits.data_ptr(), labels.data_ptr(), -1 if self.ignore_index is None else self.ignore_index,
+                      self.w_overlap, self.alpha, self.beta, self.eps, REDUCE[self.reduce], self.w_focal, self.gamma, _lib.ptr(ca),
+                      int(self.size_average), self.topk_ppm, ws.data_ptr(), loss.data_ptr(), terms.data_ptr(), counts.data_ptr(),
+                      _lib.ptr(dlogits), _lib.ptr(pixel_terms), _lib.ptr(kept), B, C, H, W, _lib.stream_ptr())
+            return loss, terms, counts, dlogits
         if self.ignore_index is not None:
             _lib.call('bdn_criterion_masked', logits.data_ptr(), labels.data_ptr(), self.ignore_index, self.w_overlap, self.alpha, self.beta,
                       self.eps, REDUCE[self.reduce], self.w_focal, self.gamma, _lib.ptr(ca), int(self.size_average), ws.data_ptr(),

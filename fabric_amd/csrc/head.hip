@@ -594,10 +594,14 @@ extern "C" int bdn_outc_bn_bwd_apply(int dtype, const float* dlogits, const floa
 // the valid pixels (pcounts[block][5]), the finish forms the focal scale 1/valid from that count and leaves it in device memory for
 // the gradient pass, which writes 0.0f at an ignored pixel.  A term with weight 0 contributes nothing (it is selected out, not
 // multiplied by 0).  MASKED = false is the code as it was.
-struct FocalStats { const float* calpha; float gamma; double* part; int ignore; };        // class weights or NULL; partial [gx*gy]
+// TOPK (bdn_criterion_topk, with FOCAL and MASKED; the section "criterion with top-k hard-pixel mining" below): the statistics pass stores
+// every pixel's float32 focal term in the workspace (pterm[(b*H + y)*W + x], 0 at an ignored pixel) instead of summing it; the radix select
+// ranks those stored values, the finish takes the kept count K for the valid count in the focal scale, and the gradient pass selects the
+// focal part out at a pixel whose kept byte is 0.  TOPK = false is the code as it was.
+struct FocalStats { const float* calpha; float gamma; double* part; int ignore; float* pterm; };   // class weights or NULL; partial [gx*gy]
 __device__ __forceinline__ float focal_mod(float pt, float gamma) { return gamma == 0.f ? 1.f : powf(fmaxf(1.f - pt, 0.f), gamma); }
 
-template <int NC, bool FOCAL = false, bool MASKED = false>
+template <int NC, bool FOCAL = false, bool MASKED = false, bool TOPK = false>
 __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                     float* __restrict__ part, int32_t* __restrict__ pcounts, int B, int ncls, int H, int W,
                                     int rows_per_block, int We, FastDiv dH, FocalStats fs = {}) {
@@ -632,6 +636,12 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (r0 + u * RL >= r_end) break;
+                if constexpr (TOPK) {
+                    if (tv[u] == fs.ignore) {              // (the stored term of an ignored pixel is never ranked: written so that no byte stays unset)
+                        int b, y; dH.divmod(r0 + u * RL, b, y);
+                        fs.pterm[(size_t)b * hw + (size_t)y * W + x] = 0.f;
+                    }
+                }
                 if constexpr (MASKED) { if (tv[u] == fs.ignore) continue; c_valid++; }      // an ignored pixel: nothing of it is used
                 float l[NC]; float m = -INFINITY; int am = 0;
 #pragma unroll
@@ -652,6 +662,10 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
 #pragma unroll
                     for (int k = 0; k < NC; k++) if (k < ncls && t == k) ltm = lv[u][k] - m;      // (lv is -inf for k >= ncls: 0 * inf otherwise)
                     const float a = t < ncls ? (fs.calpha ? fs.calpha[t] : 1.f) : 0.f;       // a label >= ncls has no true class: no focal term
+                    if constexpr (TOPK) {                  // the same float32 expression, kept per pixel: what the select ranks
+                        int b, y; dH.divmod(r0 + u * RL, b, y);
+                        fs.pterm[(size_t)b * hw + (size_t)y * W + x] = -focal_mod(pt, fs.gamma) * a * (ltm - logf(den));
+                    } else
                     facc += (double)(-focal_mod(pt, fs.gamma) * a * (ltm - logf(den)));
                 }
                 c_tp += (am == 1 && t == 1); c_fp += (am == 1 && t != 1); c_fn += (am != 1 && t == 1); c_ok += (am == t);
@@ -698,7 +712,7 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
         if constexpr (MASKED) ism[tid * NCNT + 4] = c_valid;
         __syncthreads();
         if (tid < NCNT) { int v = 0; for (int i = 0; i < 256; i++) v += ism[i * NCNT + tid]; pcounts[nblk_lin * NCNT + tid] = v; }
-        if constexpr (FOCAL) {                             // the block's focal partial: LDS tree over the 256 lanes, a fixed order
+        if constexpr (FOCAL && !TOPK) {                    // the block's focal partial: LDS tree over the 256 lanes, a fixed order
             double* dsm = reinterpret_cast<double*>(sm);
             __syncthreads();
             dsm[tid] = facc;
@@ -714,8 +728,12 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
 // FOCAL: also adds the nfp focal block partials (fixed order), loss = w_o overlap + w_f focal, terms = the two unweighted values.
 // MASKED: five counters per block; the focal scale is formed here from the valid count (size_average: 1/valid, 1 with no valid pixel --
 // the sum is then 0 --; else 1) and left in *gscale for the gradient pass; a term with weight 0 is reported as 0 and adds nothing.
-struct FocalFinish { const double* part; int nfp; double scale; float w_o, w_f; float* terms; int size_average; float* gscale; };
-template <bool FOCAL = false, bool MASKED = false>
+// TOPK: the focal scale is 1/K (K the kept count, state[0] of the select's last level; 1 when K = 0), counts[5] = K, terms[2] = the K-th
+// largest term (state[2] holds its key; 0 when K = 0), and `part` holds the nfp block partials of the kept terms.
+struct FocalFinish { const double* part; int nfp; double scale; float w_o, w_f; float* terms; int size_average; float* gscale; const long long* kstate; };
+__device__ __forceinline__ unsigned topk_key(float v) { const unsigned u = __float_as_uint(v); return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u); }
+__device__ __forceinline__ float topk_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+template <bool FOCAL = false, bool MASKED = false, bool TOPK = false>
 __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict__ sums, const float* __restrict__ part, int nblk,
                                       const int32_t* __restrict__ pcounts, int ncblk, int32_t* __restrict__ counts,
                                       float alpha, float beta, float eps, int ncls, int W, float* __restrict__ loss,    // W = effective width (1 when the columns are reduced too)
@@ -760,6 +778,7 @@ __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict_
         __syncthreads();
         for (int s2 = 64; s2 >= 1; s2 >>= 1) { if (tid < 640 && l < s2) ired[tid] += ired[tid + s2]; __syncthreads(); }
         if (tid < 5 && counts) counts[tid] = ired[tid * 128];
+        if constexpr (TOPK) { if (tid == 5 && counts) counts[5] = (int32_t)ff.kstate[0]; }
         if (tid == 0) nvalid = ired[4 * 128];
     } else
     if (counts) {                                          // TP / FP / FN / correct counts: 256 block lanes x 4 counters, LDS tree (integers: any order)
@@ -795,11 +814,14 @@ __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict_
         for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
         if constexpr (MASKED) {
             if (tid == 0) {
-                const double scale = ff.size_average && nvalid > 0 ? 1.0 / (double)nvalid : 1.0;
+                long long nmean = nvalid;                 // the pixels the focal mean runs over
+                if constexpr (TOPK) nmean = ff.kstate[0];
+                const double scale = ff.size_average && nmean > 0 ? 1.0 / (double)nmean : 1.0;
                 const float fo = (float)(red[0] * scale);
                 const float lo = ff.w_o != 0.f ? ff.w_o * ov : 0.f, lf = ff.w_f != 0.f ? ff.w_f * fo : 0.f;
                 *loss = lo + lf;
                 if (ff.terms) { ff.terms[0] = ff.w_o != 0.f ? ov : 0.f; ff.terms[1] = ff.w_f != 0.f ? fo : 0.f; }
+                if constexpr (TOPK) { if (ff.terms) ff.terms[2] = nmean > 0 ? topk_unkey((unsigned)ff.kstate[2]) : 0.f; }
                 *ff.gscale = (float)scale;
             }
         } else
@@ -814,8 +836,9 @@ __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict_
 
 // FOCAL: dlogits = w_o dO + w_f dF with dF_k = -(1 - pt)^gamma a[t] gscale ([k == t] - p_k), the factor a constant (focal_kernel)
 // MASKED: 0.0f for every class at an ignored pixel (written: the buffer is uninitialised), the focal scale read from *gscale_dev
-struct FocalBwd { const float* calpha; float gamma, gscale, w_o, w_f; const float* gscale_dev; int ignore; };
-template <bool FOCAL = false, bool MASKED = false>
+// TOPK: the focal part is written only where kept[p] != 0 (selected out elsewhere, not multiplied by 0); the overlap part reaches every valid pixel
+struct FocalBwd { const float* calpha; float gamma, gscale, w_o, w_f; const float* gscale_dev; int ignore; const uint8_t* kept; };
+template <bool FOCAL = false, bool MASKED = false, bool TOPK = false>
 __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                    const float* __restrict__ coef, float alpha, float beta, float* __restrict__ dlogits,
                                    int B, int ncls, int H, int Wimg, int W, FastDiv dhw, FastDiv dWimg, FocalBwd fb = {}) {
@@ -857,10 +880,12 @@ __global__ void tversky_bwd_kernel(const float* __restrict__ logits, const uint8
         const float a = t < ncls ? (fb.calpha ? fb.calpha[t] : 1.f) : 0.f;                   // a label >= ncls: no focal gradient
         if constexpr (MASKED) {
             const float c = -focal_mod(pt, fb.gamma) * a * fb.gscale_dev[0];
+            bool wf = fb.w_f != 0.f;
+            if constexpr (TOPK) wf = wf && fb.kept[p] != 0;
 #pragma unroll
             for (int k = 0; k < OUTC_MAXCLS; k++) if (k < ncls) {
                 const float go = fb.w_o != 0.f ? fb.w_o * (l[k] * (dp[k] - dot)) : 0.f;
-                const float gf = fb.w_f != 0.f ? fb.w_f * (c * ((k == t ? 1.f : 0.f) - l[k])) : 0.f;
+                const float gf = wf ? fb.w_f * (c * ((k == t ? 1.f : 0.f) - l[k])) : 0.f;
                 dlogits[(b * ncls + k) * hw + q] = go + gf;
             }
         } else {
@@ -1103,6 +1128,257 @@ extern "C" int bdn_criterion_masked(const float* logits, const uint8_t* labels, 
         hipLaunchKernelGGL((tversky_bwd_kernel<true, true>), dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, logits, labels, sums, alpha, beta, dlogits, B, ncls, H, W, p.We,
                            FastDiv(H * W), FastDiv(W), FocalBwd{class_alpha, gamma, 1.f, w_overlap, w_focal, gscale, ignore_label});
         BDN_CHECK_LAUNCH("criterion_masked_bwd");
+    }
+    return BDN_OK;
+}
+
+// ============================================================ criterion with top-k hard-pixel mining
+// bdn_criterion_masked's function with the focal term averaged over the K hardest valid pixels only (include/bidate_hip.h states the
+// semantics).  The statistics pass stores every pixel's float32 focal term; an exact radix select over the 32-bit keys
+//   key = u ^ 0x80000000 (sign bit clear) or ~u (sign bit set), u the term's bit pattern       -- monotone: -0 < +0, +inf on top
+// finds the K-th largest key T in three levels of 11 + 11 + 10 bits; ties at T are kept in pixel-index order.  Launches:
+//   memset   the three level histograms (20 KB)
+//   stats    tversky_sums_kernel<.., TOPK>: overlap partials, counts, pterm[p]
+//   hist<0>  histogram of key >> 21 over the valid pixels
+//   hist<1>  every block first reduces level 0's histogram to (K, digit, remaining rank) -- block 0 records it --, then histograms
+//            (key >> 10) & 2047 among the keys with that top digit
+//   hist<2>  the same one level down: key & 1023 among the keys with the 22-bit prefix
+//   hist<3>  reduces level 2 to T and the number of ties to keep, then counts the keys == T per chunk of 256 consecutive pixels
+//   sum      per block a run of consecutive chunks: the ties before it (sum of the chunk counts), the kept byte of every pixel
+//            (key > T, or key == T and fewer than `ties to keep` ties before it in index order), the block's sum of kept terms in double
+//   finish   tversky_finish_kernel<.., TOPK>: block partials in a fixed order, 1/K, counts[5] = K, terms[2] = the threshold
+//   bwd      tversky_bwd_kernel<.., TOPK>
+// Histogram counts are integers (LDS and global integer atomics: their order cannot change a sum); no float atomics, no host read-back.
+// ws: [kept-term block partials, double][sums n][part nblk*n][pcounts gx*gy*5][gscale, 16 B][state 3 x 4 int64][hist 2048 + 2048 + 1024]
+//     [chunk tie counts][pterm npix f32][kept npix u8], every part padded to 16 bytes.
+__host__ __device__ constexpr int topk_bins(int level) { return level < 2 ? 2048 : 1024; }
+__host__ __device__ constexpr int topk_shift(int level) { return level == 0 ? 21 : level == 1 ? 10 : 0; }
+__host__ __device__ constexpr int topk_hist_off(int level) { return level * 2048; }
+constexpr int TOPK_HIST_TOTAL = 5120;
+constexpr int TOPK_CHUNK = 256;                    // pixels per tie-count chunk = one block's pass over consecutive pixels
+
+struct TopkPlan { OverlapPlan ov; int npix, nchunks, cpb, nsb, hgrid; size_t o_sums, o_state, o_hist, o_tie, o_pterm, o_kept, total; };
+static inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+static TopkPlan topk_plan(int B, int ncls, int H, int W, int reduce_w) {
+    TopkPlan t;
+    t.ov = overlap_plan(B, ncls, H, W, reduce_w);
+    t.npix = B * H * W;
+    t.nchunks = (t.npix + TOPK_CHUNK - 1) / TOPK_CHUNK;
+    t.cpb = (t.nchunks + 511) / 512;                                           // chunks per block of the sum pass: at most 512 blocks
+    t.nsb = (t.nchunks + t.cpb - 1) / t.cpb;
+    t.hgrid = t.nchunks < 1024 ? t.nchunks : 1024;                             // histogram passes: grid-stride over the chunks
+    t.o_sums = up16(sizeof(double) * t.nsb);
+    t.o_state = up16(t.o_sums + sizeof(float) * (size_t)t.ov.n * (t.ov.nblk + 1) + sizeof(int32_t) * 5 * t.ov.gx * t.ov.gy + 16);
+    t.o_hist = t.o_state + sizeof(long long) * 12;
+    t.o_tie = t.o_hist + sizeof(unsigned) * TOPK_HIST_TOTAL;
+    t.o_pterm = up16(t.o_tie + sizeof(int32_t) * t.nchunks);
+    t.o_kept = up16(t.o_pterm + sizeof(float) * (size_t)t.npix);
+    t.total = up16(t.o_kept + (size_t)t.npix);
+    return t;
+}
+
+// The select of one level, by every thread of a 256-thread block: the digit d of the level's histogram with
+//   count(bins > d) < rem <= count(bins >= d),   and greater = count(bins > d).
+// FIRST: rem is formed here from the histogram's total (= the valid pixels): K = max(1, total * ppm / 1e6), 0 without a valid pixel.
+// rem = 0 (no valid pixel) gives digit 0, greater 0.  Bins are walked from the top: thread t owns bins NB-1 - t*PER - j.
+template <int NB, bool FIRST>
+__device__ void topk_block_select(const unsigned* __restrict__ hist, long long& rem, int ppm, int& digit, long long& greater) {
+    constexpr int PER = NB / 256;
+    __shared__ unsigned scan[256];
+    __shared__ int s_digit; __shared__ unsigned s_greater;
+    const int tid = threadIdx.x;
+    unsigned c[PER], s = 0;
+#pragma unroll
+    for (int j = 0; j < PER; j++) { c[j] = hist[NB - 1 - tid * PER - j]; s += c[j]; }
+    if (tid == 0) { s_digit = 0; s_greater = 0; }
+    scan[tid] = s;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {              // inclusive scan (counts stay below 2^31: B*H*W does)
+        const unsigned v = tid >= off ? scan[tid - off] : 0u;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    if constexpr (FIRST) {
+        const long long total = scan[255];
+        const long long k = total * (long long)ppm / 1000000;
+        rem = total == 0 ? 0 : (k < 1 ? 1 : k);
+    }
+    const long long incl = scan[tid], excl = incl - s;
+    if (rem > excl && rem <= incl) {                       // one thread at most
+        long long run = excl;
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            if (run + c[j] >= rem) { s_digit = NB - 1 - tid * PER - j; s_greater = (unsigned)run; break; }
+            run += c[j];
+        }
+    }
+    __syncthreads();
+    digit = s_digit; greater = s_greater;
+    __syncthreads();                                       // (the shared cells are free for a second call)
+}
+
+// state[l] = {K, remaining rank after level l, key prefix after level l, unused}; state[2] = {K, ties to keep, T}
+// LEVEL 0..2: the histogram of that level's digit; LEVEL 3: the chunk tie counts.
+template <int LEVEL>
+__global__ __launch_bounds__(256) void topk_hist_kernel(const float* __restrict__ pterm, const uint8_t* __restrict__ labels, int ignore,
+                                                        int npix, int nchunks, int ppm, unsigned* __restrict__ hist,
+                                                        long long* __restrict__ state, int32_t* __restrict__ tiecnt) {
+    constexpr int NB = topk_bins(LEVEL < 3 ? LEVEL : 2);
+    __shared__ unsigned lh[NB];
+    const int tid = threadIdx.x, lane = tid & 63;
+    unsigned prefix = 0;
+    if constexpr (LEVEL >= 1) {                            // the level above, reduced by every block alike
+        constexpr int PL = LEVEL - 1;
+        long long K = 0, rem = 0, greater; int digit;
+        if constexpr (PL > 0) { K = state[(PL - 1) * 4 + 0]; rem = state[(PL - 1) * 4 + 1]; prefix = (unsigned)state[(PL - 1) * 4 + 2]; }
+        topk_block_select<topk_bins(PL), PL == 0>(hist + topk_hist_off(PL), rem, ppm, digit, greater);
+        if constexpr (PL == 0) K = rem;
+        rem -= greater;
+        prefix |= (unsigned)digit << topk_shift(PL);
+        if (blockIdx.x == 0 && tid == 0) { state[PL * 4 + 0] = K; state[PL * 4 + 1] = rem; state[PL * 4 + 2] = prefix; state[PL * 4 + 3] = 0; }
+    }
+    if constexpr (LEVEL == 3) {
+        for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+            const int p = c * TOPK_CHUNK + tid;
+            bool tie = false;
+            if (p < npix && labels[p] != ignore) tie = topk_key(pterm[p]) == prefix;
+            const int n = __syncthreads_count(tie);
+            if (tid == 0) tiecnt[c] = n;
+        }
+    } else {
+        for (int i = tid; i < NB; i += 256) lh[i] = 0;
+        __syncthreads();
+        for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+            const int p = c * TOPK_CHUNK + tid;
+            bool active = false; unsigned digit = 0;
+            if (p < npix && labels[p] != ignore) {
+                const unsigned key = topk_key(pterm[p]);
+                if constexpr (LEVEL == 0) active = true;
+                else active = (key >> topk_shift(LEVEL - 1)) == (prefix >> topk_shift(LEVEL - 1));
+                digit = (key >> topk_shift(LEVEL)) & (NB - 1);
+            }
+            // the top digit is sign, exponent and two mantissa bits: most of a wave's lanes share a few values, and same-address LDS atomics
+            // serialise.  Up to four rounds of "the first active lane's digit, one add of the matching lanes' count"; what is left (many
+            // distinct digits: the lower levels) goes lane by lane to different addresses.
+            for (int round = 0; round < 4; round++) {
+                const unsigned long long am = __ballot(active);
+                if (am == 0) break;                        // wave-uniform
+                const int leader = __ffsll((long long)am) - 1;
+                const unsigned d0 = __shfl(digit, leader);
+                const bool same = active && digit == d0;
+                const unsigned long long sm = __ballot(same);
+                if (lane == leader) atomicAdd(&lh[d0], (unsigned)__popcll(sm));
+                active = active && !same;
+            }
+            if (active) atomicAdd(&lh[digit], 1u);
+        }
+        __syncthreads();
+        unsigned* gh = hist + topk_hist_off(LEVEL < 3 ? LEVEL : 2);
+        for (int i = tid; i < NB; i += 256) { const unsigned v = lh[i]; if (v) atomicAdd(&gh[i], v); }
+    }
+}
+
+// kept bytes and the block partials of the kept terms.  Block b owns chunks [b*cpb, (b+1)*cpb): a thread adds its pixels in chunk order,
+// the block's 256 lanes meet in an LDS tree -- a fixed order.
+__global__ __launch_bounds__(256) void topk_sum_kernel(const float* __restrict__ pterm, const uint8_t* __restrict__ labels, int ignore,
+                                                       int npix, int nchunks, int cpb, const long long* __restrict__ state,
+                                                       const int32_t* __restrict__ tiecnt, uint8_t* __restrict__ kept_ws,
+                                                       double* __restrict__ part, float* __restrict__ terms_out, uint8_t* __restrict__ kept_out) {
+    __shared__ long long lred[256];
+    __shared__ double dred[256];
+    __shared__ int wcnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long keep_ties = state[2 * 4 + 1];
+    const unsigned T = (unsigned)state[2 * 4 + 2];
+    const int c0 = blockIdx.x * cpb, c1 = min(nchunks, c0 + cpb);
+    long long before = 0;                                  // ties in the chunks in front of this block
+    for (int c = tid; c < c0; c += 256) before += tiecnt[c];
+    lred[tid] = before;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if (tid < s) lred[tid] += lred[tid + s]; __syncthreads(); }
+    before = lred[0];
+    double acc = 0.0;
+    for (int c = c0; c < c1; c++) {
+        const int p = c * TOPK_CHUNK + tid;
+        const bool in = p < npix;
+        float v = 0.f; bool valid = false;
+        if (in) { v = pterm[p]; valid = labels[p] != ignore; }
+        const unsigned key = topk_key(v);
+        const bool tie = valid && key == T;
+        const unsigned long long tm = __ballot(tie);
+        if (lane == 0) wcnt[wave] = __popcll(tm);
+        __syncthreads();
+        long long rank = before + __popcll(tm & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; w++) rank += wcnt[w];
+        const bool kept = valid && (key > T || (tie && rank < keep_ties));
+        if (in) {
+            kept_ws[p] = kept ? 1 : 0;
+            if (kept_out) kept_out[p] = kept ? 1 : 0;
+            if (terms_out) terms_out[p] = v;
+        }
+        if (kept) acc += (double)v;
+        before += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();                                   // wcnt is rewritten by the next chunk
+    }
+    dred[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if (tid < s) dred[tid] += dred[tid + s]; __syncthreads(); }
+    if (tid == 0) part[blockIdx.x] = dred[0];
+}
+
+extern "C" size_t bdn_criterion_topk_workspace_bytes(int B, int ncls, int H, int W, int reduce_w) {
+    if (B <= 0 || H <= 0 || W <= 0 || ncls < 2 || ncls > OUTC_MAXCLS || (size_t)B * H * W >= ((size_t)1 << 31)) return 0;
+    return topk_plan(B, ncls, H, W, reduce_w).total;
+}
+
+extern "C" int bdn_criterion_topk(const float* logits, const uint8_t* labels, int ignore_label, float w_overlap, float alpha, float beta,
+                                  float eps, int reduce_w, float w_focal, float gamma, const float* class_alpha, int size_average,
+                                  int topk_ppm, void* ws, float* loss, float* terms, int32_t* counts, float* dlogits, float* pixel_terms,
+                                  uint8_t* kept, int B, int ncls, int H, int W, void* stream) {
+    if (!logits || !labels || !ws || !loss) BDN_FAIL(BDN_E_ARG, "criterion_topk: null pointer");
+    if (ignore_label < -1 || ignore_label > 255) BDN_FAIL(BDN_E_ARG, "criterion_topk: ignore_label=%d is neither -1 (none) nor a byte value (0..255)", ignore_label);
+    if (topk_ppm < 1 || topk_ppm > 1000000) BDN_FAIL(BDN_E_ARG, "criterion_topk: topk_ppm=%d outside 1..1000000", topk_ppm);
+    if (!(w_overlap >= 0.f) || !(w_focal > 0.f)) BDN_FAIL(BDN_E_ARG, "criterion_topk: top-k ranks the focal term: w_focal > 0 and w_overlap >= 0 (w_overlap=%g, w_focal=%g)", w_overlap, w_focal);
+    if (!(gamma >= 0.f)) BDN_FAIL(BDN_E_ARG, "criterion_topk: negative gamma");
+    if (ncls < 2 || ncls > OUTC_MAXCLS) BDN_FAIL(BDN_E_SHAPE, "criterion_topk: ncls=%d unsupported (2..%d)", ncls, OUTC_MAXCLS);
+    if (B <= 0 || H <= 0 || W <= 0 || (size_t)B * H * W >= ((size_t)1 << 31)) BDN_FAIL(BDN_E_SHAPE, "criterion_topk: bad shape (B*H*W must stay below 2^31)");
+    if ((uintptr_t)ws & 15) BDN_FAIL(BDN_E_ARG, "criterion_topk: ws must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const TopkPlan t = topk_plan(B, ncls, H, W, reduce_w);
+    const OverlapPlan& p = t.ov;
+    char* base = (char*)ws;
+    double* fpart = (double*)base;                                             // [nsb] block partials of the kept terms
+    float* sums = (float*)(base + t.o_sums);                                   // bdn_criterion_masked's layout from here to gscale
+    float* part = sums + p.n;
+    int32_t* pcounts = reinterpret_cast<int32_t*>(part + (size_t)p.nblk * p.n);
+    float* gscale = reinterpret_cast<float*>(pcounts + (size_t)5 * p.gx * p.gy);
+    long long* state = (long long*)(base + t.o_state);
+    unsigned* hist = (unsigned*)(base + t.o_hist);
+    int32_t* tiecnt = (int32_t*)(base + t.o_tie);
+    float* pterm = (float*)(base + t.o_pterm);
+    uint8_t* kept_ws = (uint8_t*)(base + t.o_kept);
+    if (hipMemsetAsync(hist, 0, sizeof(unsigned) * TOPK_HIST_TOTAL, st) != hipSuccess) BDN_FAIL(BDN_E_HIP, "criterion_topk: memset failed");
+    const FocalStats fs{class_alpha, gamma, nullptr, ignore_label, pterm};
+    dim3 grid(p.gx, p.gy), block(p.RL, p.CW);
+    if (ncls <= 2) hipLaunchKernelGGL((tversky_sums_kernel<2, true, true, true>), grid, block, sizeof(float) * 256 * 3 * 2, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, p.We, FastDiv(H), fs);
+    else hipLaunchKernelGGL((tversky_sums_kernel<OUTC_MAXCLS, true, true, true>), grid, block, sizeof(float) * 256 * 3 * OUTC_MAXCLS, st, logits, labels, part, pcounts, B, ncls, H, W, p.rpb, p.We, FastDiv(H), fs);
+    BDN_CHECK_LAUNCH("criterion_topk_stats");
+#define TOPK_HIST(L_) hipLaunchKernelGGL(topk_hist_kernel<L_>, dim3(t.hgrid), dim3(256), 0, st, pterm, labels, ignore_label, t.npix, t.nchunks, topk_ppm, hist, state, tiecnt)
+    TOPK_HIST(0); BDN_CHECK_LAUNCH("criterion_topk_hist0");
+    TOPK_HIST(1); BDN_CHECK_LAUNCH("criterion_topk_hist1");
+    TOPK_HIST(2); BDN_CHECK_LAUNCH("criterion_topk_hist2");
+    TOPK_HIST(3); BDN_CHECK_LAUNCH("criterion_topk_ties");
+#undef TOPK_HIST
+    hipLaunchKernelGGL(topk_sum_kernel, dim3(t.nsb), dim3(256), 0, st, pterm, labels, ignore_label, t.npix, t.nchunks, t.cpb, state, tiecnt, kept_ws, fpart, pixel_terms, kept);
+    BDN_CHECK_LAUNCH("criterion_topk_sum");
+    hipLaunchKernelGGL((tversky_finish_kernel<true, true, true>), dim3(1), dim3(1024), 0, st, sums, part, p.nblk, pcounts, p.gx * p.gy, counts, alpha, beta, eps, ncls, p.We, loss,
+                       FocalFinish{fpart, t.nsb, 1.0, w_overlap, w_focal, terms, size_average, gscale, state + 8});
+    BDN_CHECK_LAUNCH("criterion_topk_finish");
+    if (dlogits) {
+        hipLaunchKernelGGL((tversky_bwd_kernel<true, true, true>), dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, logits, labels, sums, alpha, beta, dlogits, B, ncls, H, W, p.We,
+                           FastDiv(H * W), FastDiv(W), FocalBwd{class_alpha, gamma, 1.f, w_overlap, w_focal, gscale, ignore_label, kept_ws});
+        BDN_CHECK_LAUNCH("criterion_topk_bwd");
     }
     return BDN_OK;
 }

@@ -9,6 +9,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --freeze inc --optimizer adamw
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --accumulate 4 --max_grad_norm 1.0
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --ignore_label 255
+    python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --loss_topk 0.25
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --ema_decay 0.999        # validate and save the averaged weights
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
@@ -119,14 +120,17 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
     from .device_loader import DevicePatchLoader
     from .input_pipeline import DeviceFeeder
     step.model.train()
-    recs, norms = [], []
+    recs, norms, mined = [], [], []
     clip = step.max_grad_norm is not None
+    topk = getattr(step.criterion, 'topk', None) is not None      # hard-pixel mining: K and the threshold of every batch, read back with the losses
     if not isinstance(loader, DevicePatchLoader):
         feeder = feeder or DeviceFeeder(dev)
     with torch.cuda.stream(step.stream()):                # the loop lives on the step's own stream: no joins per step
         for b1, b2, labels in _device_batches(loader, dev, feeder):
             loss = step.step(b1, b2, labels)
             recs.append((loss, step.last_counts.clone(), labels.shape[0]))
+            if topk:
+                mined.append(step.last_terms.clone())
             if clip and step.micro == 0:                  # this call ended with an update
                 norms.append((step.last_grad_norm.clone(), step.last_clip_coef.clone()))
         if step.flush() and clip:                         # --accumulate: the batches left over at the end of the epoch
@@ -137,6 +141,10 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
         c = counts.cpu()
         metrics = set_metrics(metrics, loss.item(), batch_accuracy(c, n * patch_size ** 2), batch_prf_from_counts(c))
     out = get_mean_metrics(metrics) if recs else {}
+    if mined:                                             # --loss_topk: kept / valid pixels over the epoch, and the mean K-th largest term
+        cs = torch.stack([r[1] for r in recs]).cpu().double()
+        out.update(topk_kept_frac=float(cs[:, 5].sum() / cs[:, 4].sum()) if float(cs[:, 4].sum()) else 0.0,
+                   topk_threshold_mean=float(torch.stack(mined)[:, 2].double().mean()))
     if norms:                                             # --max_grad_norm: read back once per epoch, beside the losses
         nc = torch.stack([torch.stack(v) for v in norms]).cpu()
         out.update(grad_norm_mean=float(nc[:, 0].mean()), grad_norm_max=float(nc[:, 0].max()), clipped_frac=float((nc[:, 1] < 1).float().mean()))
@@ -327,6 +335,10 @@ def main(argv=None):
     ap.add_argument('--ignore_label', type=int, default=None, metavar='V',
                     help='--fused_step true only: pixels labelled V (0..255, e.g. 255 for nodata / unlabelled) are left out of the loss, '
                          'its gradient and the accuracy / precision / recall / F1 (Criterion(ignore_index=V))')
+    ap.add_argument('--loss_topk', type=float, default=None, metavar='F',
+                    help='--fused_step true only, a --loss_function with a focal term: hard-pixel mining, the focal term is averaged over the '
+                         'hardest fraction F (0 < F <= 1) of the valid pixels of every batch (Criterion(topk=F)); the epoch record gains '
+                         'train_topk_kept_frac and train_topk_threshold_mean')
     ap.add_argument('--synthetic_ignore_frac', type=float, default=0.1,
                     help='--synthetic with --ignore_label V: the fraction of every label raster painted with V')
     ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam', 'adamw'],
@@ -394,6 +406,14 @@ def main(argv=None):
             raise SystemExit(f'--ignore_label {opt.ignore_label}: a label byte 0..255')
         if not 0.0 <= opt.synthetic_ignore_frac < 1.0:
             raise SystemExit(f'--synthetic_ignore_frac {opt.synthetic_ignore_frac}: a fraction in [0, 1)')
+    if opt.loss_topk is not None:
+        if 'focal' not in opt.loss_function.split('+'):
+            raise SystemExit(f'--loss_topk {opt.loss_topk} ranks the focal term: --loss_function {opt.loss_function} has none '
+                             f'(focal, focal+dice, focal+jaccard, focal+tversky)')
+        if not opt.fused_step:
+            raise SystemExit(f'--loss_topk {opt.loss_topk} is built into the criterion of the fused step: add --fused_step true')
+        if not 0.0 < opt.loss_topk <= 1.0:
+            raise SystemExit(f'--loss_topk {opt.loss_topk}: a fraction 0 < F <= 1')
     step_criterion = None                                  # --fused_step true: ONE Criterion for the step and for validation
     if opt.fused_step:
         from .utils.helpers import criterion_from_opt

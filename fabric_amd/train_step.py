@@ -50,6 +50,9 @@ class TrainStep:
         {TP, FP, FN, correct, valid}, `last_dlogits` is exactly 0 at the ignored pixels, and a batch without a valid pixel is a step with
         a zero gradient (weight decay still applies).  Data-parallel, every rank normalises by its own valid count and the gradients are
         averaged over the ranks with equal weight, as torch's DistributedDataParallel does with ignore_index.
+        A Criterion with a topk (bdn_criterion_topk, hard-pixel mining) averages the focal term over the hardest fraction of the valid
+        pixels of the batch: `last_counts` has six entries, {.., valid, K}, `last_terms` three, {overlap, focal, the K-th largest focal
+        term}.  The selection is per call: per micro-step with accumulate > 1, per rank in a data-parallel run.
 
         bn: 'batch' (BatchNorm on batch statistics, running statistics updated: a training step) or 'frozen' (BatchNorm on its running
         statistics, which are constants: running_mean / running_var / num_batches_tracked are not touched, and the conv biases in

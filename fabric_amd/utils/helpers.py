@@ -47,11 +47,12 @@ def get_criterion(opt):
 
 def criterion_from_opt(opt):
     """fabric_amd.criterion.Criterion of the --loss_function / --tversky_alpha / --tversky_beta / --focal_gamma / --focal_alpha /
-    --loss_weights (W_FOCAL W_OVERLAP) / --ignore_label options; ValueError as Criterion.parse raises it."""
+    --loss_weights (W_FOCAL W_OVERLAP) / --ignore_label / --loss_topk options; ValueError as Criterion.parse raises it."""
     from ..criterion import Criterion
     return Criterion.parse(opt.loss_function, tversky_alpha=getattr(opt, 'tversky_alpha', 0.5), tversky_beta=getattr(opt, 'tversky_beta', 0.5),
                            focal_gamma=getattr(opt, 'focal_gamma', None), focal_alpha=getattr(opt, 'focal_alpha', None),
-                           weights=tuple(getattr(opt, 'loss_weights', None) or (1, 1)), ignore_index=getattr(opt, 'ignore_label', None))
+                           weights=tuple(getattr(opt, 'loss_weights', None) or (1, 1)), ignore_index=getattr(opt, 'ignore_label', None),
+                           topk=getattr(opt, 'loss_topk', None))
 
 
 def get_loaders(opt):

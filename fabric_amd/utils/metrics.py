@@ -165,7 +165,7 @@ class _CriterionFunction(torch.autograd.Function):
 class CompoundLoss(nn.Module):
     """w_overlap * (dice | jaccard | Tversky) + w_focal * FocalLoss as one criterion (fabric_amd.criterion.Criterion, bdn_criterion):
     the module form for validation and the autograd route.  The criterion's `reduce` decides the overlap reduction, not the label
-    rank."""
+    rank.  A criterion with a topk (bdn_criterion_topk) runs here as any other: the selection is a constant for the gradient."""
 
     def __init__(self, criterion):
         super(CompoundLoss, self).__init__()
@@ -178,12 +178,13 @@ class CompoundLoss(nn.Module):
     @property
     def last_counts(self):
         """int32[4] device tensor {TP, FP, FN, correct} of argmax(logits) vs labels for the last call; int32[5] = {.., valid}, over the
-        valid pixels, when the criterion has an ignore_index."""
+        valid pixels, when the criterion has an ignore_index; int32[6] = {.., valid, K} when it has a topk (K the kept pixels)."""
         return self._holder.get('counts')
 
     @property
     def last_terms(self):
-        """f32[2] device tensor: the unweighted overlap and focal values of the last call."""
+        """f32[2] device tensor: the unweighted overlap and focal values of the last call; f32[3] = {.., the K-th largest focal term} when
+        the criterion has a topk."""
         return self._holder.get('terms')
 
 

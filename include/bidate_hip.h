@@ -487,6 +487,39 @@ int bdn_criterion_masked(const float* logits, const uint8_t* labels, int ignore_
                          int reduce_w, float w_focal, float gamma, const float* class_alpha, int size_average, void* ws, float* loss,
                          float* terms, int32_t* counts, float* dlogits, int B, int ncls, int H, int W, void* stream);
 
+/* ---- the masked criterion with top-k hard-pixel mining (nnU-Net's TopKLoss / bootstrapped cross-entropy / OHEM; the reference has none) ----
+ * bdn_criterion_masked's function with the focal term averaged over the K hardest valid pixels of the batch only.  ignore_label: -1 (no
+ * pixel is ignored) or a byte value 0..255.  topk_ppm in 1..1000000 is the kept fraction in parts per million.
+ *   Kept count  n_valid = the pixels whose label is not ignore_label (a valid label >= ncls counts, as in the focal mean);
+ *               K = max(1, (n_valid * topk_ppm) / 1000000) in 64-bit integers, K = 0 when n_valid = 0; formed on the device.
+ *   Ranked      the float32 focal term of utils/metrics.py:8-48 that the statistics pass forms, -(1 - pt)^gamma a[t] log pt (bdn_focal's
+ *               expression, unchanged; 0 for a label >= ncls), through its bit pattern u:
+ *                   key = u ^ 0x80000000 when the sign bit is clear, ~u otherwise
+ *               (monotone: -0 < +0, +inf ranks highest, every bit pattern has a place).  Among equal keys the lower linear pixel index
+ *               (b*H + y)*W + x ranks first.  The kept set is the first K pixels of that order: an exact select on the 32-bit keys (three
+ *               radix levels of 11 + 11 + 10 bits), not a histogram approximation.
+ *   Focal       S / K with size_average (0 when K = 0), else S; S = the kept terms summed in double in a fixed order.
+ *   dlogits     at a kept pixel bdn_criterion_masked's focal gradient with the scale 1 / K (1 without size_average); at a valid pixel that
+ *               is not kept the focal part is exactly 0 (selected out, not multiplied by 0); exactly 0.0f at an ignored pixel, none of
+ *               whose logits is read.  The selection is a constant for the gradient, as torch.topk is under autograd.
+ *   Overlap     unchanged: over all valid pixels; its gradient reaches the pixels that are not kept.
+ *   terms       NULL or f32[3] = overlap, focal, the K-th largest term (the threshold; 0 when K = 0).
+ *   counts      NULL or int32[6] = {TP, FP, FN, correct, valid, K}.
+ *   pixel_terms NULL or f32[B*H*W]: the ranked terms (unspecified at ignored pixels).  kept: NULL or uint8[B*H*W] of 0 / 1.
+ * w_focal > 0 (top-k ranks the focal term; gamma = 0 is top-k cross-entropy), w_overlap >= 0; class_alpha values must be >= 0 (the
+ * caller's contract: they are device memory).  Non-finite logits at a valid pixel give unspecified values, but exactly K pixels are kept.
+ * Launches: one 20 KB memset of the level histograms on the stream, the statistics pass (it also stores every pixel's term), three
+ * histogram passes and a tie-count pass (each first reduces the level above to its digit and remaining rank), the kept-term sum, the
+ * finish and the gradient pass (none with dlogits == NULL).  Integer histogram atomics only -- no float atomics, no host read-back; the
+ * caller never clears the workspace: the same bits on every run, whatever the workspace held.
+ * ws: bdn_criterion_topk_workspace_bytes() bytes, 16-byte aligned (about 5 bytes per pixel more than bdn_criterion_masked's).
+ * Other arguments and checks as bdn_criterion_masked.  Data-parallel: each rank selects its own K from its own batch. */
+size_t bdn_criterion_topk_workspace_bytes(int B, int ncls, int H, int W, int reduce_w);
+int bdn_criterion_topk(const float* logits, const uint8_t* labels, int ignore_label, float w_overlap, float alpha, float beta, float eps,
+                       int reduce_w, float w_focal, float gamma, const float* class_alpha, int size_average, int topk_ppm, void* ws,
+                       float* loss, float* terms, int32_t* counts, float* dlogits, float* pixel_terms, uint8_t* kept,
+                       int B, int ncls, int H, int W, void* stream);
+
 /* ---- OSCD ingest: utils/dataloaders.py:86-111 city_loader, per band ----
  * dst [H][W] f32 (one plane of a [C][H][W] scene) = cv2.resize((src - mean) / std, (W, H)) with cv2's default float
  * INTER_LINEAR sampling (half-pixel centres, border weights (1,0)).  src: [hs][ws] uint16 (src_is_f32 = 0) or f32, on
