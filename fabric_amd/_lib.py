@@ -127,6 +127,9 @@ SIGNATURES = {
     'bdn_ema_update': (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _sz, _vp]),
     'bdn_ema_update_multi': (_i, [_vp, _i, _i, _f, _i, _vp]),
     'bdn_swap_segments': (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp]),
+    'bdn_score_hist': (_i, [_vp, _i, _vp, _i, _i, _i, _i, C.c_longlong, _i, _vp, _vp, _vp]),
+    'bdn_score_curve': (_i, [_vp, _i, _vp, _vp, _vp]),
+    'bdn_threshold_mask': (_i, [_vp, _i, _f, _vp, _i, C.c_longlong, _vp]),
 }
 
 

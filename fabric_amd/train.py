@@ -11,6 +11,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --ignore_label 255
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --loss_topk 0.25
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --ema_decay 0.999        # validate and save the averaged weights
+    python -m fabric_amd.train --metadata metadata.json --val_curve_bins 1024 --scene_stride 64 --scene_threshold val      # best-F1 threshold, AP
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
 predicted tile by tile (utils/inference.py) -- here on the device-resident city stacks -- and written as PNG masks.
@@ -152,19 +153,32 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
 
 
 @torch.no_grad()
-def validate(model, loader, dev, patch_size, criterion, feeder=None, ignore_index=None):
+def validate(model, loader, dev, patch_size, criterion, feeder=None, ignore_index=None, curve=None, world=1):
     """train.py:125-172: eval-mode forward, the SAME criterion the run optimises (train.py:137), per-batch accuracy / P / R / F1,
     mean over batches.  Batches arrive through the feeder's copy stream when one is given.  ignore_index: the run's ignore label --
-    the counts, and with them accuracy / P / R / F1, are taken over the other pixels."""
+    the counts, and with them accuracy / P / R / F1, are taken over the other pixels.
+    curve: a fabric_amd.utils.metrics.ScoreCurve (--val_curve_bins): it is reset, fed the logits of every batch (one launch each, no host
+    sync), summed over the `world` ranks and read once after the pass; the result gains best_f1, best_threshold and ap -- over ALL
+    validation pixels, not a mean over batches.  None: exactly the calls above."""
     from .utils.metrics import confusion_counts
     model.eval()
     metrics = initialize_metrics()
+    if curve is not None:
+        curve.reset()
     for b1, b2, labels in _device_batches(loader, dev, feeder):
         logits = model(b1, b2)
         loss = criterion(logits, labels.long())
+        if curve is not None:
+            curve.update(logits, labels)
         c = confusion_counts(logits, labels, ignore_index).cpu()
         metrics = set_metrics(metrics, loss.item(), batch_accuracy(c, labels.shape[0] * patch_size ** 2), batch_prf_from_counts(c))
-    return get_mean_metrics(metrics)
+    out = get_mean_metrics(metrics)
+    if curve is not None:
+        if world > 1:
+            curve.all_reduce()
+        c = curve.compute()
+        out.update(best_f1=c['best_f1'], best_threshold=c['best_threshold'], ap=c['ap'])
+    return out
 
 
 def train_epoch_autograd(model, criterion, optimizer, loader, dev, patch_size, world=1, feeder=None):
@@ -312,6 +326,28 @@ def scene_scores(mask, label):
     return {'tp': int(counts[0]), 'fp': int(counts[1]), 'fn': int(counts[2]), 'precision': pr, 'recall': rc, 'f1': f1}
 
 
+def check_curve_flags(val_curve_bins, scene_threshold, scene_stride):
+    """--val_curve_bins / --scene_threshold / --scene_stride together, without a device: returns 'argmax', 'val' or the float threshold;
+    raises ValueError with the reason otherwise."""
+    n = val_curve_bins
+    if n != 0 and (n < 2 or n > 4096 or n & (n - 1)):
+        raise ValueError(f'--val_curve_bins {n}: 0 (off) or a power of two in 2..4096')
+    if scene_threshold in ('argmax', 'val'):
+        thr = scene_threshold
+    else:
+        try:
+            thr = float(scene_threshold)
+        except ValueError:
+            thr = float('nan')
+        if not 0.0 <= thr <= 1.0:
+            raise ValueError(f'--scene_threshold {scene_threshold}: argmax, val or a number in [0, 1]')
+    if thr == 'val' and n == 0:
+        raise ValueError('--scene_threshold val applies the best-F1 threshold of the validation pass: add --val_curve_bins N')
+    if thr != 'argmax' and scene_stride <= 0:
+        raise ValueError(f'--scene_threshold {scene_threshold} thresholds the blended scene probabilities: add --scene_stride N > 0')
+    return thr
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Training change detection network (HIP path)')
     for k, v in DEFAULTS.items():
@@ -380,6 +416,13 @@ def main(argv=None):
     ap.add_argument('--scene_window', default='gaussian', choices=['gaussian', 'flat'], help='blending weights of --scene_stride N > 0')
     ap.add_argument('--scene_tta', type=int, default=1, choices=[1, 2, 4, 8],
                     help='symmetries of the square averaged per tile with --scene_stride N > 0: codes (0,), (0,1), (0,1,2,3), 0..7')
+    ap.add_argument('--val_curve_bins', type=int, default=0, metavar='N',
+                    help='0: off; a power of two in 2..4096: the validation pass also builds the precision / recall curve of class 1 over N '
+                         'score bins on the device (ScoreCurve) and the epoch record and the checkpoint metadata gain validate_best_f1, '
+                         'validate_best_threshold and validate_ap; with --scene_stride N > 0 the scene line gains ap, best_f1, best_threshold')
+    ap.add_argument('--scene_threshold', default='argmax', metavar='argmax|val|FLOAT',
+                    help='--scene_stride N > 0: the full-scene masks are the argmax (default), or P(change) >= the best-F1 threshold of '
+                         'this epoch\'s validation pass (val; needs --val_curve_bins), or >= a fixed FLOAT in [0, 1]')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
                                                      "band_stds, ...): its entries become defaults like utils/parser.py:7-10")
     pre, _ = ap.parse_known_args(argv)
@@ -449,6 +492,10 @@ def main(argv=None):
         raise SystemExit('--ema_decay / --swa / --ema_every / --ema_start / --ema_buffers are built into the fused step: add --fused_step true')
     if not averaging and (opt.ema_every != 1 or opt.ema_start != 0 or not opt.ema_buffers):
         raise SystemExit('--ema_every / --ema_start / --ema_buffers shape an average that is not on: add --ema_decay D or --swa')
+    try:
+        scene_thr = check_curve_flags(opt.val_curve_bins, opt.scene_threshold, opt.scene_stride)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
 
@@ -534,6 +581,10 @@ def main(argv=None):
             for p in model.parameters():
                 dist.broadcast(p.data, src=0)
     best = {'cd_f1scores': -1, 'cd_recalls': -1, 'cd_precisions': -1}              # train.py:62
+    val_curve = None
+    if opt.val_curve_bins:
+        from .utils.metrics import ScoreCurve
+        val_curve = ScoreCurve(opt.val_curve_bins, 1, opt.ignore_label)
     run_meta = dict(meta, **{k: getattr(opt, k) for k in DEFAULTS}, precision=opt.precision, world_size=world)
     for epoch in range(first_epoch, opt.epochs):
         train_loader.sampler.set_epoch(epoch)
@@ -542,13 +593,18 @@ def main(argv=None):
         else:
             tr = train_epoch_autograd(model, criterion, optimizer, train_loader, dev, opt.patch_size, world, feeder)
         with step.ema_weights() if averaging else contextlib.nullcontext():       # --ema_decay / --swa: evaluate the averaged weights
-            va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder, ignore_index=opt.ignore_label)
+            if val_curve is None:
+                va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder, ignore_index=opt.ignore_label)
+            else:
+                va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder, ignore_index=opt.ignore_label, curve=val_curve,
+                              world=world)
             if rank == 0:
                 print(json.dumps({'epoch': epoch, **{'train_' + k: float(v) for k, v in tr.items()},
                                   **{'validate_' + k: float(v) for k, v in va.items()},
                                   **({'ema_n_averaged': step.n_averaged} if averaging else {})}), flush=True)
             if scenes is not None and rank == 0:               # train.py:182-205: full validation images
-                _predict_scenes(model, scenes, val_cities, opt, epoch)
+                _predict_scenes(model, scenes, val_cities, opt, epoch, va['best_threshold'] if scene_thr == 'val' else
+                                None if scene_thr == 'argmax' else scene_thr)
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
                                   step.optimizer_state_dict() if fused else optimizer.state_dict(),
@@ -559,8 +615,12 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def _predict_scenes(model, scenes, val_cities, opt, epoch):
-    """train.py:182-205: the full validation scenes of one epoch, written as PNG masks (and, blended, as probabilities with a scene F1 line)."""
+def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None):
+    """train.py:182-205: the full validation scenes of one epoch, written as PNG masks (and, blended, as probabilities with a scene F1 line).
+    threshold (--scene_threshold): None = the argmax masks, else the masks are P(change) >= threshold.  With --val_curve_bins the scene
+    line of every city comes from a ScoreCurve over its probabilities and label raster (the run's --ignore_label left out), on the device:
+    ap, best_f1, best_threshold, and tp / fp / fn / precision / recall / f1 at the applied threshold (0.5 for the argmax masks),
+    rounded down to a bin edge."""
     from .utils import ingest
     from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
     os.makedirs(opt.log_dir, exist_ok=True)
@@ -571,10 +631,18 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch):
         if opt.scene_stride > 0:
             proba, mask = predict_scene_blended(model, st[0], st[1], patch_size=opt.patch_size, stride=opt.scene_stride,
                                                 window=opt.scene_window, symmetries=TTA_SYMMETRIES[opt.scene_tta],
-                                                batch_size=opt.batch_size)
+                                                batch_size=opt.batch_size, **({} if threshold is None else {'threshold': threshold}))
             ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}_proba.png'),
                                   torch.round(proba[1] * 255).to(torch.uint8).cpu().numpy())
-            scene_counts[city] = scene_scores(mask.cpu().numpy(), scenes[city]['labels'])
+            if getattr(opt, 'val_curve_bins', 0):
+                from .utils.metrics import ScoreCurve
+                sc = ScoreCurve(opt.val_curve_bins, 1, getattr(opt, 'ignore_label', None))
+                sc.update_proba(proba, torch.as_tensor(scenes[city]['labels']).to(proba.device))
+                c = sc.compute()
+                scene_counts[city] = dict(sc.at(0.5 if threshold is None else threshold), ap=c['ap'], best_f1=c['best_f1'],
+                                          best_threshold=c['best_threshold'], threshold='argmax' if threshold is None else threshold)
+            else:
+                scene_counts[city] = scene_scores(mask.cpu().numpy(), scenes[city]['labels'])
         else:
             mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
         ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}.png'), (mask * 255).cpu().numpy())

@@ -265,7 +265,7 @@ def check_blend_args(h, w, patch_size, stride, window, symmetries, n_classes, ba
 
 @torch.no_grad()
 def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None, window='gaussian', symmetries=(0,), batch_size=64,
-                          band_rows=None, two_streams=None):
+                          band_rows=None, two_streams=None, threshold=None, pos_class=1):
     """Class probabilities of a whole scene from overlapping tiles.
 
     Tiles of patch_size at `stride` (default patch_size // 2; blend_tile_origins), each under every code of `symmetries` (codes 0..7 of
@@ -274,8 +274,14 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
     through the inverse symmetry and weighted by `window` ('gaussian', 'flat' or a strictly positive float32 [p,p] tensor in scene
     orientation).  Returns (proba float32 [n_classes,H,W] = sum w softmax / sum w over every image that covers a pixel, mask uint8 [H,W]
     = its argmax, first maximum winning), both on the model's device.  Bit-reproducible, and the same bits for any batch_size split of
-    the same logits and for one lane or two.  scene_d1 / scene_d2, band_rows and two_streams as in predict_scene."""
+    the same logits and for one lane or two.  scene_d1 / scene_d2, band_rows and two_streams as in predict_scene.
+    threshold: None: the argmax mask (the launches and the bits of a call without the argument); a number in [0, 1]: mask =
+    proba[pos_class] >= threshold instead (bdn_threshold_mask, one more launch; proba keeps its bits) -- e.g. the best-F1 threshold of a
+    validation pass (fabric_amd.utils.metrics.ScoreCurve).  For two classes 0.5 and the argmax differ only at exact ties, proba[0] ==
+    proba[1]: the argmax gives class 0 there (the first maximum), the threshold 0.5 class 1."""
+    from .metrics import check_threshold
     eng = model.engine()
+    threshold, pos_class = check_threshold(threshold, pos_class, eng.n_classes)
     s1, s2 = torch.as_tensor(scene_d1), torch.as_tensor(scene_d2)
     if s1.dim() != 3 or s1.shape != s2.shape:
         raise RuntimeError(f'expected two [C,H,W] scenes of one shape, got {tuple(s1.shape)} and {tuple(s2.shape)}')
@@ -329,6 +335,8 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
         if feed is not None:
             feed.close()
     _lib.call('bdn_blend_finalize', _lib.ptr(proba), _lib.ptr(wsum), _lib.ptr(mask), ncls, h, w, _lib.stream_ptr())
+    if threshold is not None:
+        _lib.call('bdn_threshold_mask', _lib.ptr(proba), pos_class, threshold, _lib.ptr(mask), ncls, h * w, _lib.stream_ptr())
     return proba, mask
 
 

@@ -211,3 +211,125 @@ def batch_prf_from_counts(counts):
     r = tp / (tp + fn) if tp + fn else 0.0
     f = 2 * p * r / (p + r) if p + r else 0.0
     return p, r, f
+
+
+def check_threshold(threshold, pos_class=1, n_classes=2):
+    """Validate the threshold= / pos_class= pair of predict_scene_blended and ScoreCurve.at without touching a device: threshold None
+    (the argmax) or a real number in [0, 1], pos_class an integer class index.  Returns (None or float, int)."""
+    if isinstance(pos_class, bool) or not isinstance(pos_class, int) or not 0 <= pos_class < n_classes:
+        raise ValueError(f'pos_class must be an integer in 0..{n_classes - 1}, got {pos_class!r}')
+    if threshold is None:
+        return None, pos_class
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 <= float(threshold) <= 1.0:       # NaN fails the comparison
+        raise ValueError(f'threshold must be None (the argmax) or a number in [0, 1], got {threshold!r}')
+    return float(threshold), pos_class
+
+
+class ScoreCurve:
+    """Threshold-free validation of one class against the rest: a fixed-bin histogram of the score s = softmax(logits)[pos_class] of every
+    valid pixel, split by label, accumulated on the device over any number of batches (bdn_score_hist: integers, so exact, order-independent
+    and bit-reproducible), and turned by one launch (bdn_score_curve) into the precision / recall curve over the thresholds t_i = i / n_bins
+    (predict positive iff s >= t_i), the best-F1 threshold and the average precision -- sklearn's average_precision_score on the
+    bin-quantised scores.  Replaces the argmax-only precision_recall_fscore_support of the reference (train.py:96-106, 151-158).
+
+    n_bins: a power of two in 2..4096.  ignore_index: a label byte 0..255 left out of every count (None: no label is).  A pixel is
+    positive iff its label equals pos_class; every other valid label is negative.  Everything runs on the current stream; nothing waits
+    for the device except compute() and at(), which read one small buffer back.  CPU tensors raise: there is no CPU path."""
+
+    def __init__(self, n_bins=1024, pos_class=1, ignore_index=None):
+        if isinstance(n_bins, bool) or not isinstance(n_bins, int) or not 2 <= n_bins <= 4096 or n_bins & (n_bins - 1):
+            raise ValueError(f'n_bins must be a power of two in 2..4096, got {n_bins!r}')
+        if isinstance(pos_class, bool) or not isinstance(pos_class, int) or not 0 <= pos_class <= 255:
+            raise ValueError(f'pos_class must be a class index 0..255, got {pos_class!r}')
+        if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not 0 <= ignore_index <= 255):
+            raise ValueError(f'ignore_index must be None or a label byte 0..255, got {ignore_index!r}')
+        self.n_bins, self.pos_class, self.ignore_index = n_bins, pos_class, ignore_index
+        self._hist = None                                  # made on first use, on the device of the first batch
+
+    @property
+    def hist(self):
+        """The int64 [2, n_bins] device tensor of the counts, negatives first."""
+        return self._hist_on(self._hist.device if self._hist is not None else torch.device('cuda', torch.cuda.current_device()))
+
+    def _hist_on(self, device):
+        if self._hist is None:
+            self._hist = torch.zeros(2, self.n_bins, dtype=torch.int64, device=device)
+        elif self._hist.device != device:
+            raise RuntimeError(f'ScoreCurve: the histogram lives on {self._hist.device}, got tensors on {device}')
+        return self._hist
+
+    def _add(self, x, labels, is_logits, scores_out):
+        if not x.is_cuda:
+            raise RuntimeError('fabric_amd: ScoreCurve runs only on a ROCm device -- there is no CPU path')
+        B, C, H, W = x.shape
+        if not self.pos_class < C:
+            raise RuntimeError(f'pos_class {self.pos_class} is not a class of {C}-class scores')
+        xs = x.detach().contiguous().float()
+        lb, _ = _check_labels(xs, labels.to(xs.device))
+        if scores_out is not None:
+            if not (scores_out.is_cuda and scores_out.dtype == torch.float32 and scores_out.is_contiguous() and scores_out.numel() == B * H * W):
+                raise RuntimeError(f'scores_out must be a contiguous float32 device tensor of {B * H * W} elements')
+        _lib.call('bdn_score_hist', xs.data_ptr(), 1 if is_logits else 0, lb.data_ptr(), -1 if self.ignore_index is None else self.ignore_index,
+                  self.pos_class, B, C, H * W, self.n_bins, self._hist_on(xs.device).data_ptr(), _lib.ptr(scores_out), _lib.stream_ptr())
+
+    def update(self, logits, labels, scores_out=None):
+        """Add a batch: logits [B,ncls,H,W], labels [B,H,W] or [B,1,H,W] of any integer dtype.  scores_out: a float32 [B,H,W] device tensor
+        that receives every pixel's score (0 at an ignored pixel)."""
+        if logits.dim() != 4:
+            raise RuntimeError(f'logits must be [B,ncls,H,W], got {tuple(logits.shape)}')
+        self._add(logits, labels, True, scores_out)
+
+    def update_proba(self, proba, labels, scores_out=None):
+        """Add probabilities as they are: proba [ncls,H,W] (a scene of predict_scene_blended; labels [H,W]) or [B,ncls,H,W]."""
+        if proba.dim() == 3:
+            proba, labels = proba[None], labels[None]
+        if proba.dim() != 4:
+            raise RuntimeError(f'proba must be [ncls,H,W] or [B,ncls,H,W], got {tuple(proba.shape)}')
+        self._add(proba, labels, False, scores_out)
+
+    def reset(self):
+        if self._hist is not None:
+            self._hist.zero_()
+
+    def merge(self, other):
+        """Add another instance's histogram (same bins, class and ignore label)."""
+        if (other.n_bins, other.pos_class, other.ignore_index) != (self.n_bins, self.pos_class, self.ignore_index):
+            raise ValueError('ScoreCurve.merge: the two curves differ in n_bins, pos_class or ignore_index')
+        if other._hist is not None:
+            self._hist_on(other._hist.device).add_(other._hist)
+
+    def all_reduce(self, group=None):
+        """One SUM of the int64 histogram over the process group: exact whatever the world size."""
+        import torch.distributed as dist
+        dist.all_reduce(self.hist, op=dist.ReduceOp.SUM, group=group)
+
+    def _curve(self, want_curve):
+        dev = self.hist.device
+        summary = torch.empty(8, dtype=torch.float64, device=dev)
+        curve = torch.empty(4, self.n_bins, dtype=torch.float64, device=dev) if want_curve else None
+        _lib.call('bdn_score_curve', self.hist.data_ptr(), self.n_bins, _lib.ptr(curve), summary.data_ptr(), _lib.stream_ptr())
+        return summary, curve
+
+    def compute(self):
+        """One bdn_score_curve and one host read: best_f1, best_threshold (= best_bin / n_bins, the first maximum of F1 in ascending
+        threshold), best_bin, precision and recall at it, ap, n_pos, n_neg -- Python floats and ints."""
+        s = self._curve(False)[0].tolist()
+        return {'best_f1': s[0], 'best_threshold': s[1], 'best_bin': int(s[2]), 'precision': s[3], 'recall': s[4], 'ap': s[5],
+                'n_pos': int(s[6]), 'n_neg': int(s[7])}
+
+    def curve(self):
+        """(TP, FP, precision, recall): four float64 [n_bins] device tensors over the thresholds i / n_bins."""
+        c = self._curve(True)[1]
+        return c[0], c[1], c[2], c[3]
+
+    def at(self, threshold):
+        """Counts and scores at an arbitrary threshold, rounded down to a bin edge: {tp, fp, fn, precision, recall, f1}."""
+        t, _ = check_threshold(threshold)
+        if t is None:
+            raise ValueError('ScoreCurve.at needs a threshold in [0, 1]')
+        i = min(int(t * self.n_bins), self.n_bins - 1)
+        tp, fp, _, _ = self.curve()
+        tp0, tpi, fpi = [int(v) for v in torch.stack([tp[0], tp[i], fp[i]]).tolist()]
+        fn = tp0 - tpi
+        return {'tp': tpi, 'fp': fpi, 'fn': fn, 'precision': tpi / (tpi + fpi) if tpi + fpi else 0.0, 'recall': tpi / tp0 if tp0 else 0.0,
+                'f1': 2 * tpi / (2 * tpi + fpi + fn) if 2 * tpi + fpi + fn else 0.0}

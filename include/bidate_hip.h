@@ -665,6 +665,33 @@ int bdn_ema_update(float* avg, const float* params, const uint32_t* seg_end, con
 int bdn_ema_update_multi(const void* desc_dev, int n_tensors, int max_len, float weight, int copy, void* stream);
 int bdn_swap_segments(float* a, float* b, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, size_t n, void* stream);
 
+/* ---- threshold-free validation: the score histogram, the precision / recall curve and a thresholded scene mask.  The reference judges
+ * a model at the argmax only -- train.py:96-106 and train.py:151-158 (argmax + sklearn's prfs per batch), train.py:199 (the scene mask) --
+ * which for two classes is a probability threshold of 0.5.
+ * bdn_score_hist (replaces train.py:96-106 / train.py:151-158): x [n_img][ncls][HW] f32 (a logits batch [B,ncls,H,W], or a scene
+ *   probability map [ncls,H,W] with n_img = 1; HW is 64-bit: a 10 000^2 scene works), labels [n_img][HW] uint8.  The score of a pixel is
+ *   s = P(pos_class): x_is_logits = 1: formed exactly as bdn_blend_fold forms it (m = max_c l_c, e_c = expf(l_c - m), sum in class order,
+ *   e_pos / sum); x_is_logits = 0: x[pos_class] as it is.  bin = n_bins - 1 if s >= 1, (int)(s * n_bins) if s > 0, 0 otherwise (NaN lands
+ *   there); n_bins is a power of two in 2..4096, so the product is exact and bin >= i <=> s >= (float)i / n_bins.  A pixel whose label
+ *   equals ignore_label (0..255; -1 = none) is skipped before any of its logits is used (inf / NaN there reaches no output); a pixel is
+ *   positive iff label == pos_class, every other valid label (values >= ncls included) is negative.  hist: uint64 [2][n_bins], negatives
+ *   first; the kernel ADDS into it -- zero it once per pass, then accumulate batches without a host sync.  scores_out (NULL: not stored):
+ *   f32 [n_img][HW], every pixel's score and exactly 0.0f at an ignored pixel (written, not skipped).  Integer atomics (LDS and global)
+ *   carry the counts: integer sums do not depend on arrival order, so hist is the same bits on every run.  At most 2^40 pixels per call.
+ * bdn_score_curve (replaces the prfs of train.py:103-106 / train.py:155-158): one launch, one block, fixed order, double precision.
+ *   For threshold index i in 0..n_bins-1, t_i = i / n_bins (predict positive iff bin >= i): TP_i = sum_{b>=i} hist[1][b],
+ *   FP_i = sum_{b>=i} hist[0][b] (exact 64-bit suffix sums), n_pos = TP_0, n_neg = FP_0, P_i = TP_i / (TP_i + FP_i), R_i = TP_i / n_pos,
+ *   F_i = 2 TP_i / (2 TP_i + FP_i + n_pos - TP_i): each one correctly rounded double division of integers, 0 where the denominator is 0.
+ *   AP = sum_i (R_i - R_{i+1}) P_i with R_{n_bins} = 0 (sklearn's average_precision_score on the bin-quantised scores).  The best
+ *   threshold is the first maximum of F_i in ascending i.  summary: double[8] = {F_best, t_best, i_best, P_best, R_best, AP, n_pos,
+ *   n_neg}; curve_out (NULL: not stored): double [4][n_bins] = {TP, FP, P, R}.  An all-zero histogram gives an all-zero summary.
+ * bdn_threshold_mask (replaces train.py:199 where a threshold is wanted): mask[i] = proba[pos_class][i] >= threshold as uint8 0 / 1 for a
+ *   [ncls][HW] f32 map; threshold outside [0, 1] or NaN: BDN_E_ARG. ---- */
+int bdn_score_hist(const float* x, int x_is_logits, const uint8_t* labels, int ignore_label, int pos_class, int n_img, int ncls,
+                   long long HW, int n_bins, unsigned long long* hist, float* scores_out, void* stream);
+int bdn_score_curve(const unsigned long long* hist, int n_bins, double* curve_out, double* summary, void* stream);
+int bdn_threshold_mask(const float* proba, int pos_class, float threshold, uint8_t* mask, int ncls, long long HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
