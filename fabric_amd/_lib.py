@@ -130,6 +130,12 @@ SIGNATURES = {
     'bdn_score_hist': (_i, [_vp, _i, _vp, _i, _i, _i, _i, C.c_longlong, _i, _vp, _vp, _vp]),
     'bdn_score_curve': (_i, [_vp, _i, _vp, _vp, _vp]),
     'bdn_threshold_mask': (_i, [_vp, _i, _f, _vp, _i, C.c_longlong, _vp]),
+    'bdn_cc_workspace_bytes': (_sz, [_i, _i]),
+    'bdn_cc_tile': (_i, []),
+    'bdn_cc_label': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'bdn_cc_compact': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'bdn_cc_filter': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    'bdn_cc_stats': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

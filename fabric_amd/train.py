@@ -348,6 +348,18 @@ def check_curve_flags(val_curve_bins, scene_threshold, scene_stride):
     return thr
 
 
+def check_object_flags(scene_min_area, scene_objects, scene_connectivity, scene_stride):
+    """--scene_min_area / --scene_objects / --scene_connectivity / --scene_stride together, without a device: returns the min_area for
+    predict_scene_blended (None: no filtering); raises ValueError with the reason otherwise."""
+    if scene_min_area < 0:
+        raise ValueError(f'--scene_min_area {scene_min_area}: 0 (off) or the smallest object kept, in pixels')
+    if scene_connectivity not in (4, 8):
+        raise ValueError(f'--scene_connectivity {scene_connectivity}: 4 or 8')
+    if (scene_min_area > 0 or scene_objects) and scene_stride <= 0:
+        raise ValueError('--scene_min_area / --scene_objects work on the blended scene masks: add --scene_stride N > 0')
+    return scene_min_area if scene_min_area > 0 else None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Training change detection network (HIP path)')
     for k, v in DEFAULTS.items():
@@ -423,6 +435,14 @@ def main(argv=None):
     ap.add_argument('--scene_threshold', default='argmax', metavar='argmax|val|FLOAT',
                     help='--scene_stride N > 0: the full-scene masks are the argmax (default), or P(change) >= the best-F1 threshold of '
                          'this epoch\'s validation pass (val; needs --val_curve_bins), or >= a fixed FLOAT in [0, 1]')
+    ap.add_argument('--scene_min_area', type=int, default=0, metavar='N',
+                    help='--scene_stride N > 0: connected components of the scene mask below N pixels are removed on the device before the '
+                         'PNG is written (remove_small_objects); 0: off')
+    ap.add_argument('--scene_objects', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=False,
+                    help='--scene_stride N > 0: the scene line gains objects_pred, objects_true, object_precision, object_recall, object_f1 '
+                         'and min_area (object_scores on the unfiltered mask with min_area = --scene_min_area; --ignore_label pixels are cut out '
+                         'before the areas are measured)')
+    ap.add_argument('--scene_connectivity', type=int, default=8, choices=[4, 8], help='connectivity of --scene_min_area / --scene_objects')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
                                                      "band_stds, ...): its entries become defaults like utils/parser.py:7-10")
     pre, _ = ap.parse_known_args(argv)
@@ -494,6 +514,7 @@ def main(argv=None):
         raise SystemExit('--ema_every / --ema_start / --ema_buffers shape an average that is not on: add --ema_decay D or --swa')
     try:
         scene_thr = check_curve_flags(opt.val_curve_bins, opt.scene_threshold, opt.scene_stride)
+        scene_min_area = check_object_flags(opt.scene_min_area, opt.scene_objects, opt.scene_connectivity, opt.scene_stride)
     except ValueError as e:
         raise SystemExit(str(e))
     if opt.init_from and opt.resume:
@@ -604,7 +625,7 @@ def main(argv=None):
                                   **({'ema_n_averaged': step.n_averaged} if averaging else {})}), flush=True)
             if scenes is not None and rank == 0:               # train.py:182-205: full validation images
                 _predict_scenes(model, scenes, val_cities, opt, epoch, va['best_threshold'] if scene_thr == 'val' else
-                                None if scene_thr == 'argmax' else scene_thr)
+                                None if scene_thr == 'argmax' else scene_thr, min_area=scene_min_area)
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
                                   step.optimizer_state_dict() if fused else optimizer.state_dict(),
@@ -615,23 +636,34 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None):
+def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_area=None):
     """train.py:182-205: the full validation scenes of one epoch, written as PNG masks (and, blended, as probabilities with a scene F1 line).
     threshold (--scene_threshold): None = the argmax masks, else the masks are P(change) >= threshold.  With --val_curve_bins the scene
     line of every city comes from a ScoreCurve over its probabilities and label raster (the run's --ignore_label left out), on the device:
     ap, best_f1, best_threshold, and tp / fp / fn / precision / recall / f1 at the applied threshold (0.5 for the argmax masks),
-    rounded down to a bin edge."""
+    rounded down to a bin edge.
+    min_area (--scene_min_area, from check_object_flags): the components of the mask below that many pixels are removed before the PNG is
+    written and the pixel counts are taken.  With --scene_objects the objects are scored on the unfiltered mask by
+    object_scores(mask, truth, ignore_index=--ignore_label, min_area=min_area): the ignore pixels are cut out BEFORE the areas are
+    measured, so a component held above min_area only by pixels inside the ignore region is no object, although the PNG keeps it."""
     from .utils import ingest
     from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
     os.makedirs(opt.log_dir, exist_ok=True)
     model.eval()
     scene_counts = {}
+    conn = getattr(opt, 'scene_connectivity', 8)
+    objects = getattr(opt, 'scene_objects', False)
     for city in val_cities:
         st = scenes[city]['images']
         if opt.scene_stride > 0:
             proba, mask = predict_scene_blended(model, st[0], st[1], patch_size=opt.patch_size, stride=opt.scene_stride,
                                                 window=opt.scene_window, symmetries=TTA_SYMMETRIES[opt.scene_tta],
-                                                batch_size=opt.batch_size, **({} if threshold is None else {'threshold': threshold}))
+                                                batch_size=opt.batch_size, **({} if threshold is None else {'threshold': threshold}),
+                                                **({} if min_area is None or objects else {'min_area': min_area, 'connectivity': conn}))
+            raw = mask
+            if min_area is not None and objects:             # the unfiltered mask is scored below; the same launches as min_area= above
+                from .utils.objects import remove_small_objects
+                mask = remove_small_objects(raw, min_area, conn)
             ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}_proba.png'),
                                   torch.round(proba[1] * 255).to(torch.uint8).cpu().numpy())
             if getattr(opt, 'val_curve_bins', 0):
@@ -643,6 +675,14 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None):
                                           best_threshold=c['best_threshold'], threshold='argmax' if threshold is None else threshold)
             else:
                 scene_counts[city] = scene_scores(mask.cpu().numpy(), scenes[city]['labels'])
+            if objects:
+                from .utils.objects import object_scores
+                truth = torch.as_tensor(scenes[city]['labels']).to(device=mask.device, dtype=torch.uint8).contiguous()
+                obj = object_scores(raw, truth, 1, getattr(opt, 'ignore_label', None), conn, min_area or 1)
+                scene_counts[city].update({k: obj[k] for k in ('objects_pred', 'objects_true', 'object_precision', 'object_recall',
+                                                               'object_f1')})
+            if min_area is not None or objects:
+                scene_counts[city]['min_area'] = min_area or 1
         else:
             mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
         ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}.png'), (mask * 255).cpu().numpy())

@@ -265,7 +265,7 @@ def check_blend_args(h, w, patch_size, stride, window, symmetries, n_classes, ba
 
 @torch.no_grad()
 def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None, window='gaussian', symmetries=(0,), batch_size=64,
-                          band_rows=None, two_streams=None, threshold=None, pos_class=1):
+                          band_rows=None, two_streams=None, threshold=None, pos_class=1, min_area=None, connectivity=8):
     """Class probabilities of a whole scene from overlapping tiles.
 
     Tiles of patch_size at `stride` (default patch_size // 2; blend_tile_origins), each under every code of `symmetries` (codes 0..7 of
@@ -278,10 +278,16 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
     threshold: None: the argmax mask (the launches and the bits of a call without the argument); a number in [0, 1]: mask =
     proba[pos_class] >= threshold instead (bdn_threshold_mask, one more launch; proba keeps its bits) -- e.g. the best-F1 threshold of a
     validation pass (fabric_amd.utils.metrics.ScoreCurve).  For two classes 0.5 and the argmax differ only at exact ties, proba[0] ==
-    proba[1]: the argmax gives class 0 there (the first maximum), the threshold 0.5 class 1."""
+    proba[1]: the argmax gives class 0 there (the first maximum), the threshold 0.5 class 1.
+    min_area: None: the mask as it is (the launches and the bits of a call without the argument); an integer >= 1: the connected components
+    (`connectivity` 4 or 8) of mask == 1 with fewer pixels are removed from the mask (fabric_amd.utils.objects.remove_small_objects, on the
+    current stream behind the finalize / threshold launch, no host read; proba keeps its bits)."""
     from .metrics import check_threshold
     eng = model.engine()
     threshold, pos_class = check_threshold(threshold, pos_class, eng.n_classes)
+    if min_area is not None:
+        from .objects import check_cc_args, remove_small_objects
+        check_cc_args(torch.empty(1, 1, dtype=torch.uint8, device='meta'), connectivity, min_area=min_area)
     s1, s2 = torch.as_tensor(scene_d1), torch.as_tensor(scene_d2)
     if s1.dim() != 3 or s1.shape != s2.shape:
         raise RuntimeError(f'expected two [C,H,W] scenes of one shape, got {tuple(s1.shape)} and {tuple(s2.shape)}')
@@ -337,6 +343,8 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
     _lib.call('bdn_blend_finalize', _lib.ptr(proba), _lib.ptr(wsum), _lib.ptr(mask), ncls, h, w, _lib.stream_ptr())
     if threshold is not None:
         _lib.call('bdn_threshold_mask', _lib.ptr(proba), pos_class, threshold, _lib.ptr(mask), ncls, h * w, _lib.stream_ptr())
+    if min_area is not None:
+        remove_small_objects(mask, min_area, connectivity, out=mask)
     return proba, mask
 
 

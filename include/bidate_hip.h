@@ -692,6 +692,40 @@ int bdn_score_hist(const float* x, int x_is_logits, const uint8_t* labels, int i
 int bdn_score_curve(const unsigned long long* hist, int n_bins, double* curve_out, double* summary, void* stream);
 int bdn_threshold_mask(const float* proba, int pos_class, float threshold, uint8_t* mask, int ncls, long long HW, void* stream);
 
+/* ---- connected components of a scene mask: label, compact, filter by area, per-object statistics.  They replace the host-side
+ * scipy.ndimage.label + np.bincount after a device-to-host copy of the scene mask that train.py:199 produces (the reference stops at the
+ * pixel mask; dropping speckle and counting objects are the steps a change-detection product takes next).  All rasters are [H][W]
+ * row-major, 1 <= H, W and H * W <= 2^31 - 2; connectivity is 4 or 8; a null required pointer, a misaligned pointer or a value outside
+ * its range is BDN_E_ARG before any launch.  Integer arithmetic only: integer sums do not depend on arrival order and a component's root
+ * is its smallest linear index y * W + x whatever the schedule, so every output is the same bits on every run.  The number of launches
+ * depends on H and W only; nothing is read back; no loop waits for another thread and every chain walk is capped (counts[2]).
+ * bdn_cc_workspace_bytes: the workspace of bdn_cc_label and bdn_cc_compact (16-byte aligned; 0 for a shape outside the limits).  The
+ *   kernels initialise every word they read: a workspace born 0xFF gives the outputs of a zeroed one.  bdn_cc_tile: the tile edge (64).
+ * bdn_cc_label: a pixel is foreground iff src[i] == fg_value (uint8) and, with exclude non-NULL, exclude[i] != exclude_value (the ignore
+ *   label of a truth raster applied to a predicted mask).  labels int32 [H][W]: 0 on background, 1 + r elsewhere, r the smallest linear
+ *   index of the pixel's component (canonical: comparable without relabelling).  area int32 [H][W] (NULL: not computed): the component's
+ *   pixel count at its root pixel r, 0 everywhere else (written, not skipped).  counts int32[4] = {n_components, n_foreground, status, 0};
+ *   status is non-zero only if an iteration cap was hit (the result is then unspecified).  Three launches (tiles in LDS, seams, flatten).
+ * bdn_cc_compact: compact int32 [H][W] (not aliasing labels): 0 on background, elsewhere the 1-based rank of the pixel's root among all
+ *   roots in ascending index -- scipy.ndimage.label's numbering.  counts (NULL allowed): counts[0] = the number of roots, the other
+ *   words stay.  Four launches: block sums, one block scanning them, ranks at the roots, ranks spread; no block waits for another.
+ * bdn_cc_filter: out_mask[i] (uint8) = 1 iff labels[i] != 0 and area[labels[i] - 1] >= min_area, else 0; min_area <= 1 keeps every
+ *   foreground pixel (area may then be NULL).  src_mask is not read (labels carry the foreground test) and out_mask may alias it.
+ * bdn_cc_stats: table int32 [n_max][8] = {area, ymin, xmin, ymax, xmax, overlap, 0, 0} of compact label k in row k - 1; overlap = the
+ *   component's pixels with other[i] == other_value (other uint8, NULL: 0); a pixel with other[i] == other_exclude_value (-1: none) adds
+ *   to no column.  Rows of labels that do not occur are {0, H, W, -1, -1, 0, 0, 0}; a label above n_max (1..2^28 - 1) is skipped.  The
+ *   kernel initialises the table itself, then integer atomicAdd / atomicMin / atomicMax.
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+size_t bdn_cc_workspace_bytes(int H, int W);
+int bdn_cc_tile(void);
+int bdn_cc_label(const uint8_t* src, int fg_value, const uint8_t* exclude, int exclude_value, int connectivity, int H, int W,
+                 int32_t* labels, int32_t* area, int32_t* counts, void* workspace, void* stream);
+int bdn_cc_compact(const int32_t* labels, int H, int W, int32_t* compact, int32_t* counts, void* workspace, void* stream);
+int bdn_cc_filter(const uint8_t* src_mask, const int32_t* labels, const int32_t* area, int min_area, uint8_t* out_mask, int H, int W,
+                  void* stream);
+int bdn_cc_stats(const int32_t* compact, int n_max, const uint8_t* other, int other_value, int other_exclude_value, int H, int W,
+                 int32_t* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
