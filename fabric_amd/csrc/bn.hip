@@ -8,8 +8,6 @@
 // (deterministic, no atomics) and are summed in double.
 #include "common.hpp"
 
-static inline unsigned grid_for(size_t n, int block = 256) { return (unsigned)((n + block - 1) / block); }
-
 // ---------------------------------------------------------------- row reduction helpers
 // partial: [n_rows][2][C] f32.  Stage A (many rows): grid (ceil(C/64), G, RS), 256 threads = 16 row lanes x 16 channel
 // quads (16-byte loads); block (cb, g, s) sums rows [s*rps, (s+1)*rps) of group g in double -> part2[g][s][2][C].

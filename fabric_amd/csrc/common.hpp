@@ -27,6 +27,12 @@ void bdn_set_error(const char* fmt, ...);
     if (err_ != hipSuccess) BDN_FAIL(BDN_E_HIP, "%s: hipFuncSetAttribute(%d): %s", name_, (int)(bytes_), hipGetErrorString(err_)); \
 } while (0)
 
+// blocks of `block` threads that cover n items, one item per thread
+static inline unsigned grid_for(size_t n, int block = 256) { return (unsigned)((n + block - 1) / block); }
+
+// the largest class count of the 1x1 classifier (head.hip) and of the criteria on its logits (loss.hip)
+constexpr int OUTC_MAXCLS = 8;
+
 // bf16x3 helpers defined in x3.hip, used by the dtype dispatch of bdn_pack_weights / bdn_conv3x3_wgrad_ex
 int bdn_pack_weights_x3(const float* w_oihw, void* wf, void* wd, int Cout, int Cin, int Cin_pad, hipStream_t st);
 // bdn_pack_weights_multi's device record: one per layer

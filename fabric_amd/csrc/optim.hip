@@ -1,0 +1,717 @@
+// Parameter updates over the flat float32 buffers: SGD, momentum SGD, Adam / AdamW, their grouped and _ex forms, EMA / SWA averaging and
+// the buffer swap, gradient accumulation and the global gradient norm.  Memory-bound float4 passes; no atomics, fixed-order reductions.
+#include "common.hpp"
+
+// ============================================================ SGD (train.py:55,95)
+__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float step, size_t n4, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n4) {
+        float4 a = reinterpret_cast<float4*>(p)[i]; const float4 b = reinterpret_cast<const float4*>(g)[i];
+        a.x -= step * b.x; a.y -= step * b.y; a.z -= step * b.z; a.w -= step * b.w;
+        reinterpret_cast<float4*>(p)[i] = a;
+    }
+    if (i == 0) for (size_t k = n4 * 4; k < n; k++) p[k] -= step * g[k];
+}
+
+extern "C" int bdn_sgd_step(float* params, const float* grads, float lr, float grad_scale, size_t n, void* stream) {
+    if (!params || !grads) BDN_FAIL(BDN_E_ARG, "sgd_step: null pointer");
+    if (((uintptr_t)params | (uintptr_t)grads) & 15) BDN_FAIL(BDN_E_ARG, "sgd_step: buffers must be 16-byte aligned");
+    if (n == 0) return BDN_OK;
+    const size_t n4 = n / 4;
+    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n4 > 0 ? n4 : 1)), dim3(256), 0, (hipStream_t)stream, params, grads, lr * grad_scale, n4, n);
+    BDN_CHECK_LAUNCH("sgd_step");
+    return BDN_OK;
+}
+
+// ============================================================ momentum SGD / Adam / AdamW (train.py:55-56,95)
+// torch.optim's single-tensor update rules over the flat f32 buffers, one element per lane and OPT_VEC float4s in flight per
+// thread (every load of a pass is issued before the first store).  Memory-bound: the grid is capped at 8 blocks per CU of the
+// 256 and grid-strides the rest.  No LDS, no atomics: every element's result depends only on its own inputs (bit-reproducible).
+// IEEE division and sqrt (hipcc's default correctly rounded f32 divide / sqrt).
+constexpr int OPT_VEC = 4;
+
+static inline unsigned opt_grid(size_t n4) {
+    const size_t b = (n4 + 256 * OPT_VEC - 1) / (256 * OPT_VEC);
+    return (unsigned)(b == 0 ? 1 : (b < 2048 ? b : 2048));
+}
+
+struct SgdmParams { float lr, grad_scale, momentum, damp1 /* 1 - dampening */, weight_decay; int first, nesterov; };
+
+// SGD (torch 2.10 _single_tensor_sgd): g = s*grad (+ wd*p); buf = g on the first step, momentum*buf + (1-dampening)*g after it;
+// g = g + momentum*buf (nesterov) or buf; p -= lr*g.  MOM = false: no momentum buffer is read or written.
+template <bool MOM>
+__device__ __forceinline__ void sgdm_elem(float& p, float gr, float& buf, const SgdmParams& a) {
+    float g = a.grad_scale * gr;
+    if (a.weight_decay != 0.f) g = g + a.weight_decay * p;
+    if (MOM) {
+        buf = a.first ? g : a.momentum * buf + a.damp1 * g;
+        g = a.nesterov ? g + a.momentum * buf : buf;
+    }
+    p = p - a.lr * g;
+}
+
+template <bool MOM>
+__global__ void __launch_bounds__(256) sgdm_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                   SgdmParams a, size_t n4, size_t n) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t base = (size_t)blockIdx.x * 256 + threadIdx.x; base < n4; base += stride * OPT_VEC) {
+        float4 P[OPT_VEC], G[OPT_VEC], M[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                P[u] = reinterpret_cast<const float4*>(p)[i]; G[u] = reinterpret_cast<const float4*>(g)[i];
+                if (MOM && !a.first) M[u] = reinterpret_cast<const float4*>(buf)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                sgdm_elem<MOM>(P[u].x, G[u].x, M[u].x, a); sgdm_elem<MOM>(P[u].y, G[u].y, M[u].y, a);
+                sgdm_elem<MOM>(P[u].z, G[u].z, M[u].z, a); sgdm_elem<MOM>(P[u].w, G[u].w, M[u].w, a);
+                reinterpret_cast<float4*>(p)[i] = P[u];
+                if (MOM) reinterpret_cast<float4*>(buf)[i] = M[u];
+            }
+        }
+    }
+    // the n % 4 trailing elements (never for a FlatLayout buffer: every tensor is padded to 4 floats)
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        const size_t k = n4 * 4 + threadIdx.x;
+        float m = (MOM && !a.first) ? buf[k] : 0.f, q = p[k];
+        sgdm_elem<MOM>(q, g[k], m, a);
+        p[k] = q;
+        if (MOM) buf[k] = m;
+    }
+}
+
+// the rule's checks and kernel parameters, one place for bdn_sgd_momentum_step and the grouped launcher (per group): the same bits in both
+static int sgdm_rule_check(const char* what, float momentum, const float* momentum_buf, float dampening, int nesterov) {
+    if ((momentum != 0.f) != (momentum_buf != nullptr)) BDN_FAIL(BDN_E_ARG, "%s: momentum_buf must be given iff momentum != 0", what);
+    if (nesterov && (momentum <= 0.f || dampening != 0.f)) BDN_FAIL(BDN_E_ARG, "%s: nesterov needs momentum > 0 and zero dampening", what);
+    return BDN_OK;
+}
+static SgdmParams sgdm_params(float lr, float weight_decay, float grad_scale, float momentum, float dampening, int nesterov, int first_step) {
+    return SgdmParams{lr, grad_scale, momentum, (float)(1.0 - (double)dampening), weight_decay, first_step ? 1 : 0, nesterov ? 1 : 0};
+}
+
+extern "C" int bdn_sgd_momentum_step(float* params, const float* grads, float* momentum_buf, float lr, float grad_scale, float momentum,
+                                     float dampening, float weight_decay, int nesterov, int first_step, size_t n, void* stream) {
+    if (!params || !grads) BDN_FAIL(BDN_E_ARG, "sgd_momentum_step: null pointer");
+    if (int rc = sgdm_rule_check("sgd_momentum_step", momentum, momentum_buf, dampening, nesterov)) return rc;
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15)
+        BDN_FAIL(BDN_E_ARG, "sgd_momentum_step: buffers must be 16-byte aligned");
+    if (n == 0) return BDN_OK;
+    const size_t n4 = n / 4;
+    const SgdmParams a = sgdm_params(lr, weight_decay, grad_scale, momentum, dampening, nesterov, first_step);
+    if (momentum_buf)
+        hipLaunchKernelGGL(sgdm_kernel<true>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, params, grads, momentum_buf, a, n4, n);
+    else
+        hipLaunchKernelGGL(sgdm_kernel<false>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, params, grads, momentum_buf, a, n4, n);
+    BDN_CHECK_LAUNCH("sgd_momentum_step");
+    return BDN_OK;
+}
+
+struct AdamParams { float grad_scale, w1 /* lerp weight 1 - beta1 */, beta2, c2 /* 1 - beta2 */, eps, l2 /* Adam's coupled weight
+                    decay */, decay /* AdamW: 1 - lr*wd */, step_size /* lr / bc1 */, bc2_sqrt; int lerp_hi; };
+
+// Adam / AdamW (torch 2.10 _single_tensor_adam): g = s*grad; AdamW p *= 1 - lr*wd, Adam g += wd*p; m = lerp(m, g, 1-beta1);
+// v = beta2*v + (1-beta2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps).  lerp as torch evaluates it: weight < 0.5 ? m + w*(g-m)
+// : g - (g-m)*(1-w).
+__device__ __forceinline__ void adam_elem(float& p, float gr, float& m, float& v, const AdamParams& a) {
+    float g = a.grad_scale * gr;
+    p = p * a.decay;
+    if (a.l2 != 0.f) g = g + a.l2 * p;
+    m = a.lerp_hi ? g - (g - m) * (1.f - a.w1) : m + a.w1 * (g - m);
+    v = a.beta2 * v + a.c2 * g * g;
+    const float den = sqrtf(v) / a.bc2_sqrt + a.eps;
+    p = p - a.step_size * (m / den);
+}
+
+__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, AdamParams a, size_t n4, size_t n) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t base = (size_t)blockIdx.x * 256 + threadIdx.x; base < n4; base += stride * OPT_VEC) {
+        float4 P[OPT_VEC], G[OPT_VEC], M[OPT_VEC], V[OPT_VEC];
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                P[u] = reinterpret_cast<const float4*>(p)[i]; G[u] = reinterpret_cast<const float4*>(g)[i];
+                M[u] = reinterpret_cast<const float4*>(m)[i]; V[u] = reinterpret_cast<const float4*>(v)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = base + u * stride;
+            if (i < n4) {
+                adam_elem(P[u].x, G[u].x, M[u].x, V[u].x, a); adam_elem(P[u].y, G[u].y, M[u].y, V[u].y, a);
+                adam_elem(P[u].z, G[u].z, M[u].z, V[u].z, a); adam_elem(P[u].w, G[u].w, M[u].w, V[u].w, a);
+                reinterpret_cast<float4*>(p)[i] = P[u]; reinterpret_cast<float4*>(m)[i] = M[u]; reinterpret_cast<float4*>(v)[i] = V[u];
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {
+        const size_t k = n4 * 4 + threadIdx.x;
+        float q = p[k], mk = m[k], vk = v[k];
+        adam_elem(q, g[k], mk, vk, a);
+        p[k] = q; m[k] = mk; v[k] = vk;
+    }
+}
+
+// likewise for bdn_adam_step and the grouped launcher (bdn_adam_step has tested the state pointers before it asks)
+static int adam_rule_check(const char* what, const float* exp_avg, const float* exp_avg_sq, long long step, double beta1, double beta2) {
+    if (!exp_avg || !exp_avg_sq) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (step < 1) BDN_FAIL(BDN_E_ARG, "%s: step must be >= 1 (1-based, counted after the increment), got %lld", what, step);
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) BDN_FAIL(BDN_E_ARG, "%s: betas must lie in [0, 1)", what);
+    return BDN_OK;
+}
+// 1 - beta and the bias corrections in double on the host, as torch computes them from Python floats: no device sync
+static AdamParams adam_params(float lr, float weight_decay, float grad_scale, double beta1, double beta2, float eps, int decoupled, long long step) {
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    const float w1 = (float)(1.0 - beta1);
+    const bool dec = decoupled != 0;
+    return AdamParams{grad_scale, w1, (float)beta2, (float)(1.0 - beta2), eps, dec ? 0.f : weight_decay,
+                      dec ? (float)(1.0 - (double)lr * (double)weight_decay) : 1.f, (float)((double)lr / bc1), (float)std::sqrt(bc2),
+                      w1 >= 0.5f ? 1 : 0};
+}
+
+extern "C" int bdn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float lr, float grad_scale,
+                             double beta1, double beta2, float eps, float weight_decay, int decoupled_weight_decay, long long step,
+                             size_t n, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq) BDN_FAIL(BDN_E_ARG, "adam_step: null pointer");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15)
+        BDN_FAIL(BDN_E_ARG, "adam_step: buffers must be 16-byte aligned");
+    if (int rc = adam_rule_check("adam_step", exp_avg, exp_avg_sq, step, beta1, beta2)) return rc;
+    if (n == 0) return BDN_OK;
+    const AdamParams a = adam_params(lr, weight_decay, grad_scale, beta1, beta2, eps, decoupled_weight_decay, step);
+    const size_t n4 = n / 4;
+    hipLaunchKernelGGL(adam_kernel, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, a, n4, n);
+    BDN_CHECK_LAUNCH("adam_step");
+    return BDN_OK;
+}
+
+// ============================================================ the same rules with parameter groups and frozen tensors (train.py:55-56,95)
+// One launch over the flat buffers in which every float4 takes the hyperparameters of the group its tensor belongs to, or is skipped
+// (frozen: neither read nor written).  FlatLayout pads every tensor to 4 floats, so a float4 never straddles two tensors.  The layout is
+// a segment table in device memory -- sorted segment ends in float4 units and one group id per segment, OPT_FROZEN for a frozen one --
+// staged in LDS once per block; the per-group hyperparameters travel by value in the kernel arguments and are staged beside it.  A
+// block's 256 consecutive vectors almost always lie in one segment: one lookup of the first vector then serves the block (the lookup is
+// per lane otherwise).  A vector behind the last segment end or with a group id outside [0, n_groups) is skipped, so a wrong table can
+// not move an access out of the buffers.  The element formulas are sgd's p -= step*g, sgdm_elem and adam_elem above; the pass keeps
+// their shape (OPT_VEC float4s per thread, every load issued before the first store, no reductions, no atomics).
+constexpr int OPT_MAX_GROUPS = 8;
+constexpr int OPT_MAX_SEGS = 256;
+constexpr int OPT_FROZEN = -1;
+
+struct SegTable { const uint32_t* end; const int32_t* group; int n_seg, n_groups; };
+template <typename P> struct GroupArgs { P g[OPT_MAX_GROUPS]; };
+
+struct RuleSgd {                                        // plain SGD: bdn_sgd_step's p -= (lr * grad_scale) * g
+    using Params = float;
+    static constexpr int NS = 0;
+    static constexpr bool GRAD = true;
+    static __device__ __forceinline__ void scale(Params& step, float s) { step *= s; }
+    static __device__ __forceinline__ bool reads_state(const Params&) { return false; }
+    static __device__ __forceinline__ void elem(float& p, float g, float&, float&, const Params& step) { p -= step * g; }
+};
+template <bool MOM> struct RuleSgdm {
+    using Params = SgdmParams;
+    static constexpr int NS = MOM ? 1 : 0;
+    static constexpr bool GRAD = true;
+    static __device__ __forceinline__ void scale(Params& a, float s) { a.grad_scale *= s; }
+    static __device__ __forceinline__ bool reads_state(const Params& a) { return MOM && !a.first; }
+    static __device__ __forceinline__ void elem(float& p, float g, float& buf, float&, const Params& a) { sgdm_elem<MOM>(p, g, buf, a); }
+};
+struct RuleAdam {
+    using Params = AdamParams;
+    static constexpr int NS = 2;
+    static constexpr bool GRAD = true;
+    static __device__ __forceinline__ void scale(Params& a, float s) { a.grad_scale *= s; }
+    static __device__ __forceinline__ bool reads_state(const Params&) { return true; }
+    static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v, const Params& a) { adam_elem(p, g, m, v, a); }
+};
+
+// One halving step of the lookup "first s with end[s] > i" over the LDS table, which is padded with UINT32_MAX to `cap` entries, a power
+// of two: branch-free, so the OPT_VEC lookups of a pass advance side by side (their LDS reads are independent) and lanes never diverge.
+__device__ __forceinline__ void seg_step(const uint32_t* s_end, int h, uint32_t i, int& s) {
+    if (s_end[s + h - 1] <= i) s += h;
+}
+
+template <typename Rule>
+__global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                      float* __restrict__ s1, SegTable t, GroupArgs<typename Rule::Params> a,
+                                                      const float* __restrict__ dev_scale, size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS];
+    __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
+    int cap = 1;
+    while (cap < t.n_seg) cap <<= 1;
+    for (int k = threadIdx.x; k < cap; k += 256) {
+        s_end[k] = k < t.n_seg ? t.end[k] : 0xffffffffu;
+        s_grp[k] = k < t.n_seg ? t.group[k] : (t.n_seg == 0 ? 0 : OPT_FROZEN);      // no table (bdn_ema_update): one segment of group 0
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < OPT_MAX_GROUPS; k++) s_par[k] = a.g[k];
+        if (dev_scale) {                                     // the _ex entry points: grad_scale * *dev_scale, formed once per block
+            const float ds = *dev_scale;
+#pragma unroll
+            for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
+        }
+    }
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
+        int gid[OPT_VEC], seg[OPT_VEC] = {};
+        for (int h = cap >> 1; h > 0; h >>= 1) {             // the segment of each pass's first vector (clamped: a pass past the end is skipped below)
+#pragma unroll
+            for (int u = 0; u < OPT_VEC; u++) {
+                const size_t first = b0 + u * stride;
+                seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), seg[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t first = b0 + u * stride, i = first + threadIdx.x;
+            int grp = OPT_FROZEN;
+            if (i < n4) {
+                const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
+                int s = seg[u];
+                if (!(s_end[s] > last)) {                    // the block's 256 vectors span a boundary (or lie behind the table): per lane
+                    s = 0;
+                    for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+                }
+                if (s_end[s] > i) grp = s_grp[s];
+            }
+            gid[u] = (unsigned)grp < (unsigned)t.n_groups ? grp : OPT_FROZEN;
+        }
+        float4 P[OPT_VEC], G[OPT_VEC], S0[OPT_VEC] = {}, S1[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (gid[u] != OPT_FROZEN) {
+                P[u] = reinterpret_cast<const float4*>(p)[i];
+                if (Rule::GRAD) G[u] = reinterpret_cast<const float4*>(g)[i];
+                if (Rule::NS > 0 && Rule::reads_state(s_par[0])) S0[u] = reinterpret_cast<const float4*>(s0)[i];
+                if (Rule::NS > 1) S1[u] = reinterpret_cast<const float4*>(s1)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (gid[u] != OPT_FROZEN) {
+                const typename Rule::Params q = s_par[gid[u]];
+                float4 g4 = {};                              // a rule without `g` never loaded G[u]: it is not read either
+                if constexpr (Rule::GRAD) g4 = G[u];
+                Rule::elem(P[u].x, g4.x, S0[u].x, S1[u].x, q); Rule::elem(P[u].y, g4.y, S0[u].y, S1[u].y, q);
+                Rule::elem(P[u].z, g4.z, S0[u].z, S1[u].z, q); Rule::elem(P[u].w, g4.w, S0[u].w, S1[u].w, q);
+                reinterpret_cast<float4*>(p)[i] = P[u];
+                if (Rule::NS > 0) reinterpret_cast<float4*>(s0)[i] = S0[u];
+                if (Rule::NS > 1) reinterpret_cast<float4*>(s1)[i] = S1[u];
+            }
+        }
+    }
+}
+
+static int grouped_check(const char* what, const void* params, const void* grads, const void* s0, const void* s1, const uint32_t* seg_end,
+                         const int32_t* seg_group, int n_seg, int n_groups, const float* lr, size_t n) {
+    if (!params || !grads || !seg_end || !seg_group || !lr) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (n_groups < 1 || n_groups > OPT_MAX_GROUPS)
+        BDN_FAIL(BDN_E_ARG, "%s: %d groups (1..%d: their hyperparameters travel in the kernel arguments)", what, n_groups, OPT_MAX_GROUPS);
+    if (n_seg < 1 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d segments (1..%d)", what, n_seg, OPT_MAX_SEGS);
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)s0 | (uintptr_t)s1) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
+    if (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3) BDN_FAIL(BDN_E_ARG, "%s: segment table must be 4-byte aligned", what);
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
+    return BDN_OK;
+}
+
+// The grouped entry points and their _ex forms share one launcher each: dev_scale == nullptr is the plain form (the kernel then never
+// touches the staged parameters, so its bits are those it always gave), a device pointer the _ex form.
+static int ex_check(const char* what, const float* dev_scale) {
+    if (!dev_scale) BDN_FAIL(BDN_E_ARG, "%s: null pointer (dev_scale)", what);
+    if ((uintptr_t)dev_scale & 3) BDN_FAIL(BDN_E_ARG, "%s: dev_scale must be 4-byte aligned", what);
+    return BDN_OK;
+}
+
+static int sgd_grouped_launch(const char* what, float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group,
+                              int n_seg, int n_groups, const float* lr, float grad_scale, const float* dev_scale, size_t n, void* stream) {
+    if (int rc = grouped_check(what, params, grads, nullptr, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+    if (n == 0) return BDN_OK;
+    GroupArgs<float> a{};
+    for (int k = 0; k < n_groups; k++) a.g[k] = lr[k] * grad_scale;
+    const SegTable t{seg_end, seg_group, n_seg, n_groups};
+    hipLaunchKernelGGL(grouped_kernel<RuleSgd>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads, (float*)nullptr,
+                       (float*)nullptr, t, a, dev_scale, n / 4);
+    BDN_CHECK_LAUNCH(what);
+    return BDN_OK;
+}
+
+extern "C" int bdn_sgd_step_grouped(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg,
+                                    int n_groups, const float* lr, float grad_scale, size_t n, void* stream) {
+    return sgd_grouped_launch("sgd_step_grouped", params, grads, seg_end, seg_group, n_seg, n_groups, lr, grad_scale, nullptr, n, stream);
+}
+
+extern "C" int bdn_sgd_step_grouped_ex(float* params, const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg,
+                                       int n_groups, const float* lr, float grad_scale, const float* dev_scale, size_t n, void* stream) {
+    if (int rc = ex_check("sgd_step_grouped_ex", dev_scale)) return rc;
+    return sgd_grouped_launch("sgd_step_grouped_ex", params, grads, seg_end, seg_group, n_seg, n_groups, lr, grad_scale, dev_scale, n, stream);
+}
+
+static int sgdm_grouped_launch(const char* what, float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                               const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                               float grad_scale, const float* dev_scale, float momentum, float dampening, int nesterov, int first_step,
+                               size_t n, void* stream) {
+    if (int rc = grouped_check(what, params, grads, momentum_buf, nullptr, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+    if (!weight_decay) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (int rc = sgdm_rule_check(what, momentum, momentum_buf, dampening, nesterov)) return rc;
+    if (n == 0) return BDN_OK;
+    GroupArgs<SgdmParams> a{};
+    for (int k = 0; k < n_groups; k++) a.g[k] = sgdm_params(lr[k], weight_decay[k], grad_scale, momentum, dampening, nesterov, first_step);
+    for (int k = n_groups; k < OPT_MAX_GROUPS; k++) a.g[k].first = first_step ? 1 : 0;        // reads_state() asks entry 0 only; keep all alike
+    const SegTable t{seg_end, seg_group, n_seg, n_groups};
+    if (momentum_buf)
+        hipLaunchKernelGGL(grouped_kernel<RuleSgdm<true>>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                           momentum_buf, (float*)nullptr, t, a, dev_scale, n / 4);
+    else
+        hipLaunchKernelGGL(grouped_kernel<RuleSgdm<false>>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads,
+                           (float*)nullptr, (float*)nullptr, t, a, dev_scale, n / 4);
+    BDN_CHECK_LAUNCH(what);
+    return BDN_OK;
+}
+
+extern "C" int bdn_sgd_momentum_step_grouped(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                                             const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                             float grad_scale, float momentum, float dampening, int nesterov, int first_step, size_t n,
+                                             void* stream) {
+    return sgdm_grouped_launch("sgd_momentum_step_grouped", params, grads, momentum_buf, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, nullptr, momentum, dampening, nesterov, first_step, n, stream);
+}
+
+extern "C" int bdn_sgd_momentum_step_grouped_ex(float* params, const float* grads, float* momentum_buf, const uint32_t* seg_end,
+                                                const int32_t* seg_group, int n_seg, int n_groups, const float* lr,
+                                                const float* weight_decay, float grad_scale, const float* dev_scale, float momentum,
+                                                float dampening, int nesterov, int first_step, size_t n, void* stream) {
+    if (int rc = ex_check("sgd_momentum_step_grouped_ex", dev_scale)) return rc;
+    return sgdm_grouped_launch("sgd_momentum_step_grouped_ex", params, grads, momentum_buf, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, dev_scale, momentum, dampening, nesterov, first_step, n, stream);
+}
+
+static int adam_grouped_launch(const char* what, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                               const uint32_t* seg_end, const int32_t* seg_group, int n_seg, int n_groups, const float* lr,
+                               const float* weight_decay, float grad_scale, const float* dev_scale, double beta1, double beta2, float eps,
+                               int decoupled_weight_decay, long long step, size_t n, void* stream) {
+    if (int rc = grouped_check(what, params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr, n)) return rc;
+    if (!weight_decay) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (int rc = adam_rule_check(what, exp_avg, exp_avg_sq, step, beta1, beta2)) return rc;
+    if (n == 0) return BDN_OK;
+    GroupArgs<AdamParams> a{};
+    for (int k = 0; k < n_groups; k++) a.g[k] = adam_params(lr[k], weight_decay[k], grad_scale, beta1, beta2, eps, decoupled_weight_decay, step);
+    const SegTable t{seg_end, seg_group, n_seg, n_groups};
+    hipLaunchKernelGGL(grouped_kernel<RuleAdam>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, t, a, dev_scale, n / 4);
+    BDN_CHECK_LAUNCH(what);
+    return BDN_OK;
+}
+
+extern "C" int bdn_adam_step_grouped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
+                                     const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                     float grad_scale, double beta1, double beta2, float eps, int decoupled_weight_decay, long long step,
+                                     size_t n, void* stream) {
+    return adam_grouped_launch("adam_step_grouped", params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, nullptr, beta1, beta2, eps, decoupled_weight_decay, step, n, stream);
+}
+
+extern "C" int bdn_adam_step_grouped_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* seg_end,
+                                        const int32_t* seg_group, int n_seg, int n_groups, const float* lr, const float* weight_decay,
+                                        float grad_scale, const float* dev_scale, double beta1, double beta2, float eps,
+                                        int decoupled_weight_decay, long long step, size_t n, void* stream) {
+    if (int rc = ex_check("adam_step_grouped_ex", dev_scale)) return rc;
+    return adam_grouped_launch("adam_step_grouped_ex", params, grads, exp_avg, exp_avg_sq, seg_end, seg_group, n_seg, n_groups, lr,
+                               weight_decay, grad_scale, dev_scale, beta1, beta2, eps, decoupled_weight_decay, step, n, stream);
+}
+
+// ============================================================ averaged weights: EMA / SWA (torch.optim.swa_utils.AveragedModel)
+// avg = lerp(avg, p, w) as torch evaluates it (ATen lerp: w < 0.5 ? avg + w*(p - avg) : p - (p - avg)*(1 - w)), or avg = p for the first
+// update, and the in-place exchange of two flat buffers.  Both are rules of grouped_kernel above -- its LDS-staged segment lookup, its pass
+// shape (one float4 per lane, OPT_VEC in flight, every load issued before the first store), no atomics -- in which `p` is the average and
+// `g` the parameters (RuleEma), or `p` and `s0` the two buffers and no `g` at all (RuleSwap).  Every group id 0..7 counts alike: only
+// frozen vectors and vectors behind the table's end are skipped, in every buffer.
+struct EmaParams { float w; int copy, hi; };
+
+__device__ __forceinline__ void ema_elem(float& a, float p, const EmaParams& q) {
+    if (q.copy) a = p;
+    else a = q.hi ? p - (p - a) * (1.f - q.w) : a + q.w * (p - a);
+}
+
+struct RuleEma {
+    using Params = EmaParams;
+    static constexpr int NS = 0;
+    static constexpr bool GRAD = true;
+    static __device__ __forceinline__ void scale(Params&, float) {}
+    static __device__ __forceinline__ bool reads_state(const Params&) { return false; }
+    static __device__ __forceinline__ void elem(float& a, float p, float&, float&, const Params& q) { ema_elem(a, p, q); }
+};
+struct RuleSwap {                                       // bits are moved, never computed
+    using Params = int;
+    static constexpr int NS = 1;
+    static constexpr bool GRAD = false;
+    static __device__ __forceinline__ void scale(Params&, float) {}
+    static __device__ __forceinline__ bool reads_state(const Params&) { return true; }
+    static __device__ __forceinline__ void elem(float& a, float, float& b, float&, const Params&) { const float t = a; a = b; b = t; }
+};
+
+static int segments_check(const char* what, const void* a, const void* b, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, size_t n) {
+    if (!a || !b) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (n_seg < 0 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d segments (0..%d; 0: no table, every vector counts)", what, n_seg, OPT_MAX_SEGS);
+    if (n_seg > 0 && (!seg_end || !seg_group)) BDN_FAIL(BDN_E_ARG, "%s: null pointer (segment table of %d segments)", what, n_seg);
+    if (((uintptr_t)a | (uintptr_t)b) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
+    if (n_seg > 0 && (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3)) BDN_FAIL(BDN_E_ARG, "%s: segment table must be 4-byte aligned", what);
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
+    return BDN_OK;
+}
+
+static int ema_params(const char* what, float weight, int copy, EmaParams& q) {
+    if (!(weight >= 0.f && weight <= 1.f)) BDN_FAIL(BDN_E_ARG, "%s: weight = %g must lie in [0, 1]", what, (double)weight);
+    if (copy != 0 && copy != 1) BDN_FAIL(BDN_E_ARG, "%s: copy must be 0 or 1, got %d", what, copy);
+    q = EmaParams{weight, copy, weight >= 0.5f ? 1 : 0};
+    return BDN_OK;
+}
+
+extern "C" int bdn_ema_update(float* avg, const float* params, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float weight,
+                              int copy, size_t n, void* stream) {
+    if (int rc = segments_check("ema_update", avg, params, seg_end, seg_group, n_seg, n)) return rc;
+    EmaParams q;
+    if (int rc = ema_params("ema_update", weight, copy, q)) return rc;
+    if (n == 0) return BDN_OK;
+    GroupArgs<EmaParams> a{};
+    for (int k = 0; k < OPT_MAX_GROUPS; k++) a.g[k] = q;
+    const SegTable t{seg_end, seg_group, n_seg, OPT_MAX_GROUPS};
+    hipLaunchKernelGGL(grouped_kernel<RuleEma>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, avg, params, (float*)nullptr,
+                       (float*)nullptr, t, a, (const float*)nullptr, n / 4);
+    BDN_CHECK_LAUNCH("ema_update");
+    return BDN_OK;
+}
+
+extern "C" int bdn_swap_segments(float* a, float* b, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, size_t n, void* stream) {
+    if (int rc = segments_check("swap_segments", a, b, seg_end, seg_group, n_seg, n)) return rc;
+    if (a == b) BDN_FAIL(BDN_E_ARG, "swap_segments: a and b are the same buffer");
+    if (n == 0) return BDN_OK;
+    const SegTable t{seg_end, seg_group, n_seg, OPT_MAX_GROUPS};
+    hipLaunchKernelGGL(grouped_kernel<RuleSwap>, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, a, (const float*)nullptr, b,
+                       (float*)nullptr, t, GroupArgs<int>{}, (const float*)nullptr, n / 4);
+    BDN_CHECK_LAUNCH("swap_segments");
+    return BDN_OK;
+}
+
+// The same rule over a device table of small tensors (the BatchNorm running statistics) in one launch: block row y owns tensor y and
+// grid-strides it, a float4 body where both pointers are 16-byte aligned and one element per lane for the rest.
+struct EmaDesc { float* avg; const float* src; int len, pad_; };
+constexpr int EMA_MULTI_MAX_BLOCKS = 64;
+
+__global__ void __launch_bounds__(256) ema_multi_kernel(const EmaDesc* __restrict__ desc, EmaParams q) {
+    const EmaDesc d = desc[blockIdx.y];
+    const int stride = gridDim.x * 256, tid = blockIdx.x * 256 + threadIdx.x;
+    const int n4 = ((((uintptr_t)d.avg | (uintptr_t)d.src) & 15) == 0 && d.len > 0) ? d.len / 4 : 0;
+    for (int i = tid; i < n4; i += stride) {
+        float4 a = reinterpret_cast<float4*>(d.avg)[i];
+        const float4 p = reinterpret_cast<const float4*>(d.src)[i];
+        ema_elem(a.x, p.x, q); ema_elem(a.y, p.y, q); ema_elem(a.z, p.z, q); ema_elem(a.w, p.w, q);
+        reinterpret_cast<float4*>(d.avg)[i] = a;
+    }
+    for (int i = n4 * 4 + tid; i < d.len; i += stride) {
+        float a = d.avg[i];
+        ema_elem(a, d.src[i], q);
+        d.avg[i] = a;
+    }
+}
+
+extern "C" int bdn_ema_update_multi(const void* desc_dev, int n_tensors, int max_len, float weight, int copy, void* stream) {
+    if (!desc_dev) BDN_FAIL(BDN_E_ARG, "ema_update_multi: null pointer");
+    if ((uintptr_t)desc_dev & 7) BDN_FAIL(BDN_E_ARG, "ema_update_multi: the descriptor table must be 8-byte aligned");
+    if (n_tensors < 0 || n_tensors > 65535 || max_len < 0) BDN_FAIL(BDN_E_SHAPE, "ema_update_multi: n_tensors=%d (0..65535) max_len=%d", n_tensors, max_len);
+    EmaParams q;
+    if (int rc = ema_params("ema_update_multi", weight, copy, q)) return rc;
+    if (n_tensors == 0 || max_len == 0) return BDN_OK;
+    const int want = (max_len + 1023) / 1024;
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(want < EMA_MULTI_MAX_BLOCKS ? want : EMA_MULTI_MAX_BLOCKS, n_tensors), dim3(256), 0,
+                       (hipStream_t)stream, static_cast<const EmaDesc*>(desc_dev), q);
+    BDN_CHECK_LAUNCH("ema_update_multi");
+    return BDN_OK;
+}
+
+// ============================================================ gradient accumulation and the global gradient norm (clip_grad_norm_)
+// Two memory-bound passes on the path between backward and the update, in the update kernels' shape (float4, OPT_VEC loads in flight).
+//
+// bdn_grad_accumulate: dst = src (add = 0) or dst = dst + src (add = 1), one IEEE float32 add per element; a micro-step's gradients go
+// into the accumulator, the last micro-step's come out of it, and no zero-fill is ever needed.
+//
+// bdn_grad_norm: out[0] = grad_scale * sqrt(sum g^2) over the vectors that count, out[1] = torch's clip coefficient of it.  Every float32
+// is converted to double before it is squared and everything is accumulated in double (a square neither overflows nor underflows; the
+// sum of 2^32 vectors errs by ~n 2^-53).  Stage 1: block b owns the NORM_CHUNK consecutive vectors [b NORM_CHUNK, (b + 1) NORM_CHUNK) --
+// the block count is a function of n alone -- each lane sums its vectors in index order, a wave64 butterfly (__shfl_xor, the same tree in
+// every wave) sums the lanes, thread 0 adds the four wave sums in wave order and writes ONE double.  Stage 2: one thread adds the partials
+// in index order (staged through LDS 1024 at a time) and forms norm and coefficient.  No atomics, no memset, the same bits on any device.
+// With a segment table (the update kernels') a vector of a frozen segment, or behind the table's end, is not read.
+__device__ __forceinline__ float4 add4(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// A pass whose OPT_VEC vectors are all in range issues its loads without a bounds test (named registers: hipcc moved a conditionally
+// loaded float4[OPT_VEC] of the copy form into LDS and waited for every load in turn); the last, partial pass goes vector by vector.
+template <bool ADD>
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n4, size_t n) {
+    static_assert(OPT_VEC == 4, "four loads in flight, written out");
+    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(dst);
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t base = (size_t)blockIdx.x * 256 + threadIdx.x; base < n4; base += stride * OPT_VEC) {
+        if (base + 3 * stride < n4) {
+            float4 a0 = s4[base], a1 = s4[base + stride], a2 = s4[base + 2 * stride], a3 = s4[base + 3 * stride];
+            if (ADD) {
+                const float4 c0 = d4[base], c1 = d4[base + stride], c2 = d4[base + 2 * stride], c3 = d4[base + 3 * stride];
+                a0 = add4(c0, a0); a1 = add4(c1, a1); a2 = add4(c2, a2); a3 = add4(c3, a3);
+            }
+            d4[base] = a0; d4[base + stride] = a1; d4[base + 2 * stride] = a2; d4[base + 3 * stride] = a3;
+        } else {
+            for (size_t i = base; i < n4; i += stride) {
+                float4 v = s4[i];
+                if (ADD) v = add4(d4[i], v);
+                d4[i] = v;
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - n4 * 4) {       // the n % 4 trailing elements
+        const size_t k = n4 * 4 + threadIdx.x;
+        dst[k] = ADD ? dst[k] + src[k] : src[k];
+    }
+}
+
+extern "C" int bdn_grad_accumulate(float* dst, const float* src, size_t n, int add, void* stream) {
+    if (!dst || !src) BDN_FAIL(BDN_E_ARG, "grad_accumulate: null pointer");
+    if (((uintptr_t)dst | (uintptr_t)src) & 15) BDN_FAIL(BDN_E_ARG, "grad_accumulate: buffers must be 16-byte aligned");
+    if (add != 0 && add != 1) BDN_FAIL(BDN_E_ARG, "grad_accumulate: add must be 0 or 1, got %d", add);
+    if (n == 0) return BDN_OK;
+    const size_t n4 = n / 4;
+    if (add) hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, dst, src, n4, n);
+    else hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, dst, src, n4, n);
+    BDN_CHECK_LAUNCH("grad_accumulate");
+    return BDN_OK;
+}
+
+constexpr int NORM_ROUNDS = 4;                                   // passes of OPT_VEC float4s per thread
+constexpr size_t NORM_CHUNK = (size_t)256 * OPT_VEC * NORM_ROUNDS;   // vectors per block and per partial: 4096 (64 KiB of gradients)
+
+static inline size_t norm_blocks(size_t n4) { return (n4 + NORM_CHUNK - 1) / NORM_CHUNK; }
+
+__device__ __forceinline__ double sq_acc(double acc, const float4& v) {
+    const double x = (double)v.x, y = (double)v.y, z = (double)v.z, w = (double)v.w;
+    acc = fma(x, x, acc); acc = fma(y, y, acc); acc = fma(z, z, acc); acc = fma(w, w, acc);
+    return acc;
+}
+
+__global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float* __restrict__ g, const uint32_t* __restrict__ seg_end,
+                                                                const int32_t* __restrict__ seg_group, int n_seg,
+                                                                double* __restrict__ part, size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS];
+    __shared__ double s_wave[4];
+    int cap = 1;
+    if (n_seg > 0) {
+        while (cap < n_seg) cap <<= 1;
+        for (int k = threadIdx.x; k < cap; k += 256) {
+            s_end[k] = k < n_seg ? seg_end[k] : 0xffffffffu;
+            s_grp[k] = k < n_seg ? seg_group[k] : OPT_FROZEN;
+        }
+        __syncthreads();
+    }
+    const size_t c0 = (size_t)blockIdx.x * NORM_CHUNK;
+    // A block's 4096 consecutive vectors almost always lie in one segment: one lookup of its first and of its last vector then serves the
+    // block (a frozen block reads nothing at all); a block that spans a boundary looks every vector up.  The sums are the same either way.
+    bool per_lane = false, whole = true;
+    if (n_seg > 0) {
+        const size_t last = (c0 + NORM_CHUNK < n4 ? c0 + NORM_CHUNK : n4) - 1;
+        int s_lo = 0, s_hi = 0;
+        for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)c0, s_lo); seg_step(s_end, h, (uint32_t)last, s_hi); }
+        per_lane = s_lo != s_hi;
+        whole = s_end[s_lo] > last && s_grp[s_lo] != OPT_FROZEN;
+    }
+    double acc = 0.0;
+    for (int r = 0; r < NORM_ROUNDS; r++) {
+        bool take[OPT_VEC];
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+            take[u] = i < n4 && (per_lane || whole);
+            if (take[u] && per_lane) {                       // first segment whose end lies behind i
+                int s = 0;
+                for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+                take[u] = s_end[s] > i && s_grp[s] != OPT_FROZEN;
+            }
+        }
+        float4 G[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+            if (take[u]) G[u] = reinterpret_cast<const float4*>(g)[i];
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) acc = sq_acc(acc, G[u]);           // a vector not taken adds +0.0: the sum is unchanged
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+__global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __restrict__ part, size_t nblk, float grad_scale, float max_norm,
+                                                               float* __restrict__ out) {
+    __shared__ double s_part[1024];
+    double sum = 0.0;
+    for (size_t b0 = 0; b0 < nblk; b0 += 1024) {
+        const size_t m = nblk - b0 < 1024 ? nblk - b0 : 1024;
+        for (size_t k = threadIdx.x; k < m; k += 256) s_part[k] = part[b0 + k];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (size_t k = 0; k < m; k++) sum += s_part[k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm32 = (float)((double)grad_scale * sqrt(sum));
+        // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1), the quotient as torch evaluates a Python float over a
+        // tensor (Tensor.__rtruediv__): reciprocal, then product
+        float coef = (1.0f / (norm32 + 1e-6f)) * max_norm;
+        if (coef > 1.0f) coef = 1.0f;                        // a comparison, not fminf: a NaN norm keeps its NaN coefficient
+        out[0] = norm32;
+        out[1] = coef;
+    }
+}
+
+extern "C" size_t bdn_grad_norm_workspace_bytes(size_t n) {
+    const size_t nb = norm_blocks(n / 4);
+    return ((nb ? nb : 1) * sizeof(double) + 15) / 16 * 16;
+}
+
+extern "C" int bdn_grad_norm(const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float grad_scale,
+                             float max_norm, void* workspace, float* out, size_t n, void* stream) {
+    if (!grads || !workspace || !out) BDN_FAIL(BDN_E_ARG, "grad_norm: null pointer");
+    if (n_seg < 0 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "grad_norm: %d segments (0..%d; 0: no table, every element counts)", n_seg, OPT_MAX_SEGS);
+    if (n_seg > 0 && (!seg_end || !seg_group)) BDN_FAIL(BDN_E_ARG, "grad_norm: null pointer (segment table of %d segments)", n_seg);
+    if ((uintptr_t)grads & 15) BDN_FAIL(BDN_E_ARG, "grad_norm: buffers must be 16-byte aligned");
+    if ((uintptr_t)workspace & 7) BDN_FAIL(BDN_E_ARG, "grad_norm: workspace must be 8-byte aligned");
+    if ((uintptr_t)out & 3) BDN_FAIL(BDN_E_ARG, "grad_norm: out must be 4-byte aligned");
+    if (n_seg > 0 && (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3)) BDN_FAIL(BDN_E_ARG, "grad_norm: segment table must be 4-byte aligned");
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "grad_norm: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", n);
+    if (!(max_norm >= 0.f)) BDN_FAIL(BDN_E_ARG, "grad_norm: max_norm = %g must be >= 0 (+inf: measure only)", (double)max_norm);
+    const size_t n4 = n / 4, nblk = norm_blocks(n4);
+    if (nblk) {
+        hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, grads, seg_end, seg_group, n_seg,
+                           (double*)workspace, n4);
+        BDN_CHECK_LAUNCH("grad_norm");
+    }
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, nblk, grad_scale, max_norm, out);
+    BDN_CHECK_LAUNCH("grad_norm_finish");
+    return BDN_OK;
+}

@@ -5,8 +5,6 @@
 #include <climits>
 #include <type_traits>
 
-static inline unsigned grid_for(size_t n, int block = 256) { return (unsigned)((n + block - 1) / block); }
-
 // ============================================================ band upload
 // One row band of ALL band planes of a host scene in ONE copy: [C] planes of H x W float32, rows [r0, r1) of each -- a 2-D copy of C "rows" of
 // (r1 - r0) * W * 4 bytes at pitch H * W * 4 (what train.py:190-193 does per batch with .to(device), here per band of the resident scene).
