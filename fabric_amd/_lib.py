@@ -43,6 +43,8 @@ SIGNATURES = {
     'bdn_conv3x3_wgrad': (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_conv3x3_wgrad_ex': (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'bdn_conv3x3_wgrad_variant': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    'bdn_conv3x3_wgrad_kernels': (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    'bdn_conv3x3_wgrad_bnbwd_kernels': (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
     'bdn_wgrad_workspace_bytes_ex': (_sz, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     'bdn_conv3x3_wgrad_bnbwd_supported': (_i, [_i, _i, _i, _i, _i, _i, _i]),
     'bdn_conv3x3_wgrad_bnbwd': (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),

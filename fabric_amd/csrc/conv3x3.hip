@@ -1000,13 +1000,8 @@ static int dispatch_conv_bb(const ConvArgs& a, const ConvPlan& p, hipStream_t st
 // bf16x3 with the split product fused into one reduction (operands of at least 64 channels): two patches per chunk in LDS, so no 16x16 tiles
 static ConvPlan conv_plan_x3f(int N, int H, int W, int Cout, int imgs_per_group) {
     ConvPlan p;
-    TileGeom& g = p.g;
-    if (W <= 8 && H <= 8 && imgs_per_group % 2 == 0) { g.TI = 2; g.TH = 8; g.TW = 8; }
-    else { g.TI = 1; g.TH = 8; g.TW = 16; }
-    g.tiles_y = (H + g.TH - 1) / g.TH;
-    g.tiles_x = (W + g.TW - 1) / g.TW;
-    g.n_mtiles = ((N + g.TI - 1) / g.TI) * g.tiles_y * g.tiles_x;
-    p.BN = (g.TI == 1 && Cout % 128 == 0 && (long)g.n_mtiles * (Cout / 128) >= 512) ? 128 : 64;
+    p.g = pick_tile(N, H, W, imgs_per_group);          // the weight gradient's tiles (common.hpp)
+    p.BN = (p.g.TI == 1 && Cout % 128 == 0 && (long)p.g.n_mtiles * (Cout / 128) >= 512) ? 128 : 64;
     return p;
 }
 

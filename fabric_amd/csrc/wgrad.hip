@@ -14,6 +14,7 @@
 // The f32 variant feeds v_mfma_f32_32x32x2_f32, whose one-value-per-lane operands are plain
 // conflict-free ds_read_b32.
 #include "common.hpp"
+#include <string.h>
 
 struct WgradArgs {
     const void* dz; int Cout;
@@ -681,8 +682,24 @@ __global__ __launch_bounds__(512, 1) void wgrad7x_kernel(WgradArgs a) {
     }
 }
 
+// Query mode (bdn_conv3x3_wgrad_kernels / bdn_conv3x3_wgrad_bnbwd_kernels, as g_conv_query in conv3x3.hip): the entry points run as
+// usual but every launch_* below appends its kernel's name, '+'-joined in launch order, instead of launching -- one source of truth for
+// profilers and for the launch-shape table of the tests.  wg_named: false outside query mode, so `if (wg_named(...)) return BDN_OK;`
+static thread_local bool g_wg_query = false;
+static thread_local char g_wg_names[256];
+static bool wg_named(const char* fmt, ...) {
+    if (!g_wg_query) return false;
+    size_t n = strlen(g_wg_names);
+    if (n && n + 1 < sizeof(g_wg_names)) g_wg_names[n++] = '+';
+    va_list ap; va_start(ap, fmt);
+    vsnprintf(g_wg_names + n, sizeof(g_wg_names) - n, fmt, ap);
+    va_end(ap);
+    return true;
+}
+
 template <int TERMS>
 static int launch_wgrad7x(const WgradArgs& a, hipStream_t st) {
+    if (wg_named("wgrad7x_kernel<%d>", TERMS)) return BDN_OK;
     constexpr int SMEM = 2 * (TERMS == 3 ? 2 * Wg6::BUF : Wg6::BUF + Wg6::PATCH_BYTES);
     auto kern = wgrad7x_kernel<TERMS>;
     BDN_SET_SMEM_ONCE(kern, SMEM, "wgrad7x");
@@ -693,6 +710,7 @@ static int launch_wgrad7x(const WgradArgs& a, hipStream_t st) {
 
 template <bool USE_BN>
 static int launch_wgrad7(const WgradArgs& a, hipStream_t st) {
+    if (wg_named("wgrad7_kernel<%s>", USE_BN ? "true" : "false")) return BDN_OK;
     auto kern = wgrad7_kernel<USE_BN>;
     BDN_SET_SMEM_ONCE(kern, 3 * Wg6::BUF, "wgrad7");
     hipLaunchKernelGGL(kern, dim3(a.S * a.n_tiles), dim3(512), 3 * Wg6::BUF, st, a);
@@ -1109,22 +1127,21 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, float* __
     }
 }
 
-static void launch_wgrad_reduce(const float* partial, float* dw, int S, int Cout, int Cin, int Cin_real, hipStream_t st,
-                                int ostride = 9, int ooff = 0) {
+static int launch_wgrad_reduce(const float* partial, float* dw, int S, int Cout, int Cin, int Cin_real, hipStream_t st,
+                               int ostride = 9, int ooff = 0, const char* what = "wgrad_reduce") {
     const size_t plane = (size_t)Cout * Cin;
     // split lanes give the small filters some parallelism -- up to ~256 blocks, never more lanes than splits.  More, thinner
     // blocks (the first version went to 2048) read 64-byte pieces of every partial tile: the same speed alone, but inside
     // the step, where this kernel shares HBM with the dz chain, the fatter blocks make the step 0.9 % shorter.
     int SL = 1;
     while (SL < 16 && SL * 2 <= S && plane / (256 / (SL * 2)) < 256) SL *= 2;
+    if (wg_named("wgrad_reduce_kernel<%d>", SL)) return BDN_OK;
     const unsigned grid = (unsigned)((plane + 256 / SL - 1) / (256 / SL));
-    switch (SL) {
-        case 1: hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(grid), dim3(256), 0, st, partial, dw, S, Cout, Cin, Cin_real, ostride, ooff); break;
-        case 2: hipLaunchKernelGGL(wgrad_reduce_kernel<2>, dim3(grid), dim3(256), 0, st, partial, dw, S, Cout, Cin, Cin_real, ostride, ooff); break;
-        case 4: hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(grid), dim3(256), 0, st, partial, dw, S, Cout, Cin, Cin_real, ostride, ooff); break;
-        case 8: hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3(grid), dim3(256), 0, st, partial, dw, S, Cout, Cin, Cin_real, ostride, ooff); break;
-        default: hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3(grid), dim3(256), 0, st, partial, dw, S, Cout, Cin, Cin_real, ostride, ooff); break;
-    }
+    auto kern = SL == 1 ? wgrad_reduce_kernel<1> : SL == 2 ? wgrad_reduce_kernel<2> : SL == 4 ? wgrad_reduce_kernel<4>
+              : SL == 8 ? wgrad_reduce_kernel<8> : wgrad_reduce_kernel<16>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, partial, dw, S, Cout, Cin, Cin_real, ostride, ooff);
+    BDN_CHECK_LAUNCH(what);
+    return BDN_OK;
 }
 
 // ---- plan: tile geometry, split count, kernel variant.  A pure function of the shape and of the caller's `flags` word
@@ -1177,7 +1194,7 @@ extern "C" size_t bdn_wgrad_workspace_bytes_ex(int dtype, int N, int H, int W, i
                                                             flags | WG_X3_SKIP | (dtype == BDN_BF16X2 ? WG_X3_TWO : 0))
                                + (size_t)4 * Cout * (C0 + C1) * 9 * sizeof(float);
         const size_t fused = bdn_wgrad_workspace_bytes_ex(BDN_BF16, N, H, W, Cout, C0 + C1, 0, imgs_per_group, BDN_IN_PLAIN, flags);   // wgrad7x: the logical plan
-        return doubled > fused ? doubled : fused;
+        return doubled > fused ? doubled : fused;        // (kept quirk: the larger of both routes, not the one wgrad_x3_fused picks)
     }
     const WgPlan p = wgrad_plan(dtype, N, H, W, Cout, C0, C1, imgs_per_group, in_mode, flags);
     return (size_t)p.S * (p.ksplit ? 2 : 1) * 9 * Cout * (C0 + C1) * sizeof(float);
@@ -1201,11 +1218,46 @@ extern "C" size_t bdn_wgrad_workspace_bytes(int N, int H, int W, int Cout, int C
 template <typename T, int TH, int TW, int TI, bool KSPLIT>
 static int launch_wgrad(const WgradArgs& a, hipStream_t st) {
     using CF = WgCfg<T, TH, TW, TI>;
+    if (wg_named("wgrad_kernel<%s,%d,%d,%d,%s>", sizeof(T) == 2 ? "bf16" : "f32", TH, TW, TI, KSPLIT ? "true" : "false")) return BDN_OK;
     auto kern = wgrad_kernel<T, TH, TW, TI, KSPLIT>;
     BDN_SET_SMEM_ONCE(kern, CF::SMEM, "wgrad");
     hipLaunchKernelGGL(kern, dim3(a.S * a.n_tiles), dim3(256), CF::SMEM, st, a);
     BDN_CHECK_LAUNCH("wgrad");
     return BDN_OK;
+}
+
+// the kernel arguments of a plan on plain 2-D operands; a caller sets what differs (in_bn; Dz / dshift in 3x3x3 mode)
+static WgradArgs wgrad_args(const WgPlan& p, const void* dz, int Cout, const void* in0, int C0, const void* in1, int C1,
+                            int imgs_per_group, float* partial, int N, int H, int W) {
+    WgradArgs a;
+    a.dz = dz; a.Cout = Cout; a.in0 = in0; a.in1 = in1; a.C0 = C0; a.C1 = C1; a.in_bn = nullptr; a.imgs_per_group = imgs_per_group;
+    a.partial = partial; a.N = N; a.H = H; a.W = W;
+    a.tiles_y = p.g.tiles_y; a.tiles_x = p.g.tiles_x; a.n_mtiles = p.g.n_mtiles;
+    a.S = p.S; a.per_split = p.per_split; a.n_cot = p.n_cot; a.n_cit = p.n_cit; a.x3h = p.x3h; a.n_tiles = p.n_tiles;
+    a.Dz = 0; a.dshift = 0;
+    return a;
+}
+
+// the one switch over GEMM instantiations.  dtype BDN_BF16X3 / BDN_BF16X2: the fused split product (wgrad_x3_fused said yes)
+static int launch_wgrad_gemm(int dtype, const WgPlan& p, const WgradArgs& a, hipStream_t st) {
+    const bool t1 = p.g.TI == 1;
+    if (dtype == BDN_BF16X3) return launch_wgrad7x<3>(a, st);
+    if (dtype == BDN_BF16X2) return launch_wgrad7x<2>(a, st);
+    if (dtype == BDN_BF16) {
+        if (p.variant == BDN_WG_ROLE) return a.in_bn ? launch_wgrad7<true>(a, st) : launch_wgrad7<false>(a, st);
+        if (p.ksplit) return t1 ? launch_wgrad<bf16s, 8, 16, 1, true>(a, st) : launch_wgrad<bf16s, 8, 8, 2, true>(a, st);
+        return t1 ? launch_wgrad<bf16s, 8, 16, 1, false>(a, st) : launch_wgrad<bf16s, 8, 8, 2, false>(a, st);
+    }
+    if (p.ksplit) return t1 ? launch_wgrad<float, 8, 16, 1, true>(a, st) : launch_wgrad<float, 8, 8, 2, true>(a, st);
+    return t1 ? launch_wgrad<float, 8, 16, 1, false>(a, st) : launch_wgrad<float, 8, 8, 2, false>(a, st);
+}
+
+// Does this split-operand (bf16x3 / bf16x2) call run the fused wgrad7x kernel?  Full 64-channel tiles on 8 x 16 spatial tiles whose DOUBLED
+// tensors stay below 2^31 elements; pf = the plan of the LOGICAL [Cout] x [C0] problem.  Otherwise: the bf16 GEMM on the doubled operands.
+static bool wgrad_x3_fused(int N, int H, int W, int Cout, int C0, int imgs_per_group, int flags, WgPlan& pf) {
+    if (Cout % 64 || C0 % 64 || (size_t)N * H * W * 2 * (size_t)(Cout > C0 ? Cout : C0) >= ((size_t)1 << 31)) return false;
+    pf = wgrad_plan(BDN_BF16, N, H, W, Cout, C0, 0, imgs_per_group, BDN_IN_PLAIN, flags);
+    return pf.variant == BDN_WG_ROLE;
 }
 
 // flags bits 0-1 = phases: bit 0 = the split-K GEMM (partial tiles into `partial`), bit 1 = the fixed-order reduction of the
@@ -1215,9 +1267,10 @@ extern "C" int bdn_conv3x3_wgrad_ex(int dtype, const void* dz, int Cout,
                                     const void* in0, int C0, const void* in1, int C1,
                                     int in_mode, const float* in_bn, int imgs_per_group,
                                     float* partial, float* dw_oihw, int Cin_real,
-                                    int N, int H, int W, int phases, void* stream) {
+                                    int N, int H, int W, int flags, void* stream) {
     if (!dz || !in0 || !partial || !dw_oihw) BDN_FAIL(BDN_E_ARG, "wgrad: null pointer");
-    if (!(phases & 3)) BDN_FAIL(BDN_E_ARG, "wgrad: phases must select the GEMM (1), the reduction (2) or both (3)");
+    if (!(flags & 3)) BDN_FAIL(BDN_E_ARG, "wgrad: phases must select the GEMM (1), the reduction (2) or both (3)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype == BDN_BF16X3 || dtype == BDN_BF16X2) {
         const int xfl = WG_X3_SKIP | (dtype == BDN_BF16X2 ? WG_X3_TWO : 0);          // BDN_BF16X2: dw = T[hi,hi] + T[hi,lo] (dz rounded to bf16)
         // dz = split operand [N,H,W,2 Cout] (hi | lo), in0 = split operand [N,H,W,2 C0] from bdn_split_pack (which did any cat /
@@ -1227,36 +1280,20 @@ extern "C" int bdn_conv3x3_wgrad_ex(int dtype, const void* dz, int Cout,
             BDN_FAIL(BDN_E_SHAPE, "wgrad(bf16x3): Cout=%d must be a multiple of 32, C0=%d of 8, Cin_real=%d <= C0", Cout, C0, Cin_real);
         if (N <= 0 || H <= 0 || W <= 0 || imgs_per_group <= 0 || N % imgs_per_group)
             BDN_FAIL(BDN_E_SHAPE, "wgrad(bf16x3): bad N=%d H=%d W=%d imgs_per_group=%d", N, H, W, imgs_per_group);
-        if (Cout % 64 == 0 && C0 % 64 == 0 && (size_t)N * H * W * 2 * (size_t)(Cout > C0 ? Cout : C0) < ((size_t)1 << 31)) {
-            // full 64-channel tiles on 8 x 16 spatial tiles: the terms of the split product in one accumulator (wgrad7x_kernel), the plan of
-            // the LOGICAL [Cout] x [C0] problem, the plain split-K reduction straight into dw
-            const WgPlan pf = wgrad_plan(BDN_BF16, N, H, W, Cout, C0, 0, imgs_per_group, BDN_IN_PLAIN, phases);
-            if (pf.variant == BDN_WG_ROLE) {
-                WgradArgs a;
-                a.dz = dz; a.Cout = Cout; a.in0 = in0; a.in1 = nullptr; a.C0 = C0; a.C1 = 0; a.in_bn = nullptr; a.imgs_per_group = imgs_per_group;
-                a.partial = partial; a.N = N; a.H = H; a.W = W;
-                a.tiles_y = pf.g.tiles_y; a.tiles_x = pf.g.tiles_x; a.n_mtiles = pf.g.n_mtiles;
-                a.S = pf.S; a.per_split = pf.per_split; a.n_cot = pf.n_cot; a.n_cit = pf.n_cit; a.x3h = 0; a.n_tiles = pf.n_tiles;
-                a.Dz = 0; a.dshift = 0;
-                hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-                if (phases & 1) {
-                    const int rc = dtype == BDN_BF16X3 ? launch_wgrad7x<3>(a, st) : launch_wgrad7x<2>(a, st);
-                    if (rc) return rc;
-                }
-                if (phases & 2) {
-                    launch_wgrad_reduce(partial, dw_oihw, pf.S, Cout, C0, Cin_real, st);
-                    BDN_CHECK_LAUNCH("wgrad_reduce");
-                }
-                return BDN_OK;
-            }
+        WgPlan pf;
+        if (wgrad_x3_fused(N, H, W, Cout, C0, imgs_per_group, flags, pf)) {
+            // the terms of the split product in one accumulator (wgrad7x_kernel), the plain split-K reduction straight into dw
+            const WgradArgs a = wgrad_args(pf, dz, Cout, in0, C0, nullptr, 0, imgs_per_group, partial, N, H, W);
+            if (flags & 1) { const int rc = launch_wgrad_gemm(dtype, pf, a, st); if (rc) return rc; }
+            return (flags & 2) ? launch_wgrad_reduce(partial, dw_oihw, pf.S, Cout, C0, Cin_real, st) : BDN_OK;
         }
-        const size_t gemm_bytes = bdn_wgrad_workspace_bytes_ex(BDN_BF16, N, H, W, 2 * Cout, 2 * C0, 0, imgs_per_group, BDN_IN_PLAIN, phases | xfl);
+        const size_t gemm_bytes = bdn_wgrad_workspace_bytes_ex(BDN_BF16, N, H, W, 2 * Cout, 2 * C0, 0, imgs_per_group, BDN_IN_PLAIN, flags | xfl);
         float* tile = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(partial) + gemm_bytes);
         const int rc = bdn_conv3x3_wgrad_ex(BDN_BF16, dz, 2 * Cout, in0, 2 * C0, nullptr, 0, BDN_IN_PLAIN, nullptr, imgs_per_group,
-                                            partial, tile, 2 * C0, N, H, W, phases | xfl, stream);
+                                            partial, tile, 2 * C0, N, H, W, flags | xfl, stream);
         if (rc) return rc;
-        if (phases & 2) return bdn_wgrad_x3_combine(tile, dw_oihw, Cout, C0, Cin_real, 9, dtype == BDN_BF16X2 ? 2 : 3, reinterpret_cast<hipStream_t>(stream));
-        return BDN_OK;
+        if (!(flags & 2) || wg_named("wgrad_x3_combine_kernel")) return BDN_OK;
+        return bdn_wgrad_x3_combine(tile, dw_oihw, Cout, C0, Cin_real, 9, dtype == BDN_BF16X2 ? 2 : 3, st);
     }
     if (N <= 0 || H <= 0 || W <= 0 || imgs_per_group <= 0 || N % imgs_per_group)
         BDN_FAIL(BDN_E_SHAPE, "wgrad: bad N=%d H=%d W=%d imgs_per_group=%d", N, H, W, imgs_per_group);
@@ -1268,31 +1305,11 @@ extern "C" int bdn_conv3x3_wgrad_ex(int dtype, const void* dz, int Cout,
     const int Cin = C0 + C1;
     if (Cin_real <= 0 || Cin_real > Cin) BDN_FAIL(BDN_E_SHAPE, "wgrad: Cin_real=%d out of range", Cin_real);
     if (dtype != BDN_BF16 && dtype != BDN_F32) BDN_FAIL(BDN_E_ARG, "wgrad: bad dtype %d", dtype);
-    const WgPlan p = wgrad_plan(dtype, N, H, W, Cout, C0, C1, imgs_per_group, in_mode, phases);
-    WgradArgs a;
-    a.dz = dz; a.Cout = Cout; a.in0 = in0; a.in1 = in1; a.C0 = C0; a.C1 = C1;
-    a.in_bn = in_mode == BDN_IN_BNRELU ? in_bn : nullptr; a.imgs_per_group = imgs_per_group;
-    a.partial = partial; a.N = N; a.H = H; a.W = W;
-    a.tiles_y = p.g.tiles_y; a.tiles_x = p.g.tiles_x; a.n_mtiles = p.g.n_mtiles;
-    a.S = p.S; a.per_split = p.per_split; a.n_cot = p.n_cot; a.n_cit = p.n_cit; a.x3h = p.x3h; a.n_tiles = p.n_tiles;
-    a.Dz = 0; a.dshift = 0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rc = BDN_OK;
-    if (!(phases & 1)) {
-    } else if (dtype == BDN_BF16) {
-        if (p.variant == BDN_WG_ROLE) rc = a.in_bn ? launch_wgrad7<true>(a, st) : launch_wgrad7<false>(a, st);
-        else if (p.ksplit) rc = p.g.TI == 1 ? launch_wgrad<bf16s, 8, 16, 1, true>(a, st) : launch_wgrad<bf16s, 8, 8, 2, true>(a, st);
-        else rc = p.g.TI == 1 ? launch_wgrad<bf16s, 8, 16, 1, false>(a, st) : launch_wgrad<bf16s, 8, 8, 2, false>(a, st);
-    } else {
-        if (p.ksplit) rc = p.g.TI == 1 ? launch_wgrad<float, 8, 16, 1, true>(a, st) : launch_wgrad<float, 8, 8, 2, true>(a, st);
-        else rc = p.g.TI == 1 ? launch_wgrad<float, 8, 16, 1, false>(a, st) : launch_wgrad<float, 8, 8, 2, false>(a, st);
-    }
-    if (rc) return rc;
-    if (phases & 2) {
-        launch_wgrad_reduce(partial, dw_oihw, p.S * (p.ksplit ? 2 : 1), Cout, Cin, Cin_real, st);
-        BDN_CHECK_LAUNCH("wgrad_reduce");
-    }
-    return BDN_OK;
+    const WgPlan p = wgrad_plan(dtype, N, H, W, Cout, C0, C1, imgs_per_group, in_mode, flags);
+    WgradArgs a = wgrad_args(p, dz, Cout, in0, C0, in1, C1, imgs_per_group, partial, N, H, W);
+    a.in_bn = in_mode == BDN_IN_BNRELU ? in_bn : nullptr;
+    if (flags & 1) { const int rc = launch_wgrad_gemm(dtype, p, a, st); if (rc) return rc; }
+    return (flags & 2) ? launch_wgrad_reduce(partial, dw_oihw, p.S * (p.ksplit ? 2 : 1), Cout, Cin, Cin_real, st) : BDN_OK;
 }
 
 extern "C" int bdn_conv3x3_wgrad(int dtype, const void* dz, int Cout,
@@ -1313,6 +1330,32 @@ extern "C" int bdn_conv3x3_wgrad_bnbwd_supported(int dtype, int N, int H, int W,
     return (size_t)N * H * W * 64 < ((size_t)1 << 31) ? 1 : 0;
 }
 
+// what the plan sets of WgFirstArgs / WgFirstX3Args
+template <typename A>
+static void wgrad_first_fill(A& a, const WgPlan& p, float* partial, int N, int H, int W, int imgs_per_group) {
+    a.partial = partial; a.N = N; a.H = H; a.W = W; a.imgs_per_group = imgs_per_group;
+    a.tiles_y = p.g.tiles_y; a.tiles_x = p.g.tiles_x; a.n_mtiles = p.g.n_mtiles; a.S = p.S; a.per_split = p.per_split;
+    a.invM = 1.f / (float)((size_t)imgs_per_group * H * W);
+}
+
+template <bool P3>
+static int launch_wgrad_first(const WgFirstArgs& a, hipStream_t st, const char* what = "wgrad_first") {
+    if (wg_named("wgrad_first_kernel")) return BDN_OK;
+    hipLaunchKernelGGL(wgrad_first_kernel<P3>, dim3(a.S), dim3(256), WgF::SMEM, st, a);
+    BDN_CHECK_LAUNCH(what);
+    return BDN_OK;
+}
+
+template <int TERMS>
+static int launch_wgrad_first_x3(const WgFirstX3Args& x, hipStream_t st) {
+    if (wg_named("wgrad_first_x3_kernel<%d>", TERMS)) return BDN_OK;
+    auto kern = wgrad_first_x3_kernel<TERMS>;
+    BDN_SET_SMEM_ONCE(kern, WgFX::SMEM, "wgrad_first_x3");
+    hipLaunchKernelGGL(kern, dim3(x.S), dim3(256), WgFX::SMEM, st, x);
+    BDN_CHECK_LAUNCH("wgrad_first_x3");
+    return BDN_OK;
+}
+
 extern "C" int bdn_conv3x3_wgrad_bnbwd(int dtype, const void* dA, int ldA, const void* z, const float* bn, const float* sums,
                                        int imgs_per_group, int Cout, const void* in0, int C0,
                                        float* partial, float* dw_oihw, int Cin_real, int N, int H, int W, void* stream) {
@@ -1323,45 +1366,49 @@ extern "C" int bdn_conv3x3_wgrad_bnbwd(int dtype, const void* dA, int ldA, const
     // runs at the very end of backward on the MAIN stream (two blocks per CU, nothing of the chain left): its own grid of 512
     const WgPlan p = wgrad_plan(BDN_BF16, N, H, W, Cout, C0, 0, imgs_per_group, BDN_IN_PLAIN, BDN_WG_FLAGS(0, 0, 256));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int rc;
     if (dtype != BDN_BF16) {
         // float32 dA [.., ldA] and z [.., 64]; in0 = the first convolution's split operand [N,H,W,32] bf16 = hi(16) | lo(16)
         WgFirstX3Args x;
         x.dA = (const float*)dA; x.ldA = ldA; x.z = (const float*)z; x.bn = bn; x.sums = sums; x.xs = (const bf16s*)in0;
-        x.partial = partial; x.N = N; x.H = H; x.W = W; x.imgs_per_group = imgs_per_group;
-        x.tiles_y = p.g.tiles_y; x.tiles_x = p.g.tiles_x; x.n_mtiles = p.g.n_mtiles; x.S = p.S; x.per_split = p.per_split;
-        x.invM = 1.f / (float)((size_t)imgs_per_group * H * W);
-        if (dtype == BDN_BF16X3) {
-            auto kern = wgrad_first_x3_kernel<3>;
-            BDN_SET_SMEM_ONCE(kern, WgFX::SMEM, "wgrad_first_x3");
-            hipLaunchKernelGGL(kern, dim3(p.S), dim3(256), WgFX::SMEM, st, x);
-        } else {
-            auto kern = wgrad_first_x3_kernel<2>;
-            BDN_SET_SMEM_ONCE(kern, WgFX::SMEM, "wgrad_first_x3");
-            hipLaunchKernelGGL(kern, dim3(p.S), dim3(256), WgFX::SMEM, st, x);
-        }
-        BDN_CHECK_LAUNCH("wgrad_first_x3");
-        launch_wgrad_reduce(partial, dw_oihw, p.S, Cout, C0, Cin_real, st);
-        BDN_CHECK_LAUNCH("wgrad_reduce");
-        return BDN_OK;
+        wgrad_first_fill(x, p, partial, N, H, W, imgs_per_group);
+        rc = dtype == BDN_BF16X3 ? launch_wgrad_first_x3<3>(x, st) : launch_wgrad_first_x3<2>(x, st);
+    } else {
+        WgFirstArgs a;
+        a.dA = (const bf16s*)dA; a.ldA = ldA; a.z = (const bf16s*)z; a.bn = bn; a.sums = sums; a.x = (const bf16s*)in0;
+        wgrad_first_fill(a, p, partial, N, H, W, imgs_per_group);
+        a.Dz = 0; a.dshift = 0;
+        rc = launch_wgrad_first<false>(a, st);
     }
-    WgFirstArgs a;
-    a.dA = (const bf16s*)dA; a.ldA = ldA; a.z = (const bf16s*)z; a.bn = bn; a.sums = sums; a.x = (const bf16s*)in0;
-    a.partial = partial; a.N = N; a.H = H; a.W = W; a.imgs_per_group = imgs_per_group;
-    a.tiles_y = p.g.tiles_y; a.tiles_x = p.g.tiles_x; a.n_mtiles = p.g.n_mtiles; a.S = p.S; a.per_split = p.per_split;
-    a.invM = 1.f / (float)((size_t)imgs_per_group * H * W);
-    a.Dz = 0; a.dshift = 0;
-    hipLaunchKernelGGL(wgrad_first_kernel<false>, dim3(p.S), dim3(256), WgF::SMEM, st, a);
-    BDN_CHECK_LAUNCH("wgrad_first");
-    launch_wgrad_reduce(partial, dw_oihw, p.S, Cout, C0, Cin_real, st);
-    BDN_CHECK_LAUNCH("wgrad_reduce");
-    return BDN_OK;
+    return rc ? rc : launch_wgrad_reduce(partial, dw_oihw, p.S, Cout, C0, Cin_real, st);
 }
 
 // which kernel the GEMM phase runs for `flags` (bench.py names its roofline line after it): BDN_WG_SIMPLE / BDN_WG_ROLE
 extern "C" int bdn_conv3x3_wgrad_variant(int dtype, int N, int H, int W, int Cout, int C0, int C1, int imgs_per_group, int in_mode, int flags) {
     if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || C0 <= 0 || imgs_per_group <= 0) return 0;
+    // (kept quirk: BDN_BF16X3 answers from the doubled plan whichever route wgrad_x3_fused picks, BDN_BF16X2 falls through to BDN_WG_SIMPLE)
     if (dtype == BDN_BF16X3) return wgrad_plan(BDN_BF16, N, H, W, 2 * Cout, 2 * (C0 + C1), 0, imgs_per_group, BDN_IN_PLAIN, flags).variant;
     return wgrad_plan(dtype, N, H, W, Cout, C0, C1, imgs_per_group, in_mode, flags).variant;
+}
+
+// The kernels bdn_conv3x3_wgrad_ex launches for these arguments and this flags word (phase bits 0 = both phases), '+'-joined in launch
+// order; "" where it refuses.  Its own code path in query mode on dummy pointers that are never dereferenced (as bdn_conv3x3_variant).
+extern "C" const char* bdn_conv3x3_wgrad_kernels(int dtype, int N, int H, int W, int Cout, int C0, int C1, int imgs_per_group, int in_mode, int flags) {
+    float* dummy = reinterpret_cast<float*>(16);
+    g_wg_names[0] = 0; g_wg_query = true;
+    const int rc = bdn_conv3x3_wgrad_ex(dtype, dummy, Cout, dummy, C0, C1 ? dummy : nullptr, C1, in_mode, dummy, imgs_per_group, dummy, dummy, 1,
+                                        N, H, W, (flags & 3) ? flags : flags | 3, nullptr);
+    g_wg_query = false;
+    return rc == BDN_OK ? g_wg_names : "";
+}
+
+// the same for bdn_conv3x3_wgrad_bnbwd; "" outside bdn_conv3x3_wgrad_bnbwd_supported
+extern "C" const char* bdn_conv3x3_wgrad_bnbwd_kernels(int dtype, int N, int H, int W, int Cout, int C0, int imgs_per_group) {
+    float* dummy = reinterpret_cast<float*>(16);
+    g_wg_names[0] = 0; g_wg_query = true;
+    const int rc = bdn_conv3x3_wgrad_bnbwd(dtype, dummy, 64, dummy, dummy, dummy, imgs_per_group, Cout, dummy, C0, dummy, dummy, 1, N, H, W, nullptr);
+    g_wg_query = false;
+    return rc == BDN_OK ? g_wg_names : "";
 }
 
 // ---- weight gradient of the 3x3x3 convolution (bdn_conv3d): dw[co][ci][kd][kh][kw], f32 OIDHW.
@@ -1388,45 +1435,32 @@ extern "C" int bdn_conv3d_wgrad(int dtype, const void* dz, int Cout, const void*
     const int NS = N * D;
     const WgPlan p = wgrad_plan(dtype, NS, H, W, Cout, C, 0, 1 /* one slice per tile */, BDN_IN_PLAIN, 0);
     if (p.g.TI != 1) BDN_FAIL(BDN_E_SHAPE, "conv3d_wgrad: internal plan error");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype == BDN_BF16 && Cout == 64 && C == 16 && (size_t)NS * H * W * 64 < ((size_t)1 << 31)) {
         // the first layer of a multi-date stack (13 -> 64): the 2-D first-layer kernel in its plain-dz form, once per depth tap -- 64 x 16 x 9
         // accumulators per block, HBM-bound (dz is read three times, 4.6 TB/s) where the generic k-split GEMM ran at 1.6 TB/s
         WgFirstArgs f;
         f.dA = (const bf16s*)dz; f.ldA = Cout; f.z = nullptr; f.bn = nullptr; f.sums = nullptr; f.x = (const bf16s*)in;
-        f.partial = partial; f.N = NS; f.H = H; f.W = W; f.imgs_per_group = 1;
-        f.tiles_y = p.g.tiles_y; f.tiles_x = p.g.tiles_x; f.n_mtiles = p.g.n_mtiles; f.S = p.S * (p.ksplit ? 2 : 1);
+        wgrad_first_fill(f, p, partial, NS, H, W, 1);
+        f.S = p.S * (p.ksplit ? 2 : 1);
         f.per_split = (p.g.n_mtiles + f.S - 1) / f.S;
         f.S = (p.g.n_mtiles + f.per_split - 1) / f.per_split;      // no empty splits (their partial tiles would be read uninitialised)
         f.invM = 0.f; f.Dz = D;
-        hipStream_t st1 = reinterpret_cast<hipStream_t>(stream);
         for (int kd = 0; kd < 3; kd++) {
             f.dshift = kd - 1;
-            hipLaunchKernelGGL(wgrad_first_kernel<true>, dim3(f.S), dim3(256), WgF::SMEM, st1, f);
-            BDN_CHECK_LAUNCH("conv3d_wgrad_first");
-            launch_wgrad_reduce(partial, dw_oidhw, f.S, Cout, C, Cin_real, st1, 27, 9 * kd);
-            BDN_CHECK_LAUNCH("conv3d_wgrad_reduce");
+            int rc = launch_wgrad_first<true>(f, st, "conv3d_wgrad_first");
+            if (!rc) rc = launch_wgrad_reduce(partial, dw_oidhw, f.S, Cout, C, Cin_real, st, 27, 9 * kd, "conv3d_wgrad_reduce");
+            if (rc) return rc;
         }
         return BDN_OK;
     }
-    WgradArgs a;
-    a.dz = dz; a.Cout = Cout; a.in0 = in; a.in1 = nullptr; a.C0 = C; a.C1 = 0; a.in_bn = nullptr; a.imgs_per_group = 1;
-    a.partial = partial; a.N = NS; a.H = H; a.W = W;
-    a.tiles_y = p.g.tiles_y; a.tiles_x = p.g.tiles_x; a.n_mtiles = p.g.n_mtiles;
-    a.S = p.S; a.per_split = p.per_split; a.n_cot = p.n_cot; a.n_cit = p.n_cit; a.x3h = 0; a.n_tiles = p.n_tiles;
+    WgradArgs a = wgrad_args(p, dz, Cout, in, C, nullptr, 0, 1, partial, NS, H, W);
     a.Dz = D;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     for (int kd = 0; kd < 3; kd++) {
         a.dshift = kd - 1;
-        int rc;
-        if (dtype == BDN_BF16) {
-            if (p.variant == BDN_WG_ROLE) rc = launch_wgrad7<false>(a, st);
-            else rc = p.ksplit ? launch_wgrad<bf16s, 8, 16, 1, true>(a, st) : launch_wgrad<bf16s, 8, 16, 1, false>(a, st);
-        } else {
-            rc = p.ksplit ? launch_wgrad<float, 8, 16, 1, true>(a, st) : launch_wgrad<float, 8, 16, 1, false>(a, st);
-        }
+        int rc = launch_wgrad_gemm(dtype, p, a, st);
+        if (!rc) rc = launch_wgrad_reduce(partial, dw_oidhw, p.S * (p.ksplit ? 2 : 1), Cout, C, Cin_real, st, 27, 9 * kd, "conv3d_wgrad_reduce");
         if (rc) return rc;
-        launch_wgrad_reduce(partial, dw_oidhw, p.S * (p.ksplit ? 2 : 1), Cout, C, Cin_real, st, 27, 9 * kd);
-        BDN_CHECK_LAUNCH("conv3d_wgrad_reduce");
     }
     return BDN_OK;
 }

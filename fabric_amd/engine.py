@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import torch
 
 from . import _lib
-from ._lib import BDN_BF16, BDN_BF16X2, BDN_BF16X3, BDN_F32, IN_BNRELU, IN_PLAIN, WG_ROLE, call, ptr, wg_flags
+from ._lib import BDN_BF16, BDN_BF16X2, BDN_BF16X3, BDN_F32, IN_BNRELU, IN_PLAIN, call, ptr, wg_flags
 
 ENC_CH = (64, 128, 256, 512, 512)           # models/bidate_model.py:10-14
 DEC_OUT = (256, 128, 64, 64)                # models/bidate_model.py:16-19
@@ -712,22 +712,9 @@ class BiDateEngine:
 
     @staticmethod
     def wgrad_gemm_name(dtype, n, h, w, cout, c0, c1, ipg, mode, flags):
-        """The GEMM instantiation(s) bdn_conv3x3_wgrad_ex runs, '+'-joined.  The family is the library's answer (bdn_conv3x3_wgrad_variant);
-        the tile geometry of the one-chunk-at-a-time kernel and the bf16x3 fused / doubled-operand choice are HAND COPIES of pick_tile
-        (common.hpp) and bdn_conv3x3_wgrad_ex: tests/test_gpu_launch_shapes.py checks them against recorded launches."""
-        lib = _lib.load()
-        if dtype in (BDN_BF16X3, BDN_BF16X2):
-            terms = 3 if dtype == BDN_BF16X3 else 2
-            if cout % 64 == 0 and c0 % 64 == 0 and lib.bdn_conv3x3_wgrad_variant(BDN_BF16, n, h, w, cout, c0, 0, ipg, IN_PLAIN, flags) == WG_ROLE:
-                return f'wgrad7x_kernel<{terms}>'
-            # the doubled operands through the bf16 GEMM (internal plan flags: the lo x lo quadrant left out), then the quadrant sum
-            xfl = (1 << 30) | ((1 << 29) if terms == 2 else 0)
-            return BiDateEngine.wgrad_gemm_name(BDN_BF16, n, h, w, 2 * cout, 2 * c0, 0, ipg, IN_PLAIN, flags | xfl) + '+wgrad_x3_combine_kernel'
-        if lib.bdn_conv3x3_wgrad_variant(dtype, n, h, w, cout, c0, c1, ipg, mode, flags) == WG_ROLE:
-            return f'wgrad7_kernel<{"true" if mode == IN_BNRELU else "false"}>'
-        small = h <= 8 and w <= 8 and ipg % 2 == 0
-        return (f'wgrad_kernel<{"bf16" if dtype == BDN_BF16 else "f32"},8,{"8,2" if small else "16,1"},'
-                f'{"true" if c0 + c1 <= 32 else "false"}>')
+        """The GEMM instantiation(s) bdn_conv3x3_wgrad_ex runs, '+'-joined: the library's answer (bdn_conv3x3_wgrad_kernels) less the reduction."""
+        k = _lib.load().bdn_conv3x3_wgrad_kernels(dtype, n, h, w, cout, c0, c1, ipg, mode, flags | 3).decode()
+        return '+'.join(x for x in k.split('+') if not x.startswith('wgrad_reduce_kernel<'))
 
     # ------------------------------------------------------------------ backward
     def backward(self, ws, dlogits, P, grads, on_ready=None, zero_bias_grads=True, wgrad_stream=True, dx=None, bn_mode='batch',
@@ -898,7 +885,7 @@ class BiDateEngine:
                 call('bdn_conv3x3_wgrad_ex', *args, flg, stp)
                 return
             ph = flg & ~3                            # the flags word without its phase bits
-            self._timed(lambda: self.wgrad_gemm_name(dt, n, hk, wk, L.cout, c0, c1, ipg, mode, ph | 3),
+            self._timed(lambda: _lib.load().bdn_conv3x3_wgrad_kernels(dt, n, hk, wk, L.cout, c0, c1, ipg, mode, ph | 1).decode(),
                         2.0 * n * hk * wk * L.cout * 9 * (c0 + c1), 'bdn_conv3x3_wgrad_ex', *args, flg, stp,
                         split=(('bdn_conv3x3_wgrad_ex', *args, ph | 1, stp), ('bdn_conv3x3_wgrad_ex', *args, ph | 2, stp)))
 
@@ -952,7 +939,10 @@ class BiDateEngine:
 
                 def launch(stp, role):               # always on the chain's stream (last=True): the 'chain' scratch
                     part = ws.wgrad_scratch('chain', 'bdn_wgrad_workspace_bytes', n, hk, wk, L.cout, L.cin, B)
-                    self._timed(lambda: 'wgrad_first_kernel', 2.0 * n * hk * wk * L.cout * 9 * L.cin, 'bdn_conv3x3_wgrad_bnbwd',
+                    def name():                      # (wgrad_first_x3_kernel<T>, the split-operand form, keeps the label it always had)
+                        k = _lib.load().bdn_conv3x3_wgrad_bnbwd_kernels(fdt, n, hk, wk, L.cout, L.cin, B).decode().split('+')[0]
+                        return 'wgrad_first_kernel' if k.startswith('wgrad_first_x3_kernel<') else k
+                    self._timed(name, 2.0 * n * hk * wk * L.cout * 9 * L.cin, 'bdn_conv3x3_wgrad_bnbwd',
                                 fdt, dA, L.cout, ptr(ws.z[L.name]), ptr(ws.bn[L.name]), ptr(sc['sums']), B, L.cout,
                                 ptr(fin), L.cin, ptr(part), ptr(grads[f'{L.conv}.weight']), L.cin_real, n, hk, wk, stp)
                 release(L, launch, last=True)

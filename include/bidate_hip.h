@@ -204,6 +204,14 @@ int bdn_conv3x3_wgrad_ex(int dtype, const void* dz, int Cout,
                          int N, int H, int W, int flags, void* stream);
 int bdn_conv3x3_wgrad_variant(int dtype, int N, int H, int W, int Cout, int C0, int C1, int imgs_per_group,
                               int in_mode, int flags);
+/* The kernels bdn_conv3x3_wgrad_ex launches for these arguments and this flags word, '+'-joined in launch order, e.g.
+ * "wgrad7_kernel<true>+wgrad_reduce_kernel<8>" or "wgrad_kernel<bf16,8,8,2,false>+wgrad_reduce_kernel<1>+wgrad_x3_combine_kernel":
+ * the entry point's own code path with the launches replaced by their names (host only, no device needed), so the GEMM instantiation,
+ * the bf16x3 / bf16x2 route (fused wgrad7x_kernel or doubled operands + combine) and the split lanes of the reduction all come from the
+ * code that launches.  Phase bits as in `flags` (1: the GEMM alone; 2: the reduction, and the combine where there is one; 0 is read as
+ * 3).  "" where bdn_conv3x3_wgrad_ex refuses the arguments.  The string is thread-local and valid until the thread's next query. */
+const char* bdn_conv3x3_wgrad_kernels(int dtype, int N, int H, int W, int Cout, int C0, int C1, int imgs_per_group,
+                                      int in_mode, int flags);
 /* Weight gradient of the FIRST convolution (inc.conv.conv.0, models/unet_parts.py:13 via unet_model.py inconv) with the
  * BatchNorm+ReLU backward of its own output (unet_parts.py:14-15) fused into the staging: the layer has no data gradient,
  * so dz = bn_bwd(dA, z) is never written -- the kernel reads dA [N,H,W,ldA>=64] and z [N,H,W,64], applies
@@ -218,6 +226,8 @@ int bdn_conv3x3_wgrad_bnbwd_supported(int dtype, int N, int H, int W, int Cout, 
 int bdn_conv3x3_wgrad_bnbwd(int dtype, const void* dA, int ldA, const void* z, const float* bn, const float* sums,
                             int imgs_per_group, int Cout, const void* in0, int C0,
                             float* partial, float* dw_oihw, int Cin_real, int N, int H, int W, void* stream);
+/* Its kernels, as bdn_conv3x3_wgrad_kernels ("wgrad_first_kernel+wgrad_reduce_kernel<16>"); "" outside bdn_conv3x3_wgrad_bnbwd_supported. */
+const char* bdn_conv3x3_wgrad_bnbwd_kernels(int dtype, int N, int H, int W, int Cout, int C0, int imgs_per_group);
 /* Data gradient of the FIRST convolution (inc.conv.conv.0, models/unet_parts.py:13 in models/bidate_model.py:22-30): the gradient on the
  * two input images.  dA [2B,H,W,ldA >= 64], z [2B,H,W,64] of the shared encoder's 2B images (date 1 first: bdn_pack_input's order),
  * dz formed on load with bdn_bn_bwd_apply's expression from bn [G][4][64] and sums [G][2][64] (bdn_bn_bwd_finalize: batch statistics;

@@ -184,44 +184,22 @@ def eval_inst(kind, dtype, N, H, W, C0, C1, Cout):
     return _s(_lib.load().bdn_conv3x3_eval_variant(kind, dtype, N, H, W, C0, C1, Cout))
 
 
-def _reduce_lanes(S, plane):
-    """Split lanes of wgrad_reduce_kernel<SL>: a HAND COPY of the rule in wgrad.hip launch_wgrad_reduce, which has no query entry point.
-    Nothing checks the copy against the C code -- the GPU test maps recorded calls through this same function -- so a change of that rule
-    must be mirrored here, or the lanes the rows claim go stale unnoticed."""
-    sl = 1
-    while sl < 16 and sl * 2 <= S and plane // (256 // (sl * 2)) < 256:
-        sl *= 2
-    return sl
-
-
-def _splits(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags):
-    """Split count S of a weight-gradient plan, read back from its workspace size (S x (2 when Cin <= 32) x 9 Cout Cin floats)."""
-    nb = _lib.load().bdn_wgrad_workspace_bytes_ex(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
-    per = 9 * Cout * (C0 + C1) * 4 * (2 if C0 + C1 <= 32 else 1)
-    assert nb % per == 0, (nb, per)
-    return nb // per
+def _gemm_and_lanes(kernels):
+    """'+'-joined kernel names of a weight-gradient call -> (the names without the reduction, its split lanes)."""
+    names = _s(kernels).split('+')
+    red = [n for n in names if n.startswith('wgrad_reduce_kernel<')]
+    assert len(red) == 1, names
+    return '+'.join(n for n in names if n not in red), int(red[0][len('wgrad_reduce_kernel<'):-1])
 
 
 def wgrad_inst(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags=wg_flags()):
-    """(GEMM instantiation, split lanes of its reduction) of bdn_conv3x3_wgrad_ex.  The GEMM is the engine's answer
-    (BiDateEngine.wgrad_gemm_name), the split count comes from the plan's workspace size (the library's own answer)."""
-    g = BiDateEngine.wgrad_gemm_name(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
-    if dtype in (BDN_BF16X3, BDN_BF16X2):
-        if not g.endswith('+wgrad_x3_combine_kernel'):
-            return g, _reduce_lanes(_splits(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, flags), Cout * C0)
-        # the doubled operands through the bf16 GEMM (internal plan flags: the lo x lo quadrant left out), then the quadrant sum
-        xfl = (1 << 30) | ((1 << 29) if dtype == BDN_BF16X2 else 0)
-        return g, wgrad_inst(BDN_BF16, N, H, W, 2 * Cout, 2 * C0, 0, ipg, IN_PLAIN, flags | xfl)[1]
-    ks = C0 + C1 <= 32
-    S = _splits(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags)
-    return g, _reduce_lanes(S * (2 if ks else 1), Cout * (C0 + C1))
+    """(GEMM instantiation(s), split lanes of the reduction) of bdn_conv3x3_wgrad_ex: the library's answer (bdn_conv3x3_wgrad_kernels)."""
+    return _gemm_and_lanes(_lib.load().bdn_conv3x3_wgrad_kernels(dtype, N, H, W, Cout, C0, C1, ipg, mode, flags | 3))
 
 
 def wgrad_bnbwd_inst(dtype, N, H, W, Cout, C0, ipg):
-    """(instantiation, split lanes) of bdn_conv3x3_wgrad_bnbwd: its own 256-block plan of the bf16 first-layer shape."""
-    S = _splits(BDN_BF16, N, H, W, Cout, C0, 0, ipg, IN_PLAIN, wg_flags(0, 0, 256))
-    name = 'wgrad_first_kernel' if dtype == BDN_BF16 else f'wgrad_first_x3_kernel<{3 if dtype == BDN_BF16X3 else 2}>'
-    return name, _reduce_lanes(S, Cout * C0)
+    """(instantiation, split lanes) of bdn_conv3x3_wgrad_bnbwd (bdn_conv3x3_wgrad_bnbwd_kernels)."""
+    return _gemm_and_lanes(_lib.load().bdn_conv3x3_wgrad_bnbwd_kernels(dtype, N, H, W, Cout, C0, ipg))
 
 
 def instantiation(r):
