@@ -21,26 +21,43 @@ autograd.  The overlap term still runs over all valid pixels.  terms becomes f32
 threshold), counts int32[6] = {TP, FP, FN, correct, valid, K}.  It needs a focal weight (gamma = 0 is top-k cross-entropy) and class
 weights >= 0, and composes with ignore_index.  Data-parallel: each rank selects its own K from its own batch; with gradient accumulation
 the selection is per micro-step.  topk=None is the criterion as it was, call for call.
+
+w_lovasz (>= 0) adds w_lovasz * the Lovasz-Softmax term (Berman, Rahman Triki, Blaschko, CVPR 2018, batch level: the loss that optimises
+the Jaccard index itself) -- ``bdn_lovasz_softmax``, an add-on pass behind whichever entry point above has run: per class the valid pixels
+are sorted by |fg - p_c| descending on the device (the top-k key map, ties: the lower pixel index first) and weighted by the increments of
+the Jaccard index along that order; the term is the mean over the classes present among the valid pixels (lovasz_classes='present') or
+over every class ('all'); the order is a constant for the gradient, as torch.sort is under autograd.  `terms` gains one trailing element,
+the unweighted Lovasz value; counts keep their shape.  With the Lovasz term alone the counts are those of confusion_counts().  It composes
+with ignore_index and topk.  Data-parallel: each rank sorts its own batch; with gradient accumulation the sort is per micro-step.
+w_lovasz=0 is the criterion as it was, call for call.
 """
 
 NAMES = ('tversky', 'dice', 'jaccard', 'focal', 'focal+tversky', 'focal+dice', 'focal+jaccard')
 COMPOUND = tuple(n for n in NAMES if '+' in n)
+LOVASZ_NAMES = ('lovasz', 'focal+lovasz')
+LOVASZ_CLASSES = {'present': 0, 'all': 1}
 REDUCE = {'columns': 0, 'image': 1}
 
 
 class Criterion:
     def __init__(self, w_overlap=1.0, alpha=0.5, beta=0.5, eps=1e-7, reduce='columns', w_focal=0.0, gamma=0.0, class_alpha=None,
-                 size_average=True, ignore_index=None, topk=None):
+                 size_average=True, ignore_index=None, topk=None, w_lovasz=0.0, lovasz_classes='present'):
         """reduce: 'columns' -- what the reference's train.py gets from [B,H,W] labels, sums over dims (0,2), one ratio per (class,
         column) -- or 'image', dims (0,2,3), one ratio per class ([B,1,H,W] labels there).  class_alpha: None, a float a (class
         weights [a, 1 - a], utils/metrics.py:13-14) or a sequence of ncls class weights.  ignore_index: None -- every pixel carries a label,
         bdn_criterion -- or the label byte (0..255) of the pixels to leave out (module docstring), bdn_criterion_masked.  topk: None, or the fraction 0 < f <= 1 of the valid pixels the
-        focal term is averaged over, the hardest first (module docstring), bdn_criterion_topk."""
-        w_overlap, w_focal = float(w_overlap), float(w_focal)
+        focal term is averaged over, the hardest first (module docstring), bdn_criterion_topk.  w_lovasz: the weight of the Lovasz-Softmax term,
+        lovasz_classes 'present' or 'all' (module docstring), bdn_lovasz_softmax."""
+        w_overlap, w_focal, w_lovasz = float(w_overlap), float(w_focal), float(w_lovasz)
         if not (w_overlap >= 0.0 and w_focal >= 0.0):
             raise ValueError(f'criterion weights must be >= 0, got w_overlap={w_overlap}, w_focal={w_focal}')
-        if w_overlap == 0.0 and w_focal == 0.0:
+        if not w_lovasz >= 0.0:
+            raise ValueError(f'criterion weights must be >= 0, got w_lovasz={w_lovasz}')
+        if lovasz_classes not in LOVASZ_CLASSES:
+            raise ValueError(f"lovasz_classes must be 'present' or 'all', got {lovasz_classes!r}")
+        if w_overlap == 0.0 and w_focal == 0.0 and w_lovasz == 0.0:
             raise ValueError('criterion weights are both zero')
+        self.w_lovasz, self.lovasz_classes = w_lovasz, lovasz_classes
         if reduce not in REDUCE:
             raise ValueError(f"reduce must be 'columns' or 'image', got {reduce!r}")
         if not float(gamma) >= 0.0:
@@ -72,11 +89,18 @@ class Criterion:
 
     @classmethod
     def parse(cls, name, tversky_alpha=0.5, tversky_beta=0.5, focal_gamma=None, focal_alpha=None, weights=(1, 1), eps=1e-7,
-              reduce='columns', ignore_index=None, topk=None):
+              reduce='columns', ignore_index=None, topk=None, lovasz_classes='present'):
         """The criterion of a --loss_function name.  weights = (w_focal, w_overlap), used by the compound names only.  topk: a name with a
-        focal term only (Criterion raises ValueError otherwise)."""
+        focal term only (Criterion raises ValueError otherwise).  LOVASZ_NAMES: 'lovasz' is the Lovasz-Softmax term alone; 'focal+lovasz'
+        has weights = (w_focal, w_lovasz) and, with focal_gamma None, gamma 0: cross-entropy + Lovasz, the usual pairing."""
+        if name in LOVASZ_NAMES:
+            focal = name != 'lovasz'
+            w_focal, w_lovasz = (float(weights[0]), float(weights[1])) if focal else (0.0, 1.0)
+            return cls(0.0, eps=eps, reduce=reduce, w_focal=w_focal, gamma=(focal_gamma or 0.0) if focal else 0.0,
+                       class_alpha=focal_alpha if focal else None, ignore_index=ignore_index, topk=topk, w_lovasz=w_lovasz,
+                       lovasz_classes=lovasz_classes)
         if name not in NAMES:
-            raise ValueError(f'unknown criterion {name!r}: one of {", ".join(NAMES)}')
+            raise ValueError(f'unknown criterion {name!r}: one of {", ".join(NAMES + LOVASZ_NAMES)}')
         parts = name.split('+')
         focal, overlap = 'focal' in parts, parts[-1] if parts[-1] != 'focal' else None
         if focal and focal_gamma is None:
@@ -91,7 +115,8 @@ class Criterion:
         return (f'Criterion(w_overlap={self.w_overlap}, alpha={self.alpha}, beta={self.beta}, eps={self.eps}, reduce={self.reduce!r}, '
                 f'w_focal={self.w_focal}, gamma={self.gamma}, class_alpha={self.class_alpha}, size_average={self.size_average}'
                 + (f', ignore_index={self.ignore_index}' if self.ignore_index is not None else '')
-                + (f', topk={self.topk}' if self.topk is not None else '') + ')')
+                + (f', topk={self.topk}' if self.topk is not None else '')
+                + (f', w_lovasz={self.w_lovasz}, lovasz_classes={self.lovasz_classes!r}' if self.w_lovasz else '') + ')')
 
     # ------------------------------------------------------------------ device side
     def _class_alpha(self, device, ncls):
@@ -107,7 +132,8 @@ class Criterion:
 
     def buffers(self, shape, device):
         """Persistent outputs for logits of `shape`: (workspace, loss, terms, counts), the `out` of evaluate().  counts is int32[4], or
-        int32[5] with an ignore_index; with topk, terms is f32[3] and counts int32[6]."""
+        int32[5] with an ignore_index; with topk, terms is f32[3] and counts int32[6].  With w_lovasz the workspace also holds
+        bdn_lovasz_softmax's (behind the other, 256-byte aligned) and terms has one more element, the last."""
         import torch
         from . import _lib
         B, C, H, W = shape
@@ -118,11 +144,33 @@ class Criterion:
         n = query(B, C, H, W, REDUCE[self.reduce])
         if n == 0:
             raise RuntimeError(f'fabric_amd: the criterion takes logits [B, 2..8, H, W] with B*H*W < 2^31, got {tuple(shape)}')
-        return (torch.empty((n + 15) // 16 * 16, dtype=torch.uint8, device=device), torch.empty((), dtype=torch.float32, device=device),
-                torch.empty(3 if self.topk is not None else 2, dtype=torch.float32, device=device),
+        n_terms = 3 if self.topk is not None else 2
+        if self.w_lovasz:
+            n = self._lovasz_offset(n) + _lib.load().bdn_lovasz_workspace_bytes(B, C, H, W)
+            n_terms += 1
+        # the Lovasz term alone: the entry point that counts writes no term, so the terms in front of the last one are zeroed here, once
+        terms = (torch.zeros if self._lovasz_only else torch.empty)(n_terms, dtype=torch.float32, device=device)
+        return (torch.empty((n + 15) // 16 * 16, dtype=torch.uint8, device=device), torch.empty((), dtype=torch.float32, device=device), terms,
                 torch.empty(6 if self.topk is not None else 5 if masked else 4, dtype=torch.int32, device=device))
 
-    def evaluate(self, logits, labels, want_grad=True, out=None, pixel_terms=None, kept=None):
+    @staticmethod
+    def _lovasz_offset(n):
+        """Where bdn_lovasz_softmax's workspace starts behind the n bytes of the other entry point's."""
+        return (n + 255) // 256 * 256
+
+    @property
+    def _lovasz_only(self):
+        return self.w_lovasz > 0.0 and self.w_overlap == 0.0 and self.w_focal == 0.0
+
+    def _lovasz(self, logits, labels, ws, n_base, loss, terms, dlogits, accumulate, pixel_errors, ranks):
+        from . import _lib
+        B, C, H, W = logits.shape
+        _lib.call('bdn_lovasz_softmax', logits.data_ptr(), labels.data_ptr(), -1 if self.ignore_index is None else self.ignore_index,
+                  LOVASZ_CLASSES[self.lovasz_classes], self.w_lovasz, int(accumulate), ws.data_ptr() + self._lovasz_offset(n_base),
+                  loss.data_ptr(), terms.data_ptr() + 4 * (terms.numel() - 1), _lib.ptr(dlogits), _lib.ptr(pixel_errors), _lib.ptr(ranks),
+                  B, C, H, W, _lib.stream_ptr())
+
+    def evaluate(self, logits, labels, want_grad=True, out=None, pixel_terms=None, kept=None, pixel_errors=None, ranks=None):
         """-> (loss, terms, counts, dlogits) of float32 [B,C,H,W] logits and [B,H,W] or [B,1,H,W] class-index labels, on the current
         stream: loss a 0-dim tensor, terms f32[2] = the unweighted overlap and focal values, counts int32[4] = {TP, FP, FN, correct} of
         argmax(logits), dlogits = d loss / d logits (None without want_grad: no gradient pass is launched).  `out`: buffers() of this
@@ -130,7 +178,11 @@ class Criterion:
         whichever rank the labels have.  With an ignore_index: counts int32[5] = {TP, FP, FN, correct, valid} over the valid pixels and
         dlogits exactly 0 at the ignored ones (module docstring).  With topk: terms f32[3] = overlap, focal, threshold and counts int32[6]
         = {.., valid, K}; `pixel_terms` (contiguous float32, B*H*W elements) and `kept` (contiguous uint8, B*H*W) are optional caller
-        tensors that receive every pixel's ranked term (unspecified at ignored pixels) and its 0 / 1 kept flag."""
+        tensors that receive every pixel's ranked term (unspecified at ignored pixels) and its 0 / 1 kept flag.  With w_lovasz: the entry
+        point above runs as it always did, then bdn_lovasz_softmax adds its term to loss and dlogits on the same stream (the term alone:
+        the counts of confusion_counts(), then bdn_lovasz_softmax writes loss and dlogits); terms[-1] is the unweighted Lovasz value;
+        `pixel_errors` (contiguous float32, C*B*H*W) and `ranks` (contiguous int32, C*B*H*W) are optional caller tensors that receive
+        every class's errors and 0-based ranks (-1 at ignored pixels)."""
         import torch
         from . import _lib
         if not logits.is_cuda:
@@ -146,6 +198,37 @@ class Criterion:
         ws, loss, terms, counts = out if out is not None else self.buffers(logits.shape, logits.device)
         dlogits = torch.empty_like(logits) if want_grad else None
         ca = self._class_alpha(logits.device, C)
+        if not self.w_lovasz:
+            if pixel_errors is not None or ranks is not None:
+                raise RuntimeError('fabric_amd: pixel_errors / ranks are outputs of a criterion with w_lovasz')
+            return self._evaluate_base(logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept)
+        for t, dt, what in ((pixel_errors, torch.float32, 'pixel_errors'), (ranks, torch.int32, 'ranks')):
+            if t is not None and (t.device != logits.device or t.dtype != dt or t.numel() != C * B * H * W or not t.is_contiguous()):
+                raise RuntimeError(f'fabric_amd: {what} must be a contiguous {dt} tensor of {C * B * H * W} elements on {logits.device}')
+        masked = self.ignore_index is not None
+        query = 'bdn_criterion_topk_workspace_bytes' if self.topk is not None else \
+            'bdn_criterion_masked_workspace_bytes' if masked else 'bdn_criterion_workspace_bytes'
+        n_base = getattr(_lib.load(), query)(B, C, H, W, REDUCE[self.reduce])
+        if self._lovasz_only:                              # the counts: the statistics and finish passes of the overlap loss, no gradient pass
+            if pixel_terms is not None or kept is not None:
+                raise RuntimeError('fabric_amd: pixel_terms / kept are outputs of a criterion with topk')
+            if masked:
+                _lib.call('bdn_criterion_masked', logits.data_ptr(), labels.data_ptr(), self.ignore_index, 1.0, self.alpha, self.beta, self.eps,
+                          REDUCE[self.reduce], 0.0, 0.0, None, 1, ws.data_ptr(), loss.data_ptr(), None, counts.data_ptr(), None, B, C, H, W,
+                          _lib.stream_ptr())
+            else:
+                _lib.call('bdn_criterion', logits.data_ptr(), labels.data_ptr(), 1.0, self.alpha, self.beta, self.eps, REDUCE[self.reduce], 0.0,
+                          0.0, None, 1, ws.data_ptr(), loss.data_ptr(), None, counts.data_ptr(), None, B, C, H, W, _lib.stream_ptr())
+        else:
+            self._evaluate_base(logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept)
+        self._lovasz(logits, labels, ws, n_base, loss, terms, dlogits, not self._lovasz_only, pixel_errors, ranks)
+        return loss, terms, counts, dlogits
+
+    def _evaluate_base(self, logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept):
+        """The overlap / focal entry point of this criterion, as evaluate() has always called it."""
+        import torch
+        from . import _lib
+        B, C, H, W = logits.shape
         if self.topk is None:
             if pixel_terms is not None or kept is not None:
                 raise RuntimeError('fabric_amd: pixel_terms / kept are outputs of a criterion with topk')

@@ -40,6 +40,11 @@ struct PackDesc { const float* w; void* wf; void* wd; int Cout, Cin, Cinp, pad_;
 int bdn_pack_weights_x3_multi(const PackDesc* desc, int n_layers, hipStream_t st);
 int bdn_wgrad_x3_combine(const float* T, float* dw, int Cout, int Cinp, int Cin_real, int taps, int terms, hipStream_t st);
 
+// the monotone 32-bit key of a float32 bit pattern (bdn_criterion_topk's select in loss.hip, bdn_lovasz_softmax's sort in lovasz.hip):
+// ascending keys are ascending floats, -0 < +0, +inf above every finite value, every bit pattern (NaN included) has a place
+__device__ __forceinline__ unsigned topk_key(float v) { const unsigned u = __float_as_uint(v); return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u); }
+__device__ __forceinline__ float topk_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
 // ---------------------------------------------------------------- division by a launch-invariant integer
 // n / d for 0 <= n < 2^31 as one v_mul_hi_u32 and a shift (the round-up multiplier; exhaustively checked against n / d on the host
 // for every d <= 70 000 at the critical n and on 2e6 random pairs).  A runtime integer division is 15-20 VALU instructions, and the

@@ -151,8 +151,6 @@ __global__ void tversky_sums_kernel(const float* __restrict__ logits, const uint
 // TOPK: the focal scale is 1/K (K the kept count, state[0] of the select's last level; 1 when K = 0), counts[5] = K, terms[2] = the K-th
 // largest term (state[2] holds its key; 0 when K = 0), and `part` holds the nfp block partials of the kept terms.
 struct FocalFinish { const double* part; int nfp; double scale; float w_o, w_f; float* terms; int size_average; float* gscale; const long long* kstate; };
-__device__ __forceinline__ unsigned topk_key(float v) { const unsigned u = __float_as_uint(v); return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u); }
-__device__ __forceinline__ float topk_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 template <bool FOCAL = false, bool MASKED = false, bool TOPK = false>
 __global__ __launch_bounds__(1024) void tversky_finish_kernel(float* __restrict__ sums, const float* __restrict__ part, int nblk,
                                       const int32_t* __restrict__ pcounts, int ncblk, int32_t* __restrict__ counts,

@@ -10,6 +10,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --accumulate 4 --max_grad_norm 1.0
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --ignore_label 255
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --loss_topk 0.25
+    python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+lovasz --focal_gamma 0       # cross-entropy + Lovasz-Softmax
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --ema_decay 0.999        # validate and save the averaged weights
     python -m fabric_amd.train --metadata metadata.json --val_curve_bins 1024 --scene_stride 64 --scene_threshold val      # best-F1 threshold, AP
 
@@ -121,9 +122,10 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
     from .device_loader import DevicePatchLoader
     from .input_pipeline import DeviceFeeder
     step.model.train()
-    recs, norms, mined = [], [], []
+    recs, norms, mined, lov = [], [], [], []
     clip = step.max_grad_norm is not None
     topk = getattr(step.criterion, 'topk', None) is not None      # hard-pixel mining: K and the threshold of every batch, read back with the losses
+    lovasz = getattr(step.criterion, 'w_lovasz', 0.0) > 0.0        # the Lovasz-Softmax term of every batch (terms[-1]), read back with the losses
     if not isinstance(loader, DevicePatchLoader):
         feeder = feeder or DeviceFeeder(dev)
     with torch.cuda.stream(step.stream()):                # the loop lives on the step's own stream: no joins per step
@@ -132,6 +134,8 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
             recs.append((loss, step.last_counts.clone(), labels.shape[0]))
             if topk:
                 mined.append(step.last_terms.clone())
+            if lovasz:
+                lov.append(step.last_terms[-1:].clone())
             if clip and step.micro == 0:                  # this call ended with an update
                 norms.append((step.last_grad_norm.clone(), step.last_clip_coef.clone()))
         if step.flush() and clip:                         # --accumulate: the batches left over at the end of the epoch
@@ -146,6 +150,8 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
         cs = torch.stack([r[1] for r in recs]).cpu().double()
         out.update(topk_kept_frac=float(cs[:, 5].sum() / cs[:, 4].sum()) if float(cs[:, 4].sum()) else 0.0,
                    topk_threshold_mean=float(torch.stack(mined)[:, 2].double().mean()))
+    if lov:                                               # a criterion with a Lovasz-Softmax term: its unweighted mean over the epoch
+        out.update(lovasz_mean=float(torch.cat(lov).double().mean()))
     if norms:                                             # --max_grad_norm: read back once per epoch, beside the losses
         nc = torch.stack([torch.stack(v) for v in norms]).cpu()
         out.update(grad_norm_mean=float(nc[:, 0].mean()), grad_norm_max=float(nc[:, 0].max()), clipped_frac=float((nc[:, 1] < 1).float().mean()))
@@ -379,7 +385,10 @@ def main(argv=None):
                          'work with all of them), and the compound criteria focal+dice / focal+jaccard / focal+tversky are available; '
                          'false: tversky on the fused step, dice / jaccard / focal on the autograd route')
     ap.add_argument('--loss_weights', type=float, nargs=2, default=[1.0, 1.0], metavar=('W_FOCAL', 'W_OVERLAP'),
-                    help='weights of the two terms of a compound --loss_function')
+                    help='weights of the two terms of a compound --loss_function (focal+lovasz: W_FOCAL W_LOVASZ)')
+    ap.add_argument('--lovasz_classes', default='present', choices=['present', 'all'],
+                    help='--loss_function lovasz / focal+lovasz: average the Lovasz-Softmax term over the classes present among the labelled '
+                         'pixels of the batch, or over all classes (Criterion(lovasz_classes=)); the epoch record gains train_lovasz_mean')
     ap.add_argument('--ignore_label', type=int, default=None, metavar='V',
                     help='--fused_step true only: pixels labelled V (0..255, e.g. 255 for nodata / unlabelled) are left out of the loss, '
                          'its gradient and the accuracy / precision / recall / F1 (Criterion(ignore_index=V))')
@@ -454,10 +463,12 @@ def main(argv=None):
     opt = ap.parse_args(argv)
     for k in ('band_ids', 'band_means', 'band_stds'):
         setattr(opt, k, meta.get(k))
-    from .criterion import COMPOUND
+    from .criterion import COMPOUND, LOVASZ_NAMES
     if opt.loss_function in COMPOUND and not opt.fused_step:
         raise SystemExit(f'--loss_function {opt.loss_function} is a compound criterion of the fused step: add --fused_step true')
-    if opt.loss_function not in ('tversky', 'dice', 'jaccard', 'focal') + COMPOUND:
+    if opt.loss_function in LOVASZ_NAMES and not opt.fused_step:
+        raise SystemExit(f'--loss_function {opt.loss_function} is a criterion of the fused step (the Lovasz-Softmax term): add --fused_step true')
+    if opt.loss_function not in ('tversky', 'dice', 'jaccard', 'focal') + COMPOUND + LOVASZ_NAMES:
         raise SystemExit(f'--loss_function {opt.loss_function}: the reference offers bce / focal / dice / jaccard / tversky '
                          f"(utils/helpers.py:288-314); its bce branch cannot run on BiDateNet's logits and is not built")
     if 'focal' in opt.loss_function.split('+') and opt.focal_gamma is None:
@@ -472,7 +483,7 @@ def main(argv=None):
     if opt.loss_topk is not None:
         if 'focal' not in opt.loss_function.split('+'):
             raise SystemExit(f'--loss_topk {opt.loss_topk} ranks the focal term: --loss_function {opt.loss_function} has none '
-                             f'(focal, focal+dice, focal+jaccard, focal+tversky)')
+                             f'(focal, focal+dice, focal+jaccard, focal+tversky, focal+lovasz)')
         if not opt.fused_step:
             raise SystemExit(f'--loss_topk {opt.loss_topk} is built into the criterion of the fused step: add --fused_step true')
         if not 0.0 < opt.loss_topk <= 1.0:

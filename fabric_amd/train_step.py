@@ -53,6 +53,9 @@ class TrainStep:
         A Criterion with a topk (bdn_criterion_topk, hard-pixel mining) averages the focal term over the hardest fraction of the valid
         pixels of the batch: `last_counts` has six entries, {.., valid, K}, `last_terms` three, {overlap, focal, the K-th largest focal
         term}.  The selection is per call: per micro-step with accumulate > 1, per rank in a data-parallel run.
+        A Criterion with a w_lovasz (bdn_lovasz_softmax, the names 'lovasz' and 'focal+lovasz': gamma 0, cross-entropy + Lovasz) adds the
+        Lovasz-Softmax term behind that entry point: `last_terms` gains one trailing element, the unweighted term; `last_counts` keeps its
+        shape.  The sort is per call: per micro-step with accumulate > 1, per rank in a data-parallel run.
 
         bn: 'batch' (BatchNorm on batch statistics, running statistics updated: a training step) or 'frozen' (BatchNorm on its running
         statistics, which are constants: running_mean / running_var / num_batches_tracked are not touched, and the conv biases in

@@ -530,6 +530,42 @@ int bdn_criterion_topk(const float* logits, const uint8_t* labels, int ignore_la
                        float* loss, float* terms, int32_t* counts, float* dlogits, float* pixel_terms, uint8_t* kept,
                        int B, int ncls, int H, int W, void* stream);
 
+/* ---- the Lovasz-Softmax term (Berman, Rahman Triki, Blaschko, CVPR 2018; the reference has none) ----
+ * The loss that optimises the Jaccard index itself, batch level (the paper's per_image = False): an add-on term of the criterion of a run,
+ * utils/helpers.py:303-312, the loss selection it extends.  ignore_label: -1 (no pixel is ignored) or a byte value 0..255.
+ *   Valid       the n pixels whose label is not ignore_label.  A valid label >= ncls is foreground of no class.
+ *   Errors      p = softmax(logits) per pixel as bdn_criterion forms it; for class c  fg = (label == c), G = sum fg, err = |fg - p_c| in
+ *               float32 with the sign bit clear.
+ *   Order       per class the valid pixels by err descending, through bdn_criterion_topk's key of the bit pattern u of err:
+ *                   key = u ^ 0x80000000 when the sign bit is clear, ~u otherwise
+ *               (monotone, +inf on top, every bit pattern -- NaN included -- has a place).  Among equal keys the lower linear pixel index
+ *               (b*H + y)*W + x comes first.  A full stable sort (LSD radix, four passes of eight bits, on the complemented key), not an
+ *               approximation: the order is a permutation of the valid pixels whatever the logits hold.
+ *   Coefficient at 0-based rank r with c_prev foreground pixels at ranks < r:  I = G - c_prev, U = G + r - c_prev,
+ *                   g = 1 / U at a foreground pixel, I / (U (U + 1)) elsewhere, 1 when U = 0 (first pixel of a class with G = 0)
+ *               -- the increment J_r - J_(r-1) of the paper's lovasz_grad, formed from the integers in float64.
+ *   Term        L_c = sum_r err_r g_r in double in a fixed order; term = the mean of L_c over the included classes: those with G > 0
+ *               (classes_all = 0, the paper's 'present') or every class (classes_all = 1).  No included class, or n = 0: term 0, gradient 0.
+ *   Gradient    the order is a constant.  With m included classes  q_c = (fg ? -g : +g) / m  (0 for a class that is not included) and
+ *               dterm / dlogit_j = p_j (q_j - sum_c q_c p_c).  Exactly 0.0f at an ignored pixel, none of whose logits is read.
+ *   accumulate  0: *loss = weight * term, dlogits = weight * dterm.  1: *loss += weight * term and dlogits += weight * dterm, every element
+ *               read and written once by one thread, the product rounded to float32 before the add, ignored pixels untouched -- how the
+ *               term joins a criterion that has already run on the same stream.
+ *   term        NULL or f32[1]: the unweighted value.  dlogits: NULL launches no gradient pass.
+ *   pixel_errors NULL or f32[ncls][B*H*W]: err (0 at ignored pixels).  ranks: NULL or int32[ncls][B*H*W]: the 0-based rank, -1 at ignored.
+ * Two classes are sorted separately: p_0 and p_1 are rounded separately in float32, so the two error arrays differ.
+ * Launches, whatever the data: one preparation pass (softmax, keys, the first digit histogram), per radix pass a tile histogram (not
+ * the first), a scan and a stable scatter, then the foreground count per tile, its scan, the coefficient pass, the finish and the gradient
+ * pass: 17 (16 without dlogits).  Integer histogram atomics in LDS only -- no float atomics, no host read-back, no kernel waits for another
+ * block; the caller never clears the workspace: the same bits on every run, whatever the workspace held.
+ * ws: bdn_lovasz_workspace_bytes() bytes (0 for an invalid shape), 16-byte aligned: 16 bytes per pixel and class (two key and two payload
+ * buffers; the coefficients reuse one) plus 1 KB per class and 4096 pixels.  weight >= 0; ncls in 2..8; B*H*W < 2^31.
+ * Data-parallel: each rank sorts its own batch. */
+size_t bdn_lovasz_workspace_bytes(int B, int ncls, int H, int W);
+int bdn_lovasz_softmax(const float* logits, const uint8_t* labels, int ignore_label, int classes_all, float weight, int accumulate,
+                       void* ws, float* loss, float* term, float* dlogits, float* pixel_errors, int32_t* ranks,
+                       int B, int ncls, int H, int W, void* stream);
+
 /* ---- OSCD ingest: utils/dataloaders.py:86-111 city_loader, per band ----
  * dst [H][W] f32 (one plane of a [C][H][W] scene) = cv2.resize((src - mean) / std, (W, H)) with cv2's default float
  * INTER_LINEAR sampling (half-pixel centres, border weights (1,0)).  src: [hs][ws] uint16 (src_is_f32 = 0) or f32, on
