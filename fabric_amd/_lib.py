@@ -140,6 +140,14 @@ SIGNATURES = {
     'bdn_cc_compact': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     'bdn_cc_filter': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'bdn_cc_stats': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'bdn_edt_workspace_bytes': (_sz, [_i, _i, _i]),
+    'bdn_edt': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_boundary_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'bdn_boundary_loss': (_i, [_vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_signed_distance_workspace_bytes': (_sz, [_i, _i, _i]),
+    'bdn_signed_distance': (_i, [_vp, _i, _i, _f, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_boundary_mask': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp]),
+    'bdn_boundary_score': (_i, [_vp, _vp, C.c_longlong, _vp, _i, _i, _vp]),
 }
 
 

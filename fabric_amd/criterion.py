@@ -30,32 +30,56 @@ over every class ('all'); the order is a constant for the gradient, as torch.sor
 the unweighted Lovasz value; counts keep their shape.  With the Lovasz term alone the counts are those of confusion_counts().  It composes
 with ignore_index and topk.  Data-parallel: each rank sorts its own batch; with gradient accumulation the sort is per micro-step.
 w_lovasz=0 is the criterion as it was, call for call.
+
+w_boundary (>= 0) adds w_boundary * the boundary term of Kervadec et al. (MIDL 2019) -- ``bdn_boundary_loss``, a second add-on pass through
+the same seam (behind the Lovasz one if both are present): per image and included class the signed distance phi to the contour of the
+class is computed on the device each call (exact integer distance transforms of the label patch, the ignored pixels out of both site
+sets), and the term is the mean over the valid pixels of sum_c softmax_c * phi_c; phi is a constant for the gradient.  boundary_classes
+'foreground' (classes 1.., the paper's choice for the binary case) or 'all'; boundary_max_dist clamps phi to [-d, d].  The term can be
+negative, and it is meant to be ramped up beside a region loss: the weight is passed per call, so ``criterion.w_boundary = x`` between
+two steps takes effect at the next one (it must have been > 0 at construction, which decides the buffers).  `terms` gains one trailing
+element, after the Lovasz one.  With add-on terms alone the counts are those of confusion_counts().  Data-parallel: each rank normalises by
+its own valid count; with gradient accumulation the maps are computed per micro-step.  w_boundary=0 is the criterion as it was.
 """
 
 NAMES = ('tversky', 'dice', 'jaccard', 'focal', 'focal+tversky', 'focal+dice', 'focal+jaccard')
 COMPOUND = tuple(n for n in NAMES if '+' in n)
 LOVASZ_NAMES = ('lovasz', 'focal+lovasz')
 LOVASZ_CLASSES = {'present': 0, 'all': 1}
+BOUNDARY_CLASSES = {'foreground': 0, 'all': 1}
 REDUCE = {'columns': 0, 'image': 1}
 
 
 class Criterion:
     def __init__(self, w_overlap=1.0, alpha=0.5, beta=0.5, eps=1e-7, reduce='columns', w_focal=0.0, gamma=0.0, class_alpha=None,
-                 size_average=True, ignore_index=None, topk=None, w_lovasz=0.0, lovasz_classes='present'):
+                 size_average=True, ignore_index=None, topk=None, w_lovasz=0.0, lovasz_classes='present', w_boundary=0.0,
+                 boundary_classes='foreground', boundary_max_dist=None):
         """reduce: 'columns' -- what the reference's train.py gets from [B,H,W] labels, sums over dims (0,2), one ratio per (class,
         column) -- or 'image', dims (0,2,3), one ratio per class ([B,1,H,W] labels there).  class_alpha: None, a float a (class
         weights [a, 1 - a], utils/metrics.py:13-14) or a sequence of ncls class weights.  ignore_index: None -- every pixel carries a label,
         bdn_criterion -- or the label byte (0..255) of the pixels to leave out (module docstring), bdn_criterion_masked.  topk: None, or the fraction 0 < f <= 1 of the valid pixels the
         focal term is averaged over, the hardest first (module docstring), bdn_criterion_topk.  w_lovasz: the weight of the Lovasz-Softmax term,
-        lovasz_classes 'present' or 'all' (module docstring), bdn_lovasz_softmax."""
-        w_overlap, w_focal, w_lovasz = float(w_overlap), float(w_focal), float(w_lovasz)
+        lovasz_classes 'present' or 'all' (module docstring), bdn_lovasz_softmax.  w_boundary: the weight of the boundary term,
+        boundary_classes 'foreground' or 'all', boundary_max_dist None or the clamp of the signed distance in pixels (module docstring),
+        bdn_boundary_loss."""
+        w_overlap, w_focal, w_lovasz, w_boundary = float(w_overlap), float(w_focal), float(w_lovasz), float(w_boundary)
+        if not w_boundary >= 0.0:
+            raise ValueError(f'criterion weights must be >= 0, got w_boundary={w_boundary}')
+        if boundary_classes not in BOUNDARY_CLASSES:
+            raise ValueError(f"boundary_classes must be 'foreground' or 'all', got {boundary_classes!r}")
+        if boundary_max_dist is not None:
+            if isinstance(boundary_max_dist, bool) or not isinstance(boundary_max_dist, (int, float)) or not 0.0 < float(boundary_max_dist) < float('inf'):
+                raise ValueError(f'boundary_max_dist must be None or a positive number of pixels, got {boundary_max_dist!r}')
+            boundary_max_dist = float(boundary_max_dist)
+        self._w_boundary, self._boundary_pass = w_boundary, w_boundary > 0.0
+        self.boundary_classes, self.boundary_max_dist = boundary_classes, boundary_max_dist
         if not (w_overlap >= 0.0 and w_focal >= 0.0):
             raise ValueError(f'criterion weights must be >= 0, got w_overlap={w_overlap}, w_focal={w_focal}')
         if not w_lovasz >= 0.0:
             raise ValueError(f'criterion weights must be >= 0, got w_lovasz={w_lovasz}')
         if lovasz_classes not in LOVASZ_CLASSES:
             raise ValueError(f"lovasz_classes must be 'present' or 'all', got {lovasz_classes!r}")
-        if w_overlap == 0.0 and w_focal == 0.0 and w_lovasz == 0.0:
+        if w_overlap == 0.0 and w_focal == 0.0 and w_lovasz == 0.0 and w_boundary == 0.0:
             raise ValueError('criterion weights are both zero')
         self.w_lovasz, self.lovasz_classes = w_lovasz, lovasz_classes
         if reduce not in REDUCE:
@@ -87,18 +111,41 @@ class Criterion:
         self.topk = topk
         self._alpha_dev = {}
 
+    @property
+    def has_boundary(self):
+        """True when the criterion was built with w_boundary > 0: the boundary pass runs, `terms` carries its value, the workspace its part."""
+        return self._boundary_pass
+
+    @property
+    def w_boundary(self):
+        return self._w_boundary
+
+    @w_boundary.setter
+    def w_boundary(self, value):
+        """The weight goes to bdn_boundary_loss with every call: a loop may ramp it between steps.  Whether the pass exists (workspace,
+        terms) was decided at construction."""
+        value = float(value)
+        if not value >= 0.0:
+            raise ValueError(f'criterion weights must be >= 0, got w_boundary={value}')
+        if value > 0.0 and not self.has_boundary:
+            raise ValueError('w_boundary can only be changed on a criterion built with w_boundary > 0')
+        self._w_boundary = value
+
     @classmethod
     def parse(cls, name, tversky_alpha=0.5, tversky_beta=0.5, focal_gamma=None, focal_alpha=None, weights=(1, 1), eps=1e-7,
-              reduce='columns', ignore_index=None, topk=None, lovasz_classes='present'):
+              reduce='columns', ignore_index=None, topk=None, lovasz_classes='present', w_boundary=0.0, boundary_classes='foreground',
+              boundary_max_dist=None):
         """The criterion of a --loss_function name.  weights = (w_focal, w_overlap), used by the compound names only.  topk: a name with a
         focal term only (Criterion raises ValueError otherwise).  LOVASZ_NAMES: 'lovasz' is the Lovasz-Softmax term alone; 'focal+lovasz'
-        has weights = (w_focal, w_lovasz) and, with focal_gamma None, gamma 0: cross-entropy + Lovasz, the usual pairing."""
+        has weights = (w_focal, w_lovasz) and, with focal_gamma None, gamma 0: cross-entropy + Lovasz, the usual pairing.  w_boundary,
+        boundary_classes, boundary_max_dist: the boundary term beside any name (--boundary_weight)."""
+        bnd = dict(w_boundary=w_boundary, boundary_classes=boundary_classes, boundary_max_dist=boundary_max_dist)      # validated at any weight
         if name in LOVASZ_NAMES:
             focal = name != 'lovasz'
             w_focal, w_lovasz = (float(weights[0]), float(weights[1])) if focal else (0.0, 1.0)
             return cls(0.0, eps=eps, reduce=reduce, w_focal=w_focal, gamma=(focal_gamma or 0.0) if focal else 0.0,
                        class_alpha=focal_alpha if focal else None, ignore_index=ignore_index, topk=topk, w_lovasz=w_lovasz,
-                       lovasz_classes=lovasz_classes)
+                       lovasz_classes=lovasz_classes, **bnd)
         if name not in NAMES:
             raise ValueError(f'unknown criterion {name!r}: one of {", ".join(NAMES + LOVASZ_NAMES)}')
         parts = name.split('+')
@@ -109,14 +156,16 @@ class Criterion:
         coef = {'tversky': (tversky_alpha, tversky_beta, eps), 'dice': (0.5, 0.5, 0.5 * eps), 'jaccard': (1.0, 1.0, eps),
                 None: (0.5, 0.5, eps)}[overlap]
         return cls(w_overlap, *coef, reduce=reduce, w_focal=w_focal, gamma=focal_gamma if focal else 0.0,
-                   class_alpha=focal_alpha if focal else None, ignore_index=ignore_index, topk=topk)
+                   class_alpha=focal_alpha if focal else None, ignore_index=ignore_index, topk=topk, **bnd)
 
     def __repr__(self):
         return (f'Criterion(w_overlap={self.w_overlap}, alpha={self.alpha}, beta={self.beta}, eps={self.eps}, reduce={self.reduce!r}, '
                 f'w_focal={self.w_focal}, gamma={self.gamma}, class_alpha={self.class_alpha}, size_average={self.size_average}'
                 + (f', ignore_index={self.ignore_index}' if self.ignore_index is not None else '')
                 + (f', topk={self.topk}' if self.topk is not None else '')
-                + (f', w_lovasz={self.w_lovasz}, lovasz_classes={self.lovasz_classes!r}' if self.w_lovasz else '') + ')')
+                + (f', w_lovasz={self.w_lovasz}, lovasz_classes={self.lovasz_classes!r}' if self.w_lovasz else '')
+                + (f', w_boundary={self.w_boundary}, boundary_classes={self.boundary_classes!r}, boundary_max_dist={self.boundary_max_dist}'
+                   if self.has_boundary else '') + ')')
 
     # ------------------------------------------------------------------ device side
     def _class_alpha(self, device, ncls):
@@ -148,8 +197,14 @@ class Criterion:
         if self.w_lovasz:
             n = self._lovasz_offset(n) + _lib.load().bdn_lovasz_workspace_bytes(B, C, H, W)
             n_terms += 1
-        # the Lovasz term alone: the entry point that counts writes no term, so the terms in front of the last one are zeroed here, once
-        terms = (torch.zeros if self._lovasz_only else torch.empty)(n_terms, dtype=torch.float32, device=device)
+        if self.has_boundary:
+            nb = _lib.load().bdn_boundary_workspace_bytes(B, C, H, W)
+            if nb == 0:
+                raise RuntimeError(f'fabric_amd: the boundary term takes H, W <= 32767 and 2*C*B*H*W < 2^31, got {tuple(shape)}')
+            n = self._lovasz_offset(n) + nb
+            n_terms += 1
+        # add-on terms alone: the entry point that counts writes no term, so the terms in front of theirs are zeroed here, once
+        terms = (torch.zeros if self._addon_only else torch.empty)(n_terms, dtype=torch.float32, device=device)
         return (torch.empty((n + 15) // 16 * 16, dtype=torch.uint8, device=device), torch.empty((), dtype=torch.float32, device=device), terms,
                 torch.empty(6 if self.topk is not None else 5 if masked else 4, dtype=torch.int32, device=device))
 
@@ -160,17 +215,31 @@ class Criterion:
 
     @property
     def _lovasz_only(self):
-        return self.w_lovasz > 0.0 and self.w_overlap == 0.0 and self.w_focal == 0.0
+        return self.w_lovasz > 0.0 and self.w_overlap == 0.0 and self.w_focal == 0.0 and not self.has_boundary
+
+    @property
+    def _addon_only(self):
+        """Only add-on terms (Lovasz, boundary): the overlap / focal entry point runs for the counts alone."""
+        return (self.w_lovasz > 0.0 or self.has_boundary) and self.w_overlap == 0.0 and self.w_focal == 0.0
 
     def _lovasz(self, logits, labels, ws, n_base, loss, terms, dlogits, accumulate, pixel_errors, ranks):
         from . import _lib
         B, C, H, W = logits.shape
         _lib.call('bdn_lovasz_softmax', logits.data_ptr(), labels.data_ptr(), -1 if self.ignore_index is None else self.ignore_index,
                   LOVASZ_CLASSES[self.lovasz_classes], self.w_lovasz, int(accumulate), ws.data_ptr() + self._lovasz_offset(n_base),
-                  loss.data_ptr(), terms.data_ptr() + 4 * (terms.numel() - 1), _lib.ptr(dlogits), _lib.ptr(pixel_errors), _lib.ptr(ranks),
-                  B, C, H, W, _lib.stream_ptr())
+                  loss.data_ptr(), terms.data_ptr() + 4 * (terms.numel() - 1 - int(self.has_boundary)), _lib.ptr(dlogits),
+                  _lib.ptr(pixel_errors), _lib.ptr(ranks), B, C, H, W, _lib.stream_ptr())
 
-    def evaluate(self, logits, labels, want_grad=True, out=None, pixel_terms=None, kept=None, pixel_errors=None, ranks=None):
+    def _boundary(self, logits, labels, ws, n_front, loss, terms, dlogits, accumulate, phi):
+        """bdn_boundary_loss behind n_front bytes of the workspace (the other entry points'), its term the last of `terms`."""
+        from . import _lib
+        B, C, H, W = logits.shape
+        _lib.call('bdn_boundary_loss', logits.data_ptr(), labels.data_ptr(), -1 if self.ignore_index is None else self.ignore_index,
+                  BOUNDARY_CLASSES[self.boundary_classes], self.boundary_max_dist or 0.0, self._w_boundary, int(accumulate),
+                  ws.data_ptr() + self._lovasz_offset(n_front), loss.data_ptr(), terms.data_ptr() + 4 * (terms.numel() - 1), _lib.ptr(dlogits),
+                  _lib.ptr(phi), B, C, H, W, _lib.stream_ptr())
+
+    def evaluate(self, logits, labels, want_grad=True, out=None, pixel_terms=None, kept=None, pixel_errors=None, ranks=None, phi=None):
         """-> (loss, terms, counts, dlogits) of float32 [B,C,H,W] logits and [B,H,W] or [B,1,H,W] class-index labels, on the current
         stream: loss a 0-dim tensor, terms f32[2] = the unweighted overlap and focal values, counts int32[4] = {TP, FP, FN, correct} of
         argmax(logits), dlogits = d loss / d logits (None without want_grad: no gradient pass is launched).  `out`: buffers() of this
@@ -182,7 +251,9 @@ class Criterion:
         point above runs as it always did, then bdn_lovasz_softmax adds its term to loss and dlogits on the same stream (the term alone:
         the counts of confusion_counts(), then bdn_lovasz_softmax writes loss and dlogits); terms[-1] is the unweighted Lovasz value;
         `pixel_errors` (contiguous float32, C*B*H*W) and `ranks` (contiguous int32, C*B*H*W) are optional caller tensors that receive
-        every class's errors and 0-based ranks (-1 at ignored pixels)."""
+        every class's errors and 0-based ranks (-1 at ignored pixels).  With w_boundary: bdn_boundary_loss runs last through the same seam;
+        terms[-1] is the unweighted boundary value (the Lovasz one, if present, is terms[-2]); `phi` (contiguous float32, C*B*H*W) is an
+        optional caller tensor that receives every class's signed distance (0 for a class that is not included)."""
         import torch
         from . import _lib
         if not logits.is_cuda:
@@ -198,18 +269,20 @@ class Criterion:
         ws, loss, terms, counts = out if out is not None else self.buffers(logits.shape, logits.device)
         dlogits = torch.empty_like(logits) if want_grad else None
         ca = self._class_alpha(logits.device, C)
-        if not self.w_lovasz:
-            if pixel_errors is not None or ranks is not None:
-                raise RuntimeError('fabric_amd: pixel_errors / ranks are outputs of a criterion with w_lovasz')
+        if not self.w_lovasz and (pixel_errors is not None or ranks is not None):
+            raise RuntimeError('fabric_amd: pixel_errors / ranks are outputs of a criterion with w_lovasz')
+        if not self.has_boundary and phi is not None:
+            raise RuntimeError('fabric_amd: phi is an output of a criterion with w_boundary')
+        if not self.w_lovasz and not self.has_boundary:
             return self._evaluate_base(logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept)
-        for t, dt, what in ((pixel_errors, torch.float32, 'pixel_errors'), (ranks, torch.int32, 'ranks')):
+        for t, dt, what in ((pixel_errors, torch.float32, 'pixel_errors'), (ranks, torch.int32, 'ranks'), (phi, torch.float32, 'phi')):
             if t is not None and (t.device != logits.device or t.dtype != dt or t.numel() != C * B * H * W or not t.is_contiguous()):
                 raise RuntimeError(f'fabric_amd: {what} must be a contiguous {dt} tensor of {C * B * H * W} elements on {logits.device}')
         masked = self.ignore_index is not None
         query = 'bdn_criterion_topk_workspace_bytes' if self.topk is not None else \
             'bdn_criterion_masked_workspace_bytes' if masked else 'bdn_criterion_workspace_bytes'
         n_base = getattr(_lib.load(), query)(B, C, H, W, REDUCE[self.reduce])
-        if self._lovasz_only:                              # the counts: the statistics and finish passes of the overlap loss, no gradient pass
+        if self._addon_only:                               # the counts: the statistics and finish passes of the overlap loss, no gradient pass
             if pixel_terms is not None or kept is not None:
                 raise RuntimeError('fabric_amd: pixel_terms / kept are outputs of a criterion with topk')
             if masked:
@@ -221,7 +294,12 @@ class Criterion:
                           0.0, None, 1, ws.data_ptr(), loss.data_ptr(), None, counts.data_ptr(), None, B, C, H, W, _lib.stream_ptr())
         else:
             self._evaluate_base(logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept)
-        self._lovasz(logits, labels, ws, n_base, loss, terms, dlogits, not self._lovasz_only, pixel_errors, ranks)
+        accumulate, n_front = not self._addon_only, n_base    # the first add-on pass of an add-on-only criterion writes, every other one adds
+        if self.w_lovasz:
+            self._lovasz(logits, labels, ws, n_base, loss, terms, dlogits, accumulate, pixel_errors, ranks)
+            accumulate, n_front = True, self._lovasz_offset(n_base) + _lib.load().bdn_lovasz_workspace_bytes(B, C, H, W)
+        if self.has_boundary:
+            self._boundary(logits, labels, ws, n_front, loss, terms, dlogits, accumulate, phi)
         return loss, terms, counts, dlogits
 
     def _evaluate_base(self, logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept):

@@ -11,6 +11,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --ignore_label 255
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --loss_topk 0.25
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+lovasz --focal_gamma 0       # cross-entropy + Lovasz-Softmax
+    python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --boundary_weight 0.01      # + the boundary term
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --ema_decay 0.999        # validate and save the averaged weights
     python -m fabric_amd.train --metadata metadata.json --val_curve_bins 1024 --scene_stride 64 --scene_threshold val      # best-F1 threshold, AP
 
@@ -122,10 +123,12 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
     from .device_loader import DevicePatchLoader
     from .input_pipeline import DeviceFeeder
     step.model.train()
-    recs, norms, mined, lov = [], [], [], []
+    recs, norms, mined, lov, bnd = [], [], [], [], []
     clip = step.max_grad_norm is not None
     topk = getattr(step.criterion, 'topk', None) is not None      # hard-pixel mining: K and the threshold of every batch, read back with the losses
-    lovasz = getattr(step.criterion, 'w_lovasz', 0.0) > 0.0        # the Lovasz-Softmax term of every batch (terms[-1]), read back with the losses
+    boundary = step.criterion is not None and step.criterion.has_boundary    # the boundary term of every batch (terms[-1]), read back with the losses
+    lovasz = getattr(step.criterion, 'w_lovasz', 0.0) > 0.0        # the Lovasz-Softmax term of every batch (the last term in front of the boundary one)
+    lov_at = -2 if boundary else -1
     if not isinstance(loader, DevicePatchLoader):
         feeder = feeder or DeviceFeeder(dev)
     with torch.cuda.stream(step.stream()):                # the loop lives on the step's own stream: no joins per step
@@ -135,7 +138,9 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
             if topk:
                 mined.append(step.last_terms.clone())
             if lovasz:
-                lov.append(step.last_terms[-1:].clone())
+                lov.append(step.last_terms[lov_at:][:1].clone())
+            if boundary:
+                bnd.append(step.last_terms[-1:].clone())
             if clip and step.micro == 0:                  # this call ended with an update
                 norms.append((step.last_grad_norm.clone(), step.last_clip_coef.clone()))
         if step.flush() and clip:                         # --accumulate: the batches left over at the end of the epoch
@@ -152,6 +157,8 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
                    topk_threshold_mean=float(torch.stack(mined)[:, 2].double().mean()))
     if lov:                                               # a criterion with a Lovasz-Softmax term: its unweighted mean over the epoch
         out.update(lovasz_mean=float(torch.cat(lov).double().mean()))
+    if bnd:                                               # --boundary_weight: the unweighted boundary term's mean over the epoch
+        out.update(boundary_mean=float(torch.cat(bnd).double().mean()))
     if norms:                                             # --max_grad_norm: read back once per epoch, beside the losses
         nc = torch.stack([torch.stack(v) for v in norms]).cpu()
         out.update(grad_norm_mean=float(nc[:, 0].mean()), grad_norm_max=float(nc[:, 0].max()), clipped_frac=float((nc[:, 1] < 1).float().mean()))
@@ -366,6 +373,33 @@ def check_object_flags(scene_min_area, scene_objects, scene_connectivity, scene_
     return scene_min_area if scene_min_area > 0 else None
 
 
+def check_boundary_flags(boundary_weight, boundary_classes, boundary_max_dist, fused_step, scene_boundary_tol, scene_stride):
+    """--boundary_weight / --boundary_classes / --boundary_max_dist / --fused_step and --scene_boundary_tol / --scene_stride together,
+    without a device: returns the tolerance for boundary_scores (None: the scene line stays as it is); raises ValueError with the reason
+    otherwise."""
+    if boundary_weight is not None:
+        if not boundary_weight > 0.0:
+            raise ValueError(f'--boundary_weight {boundary_weight}: a weight > 0 (leave the flag out for no boundary term)')
+        if not fused_step:
+            raise ValueError(f'--boundary_weight {boundary_weight} is a term of the criterion of the fused step: add --fused_step true')
+    elif boundary_classes != 'foreground' or boundary_max_dist is not None:
+        raise ValueError('--boundary_classes / --boundary_max_dist shape a term that is not on: add --boundary_weight W')
+    if boundary_classes not in ('foreground', 'all'):
+        raise ValueError(f"--boundary_classes {boundary_classes}: 'foreground' or 'all'")
+    if boundary_max_dist is not None and not 0.0 < boundary_max_dist < float('inf'):
+        raise ValueError(f'--boundary_max_dist {boundary_max_dist}: a positive number of pixels')
+    if scene_boundary_tol is None:
+        return None
+    from .utils.distance import check_boundary_tolerance
+    try:
+        check_boundary_tolerance(scene_boundary_tol)
+    except ValueError as e:
+        raise ValueError(f'--scene_boundary_tol: {e}')
+    if scene_stride <= 0:
+        raise ValueError('--scene_boundary_tol scores the blended scene masks: add --scene_stride N > 0')
+    return scene_boundary_tol
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Training change detection network (HIP path)')
     for k, v in DEFAULTS.items():
@@ -389,6 +423,17 @@ def main(argv=None):
     ap.add_argument('--lovasz_classes', default='present', choices=['present', 'all'],
                     help='--loss_function lovasz / focal+lovasz: average the Lovasz-Softmax term over the classes present among the labelled '
                          'pixels of the batch, or over all classes (Criterion(lovasz_classes=)); the epoch record gains train_lovasz_mean')
+    ap.add_argument('--boundary_weight', type=float, default=None, metavar='W',
+                    help='--fused_step true only: adds W * the boundary term of Kervadec et al. (softmax weighted by the signed distance to the '
+                         'contour of the labels, computed on the device every step) to any --loss_function (Criterion(w_boundary=W)); the '
+                         'epoch record gains train_boundary_mean')
+    ap.add_argument('--boundary_classes', default='foreground', choices=['foreground', 'all'],
+                    help='--boundary_weight: the classes of the boundary term, 1.. (foreground) or every class')
+    ap.add_argument('--boundary_max_dist', type=float, default=None, metavar='D', help='--boundary_weight: clamp the signed distance to [-D, D] pixels')
+    ap.add_argument('--scene_boundary_tol', type=int, default=None, metavar='T',
+                    help='--scene_stride N > 0: the scene line gains boundary_precision, boundary_recall, boundary_f1 (boundary pixels within T '
+                         'pixels of the other contour), hausdorff and boundary_tol (boundary_scores on the mask that is written; --ignore_label '
+                         'pixels make no contour)')
     ap.add_argument('--ignore_label', type=int, default=None, metavar='V',
                     help='--fused_step true only: pixels labelled V (0..255, e.g. 255 for nodata / unlabelled) are left out of the loss, '
                          'its gradient and the accuracy / precision / recall / F1 (Criterion(ignore_index=V))')
@@ -488,6 +533,11 @@ def main(argv=None):
             raise SystemExit(f'--loss_topk {opt.loss_topk} is built into the criterion of the fused step: add --fused_step true')
         if not 0.0 < opt.loss_topk <= 1.0:
             raise SystemExit(f'--loss_topk {opt.loss_topk}: a fraction 0 < F <= 1')
+    try:
+        scene_boundary_tol = check_boundary_flags(opt.boundary_weight, opt.boundary_classes, opt.boundary_max_dist, opt.fused_step,
+                                                  opt.scene_boundary_tol, opt.scene_stride)
+    except ValueError as e:
+        raise SystemExit(str(e))
     step_criterion = None                                  # --fused_step true: ONE Criterion for the step and for validation
     if opt.fused_step:
         from .utils.helpers import criterion_from_opt
@@ -636,7 +686,8 @@ def main(argv=None):
                                   **({'ema_n_averaged': step.n_averaged} if averaging else {})}), flush=True)
             if scenes is not None and rank == 0:               # train.py:182-205: full validation images
                 _predict_scenes(model, scenes, val_cities, opt, epoch, va['best_threshold'] if scene_thr == 'val' else
-                                None if scene_thr == 'argmax' else scene_thr, min_area=scene_min_area)
+                                None if scene_thr == 'argmax' else scene_thr, min_area=scene_min_area,
+                                **({} if scene_boundary_tol is None else {'boundary_tol': scene_boundary_tol}))
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
                                   step.optimizer_state_dict() if fused else optimizer.state_dict(),
@@ -647,7 +698,7 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_area=None):
+def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_area=None, boundary_tol=None):
     """train.py:182-205: the full validation scenes of one epoch, written as PNG masks (and, blended, as probabilities with a scene F1 line).
     threshold (--scene_threshold): None = the argmax masks, else the masks are P(change) >= threshold.  With --val_curve_bins the scene
     line of every city comes from a ScoreCurve over its probabilities and label raster (the run's --ignore_label left out), on the device:
@@ -656,7 +707,9 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
     min_area (--scene_min_area, from check_object_flags): the components of the mask below that many pixels are removed before the PNG is
     written and the pixel counts are taken.  With --scene_objects the objects are scored on the unfiltered mask by
     object_scores(mask, truth, ignore_index=--ignore_label, min_area=min_area): the ignore pixels are cut out BEFORE the areas are
-    measured, so a component held above min_area only by pixels inside the ignore region is no object, although the PNG keeps it."""
+    measured, so a component held above min_area only by pixels inside the ignore region is no object, although the PNG keeps it.
+    boundary_tol (--scene_boundary_tol, from check_boundary_flags): the scene line gains boundary_precision, boundary_recall, boundary_f1,
+    hausdorff and boundary_tol from boundary_scores(the mask that is written, truth, boundary_tol, ignore_index=--ignore_label)."""
     from .utils import ingest
     from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
     os.makedirs(opt.log_dir, exist_ok=True)
@@ -694,6 +747,11 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
                                                                'object_f1')})
             if min_area is not None or objects:
                 scene_counts[city]['min_area'] = min_area or 1
+            if boundary_tol is not None:
+                from .utils.distance import boundary_scores
+                truth = torch.as_tensor(scenes[city]['labels']).to(device=mask.device, dtype=torch.uint8).contiguous()
+                bs = boundary_scores(mask.contiguous(), truth, boundary_tol, 1, getattr(opt, 'ignore_label', None))
+                scene_counts[city].update({k: bs[k] for k in ('boundary_precision', 'boundary_recall', 'boundary_f1', 'hausdorff', 'boundary_tol')})
         else:
             mask = predict_scene(model, st[0], st[1], patch_size=opt.patch_size, batch_size=opt.batch_size)
         ingest.write_png_gray(os.path.join(opt.log_dir, f'{city}_epoch_{epoch}.png'), (mask * 255).cpu().numpy())

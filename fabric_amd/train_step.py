@@ -56,6 +56,9 @@ class TrainStep:
         A Criterion with a w_lovasz (bdn_lovasz_softmax, the names 'lovasz' and 'focal+lovasz': gamma 0, cross-entropy + Lovasz) adds the
         Lovasz-Softmax term behind that entry point: `last_terms` gains one trailing element, the unweighted term; `last_counts` keeps its
         shape.  The sort is per call: per micro-step with accumulate > 1, per rank in a data-parallel run.
+        A Criterion with a w_boundary (bdn_boundary_loss) adds the boundary term last: `last_terms[-1]` is its unweighted value (the
+        Lovasz one, if present, moves to [-2]).  The distance maps are computed per call -- per micro-step, per rank, each rank normalising
+        by its own valid count -- and the weight is read per call: `step.criterion.w_boundary = x` takes effect at the next step.
 
         bn: 'batch' (BatchNorm on batch statistics, running statistics updated: a training step) or 'frozen' (BatchNorm on its running
         statistics, which are constants: running_mean / running_var / num_batches_tracked are not touched, and the conv biases in

@@ -1,1 +1,2 @@
 from .objects import check_cc_args, component_table, label_components, object_scores, remove_small_objects  # noqa: F401
+from .distance import boundary_scores, check_edt_args, distance_transform_sq, signed_distance  # noqa: F401

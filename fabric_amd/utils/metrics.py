@@ -166,7 +166,8 @@ class CompoundLoss(nn.Module):
     """w_overlap * (dice | jaccard | Tversky) + w_focal * FocalLoss as one criterion (fabric_amd.criterion.Criterion, bdn_criterion):
     the module form for validation and the autograd route.  The criterion's `reduce` decides the overlap reduction, not the label
     rank.  A criterion with a topk (bdn_criterion_topk) runs here as any other: the selection is a constant for the gradient; so does one
-    with a w_lovasz (bdn_lovasz_softmax): the order is a constant for the gradient."""
+    with a w_lovasz (bdn_lovasz_softmax): the order is a constant for the gradient; and one with a w_boundary (bdn_boundary_loss): the
+    signed distance is a constant for the gradient, last_terms[-1] the unweighted boundary value."""
 
     def __init__(self, criterion):
         super(CompoundLoss, self).__init__()

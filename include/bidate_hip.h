@@ -772,6 +772,61 @@ int bdn_cc_filter(const uint8_t* src_mask, const int32_t* labels, const int32_t*
 int bdn_cc_stats(const int32_t* compact, int n_max, const uint8_t* other, int other_value, int other_exclude_value, int H, int W,
                  int32_t* table, void* stream);
 
+/* ---- exact squared Euclidean distance transform, the boundary loss and the boundary scores built on it.  They replace a device-to-host
+ * copy and scipy.ndimage.distance_transform_edt.  Rasters are [N][H][W] row-major uint8; 1 <= N, 1 <= H, W <= 32767 and N*H*W < 2^31, so
+ * every squared distance fits an int32.  Integer arithmetic only (the signed distance takes one correctly rounded square root of an integer: the float64 root rounded to float32);
+ * a fixed number of launches for a shape; no float atomics, no host read-back, no kernel waits for another block; the caller never
+ * clears a workspace: the same bits on every run, whatever the workspace held.  A null required pointer, a misaligned one, a value
+ * outside its range or a shape outside the limits is BDN_E_ARG before anything touches a device.
+ * bdn_edt: the N images are independent.  A pixel is valid unless valid_src is given and its byte there equals invalid_value; it is a site
+ *   if it is valid and its byte in src compares to site_value as site_equal says (1: ==, 0: !=).
+ *       out_d2[n][y][x] = min(limit, min over the sites (y', x') of image n of (y - y')^2 + (x - x')^2)
+ *   limit in 1..2^31-1; an image without a site gives limit everywhere, a site 0.  Two launches: per column the distance to the nearest
+ *   site of the column (one thread per column, a down and an up sweep), then per row the lower envelope of the parabolas
+ *   (x - x')^2 + g(x')^2 (Meijster, Roerdink, Hesselink 2000), one lane per row over the transposed column result: O(W) per row for every
+ *   input.  Rows up to 128 wide keep their stack in LDS, wider ones in the workspace.  ws: bdn_edt_workspace_bytes() bytes (0 for a shape
+ *   outside the limits), 16-byte aligned: 2 bytes per pixel, 6 for W > 128.
+ * bdn_boundary_loss: the boundary term of Kervadec et al. (MIDL 2019) on float32 NCHW logits and uint8 labels, an add-on pass with the
+ *   calling shape of bdn_lovasz_softmax.
+ *   Valid       the n pixels of the batch whose label is not ignore_label (-1: none is ignored).
+ *   Included    classes 1..ncls-1 (classes_all = 0, the paper's choice for the binary case) or every class (classes_all = 1).
+ *   Distance    per image and included class c, on the device each call: fg = valid and label == c, bg = valid and label != c (a valid
+ *               label >= ncls is foreground of no class);  phi_c = +sqrtf(d2 to the nearest fg pixel) at a bg pixel,
+ *               -(sqrtf(d2 to the nearest bg pixel) - 1) at an fg pixel, 0 at an ignored pixel, and 0 over an image without an fg or
+ *               without a bg pixel of the class (no contour) -- the paper's one_hot2dist with the ignored pixels out of both site sets.
+ *               max_dist > 0 clamps phi to [-max_dist, max_dist]; 0: no clamp.
+ *   Term        p = softmax(logits) as bdn_criterion forms it; term = (1/n) sum over valid pixels and included classes of p_c phi_c, in
+ *               double in a fixed order.  n = 0: term 0, gradient 0.  The term can be negative.
+ *   Gradient    phi is a constant; phi'_c = phi_c for an included class, 0 otherwise; dterm / dlogit_j = p_j (phi'_j - sum_c phi'_c p_c) / n.
+ *               Exactly 0.0f at an ignored pixel, none of whose logits is read.
+ *   accumulate, loss, term, dlogits = NULL: exactly as in bdn_lovasz_softmax.  phi_out: NULL or f32[ncls][B*H*W], 0 for a class that is
+ *               not included.
+ *   Five launches (four without dlogits): the two of the transform over 2 x included classes x B images, phi and the blocks' partial
+ *   sums, the finish, the gradient.  ws: bdn_boundary_workspace_bytes() bytes (0 for an invalid shape; sized for classes_all = 1),
+ *   16-byte aligned.  weight >= 0; max_dist >= 0; ncls in 2..8; 2*ncls*B*H*W < 2^31.  Data-parallel: each rank uses its own n.
+ * bdn_signed_distance: phi of one class cls (0..255) of [N][H][W] labels, as defined above, without logits: three launches.
+ * bdn_boundary_mask: out[i] (uint8) = 1 iff pixel i is valid, src[i] == fg_value and one of its 4-neighbours inside the image is valid
+ *   and not fg_value, else 0 (valid as in bdn_edt): valid & fg & ~binary_erosion(fg | ~valid, cross, border_value = 1).  The image edge
+ *   and the invalid region make no contour.  One [H][W] raster; out must not alias src.
+ * bdn_boundary_score: bnd uint8 [2][H][W] = the boundary sets of the prediction and of the truth, d2 int32 [2][H][W] = bdn_edt of bnd with
+ *   site_value 1 and limit 2^31-1.  out int64[6] = {n_pred, n_true, pred_hit, true_hit, hd2_pred_to_true, hd2_true_to_pred}: the set
+ *   sizes, the boundary pixels whose d2 to the other set is <= tol2, and the largest d2 of a set's pixels to the other set (-1 if either
+ *   set is empty).  Integer block sums, one 64-bit atomicAdd per block and count, integer atomicMax; out is cleared by the call.
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+size_t bdn_edt_workspace_bytes(int N, int H, int W);
+int bdn_edt(const uint8_t* src, int site_value, int site_equal, const uint8_t* valid_src, int invalid_value, int limit, int32_t* out_d2,
+            void* ws, int N, int H, int W, void* stream);
+size_t bdn_boundary_workspace_bytes(int B, int ncls, int H, int W);
+int bdn_boundary_loss(const float* logits, const uint8_t* labels, int ignore_label, int classes_all, float max_dist, float weight,
+                      int accumulate, void* ws, float* loss, float* term, float* dlogits, float* phi_out, int B, int ncls, int H, int W,
+                      void* stream);
+size_t bdn_signed_distance_workspace_bytes(int N, int H, int W);
+int bdn_signed_distance(const uint8_t* labels, int cls, int ignore_label, float max_dist, void* ws, float* phi, int N, int H, int W,
+                        void* stream);
+int bdn_boundary_mask(const uint8_t* src, int fg_value, const uint8_t* valid_src, int invalid_value, uint8_t* out, int H, int W,
+                      void* stream);
+int bdn_boundary_score(const uint8_t* bnd, const int32_t* d2, long long tol2, long long* out, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
