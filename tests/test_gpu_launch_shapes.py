@@ -13,6 +13,7 @@ LAUNCH_SHAPES_REPORT=<file> appends each row's worst error (in units of its bar)
 """
 import json
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -122,12 +123,9 @@ def _finalize_and_check(name, stats, nt, z64, G, ipg, H, W, Cout, fp32):
 
 
 # ------------------------------------------------------------------ forward + statistics (+ finalize)
-@pytest.mark.parametrize('r', _rows('fwd'), ids=_rid)
-@guarded
-def test_forward_and_statistics(r):
-    _assert_variant(r)
+def forward_case(r):
+    """Inputs and float64 reference of a 'fwd' row (host tensors only)."""
     N, H, W, C0, C1, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg, r.prec
-    dt, td = lc.DTYPE[p], (torch.bfloat16 if p == 'bf16' else torch.float32)
     G = N // ipg
     x0 = rnd(p, _rand((N, C0, H, W), 1))
     x1 = rnd(p, _rand((N, C1, H, W), 2)) if C1 else None
@@ -137,22 +135,46 @@ def test_forward_and_statistics(r):
     a0 = bnrelu_ref(p, x0, bn_in, ipg) if r.bnrelu else x0
     a = torch.cat([a0, x1], 1) if C1 else a0
     ref = F.conv2d(a.double(), w.double(), b.double(), padding=1)
-    wf, _ = pack_w(p, w, C0 + C1)
-    d0, d1 = to_nhwc(p, x0), (to_nhwc(p, x1) if C1 else None)
-    out = guard.full((N, H, W, Cout), NAN, dtype=td)
-    nt = _lib.load().bdn_conv3x3_num_mtiles(N, H, W, Cout, ipg)
-    stats = guard.full((nt, 2, Cout), NAN)
-    dbn, db = (dev(bn_in) if r.bnrelu else None), dev(b)
-    _lib.call('bdn_conv3x3', dt, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1, IN_BNRELU if r.bnrelu else IN_PLAIN,
-              dbn.data_ptr() if r.bnrelu else None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(), stats.data_ptr(), N, H, W, Cout, st())
+    return SimpleNamespace(x0=x0, x1=x1, w=w, b=b, bn_in=bn_in, ref=ref)
+
+
+def forward_launch(r, c, d0, d1, out, stats, N=None, ipg=None):
+    """bdn_conv3x3 of a 'fwd' row on device operands (N / ipg: those of the launch when they are not the row's)."""
+    N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
+    wf, _ = pack_w(r.prec, c.w, r.C0 + r.C1)
+    dbn, db = (dev(c.bn_in) if r.bnrelu else None), dev(c.b)
+    _lib.call('bdn_conv3x3', lc.DTYPE[r.prec], d0.data_ptr(), r.C0, d1.data_ptr() if r.C1 else None, r.C1,
+              IN_BNRELU if r.bnrelu else IN_PLAIN, dbn.data_ptr() if r.bnrelu else None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
+              stats.data_ptr(), N, r.H, r.W, r.Cout, st())
     torch.cuda.synchronize()
-    check(f'{_rid(r)} out', from_nhwc(out), ref, p)
+
+
+def forward_compare(r, c, out, stats, finalize=True):
+    """Output and tile partials of a 'fwd' launch at the row's N against the float64 reference (+ bdn_bn_finalize on the partials)."""
+    G, p, nt = r.N // r.ipg, r.prec, stats.shape[0]
+    check(f'{_rid(r)} out', from_nhwc(out), c.ref, p)
     # per-group totals of the tile partials (every row written: NaN-filled) against the exact sums
-    s = stats.cpu().double().reshape(G, nt // G, 2, Cout).sum(1)
-    for g, zg in enumerate(_grp(ref, G)):
+    s = stats.cpu().double().reshape(G, nt // G, 2, r.Cout).sum(1)
+    for g, zg in enumerate(_grp(c.ref, G)):
         check(f'{_rid(r)} sum g{g}', s[g, 0], zg.sum((0, 2, 3)), 'fp32', tol=1e-5 if p == 'fp32' else 1e-4)
         check(f'{_rid(r)} sumsq g{g}', s[g, 1], (zg * zg).sum((0, 2, 3)), 'fp32', tol=1e-5 if p == 'fp32' else 1e-4)
-    _finalize_and_check(_rid(r), stats, nt, ref, G, ipg, H, W, Cout, p == 'fp32')
+    if finalize:
+        _finalize_and_check(_rid(r), stats, nt, c.ref, G, r.ipg, r.H, r.W, r.Cout, p == 'fp32')
+
+
+@pytest.mark.parametrize('r', _rows('fwd'), ids=_rid)
+@guarded
+def test_forward_and_statistics(r):
+    _assert_variant(r)
+    p = r.prec
+    td = torch.bfloat16 if p == 'bf16' else torch.float32
+    c = forward_case(r)
+    d0, d1 = to_nhwc(p, c.x0), (to_nhwc(p, c.x1) if r.C1 else None)
+    out = guard.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td)
+    nt = _lib.load().bdn_conv3x3_num_mtiles(r.N, r.H, r.W, r.Cout, r.ipg)
+    stats = guard.full((nt, 2, r.Cout), NAN)
+    forward_launch(r, c, d0, d1, out, stats)
+    forward_compare(r, c, out, stats)
 
 
 # ------------------------------------------------------------------ data gradient: plain, with fused statistics, BatchNorm backward on load
@@ -160,8 +182,26 @@ def _dgrad_setup(r, seed=11):
     p = r.prec
     dz = rnd(p, _rand((r.N, r.C0, r.H, r.W), seed))
     w = rnd(p, _rand((r.C0, r.Cout, 3, 3), seed + 1, 0.05))          # the layer: Cout -> C0 channels; its data gradient C0 -> Cout
-    _, wd = pack_w(p, w, r.Cout)
-    return dz, w, wd
+    return dz, w
+
+
+def dgrad_case(r):
+    """Inputs and float64 reference of a 'dgrad' row."""
+    dz, w = _dgrad_setup(r)
+    ref = torch.nn.grad.conv2d_input((r.N, r.Cout, r.H, r.W), w.double(), dz.double(), padding=1)
+    return SimpleNamespace(dz=dz, w=w, ref=ref)
+
+
+def dgrad_launch(r, c, ddz, out, N=None, ipg=None):
+    N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
+    _, wd = pack_w(r.prec, c.w, r.Cout)
+    _lib.call('bdn_conv3x3', lc.DTYPE[r.prec], ddz.data_ptr(), r.C0, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None, out.data_ptr(), None,
+              N, r.H, r.W, r.Cout, st())
+    torch.cuda.synchronize()
+
+
+def dgrad_compare(r, c, out):
+    check(f'{_rid(r)} dA', from_nhwc(out), c.ref, r.prec)
 
 
 @pytest.mark.parametrize('r', _rows('dgrad'), ids=_rid)
@@ -169,15 +209,11 @@ def _dgrad_setup(r, seed=11):
 def test_data_gradient(r):
     _assert_variant(r)
     p = r.prec
-    dt, td = lc.DTYPE[p], (torch.bfloat16 if p == 'bf16' else torch.float32)
-    dz, w, wd = _dgrad_setup(r)
-    ref = torch.nn.grad.conv2d_input((r.N, r.Cout, r.H, r.W), w.double(), dz.double(), padding=1)
+    td = torch.bfloat16 if p == 'bf16' else torch.float32
+    c = dgrad_case(r)
     out = guard.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td)
-    ddz = to_nhwc(p, dz)
-    _lib.call('bdn_conv3x3', dt, ddz.data_ptr(), r.C0, None, 0, IN_PLAIN, None, r.ipg, wd.data_ptr(), None, out.data_ptr(), None,
-              r.N, r.H, r.W, r.Cout, st())
-    torch.cuda.synchronize()
-    check(f'{_rid(r)} dA', from_nhwc(out), ref, p)
+    dgrad_launch(r, c, to_nhwc(p, c.dz), out)
+    dgrad_compare(r, c, out)
 
 
 def _bs_reference(g_stored, zprev, G):
@@ -194,39 +230,55 @@ def _check_bs(name, part, nt, refs, G, Cout):
         check(f'{name} sum g*z g{g}', s[g, 1], s1, 'fp32', tol=1e-5)
 
 
+def dgrad_bs_case(r):
+    """Inputs and float64 reference of a 'dgrad_bs' row."""
+    G = r.N // r.ipg
+    dz, w = _dgrad_setup(r, 51)
+    ref = torch.nn.grad.conv2d_input((r.N, r.Cout, r.H, r.W), w.double(), dz.double(), padding=1)
+    zprev = rnd(r.prec, _rand((r.N, r.Cout, r.H, r.W), 53))
+    bnp = _bn_from(zprev, G, 54)
+    return SimpleNamespace(dz=dz, w=w, ref=ref, zprev=zprev, bnp=bnp)
+
+
+def dgrad_bs_launch(r, c, ddz, zp_d, plain, dA, part, N=None, ipg=None):
+    """The plain data gradient into `plain`, bdn_conv3x3_dgrad_bs into dA / part."""
+    N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
+    dt = lc.DTYPE[r.prec]
+    _, wd = pack_w(r.prec, c.w, r.Cout)
+    bnp_d = dev(c.bnp)
+    _lib.call('bdn_conv3x3', dt, ddz.data_ptr(), r.C0, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None, plain.data_ptr(), None,
+              N, r.H, r.W, r.Cout, st())
+    _lib.call('bdn_conv3x3_dgrad_bs', dt, ddz.data_ptr(), r.C0, wd.data_ptr(), dA.data_ptr(), zp_d.data_ptr(), bnp_d.data_ptr(), ipg,
+              part.data_ptr(), N, r.H, r.W, r.Cout, st())
+    torch.cuda.synchronize()
+
+
+def dgrad_bs_compare(r, c, plain, dA, part):
+    G = r.N // r.ipg
+    check(f'{_rid(r)} dA', from_nhwc(plain), c.ref, r.prec)
+    assert_masked(_rid(r), from_nhwc(dA), from_nhwc(plain), preact(c.zprev, c.bnp, r.ipg))
+    _check_bs(_rid(r), part, part.shape[0], _bs_reference(from_nhwc(dA), c.zprev, G), G, r.Cout)
+
+
 @pytest.mark.parametrize('r', _rows('dgrad_bs'), ids=_rid)
 @guarded
 def test_data_gradient_with_fused_statistics(r):
     _assert_variant(r)
     p = r.prec
-    dt, td = lc.DTYPE[p], (torch.bfloat16 if p == 'bf16' else torch.float32)
-    G = r.N // r.ipg
-    dz, w, wd = _dgrad_setup(r, 51)
-    ref = torch.nn.grad.conv2d_input((r.N, r.Cout, r.H, r.W), w.double(), dz.double(), padding=1)
-    zprev = rnd(p, _rand((r.N, r.Cout, r.H, r.W), 53))
-    bnp = _bn_from(zprev, G, 54)
-    ddz, zp_d, bnp_d = to_nhwc(p, dz), to_nhwc(p, zprev), dev(bnp)
+    td = torch.bfloat16 if p == 'bf16' else torch.float32
+    c = dgrad_bs_case(r)
+    ddz, zp_d = to_nhwc(p, c.dz), to_nhwc(p, c.zprev)
     plain = guard.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td)
-    _lib.call('bdn_conv3x3', dt, ddz.data_ptr(), r.C0, None, 0, IN_PLAIN, None, r.ipg, wd.data_ptr(), None, plain.data_ptr(), None,
-              r.N, r.H, r.W, r.Cout, st())
     nt = _lib.load().bdn_conv3x3_num_mtiles(r.N, r.H, r.W, r.Cout, r.ipg)
     part = guard.full((nt, 2, r.Cout), NAN)
     dA = guard.full_like(plain, NAN)
-    _lib.call('bdn_conv3x3_dgrad_bs', dt, ddz.data_ptr(), r.C0, wd.data_ptr(), dA.data_ptr(), zp_d.data_ptr(), bnp_d.data_ptr(), r.ipg,
-              part.data_ptr(), r.N, r.H, r.W, r.Cout, st())
-    torch.cuda.synchronize()
-    check(f'{_rid(r)} dA', from_nhwc(plain), ref, p)
-    assert_masked(_rid(r), from_nhwc(dA), from_nhwc(plain), preact(zprev, bnp, r.ipg))
-    _check_bs(_rid(r), part, nt, _bs_reference(from_nhwc(dA), zprev, G), G, r.Cout)
+    dgrad_bs_launch(r, c, ddz, zp_d, plain, dA, part)
+    dgrad_bs_compare(r, c, plain, dA, part)
 
 
-@pytest.mark.parametrize('r', _rows('dgrad_bb'), ids=_rid)
-@guarded
-def test_data_gradient_with_bn_backward_on_load(r):
-    """bdn_conv3x3_dgrad_bb against an independent float64 computation: the BatchNorm backward dz = scale (g - s0/M - xhat s1/M) with the
-    sums of g in float64, then conv2d_input of bf16(dz); and against the two-kernel path (bdn_bn_bwd + the plain data gradient)."""
-    _assert_variant(r)
-    lib = _lib.load()
+def dgrad_bb_case(r):
+    """Inputs and the independent float64 computation of a 'dgrad_bb' row: the BatchNorm backward dz = scale (g - s0/M - xhat s1/M) with the
+    sums of g in float64, then conv2d_input of bf16(dz)."""
     N, H, W, C0, Cout, ipg = r.N, r.H, r.W, r.C0, r.Cout, r.ipg
     G, M = N // ipg, ipg * H * W
     z = rnd('bf16', _rand((N, C0, H, W), 62))
@@ -234,9 +286,6 @@ def test_data_gradient_with_bn_backward_on_load(r):
     pre = preact(z, bn, ipg)
     dA = rnd('bf16', _rand((N, C0, H, W), 61)) * (pre > 1e-4)          # g: masked, and zero at the switching point whichever way it rounds
     w = rnd('bf16', _rand((C0, Cout, 3, 3), 64, 0.05))
-    _, wd = pack_w('bf16', w, Cout)
-    dA_d, z_d, bn_d = to_nhwc('bf16', dA), to_nhwc('bf16', z), dev(bn)
-    # float64 reference
     dz64 = torch.empty(N, C0, H, W, dtype=torch.float64)
     sums64 = torch.empty(G, 2, C0, dtype=torch.float64)
     for g in range(G):
@@ -247,6 +296,46 @@ def test_data_gradient_with_bn_backward_on_load(r):
         sums64[g, 0], sums64[g, 1] = s0, s1
         dz64[sl] = scale * (gg - s0[None, :, None, None] / M - xhat * s1[None, :, None, None] / M)
     ref = torch.nn.grad.conv2d_input((N, Cout, H, W), w.double(), dz64.to(torch.bfloat16).double(), padding=1)
+    zprev = rnd('bf16', _rand((N, Cout, H, W), 65))
+    bnp = _bn_from(zprev, G, 66)
+    return SimpleNamespace(z=z, bn=bn, dA=dA, w=w, dz64=dz64, sums64=sums64, ref=ref, zprev=zprev, bnp=bnp)
+
+
+def dgrad_bb_launch(r, c, wd, dA_d, z_d, bn_d, sums, zp_d, out, dz, outm, part, N=None, ipg=None):
+    """bdn_conv3x3_dgrad_bb without (out, dz) and with (outm, part) the producing layer's statistics; `sums` is an input.  out = None or
+    outm = None leaves that launch out."""
+    N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
+    C0 = r.C0
+    if out is not None:
+        _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
+                  out.data_ptr(), None, None, None, dz.data_ptr(), N, r.H, r.W, r.Cout, st())
+    if outm is not None:
+        bnp_d = dev(c.bnp)
+        _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
+                  outm.data_ptr(), zp_d.data_ptr(), bnp_d.data_ptr(), part.data_ptr(), None, N, r.H, r.W, r.Cout, st())
+    torch.cuda.synchronize()
+
+
+def dgrad_bb_compare(r, c, out, dz, outm, part):
+    name, G = _rid(r), r.N // r.ipg
+    check(f'{name} dz', from_nhwc(dz), c.dz64, 'bf16')
+    check(f'{name} dA_prev', from_nhwc(out), c.ref, 'bf16')
+    assert_masked(name, from_nhwc(outm), from_nhwc(out), preact(c.zprev, c.bnp, r.ipg))
+    _check_bs(name, part, part.shape[0], _bs_reference(from_nhwc(outm), c.zprev, G), G, r.Cout)
+
+
+@pytest.mark.parametrize('r', _rows('dgrad_bb'), ids=_rid)
+@guarded
+def test_data_gradient_with_bn_backward_on_load(r):
+    """bdn_conv3x3_dgrad_bb against an independent float64 computation: the BatchNorm backward dz = scale (g - s0/M - xhat s1/M) with the
+    sums of g in float64, then conv2d_input of bf16(dz); and against the two-kernel path (bdn_bn_bwd + the plain data gradient)."""
+    _assert_variant(r)
+    lib = _lib.load()
+    N, H, W, C0, Cout, ipg = r.N, r.H, r.W, r.C0, r.Cout, r.ipg
+    G = N // ipg
+    c = dgrad_bb_case(r)
+    _, wd = pack_w('bf16', c.w, Cout)
+    dA_d, z_d, bn_d = to_nhwc('bf16', c.dA), to_nhwc('bf16', c.z), dev(c.bn)
     # two-kernel path: its sums feed the fused kernel
     ws = guard.empty(lib.bdn_bn_bwd_workspace_bytes(BDN_BF16, N, H, W, C0, ipg) // 4)
     sums = guard.full((G, 2, C0), NAN)
@@ -258,25 +347,16 @@ def test_data_gradient_with_bn_backward_on_load(r):
     _lib.call('bdn_conv3x3', BDN_BF16, dz_two.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, wd.data_ptr(), None, out_two.data_ptr(), None,
               N, H, W, Cout, st())
     # fused: without and with the producing layer's statistics
-    zprev = rnd('bf16', _rand((N, Cout, H, W), 65))
-    bnp = _bn_from(zprev, G, 66)
-    zp_d, bnp_d = to_nhwc('bf16', zprev), dev(bnp)
+    zp_d = to_nhwc('bf16', c.zprev)
     nt = lib.bdn_conv3x3_num_mtiles(N, H, W, Cout, ipg)
     part = guard.full((nt, 2, Cout), NAN)
     out = guard.full((N, H, W, Cout), NAN, dtype=torch.bfloat16)
     dz = guard.full((N, H, W, C0), NAN, dtype=torch.bfloat16)
-    _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
-              out.data_ptr(), None, None, None, dz.data_ptr(), N, H, W, Cout, st())
     outm = guard.full_like(out, NAN)
-    _lib.call('bdn_conv3x3_dgrad_bb', BDN_BF16, dA_d.data_ptr(), C0, z_d.data_ptr(), bn_d.data_ptr(), sums.data_ptr(), ipg, wd.data_ptr(),
-              outm.data_ptr(), zp_d.data_ptr(), bnp_d.data_ptr(), part.data_ptr(), None, N, H, W, Cout, st())
-    torch.cuda.synchronize()
+    dgrad_bb_launch(r, c, wd, dA_d, z_d, bn_d, sums, zp_d, out, dz, outm, part)
     name = _rid(r)
-    check(f'{name} sums', sums.cpu(), sums64, 'fp32', tol=1e-5)
-    check(f'{name} dz', from_nhwc(dz), dz64, 'bf16')
-    check(f'{name} dA_prev', from_nhwc(out), ref, 'bf16')
-    assert_masked(name, from_nhwc(outm), from_nhwc(out), preact(zprev, bnp, ipg))
-    _check_bs(name, part, nt, _bs_reference(from_nhwc(outm), zprev, G), G, Cout)
+    check(f'{name} sums', sums.cpu(), c.sums64, 'fp32', tol=1e-5)
+    dgrad_bb_compare(r, c, out, dz, outm, part)
     # the two-kernel path: dz equal or one bf16 step apart, the data gradient within the kernel bar of each other
     assert (dz.float() - dz_two.float()).abs().max() <= 2.0 ** -7 * dz_two.float().abs().max()
     assert (dz == dz_two).float().mean().item() > 0.9
@@ -308,9 +388,21 @@ def test_split_product_convolution(r):
     """bf16x3 (three terms: the float32 product to ~2^-16) and bf16x2 (a_hi w_hi + a_lo w_hi = a times the filter rounded to bf16) on the
     split operand (bdn_conv3x3) and on the float32 operand (bdn_conv3x3_x3src, BatchNorm+ReLU on load), with statistics."""
     _assert_variant(r)
-    lib = _lib.load()
     N, H, W, C0, Cout, ipg = r.N, r.H, r.W, r.C0, r.Cout, r.ipg
-    dt, G = lc.DTYPE[r.prec], N // ipg
+    c = x3_case(r)
+    nt = _lib.load().bdn_conv3x3_num_mtiles_ex(lc.DTYPE[r.prec], N, H, W, C0, Cout, ipg)
+    out = guard.full((N, H, W, Cout), NAN)
+    stats = guard.full((nt, 2, Cout), NAN) if r.stats else None
+    sp_out = guard.full((N, H, W, 2 * C0), NAN, dtype=torch.bfloat16) if r.op == 'x3src' and r.stats else None
+    xin = _split(c.x, ipg) if r.op == 'x3' else to_nhwc('fp32', c.x)
+    x3_launch(r, c, xin, out, stats, sp_out)
+    x3_compare(r, c, out, stats, sp_out)
+
+
+def x3_case(r):
+    """Inputs and float64 reference of an 'x3' / 'x3src' row."""
+    N, H, W, C0, Cout, ipg = r.N, r.H, r.W, r.C0, r.Cout, r.ipg
+    G = N // ipg
     x = _rand((N, C0, H, W), 311)
     w = _rand((Cout, C0, 3, 3), 312, (2.0 / (9 * C0)) ** 0.5)
     b = _rand((Cout,), 313, 0.1)
@@ -318,32 +410,38 @@ def test_split_product_convolution(r):
     a = bnrelu_ref('fp32', x, bn, ipg) if r.bnrelu else x
     wr = w if r.prec == 'bf16x3' else w.to(torch.bfloat16).float()
     ref = F.conv2d(a.double(), wr.double(), b.double(), padding=1)
-    wf = _x3_weights(w)
-    nt = lib.bdn_conv3x3_num_mtiles_ex(dt, N, H, W, C0, Cout, ipg)
-    out = guard.full((N, H, W, Cout), NAN)
-    stats = guard.full((nt, 2, Cout), NAN) if r.stats else None
-    sp_out = None
-    db = dev(b)
+    return SimpleNamespace(x=x, w=w, b=b, bn=bn, a=a, ref=ref)
+
+
+def x3_launch(r, c, xin, out, stats, sp_out, N=None, ipg=None):
+    """'x3': bdn_conv3x3 on the split operand `xin`; 'x3src': bdn_conv3x3_x3src on the float32 operand `xin`."""
+    N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
+    dt, C0 = lc.DTYPE[r.prec], r.C0
+    wf = _x3_weights(c.w)
+    db = dev(c.b)
     if r.op == 'x3':
-        xs = _split(x, ipg)
-        _lib.call('bdn_conv3x3', dt, xs.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
-                  stats.data_ptr(), N, H, W, Cout, st())
+        _lib.call('bdn_conv3x3', dt, xin.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
+                  stats.data_ptr(), N, r.H, r.W, r.Cout, st())
     else:
-        sp_out = guard.full((N, H, W, 2 * C0), NAN, dtype=torch.bfloat16) if r.stats else None
-        xd, dbn = to_nhwc('fp32', x), (dev(bn) if r.bnrelu else None)
-        _lib.call('bdn_conv3x3_x3src', dt, xd.data_ptr(), C0, IN_BNRELU if r.bnrelu else IN_PLAIN,
+        dbn = dev(c.bn) if r.bnrelu else None
+        _lib.call('bdn_conv3x3_x3src', dt, xin.data_ptr(), C0, IN_BNRELU if r.bnrelu else IN_PLAIN,
                   dbn.data_ptr() if r.bnrelu else None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
-                  stats.data_ptr() if r.stats else None, sp_out.data_ptr() if r.stats else None, N, H, W, Cout, st())
+                  stats.data_ptr() if r.stats else None, sp_out.data_ptr() if r.stats else None, N, r.H, r.W, r.Cout, st())
     torch.cuda.synchronize()
-    check(f'{_rid(r)} out', from_nhwc(out), ref, 'x3')
+
+
+def x3_compare(r, c, out, stats, sp_out):
+    G, C0, Cout = r.N // r.ipg, r.C0, r.Cout
+    check(f'{_rid(r)} out', from_nhwc(out), c.ref, 'x3')
     if r.stats:
+        nt = stats.shape[0]
         s = stats.cpu().double().reshape(G, nt // G, 2, Cout).sum(1)
-        for g, zg in enumerate(_grp(ref, G)):
+        for g, zg in enumerate(_grp(c.ref, G)):
             check(f'{_rid(r)} sum g{g}', s[g, 0], zg.sum((0, 2, 3)), 'x3')
             check(f'{_rid(r)} sumsq g{g}', s[g, 1], (zg * zg).sum((0, 2, 3)), 'x3')
     if sp_out is not None:                      # the split operand left for the weight gradient: hi + lo reproduces relu(bn(x))
         rec = (sp_out[..., :C0].float() + sp_out[..., C0:].float()).cpu().permute(0, 3, 1, 2)
-        check(f'{_rid(r)} split operand', rec, a.double(), 'x3', tol=2e-5)
+        check(f'{_rid(r)} split operand', rec, c.a.double(), 'x3', tol=2e-5)
 
 
 # ------------------------------------------------------------------ eval epilogue
@@ -355,8 +453,7 @@ def _eval_inputs(r, seed):
     sc, sh = _rand((r.Cout,), seed + 3).abs() + 0.5, _rand((r.Cout,), seed + 4, 0.3)
     a = torch.cat([x0, x1], 1) if r.C1 else x0
     act = torch.relu(F.conv2d(a.double(), w.double(), None, padding=1) * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
-    wf, _ = pack_w(p, w, r.C0 + r.C1)
-    return x0, x1, wf, dev(sc), dev(sh), act
+    return x0, x1, w, sc, sh, act
 
 
 def _pool64(t):
@@ -369,44 +466,74 @@ def test_eval_stage(r):
     """Eval-mode launches (conv -> folded BatchNorm -> ReLU in the epilogue): the stored activation / date product / pooled maps / logits."""
     _assert_variant(r)
     p = r.prec
-    dt, td = lc.DTYPE[p], (torch.bfloat16 if p == 'bf16' else torch.float32)
-    N, H, W, Cout = r.N, r.H, r.W, r.Cout
-    x0, x1, wf, dsc, dsh, act = _eval_inputs(r, 401)
-    d0, d1 = to_nhwc(p, x0), (to_nhwc(p, x1) if r.C1 else None)
-    name = _rid(r)
+    c = eval_case(r)
+    d0, d1 = to_nhwc(p, c.x0), (to_nhwc(p, c.x1) if r.C1 else None)
+    outs = eval_outputs(r, r.N)
+    eval_launch(r, c, d0, d1, outs)
+    eval_compare(r, c, outs)
+
+
+EVAL_NCLS = 2
+
+
+def eval_case(r):
+    """Inputs and float64 reference of an 'eval' / 'eval_pair' / 'eval_cls' row (host tensors; the filter image is packed at the launch)."""
+    x0, x1, w, sc, sh, act = _eval_inputs(r, 401)
+    c = SimpleNamespace(x0=x0, x1=x1, w=w, sc=sc, sh=sh, act=act)
+    if r.op == 'eval_cls':
+        c.cw, c.cb = _rand((EVAL_NCLS, r.Cout), 409, 0.2), _rand((EVAL_NCLS,), 410, 0.1)
+    return c
+
+
+def eval_outputs(r, N, born=False):
+    """The NaN-filled outputs of an eval launch of N images (eval_pair: N pairs), by name (born: left as allocated, every byte 0xFF)."""
+    td = torch.bfloat16 if r.prec == 'bf16' else torch.float32
+    H, W, Cout = r.H, r.W, r.Cout
+
+    def nan(shape, dtype=torch.float32):
+        return guard.empty(shape, dtype=dtype) if born else guard.full(shape, NAN, dtype=dtype)
     if r.op == 'eval':
-        out = guard.full((N, H, W, Cout), NAN, dtype=td)
-        pool = guard.full((N, H // 2, W // 2, Cout), NAN, dtype=td)
+        return {'out': nan((N, H, W, Cout), td), 'pool': nan((N, H // 2, W // 2, Cout), td)}
+    if r.op == 'eval_pair':
+        return {'f': nan((N, H, W, Cout), td), 'pool': nan((2 * N, H // 2, W // 2, Cout), td)}
+    return {'a_out': nan((N, H, W, Cout), td), 'logits': nan((N, EVAL_NCLS, H, W)), 'mask': guard.full((N, H, W), 255, dtype=torch.uint8)}
+
+
+def eval_launch(r, c, d0, d1, o, N=None):
+    N = r.N if N is None else N
+    dt, H, W, Cout = lc.DTYPE[r.prec], r.H, r.W, r.Cout
+    wf, _ = pack_w(r.prec, c.w, r.C0 + r.C1)
+    dsc, dsh = dev(c.sc), dev(c.sh)
+    if r.op == 'eval':
         _lib.call('bdn_conv3x3_eval', dt, d0.data_ptr(), r.C0, d1.data_ptr() if r.C1 else None, r.C1, wf.data_ptr(),
-                  dsc.data_ptr(), dsh.data_ptr(), out.data_ptr(), None, pool.data_ptr(), N, H, W, Cout, st())
-        torch.cuda.synchronize()
-        check(f'{name} activation', from_nhwc(out), act, p)
-        check(f'{name} pooled', from_nhwc(pool), _pool64(act), p)
+                  dsc.data_ptr(), dsh.data_ptr(), o['out'].data_ptr(), None, o['pool'].data_ptr(), N, H, W, Cout, st())
     elif r.op == 'eval_pair':
-        B = N
-        f = guard.full((B, H, W, Cout), NAN, dtype=td)
-        pool = guard.full((2 * B, H // 2, W // 2, Cout), NAN, dtype=td)
-        _lib.call('bdn_conv3x3_eval_pair', dt, d0.data_ptr(), r.C0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), f.data_ptr(),
-                  pool.data_ptr(), B, H, W, Cout, st())
-        torch.cuda.synchronize()
-        # the product of two rounded activations, rounded again: two bf16 roundings in the chain
-        check(f'{name} date product', from_nhwc(f), act[:B] * act[B:], p, rel=2.0 ** -7)
-        check(f'{name} pooled', from_nhwc(pool), _pool64(act), p)
+        _lib.call('bdn_conv3x3_eval_pair', dt, d0.data_ptr(), r.C0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), o['f'].data_ptr(),
+                  o['pool'].data_ptr(), N, H, W, Cout, st())
     else:
-        ncls = 2
-        cw, cb = _rand((ncls, Cout), 409, 0.2), _rand((ncls,), 410, 0.1)
-        dcw, dcb = dev(cw), dev(cb)
-        a_out = guard.full((N, H, W, Cout), NAN, dtype=td)
-        logits = guard.full((N, ncls, H, W), NAN)
-        mask = guard.full((N, H, W), 255, dtype=torch.uint8)
-        _lib.call('bdn_conv3x3_eval_cls', dt, d0.data_ptr(), r.C0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), a_out.data_ptr(),
-                  dcw.data_ptr(), dcb.data_ptr(), ncls, logits.data_ptr(), mask.data_ptr(), None, 0, 0, N, H, W, Cout, st())
-        torch.cuda.synchronize()
-        a_dev = from_nhwc(a_out)
+        dcw, dcb = dev(c.cw), dev(c.cb)
+        _lib.call('bdn_conv3x3_eval_cls', dt, d0.data_ptr(), r.C0, wf.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), o['a_out'].data_ptr(),
+                  dcw.data_ptr(), dcb.data_ptr(), EVAL_NCLS, o['logits'].data_ptr(), o['mask'].data_ptr(), None, 0, 0, N, H, W, Cout, st())
+    torch.cuda.synchronize()
+
+
+def eval_compare(r, c, o):
+    p, name, act = r.prec, _rid(r), c.act
+    if r.op == 'eval':
+        check(f'{name} activation', from_nhwc(o['out']), act, p)
+        check(f'{name} pooled', from_nhwc(o['pool']), _pool64(act), p)
+    elif r.op == 'eval_pair':
+        B = r.N
+        # the product of two rounded activations, rounded again: two bf16 roundings in the chain
+        check(f'{name} date product', from_nhwc(o['f']), act[:B] * act[B:], p, rel=2.0 ** -7)
+        check(f'{name} pooled', from_nhwc(o['pool']), _pool64(act), p)
+    else:
+        logits = o['logits']
+        a_dev = from_nhwc(o['a_out'])
         check(f'{name} activation', a_dev, act, p)
-        lref = torch.einsum('nchw,kc->nkhw', a_dev.double(), cw.double()) + cb.double()[None, :, None, None]
+        lref = torch.einsum('nchw,kc->nkhw', a_dev.double(), c.cw.double()) + c.cb.double()[None, :, None, None]
         check(f'{name} logits (of the stored activation)', logits.cpu(), lref, 'fp32', tol=1e-5)
-        assert torch.equal(mask.cpu(), (logits[:, 1] > logits[:, 0]).to(torch.uint8).cpu())
+        assert torch.equal(o['mask'].cpu(), (logits[:, 1] > logits[:, 0]).to(torch.uint8).cpu())
 
 
 # ------------------------------------------------------------------ weight gradient at the production plan
@@ -418,13 +545,11 @@ def test_weight_gradient(r):
     run_weight_gradient(r)
 
 
-def run_weight_gradient(r, flags=3):
-    """The body of test_weight_gradient at plan flags `flags` (tests/test_gpu_bounds.py runs it at other plans and kernels)."""
-    lib = _lib.load()
+def weight_gradient_case(r):
+    """Inputs and float64 reference of a 'wgrad' row."""
     N, H, W, C0, C1, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg, r.prec
-    dt, G = lc.DTYPE[p], N // ipg
-    x3 = p in ('bf16x3', 'bf16x2')
-    sp = 'fp32' if x3 else p
+    G = N // ipg
+    sp = 'fp32' if p in ('bf16x3', 'bf16x2') else p
     x0 = rnd(sp, _rand((N, C0, H, W), 21))
     x1 = rnd(sp, _rand((N, C1, H, W), 22)) if C1 else None
     dz = rnd(sp, _rand((N, Cout, H, W), 23))
@@ -433,37 +558,52 @@ def run_weight_gradient(r, flags=3):
     a = torch.cat([a0, x1], 1) if C1 else a0
     dzr = dz.to(torch.bfloat16).float() if p == 'bf16x2' else dz          # two terms: dz_hi x [a_hi | a_lo]
     ref = torch.nn.grad.conv2d_weight(a.double(), (Cout, C0 + C1, 3, 3), dzr.double(), padding=1)
-    nb = lib.bdn_wgrad_workspace_bytes_ex(dt, N, H, W, Cout, C0, C1, ipg, IN_BNRELU if r.bnrelu else IN_PLAIN, flags)
+    return SimpleNamespace(x0=x0, x1=x1, dz=dz, bn_in=bn_in, ref=ref)
+
+
+def weight_gradient_launch(r, bn_in, ddz, d0, d1, part, dw, flags=3, N=None, ipg=None):
+    """bdn_conv3x3_wgrad_ex of a 'wgrad' row on device operands (bf16x3 / bf16x2: ddz and d0 are the split operands of bdn_split_pack)."""
+    N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
+    C0, C1, Cout, dt = r.C0, r.C1, r.Cout, lc.DTYPE[r.prec]
+    if r.prec in ('bf16x3', 'bf16x2'):
+        assert not r.bnrelu and not C1
+        _lib.call('bdn_conv3x3_wgrad_ex', dt, ddz.data_ptr(), Cout, d0.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg,
+                  part.data_ptr(), dw.data_ptr(), C0, N, r.H, r.W, flags, st())
+    else:
+        dbn = dev(bn_in) if r.bnrelu else None
+        _lib.call('bdn_conv3x3_wgrad_ex', dt, ddz.data_ptr(), Cout, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1,
+                  IN_BNRELU if r.bnrelu else IN_PLAIN, dbn.data_ptr() if r.bnrelu else None, ipg, part.data_ptr(), dw.data_ptr(), C0 + C1,
+                  N, r.H, r.W, flags, st())
+    torch.cuda.synchronize()
+
+
+def run_weight_gradient(r, flags=3):
+    """The body of test_weight_gradient at plan flags `flags` (tests/test_gpu_bounds.py runs it at other plans and kernels)."""
+    lib = _lib.load()
+    N, H, W, C0, C1, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg, r.prec
+    x3 = p in ('bf16x3', 'bf16x2')
+    c = weight_gradient_case(r)
+    nb = lib.bdn_wgrad_workspace_bytes_ex(lc.DTYPE[p], N, H, W, Cout, C0, C1, ipg, IN_BNRELU if r.bnrelu else IN_PLAIN, flags)
     assert flags != 3 or nb <= lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0 + C1, ipg)
     part = guard.empty(nb // 4)
     dw = guard.full((Cout, C0 + C1, 3, 3), NAN)
     if x3:
-        assert not r.bnrelu and not C1
-        sdz, sx = _split(dz, ipg), _split(x0, ipg)
-        _lib.call('bdn_conv3x3_wgrad_ex', dt, sdz.data_ptr(), Cout, sx.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg,
-                  part.data_ptr(), dw.data_ptr(), C0, N, H, W, flags, st())
+        ddz, d0, d1 = _split(c.dz, ipg), _split(c.x0, ipg), None
     else:
-        ddz, d0, d1 = to_nhwc(p, dz), to_nhwc(p, x0), (to_nhwc(p, x1) if C1 else None)
-        dbn = dev(bn_in) if r.bnrelu else None
-        _lib.call('bdn_conv3x3_wgrad_ex', dt, ddz.data_ptr(), Cout, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1,
-                  IN_BNRELU if r.bnrelu else IN_PLAIN, dbn.data_ptr() if r.bnrelu else None, ipg, part.data_ptr(), dw.data_ptr(), C0 + C1,
-                  N, H, W, flags, st())
-    torch.cuda.synchronize()
-    check(f'{_rid(r)} dW', dw, ref, 'x3' if x3 else 'fp32')
+        ddz, d0, d1 = to_nhwc(p, c.dz), to_nhwc(p, c.x0), (to_nhwc(p, c.x1) if C1 else None)
+    weight_gradient_launch(r, c.bn_in, ddz, d0, d1, part, dw, flags)
+    check(f'{_rid(r)} dW', dw, c.ref, 'x3' if x3 else 'fp32')
 
 
-@pytest.mark.parametrize('r', _rows('wgrad_bnbwd'), ids=_rid)
-@guarded
-def test_first_layer_weight_gradient(r):
-    """bdn_bn_bwd_finalize + bdn_conv3x3_wgrad_bnbwd (256-block plan, 16 split lanes) against float64: dz = scale (g - s0/M - xhat s1/M)
-    from the float64 sums (bf16: rounded to bf16 like the kernel's staging; bf16x2: dz rounded, x in full), then conv2d_weight."""
-    _assert_variant(r)
-    assert lc.reduce_lanes(r) == r.lanes
-    lib = _lib.load()
+FIRST_LDA, FIRST_CREAL = 80, 13
+
+
+def first_layer_case(r):
+    """Inputs, partial rows and float64 reference of a 'wgrad_bnbwd' row: dz = scale (g - s0/M - xhat s1/M) from the float64 sums (bf16:
+    rounded to bf16 like the kernel's staging; bf16x2: dz rounded, x in full), then conv2d_weight."""
     N, H, W, C0, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.Cout, r.ipg, r.prec
-    G, M, Creal, ldA = N // ipg, ipg * H * W, 13, 80
-    x3 = p != 'bf16'
-    sp = 'fp32' if x3 else 'bf16'
+    G, M, Creal, ldA = N // ipg, ipg * H * W, FIRST_CREAL, FIRST_LDA
+    sp = 'fp32' if p != 'bf16' else 'bf16'
     dA_full = rnd(sp, _rand((N, ldA, H, W), 301))
     z = rnd(sp, _rand((N, Cout, H, W), 302))
     x = rnd(sp, _rand((N, C0, H, W), 303))
@@ -489,21 +629,43 @@ def test_first_layer_weight_gradient(r):
         dz64[sl] = scale * (gm[sl] - s0[None, :, None, None] / M - xhat * s1[None, :, None, None] / M)
     dzr = dz64 if p == 'bf16x3' else dz64.to(torch.bfloat16).double()
     ref = torch.nn.grad.conv2d_weight(x[:, :Creal].double(), (Cout, Creal, 3, 3), dzr, padding=1)
+    return SimpleNamespace(dA_full=dA_full, z=z, x=x, bn=bn, part=part, rows=rows, ref=ref)
+
+
+def first_layer_launch(r, dA_d, z_d, bn_d, sums, xin, wpart, dw, N=None, ipg=None, ldA=FIRST_LDA):
+    """bdn_conv3x3_wgrad_bnbwd on device operands; dA_d [N,H,W,ldA] carries the layer's gradient in its first Cout channels."""
+    N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
+    _lib.call('bdn_conv3x3_wgrad_bnbwd', lc.DTYPE[r.prec], dA_d.data_ptr(), ldA, z_d.data_ptr(), bn_d.data_ptr(),
+              sums.data_ptr(), ipg, r.Cout, xin.data_ptr(), r.C0, wpart.data_ptr(), dw.data_ptr(), FIRST_CREAL, N, r.H, r.W, st())
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('r', _rows('wgrad_bnbwd'), ids=_rid)
+@guarded
+def test_first_layer_weight_gradient(r):
+    """bdn_bn_bwd_finalize + bdn_conv3x3_wgrad_bnbwd (256-block plan, 16 split lanes) against float64: dz = scale (g - s0/M - xhat s1/M)
+    from the float64 sums (bf16: rounded to bf16 like the kernel's staging; bf16x2: dz rounded, x in full), then conv2d_weight."""
+    _assert_variant(r)
+    assert lc.reduce_lanes(r) == r.lanes
+    lib = _lib.load()
+    N, H, W, C0, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.Cout, r.ipg, r.prec
+    G, Creal = N // ipg, FIRST_CREAL
+    x3 = p != 'bf16'
+    sp = 'fp32' if x3 else 'bf16'
+    c = first_layer_case(r)
     sums = guard.full((G, 2, Cout), NAN)
     dg, db = guard.empty(Cout), guard.empty(Cout)
-    bn_d, part_d = dev(bn), dev(part)
-    _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), G, Cout, part_d.data_ptr(), rows, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(),
+    bn_d, part_d = dev(c.bn), dev(c.part)
+    _lib.call('bdn_bn_bwd_finalize', bn_d.data_ptr(), G, Cout, part_d.data_ptr(), c.rows, 1, sums.data_ptr(), dg.data_ptr(), db.data_ptr(),
               None, st())
-    xin = _split(x, ipg) if x3 else to_nhwc('bf16', x)
+    xin = _split(c.x, ipg) if x3 else to_nhwc('bf16', c.x)
     wsz = max(lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0, ipg), lib.bdn_wgrad_workspace_bytes_ex(lc.DTYPE[p], N, H, W, Cout, C0, 0, ipg, IN_PLAIN, 3))
     wpart = guard.empty(wsz // 4)
     dw = guard.full((Cout, Creal, 3, 3), NAN)
-    dA_d, z_d = to_nhwc(sp, dA_full), to_nhwc(sp, z)
+    dA_d, z_d = to_nhwc(sp, c.dA_full), to_nhwc(sp, c.z)
     dA_d[..., Cout:] = NAN                               # the foreign channels of the wider dA: a read of them poisons the result
-    _lib.call('bdn_conv3x3_wgrad_bnbwd', lc.DTYPE[p], dA_d.data_ptr(), ldA, z_d.data_ptr(), bn_d.data_ptr(),
-              sums.data_ptr(), ipg, Cout, xin.data_ptr(), C0, wpart.data_ptr(), dw.data_ptr(), Creal, N, H, W, st())
-    torch.cuda.synchronize()
-    check(f'{_rid(r)} dW', dw, ref, 'x3' if x3 else 'fp32', tol=2e-4 if x3 else 1e-4)
+    first_layer_launch(r, dA_d, z_d, bn_d, sums, xin, wpart, dw)
+    check(f'{_rid(r)} dW', dw, c.ref, 'x3' if x3 else 'fp32', tol=2e-4 if x3 else 1e-4)
 
 
 # ------------------------------------------------------------------ statistics reductions on synthetic partials
