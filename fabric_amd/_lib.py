@@ -21,6 +21,7 @@ def wg_flags(phases=3, kernel=0, blocks=0):
 
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 _hf = C.POINTER(C.c_float)          # a HOST float array (floats() below), where a void* would be taken for a device pointer
+_hi = C.POINTER(C.c_int32)          # a HOST int32 array (host_int32() below)
 
 # name -> (restype, argtypes); mirrors include/bidate_hip.h one to one
 SIGNATURES = {
@@ -115,6 +116,8 @@ SIGNATURES = {
     'bdn_blend_stitch': (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'bdn_blend_finalize': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'bdn_sample_patches': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'bdn_sample_patches_aug': (_i, [_vp, _hi, _i, _i, _hi, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _f, _f, _f, _f, _i, _i, _i,
+                                    _f, _vp, _vp, _vp]),
     'bdn_sgd_step': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
     'bdn_sgd_momentum_step': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _sz, _vp]),
     'bdn_adam_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, C.c_double, C.c_double, _f, _f, _i, _i64, _sz, _vp]),
@@ -154,6 +157,18 @@ SIGNATURES = {
 def floats(values):
     """A host float array for an entry point that takes per-group hyperparameters (const float*, read during the call)."""
     return (C.c_float * len(values))(*values)
+
+
+def host_int32(a):
+    """A host int32 table for an entry point that takes one as const int32_t* (read during the call): a contiguous int32 numpy array,
+    the address of one (a pinned tensor's data_ptr()), or None."""
+    if a is None:
+        return None
+    if isinstance(a, int):
+        return C.cast(a, _hi)
+    if str(a.dtype) != 'int32' or not a.flags['C_CONTIGUOUS']:
+        raise RuntimeError('fabric_amd: host table must be a contiguous int32 array')
+    return a.ctypes.data_as(_hi)
 
 _lib = None
 

@@ -1,0 +1,94 @@
+"""The augmentation policy of device-cut patches (bdn_sample_patches_aug; DevicePatchLoader(augment=...)).
+
+A policy is a handful of scalars.  Every draw of a sample comes from Philox4x32-10 keyed by (seed, sample key), where the sample key is
+epoch << 32 | dataset index: what a sample looks like does not depend on the batch split, the rank count or the process's `random`
+state, and a resumed epoch repeats it.  The stages and their draws are specified in include/bidate_hip.h and DESIGN.md; a stage at its
+default is off and does no arithmetic.
+
+    policy = PatchAugment(seed=3, jitter=8, gain=0.1, bias=0.05, noise_std=0.02, erase_p=0.25, erase_size=(8, 32), erase_label=255)
+    loader = DevicePatchLoader(train_ds, stacks, 64, sampler=sampler, drop_last=True, augment=policy)
+"""
+import math
+import operator
+
+FLAG_SYMMETRY, FLAG_PER_DATE = 1, 2          # AUG_SYMMETRY, AUG_PER_DATE of csrc/scene.hip
+MAX_JITTER = 1 << 24
+
+
+def _integer(name, v):
+    if isinstance(v, bool):
+        raise ValueError(f'PatchAugment: {name} must be an integer, got {v!r}')
+    try:
+        return operator.index(v)
+    except TypeError:
+        raise ValueError(f'PatchAugment: {name} must be an integer, got {v!r}')
+
+
+def _finite(name, v):
+    v = float(v)
+    if not math.isfinite(v):
+        raise ValueError(f'PatchAugment: {name} must be finite, got {v}')
+    return v
+
+
+class PatchAugment:
+    """seed: 64-bit key of every draw.  jitter: J >= 0, the crop origin moves by up to J pixels on either axis (clamped into the city).
+    symmetry: draw one of the eight symmetries of the square per sample.  gain, bias: per band, out = g x + b with g in
+    [1 - gain, 1 + gain] and b in [-bias, bias]; per_date: the two dates draw their own (g, b) (False: one pair per band for both).
+    noise_std: sigma of additive Gaussian noise.  erase_p: the probability that a sample loses a rectangle of erase_size = (lo, hi)
+    pixels a side (each side drawn in lo..hi, hi at most the patch size) on every band of both dates, set to erase_fill; erase_label:
+    the byte the rectangle of the label patch becomes (the criterion's ignore_index), None to keep the labels."""
+
+    def __init__(self, seed=0, jitter=0, symmetry=True, gain=0.0, bias=0.0, per_date=True, noise_std=0.0, erase_p=0.0,
+                 erase_size=(1, 1), erase_label=None, erase_fill=0.0):
+        seed, jitter = _integer('seed', seed), _integer('jitter', jitter)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f'PatchAugment: seed {seed} outside [0, 2^64)')
+        if not 0 <= jitter <= MAX_JITTER:
+            raise ValueError(f'PatchAugment: jitter {jitter} outside [0, 2^24]')
+        self.seed, self.jitter = seed, jitter
+        self.symmetry, self.per_date = bool(symmetry), bool(per_date)
+        self.gain, self.bias, self.erase_fill = _finite('gain', gain), _finite('bias', bias), _finite('erase_fill', erase_fill)
+        self.noise_std = _finite('noise_std', noise_std)
+        if self.noise_std < 0.0:
+            raise ValueError(f'PatchAugment: noise_std {noise_std} must be >= 0')
+        self.erase_p = float(erase_p)
+        if not 0.0 <= self.erase_p <= 1.0:
+            raise ValueError(f'PatchAugment: erase_p {erase_p} outside [0, 1]')
+        try:
+            lo, hi = erase_size
+        except (TypeError, ValueError):
+            raise ValueError(f'PatchAugment: erase_size must be (lo, hi), got {erase_size!r}')
+        lo, hi = _integer('erase_size', lo), _integer('erase_size', hi)
+        if not 1 <= lo <= hi:
+            raise ValueError(f'PatchAugment: erase_size needs integers 1 <= lo <= hi, got {erase_size!r}')
+        self.erase_size = (lo, hi)
+        if erase_label is not None and not 0 <= _integer('erase_label', erase_label) <= 255:
+            raise ValueError(f'PatchAugment: erase_label {erase_label!r}: a label byte 0..255, or None to keep the labels')
+        self.erase_label = None if erase_label is None else int(erase_label)
+
+    @property
+    def flags(self):
+        return (FLAG_SYMMETRY if self.symmetry else 0) | (FLAG_PER_DATE if self.per_date else 0)
+
+    def check_patch_size(self, S):
+        if self.erase_p > 0.0 and self.erase_size[1] > S:
+            raise ValueError(f'PatchAugment: erase_size {self.erase_size} exceeds the patch size {S}')
+
+    @staticmethod
+    def sample_key(epoch, index):
+        """The 64-bit key of dataset item `index` in epoch `epoch`: epoch << 32 | index."""
+        epoch, index = int(epoch), int(index)
+        if not 0 <= epoch < 1 << 32 or not 0 <= index < 1 << 32:
+            raise ValueError(f'PatchAugment.sample_key: epoch {epoch} and index {index} must fit 32 bits')
+        return epoch << 32 | index
+
+    def abi_args(self):
+        """The policy as bdn_sample_patches_aug takes it: (seed, J, flags, gain, bias, sigma, erase_p, lo, hi, erase_label, erase_fill)."""
+        return (self.seed, self.jitter, self.flags, self.gain, self.bias, self.noise_std, self.erase_p, self.erase_size[0],
+                self.erase_size[1], -1 if self.erase_label is None else self.erase_label, self.erase_fill)
+
+    def __repr__(self):
+        return (f'PatchAugment(seed={self.seed}, jitter={self.jitter}, symmetry={self.symmetry}, gain={self.gain}, bias={self.bias}, '
+                f'per_date={self.per_date}, noise_std={self.noise_std}, erase_p={self.erase_p}, erase_size={self.erase_size}, '
+                f'erase_label={self.erase_label}, erase_fill={self.erase_fill})')

@@ -2,7 +2,10 @@
 // The two dates of a scene stay resident in HBM as band planes; tiles are gathered straight into the packed
 // NHWC batch and predictions are written straight into the scene mask -- no host-side patch stack.
 #include "common.hpp"
+#include "philox_core.hpp"
 #include <climits>
+#include <cmath>
+#include <cstring>
 #include <type_traits>
 
 // ============================================================ band upload
@@ -230,30 +233,43 @@ __global__ __launch_bounds__(SP_TILE * SP_WAVES) void sample_patches_kernel(cons
     }
 }
 
-extern "C" int bdn_sample_patches(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
-                                  const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
-                                  float* out_d1, float* out_d2, uint8_t* out_labels, void* stream) {
+// The argument checks of bdn_sample_patches and bdn_sample_patches_aug (`who` names the entry in the message); *img_blocks: the image grid.
+static int sample_patches_check(const char* who, const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
+                                const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
+                                const float* out_d1, const float* out_d2, const uint8_t* out_labels, long long* img_blocks) {
     if (!cities_dev || !city_hw_host || !desc_host || !desc_dev || !out_d1 || !out_d2 || !out_labels)
-        BDN_FAIL(BDN_E_ARG, "sample_patches: null pointer");
-    if ((uintptr_t)desc_dev % 16 || (uintptr_t)cities_dev % 8) BDN_FAIL(BDN_E_ARG, "sample_patches: desc_dev must be 16-byte and cities_dev 8-byte aligned");
+        BDN_FAIL(BDN_E_ARG, "%s: null pointer", who);
+    if ((uintptr_t)desc_dev % 16 || (uintptr_t)cities_dev % 8) BDN_FAIL(BDN_E_ARG, "%s: desc_dev must be 16-byte and cities_dev 8-byte aligned", who);
     if (n <= 0 || S <= 0 || C <= 0 || n_cities <= 0)
-        BDN_FAIL(BDN_E_SHAPE, "sample_patches: need n, S, C, n_cities > 0 (got n=%d S=%d C=%d n_cities=%d)", n, S, C, n_cities);
+        BDN_FAIL(BDN_E_SHAPE, "%s: need n, S, C, n_cities > 0 (got n=%d S=%d C=%d n_cities=%d)", who, n, S, C, n_cities);
     for (int k = 0; k < n_cities; k++)
         if (city_hw_host[2 * k] <= 0 || city_hw_host[2 * k + 1] <= 0)
-            BDN_FAIL(BDN_E_SHAPE, "sample_patches: city %d has shape %d x %d", k, city_hw_host[2 * k], city_hw_host[2 * k + 1]);
+            BDN_FAIL(BDN_E_SHAPE, "%s: city %d has shape %d x %d", who, k, city_hw_host[2 * k], city_hw_host[2 * k + 1]);
     for (int k = 0; k < n; k++) {                            // every address the kernel forms comes from a descriptor checked here
         const int32_t* e = desc_host + 4 * (size_t)k;
         const int city = e[0], row = e[1], col = e[2], sym = e[3];
-        if (city < 0 || city >= n_cities) BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: city %d outside [0, %d)", k, city, n_cities);
-        if (sym < 0 || sym > 7) BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: sym %d outside [0, 8)", k, sym);
+        if (city < 0 || city >= n_cities) BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: city %d outside [0, %d)", who, k, city, n_cities);
+        if (sym < 0 || sym > 7) BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: sym %d outside [0, 8)", who, k, sym);
         const long long H = city_hw_host[2 * city], W = city_hw_host[2 * city + 1];
         if (row < 0 || (long long)row + S > H)
-            BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: row %d + S %d outside H %lld of city %d", k, row, S, H, city);
+            BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: row %d + S %d outside H %lld of city %d", who, k, row, S, H, city);
         if (col < 0 || (long long)col + S > W)
-            BDN_FAIL(BDN_E_ARG, "sample_patches: descriptor %d: col %d + S %d outside W %lld of city %d", k, col, S, W, city);
+            BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: col %d + S %d outside W %lld of city %d", who, k, col, S, W, city);
     }
-    const long long tiles = (S + SP_TILE - 1) / SP_TILE, img_blocks = (long long)n * 2 * C * tiles * tiles;
-    if (img_blocks > INT_MAX) BDN_FAIL(BDN_E_SHAPE, "sample_patches: %lld blocks exceed the grid", img_blocks);
+    const long long tiles = (S + SP_TILE - 1) / SP_TILE;
+    *img_blocks = (long long)n * 2 * C * tiles * tiles;
+    if (*img_blocks > INT_MAX) BDN_FAIL(BDN_E_SHAPE, "%s: %lld blocks exceed the grid", who, *img_blocks);
+    return BDN_OK;
+}
+
+extern "C" int bdn_sample_patches(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
+                                  const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
+                                  float* out_d1, float* out_d2, uint8_t* out_labels, void* stream) {
+    long long img_blocks = 0;
+    const int rc = sample_patches_check("sample_patches", cities_dev, city_hw_host, n_cities, C, desc_host, desc_dev, n, S,
+                                        out_d1, out_d2, out_labels, &img_blocks);
+    if (rc != BDN_OK) return rc;
+    const long long tiles = (S + SP_TILE - 1) / SP_TILE;
     hipStream_t st = (hipStream_t)stream;
     const dim3 block(SP_TILE, SP_WAVES);
     hipLaunchKernelGGL(sample_patches_kernel<false>, dim3((unsigned)img_blocks), block, 0, st, (const SampleCity*)cities_dev,
@@ -262,5 +278,221 @@ extern "C" int bdn_sample_patches(const void* cities_dev, const int32_t* city_hw
     hipLaunchKernelGGL(sample_patches_kernel<true>, dim3((unsigned)(n * tiles * tiles)), block, 0, st, (const SampleCity*)cities_dev,
                        (const int4*)desc_dev, C, S, (int)tiles, (uint32_t*)out_d1, (uint32_t*)out_d2, out_labels);
     BDN_CHECK_LAUNCH("sample_patches (labels)");
+    return BDN_OK;
+}
+
+// ============================================================ sample_patches_aug: the same cut, augmented on the way through the registers
+// No reference: the reference's loader stops at the eight symmetries (utils/dataloaders.py:148-165).  Every draw of a sample comes from
+// Philox4x32-10 (philox_core.hpp) keyed by (seed, sample key = epoch << 32 | dataset index), so a sample looks the same in any batch, on
+// any rank and after a resume.  Stages, in order: crop at the jittered and clamped origin, symmetry, per-date per-band gain / bias,
+// Gaussian noise, erase.  sample_patches_kernel's structure is kept: one 64 x 64 output tile of one plane per block, lane x walks an
+// output row, dword (byte) accesses, the 64 x 65 LDS tile for the transposing symmetries, labels in a second launch; both paths end with
+// the tile in registers in OUTPUT coordinates (row i0 + y + 4 k, column j0 + x), where the value stages run before the store.  What is
+// loaded and stored does not change.
+//   geometry, gain / bias: the sample key, the descriptor and the policy are block-uniform, so these Philox calls run on the scalar
+//     unit, once per wave, never per element.
+//   noise: one Philox call serves the four output columns 4 q .. 4 q + 3 of one row.  The four lanes of a quad share q; lane m of the quad
+//     makes the calls of the rows k = 4 kk + m (4 of the thread's 16) and both Box-Muller pairs of each, and the quad exchanges the
+//     4 x 4 values by DPP quad broadcasts (full-rate moves, no LDS, no barrier).  Every lane of the block takes part, also one whose
+//     element lies outside a ragged tile: its quad may need its call.
+// A disabled stage is compiled out (RADIO, NOISE) or skipped on a block-uniform branch (erase): with every value stage off the tile
+// travels as 32-bit patterns, as in sample_patches_kernel.  Labels are never arithmetic.
+struct AugPolicy {
+    uint64_t seed;
+    int J, flags, lo, hi, erase_label;
+    float gain, bias, sigma, erase_p;
+    uint32_t fill_bits;
+};
+constexpr int AUG_SYMMETRY = 1, AUG_PER_DATE = 2;
+
+// One rounding per operation: the products and sums below must not be contracted into fused multiply-adds, or numpy float32 could not
+// reproduce the bits.  (__fmul_rn / __fadd_rn are plain `*` and `+` in this toolchain's headers and inherit the caller's contraction.)
+__device__ __forceinline__ float aug_fmul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float aug_fadd(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float aug_u(uint32_t w) { return (float)philox_u24(w) * 0x1p-24f; }      // exact: 24 bits, a power of two
+
+template <int L> __device__ __forceinline__ float quad_bcast(float v) {          // the value of lane L of this lane's quad
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), L * 0x55, 0xf, 0xf, false));
+}
+template <int L> __device__ __forceinline__ float quad_pick(const float (&z)[4], int m) {      // z[m] of lane L of the quad
+    const float a = quad_bcast<L>(z[0]), b = quad_bcast<L>(z[1]), c = quad_bcast<L>(z[2]), d = quad_bcast<L>(z[3]);
+    const float lo = (m & 1) ? b : a, hi = (m & 1) ? d : c;
+    return (m & 2) ? hi : lo;
+}
+
+template <bool LABELS, bool RADIO, bool NOISE>
+__global__ __launch_bounds__(SP_TILE * SP_WAVES) void sample_patches_aug_kernel(const SampleCity* __restrict__ cities, const int4* __restrict__ desc,
+                                                                                const uint64_t* __restrict__ keys, const AugPolicy pol,
+                                                                                int C, int S, int tiles, uint32_t* __restrict__ o1,
+                                                                                uint32_t* __restrict__ o2, uint8_t* __restrict__ ol,
+                                                                                int32_t* __restrict__ drawn_geom, float* __restrict__ drawn_radio) {
+    using T = typename std::conditional<LABELS, uint8_t, uint32_t>::type;
+    __shared__ uint32_t lds[SP_TILE][SP_TILE + 1];
+    const int planes = LABELS ? 1 : 2 * C;
+    int b = blockIdx.x;
+    const int tt = b % (tiles * tiles); b /= tiles * tiles;
+    const int p = b % planes, s = b / planes;
+    const int4 d = desc[s];                                  // (city, row, col, sym), validated on the host
+    const SampleCity ct = cities[d.x];
+    const uint64_t key = keys[s];
+    const bool erase_on = pol.erase_p > 0.f;
+    const PhiloxGeom g = philox_geometry(pol.seed, key, d.y, d.z, d.w, ct.H, ct.W, S, pol.J, (pol.flags & AUG_SYMMETRY) != 0, erase_on,
+                                         pol.lo, pol.hi);    // row, col clamped into the city here: in range for any draw
+    const bool erased = erase_on && (float)g.erase_u24 * 0x1p-24f < pol.erase_p;
+    const int t = g.sym >> 2, rr = (g.sym >> 1) & 1, rc = g.sym & 1;
+    const int i0 = (tt / tiles) * SP_TILE, j0 = (tt % tiles) * SP_TILE;
+    const int ni = min(SP_TILE, S - i0), nj = min(SP_TILE, S - j0);
+    const size_t W = (size_t)ct.W, SS = (size_t)S * S;
+    const int date = p >= C, c = p - date * C;
+    const bool first = tt == 0 && threadIdx.x == 0 && threadIdx.y == 0;
+    const T* src;
+    T* dst;
+    if (LABELS) {
+        src = reinterpret_cast<const T*>(ct.labels);
+        dst = reinterpret_cast<T*>(ol + s * SS);
+    } else {
+        src = reinterpret_cast<const T*>(ct.images) + (size_t)p * ct.H * W;      // images [2][C][H][W]: plane p = date * C + c
+        dst = reinterpret_cast<T*>((date ? o2 : o1) + ((size_t)s * C + c) * SS);
+        if (drawn_geom && first && p == 0) {
+            int32_t* e = drawn_geom + 8 * (size_t)s;
+            e[0] = g.row; e[1] = g.col; e[2] = g.sym; e[3] = erased; e[4] = g.top; e[5] = g.left; e[6] = g.eh; e[7] = g.ew;
+        }
+    }
+    src += (size_t)g.row * W + g.col;                        // window origin
+    const int x = threadIdx.x, y = threadIdx.y;
+    const int j = j0 + x;
+    T v[SP_ROWS];
+#pragma unroll
+    for (int k = 0; k < SP_ROWS; k++) v[k] = 0;
+    if (!t) {
+        const int cj = rc ? S - 1 - j : j;
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) {
+            const int i = i0 + y + k * SP_WAVES, ri = rr ? S - 1 - i : i;
+            if (x < nj && i < i0 + ni) v[k] = src[(size_t)ri * W + cj];
+        }
+    } else {
+        // transposed: output rows i take source columns ri, output columns j take source rows cj.  The source block is rows
+        // [a0, a0 + nj) x columns [b0, b0 + ni) of the window; lds[a - a0][b - b0] holds W[a][b].
+        const int a0 = rc ? S - j0 - nj : j0, b0 = rr ? S - i0 - ni : i0;
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) {
+            const int a = y + k * SP_WAVES;
+            if (x < ni && a < nj) v[k] = src[(size_t)(a0 + a) * W + b0 + x];
+        }
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) {
+            const int a = y + k * SP_WAVES;
+            if (x < ni && a < nj) lds[a][x] = (uint32_t)v[k];
+        }
+        __syncthreads();
+        const int aa = rc ? nj - 1 - x : x;                  // a - a0 of output column j0 + x
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) {
+            const int ii = y + k * SP_WAVES, bb = rr ? ni - 1 - ii : ii;
+            if (x < nj && ii < ni) v[k] = (T)lds[aa][bb];
+        }
+    }
+    // ---- the tile is in registers in output coordinates: v[k] = out[i0 + y + 4 k][j0 + x]
+    if (!LABELS && RADIO) {                                   // stream 1: g, b of this plane, block-uniform
+        const Philox4 w = philox_draw(pol.seed, key, PHILOX_RADIOMETRY, (uint32_t)(((pol.flags & AUG_PER_DATE) ? date * C : 0) + c));
+        const float ta = aug_fadd(aug_fmul(2.f, aug_u(w.w[0])), -1.f), tb = aug_fadd(aug_fmul(2.f, aug_u(w.w[1])), -1.f);
+        const float gg = aug_fadd(1.f, aug_fmul(pol.gain, ta)), bb = aug_fmul(pol.bias, tb);
+        if (drawn_radio && first) { drawn_radio[2 * ((size_t)s * planes + p)] = gg; drawn_radio[2 * ((size_t)s * planes + p) + 1] = bb; }
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) v[k] = (T)__float_as_uint(aug_fadd(aug_fmul(gg, __uint_as_float((uint32_t)v[k])), bb));
+    } else if (!LABELS) {
+        if (drawn_radio && first) { drawn_radio[2 * ((size_t)s * planes + p)] = 1.f; drawn_radio[2 * ((size_t)s * planes + p) + 1] = 0.f; }
+    }
+    if (!LABELS && NOISE) {                                   // stream 2 + p, slot i * ceil(S / 4) + (j >> 2): every lane, no bounds test
+        const int m = x & 3;
+        const uint32_t q = (uint32_t)j >> 2, G = (uint32_t)(S + 3) >> 2;
+#pragma unroll
+        for (int kk = 0; kk < SP_ROWS / 4; kk++) {
+            const uint32_t i = (uint32_t)(i0 + y + (4 * kk + m) * SP_WAVES);
+            const Philox4 w = philox_draw(pol.seed, key, PHILOX_NOISE + (uint32_t)p, i * G + q);
+            float z[4];
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const float u1 = (float)(philox_u24(w.w[2 * h]) + 1u) * 0x1p-24f, u2 = aug_u(w.w[2 * h + 1]);      // (0, 1] and [0, 1)
+                const float r = sqrtf(-2.f * logf(u1));
+                float sn, cs;
+                sincospif(2.f * u2, &sn, &cs);               // sin, cos of 2 pi u2: the argument 2 u2 is exact
+                z[2 * h] = aug_fmul(r, cs);
+                z[2 * h + 1] = aug_fmul(r, sn);
+            }
+            const float z0 = quad_pick<0>(z, m), z1 = quad_pick<1>(z, m), z2 = quad_pick<2>(z, m), z3 = quad_pick<3>(z, m);
+            v[4 * kk + 0] = (T)__float_as_uint(aug_fadd(__uint_as_float((uint32_t)v[4 * kk + 0]), aug_fmul(pol.sigma, z0)));
+            v[4 * kk + 1] = (T)__float_as_uint(aug_fadd(__uint_as_float((uint32_t)v[4 * kk + 1]), aug_fmul(pol.sigma, z1)));
+            v[4 * kk + 2] = (T)__float_as_uint(aug_fadd(__uint_as_float((uint32_t)v[4 * kk + 2]), aug_fmul(pol.sigma, z2)));
+            v[4 * kk + 3] = (T)__float_as_uint(aug_fadd(__uint_as_float((uint32_t)v[4 * kk + 3]), aug_fmul(pol.sigma, z3)));
+        }
+    }
+    if (erased && (!LABELS || pol.erase_label >= 0)) {        // block-uniform: the rectangle [top, top + eh) x [left, left + ew) of the output
+        const T fill = LABELS ? (T)pol.erase_label : (T)pol.fill_bits;
+        const bool in_cols = j >= g.left && j < g.left + g.ew;
+#pragma unroll
+        for (int k = 0; k < SP_ROWS; k++) {
+            const int i = i0 + y + k * SP_WAVES;
+            if (in_cols && i >= g.top && i < g.top + g.eh) v[k] = fill;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < SP_ROWS; k++) {
+        const int i = i0 + y + k * SP_WAVES;
+        if (x < nj && i < i0 + ni) dst[(size_t)i * S + j] = v[k];
+    }
+}
+
+extern "C" int bdn_sample_patches_aug(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
+                                      const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
+                                      float* out_d1, float* out_d2, uint8_t* out_labels, const uint64_t* keys_dev,
+                                      uint64_t seed, int J, int flags, float gain, float bias, float sigma, float erase_p,
+                                      int lo, int hi, int erase_label, float erase_fill,
+                                      int32_t* drawn_geom, float* drawn_radio, void* stream) {
+    long long img_blocks = 0;
+    const int rc = sample_patches_check("sample_patches_aug", cities_dev, city_hw_host, n_cities, C, desc_host, desc_dev, n, S,
+                                        out_d1, out_d2, out_labels, &img_blocks);
+    if (rc != BDN_OK) return rc;
+    if (!keys_dev) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: null pointer");
+    if ((uintptr_t)keys_dev % 8) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: keys_dev must be 8-byte aligned");
+    if ((uintptr_t)drawn_geom % 4 || (uintptr_t)drawn_radio % 4) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: drawn_geom and drawn_radio must be 4-byte aligned");
+    if (J < 0 || J > (1 << 24)) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: jitter J=%d outside [0, 2^24]", J);
+    if (flags & ~(AUG_SYMMETRY | AUG_PER_DATE)) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: unknown flags %#x", flags);
+    if (!std::isfinite(gain) || !std::isfinite(bias) || !std::isfinite(erase_fill))
+        BDN_FAIL(BDN_E_ARG, "sample_patches_aug: gain, bias and erase_fill must be finite (got %g, %g, %g)", gain, bias, erase_fill);
+    if (!(sigma >= 0.f) || !std::isfinite(sigma)) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: need a finite sigma >= 0 (got %g)", sigma);
+    if (!(erase_p >= 0.f && erase_p <= 1.f)) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: erase_p %g outside [0, 1]", erase_p);
+    if (erase_p > 0.f && !(1 <= lo && lo <= hi && hi <= S))
+        BDN_FAIL(BDN_E_ARG, "sample_patches_aug: erase size needs 1 <= lo <= hi <= S (got lo=%d hi=%d S=%d)", lo, hi, S);
+    if (erase_label < -1 || erase_label > 255) BDN_FAIL(BDN_E_ARG, "sample_patches_aug: erase_label %d outside -1..255", erase_label);
+    if (sigma > 0.f && S > 65536) BDN_FAIL(BDN_E_SHAPE, "sample_patches_aug: noise slots are 32 bits: S=%d above 65536", S);
+    if (sigma > 0.f && 2LL * C + PHILOX_NOISE > UINT32_MAX) BDN_FAIL(BDN_E_SHAPE, "sample_patches_aug: too many planes");
+    AugPolicy pol;
+    pol.seed = seed; pol.J = J; pol.flags = flags; pol.lo = lo; pol.hi = hi; pol.erase_label = erase_label;
+    pol.gain = gain; pol.bias = bias; pol.sigma = sigma; pol.erase_p = erase_p;
+    memcpy(&pol.fill_bits, &erase_fill, 4);
+    const int tiles = (S + SP_TILE - 1) / SP_TILE;
+    const bool radio = gain != 0.f || bias != 0.f, noise = sigma > 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(SP_TILE, SP_WAVES), grid((unsigned)img_blocks);
+#define AUG_LAUNCH(R, N) hipLaunchKernelGGL((sample_patches_aug_kernel<false, R, N>), grid, block, 0, st, (const SampleCity*)cities_dev, \
+        (const int4*)desc_dev, keys_dev, pol, C, S, tiles, (uint32_t*)out_d1, (uint32_t*)out_d2, out_labels, drawn_geom, drawn_radio)
+    if (radio && noise) AUG_LAUNCH(true, true);
+    else if (radio) AUG_LAUNCH(true, false);
+    else if (noise) AUG_LAUNCH(false, true);
+    else AUG_LAUNCH(false, false);
+#undef AUG_LAUNCH
+    BDN_CHECK_LAUNCH("sample_patches_aug");
+    hipLaunchKernelGGL((sample_patches_aug_kernel<true, false, false>), dim3((unsigned)(n * tiles * tiles)), block, 0, st,
+                       (const SampleCity*)cities_dev, (const int4*)desc_dev, keys_dev, pol, C, S, tiles, (uint32_t*)out_d1,
+                       (uint32_t*)out_d2, out_labels, drawn_geom, drawn_radio);
+    BDN_CHECK_LAUNCH("sample_patches_aug (labels)");
     return BDN_OK;
 }

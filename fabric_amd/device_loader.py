@@ -10,12 +10,18 @@ order, when `dataset.aug`.
     loader = DevicePatchLoader(train_ds, stacks, batch_size=64, sampler=ShardSampler(len(train_ds), rank, world, seed))
     for x1, x2, y in loader:            # device tensors; valid until the next iteration (the contract of DeviceFeeder)
         loss = step.step(x1, x2, y)
+
+With `augment=PatchAugment(...)` (fabric_amd.augment) the batch is cut by bdn_sample_patches_aug instead: crop jitter, a drawn symmetry,
+per-date per-band gain / bias, Gaussian noise and erasing, every draw from a counter-based generator keyed by (policy seed, epoch,
+dataset index).  The host then draws nothing from `random` and `dataset.aug` is ignored for that loader: descriptors carry sym = 0 and a
+pinned ring of 64-bit sample keys travels beside them.  Index order and batch boundaries are unchanged.
 """
 import numpy as np
 import torch
 import torch.utils.data
 
 from . import _lib
+from .augment import PatchAugment
 from .utils.dataloaders import _draw_symmetry
 
 
@@ -66,8 +72,24 @@ def device_stacks(stacks, device):
     return out
 
 
+def plan_keys(indices, epoch, out=None):
+    """Host half of an augmented batch, no device needed: uint64 [len(indices)] sample keys epoch << 32 | dataset index."""
+    n = len(indices)
+    keys = np.empty(n, np.uint64) if out is None else out[:n]
+    for k, idx in enumerate(indices):
+        keys[k] = PatchAugment.sample_key(epoch, idx)
+    return keys
+
+
 class _Slot:
-    def __init__(self, batch_size, C, S, device):
+    def __init__(self, batch_size, C, S, device, keys=False, export=False):
+        if keys:                  # the ring of sample keys: rewritten and read under the same `done` discipline as the descriptors
+            self.keys_pin = torch.empty((batch_size,), dtype=torch.int64, pin_memory=True)
+            self.keys_np = self.keys_pin.numpy().view(np.uint64)
+            self.keys_dev = torch.empty((batch_size,), dtype=torch.int64, device=device)
+        if export:
+            self.geom = torch.empty((batch_size, 8), dtype=torch.int32, device=device)
+            self.radio = torch.empty((batch_size, 2, C, 2), dtype=torch.float32, device=device)
         self.desc_pin = torch.empty((batch_size, 4), dtype=torch.int32, pin_memory=True)
         self.desc_np = self.desc_pin.numpy()
         self.desc_dev = torch.empty((batch_size, 4), dtype=torch.int32, device=device)
@@ -80,9 +102,23 @@ class _Slot:
 class DevicePatchLoader:
     """Batches of `dataset` (an OneraPreloader: its `imgs`, `input_size` and `aug` are used) sampled on the device from `stacks`
     ({city: {'images', 'labels'}}; see device_stacks).  `depth` (>= 2) slots of pinned descriptors and device outputs are cycled;
-    a slot's pinned table is rewritten only after the launch that read it `depth` batches ago has completed."""
+    a slot's pinned table is rewritten only after the launch that read it `depth` batches ago has completed.
+    `augment`: a PatchAugment; the batches are then augmented on the device (module docstring) and `dataset.aug` is ignored.  The epoch
+    half of a sample key is `sampler.epoch` when the sampler has one, else the number of passes begun so far; set_epoch(e) overrides
+    both.  `export_drawn=True` (with a policy): `last_drawn` = (int32 [n][8] (row, col, sym, erased, top, left, eh, ew), float32
+    [n][2][C][2] (g, b)) of the batch yielded last, valid as long as the batch is."""
 
-    def __init__(self, dataset, stacks, batch_size, sampler=None, drop_last=False, device=None, depth=3):
+    def __init__(self, dataset, stacks, batch_size, sampler=None, drop_last=False, device=None, depth=3, augment=None,
+                 export_drawn=False):
+        if augment is not None:
+            if not isinstance(augment, PatchAugment):
+                raise TypeError(f'fabric_amd: augment must be a PatchAugment, got {type(augment).__name__}')
+            augment.check_patch_size(int(dataset.input_size))
+        elif export_drawn:
+            raise ValueError('fabric_amd: export_drawn needs an augment policy')
+        self.augment, self.export_drawn = augment, bool(export_drawn)
+        self.last_drawn = None
+        self._epoch, self._passes = None, 0
         self.dataset = dataset
         self.batch_sampler = batch_sampler(dataset, batch_size, sampler, drop_last)
         self.sampler = self.batch_sampler.sampler
@@ -109,7 +145,8 @@ class DevicePatchLoader:
             rec[k] = (self.stacks[c]['images'].data_ptr(), self.stacks[c]['labels'].data_ptr(), h | (w << 32))
         self.city_table = torch.from_numpy(rec).to(self.device)
         self.depth = max(2, int(depth))
-        self.slots = [_Slot(self.batch_size, self.C, self.S, self.device) for _ in range(self.depth)]
+        self.slots = [_Slot(self.batch_size, self.C, self.S, self.device, keys=augment is not None, export=self.export_drawn)
+                      for _ in range(self.depth)]
         torch.cuda.synchronize(self.device)                       # uploads and allocations are complete before any stream reads them
         self._k = 0
         self._streams = set()
@@ -120,13 +157,56 @@ class DevicePatchLoader:
             yield from (city['images'], city['labels'])
         for slot in self.slots:
             yield from (slot.desc_dev, slot.d1, slot.d2, slot.labels)
+            if self.augment is not None:
+                yield slot.keys_dev
+            if self.export_drawn:
+                yield from (slot.geom, slot.radio)
 
     def __len__(self):
         return len(self.batch_sampler)
 
+    def set_epoch(self, epoch):
+        """The epoch half of the sample keys of every pass from now on (None: back to the sampler's epoch / the pass counter)."""
+        self._epoch = None if epoch is None else int(epoch)
+
     def __iter__(self):
+        if self.augment is None:
+            for indices in self.batch_sampler:
+                yield self._sample(indices)
+            return
+        epoch = self._epoch if self._epoch is not None else getattr(self.sampler, 'epoch', self._passes)
+        self._passes += 1
         for indices in self.batch_sampler:
-            yield self._sample(indices)
+            yield self._sample_aug(indices, int(epoch))
+
+    def _sample_aug(self, indices, epoch):
+        """_sample with a policy: sym = 0 descriptors (no draw from `random`) and the sample keys through the pinned slot."""
+        slot = self.slots[self._k % self.depth]
+        self._k += 1
+        if slot.done is not None:
+            slot.done.synchronize()                               # the copies that read desc_pin and keys_pin `depth` batches ago have run
+        n = len(indices)
+        for k, idx in enumerate(indices):
+            city, i, j = self.dataset.imgs[idx]
+            slot.desc_np[k] = (self.city_index[city], i, j, 0)
+        plan_keys(indices, epoch, out=slot.keys_np)
+        cur = torch.cuda.current_stream(self.device)
+        desc_dev, keys_dev = slot.desc_dev[:n], slot.keys_dev[:n]
+        desc_dev.copy_(slot.desc_pin[:n], non_blocking=True)
+        keys_dev.copy_(slot.keys_pin[:n], non_blocking=True)
+        d1, d2, labels = slot.d1[:n], slot.d2[:n], slot.labels[:n]
+        geom, radio = (slot.geom[:n], slot.radio[:n]) if self.export_drawn else (None, None)
+        _lib.call('bdn_sample_patches_aug', self.city_table.data_ptr(), _lib.host_int32(self.city_hw), len(self.cities), self.C,
+                  _lib.host_int32(slot.desc_pin.data_ptr()), desc_dev.data_ptr(), n, self.S, d1.data_ptr(), d2.data_ptr(),
+                  labels.data_ptr(), keys_dev.data_ptr(), *self.augment.abi_args(), _lib.ptr(geom), _lib.ptr(radio), cur.cuda_stream)
+        if cur.cuda_stream not in self._streams:
+            self._streams.add(cur.cuda_stream)
+            for t in self._long_lived():
+                t.record_stream(cur)
+        slot.done = torch.cuda.Event()
+        slot.done.record(cur)
+        self.last_drawn = (geom, radio) if self.export_drawn else None
+        return d1, d2, labels
 
     def _sample(self, indices):
         """Plan the batch on the host, copy its descriptors through the next pinned slot and launch on the current stream."""

@@ -72,19 +72,40 @@ def _patch_datasets(full_load, val_cities, patch_size, stride, augmentation):
 
 
 def make_device_loaders(full_load, val_cities, patch_size, stride, batch_size, augmentation, rank=0, world_size=1, seed=0,
-                        device=None):
+                        device=None, augment=None):
     """make_loaders with the patches cut on the device (fabric_amd.device_loader): the same datasets, built and sorted the same way,
     the same ShardSampler and drop_last for training, no augmentation and no drop_last for validation.  `full_load`'s city stacks are
     used in place when they are device tensors (ingest's device= output) and uploaded once otherwise; both loaders share them.  The
-    augmentation draws come from the process's global `random` at iteration time, as with make_loaders(num_workers=0)."""
+    augmentation draws come from the process's global `random` at iteration time, as with make_loaders(num_workers=0).
+    `augment`: a fabric_amd.augment.PatchAugment for the TRAINING loader only (its draws then come from the policy's counter-based
+    generator and `augmentation` is ignored for it); validation is never augmented."""
     from .device_loader import DevicePatchLoader, device_stacks
     from .parallel import ShardSampler
     device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     train_ds, val_ds = _patch_datasets(full_load, val_cities, patch_size, stride, augmentation)
     stacks = device_stacks(full_load, device)
     sampler = ShardSampler(len(train_ds), rank, world_size, seed=seed)
-    return (DevicePatchLoader(train_ds, stacks, batch_size, sampler=sampler, drop_last=True, device=device),
+    extra = {} if augment is None else dict(augment=augment)
+    return (DevicePatchLoader(train_ds, stacks, batch_size, sampler=sampler, drop_last=True, device=device, **extra),
             DevicePatchLoader(val_ds, stacks, batch_size, device=device))
+
+
+def augment_from_opt(opt):
+    """The PatchAugment of the --aug_* flags, or None when all are at their defaults.  Raises ValueError for flags that cannot be
+    honoured: without --device_patches true (the patches of any other loader are cut on the host) or with values the policy refuses."""
+    given = [f'--aug_{k}' for k, off in (('jitter', 0), ('gain', 0.0), ('bias', 0.0), ('shared_dates', False), ('noise', 0.0),
+                                         ('erase_p', 0.0), ('erase_size', None), ('seed', None)) if getattr(opt, f'aug_{k}') != off]
+    if not given:
+        return None
+    if not opt.device_patches:
+        raise ValueError(f'{" / ".join(given)} augment the patches the device cuts: add --device_patches true')
+    from .augment import PatchAugment
+    policy = PatchAugment(seed=opt.seed if opt.aug_seed is None else opt.aug_seed, jitter=opt.aug_jitter, symmetry=bool(opt.augmentation),
+                          gain=opt.aug_gain, bias=opt.aug_bias, per_date=not opt.aug_shared_dates, noise_std=opt.aug_noise,
+                          erase_p=opt.aug_erase_p, erase_size=tuple(opt.aug_erase_size) if opt.aug_erase_size else (1, 1),
+                          erase_label=opt.ignore_label)
+    policy.check_patch_size(opt.patch_size)
+    return policy
 
 
 def _device_batches(loader, dev, feeder):
@@ -476,6 +497,18 @@ def main(argv=None):
     ap.add_argument('--device_patches', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=False,
                     help='cut and augment the patch pairs on the device from city stacks kept in HBM (fabric_amd.device_loader) '
                          'instead of on the host; --num_workers does not apply then')
+    ap.add_argument('--aug_jitter', type=int, default=0, metavar='N',
+                    help='--device_patches true: move every crop origin by up to N pixels on either axis, off the stride grid (clamped into '
+                         'the city).  Any --aug_* flag switches the training loader to the counter-based draws of fabric_amd.augment')
+    ap.add_argument('--aug_gain', type=float, default=0.0, metavar='F', help='per date and band: x *= 1 + F u, u uniform in [-1, 1)')
+    ap.add_argument('--aug_bias', type=float, default=0.0, metavar='F', help='per date and band: x += F u, u uniform in [-1, 1)')
+    ap.add_argument('--aug_shared_dates', action='store_true', help='one --aug_gain / --aug_bias draw per band for both dates')
+    ap.add_argument('--aug_noise', type=float, default=0.0, metavar='F', help='additive Gaussian noise of standard deviation F')
+    ap.add_argument('--aug_erase_p', type=float, default=0.0, metavar='F',
+                    help='probability that a sample loses a rectangle (--aug_erase_size) on every band of both dates; its labels become '
+                         '--ignore_label when that is set and are kept otherwise')
+    ap.add_argument('--aug_erase_size', type=int, nargs=2, default=None, metavar=('LO', 'HI'), help='sides of the erased rectangle, drawn in LO..HI pixels')
+    ap.add_argument('--aug_seed', type=int, default=None, metavar='N', help='seed of the augmentation draws (default: --seed)')
     ap.add_argument('--scene_stride', type=int, default=0,
                     help='full validation scenes: 0 = the reference\'s non-overlapping argmax masks (predict_scene); N > 0 = tiles every N px, '
                          'softmax probabilities blended (predict_scene_blended), also writes {city}_epoch_{e}_proba.png and a scene F1 line')
@@ -580,6 +613,10 @@ def main(argv=None):
         raise SystemExit(str(e))
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
+    try:
+        patch_augment = augment_from_opt(opt)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
     # one process per GPU (launched by torch.distributed.run): RANK / LOCAL_RANK / WORLD_SIZE from the environment
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -612,7 +649,8 @@ def main(argv=None):
     stride = opt.stride // 2 if opt.synthetic else opt.stride
     if opt.device_patches:
         train_loader, val_loader = make_device_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
-                                                       rank=rank, world_size=world, seed=opt.seed, device=dev)
+                                                       rank=rank, world_size=world, seed=opt.seed, device=dev,
+                                                       **({} if patch_augment is None else dict(augment=patch_augment)))
     else:
         train_loader, val_loader = make_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
                                                 num_workers=opt.num_workers, rank=rank, world_size=world, seed=opt.seed)

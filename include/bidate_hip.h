@@ -623,6 +623,32 @@ int bdn_blend_finalize(float* acc, const float* wsum, uint8_t* mask, int ncls, i
 int bdn_sample_patches(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
                        const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
                        float* out_d1, float* out_d2, uint8_t* out_labels, void* stream);
+/* ---- the same cut, augmented on the device: extends utils/dataloaders.py:148-165, whose augmentation ends at the eight symmetries ----
+ * Everything bdn_sample_patches takes, checked the same way, plus keys_dev: DEVICE uint64 [n], 8-byte aligned, the sample keys
+ * epoch << 32 | dataset index.  Every draw is Philox4x32-10 (csrc/philox_core.hpp) with key (seed & 0xffffffff, seed >> 32) and counter
+ * (key_lo, key_hi, slot, stream); u(w) = float(w >> 8) * 2^-24, range(w, n) = (uint64(w) * n) >> 32.  Stages, in this order:
+ *   crop      stream 0 slot 0: row' = clamp(row + range(w0, 2J+1) - J, 0, H - S), col' alike from w1 (clamped on the device: in range
+ *             for any draw); J >= 0.
+ *   symmetry  sym = w2 >> 29 of the same words if flags & 1, else the descriptor's sym.
+ *   gain/bias stream 1 slot date * C + c (slot c for both dates unless flags & 2): g = 1 + gain * (2 u(w0) - 1), b = bias * (2 u(w1) - 1),
+ *             out = g * x + b, each operation rounded once (no fused multiply-add).  Off when gain == 0 and bias == 0.
+ *   noise     stream 2 + date * C + c, slot i * ceil(S / 4) + (j >> 2) for output element (i, j): words (a, b) = (w[2k], w[2k+1]),
+ *             k = (j >> 1) & 1; u1 = float((a >> 8) + 1) * 2^-24, u2 = u(b), r = sqrt(-2 ln u1), z = r cos(2 pi u2) for even j,
+ *             r sin(2 pi u2) for odd j; out += sigma * z.  Off when sigma == 0.
+ *   erase     erased = u(w3 of stream 0 slot 0) < erase_p; stream 0 slot 1: eh = lo + range(w0, hi - lo + 1), ew alike from w1,
+ *             top = range(w2, S - eh + 1), left = range(w3, S - ew + 1).  The output rectangle [top, top + eh) x [left, left + ew) of every
+ *             image plane of both dates becomes erase_fill and, when erase_label >= 0, that of the label patch becomes that byte
+ *             (erase_label = -1: labels are kept).  Off when erase_p == 0; then lo and hi are not read.
+ * A stage that is off does no arithmetic: with gain = bias = sigma = 0 floats travel as 32-bit patterns, and with J = 0, flags = 0 and
+ * erase_p = 0 as well the outputs are those of bdn_sample_patches.  Labels are moved or overwritten, never computed.
+ * drawn_geom (or NULL): DEVICE int32 [n][8] = (row', col', sym, erased, top, left, eh, ew), the rectangle 0 when the erase stage is off;
+ * drawn_radio (or NULL): DEVICE float [n][2][C][2] = (g, b), (1, 0) when gain / bias is off. */
+int bdn_sample_patches_aug(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
+                           const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
+                           float* out_d1, float* out_d2, uint8_t* out_labels, const uint64_t* keys_dev,
+                           uint64_t seed, int J, int flags, float gain, float bias, float sigma, float erase_p,
+                           int lo, int hi, int erase_label, float erase_fill,
+                           int32_t* drawn_geom, float* drawn_radio, void* stream);
 
 /* ---- optim.SGD(lr) step, train.py:55,95: p -= lr * grad_scale * g over a flat f32 buffer ---- */
 int bdn_sgd_step(float* params, const float* grads, float lr, float grad_scale, size_t n, void* stream);
