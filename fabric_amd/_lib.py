@@ -131,6 +131,10 @@ SIGNATURES = {
     'bdn_grad_accumulate': (_i, [_vp, _vp, _sz, _i, _vp]),
     'bdn_grad_norm_workspace_bytes': (_sz, [_sz]),
     'bdn_grad_norm': (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp, _sz, _vp]),
+    'bdn_layerwise_workspace_bytes': (_sz, [_sz, _i]),
+    'bdn_lamb_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _hf, _hf, _f, _vp, C.c_double, C.c_double, _f, _f, _i64, _vp, _vp,
+                           _sz, _vp]),
+    'bdn_lars_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _hf, _hf, _f, _vp, _f, _f, _i, _i, _f, _f, _f, _vp, _vp, _sz, _vp]),
     'bdn_ema_update': (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _sz, _vp]),
     'bdn_ema_update_multi': (_i, [_vp, _i, _i, _f, _i, _vp]),
     'bdn_swap_segments': (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp]),

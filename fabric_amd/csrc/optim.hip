@@ -1,5 +1,6 @@
 // Parameter updates over the flat float32 buffers: SGD, momentum SGD, Adam / AdamW, their grouped and _ex forms, EMA / SWA averaging and
-// the buffer swap, gradient accumulation and the global gradient norm.  Memory-bound float4 passes; no atomics, fixed-order reductions.
+// the buffer swap, gradient accumulation and the global gradient norm, and the layer-wise adaptive rules LAMB / LARS (per-tensor norms
+// and trust ratios).  Memory-bound float4 passes; no atomics, fixed-order reductions.
 #include "common.hpp"
 
 // ============================================================ SGD (train.py:55,95)
@@ -714,4 +715,397 @@ extern "C" int bdn_grad_norm(const float* grads, const uint32_t* seg_end, const 
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, nblk, grad_scale, max_norm, out);
     BDN_CHECK_LAUNCH("grad_norm_finish");
     return BDN_OK;
+}
+
+// ============================================================ layer-wise adaptive rules: LAMB (You et al. 2020) and LARS (You et al. 2017)
+// Both scale a tensor's update by a trust ratio formed from two norms of that tensor, so they need a norm per TENSOR between the moment
+// update and the parameter update.  The table here is per tensor, not per segment: ten_end (sorted ends in float4 units, tiling [0, n/4)
+// like seg_end), ten_len (the real element count: the last vector of a tensor is masked by it, a pad never enters a norm), ten_group
+// (0..n_groups-1, OPT_FROZEN for frozen) and ten_adapt (0: ratio 1).  Three launches, fixed:
+//   1 partial  block b owns the LW_CHUNK vectors [b LW_CHUNK, (b + 1) LW_CHUNK), as grad_norm_partial_kernel does, and writes one
+//              pair of doubles {sum p^2, sum x^2} per PIECE, the intersection of its chunk with one tensor, to part[2 (b + t)] (b + t is
+//              strictly increasing along the pieces, so no two pieces share a slot; there are fewer than blocks + tensors of them).  A
+//              chunk inside one tensor -- a large tensor spans many blocks -- is summed by the whole block: each lane sums its vectors
+//              in index order, a wave64 butterfly, thread 0 adds the four wave sums in wave order.  A chunk that holds several tensors
+//              -- a bias is 16 vectors -- hands its pieces to its four waves round robin: lanes stride the piece, one butterfly, lane 0
+//              writes.  Which path a piece takes depends on (n, table) alone.  LAMB: x = u, and the pass writes the new moments; LARS:
+//              x = g, nothing is written.
+//   2 finish   one wave per tensor: lane l adds the tensor's pieces l, l + 64, ... in chunk order, a butterfly, and lane 0 writes
+//              trust_out[t] = {wn, xn, applied ratio} (float32, rounded once from double); a frozen tensor gets {0, 0, 0} and none of
+//              its partials is read.
+//   3 apply    the grouped kernels' pass shape (LDS-staged table, OPT_VEC float4s per thread, every load before the first store); each
+//              vector takes its tensor's ratio from trust_out and its group's lr / weight_decay.  LAMB recomputes u from the NEW moments
+//              and the still-OLD parameter through lamb_u, the function pass 1 summed: the same bits, and no n-sized scratch.
+// No atomics, no memset, no host read-back, no block waits for another; a slot of `part` that no piece owns is never read, so the
+// result does not depend on what the workspace or trust_out held.  Every float32 is converted to double before it is squared.
+constexpr int LW_ROUNDS = 1;                                     // passes of OPT_VEC float4s per thread
+constexpr size_t LW_CHUNK = (size_t)256 * OPT_VEC * LW_ROUNDS;   // vectors per block: 1024 (16 KiB per buffer).  A quarter of the gradient norm's chunk:
+                                                                 // the pass does divisions and square roots between its loads and its sums, and
+                                                                 // 3272 short blocks at the model's size overlap them where 818 long ones did not
+static inline size_t lw_blocks(size_t n4) { return (n4 + LW_CHUNK - 1) / LW_CHUNK; }
+
+struct TenTable { const uint32_t* end; const uint32_t* len; const int32_t* group; const int32_t* adapt; int n_ten, n_groups; };
+
+struct LambParams { AdamParams a; float bc1, wd, lr; };
+struct LarsParams { SgdmParams s; };
+
+// LAMB's moments: adam_elem's statements for m and v, so that the state carries Adam's bits
+__device__ __forceinline__ void lamb_moments(float gr, float& m, float& v, const AdamParams& a) {
+    const float g = a.grad_scale * gr;
+    m = a.lerp_hi ? g - (g - m) * (1.f - a.w1) : m + a.w1 * (g - m);
+    v = a.beta2 * v + a.c2 * g * g;
+}
+// u = (m / bc1) / (sqrt(v)/sqrt(bc2) + eps) + wd * p: two IEEE divisions, a sqrt, an add and ONE explicit fma -- nothing the compiler may
+// contract one way in pass 1 and another way in pass 3
+__device__ __forceinline__ float lamb_u(float p, float m, float v, const LambParams& q) {
+    const float den = sqrtf(v) / q.a.bc2_sqrt + q.a.eps;
+    return fmaf(q.wd, p, (m / q.bc1) / den);
+}
+// LARS: sgdm_elem with d = local * (g + wd * p) in place of the decayed gradient (local == 1: sgdm_elem's bits)
+template <bool MOM>
+__device__ __forceinline__ void lars_elem(float& p, float gr, float& buf, float local, const SgdmParams& a) {
+    float g = a.grad_scale * gr;
+    if (a.weight_decay != 0.f) g = g + a.weight_decay * p;
+    g = local * g;
+    if (MOM) {
+        buf = a.first ? g : a.momentum * buf + a.damp1 * g;
+        g = a.nesterov ? g + a.momentum * buf : buf;
+    }
+    p = p - a.lr * g;
+}
+
+struct RuleLamb {
+    using Params = LambParams;
+    static constexpr bool LAMB = true, MOM = true;
+    static __device__ __forceinline__ void scale(Params& q, float s) { q.a.grad_scale *= s; }
+    static __device__ __forceinline__ bool reads_state(const Params&) { return true; }
+    // pass 1: the new moments, and the value whose square is summed
+    static __device__ __forceinline__ float first(float p, float gr, float& m, float& v, const Params& q) {
+        lamb_moments(gr, m, v, q.a);
+        return lamb_u(p, m, v, q);
+    }
+    static __device__ __forceinline__ void apply(float& p, float, float& m, float& v, float ratio, const Params& q) {
+        p = p - (q.lr * ratio) * lamb_u(p, m, v, q);
+    }
+};
+template <bool MOM_> struct RuleLars {
+    using Params = LarsParams;
+    static constexpr bool LAMB = false, MOM = MOM_;
+    static __device__ __forceinline__ void scale(Params& q, float s) { q.s.grad_scale *= s; }
+    static __device__ __forceinline__ bool reads_state(const Params& q) { return MOM_ && !q.s.first; }
+    static __device__ __forceinline__ float first(float, float gr, float&, float&, const Params& q) { return q.s.grad_scale * gr; }
+    static __device__ __forceinline__ void apply(float& p, float gr, float& buf, float&, float local, const Params& q) {
+        lars_elem<MOM_>(p, gr, buf, local, q.s);
+    }
+};
+
+// the table's ends and groups into LDS, padded to a power of two (seg_step's contract), and the per-group parameters beside them
+template <typename P>
+__device__ __forceinline__ int lw_stage(const TenTable& t, const GroupArgs<P>& a, uint32_t* s_end, int* s_grp, P* s_par) {
+    int cap = 1;
+    while (cap < t.n_ten) cap <<= 1;
+    for (int k = threadIdx.x; k < cap; k += 256) {
+        s_end[k] = k < t.n_ten ? t.end[k] : 0xffffffffu;
+        s_grp[k] = k < t.n_ten ? t.group[k] : OPT_FROZEN;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < OPT_MAX_GROUPS; k++) s_par[k] = a.g[k];
+    }
+    return cap;
+}
+
+// one vector of pass 1: the first `nvalid` elements enter the two sums (a pad is replaced by 0.0, whatever it holds)
+template <typename Rule>
+__device__ __forceinline__ void lw_sum_vec(const float4& P, const float4& G, float4& M, float4& V, int nvalid,
+                                           const typename Rule::Params& q, double& aw, double& ax) {
+    const float x0 = Rule::first(P.x, G.x, M.x, V.x, q), x1 = Rule::first(P.y, G.y, M.y, V.y, q);
+    const float x2 = Rule::first(P.z, G.z, M.z, V.z, q), x3 = Rule::first(P.w, G.w, M.w, V.w, q);
+    const double p0 = nvalid > 0 ? (double)P.x : 0.0, p1 = nvalid > 1 ? (double)P.y : 0.0;
+    const double p2 = nvalid > 2 ? (double)P.z : 0.0, p3 = nvalid > 3 ? (double)P.w : 0.0;
+    const double d0 = nvalid > 0 ? (double)x0 : 0.0, d1 = nvalid > 1 ? (double)x1 : 0.0;
+    const double d2 = nvalid > 2 ? (double)x2 : 0.0, d3 = nvalid > 3 ? (double)x3 : 0.0;
+    aw = fma(p0, p0, aw); aw = fma(p1, p1, aw); aw = fma(p2, p2, aw); aw = fma(p3, p3, aw);
+    ax = fma(d0, d0, ax); ax = fma(d1, d1, ax); ax = fma(d2, d2, ax); ax = fma(d3, d3, ax);
+}
+
+template <typename Rule>
+__global__ void __launch_bounds__(256) lw_partial_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                         float* __restrict__ s1, TenTable t, GroupArgs<typename Rule::Params> a,
+                                                         const float* __restrict__ dev_scale, double* __restrict__ part, size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS];
+    __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
+    __shared__ double s_wave[4][2];
+    const int cap = lw_stage(t, a, s_end, s_grp, s_par);
+    if (threadIdx.x == 0 && dev_scale) {
+        const float ds = *dev_scale;
+#pragma unroll
+        for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
+    }
+    __syncthreads();
+    const size_t c0 = (size_t)blockIdx.x * LW_CHUNK, c1 = c0 + LW_CHUNK < n4 ? c0 + LW_CHUNK : n4;
+    int t_lo = 0, t_hi = 0;
+    for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)c0, t_lo); seg_step(s_end, h, (uint32_t)(c1 - 1), t_hi); }
+    if (t_hi > t.n_ten - 1) t_hi = t.n_ten - 1;              // vectors behind the table's end belong to no tensor
+    const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+    float4* __restrict__ m4 = reinterpret_cast<float4*>(s0);
+    float4* __restrict__ v4 = reinterpret_cast<float4*>(s1);
+    if (t_lo >= t_hi) {
+        // ---- the chunk lies in one tensor: the whole block sums [lo, hi)
+        const int k = t_lo;
+        if (k > t.n_ten - 1) return;
+        const size_t start = k ? s_end[k - 1] : 0, end = s_end[k];
+        const size_t lo = start > c0 ? start : c0, hi = end < c1 ? end : c1;
+        const int grp = s_grp[k];
+        if (!(lo < hi) || (unsigned)grp >= (unsigned)t.n_groups) return;         // block-uniform: nobody reaches the barrier below
+        const typename Rule::Params q = s_par[grp];
+        const int tail = (int)(t.len[k] - 4u * (uint32_t)(end - 1 - start));      // real elements of the tensor's last vector
+        double aw = 0.0, ax = 0.0;
+        for (int r = 0; r < LW_ROUNDS; r++) {
+            float4 P[OPT_VEC] = {}, G[OPT_VEC] = {}, M[OPT_VEC] = {}, V[OPT_VEC] = {};
+#pragma unroll
+            for (int u = 0; u < OPT_VEC; u++) {
+                const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+                if (i >= lo && i < hi) {
+                    P[u] = p4[i]; G[u] = g4[i];
+                    if (Rule::LAMB) { M[u] = m4[i]; V[u] = v4[i]; }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < OPT_VEC; u++) {
+                const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+                if (i >= lo && i < hi) {
+                    lw_sum_vec<Rule>(P[u], G[u], M[u], V[u], i + 1 == end ? tail : 4, q, aw, ax);
+                    if (Rule::LAMB) { m4[i] = M[u]; v4[i] = V[u]; }
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) { aw += __shfl_xor(aw, m); ax += __shfl_xor(ax, m); }
+        if ((threadIdx.x & 63) == 0) { s_wave[threadIdx.x >> 6][0] = aw; s_wave[threadIdx.x >> 6][1] = ax; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double* o = part + 2 * ((size_t)blockIdx.x + k);
+            o[0] = ((s_wave[0][0] + s_wave[1][0]) + s_wave[2][0]) + s_wave[3][0];
+            o[1] = ((s_wave[0][1] + s_wave[1][1]) + s_wave[2][1]) + s_wave[3][1];
+        }
+        return;
+    }
+    // ---- the chunk holds several tensors: piece k goes to wave (k - t_lo) % 4
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = t_lo + wave; k <= t_hi; k += 4) {
+        const size_t start = k ? s_end[k - 1] : 0, end = s_end[k];
+        const size_t lo = start > c0 ? start : c0, hi = end < c1 ? end : c1;
+        const int grp = s_grp[k];
+        if (!(lo < hi) || (unsigned)grp >= (unsigned)t.n_groups) continue;        // wave-uniform
+        const typename Rule::Params q = s_par[grp];
+        const int tail = (int)(t.len[k] - 4u * (uint32_t)(end - 1 - start));
+        double aw = 0.0, ax = 0.0;
+        for (size_t i = lo + lane; i < hi; i += 64) {
+            const float4 P = p4[i], G = g4[i];
+            float4 M = {}, V = {};
+            if (Rule::LAMB) { M = m4[i]; V = v4[i]; }
+            lw_sum_vec<Rule>(P, G, M, V, i + 1 == end ? tail : 4, q, aw, ax);
+            if (Rule::LAMB) { m4[i] = M; v4[i] = V; }
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) { aw += __shfl_xor(aw, m); ax += __shfl_xor(ax, m); }
+        if (lane == 0) {
+            double* o = part + 2 * ((size_t)blockIdx.x + k);
+            o[0] = aw; o[1] = ax;
+        }
+    }
+}
+
+struct TrustArgs { float wd[OPT_MAX_GROUPS]; float trust_coef, lars_eps, max_trust; };
+
+// one wave per tensor: lane l adds the pieces l, l + 64, ... of its tensor in chunk order, then the butterfly (a serial chain over the 144
+// pieces of a bottleneck filter is 144 dependent memory latencies on the update's critical path)
+template <bool LAMB>
+__global__ void __launch_bounds__(64) lw_finish_kernel(const double* __restrict__ part, TenTable t, TrustArgs a, size_t nblk, size_t n4,
+                                                       float* __restrict__ trust_out) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const int grp = t.group[k];
+    float* o = trust_out + 3 * k;
+    if ((unsigned)grp >= (unsigned)t.n_groups) {             // block-uniform
+        if (lane == 0) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; }
+        return;
+    }
+    const size_t start = k ? t.end[k - 1] : 0;
+    size_t end = t.end[k];
+    if (end > n4) end = n4;
+    double sw = 0.0, sx = 0.0;
+    if (start < end) {
+        size_t b_hi = (end - 1) / LW_CHUNK;
+        if (b_hi > nblk - 1) b_hi = nblk - 1;
+        for (size_t b = start / LW_CHUNK + lane; b <= b_hi; b += 64) { sw += part[2 * (b + k)]; sx += part[2 * (b + k) + 1]; }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) { sw += __shfl_xor(sw, m); sx += __shfl_xor(sx, m); }
+    if (lane != 0) return;
+    const double wn = sqrt(sw), xn = sqrt(sx);
+    double ratio = 1.0;
+    if (wn > 0.0 && xn > 0.0)
+        ratio = LAMB ? wn / xn : (double)a.trust_coef * wn / (xn + (double)a.wd[grp] * wn + (double)a.lars_eps);
+    if (a.max_trust > 0.f && ratio > (double)a.max_trust) ratio = (double)a.max_trust;
+    if (t.adapt[k] == 0) ratio = 1.0;
+    o[0] = (float)wn; o[1] = (float)xn; o[2] = (float)ratio;
+}
+
+template <typename Rule>
+__global__ void __launch_bounds__(256) lw_apply_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                       float* __restrict__ s1, TenTable t, GroupArgs<typename Rule::Params> a,
+                                                       const float* __restrict__ dev_scale, const float* __restrict__ trust, size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS];
+    __shared__ float s_ratio[OPT_MAX_SEGS];
+    __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
+    const int cap = lw_stage(t, a, s_end, s_grp, s_par);
+    for (int k = threadIdx.x; k < cap; k += 256) s_ratio[k] = k < t.n_ten ? trust[3 * k + 2] : 0.f;
+    if (threadIdx.x == 0 && dev_scale) {
+        const float ds = *dev_scale;
+#pragma unroll
+        for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
+    }
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
+        int gid[OPT_VEC], ten[OPT_VEC], seg[OPT_VEC] = {};
+        for (int h = cap >> 1; h > 0; h >>= 1) {
+#pragma unroll
+            for (int u = 0; u < OPT_VEC; u++) {
+                const size_t first = b0 + u * stride;
+                seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), seg[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t first = b0 + u * stride, i = first + threadIdx.x;
+            int grp = OPT_FROZEN, s = seg[u];
+            if (i < n4) {
+                const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
+                if (!(s_end[s] > last)) {                    // the block's 256 vectors span a tensor boundary (or lie behind the table): per lane
+                    s = 0;
+                    for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+                }
+                if (s_end[s] > i) grp = s_grp[s];
+            }
+            ten[u] = s;
+            gid[u] = (unsigned)grp < (unsigned)t.n_groups ? grp : OPT_FROZEN;
+        }
+        float4 P[OPT_VEC], G[OPT_VEC] = {}, S0[OPT_VEC] = {}, S1[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (gid[u] != OPT_FROZEN) {
+                P[u] = reinterpret_cast<const float4*>(p)[i];
+                if (!Rule::LAMB) G[u] = reinterpret_cast<const float4*>(g)[i];
+                if (Rule::MOM && Rule::reads_state(s_par[0])) S0[u] = reinterpret_cast<const float4*>(s0)[i];
+                if (Rule::LAMB) S1[u] = reinterpret_cast<const float4*>(s1)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (gid[u] != OPT_FROZEN) {
+                const typename Rule::Params q = s_par[gid[u]];
+                const float r = s_ratio[ten[u]];
+                Rule::apply(P[u].x, G[u].x, S0[u].x, S1[u].x, r, q); Rule::apply(P[u].y, G[u].y, S0[u].y, S1[u].y, r, q);
+                Rule::apply(P[u].z, G[u].z, S0[u].z, S1[u].z, r, q); Rule::apply(P[u].w, G[u].w, S0[u].w, S1[u].w, r, q);
+                reinterpret_cast<float4*>(p)[i] = P[u];
+                if (!Rule::LAMB && Rule::MOM) reinterpret_cast<float4*>(s0)[i] = S0[u];
+            }
+        }
+    }
+}
+
+static int layerwise_check(const char* what, const void* params, const void* grads, const void* s0, const void* s1, const uint32_t* ten_end,
+                           const uint32_t* ten_len, const int32_t* ten_group, const int32_t* ten_adapt, int n_tensors, int n_groups,
+                           const float* lr, const float* weight_decay, const float* dev_scale, float max_trust, const void* workspace,
+                           const float* trust_out, size_t n) {
+    if (!params || !grads || !ten_end || !ten_len || !ten_group || !ten_adapt || !lr || !weight_decay || !workspace || !trust_out)
+        BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (n_groups < 1 || n_groups > OPT_MAX_GROUPS)
+        BDN_FAIL(BDN_E_ARG, "%s: %d groups (1..%d: their hyperparameters travel in the kernel arguments)", what, n_groups, OPT_MAX_GROUPS);
+    if (n_tensors < 1 || n_tensors > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d tensors (1..%d)", what, n_tensors, OPT_MAX_SEGS);
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)s0 | (uintptr_t)s1) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
+    if (((uintptr_t)ten_end | (uintptr_t)ten_len | (uintptr_t)ten_group | (uintptr_t)ten_adapt) & 3)
+        BDN_FAIL(BDN_E_ARG, "%s: tensor table must be 4-byte aligned", what);
+    if ((uintptr_t)dev_scale & 3) BDN_FAIL(BDN_E_ARG, "%s: dev_scale must be 4-byte aligned", what);
+    if ((uintptr_t)workspace & 7) BDN_FAIL(BDN_E_ARG, "%s: workspace must be 8-byte aligned", what);
+    if ((uintptr_t)trust_out & 3) BDN_FAIL(BDN_E_ARG, "%s: trust_out must be 4-byte aligned", what);
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
+    if (!(max_trust >= 0.f)) BDN_FAIL(BDN_E_ARG, "%s: max_trust = %g must be >= 0 (0: no clamp)", what, (double)max_trust);
+    return BDN_OK;
+}
+
+extern "C" size_t bdn_layerwise_workspace_bytes(size_t n, int n_tensors) {
+    const size_t slots = lw_blocks(n / 4) + (size_t)(n_tensors > 0 ? n_tensors : 0);
+    return (slots ? slots : 1) * 2 * sizeof(double);
+}
+
+template <typename Rule>
+static int layerwise_launch(const char* what, float* params, const float* grads, float* s0, float* s1, const TenTable& t,
+                            const GroupArgs<typename Rule::Params>& a, const TrustArgs& ta, const float* dev_scale, void* workspace,
+                            float* trust_out, size_t n, void* stream) {
+    const size_t n4 = n / 4, nblk = lw_blocks(n4);
+    hipLaunchKernelGGL(lw_partial_kernel<Rule>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const float*)params, grads, s0, s1,
+                       t, a, dev_scale, (double*)workspace, n4);
+    BDN_CHECK_LAUNCH(what);
+    hipLaunchKernelGGL(lw_finish_kernel<Rule::LAMB>, dim3((unsigned)t.n_ten), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, t, ta, nblk, n4,
+                       trust_out);
+    BDN_CHECK_LAUNCH(what);
+    hipLaunchKernelGGL(lw_apply_kernel<Rule>, dim3(opt_grid(n4)), dim3(256), 0, (hipStream_t)stream, params, grads, s0, s1, t, a, dev_scale,
+                       (const float*)trust_out, n4);
+    BDN_CHECK_LAUNCH(what);
+    return BDN_OK;
+}
+
+extern "C" int bdn_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* ten_end,
+                             const uint32_t* ten_len, const int32_t* ten_group, const int32_t* ten_adapt, int n_tensors, int n_groups,
+                             const float* lr, const float* weight_decay, float grad_scale, const float* dev_scale, double beta1,
+                             double beta2, float eps, float max_trust, long long step, void* workspace, float* trust_out, size_t n,
+                             void* stream) {
+    if (int rc = layerwise_check("lamb_step", params, grads, exp_avg, exp_avg_sq, ten_end, ten_len, ten_group, ten_adapt, n_tensors, n_groups,
+                                 lr, weight_decay, dev_scale, max_trust, workspace, trust_out, n)) return rc;
+    if (int rc = adam_rule_check("lamb_step", exp_avg, exp_avg_sq, step, beta1, beta2)) return rc;
+    if (!(eps >= 0.f)) BDN_FAIL(BDN_E_ARG, "lamb_step: eps = %g must be >= 0", (double)eps);
+    if (n == 0) return BDN_OK;
+    GroupArgs<LambParams> a{};
+    const double bc1 = 1.0 - std::pow(beta1, (double)step);
+    for (int k = 0; k < n_groups; k++)
+        a.g[k] = LambParams{adam_params(lr[k], weight_decay[k], grad_scale, beta1, beta2, eps, 1, step), (float)bc1, weight_decay[k], lr[k]};
+    TrustArgs ta{};
+    ta.max_trust = max_trust;
+    const TenTable t{ten_end, ten_len, ten_group, ten_adapt, n_tensors, n_groups};
+    return layerwise_launch<RuleLamb>("lamb_step", params, grads, exp_avg, exp_avg_sq, t, a, ta, dev_scale, workspace, trust_out, n, stream);
+}
+
+extern "C" int bdn_lars_step(float* params, const float* grads, float* momentum_buf, const uint32_t* ten_end, const uint32_t* ten_len,
+                             const int32_t* ten_group, const int32_t* ten_adapt, int n_tensors, int n_groups, const float* lr,
+                             const float* weight_decay, float grad_scale, const float* dev_scale, float momentum, float dampening,
+                             int nesterov, int first_step, float trust_coef, float lars_eps, float max_trust, void* workspace,
+                             float* trust_out, size_t n, void* stream) {
+    if (int rc = layerwise_check("lars_step", params, grads, momentum_buf, nullptr, ten_end, ten_len, ten_group, ten_adapt, n_tensors,
+                                 n_groups, lr, weight_decay, dev_scale, max_trust, workspace, trust_out, n)) return rc;
+    if (int rc = sgdm_rule_check("lars_step", momentum, momentum_buf, dampening, nesterov)) return rc;
+    if (!(trust_coef >= 0.f)) BDN_FAIL(BDN_E_ARG, "lars_step: trust_coef = %g must be >= 0", (double)trust_coef);
+    if (!(lars_eps >= 0.f)) BDN_FAIL(BDN_E_ARG, "lars_step: lars_eps = %g must be >= 0", (double)lars_eps);
+    if (n == 0) return BDN_OK;
+    GroupArgs<LarsParams> a{};
+    TrustArgs ta{};
+    for (int k = 0; k < n_groups; k++) {
+        a.g[k].s = sgdm_params(lr[k], weight_decay[k], grad_scale, momentum, dampening, nesterov, first_step);
+        ta.wd[k] = weight_decay[k];
+    }
+    for (int k = n_groups; k < OPT_MAX_GROUPS; k++) a.g[k].s.first = first_step ? 1 : 0;      // reads_state() asks entry 0 only; keep all alike
+    ta.trust_coef = trust_coef; ta.lars_eps = lars_eps; ta.max_trust = max_trust;
+    const TenTable t{ten_end, ten_len, ten_group, ten_adapt, n_tensors, n_groups};
+    if (momentum_buf)
+        return layerwise_launch<RuleLars<true>>("lars_step", params, grads, momentum_buf, nullptr, t, a, ta, dev_scale, workspace, trust_out,
+                                                n, stream);
+    return layerwise_launch<RuleLars<false>>("lars_step", params, grads, nullptr, nullptr, t, a, ta, dev_scale, workspace, trust_out, n, stream);
 }

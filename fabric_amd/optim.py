@@ -5,25 +5,38 @@ torch 2.10's single-tensor formulas (include/bidate_hip.h: bdn_sgd_momentum_step
 The step keeps its optimizer state in flat float32 buffers in the backward-order FlatLayout of the parameters (fabric_amd/parallel.py).
 torch.optim keys the same state by the index of the parameter in ``model.parameters()``.  The conversions between the two
 (``flat_to_torch`` / ``torch_to_flat``) are plain torch and run on any device, so they can be checked without a GPU.
+
+Two layer-wise adaptive rules go beyond torch.optim, which ships neither: 'lamb' (You et al., ICLR 2020) and 'lars' (You, Gitman, Ginsburg
+2017), include/bidate_hip.h: bdn_lamb_step, bdn_lars_step.  Each is a family of its own; its param_group is AdamW's / SGD's with a key
+'layer_adapt' and the rule's own hyperparameters added, so that a saved state identifies its rule.
 """
 import math
 
 import torch
 
-KINDS = ('sgd', 'adam', 'adamw')
-STATE_KEYS = {'sgd': ('momentum_buffer',), 'adam': ('exp_avg', 'exp_avg_sq')}
+KINDS = ('sgd', 'adam', 'adamw', 'lamb', 'lars')
+LAYERWISE = ('lamb', 'lars')
+STATE_KEYS = {'sgd': ('momentum_buffer',), 'adam': ('exp_avg', 'exp_avg_sq'), 'lamb': ('exp_avg', 'exp_avg_sq'), 'lars': ('momentum_buffer',)}
+_FAMILY = {'sgd': 'sgd', 'adam': 'adam', 'adamw': 'adam', 'lamb': 'lamb', 'lars': 'lars'}
+_STEPPED = ('adam', 'lamb')          # families whose per-parameter state carries a step count
+DEFAULT_BETAS = (0.9, 0.999)
 
 
 def _family(kind):
-    return 'sgd' if kind == 'sgd' else 'adam'
+    return _FAMILY[kind]
 
 
 class OptimConfig:
     """Validated hyperparameters of one update rule.  ``weight_decay=None`` is torch's default: 0 for sgd and adam, 1e-2 for adamw.
-    Unsupported torch options (amsgrad, maximize) and settings torch itself rejects raise ValueError."""
+    Unsupported torch options (amsgrad, maximize) and settings torch itself rejects raise ValueError.
 
-    def __init__(self, kind='sgd', lr=1e-3, momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999),
-                 eps=1e-8, amsgrad=False, maximize=False):
+    'lamb' takes betas, eps, weight_decay (decoupled, default 0) and refuses momentum / dampening / nesterov; 'lars' takes momentum,
+    dampening, nesterov, weight_decay and refuses betas other than the default.  Both take max_trust (None or 0: no clamp on the trust
+    ratio) and adapt_1d (False: tensors of ndim <= 1 -- biases, BatchNorm weight and bias -- take ratio 1, the usual practice); 'lars'
+    also trust_coef and lars_eps.  For the other kinds these four keep their defaults and are not used."""
+
+    def __init__(self, kind='sgd', lr=1e-3, momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=DEFAULT_BETAS,
+                 eps=1e-8, amsgrad=False, maximize=False, trust_coef=1e-3, lars_eps=1e-8, max_trust=None, adapt_1d=False):
         if kind not in KINDS:
             raise ValueError(f'optimizer {kind!r}: expected one of {KINDS}')
         if amsgrad:
@@ -32,10 +45,17 @@ class OptimConfig:
             raise ValueError('maximize is not supported by the fused step')
         if weight_decay is None:
             weight_decay = 1e-2 if kind == 'adamw' else 0.0
-        for name, v in (('lr', lr), ('momentum', momentum), ('dampening', dampening), ('weight_decay', weight_decay), ('eps', eps)):
+        if max_trust is None:
+            max_trust = 0.0
+        for name, v in (('lr', lr), ('momentum', momentum), ('dampening', dampening), ('weight_decay', weight_decay), ('eps', eps),
+                        ('trust_coef', trust_coef), ('lars_eps', lars_eps), ('max_trust', max_trust)):
+            if isinstance(v, bool) and name in ('trust_coef', 'lars_eps', 'max_trust'):
+                raise ValueError(f'invalid {name}: {v!r} (must be a finite number >= 0)')
             if not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
                 raise ValueError(f'invalid {name}: {v!r} (must be a finite number >= 0)')
-        if kind == 'sgd':
+        if not isinstance(adapt_1d, (bool, int)):
+            raise ValueError(f'invalid adapt_1d: {adapt_1d!r} (must be a bool)')
+        if kind in ('sgd', 'lars'):
             if nesterov and (momentum <= 0 or dampening != 0):
                 raise ValueError('nesterov needs momentum > 0 and zero dampening')
         elif momentum != 0 or dampening != 0 or nesterov:
@@ -43,9 +63,16 @@ class OptimConfig:
         betas = tuple(float(b) for b in betas)
         if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
             raise ValueError(f'invalid betas {betas!r}: two values in [0, 1)')
+        if kind == 'lars' and betas != DEFAULT_BETAS:
+            raise ValueError(f'betas belong to adam / adamw / lamb, not lars (got {betas!r})')
+        if kind not in LAYERWISE and (trust_coef != 1e-3 or lars_eps != 1e-8 or max_trust != 0 or adapt_1d):
+            raise ValueError(f'trust_coef / lars_eps / max_trust / adapt_1d belong to lamb and lars, not {kind}')
+        if kind == 'lamb' and (trust_coef != 1e-3 or lars_eps != 1e-8):
+            raise ValueError('trust_coef / lars_eps belong to lars, not lamb')
         self.kind, self.lr = kind, float(lr)
         self.momentum, self.dampening, self.nesterov = float(momentum), float(dampening), bool(nesterov)
         self.weight_decay, self.betas, self.eps = float(weight_decay), betas, float(eps)
+        self.trust_coef, self.lars_eps, self.max_trust, self.adapt_1d = float(trust_coef), float(lars_eps), float(max_trust), bool(adapt_1d)
 
     @property
     def family(self):
@@ -58,25 +85,47 @@ class OptimConfig:
 
     def state_keys(self):
         """Names of the per-parameter state buffers this rule keeps (none for SGD without momentum)."""
-        if self.kind == 'sgd':
-            return STATE_KEYS['sgd'] if self.momentum != 0 else ()
-        return STATE_KEYS['adam']
+        if self.kind in ('sgd', 'lars'):
+            return STATE_KEYS[self.kind] if self.momentum != 0 else ()
+        return STATE_KEYS[self.family]
+
+    @property
+    def stepped(self):
+        """The per-parameter state carries a step count (Adam's families and LAMB)."""
+        return self.family in _STEPPED
 
     def param_group(self, params):
         """torch 2.10's param_group for this rule (``params``: parameter indices)."""
-        if self.kind == 'sgd':
+        if self.kind in ('sgd', 'lars'):
             g = dict(lr=self.lr, momentum=self.momentum, dampening=self.dampening, weight_decay=self.weight_decay,
                      nesterov=self.nesterov, maximize=False, foreach=None, differentiable=False, fused=None)
         else:
             g = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, amsgrad=False, maximize=False,
                      foreach=None, capturable=False, differentiable=False, fused=None,
-                     decoupled_weight_decay=self.kind == 'adamw')
+                     decoupled_weight_decay=self.kind in ('adamw', 'lamb'))
+        if self.kind in LAYERWISE:
+            g.update(layer_adapt=self.kind, max_trust=self.max_trust, adapt_1d=self.adapt_1d)
+        if self.kind == 'lars':
+            g.update(trust_coef=self.trust_coef, lars_eps=self.lars_eps)
         g['params'] = list(params)
         return g
 
     @classmethod
     def from_param_group(cls, group):
-        """The rule a torch SGD / Adam / AdamW param_group describes ('betas' marks the Adam family, decoupled_weight_decay AdamW)."""
+        """The rule a torch SGD / Adam / AdamW param_group describes ('betas' marks the Adam family, decoupled_weight_decay AdamW), or,
+        with a key 'layer_adapt', the LAMB / LARS rule that param_group() wrote."""
+        la = group.get('layer_adapt')
+        if la is not None:
+            if la not in LAYERWISE:
+                raise ValueError(f"unrecognised layer_adapt {la!r} in the optimizer param_group: expected one of {LAYERWISE}")
+            extra = dict(max_trust=group.get('max_trust', 0.0) or None, adapt_1d=group.get('adapt_1d', False),
+                         amsgrad=group.get('amsgrad', False), maximize=group.get('maximize', False))
+            if la == 'lamb':
+                return cls('lamb', lr=group['lr'], weight_decay=group.get('weight_decay', 0.0), betas=group.get('betas', DEFAULT_BETAS),
+                           eps=group.get('eps', 1e-8), **extra)
+            return cls('lars', lr=group['lr'], momentum=group.get('momentum', 0.0), dampening=group.get('dampening', 0.0),
+                       nesterov=group.get('nesterov', False), weight_decay=group.get('weight_decay', 0.0),
+                       trust_coef=group.get('trust_coef', 1e-3), lars_eps=group.get('lars_eps', 1e-8), **extra)
         if 'betas' in group:
             kind = 'adamw' if group.get('decoupled_weight_decay', False) else 'adam'
             return cls(kind, lr=group['lr'], weight_decay=group.get('weight_decay', 0.0), betas=group['betas'],
@@ -148,7 +197,7 @@ def flat_to_torch(cfg, layout, names, flat_state, step):
     if keys and step > 0:
         for i, k in enumerate(names):
             s = {key: layout.view(flat_state[key], k).clone() for key in keys}
-            if cfg.family == 'adam':
+            if cfg.stepped:
                 s = {'step': torch.tensor(float(step), dtype=torch.float32), **s}
             state[i] = s
     return {'state': state, 'param_groups': [cfg.param_group(range(len(names)))]}
@@ -185,19 +234,19 @@ def torch_to_flat(sd, layout, names, device=None):
         shape = layout.slices[name][2]
         if set(s) - {'step'} != set(keys):
             raise ValueError(f'parameter {pid} ({name}): state keys {sorted(s)}, expected {sorted(keys)}'
-                             + (' and step' if cfg.family == 'adam' else ''))
+                             + (' and step' if cfg.stepped else ''))
         for key in keys:
             if tuple(s[key].shape) != shape:
                 raise ValueError(f'parameter {pid} ({name}): {key} has shape {tuple(s[key].shape)}, the parameter {shape}')
             layout.view(flat[key], name).copy_(s[key].detach().to(device=device, dtype=torch.float32))
-        if cfg.family == 'adam':
+        if cfg.stepped:
             st = s.get('step')
             if st is None:
                 raise ValueError(f'parameter {pid} ({name}): no step in the Adam state')
             steps.add(float(st))
     if len(steps) > 1:
         raise ValueError(f'parameters were stepped different numbers of times ({sorted(steps)}): the flat state needs one count')
-    if cfg.family == 'adam':
+    if cfg.stepped:
         step = int(steps.pop()) if steps else 0
     else:
         step = 1 if present else 0
@@ -296,6 +345,22 @@ def segment_table(layout, groups):
     return ends, ids
 
 
+def tensor_table(layout, groups, adapt_1d=False):
+    """(ends, lens, ids, adapt) of bdn_lamb_step's / bdn_lars_step's per-tensor table for ``layout`` and ``groups`` (ParamGroups): four int32
+    torch tensors (CPU) with one entry per tensor in layout order -- the tensor's end in float4 units (they tile [0, layout.total / 4)),
+    its real element count, its group id (FROZEN for a frozen tensor) and its adapt flag: 1 when the trust ratio applies, 0 (ratio 1)
+    for a tensor of ndim <= 1 unless ``adapt_1d``.  ``ends`` holds uint32 values in int32 storage, as the segment table does."""
+    ends, lens, ids, adapt = [], [], [], []
+    for i, k in enumerate(layout.order):
+        off, n, shape = layout.slices[k]
+        ends.append((layout.slices[layout.order[i + 1]][0] if i + 1 < len(layout.order) else layout.total) // 4)
+        lens.append(n)
+        ids.append(groups.group_id(k))
+        adapt.append(int(bool(adapt_1d) or len(shape) > 1))
+    as32 = lambda v: torch.tensor(v, dtype=torch.int64).to(torch.int32)
+    return as32(ends), as32(lens), as32(ids), as32(adapt)
+
+
 def groups_to_torch(cfg, groups, layout, flat_state, step):
     """torch.optim's ``state_dict()`` of a grouped step: what ``torch.optim.{SGD,Adam,AdamW}`` built with the same param groups holds.
     One 'param_groups' entry per group with torch 2.10's keys; a parameter is identified by its index in ``model.parameters()``
@@ -308,7 +373,7 @@ def groups_to_torch(cfg, groups, layout, flat_state, step):
     if keys and step > 0:
         for k in groups.trainable():
             s = {key: layout.view(flat_state[key], k).clone() for key in keys}
-            if cfg.family == 'adam':
+            if cfg.stepped:
                 s = {'step': torch.tensor(float(step), dtype=torch.float32), **s}
             state[index[k]] = s
     out = []
@@ -366,18 +431,18 @@ def torch_to_groups(sd, groups, layout, device=None):
         shape = layout.slices[name][2]
         if set(s) - {'step'} != set(keys):
             raise ValueError(f'parameter {pid} ({name}): state keys {sorted(s)}, expected {sorted(keys)}'
-                             + (' and step' if cfg.family == 'adam' else ''))
+                             + (' and step' if cfg.stepped else ''))
         for key in keys:
             if tuple(s[key].shape) != shape:
                 raise ValueError(f'parameter {pid} ({name}): {key} has shape {tuple(s[key].shape)}, the parameter {shape}')
             layout.view(flat[key], name).copy_(s[key].detach().to(device=device, dtype=torch.float32))
-        if cfg.family == 'adam':
+        if cfg.stepped:
             if s.get('step') is None:
                 raise ValueError(f'parameter {pid} ({name}): no step in the Adam state')
             steps.add(float(s['step']))
     if len(steps) > 1:
         raise ValueError(f'parameters were stepped different numbers of times ({sorted(steps)}): the flat state needs one count')
-    if cfg.family == 'adam':
+    if cfg.stepped:
         step = int(steps.pop()) if steps else 0
     else:
         step = 1 if present else 0

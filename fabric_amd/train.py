@@ -13,6 +13,7 @@ polyaxon), the GCS download and checkpoint upload of the reference are out of sc
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+lovasz --focal_gamma 0       # cross-entropy + Lovasz-Softmax
     python -m fabric_amd.train --synthetic --fused_step true --loss_function focal+dice --focal_gamma 2 --boundary_weight 0.01      # + the boundary term
     python -m fabric_amd.train --synthetic --fused_step true --optimizer adamw --ema_decay 0.999        # validate and save the averaged weights
+    python -m fabric_amd.train --synthetic --fused_step true --optimizer lamb --lr_warmup_updates 4 --lr_schedule cosine   # layer-wise trust ratios
     python -m fabric_amd.train --metadata metadata.json --val_curve_bins 1024 --scene_stride 64 --scene_threshold val      # best-F1 threshold, AP
 
 With real data the loop also does what train.py:182-205 does after validation: the full validation scenes are
@@ -138,9 +139,12 @@ def batch_accuracy(counts, n_pixels):
     return 100.0 * int(counts[3]) / n if n else 0.0
 
 
-def train_epoch(step, loader, dev, patch_size, feeder=None):
+def train_epoch(step, loader, dev, patch_size, feeder=None, schedule=None, epoch=0):
     """train.py:73-118 without the per-step host round trip: losses / counts are read back once per epoch, and the
-    host -> device copies of batch k+1 (train.py:83-85) run on a copy stream under the step of batch k."""
+    host -> device copies of batch k+1 (train.py:83-85) run on a copy stream under the step of batch k.
+    schedule: None, or a fabric_amd.schedule.LRSchedule: the learning rates of the update batch i of `epoch` belongs to are set before
+    each call (host floats only).  With --optimizer lamb / lars the result gains trust_min / trust_max, the adapted tensors' ratios at
+    the epoch's last update (one read of step.last_trust per epoch)."""
     from .device_loader import DevicePatchLoader
     from .input_pipeline import DeviceFeeder
     step.model.train()
@@ -153,7 +157,9 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
     if not isinstance(loader, DevicePatchLoader):
         feeder = feeder or DeviceFeeder(dev)
     with torch.cuda.stream(step.stream()):                # the loop lives on the step's own stream: no joins per step
-        for b1, b2, labels in _device_batches(loader, dev, feeder):
+        for i, (b1, b2, labels) in enumerate(_device_batches(loader, dev, feeder)):
+            if schedule is not None:
+                schedule.apply(step, schedule.position(epoch, i, len(loader), step.accumulate))
             loss = step.step(b1, b2, labels)
             recs.append((loss, step.last_counts.clone(), labels.shape[0]))
             if topk:
@@ -183,6 +189,10 @@ def train_epoch(step, loader, dev, patch_size, feeder=None):
     if norms:                                             # --max_grad_norm: read back once per epoch, beside the losses
         nc = torch.stack([torch.stack(v) for v in norms]).cpu()
         out.update(grad_norm_mean=float(nc[:, 0].mean()), grad_norm_max=float(nc[:, 0].max()), clipped_frac=float((nc[:, 1] < 1).float().mean()))
+    if step.optim.kind in ('lamb', 'lars'):               # --optimizer lamb / lars: the adapted tensors' trust ratios at the last update
+        ratios = list(step.trust_ratios(adapted_only=True).values())
+        if ratios:
+            out.update(trust_min=min(ratios), trust_max=max(ratios))
     return out
 
 
@@ -239,8 +249,16 @@ def train_epoch_autograd(model, criterion, optimizer, loader, dev, patch_size, w
 
 def optimizer_kwargs(opt):
     """The update rule of the --optimizer / --momentum / --nesterov / --weight_decay / --betas / --adam_eps flags as TrainStep keywords."""
-    return dict(optimizer=opt.optimizer, momentum=opt.momentum, nesterov=opt.nesterov, weight_decay=opt.weight_decay,
-                betas=tuple(opt.betas), adam_eps=opt.adam_eps)
+    kw = dict(optimizer=opt.optimizer, momentum=opt.momentum, nesterov=opt.nesterov, weight_decay=opt.weight_decay,
+              betas=tuple(opt.betas), adam_eps=opt.adam_eps)
+    if opt.optimizer in ('lamb', 'lars'):                 # the layer-wise rules' own flags (the fused step only)
+        kw.update(layerwise_kwargs(opt))
+    return kw
+
+
+def layerwise_kwargs(opt):
+    """--trust_coef / --lars_eps / --max_trust / --adapt_1d as OptimConfig / TrainStep keywords."""
+    return dict(trust_coef=opt.trust_coef, lars_eps=opt.lars_eps, max_trust=opt.max_trust, adapt_1d=opt.adapt_1d)
 
 
 def make_torch_optimizer(params, lr, optimizer='sgd', momentum=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8):
@@ -464,8 +482,18 @@ def main(argv=None):
                          'train_topk_kept_frac and train_topk_threshold_mean')
     ap.add_argument('--synthetic_ignore_frac', type=float, default=0.1,
                     help='--synthetic with --ignore_label V: the fraction of every label raster painted with V')
-    ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam', 'adamw'],
-                    help='sgd is train.py:55 (optim.SGD); adam / adamw the torch.optim rules (train.py:56 is a commented-out Adam)')
+    ap.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam', 'adamw', 'lamb', 'lars'],
+                    help='sgd is train.py:55 (optim.SGD); adam / adamw the torch.optim rules (train.py:56 is a commented-out Adam); lamb / '
+                         'lars the layer-wise adaptive rules for large batches (fused step only: there is no autograd route for them)')
+    ap.add_argument('--trust_coef', type=float, default=1e-3, help='lars: the trust coefficient')
+    ap.add_argument('--lars_eps', type=float, default=1e-8, help='lars: the epsilon in the denominator of the local rate')
+    ap.add_argument('--max_trust', type=float, default=None, metavar='X', help='lamb / lars: clamp every trust ratio at X (default: no clamp)')
+    ap.add_argument('--adapt_1d', action='store_true', help='lamb / lars: adapt biases and BatchNorm weights / biases too (default: ratio 1)')
+    ap.add_argument('--lr_warmup_updates', type=int, default=0, metavar='N',
+                    help='fused step: ramp the learning rate linearly from lr/N to lr over the first N updates')
+    ap.add_argument('--lr_schedule', default='constant', choices=['constant', 'cosine'],
+                    help='fused step: cosine decays the learning rate to --lr_min at the last update of the run')
+    ap.add_argument('--lr_min', type=float, default=0.0, help='--lr_schedule cosine: the learning rate of the last update')
     ap.add_argument('--momentum', type=float, default=0.0, help='sgd only')
     ap.add_argument('--nesterov', action='store_true', help='sgd only, needs --momentum')
     ap.add_argument('--weight_decay', type=float, default=None, help="default: torch's (0 for sgd and adam, 1e-2 for adamw)")
@@ -581,9 +609,14 @@ def main(argv=None):
     from .optim import OptimConfig
     try:
         OptimConfig(opt.optimizer, lr=opt.learning_rate, momentum=opt.momentum, nesterov=opt.nesterov, weight_decay=opt.weight_decay,
-                    betas=opt.betas, eps=opt.adam_eps)
+                    betas=opt.betas, eps=opt.adam_eps, **layerwise_kwargs(opt))
     except ValueError as e:
         raise SystemExit(f'--optimizer {opt.optimizer}: {e}')
+    layerwise = opt.optimizer in ('lamb', 'lars')
+    scheduled = opt.lr_warmup_updates != 0 or opt.lr_schedule != 'constant' or opt.lr_min != 0.0
+    if (layerwise or scheduled) and opt.loss_function != 'tversky' and not opt.fused_step:
+        raise SystemExit(f'--optimizer lamb / lars and --lr_warmup_updates / --lr_schedule / --lr_min are built into the fused step, which '
+                         f'runs --loss_function tversky only (got {opt.loss_function}) unless --fused_step true is given')
     grouped = bool(opt.freeze or opt.frozen_bn or opt.no_decay_norm_bias or opt.lr_scale)
     if grouped and opt.loss_function != 'tversky' and not opt.fused_step:
         raise SystemExit(f'--freeze / --frozen_bn / --no_decay_norm_bias / --lr_scale are built into the fused step, which runs '
@@ -706,9 +739,20 @@ def main(argv=None):
         from .utils.metrics import ScoreCurve
         val_curve = ScoreCurve(opt.val_curve_bins, 1, opt.ignore_label)
     run_meta = dict(meta, **{k: getattr(opt, k) for k in DEFAULTS}, precision=opt.precision, world_size=world)
+    schedule = None
+    if scheduled:                                          # host floats only; its position comes from (epoch, batch), so --resume continues it
+        from .schedule import LRSchedule
+        try:
+            schedule = LRSchedule(opt.learning_rate, opt.epochs * LRSchedule.updates_per_epoch(len(train_loader), opt.accumulate),
+                                  opt.lr_warmup_updates, opt.lr_schedule, opt.lr_min,
+                                  None if groups is None else [g['lr'] for g in groups])      # the flags' values, not a resumed state's
+        except ValueError as e:
+            raise SystemExit(f'--lr_warmup_updates / --lr_schedule / --lr_min: {e}')
     for epoch in range(first_epoch, opt.epochs):
         train_loader.sampler.set_epoch(epoch)
-        if fused:
+        if fused and schedule is not None:
+            tr = train_epoch(step, train_loader, dev, opt.patch_size, feeder, schedule, epoch)
+        elif fused:
             tr = train_epoch(step, train_loader, dev, opt.patch_size, feeder)
         else:
             tr = train_epoch_autograd(model, criterion, optimizer, train_loader, dev, opt.patch_size, world, feeder)

@@ -1,7 +1,7 @@
 """The train.py step (reference train.py:83-101 + optim.SGD, train.py:55) as one fused schedule:
 
     to-device tensors -> forward -> Tversky loss, or the `criterion` given (+ argmax TP/FP/FN counts) -> backward
-    -> bucketed gradient all-reduce overlapped with backward -> SGD (or momentum SGD / Adam / AdamW: fabric_amd/optim.py)
+    -> bucketed gradient all-reduce overlapped with backward -> SGD (or momentum SGD / Adam / AdamW / LAMB / LARS: fabric_amd/optim.py)
 
 with no host synchronisation inside the step (the reference syncs every step for sklearn
 P/R/F1 and a comet upload, train.py:103-115; here the counts stay on the device).
@@ -26,11 +26,19 @@ class TrainStep:
                  process_group=None, n_buckets=4, distributed=True, force_collectives=False, guard=True,
                  optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8,
                  param_groups=None, bn='batch', criterion=None, accumulate=1, max_grad_norm=None,
-                 ema_decay=None, average='ema', ema_every=1, ema_start=0, ema_buffers=True):
+                 ema_decay=None, average='ema', ema_every=1, ema_start=0, ema_buffers=True,
+                 trust_coef=1e-3, lars_eps=1e-8, max_trust=None, adapt_1d=False):
         """optimizer: 'sgd' (torch.optim.SGD: momentum, dampening, nesterov, weight_decay), 'adam' or 'adamw' (torch.optim.Adam / AdamW:
         betas, adam_eps, weight_decay); weight_decay=None is torch's default (0 for sgd and adam, 1e-2 for adamw).  The default, plain
         SGD, is the reference's optim.SGD(lr) (train.py:55) and keeps no state; the other rules keep theirs in flat f32 buffers in the
         gradient layout (`opt_state`), with `opt_step` the number of updates applied.  `lr` may be reassigned between steps.
+        'lamb' (betas, adam_eps, decoupled weight_decay, max_trust) and 'lars' (momentum, dampening, nesterov, weight_decay, trust_coef,
+        lars_eps, max_trust) scale every tensor's update by a trust ratio (fabric_amd/optim.py; bdn_lamb_step / bdn_lars_step: three
+        launches, no host round trip).  adapt_1d=False: tensors of ndim <= 1 take ratio 1.  They always run on the per-tensor table
+        (with groups and frozen parameters, or one implicit group), compose with accumulate, max_grad_norm (the clip coefficient
+        reaches the rule on the device), the averaged weights and data-parallel runs (every rank forms the same norms from the
+        all-reduced gradients).  `last_trust` is the device [n_tensors, 3] tensor {||p||, ||u|| or ||g||, applied ratio} of the last
+        update, in layout order, {0, 0, 0} for a frozen tensor; trust_ratios() reads it on demand.
 
         param_groups: None (one set of hyperparameters, today's kernels), or a list of dicts {'params': [state-dict names or the
         nn.Parameter objects], 'lr': ..., 'weight_decay': ...} as torch.optim takes them (a missing key takes the step's value; at most 8
@@ -117,7 +125,9 @@ class TrainStep:
         self.last_grad_norm = self.last_clip_coef = None
         self.model, self.lr, self.bn = model, lr, bn
         self.optim = _optim.OptimConfig(optimizer, lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
-                                        weight_decay=weight_decay, betas=betas, eps=adam_eps)
+                                        weight_decay=weight_decay, betas=betas, eps=adam_eps, trust_coef=trust_coef, lars_eps=lars_eps,
+                                        max_trust=max_trust, adapt_1d=adapt_1d)
+        self._lw, self.last_trust = None, None
         self._guard = guard
         self.collectives_report = None
         self.alpha, self.beta, self.eps = tversky_alpha, tversky_beta, eps
@@ -182,6 +192,8 @@ class TrainStep:
                 self._implicit_table()                       # uploaded now: the step itself never waits for the device
         if ema_on:
             self._init_average()
+        if self.optim.kind in _optim.LAYERWISE:
+            self._layerwise_table()                          # uploaded now: the step itself never waits for the device
         self._grads_version = self.flat_grads._version
 
     def _implicit_table(self):
@@ -195,6 +207,48 @@ class TrainStep:
             self._clip_table = (pg, (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev),
                                      torch.tensor(ids, dtype=torch.int32).to(dev), len(ends)))
         return self._clip_table
+
+    def _layerwise_groups(self):
+        """The ParamGroups the layer-wise rules run on: the step's, or the one implicit group of every parameter, following the step's
+        lr / weight_decay as the clipped update's does."""
+        if self._groups is not None:
+            pg = self._groups
+            if self._implicit_group:
+                pg.groups[0]['lr'] = float(self.lr)
+        else:
+            pg = self._implicit_table()[0]
+            pg.groups[0]['lr'], pg.groups[0]['weight_decay'] = float(self.lr), self.optim.weight_decay
+        return pg
+
+    def _layerwise_table(self):
+        """(groups, the four device arrays of the per-tensor table, n_tensors, workspace, trust_out) of bdn_lamb_step / bdn_lars_step,
+        rebuilt and uploaded when the groups object or adapt_1d changed (set_param_groups, a loaded state), never per step.  trust_out
+        is `last_trust`."""
+        pg = self._layerwise_groups()
+        if self._lw is None or self._lw[0] is not pg or self._lw[5] != self.optim.adapt_1d:
+            dev = self.flat_params.device
+            n_ten = len(self.layout.order)
+            table = tuple(t.to(dev) for t in _optim.tensor_table(self.layout, pg, self.optim.adapt_1d))
+            ws = torch.empty(_lib.load().bdn_layerwise_workspace_bytes(self.layout.total, n_ten) // 8, dtype=torch.float64, device=dev)
+            self.last_trust = torch.zeros(n_ten, 3, dtype=torch.float32, device=dev)
+            self._lw = (pg, table, n_ten, ws, self.last_trust, self.optim.adapt_1d)
+        return self._lw
+
+    def trust_ratios(self, adapted_only=False):
+        """{parameter name: the trust ratio applied at the last update} for every trainable parameter (1.0 where the rule does not adapt:
+        ndim <= 1 without adapt_1d, a zero norm); adapted_only: only the tensors whose adapt flag is set.  One host read of
+        `last_trust`, on demand only; empty before the first update."""
+        if self.optim.kind not in _optim.LAYERWISE:
+            raise RuntimeError(f'trust_ratios(): optimizer {self.optim.kind!r} has no trust ratios (lamb and lars do)')
+        if self.opt_step == 0 or self.last_trust is None:
+            return {}
+        dev = self.flat_params.device
+        torch.cuda.current_stream(dev).wait_stream(self.stream(dev))
+        pg = self._layerwise_table()[0]
+        r = self.last_trust[:, 2].tolist()
+        every = not adapted_only or self.optim.adapt_1d
+        return {k: r[i] for i, k in enumerate(self.layout.order)
+                if pg.group_id(k) != _optim.FROZEN and (every or len(self.layout.slices[k][2]) > 1)}
 
     def _init_average(self, rebind=False):
         """flat_avg (a clone of flat_params), and with ema_buffers the averaged running statistics: views of one flat buffer, a scratch
@@ -284,6 +338,8 @@ class TrainStep:
         if pg is None:
             self.param_groups = self._groups = self._seg = self._need = None
             self._implicit_group = False
+            if self.optim.kind in _optim.LAYERWISE:
+                self._layerwise_table()
             return
         ends, ids = _optim.segment_table(self.layout, pg)
         seg = (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev), torch.tensor(ids, dtype=torch.int32).to(dev), len(ends))
@@ -302,6 +358,8 @@ class TrainStep:
         self.param_groups = pg.groups
         self._implicit_group = groups is None
         self._need = set(pg.trainable()) if frozen else None
+        if self.optim.kind in _optim.LAYERWISE:
+            self._layerwise_table()
 
     def _checked_groups(self, groups):
         """fabric_amd.optim.ParamGroups of `groups` (names or nn.Parameter objects) and the parameters' requires_grad flags as they are
@@ -730,6 +788,8 @@ class TrainStep:
         of accumulated micro-steps): per-rank loss, averaged gradients (standard DDP).  Host-side scalars only: the step
         count is a Python int, nothing syncs."""
         o, n = self.optim, self.layout.total
+        if o.kind in _optim.LAYERWISE:
+            return self._update_layerwise(st, grad_scale)
         if self._groups is not None:
             return self._update_grouped(st, grad_scale)
         if o.plain:                                          # p -= lr * g: the reference's optim.SGD(lr)
@@ -750,6 +810,8 @@ class TrainStep:
         """_update through bdn_*_step_grouped: per-group lr / weight_decay read from `param_groups` now, frozen segments skipped.
         dev_scale: None, or the device address of the clip coefficient: the _ex entry points, g = (grad_scale * coefficient) * grad."""
         o, n = self.optim, self.layout.total
+        if o.kind in _optim.LAYERWISE:
+            return self._update_layerwise(st, grad_scale, dev_scale)
         if self._groups is not None:
             pg, seg = self._groups, self._seg
             if self._implicit_group:
@@ -775,6 +837,25 @@ class TrainStep:
             _lib.call('bdn_adam_step_grouped' + ex, self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state['exp_avg'].data_ptr(),
                       self.opt_state['exp_avg_sq'].data_ptr(), *table, lr, wd, grad_scale, *ds, o.betas[0], o.betas[1], o.eps,
                       int(o.kind == 'adamw'), self.opt_step, n, st)
+
+    def _update_layerwise(self, st, grad_scale, dev_scale=None):
+        """_update through bdn_lamb_step / bdn_lars_step: always on the per-tensor table, per-group lr / weight_decay read now, the
+        clip coefficient (dev_scale, or None) multiplied in on the device."""
+        o, n = self.optim, self.layout.total
+        pg, (ends, lens, ids, adapt), n_ten, ws, trust, _ = self._layerwise_table()
+        lrs, wds = pg.hyper('lr'), pg.hyper('weight_decay')
+        table = (ends.data_ptr(), lens.data_ptr(), ids.data_ptr(), adapt.data_ptr(), n_ten, len(lrs))
+        lr, wd = _lib.floats(lrs), _lib.floats(wds)
+        first = self.opt_step == 0
+        self.opt_step += 1
+        if o.kind == 'lamb':
+            _lib.call('bdn_lamb_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.opt_state['exp_avg'].data_ptr(),
+                      self.opt_state['exp_avg_sq'].data_ptr(), *table, lr, wd, grad_scale, dev_scale, o.betas[0], o.betas[1], o.eps,
+                      o.max_trust, self.opt_step, ws.data_ptr(), trust.data_ptr(), n, st)
+        else:
+            _lib.call('bdn_lars_step', self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
+                      _lib.ptr(self.opt_state.get('momentum_buffer')), *table, lr, wd, grad_scale, dev_scale, o.momentum, o.dampening,
+                      int(o.nesterov), int(first), o.trust_coef, o.lars_eps, o.max_trust, ws.data_ptr(), trust.data_ptr(), n, st)
 
     # ------------------------------------------------------------------ optimizer state in torch.optim's format
     def optimizer_state_dict(self):
@@ -820,6 +901,8 @@ class TrainStep:
                     g.update(h)
                 cfg.lr, cfg.weight_decay = hyper[0]['lr'], hyper[0]['weight_decay']
         self.optim, self.lr, self.opt_state, self.opt_step = cfg, cfg.lr, flat, step
+        if cfg.kind in _optim.LAYERWISE:
+            self._layerwise_table()                          # adapt_1d is the saved rule's now
 
     # ------------------------------------------------------------------ averaged weights in torch.optim.swa_utils.AveragedModel's format
     def _avg_entries(self):

@@ -717,6 +717,46 @@ size_t bdn_grad_norm_workspace_bytes(size_t n);
 int bdn_grad_norm(const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float grad_scale, float max_norm,
                   void* workspace, float* out, size_t n, void* stream);
 
+/* ---- layer-wise adaptive updates: LAMB (You et al., ICLR 2020) and LARS (You, Gitman, Ginsburg 2017) over the flat f32 buffers.
+ * Both read g = (grad_scale * *dev_scale) * grads (dev_scale: DEVICE float, 4-byte aligned, or NULL = 1) and scale each TENSOR's update
+ * by a trust ratio formed from two norms of that tensor, taken before any parameter changes.
+ * LAMB (state exp_avg, exp_avg_sq; step as in bdn_adam_step; the moments are that entry's statements, so the state carries its bits):
+ *   m = m + (1-beta1)*(g-m); v = beta2*v + (1-beta2)*g*g; r = (m / bc1) / (sqrt(v)/sqrt(bc2) + eps), bc_i = 1 - beta_i^step formed in
+ *   double on the host; u = r + wd_group*p.  Per tensor t: wn = ||p_t||, un = ||u_t||; ratio = wn/un if wn > 0 and un > 0, else 1;
+ *   ratio = min(ratio, max_trust) when max_trust > 0; ratio = 1 when the tensor's adapt flag is 0.  p -= lr_group * ratio * u.
+ * LARS (state momentum_buf, NULL iff momentum == 0): per tensor wn = ||p_t||, gn = ||g_t||; local = trust_coef * wn /
+ *   (gn + wd_group*wn + lars_eps) if wn > 0 and gn > 0, else 1; the max_trust clamp and the adapt flag as for LAMB;
+ *   d = local * (g + wd_group*p); then bdn_sgd_momentum_step's buffer, dampening and Nesterov formulas with d in place of the decayed
+ *   gradient (buf = d on the first step, momentum*buf + (1-dampening)*d after it; d + momentum*buf or buf); p -= lr_group * (...).
+ * With every ratio 1, LAMB is AdamW and LARS is SGD(momentum, weight_decay) up to the association of the decay term.
+ * The per-tensor table: DEVICE arrays of n_tensors (1..256) entries, read by the kernels only (upload them when the groups change, not
+ *   per step): ten_end (uint32) the sorted tensor ends in float4 units, tiling [0, n/4) like seg_end; ten_len (uint32) the real element
+ *   count of each tensor (the last vector of a tensor is masked by it: a pad element never enters a norm, whatever it holds); ten_group
+ *   (int32) 0..n_groups-1, or -1 = frozen (neither read nor written: parameter, gradient and state keep their bits); ten_adapt (int32)
+ *   0 or 1.  A vector behind the last end or with a group id outside the groups is skipped.
+ * lr, weight_decay: HOST arrays of n_groups (1..8) floats.  n: a multiple of 4.  All flat buffers 16-byte aligned.
+ * workspace: DEVICE, 8-byte aligned, bdn_layerwise_workspace_bytes(n, n_tensors) bytes; never read before it is written.
+ * trust_out: DEVICE float32 [n_tensors][3] = {wn, un or gn, the applied ratio}, {0, 0, 0} for a frozen tensor; the apply pass reads the
+ *   ratio from it.
+ * Three launches, always: partial sums (one pair of doubles per intersection of a 1024-vector chunk with a tensor; a chunk inside one
+ *   tensor is summed by its whole block, a chunk that holds several tensors gives them to its four waves in turn), a finish with one wave per tensor,
+ *   the apply pass.  No atomics, no memset, no host read-back; every float32 is converted to double before it is squared, sums are
+ *   double and run in an order fixed by (n, table): the same bits on every run and any device, from any workspace contents.  LAMB's first
+ *   pass writes the new moments and the apply pass recomputes u from them and the still-old parameter through the same device function:
+ *   no n-sized scratch.
+ * BDN_E_ARG: null pointers, misalignment, n % 4, n_tensors or n_groups out of range, betas outside [0, 1), a negative eps, trust_coef,
+ *   lars_eps or max_trust (0: no clamp), Nesterov with dampening or without momentum, momentum_buf given iff momentum != 0, step < 1. ---- */
+size_t bdn_layerwise_workspace_bytes(size_t n, int n_tensors);
+int bdn_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const uint32_t* ten_end, const uint32_t* ten_len,
+                  const int32_t* ten_group, const int32_t* ten_adapt, int n_tensors, int n_groups, const float* lr,
+                  const float* weight_decay, float grad_scale, const float* dev_scale, double beta1, double beta2, float eps,
+                  float max_trust, long long step, void* workspace, float* trust_out, size_t n, void* stream);
+int bdn_lars_step(float* params, const float* grads, float* momentum_buf, const uint32_t* ten_end, const uint32_t* ten_len,
+                  const int32_t* ten_group, const int32_t* ten_adapt, int n_tensors, int n_groups, const float* lr,
+                  const float* weight_decay, float grad_scale, const float* dev_scale, float momentum, float dampening, int nesterov,
+                  int first_step, float trust_coef, float lars_eps, float max_trust, void* workspace, float* trust_out, size_t n,
+                  void* stream);
+
 /* ---- averaged weights (torch.optim.swa_utils.AveragedModel's EMA / SWA) over the flat f32 buffers of the fused step.
  * bdn_ema_update: copy = 1: avg = params bit for bit (AveragedModel's first update); copy = 0: avg = lerp(avg, params, weight) by torch's
  *   element formula in float32, weight < 0.5: avg + weight * (p - avg), otherwise p - (p - avg) * (1 - weight) -- so weight 0 keeps avg's
