@@ -135,6 +135,9 @@ SIGNATURES = {
     'bdn_lamb_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _hf, _hf, _f, _vp, C.c_double, C.c_double, _f, _f, _i64, _vp, _vp,
                            _sz, _vp]),
     'bdn_lars_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _hf, _hf, _f, _vp, _f, _f, _i, _i, _f, _f, _f, _vp, _vp, _sz, _vp]),
+    'bdn_sam_workspace_bytes': (_sz, [_sz, _i]),
+    'bdn_sam_perturb': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _f, _vp, _vp, _sz, _vp]),
+    'bdn_sam_restore': (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp]),
     'bdn_ema_update': (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _sz, _vp]),
     'bdn_ema_update_multi': (_i, [_vp, _i, _i, _f, _i, _vp]),
     'bdn_swap_segments': (_i, [_vp, _vp, _vp, _vp, _i, _sz, _vp]),

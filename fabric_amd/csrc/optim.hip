@@ -1,6 +1,7 @@
 // Parameter updates over the flat float32 buffers: SGD, momentum SGD, Adam / AdamW, their grouped and _ex forms, EMA / SWA averaging and
 // the buffer swap, gradient accumulation and the global gradient norm, and the layer-wise adaptive rules LAMB / LARS (per-tensor norms
-// and trust ratios).  Memory-bound float4 passes; no atomics, fixed-order reductions.
+// and trust ratios), and the perturbation and restore of sharpness-aware minimisation (SAM / ASAM).  Memory-bound float4 passes; no
+// atomics, fixed-order reductions.
 #include "common.hpp"
 
 // ============================================================ SGD (train.py:55,95)
@@ -666,9 +667,8 @@ __global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float* __r
     if (threadIdx.x == 0) part[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
 }
 
-__global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __restrict__ part, size_t nblk, float grad_scale, float max_norm,
-                                                               float* __restrict__ out) {
-    __shared__ double s_part[1024];
+// the partials added in index order by thread 0 of a 256-thread block (staged through LDS 1024 at a time); the other threads return 0
+__device__ __forceinline__ double sum_partials(const double* __restrict__ part, size_t nblk, double* s_part) {
     double sum = 0.0;
     for (size_t b0 = 0; b0 < nblk; b0 += 1024) {
         const size_t m = nblk - b0 < 1024 ? nblk - b0 : 1024;
@@ -678,6 +678,13 @@ __global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __r
             for (size_t k = 0; k < m; k++) sum += s_part[k];
         __syncthreads();
     }
+    return sum;
+}
+
+__global__ void __launch_bounds__(256) grad_norm_finish_kernel(const double* __restrict__ part, size_t nblk, float grad_scale, float max_norm,
+                                                               float* __restrict__ out) {
+    __shared__ double s_part[1024];
+    const double sum = sum_partials(part, nblk, s_part);
     if (threadIdx.x == 0) {
         const float norm32 = (float)((double)grad_scale * sqrt(sum));
         // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1), the quotient as torch evaluates a Python float over a
@@ -1108,4 +1115,260 @@ extern "C" int bdn_lars_step(float* params, const float* grads, float* momentum_
         return layerwise_launch<RuleLars<true>>("lars_step", params, grads, momentum_buf, nullptr, t, a, ta, dev_scale, workspace, trust_out,
                                                 n, stream);
     return layerwise_launch<RuleLars<false>>("lars_step", params, grads, nullptr, nullptr, t, a, ta, dev_scale, workspace, trust_out, n, stream);
+}
+
+// ============================================================ sharpness-aware minimisation: SAM (Foret et al. 2021), ASAM (Kwon et al. 2021)
+// The ascent step w -> w + e of a SAM update and its undoing, on the layer-wise rules' per-tensor table (ten_end, ten_len, ten_group; no
+// adapt flags, no groups: a group id >= 0 is trainable, OPT_FROZEN is not).  e = rho * t^2 * g / (||t * g|| + eps) with t = |w| (ASAM) or
+// 1 (SAM); the norm runs over the real elements of every trainable tensor.  bdn_sam_perturb is three launches, fixed:
+//   1 partial  grad_norm_partial_kernel's shape: block b owns the NORM_CHUNK vectors [b NORM_CHUNK, (b + 1) NORM_CHUNK) and writes ONE
+//              double; a vector takes its tensor from the LDS table (one lookup per block where the chunk lies in one tensor), a frozen
+//              vector or one behind the table is not read, and the last vector of a tensor is masked by the tensor's real length.
+//   2 finish   one thread adds the partials in index order; out = {(float)norm, rho / (out[0] + eps)}, both float32.
+//   3 apply    the update kernels' pass shape: saved = w, then w += ((out[1] * t) * t) * g on the real elements -- float32 products in
+//              that order, one float32 add, none contracted.  A product that is exactly 0 leaves w's bits alone (-0.0 stays -0.0).
+// bdn_sam_restore is one launch of the same pass shape that copies saved back: bits are moved, never computed.  Both passes move whole
+// float4s; a pad element keeps its own bits throughout.
+__device__ __forceinline__ int sam_stage(const uint32_t* __restrict__ ten_end, const uint32_t* __restrict__ ten_len,
+                                         const int32_t* __restrict__ ten_group, int n_ten, uint32_t* s_end, int* s_grp, int* s_tail) {
+    int cap = 1;
+    while (cap < n_ten) cap <<= 1;
+    for (int k = threadIdx.x; k < cap; k += 256) {
+        const bool in = k < n_ten;
+        const uint32_t end = in ? ten_end[k] : 0xffffffffu, start = (in && k) ? ten_end[k - 1] : 0u;
+        s_end[k] = end;
+        s_grp[k] = in ? ten_group[k] : OPT_FROZEN;
+        s_tail[k] = (in && ten_len) ? (int)(ten_len[k] - 4u * (end - 1u - start)) : 4;   // real elements of the tensor's last vector
+    }
+    return cap;
+}
+
+// real elements of vector i in tensor s: 0 when it is frozen or lies behind the table (the vector is then neither read nor written)
+__device__ __forceinline__ int sam_valid(const uint32_t* s_end, const int* s_grp, const int* s_tail, int s, size_t i) {
+    if (!(s_end[s] > i) || s_grp[s] < 0) return 0;
+    return i + 1 == s_end[s] ? s_tail[s] : 4;
+}
+
+template <bool ADAPT>
+__device__ __forceinline__ double sam_acc(double acc, const float4& P, const float4& G, int nvalid) {
+    double x0 = (double)G.x, x1 = (double)G.y, x2 = (double)G.z, x3 = (double)G.w;
+    if (ADAPT) { x0 *= fabs((double)P.x); x1 *= fabs((double)P.y); x2 *= fabs((double)P.z); x3 *= fabs((double)P.w); }
+    x0 = nvalid > 0 ? x0 : 0.0; x1 = nvalid > 1 ? x1 : 0.0; x2 = nvalid > 2 ? x2 : 0.0; x3 = nvalid > 3 ? x3 : 0.0;   // a pad is 0.0, whatever it holds
+    acc = fma(x0, x0, acc); acc = fma(x1, x1, acc); acc = fma(x2, x2, acc); acc = fma(x3, x3, acc);
+    return acc;
+}
+
+template <bool ADAPT>
+__global__ void __launch_bounds__(256) sam_partial_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                          const uint32_t* __restrict__ ten_end, const uint32_t* __restrict__ ten_len,
+                                                          const int32_t* __restrict__ ten_group, int n_ten, double* __restrict__ part, size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS], s_tail[OPT_MAX_SEGS];
+    __shared__ double s_wave[4];
+    const int cap = sam_stage(ten_end, ten_len, ten_group, n_ten, s_end, s_grp, s_tail);
+    __syncthreads();
+    const size_t c0 = (size_t)blockIdx.x * NORM_CHUNK, last = (c0 + NORM_CHUNK < n4 ? c0 + NORM_CHUNK : n4) - 1;
+    int t_lo = 0, t_hi = 0;
+    for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)c0, t_lo); seg_step(s_end, h, (uint32_t)last, t_hi); }
+    const bool per_lane = t_lo != t_hi;                      // the chunk spans a tensor boundary: every vector looks its tensor up
+    double acc = 0.0;
+    for (int r = 0; r < NORM_ROUNDS; r++) {
+        int nv[OPT_VEC];
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+            nv[u] = 0;
+            if (i < n4) {
+                int s = t_lo;
+                if (per_lane) {
+                    s = 0;
+                    for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+                }
+                nv[u] = sam_valid(s_end, s_grp, s_tail, s, i);
+            }
+        }
+        float4 P[OPT_VEC] = {}, G[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
+            if (nv[u] > 0) {
+                G[u] = reinterpret_cast<const float4*>(g)[i];
+                if (ADAPT) P[u] = reinterpret_cast<const float4*>(p)[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) acc = sam_acc<ADAPT>(acc, P[u], G[u], nv[u]);      // a vector not taken adds +0.0
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+__global__ void __launch_bounds__(256) sam_finish_kernel(const double* __restrict__ part, size_t nblk, float rho, float eps,
+                                                         float* __restrict__ out) {
+    __shared__ double s_part[1024];
+    const double sum = sum_partials(part, nblk, s_part);
+    if (threadIdx.x == 0) {
+        const float norm32 = (float)sqrt(sum);
+        out[0] = norm32;
+        out[1] = rho / (norm32 + eps);
+    }
+}
+
+// nv[u]: the real elements of each of a pass's OPT_VEC vectors (lw_apply_kernel's lookup: one per 256 consecutive vectors where they lie
+// in one tensor, per lane otherwise)
+__device__ __forceinline__ void sam_pass_lookup(const uint32_t* s_end, const int* s_grp, const int* s_tail, int cap, size_t b0, size_t stride,
+                                                size_t n4, int (&nv)[OPT_VEC]) {
+    int seg[OPT_VEC] = {};
+    for (int h = cap >> 1; h > 0; h >>= 1) {
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t first = b0 + u * stride;
+            seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), seg[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < OPT_VEC; u++) {
+        const size_t first = b0 + u * stride, i = first + threadIdx.x;
+        nv[u] = 0;
+        if (i < n4) {
+            const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
+            int s = seg[u];
+            if (!(s_end[s] > last)) {
+                s = 0;
+                for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+            }
+            nv[u] = sam_valid(s_end, s_grp, s_tail, s, i);
+        }
+    }
+}
+
+template <bool ADAPT>
+__device__ __forceinline__ float sam_elem(float w, float g, float scale) {
+    float c = scale;
+    if (ADAPT) { const float t = fabsf(w); c = __fmul_rn(__fmul_rn(scale, t), t); }
+    const float e = __fmul_rn(c, g);
+    return e == 0.f ? w : __fadd_rn(w, e);
+}
+
+template <bool ADAPT>
+__global__ void __launch_bounds__(256) sam_apply_kernel(float* __restrict__ p, float* __restrict__ saved, const float* __restrict__ g,
+                                                        const uint32_t* __restrict__ ten_end, const uint32_t* __restrict__ ten_len,
+                                                        const int32_t* __restrict__ ten_group, int n_ten, const float* __restrict__ out,
+                                                        size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS], s_tail[OPT_MAX_SEGS];
+    const int cap = sam_stage(ten_end, ten_len, ten_group, n_ten, s_end, s_grp, s_tail);
+    __syncthreads();
+    const float scale = out[1];
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
+        int nv[OPT_VEC];
+        sam_pass_lookup(s_end, s_grp, s_tail, cap, b0, stride, n4, nv);
+        float4 P[OPT_VEC] = {}, G[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (nv[u] > 0) { P[u] = reinterpret_cast<const float4*>(p)[i]; G[u] = reinterpret_cast<const float4*>(g)[i]; }
+        }
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t i = b0 + u * stride + threadIdx.x;
+            if (nv[u] > 0) {
+                float4 w = P[u];
+                w.x = sam_elem<ADAPT>(w.x, G[u].x, scale);
+                if (nv[u] > 1) w.y = sam_elem<ADAPT>(w.y, G[u].y, scale);
+                if (nv[u] > 2) w.z = sam_elem<ADAPT>(w.z, G[u].z, scale);
+                if (nv[u] > 3) w.w = sam_elem<ADAPT>(w.w, G[u].w, scale);
+                reinterpret_cast<float4*>(saved)[i] = P[u];
+                reinterpret_cast<float4*>(p)[i] = w;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) sam_restore_kernel(float* __restrict__ p, const float* __restrict__ saved,
+                                                          const uint32_t* __restrict__ ten_end, const int32_t* __restrict__ ten_group, int n_ten,
+                                                          size_t n4) {
+    __shared__ uint32_t s_end[OPT_MAX_SEGS];
+    __shared__ int s_grp[OPT_MAX_SEGS], s_tail[OPT_MAX_SEGS];
+    const int cap = sam_stage(ten_end, nullptr, ten_group, n_ten, s_end, s_grp, s_tail);
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
+        int nv[OPT_VEC];
+        sam_pass_lookup(s_end, s_grp, s_tail, cap, b0, stride, n4, nv);
+        float4 S[OPT_VEC] = {};
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++)
+            if (nv[u] > 0) S[u] = reinterpret_cast<const float4*>(saved)[b0 + u * stride + threadIdx.x];
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++)
+            if (nv[u] > 0) reinterpret_cast<float4*>(p)[b0 + u * stride + threadIdx.x] = S[u];
+    }
+}
+
+static int sam_check(const char* what, const void* params, const void* saved, const uint32_t* ten_end, const int32_t* ten_group, int n_tensors,
+                     size_t n) {
+    if (!params || !saved || !ten_end || !ten_group) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (params == saved) BDN_FAIL(BDN_E_ARG, "%s: params and saved are the same buffer", what);
+    if (n_tensors < 1 || n_tensors > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d tensors (1..%d)", what, n_tensors, OPT_MAX_SEGS);
+    if (((uintptr_t)params | (uintptr_t)saved) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
+    if (((uintptr_t)ten_end | (uintptr_t)ten_group) & 3) BDN_FAIL(BDN_E_ARG, "%s: tensor table must be 4-byte aligned", what);
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
+    return BDN_OK;
+}
+
+extern "C" size_t bdn_sam_workspace_bytes(size_t n, int n_tensors) {
+    (void)n_tensors;                                         // one partial per chunk, whatever the table
+    return bdn_grad_norm_workspace_bytes(n);
+}
+
+extern "C" int bdn_sam_perturb(float* params, float* saved, const float* grads, const uint32_t* ten_end, const uint32_t* ten_len,
+                               const int32_t* ten_group, int n_tensors, float rho, int adaptive, float eps, void* workspace, float* out,
+                               size_t n, void* stream) {
+    if (int rc = sam_check("sam_perturb", params, saved, ten_end, ten_group, n_tensors, n)) return rc;
+    if (!grads || !ten_len || !workspace || !out) BDN_FAIL(BDN_E_ARG, "sam_perturb: null pointer");
+    if ((uintptr_t)grads & 15) BDN_FAIL(BDN_E_ARG, "sam_perturb: buffers must be 16-byte aligned");
+    if ((uintptr_t)ten_len & 3) BDN_FAIL(BDN_E_ARG, "sam_perturb: tensor table must be 4-byte aligned");
+    if ((uintptr_t)workspace & 7) BDN_FAIL(BDN_E_ARG, "sam_perturb: workspace must be 8-byte aligned");
+    if ((uintptr_t)out & 3) BDN_FAIL(BDN_E_ARG, "sam_perturb: out must be 4-byte aligned");
+    if (!(rho > 0.f)) BDN_FAIL(BDN_E_ARG, "sam_perturb: rho = %g must be > 0", (double)rho);
+    if (!(eps >= 0.f)) BDN_FAIL(BDN_E_ARG, "sam_perturb: eps = %g must be >= 0", (double)eps);
+    if (adaptive != 0 && adaptive != 1) BDN_FAIL(BDN_E_ARG, "sam_perturb: adaptive must be 0 or 1, got %d", adaptive);
+    if (n == 0) return BDN_OK;
+    const size_t n4 = n / 4, nblk = norm_blocks(n4);
+    hipStream_t st = (hipStream_t)stream;
+    if (adaptive) {
+        hipLaunchKernelGGL(sam_partial_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)params, grads, ten_end, ten_len,
+                           ten_group, n_tensors, (double*)workspace, n4);
+    } else {
+        hipLaunchKernelGGL(sam_partial_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, st, (const float*)params, grads, ten_end, ten_len,
+                           ten_group, n_tensors, (double*)workspace, n4);
+    }
+    BDN_CHECK_LAUNCH("sam_perturb");
+    hipLaunchKernelGGL(sam_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, nblk, rho, eps, out);
+    BDN_CHECK_LAUNCH("sam_perturb");
+    if (adaptive) {
+        hipLaunchKernelGGL(sam_apply_kernel<true>, dim3(opt_grid(n4)), dim3(256), 0, st, params, saved, grads, ten_end, ten_len, ten_group,
+                           n_tensors, (const float*)out, n4);
+    } else {
+        hipLaunchKernelGGL(sam_apply_kernel<false>, dim3(opt_grid(n4)), dim3(256), 0, st, params, saved, grads, ten_end, ten_len, ten_group,
+                           n_tensors, (const float*)out, n4);
+    }
+    BDN_CHECK_LAUNCH("sam_perturb");
+    return BDN_OK;
+}
+
+extern "C" int bdn_sam_restore(float* params, const float* saved, const uint32_t* ten_end, const int32_t* ten_group, int n_tensors, size_t n,
+                               void* stream) {
+    if (int rc = sam_check("sam_restore", params, saved, ten_end, ten_group, n_tensors, n)) return rc;
+    if (n == 0) return BDN_OK;
+    hipLaunchKernelGGL(sam_restore_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, params, saved, ten_end, ten_group,
+                       n_tensors, n / 4);
+    BDN_CHECK_LAUNCH("sam_restore");
+    return BDN_OK;
 }

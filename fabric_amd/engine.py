@@ -395,9 +395,11 @@ class BiDateEngine:
                 if not ws.leased:
                     ws.release_split()
 
-    def _conv(self, ws, L, P, in0, c0, in1, c1, in_mode, in_bn, n, ipg, training, st, reuse_eval_bn=False, presplit=False, frozen=False):
+    def _conv(self, ws, L, P, in0, c0, in1, c1, in_mode, in_bn, n, ipg, training, st, reuse_eval_bn=False, presplit=False, frozen=False,
+              track_running=True):
         """One conv3x3 + BatchNorm statistics stage.  frozen: the training layout (bf16x3: per-layer split operands kept for the weight
-        gradient) on a running-statistics table -- the forward an eval-mode backward recomputes."""
+        gradient) on a running-statistics table -- the forward an eval-mode backward recomputes.  track_running=False (training): the
+        batch statistics are finalized into the same table, the running buffers and the batch count are not passed and do not move."""
         hk, wk = ws.dims[L.level - 1]
         keep = training or frozen
         wf, _ = self._weights(L, P, False)
@@ -427,22 +429,23 @@ class BiDateEngine:
         G = n // ipg
         if training:
             nt = self.mtiles(n, hk, wk, c0 + c1, L.cout, ipg)
+            running = [ptr(P[f'{L.bn}.{k}']) if track_running else None for k in ('running_mean', 'running_var', 'num_batches_tracked')]
             call('bdn_bn_finalize', ptr(ws.stats), nt, G, L.cout, ipg * hk * wk,
-                 ptr(P[f'{L.bn}.weight']), ptr(P[f'{L.bn}.bias']), BN_EPS, BN_MOMENTUM,
-                 ptr(P[f'{L.bn}.running_mean']), ptr(P[f'{L.bn}.running_var']),
-                 ptr(P[f'{L.bn}.num_batches_tracked']), ptr(bn), ptr(ws.bnws), st)
+                 ptr(P[f'{L.bn}.weight']), ptr(P[f'{L.bn}.bias']), BN_EPS, BN_MOMENTUM, *running, ptr(bn), ptr(ws.bnws), st)
         elif not reuse_eval_bn:
             call('bdn_bn_eval', ptr(P[f'{L.bn}.weight']), ptr(P[f'{L.bn}.bias']),
                  ptr(P[f'{L.bn}.running_mean']), ptr(P[f'{L.bn}.running_var']), BN_EPS, G, L.cout, ptr(bn), st)
         return z, bn
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x_d1, x_d2, P, training=True, class_map=False, frozen=False):
+    def forward(self, x_d1, x_d2, P, training=True, class_map=False, frozen=False, track_running=True):
         """x_d1, x_d2: [B,C,H,W] float32 CUDA tensors (reference layout).  P: state-dict-keyed tensors.
         Returns (logits [B,n_classes,H,W] float32, workspace).  class_map=True (eval mode only): returns the uint8 [B,H,W] map
         torch.max(logits, 1)[1] (train.py:199) instead of the logits -- on the eval-shaped schedule it comes straight out of the last
         convolution's epilogue.  frozen=True (training=False): the training-layout forward on P's running statistics, whose activations
-        backward(bn_mode='running') reads -- what an eval-mode backward recomputes."""
+        backward(bn_mode='running') reads -- what an eval-mode backward recomputes.  track_running=False (training=True): the training
+        forward on batch statistics -- the same activations, the same `bn` tables -- that leaves running_mean, running_var and
+        num_batches_tracked alone (the second pass of a sharpness-aware step: torch's momentum=0 trick without touching the modules)."""
         self._prof_seen = 0
         if not (x_d1.is_cuda and x_d2.is_cuda):
             raise RuntimeError('fabric_amd: BiDateNet runs only on a ROCm device (MI355X); '
@@ -470,6 +473,10 @@ class BiDateEngine:
                 logits = self._forward_packed(ws, P, False)
                 call('bdn_argmax', ptr(logits), ptr(cd), B, self.n_classes, H, W, _lib.stream_ptr())
             return cd, ws
+        if not track_running:
+            if not training or class_map:
+                raise RuntimeError('track_running=False belongs to the training forward (eval mode never moves the running statistics)')
+            return self._forward_packed(ws, P, True, track_running=False), ws
         return self._forward_packed(ws, P, training, frozen=frozen and not training), ws
 
     def forward_tiles(self, scene_d1, scene_d2, origins, P, patch_size, reuse_eval_bn=False, slot=0, scene_mask=None):
@@ -512,8 +519,8 @@ class BiDateEngine:
             return None, ws
         return self._forward_packed(ws, P, False, reuse_eval_bn), ws
 
-    def _forward_packed(self, ws, P, training, reuse_eval_bn=False, frozen=False):
-        """The network on the packed input already in ws.x0.  frozen: see forward()."""
+    def _forward_packed(self, ws, P, training, reuse_eval_bn=False, frozen=False, track_running=True):
+        """The network on the packed input already in ws.x0.  frozen, track_running: see forward()."""
         B, H, W = ws.B, ws.H, ws.W
         dev = ws.x0.device
         st = _lib.stream_ptr()
@@ -530,8 +537,8 @@ class BiDateEngine:
             pre = self.x3 and (training or frozen)          # bf16x3 training: pooled maps, skips and upsampled maps are stored as split operands
             src = ws.x0 if k == 1 else (None if pre else ws.pool[k])   # pool[k] was written together with the skip of level k-1
             za, bna = self._conv(ws, La, P, src, La.cin, None, 0, IN_PLAIN, None, 2 * B, B, training, st, rb,
-                                 presplit=(pre and k > 1) or (k == 1 and ws.x0_split), frozen=frozen)
-            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, 2 * B, B, training, st, rb, frozen=frozen)
+                                 presplit=(pre and k > 1) or (k == 1 and ws.x0_split), frozen=frozen, track_running=track_running)
+            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, 2 * B, B, training, st, rb, frozen=frozen, track_running=track_running)
             if k < 5 and pre:
                 Ld, Ln = by[f'd{5 - k}a'], by[f'e{k + 1}a']
                 hn, wn = ws.dims[k]
@@ -556,8 +563,8 @@ class BiDateEngine:
                 call('bdn_upsample2x', self.dt, ptr(prev), prev_mode, ptr(prev_bn), ptr(ws.U[j]),
                      B, hs, wsrc, hk, wk, cprev, st)
             za, bna = self._conv(ws, La, P, None if pre else ws.f[k], ENC_CH[k - 1], None if pre else ws.U[j], cprev, IN_PLAIN, None, B, B,
-                                 training, st, rb, presplit=pre, frozen=frozen)
-            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, B, B, training, st, rb, frozen=frozen)
+                                 training, st, rb, presplit=pre, frozen=frozen, track_running=track_running)
+            zb, bnb = self._conv(ws, Lb, P, za, Lb.cin, None, 0, IN_BNRELU, bna, B, B, training, st, rb, frozen=frozen, track_running=track_running)
             prev, prev_bn, prev_mode, cprev = zb, bnb, IN_BNRELU, Lb.cout
         logits = torch.empty(B, self.n_classes, H, W, dtype=torch.float32, device=dev)
         call('bdn_outc_fwd', self.dt, ptr(prev), ptr(prev_bn), ptr(P['outc.conv.weight']), ptr(P['outc.conv.bias']),

@@ -159,6 +159,23 @@ def check_max_grad_norm(x):
     return float(x)
 
 
+def check_sam(rho=None, adaptive=False, eps=1e-12):
+    """The fused step's sharpness-aware keywords -> (rho or None, adaptive, eps).  rho=None: off (the other two must then keep their
+    defaults: they would shape a perturbation that is not made).  ValueError: rho not a finite number > 0, adaptive not a bool, eps not a
+    finite number >= 0 (bools are refused as numbers: they are numbers to Python only)."""
+    if not isinstance(adaptive, bool):
+        raise ValueError(f'invalid sam_adaptive: {adaptive!r} (must be a bool)')
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or eps < 0:
+        raise ValueError(f'invalid sam_eps: {eps!r} (must be a finite number >= 0)')
+    if rho is None:
+        if adaptive or eps != 1e-12:
+            raise ValueError('sam_adaptive / sam_eps shape a perturbation that is not on: give sam_rho')
+        return None, False, float(eps)
+    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not math.isfinite(rho) or rho <= 0:
+        raise ValueError(f'invalid sam_rho: {rho!r} (must be a finite number > 0, or None)')
+    return float(rho), adaptive, float(eps)
+
+
 AVERAGES = ('ema', 'swa')
 
 

@@ -144,12 +144,15 @@ def train_epoch(step, loader, dev, patch_size, feeder=None, schedule=None, epoch
     host -> device copies of batch k+1 (train.py:83-85) run on a copy stream under the step of batch k.
     schedule: None, or a fabric_amd.schedule.LRSchedule: the learning rates of the update batch i of `epoch` belongs to are set before
     each call (host floats only).  With --optimizer lamb / lars the result gains trust_min / trust_max, the adapted tensors' ratios at
-    the epoch's last update (one read of step.last_trust per epoch)."""
+    the epoch's last update (one read of step.last_trust per epoch).  With --sam_rho it gains sam_sharpness_mean, the mean over the
+    batches of loss(w + e) - loss(w), and sam_norm_mean, the mean of the perturbation's gradient norm ||t * g||; both stay on the
+    device until the epoch's one read."""
     from .device_loader import DevicePatchLoader
     from .input_pipeline import DeviceFeeder
     step.model.train()
     recs, norms, mined, lov, bnd = [], [], [], [], []
     clip = step.max_grad_norm is not None
+    sam = [] if step.sam_rho is not None else None
     topk = getattr(step.criterion, 'topk', None) is not None      # hard-pixel mining: K and the threshold of every batch, read back with the losses
     boundary = step.criterion is not None and step.criterion.has_boundary    # the boundary term of every batch (terms[-1]), read back with the losses
     lovasz = getattr(step.criterion, 'w_lovasz', 0.0) > 0.0        # the Lovasz-Softmax term of every batch (the last term in front of the boundary one)
@@ -168,6 +171,8 @@ def train_epoch(step, loader, dev, patch_size, feeder=None, schedule=None, epoch
                 lov.append(step.last_terms[lov_at:][:1].clone())
             if boundary:
                 bnd.append(step.last_terms[-1:].clone())
+            if sam is not None:
+                sam.append(torch.stack((step.last_sam_loss - loss, step.last_sam_norm)))
             if clip and step.micro == 0:                  # this call ended with an update
                 norms.append((step.last_grad_norm.clone(), step.last_clip_coef.clone()))
         if step.flush() and clip:                         # --accumulate: the batches left over at the end of the epoch
@@ -189,6 +194,9 @@ def train_epoch(step, loader, dev, patch_size, feeder=None, schedule=None, epoch
     if norms:                                             # --max_grad_norm: read back once per epoch, beside the losses
         nc = torch.stack([torch.stack(v) for v in norms]).cpu()
         out.update(grad_norm_mean=float(nc[:, 0].mean()), grad_norm_max=float(nc[:, 0].max()), clipped_frac=float((nc[:, 1] < 1).float().mean()))
+    if sam:                                               # --sam_rho: read back once per epoch, beside the losses
+        sn = torch.stack(sam).cpu().double()
+        out.update(sam_sharpness_mean=float(sn[:, 0].mean()), sam_norm_mean=float(sn[:, 1].mean()))
     if step.optim.kind in ('lamb', 'lars'):               # --optimizer lamb / lars: the adapted tensors' trust ratios at the last update
         ratios = list(step.trust_ratios(adapted_only=True).values())
         if ratios:
@@ -259,6 +267,23 @@ def optimizer_kwargs(opt):
 def layerwise_kwargs(opt):
     """--trust_coef / --lars_eps / --max_trust / --adapt_1d as OptimConfig / TrainStep keywords."""
     return dict(trust_coef=opt.trust_coef, lars_eps=opt.lars_eps, max_trust=opt.max_trust, adapt_1d=opt.adapt_1d)
+
+
+def sam_kwargs(opt):
+    """--sam_rho / --sam_adaptive as TrainStep keywords: {} when neither is given.  Raises ValueError for flags that cannot be honoured:
+    without --fused_step true (the two passes, the perturbation and the restore live inside the fused step), --sam_adaptive without a
+    radius, or a radius fabric_amd.optim.check_sam refuses."""
+    if opt.sam_rho is None and not opt.sam_adaptive:
+        return {}
+    given = ' / '.join(f for f, on in (('--sam_rho', opt.sam_rho is not None), ('--sam_adaptive', opt.sam_adaptive)) if on)
+    if not opt.fused_step:
+        raise ValueError(f'{given} perturb the weights inside the fused step: add --fused_step true')
+    from .optim import check_sam
+    try:
+        check_sam(opt.sam_rho, opt.sam_adaptive)
+    except ValueError as e:
+        raise ValueError(f'{given}: {e}')
+    return dict(sam_rho=opt.sam_rho, sam_adaptive=opt.sam_adaptive)
 
 
 def make_torch_optimizer(params, lr, optimizer='sgd', momentum=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8):
@@ -503,6 +528,10 @@ def main(argv=None):
                     help='fused step: update on every K-th batch with the mean gradient of the K batches (one gradient exchange per update)')
     ap.add_argument('--max_grad_norm', type=float, default=None, metavar='X',
                     help='fused step: clip the gradients to a global L2 norm of X (torch.nn.utils.clip_grad_norm_); inf: measure only')
+    ap.add_argument('--sam_rho', type=float, default=None, metavar='F',
+                    help='--fused_step true only: sharpness-aware minimisation (SAM) with neighbourhood radius F > 0: every batch runs a second '
+                         'forward / backward at the perturbed weights; the epoch record gains train_sam_sharpness_mean and train_sam_norm_mean')
+    ap.add_argument('--sam_adaptive', action='store_true', help='--sam_rho: the scale-invariant ASAM perturbation (radii of 0.5 .. 2 are usual)')
     ap.add_argument('--ema_decay', type=float, default=None, metavar='D',
                     help='--fused_step true only: keep an exponential moving average of the weights (decay D in [0, 1), '
                          'torch.optim.swa_utils.AveragedModel); validation and the full scenes run on it, and ema_epoch_N.pt is written')
@@ -630,9 +659,13 @@ def main(argv=None):
     if (opt.accumulate != 1 or opt.max_grad_norm is not None) and opt.loss_function != 'tversky' and not opt.fused_step:
         raise SystemExit(f'--accumulate / --max_grad_norm are built into the fused step, which runs --loss_function tversky only '
                          f'(got {opt.loss_function}) unless --fused_step true is given')
+    try:
+        sam = sam_kwargs(opt)
+    except ValueError as e:
+        raise SystemExit(str(e))
     from .optim import check_ema
     try:
-        averaging = check_ema(opt.ema_decay, 'swa' if opt.swa else 'ema', opt.ema_every, opt.ema_start)[0]
+        averaging =check_ema(opt.ema_decay, 'swa' if opt.swa else 'ema', opt.ema_every, opt.ema_start)[0]
     except ValueError as e:
         raise SystemExit(f'--ema_decay / --swa / --ema_every / --ema_start: {e}')
     if (averaging or opt.ema_every != 1 or opt.ema_start != 0 or not opt.ema_buffers) and not opt.fused_step:
@@ -712,7 +745,7 @@ def main(argv=None):
                              param_groups=groups, bn='frozen' if opt.frozen_bn else 'batch', criterion=step_criterion,
                              accumulate=opt.accumulate, max_grad_norm=opt.max_grad_norm, ema_decay=opt.ema_decay,
                              average='swa' if opt.swa else 'ema', ema_every=opt.ema_every, ema_start=opt.ema_start,
-                             ema_buffers=opt.ema_buffers, **optimizer_kwargs(opt))
+                             ema_buffers=opt.ema_buffers, **optimizer_kwargs(opt), **sam)
         except ValueError as e:
             raise SystemExit(f'parameter groups: {e}')
         if opt_sd is not None:

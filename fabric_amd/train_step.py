@@ -27,7 +27,7 @@ class TrainStep:
                  optimizer='sgd', momentum=0.0, dampening=0.0, nesterov=False, weight_decay=None, betas=(0.9, 0.999), adam_eps=1e-8,
                  param_groups=None, bn='batch', criterion=None, accumulate=1, max_grad_norm=None,
                  ema_decay=None, average='ema', ema_every=1, ema_start=0, ema_buffers=True,
-                 trust_coef=1e-3, lars_eps=1e-8, max_trust=None, adapt_1d=False):
+                 trust_coef=1e-3, lars_eps=1e-8, max_trust=None, adapt_1d=False, sam_rho=None, sam_adaptive=False, sam_eps=1e-12):
         """optimizer: 'sgd' (torch.optim.SGD: momentum, dampening, nesterov, weight_decay), 'adam' or 'adamw' (torch.optim.Adam / AdamW:
         betas, adam_eps, weight_decay); weight_decay=None is torch's default (0 for sgd and adam, 1e-2 for adamw).  The default, plain
         SGD, is the reference's optim.SGD(lr) (train.py:55) and keeps no state; the other rules keep theirs in flat f32 buffers in the
@@ -78,7 +78,8 @@ class TrainStep:
         (grad_scale = 1 / (world * K)).  `micro` counts the pending micro-steps (0..K-1), `opt_step` counts updates.  The sum is kept in
         one flat float32 buffer in the gradient layout, `flat_accum`, in a fixed order: micro-step 1 acc = g1; micro-steps 2..K-1
         acc += g; micro-step K flat_grads = gK + acc (bdn_grad_accumulate, one float32 add per element each).  Micro-steps 1..K-1 issue
-        no collective and leave the engine's packed weights valid; on micro-step K the pending sum is added bucket by bucket right before
+        no collective and leave the engine's packed weights valid (not under sam_rho: every micro-step perturbs and restores the weights
+        and repacks twice); on micro-step K the pending sum is added bucket by bucket right before
         each bucket's all-reduce (GradBucketer.before_reduce), so there is one exchange per UPDATE and it still overlaps backward.
         flush() applies (or drops) an incomplete accumulation, e.g. at the end of an epoch.
 
@@ -109,6 +110,25 @@ class TrainStep:
         ema_state_dict() / load_ema_state_dict() exchange the state in AveragedModel's format; `with step.ema_weights():` evaluates
         on the averaged weights.
 
+        sam_rho, sam_adaptive, sam_eps: sharpness-aware minimisation (SAM, Foret et al. 2021; sam_adaptive=True: the scale-invariant ASAM
+        of Kwon et al. 2021).  sam_rho=None, the default: nothing is allocated or launched and the step is the one above, call for call.
+        With sam_rho > 0 every step() call -- every micro-step of accumulate=K -- runs two passes over its batch on the step's stream:
+        pass 1 (forward, criterion, backward at w; no collective; BatchNorm's running statistics update, once); bdn_sam_perturb with
+        this rank's own gradient (the paper's m-sharpness: nothing is exchanged in pass 1), which keeps w in `flat_sam` and moves the
+        trainable parameters to w + e, e = rho * t^2 * g / (||t * g|| + sam_eps), t = |w| (adaptive) or 1; pass 2 at w + e on batch
+        statistics that move NO running statistics (engine.forward(track_running=False)), carrying the step's usual bucketed exchange
+        and accumulation; bdn_sam_restore, a bit-exact copy of `flat_sam` back, so data-parallel ranks stay bit-equal; then the update
+        at w with pass 2's gradient -- norm and clip, any update rule, the averaged weights, all unchanged.  Both kernels are issued
+        where the update is: behind backward's joined streams, because backward reads parameters directly (classifier, BatchNorm
+        weight and bias, conv biases, the first layer's master weight); the engine's packed filter images are invalidated after each.
+        With bn='frozen' both passes run on the running statistics.  Frozen parameters are not perturbed and are not in the norm; the
+        table is the layer-wise rules' per-tensor one, rebuilt at set_param_groups().  step() returns the loss at w; `last_counts` and
+        `last_terms` are pass 1's (copied on the device before pass 2 reuses the criterion's buffers); `last_logits` and `last_dlogits`
+        are pass 2's, those of the perturbed weights.  `last_sam_loss` is the loss at w + e (a 0-dim device tensor),
+        `last_sam_norm` and `last_sam_scale` are 0-dim views of the kernel's {||t * g||, rho / (norm + sam_eps)}: overwritten by the
+        next step, like `last_grad_norm`.  `flat_sam` is scratch, valid only inside a step; SAM keeps no state between steps, so
+        optimizer_state_dict() does not know it.
+
         guard: when the step issues collectives (world > 1, or force_collectives) and guard_collectives() has not been called, the
         first step() runs it in its measure-only form (replace_streams=False: it may defer the buckets, it never swaps a stream the
         caller may already have adopted) and reports / warns about a stream arrangement in which they slow the step down."""
@@ -120,6 +140,10 @@ class TrainStep:
         self.flat_avg, self.avg_buffers, self.n_averaged = None, {}, 0
         self._updates, self._ema_hold, self._swapped, self._avg_desc = 0, False, False, None
         self.max_grad_norm = _optim.check_max_grad_norm(max_grad_norm)
+        self.sam_rho, self.sam_adaptive, self.sam_eps = _optim.check_sam(sam_rho, sam_adaptive, sam_eps)
+        self.flat_sam = self._sam = None
+        self.last_sam_loss = self.last_sam_norm = self.last_sam_scale = None
+        self._sam_pending = False
         self.micro = 0
         self.flat_accum = self._norm = self._clip_table = None
         self.last_grad_norm = self.last_clip_coef = None
@@ -194,7 +218,28 @@ class TrainStep:
             self._init_average()
         if self.optim.kind in _optim.LAYERWISE:
             self._layerwise_table()                          # uploaded now: the step itself never waits for the device
+        if self.sam_rho is not None:
+            self.flat_sam = torch.empty_like(self.flat_params)              # written by bdn_sam_perturb before bdn_sam_restore reads it
+            self._sam_table()                                # uploaded now, like the layer-wise table
         self._grads_version = self.flat_grads._version
+
+    def _sam_table(self):
+        """(groups, the three device arrays of bdn_sam_perturb's per-tensor table, n_tensors, workspace, out), built through the
+        layer-wise rules' route (the step's groups, or the one implicit group of every parameter) and rebuilt when the groups object
+        changed (set_param_groups), never per step.  `last_sam_norm` / `last_sam_scale` are views of out."""
+        pg = self._layerwise_groups()
+        if self._sam is None or self._sam[0] is not pg:
+            dev = self.flat_params.device
+            n_ten = len(self.layout.order)
+            ends, lens, ids, _ = (t.to(dev) for t in _optim.tensor_table(self.layout, pg))
+            if self._sam is None:
+                ws = torch.empty(_lib.load().bdn_sam_workspace_bytes(self.layout.total, n_ten) // 8, dtype=torch.float64, device=dev)
+                out = torch.zeros(2, dtype=torch.float32, device=dev)
+                self.last_sam_norm, self.last_sam_scale = out[0], out[1]
+            else:
+                ws, out = self._sam[3], self._sam[4]
+            self._sam = (pg, (ends, lens, ids), n_ten, ws, out)
+        return self._sam
 
     def _implicit_table(self):
         """The clipped update runs the grouped (_ex) entry points; without groups or frozen parameters, on one implicit group of every
@@ -340,6 +385,8 @@ class TrainStep:
             self._implicit_group = False
             if self.optim.kind in _optim.LAYERWISE:
                 self._layerwise_table()
+            if self.sam_rho is not None:
+                self._sam_table()
             return
         ends, ids = _optim.segment_table(self.layout, pg)
         seg = (torch.tensor(ends, dtype=torch.int64).to(torch.int32).to(dev), torch.tensor(ids, dtype=torch.int32).to(dev), len(ends))
@@ -360,6 +407,8 @@ class TrainStep:
         self._need = set(pg.trainable()) if frozen else None
         if self.optim.kind in _optim.LAYERWISE:
             self._layerwise_table()
+        if self.sam_rho is not None:
+            self._sam_table()
 
     def _checked_groups(self, groups):
         """fabric_amd.optim.ParamGroups of `groups` (names or nn.Parameter objects) and the parameters' requires_grad flags as they are
@@ -449,9 +498,10 @@ class TrainStep:
         with torch.cuda.stream(self._hp):
             loss = self._step(x_d1, x_d2, labels)
         cur.wait_stream(self._hp)
-        for t in (loss, self.last_logits, self.last_counts, self.last_terms, self.last_dlogits, self.last_grad_norm):
+        for t in (loss, self.last_logits, self.last_counts, self.last_terms, self.last_dlogits, self.last_grad_norm, self.last_sam_loss,
+                  self.last_sam_norm):
             if t is not None:
-                t.record_stream(cur)                          # (last_clip_coef shares last_grad_norm's buffer)
+                t.record_stream(cur)                          # (last_clip_coef shares last_grad_norm's buffer, last_sam_scale last_sam_norm's)
         return loss
 
     def flush(self, apply=True):
@@ -682,6 +732,44 @@ class TrainStep:
         return rep
 
     def _step(self, x_d1, x_d2, labels):
+        if self.sam_rho is None:
+            return self._pass(x_d1, x_d2, labels)
+        # ---- sharpness-aware: the gradient at w, w -> w + e, the step's usual pass there, w back, the update at w
+        eng = self.model.engine()
+        st = _lib.stream_ptr()
+        loss, counts = self._pass(x_d1, x_d2, labels, sam=1)
+        # pass 1's loss, counts and terms, copied on the device: pass 2 reuses the criterion's buffers
+        loss, counts = loss.clone(), counts.clone()
+        terms = None if self.last_terms is None else self.last_terms.clone()
+        _, (ends, lens, ids), n_ten, ws, out = self._sam_table()
+        # issued where the update is, behind backward's joined streams: backward reads parameters directly (the classifier, BatchNorm
+        # weight and bias, the conv biases, the first layer's master weight)
+        _lib.call('bdn_sam_perturb', self.flat_params.data_ptr(), self.flat_sam.data_ptr(), self.flat_grads.data_ptr(), ends.data_ptr(),
+                  lens.data_ptr(), ids.data_ptr(), n_ten, self.sam_rho, int(self.sam_adaptive), self.sam_eps, ws.data_ptr(),
+                  out.data_ptr(), self.layout.total, st)
+        self._sam_pending = True
+        eng.invalidate_weights()                              # the packed images hold w, the parameters w + e
+        try:
+            self.last_sam_loss = self._pass(x_d1, x_d2, labels, sam=2)
+        finally:
+            if self._sam_pending:                             # pass 2 raised before its restore: the model must not keep w + e
+                self._sam_restore(st)
+        self.last_counts, self.last_terms = counts, terms
+        return loss
+
+    def _sam_restore(self, st):
+        """w back from flat_sam, bit for bit, behind pass 2's backward (the ordering rule of the perturbation), and the packed images
+        of w + e marked stale."""
+        _, (ends, _, ids), n_ten, _, _ = self._sam_table()
+        _lib.call('bdn_sam_restore', self.flat_params.data_ptr(), self.flat_sam.data_ptr(), ends.data_ptr(), ids.data_ptr(), n_ten,
+                  self.layout.total, st)
+        self._sam_pending = False
+        self.model.engine().invalidate_weights()
+
+    def _pass(self, x_d1, x_d2, labels, sam=0):
+        """Forward, criterion, backward and what follows them.  sam=0: the whole step.  sam=1, the first pass of a sharpness-aware step:
+        no collective, no accumulation, no update; returns the criterion's (loss, counts) buffers.  sam=2, its second pass: the whole
+        step on batch statistics that move no running statistics, with the restore between backward and the update."""
         model = self.model
         eng = model.engine()
         P = self._state()
@@ -697,7 +785,7 @@ class TrainStep:
             logits, ws = eng.forward(x_d1, x_d2, P, training=False, frozen=True)
             lease = _Lease(ws)
         else:
-            logits, ws = eng.forward(x_d1, x_d2, P, training=True)
+            logits, ws = eng.forward(x_d1, x_d2, P, training=True, **({'track_running': False} if sam == 2 else {}))
         st = _lib.stream_ptr()
         if self.criterion is not None:
             loss, counts, dlogits = self._criterion_loss(logits, labels)
@@ -705,8 +793,8 @@ class TrainStep:
             loss, counts, dlogits = self._tversky_loss(logits, labels, st)
         pending = self.micro                                  # micro-steps already in flat_accum
         closing = pending + 1 >= self.accumulate              # this call ends with the update (always, without accumulation)
-        on_ready = self.bucketer.on_ready if closing else None
-        self._adding = pending > 0                            # closing: the buckets take the pending sum in right before their all-reduce
+        on_ready = self.bucketer.on_ready if closing and sam != 1 else None
+        self._adding = pending > 0 and sam != 1               # closing: the buckets take the pending sum in right before their all-reduce
         try:
             if frozen_bn:
                 try:
@@ -717,9 +805,14 @@ class TrainStep:
                         ws.release_split()
             else:
                 eng.backward(ws, dlogits, P, self.grads, on_ready=on_ready, zero_bias_grads=False, need=self._need)
+            if sam == 1:
+                return loss, counts
+            if sam == 2:                                      # backward has joined its streams: nothing reads the parameters any more
+                self._sam_restore(st)
             self.last_counts = counts
             self.last_logits = logits
-            if not closing:                                   # acc = g1, then acc += g: no collective, no update, the packed weights stay valid
+            if not closing:                                   # acc = g1, then acc += g: no collective, no update; the packed weights stay valid,
+                                                              # except under SAM, whose perturbation and restore have each made them stale
                 _lib.call('bdn_grad_accumulate', self.flat_accum.data_ptr(), self.flat_grads.data_ptr(), self.layout.total, int(pending > 0), st)
                 self.micro = pending + 1
                 self._grads_version = self.flat_grads._version

@@ -243,6 +243,8 @@ int bdn_conv3x3_dgrad_first(int dtype, const void* dA, int ldA, const void* z, c
  * bn[g][0..3][c] = {mean, invstd, scale = gamma*invstd, shift = beta - mean*scale}  (layout [G][4][C]),
  * then updates running_mean/var (momentum 0.1, unbiased variance) once per group in order g=0,1,..
  * and adds G to num_batches_tracked -- the reference calls the module once per date.
+ * running_mean and running_var NULL together, and num_batches_tracked NULL: that buffer is left alone; with all three NULL the call
+ * only writes bn (a forward on batch statistics that moves no running statistics: the second pass of a SAM step).
  * ws: scratch of bdn_bn_finalize_workspace_bytes() (double partial sums of the two-stage reduction).
  * Limit of the one-pass statistic.  The partials are per-tile float32 sums of z and z*z (bdn_conv3x3: stats_partial); they are added
  * in double and var = s1/count - mean^2, clamped at 0, so invstd <= 1/sqrt(eps) and a constant channel gives invstd = 1/sqrt(eps) or
@@ -756,6 +758,33 @@ int bdn_lars_step(float* params, const float* grads, float* momentum_buf, const 
                   const float* weight_decay, float grad_scale, const float* dev_scale, float momentum, float dampening, int nesterov,
                   int first_step, float trust_coef, float lars_eps, float max_trust, void* workspace, float* trust_out, size_t n,
                   void* stream);
+
+/* ---- sharpness-aware minimisation over the flat f32 buffers: SAM (Foret et al., ICLR 2021) and ASAM (Kwon et al., ICML 2021).
+ * bdn_sam_perturb moves the parameters to w + e, the point whose gradient a SAM update applies at w; bdn_sam_restore moves them back.
+ *   t_i = |w_i| when adaptive = 1 (ASAM), else 1;  norm = sqrt(sum (t_i * g_i)^2) over the real elements of every non-frozen tensor;
+ *   out[0] = (float)norm, out[1] = rho / (out[0] + eps) in float32;  saved_i = w_i, then w_i += ((out[1] * t_i) * t_i) * g_i: float32
+ *   products in that order and one float32 add, none contracted; a product that is exactly 0 leaves w_i's bits alone.
+ * The per-tensor table is bdn_lamb_step's without the adapt flags: DEVICE arrays of n_tensors (1..256) entries, ten_end (uint32, sorted
+ *   ends in float4 units tiling [0, n/4)), ten_len (uint32, the real element count: a pad element behind it inside the tensor's last
+ *   float4 never enters the norm and keeps its bits, whatever it holds), ten_group (int32, -1 = frozen, anything >= 0 trainable).  A
+ *   frozen tensor, and a vector behind the last end, is neither read nor written in params, grads or saved.
+ * out: DEVICE float32 [2].  workspace: DEVICE, 8-byte aligned, bdn_sam_workspace_bytes(n, n_tensors) bytes (one double per 4096
+ *   vectors today, whatever n_tensors), never read before it is written.  n: a multiple of 4; params, saved, grads 16-byte aligned.
+ * Three launches, always: one double per block of 4096 vectors, one thread adds them in index order and writes out, the apply pass.
+ *   Every float32 is converted to double before it is multiplied, the sums are double and run in an order fixed by (n, table): no
+ *   atomics, no memset, no host read-back, the same bits on every run and any device, from any workspace contents.  A zero gradient
+ *   gives out[0] = 0 and leaves params as they are (eps > 0: without a NaN).  A non-finite gradient is no special case: out is
+ *   non-finite then, and so are the parameters until the restore.
+ * bdn_sam_restore: ONE launch, params = saved bit for bit on exactly the float4s bdn_sam_perturb wrote under the same table: a copy,
+ *   never a subtraction of the perturbation (w + e - e is not w in float32).
+ * BDN_E_ARG, before any launch: null pointers, misalignment, params == saved, n % 4, n_tensors outside 1..256, rho <= 0 or NaN,
+ *   eps < 0 or NaN, adaptive other than 0 / 1. ---- */
+size_t bdn_sam_workspace_bytes(size_t n, int n_tensors);
+int bdn_sam_perturb(float* params, float* saved, const float* grads, const uint32_t* ten_end, const uint32_t* ten_len,
+                    const int32_t* ten_group, int n_tensors, float rho, int adaptive, float eps, void* workspace, float* out, size_t n,
+                    void* stream);
+int bdn_sam_restore(float* params, const float* saved, const uint32_t* ten_end, const int32_t* ten_group, int n_tensors, size_t n,
+                    void* stream);
 
 /* ---- averaged weights (torch.optim.swa_utils.AveragedModel's EMA / SWA) over the flat f32 buffers of the fused step.
  * bdn_ema_update: copy = 1: avg = params bit for bit (AveragedModel's first update); copy = 0: avg = lerp(avg, params, weight) by torch's
