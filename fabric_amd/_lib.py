@@ -118,6 +118,8 @@ SIGNATURES = {
     'bdn_sample_patches': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'bdn_sample_patches_aug': (_i, [_vp, _hi, _i, _i, _hi, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _f, _f, _f, _f, _i, _i, _i,
                                     _f, _vp, _vp, _vp]),
+    'bdn_sample_patches_warp': (_i, [_vp, _hi, _i, _i, _hi, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _f, _f, _f, _f, _i, _i, _i,
+                                     _f, _vp, _vp, _f, _f, _f, _f, _i, _hf, _vp, _vp, _vp]),
     'bdn_sgd_step': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
     'bdn_sgd_momentum_step': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _sz, _vp]),
     'bdn_adam_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, C.c_double, C.c_double, _f, _f, _i, _i64, _sz, _vp]),
@@ -176,6 +178,16 @@ def host_int32(a):
     if str(a.dtype) != 'int32' or not a.flags['C_CONTIGUOUS']:
         raise RuntimeError('fabric_amd: host table must be a contiguous int32 array')
     return a.ctypes.data_as(_hi)
+
+
+def host_float32(a):
+    """A host float32 table for an entry point that takes one as const float* (read during the call): a contiguous float32 numpy array,
+    or None."""
+    if a is None:
+        return None
+    if str(a.dtype) != 'float32' or not a.flags['C_CONTIGUOUS']:
+        raise RuntimeError('fabric_amd: host table must be a contiguous float32 array')
+    return a.ctypes.data_as(_hf)
 
 _lib = None
 

@@ -7,6 +7,9 @@ default is off and does no arithmetic.
 
     policy = PatchAugment(seed=3, jitter=8, gain=0.1, bias=0.05, noise_std=0.02, erase_p=0.25, erase_size=(8, 32), erase_label=255)
     loader = DevicePatchLoader(train_ds, stacks, 64, sampler=sampler, drop_last=True, augment=policy)
+
+PatchWarp is the second policy, for what no permutation of pixels expresses (rotation, zoom, misregistration between the dates;
+bdn_sample_patches_warp).  It rides on a PatchAugment and leaves that class, its ABI and its draws as they are.
 """
 import math
 import operator
@@ -92,3 +95,66 @@ class PatchAugment:
         return (f'PatchAugment(seed={self.seed}, jitter={self.jitter}, symmetry={self.symmetry}, gain={self.gain}, bias={self.bias}, '
                 f'per_date={self.per_date}, noise_std={self.noise_std}, erase_p={self.erase_p}, erase_size={self.erase_size}, '
                 f'erase_label={self.erase_label}, erase_fill={self.erase_fill})')
+
+
+MAX_ROTATE, MIN_SCALE, MAX_SCALE, MAX_MISREG = 180.0, 0.125, 8.0, 64.0          # the bounds bdn_sample_patches_warp checks
+
+
+class PatchWarp:
+    """The geometric policy no permutation of pixels can express (bdn_sample_patches_warp; DevicePatchLoader(augment=..., warp=...)):
+    the patch is gathered through an affine map with bilinear taps.  It rides on a PatchAugment, whose seed and sample keys its draws use.
+    rotate: R >= 0 degrees (at most 180), the angle is uniform in [-R, R].  scale: (lo, hi) with 1/8 <= lo <= hi <= 8, the zoom s is
+    log-uniform in [lo, hi]; s > 1 magnifies (the source footprint shrinks).  misreg: M >= 0 pixels (at most 64), date 2 is sampled at
+    date 1's coordinates plus (t_i, t_j), each uniform in [-M, M]; the labels follow date 1.  oob_label: None, or the byte 0..255 a label
+    pixel becomes when its source centre lies outside the city (the criterion's ignore_index); image taps outside replicate the border.
+
+        warp = PatchWarp(rotate=30, scale=(0.8, 1.25), misreg=0.75, oob_label=255)
+        loader = DevicePatchLoader(train_ds, stacks, 64, sampler=sampler, drop_last=True, augment=policy, warp=warp)
+    """
+
+    def __init__(self, rotate=0.0, scale=(1.0, 1.0), misreg=0.0, oob_label=None):
+        self.rotate = self._finite('rotate', rotate)
+        if not 0.0 <= self.rotate <= MAX_ROTATE:
+            raise ValueError(f'PatchWarp: rotate {rotate} outside [0, 180] degrees')
+        try:
+            lo, hi = scale
+        except (TypeError, ValueError):
+            raise ValueError(f'PatchWarp: scale must be (lo, hi), got {scale!r}')
+        lo, hi = self._finite('scale', lo), self._finite('scale', hi)
+        if not MIN_SCALE <= lo <= hi <= MAX_SCALE:
+            raise ValueError(f'PatchWarp: scale needs 1/8 <= lo <= hi <= 8, got {scale!r}')
+        self.scale = (lo, hi)
+        self.misreg = self._finite('misreg', misreg)
+        if not 0.0 <= self.misreg <= MAX_MISREG:
+            raise ValueError(f'PatchWarp: misreg {misreg} outside [0, 64] pixels')
+        if oob_label is not None:
+            try:
+                ok = not isinstance(oob_label, bool) and 0 <= operator.index(oob_label) <= 255
+            except TypeError:
+                ok = False
+            if not ok:
+                raise ValueError(f'PatchWarp: oob_label {oob_label!r}: a label byte 0..255, or None to keep the clamped labels')
+        self.oob_label = None if oob_label is None else int(oob_label)
+
+    @staticmethod
+    def _finite(name, v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f'PatchWarp: {name} must be a number, got {v!r}')
+        if not math.isfinite(v):
+            raise ValueError(f'PatchWarp: {name} must be finite, got {v}')
+        return v
+
+    @property
+    def off(self):
+        """True when the policy maps every patch onto itself: such a loader takes the bdn_sample_patches_aug path."""
+        return self.rotate == 0.0 and self.scale == (1.0, 1.0) and self.misreg == 0.0
+
+    def abi_args(self):
+        """The policy as bdn_sample_patches_warp takes it: (rotate_rad, log2_lo, log2_hi, misreg, oob_label or -1)."""
+        return (math.radians(self.rotate), math.log2(self.scale[0]), math.log2(self.scale[1]), self.misreg,
+                -1 if self.oob_label is None else self.oob_label)
+
+    def __repr__(self):
+        return f'PatchWarp(rotate={self.rotate}, scale={self.scale}, misreg={self.misreg}, oob_label={self.oob_label})'

@@ -21,6 +21,7 @@ constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;      // rou
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // key increments (golden ratio, sqrt(3) - 1)
 
 constexpr uint32_t PHILOX_GEOMETRY = 0, PHILOX_RADIOMETRY = 1, PHILOX_NOISE = 2;      // streams; noise plane p uses PHILOX_NOISE + p
+constexpr uint32_t PHILOX_WARP = 0x57415250u;      // bdn_sample_patches_warp's stream ('WARP'): far above any noise stream 2 .. 2 + 2C - 1
 
 PHILOX_HD Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #if defined(__HIP_DEVICE_COMPILE__)

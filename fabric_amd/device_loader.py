@@ -15,13 +15,17 @@ With `augment=PatchAugment(...)` (fabric_amd.augment) the batch is cut by bdn_sa
 per-date per-band gain / bias, Gaussian noise and erasing, every draw from a counter-based generator keyed by (policy seed, epoch,
 dataset index).  The host then draws nothing from `random` and `dataset.aug` is ignored for that loader: descriptors carry sym = 0 and a
 pinned ring of 64-bit sample keys travels beside them.  Index order and batch boundaries are unchanged.
+
+With `warp=PatchWarp(...)` beside the policy the batch is cut by bdn_sample_patches_warp: the same draws, and the patch gathered through
+a drawn rotation, zoom and between-date shift with bilinear taps.  A PatchWarp that is `off` changes nothing: the loader then issues the
+calls it issues without one.
 """
 import numpy as np
 import torch
 import torch.utils.data
 
 from . import _lib
-from .augment import PatchAugment
+from .augment import PatchAugment, PatchWarp
 from .utils.dataloaders import _draw_symmetry
 
 
@@ -82,7 +86,7 @@ def plan_keys(indices, epoch, out=None):
 
 
 class _Slot:
-    def __init__(self, batch_size, C, S, device, keys=False, export=False):
+    def __init__(self, batch_size, C, S, device, keys=False, export=False, warp=False):
         if keys:                  # the ring of sample keys: rewritten and read under the same `done` discipline as the descriptors
             self.keys_pin = torch.empty((batch_size,), dtype=torch.int64, pin_memory=True)
             self.keys_np = self.keys_pin.numpy().view(np.uint64)
@@ -90,6 +94,8 @@ class _Slot:
         if export:
             self.geom = torch.empty((batch_size, 8), dtype=torch.int32, device=device)
             self.radio = torch.empty((batch_size, 2, C, 2), dtype=torch.float32, device=device)
+            if warp:
+                self.warp = torch.empty((batch_size, 2, 6), dtype=torch.float32, device=device)
         self.desc_pin = torch.empty((batch_size, 4), dtype=torch.int32, pin_memory=True)
         self.desc_np = self.desc_pin.numpy()
         self.desc_dev = torch.empty((batch_size, 4), dtype=torch.int32, device=device)
@@ -106,17 +112,25 @@ class DevicePatchLoader:
     `augment`: a PatchAugment; the batches are then augmented on the device (module docstring) and `dataset.aug` is ignored.  The epoch
     half of a sample key is `sampler.epoch` when the sampler has one, else the number of passes begun so far; set_epoch(e) overrides
     both.  `export_drawn=True` (with a policy): `last_drawn` = (int32 [n][8] (row, col, sym, erased, top, left, eh, ew), float32
-    [n][2][C][2] (g, b)) of the batch yielded last, valid as long as the batch is."""
+    [n][2][C][2] (g, b)) of the batch yielded last, valid as long as the batch is.
+    `warp`: a PatchWarp (needs `augment`, whose seed and keys its draws use); unless it is `off` the batches are cut by
+    bdn_sample_patches_warp and `last_drawn` gains a third element, the float32 [n][2][6] warp records."""
 
     def __init__(self, dataset, stacks, batch_size, sampler=None, drop_last=False, device=None, depth=3, augment=None,
-                 export_drawn=False):
+                 export_drawn=False, warp=None):
         if augment is not None:
             if not isinstance(augment, PatchAugment):
                 raise TypeError(f'fabric_amd: augment must be a PatchAugment, got {type(augment).__name__}')
             augment.check_patch_size(int(dataset.input_size))
         elif export_drawn:
             raise ValueError('fabric_amd: export_drawn needs an augment policy')
+        if warp is not None:
+            if not isinstance(warp, PatchWarp):
+                raise TypeError(f'fabric_amd: warp must be a PatchWarp, got {type(warp).__name__}')
+            if augment is None:
+                raise ValueError('fabric_amd: warp needs an augment policy (its seed and sample keys key the warp draws)')
         self.augment, self.export_drawn = augment, bool(export_drawn)
+        self.warp = warp if warp is not None and not warp.off else None          # an `off` warp: the bdn_sample_patches_aug path, call for call
         self.last_drawn = None
         self._epoch, self._passes = None, 0
         self.dataset = dataset
@@ -145,7 +159,8 @@ class DevicePatchLoader:
             rec[k] = (self.stacks[c]['images'].data_ptr(), self.stacks[c]['labels'].data_ptr(), h | (w << 32))
         self.city_table = torch.from_numpy(rec).to(self.device)
         self.depth = max(2, int(depth))
-        self.slots = [_Slot(self.batch_size, self.C, self.S, self.device, keys=augment is not None, export=self.export_drawn)
+        self.slots = [_Slot(self.batch_size, self.C, self.S, self.device, keys=augment is not None, export=self.export_drawn,
+                            warp=self.warp is not None)
                       for _ in range(self.depth)]
         torch.cuda.synchronize(self.device)                       # uploads and allocations are complete before any stream reads them
         self._k = 0
@@ -161,6 +176,8 @@ class DevicePatchLoader:
                 yield slot.keys_dev
             if self.export_drawn:
                 yield from (slot.geom, slot.radio)
+                if self.warp is not None:
+                    yield slot.warp
 
     def __len__(self):
         return len(self.batch_sampler)
@@ -196,16 +213,21 @@ class DevicePatchLoader:
         keys_dev.copy_(slot.keys_pin[:n], non_blocking=True)
         d1, d2, labels = slot.d1[:n], slot.d2[:n], slot.labels[:n]
         geom, radio = (slot.geom[:n], slot.radio[:n]) if self.export_drawn else (None, None)
-        _lib.call('bdn_sample_patches_aug', self.city_table.data_ptr(), _lib.host_int32(self.city_hw), len(self.cities), self.C,
-                  _lib.host_int32(slot.desc_pin.data_ptr()), desc_dev.data_ptr(), n, self.S, d1.data_ptr(), d2.data_ptr(),
-                  labels.data_ptr(), keys_dev.data_ptr(), *self.augment.abi_args(), _lib.ptr(geom), _lib.ptr(radio), cur.cuda_stream)
+        args = (self.city_table.data_ptr(), _lib.host_int32(self.city_hw), len(self.cities), self.C,
+                _lib.host_int32(slot.desc_pin.data_ptr()), desc_dev.data_ptr(), n, self.S, d1.data_ptr(), d2.data_ptr(),
+                labels.data_ptr(), keys_dev.data_ptr(), *self.augment.abi_args(), _lib.ptr(geom), _lib.ptr(radio))
+        if self.warp is None:
+            _lib.call('bdn_sample_patches_aug', *args, cur.cuda_stream)
+        else:
+            records = slot.warp[:n] if self.export_drawn else None
+            _lib.call('bdn_sample_patches_warp', *args, *self.warp.abi_args(), None, None, _lib.ptr(records), cur.cuda_stream)
         if cur.cuda_stream not in self._streams:
             self._streams.add(cur.cuda_stream)
             for t in self._long_lived():
                 t.record_stream(cur)
         slot.done = torch.cuda.Event()
         slot.done.record(cur)
-        self.last_drawn = (geom, radio) if self.export_drawn else None
+        self.last_drawn = ((geom, radio) if self.warp is None else (geom, radio, records)) if self.export_drawn else None
         return d1, d2, labels
 
     def _sample(self, indices):

@@ -73,13 +73,14 @@ def _patch_datasets(full_load, val_cities, patch_size, stride, augmentation):
 
 
 def make_device_loaders(full_load, val_cities, patch_size, stride, batch_size, augmentation, rank=0, world_size=1, seed=0,
-                        device=None, augment=None):
+                        device=None, augment=None, warp=None):
     """make_loaders with the patches cut on the device (fabric_amd.device_loader): the same datasets, built and sorted the same way,
     the same ShardSampler and drop_last for training, no augmentation and no drop_last for validation.  `full_load`'s city stacks are
     used in place when they are device tensors (ingest's device= output) and uploaded once otherwise; both loaders share them.  The
     augmentation draws come from the process's global `random` at iteration time, as with make_loaders(num_workers=0).
     `augment`: a fabric_amd.augment.PatchAugment for the TRAINING loader only (its draws then come from the policy's counter-based
-    generator and `augmentation` is ignored for it); validation is never augmented."""
+    generator and `augmentation` is ignored for it); `warp`: a fabric_amd.augment.PatchWarp beside it, for the training loader only too;
+    validation is never augmented."""
     from .device_loader import DevicePatchLoader, device_stacks
     from .parallel import ShardSampler
     device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
@@ -87,15 +88,19 @@ def make_device_loaders(full_load, val_cities, patch_size, stride, batch_size, a
     stacks = device_stacks(full_load, device)
     sampler = ShardSampler(len(train_ds), rank, world_size, seed=seed)
     extra = {} if augment is None else dict(augment=augment)
+    if warp is not None:
+        extra['warp'] = warp
     return (DevicePatchLoader(train_ds, stacks, batch_size, sampler=sampler, drop_last=True, device=device, **extra),
             DevicePatchLoader(val_ds, stacks, batch_size, device=device))
 
 
 def augment_from_opt(opt):
     """The PatchAugment of the --aug_* flags, or None when all are at their defaults.  Raises ValueError for flags that cannot be
-    honoured: without --device_patches true (the patches of any other loader are cut on the host) or with values the policy refuses."""
+    honoured: without --device_patches true (the patches of any other loader are cut on the host) or with values the policy refuses.
+    A warp flag (--aug_rotate / --aug_scale / --aug_misreg) alone is enough: the PatchWarp of warp_from_opt rides on this policy."""
     given = [f'--aug_{k}' for k, off in (('jitter', 0), ('gain', 0.0), ('bias', 0.0), ('shared_dates', False), ('noise', 0.0),
-                                         ('erase_p', 0.0), ('erase_size', None), ('seed', None)) if getattr(opt, f'aug_{k}') != off]
+                                         ('erase_p', 0.0), ('erase_size', None), ('seed', None), ('rotate', 0.0), ('scale', None),
+                                         ('misreg', 0.0)) if getattr(opt, f'aug_{k}') != off]
     if not given:
         return None
     if not opt.device_patches:
@@ -107,6 +112,16 @@ def augment_from_opt(opt):
                           erase_label=opt.ignore_label)
     policy.check_patch_size(opt.patch_size)
     return policy
+
+
+def warp_from_opt(opt):
+    """The PatchWarp of --aug_rotate / --aug_scale / --aug_misreg, or None when all three are at their defaults; oob_label is
+    --ignore_label.  augment_from_opt refuses the flags without --device_patches true and builds the PatchAugment it rides on."""
+    if not opt.aug_rotate and opt.aug_scale is None and not opt.aug_misreg:
+        return None
+    from .augment import PatchWarp
+    return PatchWarp(rotate=opt.aug_rotate, scale=tuple(opt.aug_scale) if opt.aug_scale else (1.0, 1.0), misreg=opt.aug_misreg,
+                     oob_label=opt.ignore_label)
 
 
 def _device_batches(loader, dev, feeder):
@@ -566,6 +581,13 @@ def main(argv=None):
                          '--ignore_label when that is set and are kept otherwise')
     ap.add_argument('--aug_erase_size', type=int, nargs=2, default=None, metavar=('LO', 'HI'), help='sides of the erased rectangle, drawn in LO..HI pixels')
     ap.add_argument('--aug_seed', type=int, default=None, metavar='N', help='seed of the augmentation draws (default: --seed)')
+    ap.add_argument('--aug_rotate', type=float, default=0.0, metavar='DEG',
+                    help='--device_patches true: rotate every patch pair by an angle uniform in [-DEG, DEG] (bilinear taps; fabric_amd.augment.'
+                         'PatchWarp).  Label pixels whose source lies outside the city become --ignore_label when that is set')
+    ap.add_argument('--aug_scale', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help='zoom every patch pair by a factor log-uniform in [LO, HI], 1/8 <= LO <= HI <= 8; above 1 magnifies')
+    ap.add_argument('--aug_misreg', type=float, default=0.0, metavar='PX',
+                    help='misregistration: sample date 2 shifted against date 1 by up to PX pixels on either axis; the labels follow date 1')
     ap.add_argument('--scene_stride', type=int, default=0,
                     help='full validation scenes: 0 = the reference\'s non-overlapping argmax masks (predict_scene); N > 0 = tiles every N px, '
                          'softmax probabilities blended (predict_scene_blended), also writes {city}_epoch_{e}_proba.png and a scene F1 line')
@@ -681,6 +703,7 @@ def main(argv=None):
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
     try:
         patch_augment = augment_from_opt(opt)
+        patch_warp = warp_from_opt(opt) if patch_augment is not None else None
     except ValueError as e:
         raise SystemExit(str(e))
 
@@ -716,7 +739,8 @@ def main(argv=None):
     if opt.device_patches:
         train_loader, val_loader = make_device_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
                                                        rank=rank, world_size=world, seed=opt.seed, device=dev,
-                                                       **({} if patch_augment is None else dict(augment=patch_augment)))
+                                                       **({} if patch_augment is None else dict(augment=patch_augment)),
+                                                       **({} if patch_warp is None else dict(warp=patch_warp)))
     else:
         train_loader, val_loader = make_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
                                                 num_workers=opt.num_workers, rank=rank, world_size=world, seed=opt.seed)

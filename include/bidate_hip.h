@@ -651,6 +651,39 @@ int bdn_sample_patches_aug(const void* cities_dev, const int32_t* city_hw_host, 
                            uint64_t seed, int J, int flags, float gain, float bias, float sigma, float erase_p,
                            int lo, int hi, int erase_label, float erase_fill,
                            int32_t* drawn_geom, float* drawn_radio, void* stream);
+/* ---- the augmented cut through an affine map with bilinear taps: extends utils/dataloaders.py:148-165 by what no permutation of pixels
+ * expresses: rotation by any angle, zoom, and a sub-pixel shift of date 2 against date 1 (misregistration; labels stay in date 1's frame) ----
+ * Everything bdn_sample_patches_aug takes up to its two exports, checked the same way, with the same draws for the crop origin (row',
+ * col'), the symmetry and the erase rectangle; then the warp policy, an optional override of the records, and their export.
+ *   record    float32 [2][6] per sample; per date (a_ii, a_ij, t_i, a_ji, a_jj, t_j).  Drawn from stream 0x57415250 slot 0, with
+ *             sgn(w) = 2 u(w) - 1:  theta = sgn(w0) * rotate_rad,  s = exp2f(log2_lo + u(w1) * (log2_hi - log2_lo)),
+ *             a_ii = a_jj = cosf(theta) / s,  a_ij = -sinf(theta) / s,  a_ji = sinf(theta) / s;  translation (0, 0) for date 1 and
+ *             (misreg * sgn(w2), misreg * sgn(w3)) for date 2.  0 <= rotate_rad <= pi, -3 <= log2_lo <= log2_hi <= 3 (s > 1 magnifies),
+ *             0 <= misreg <= 64.  cosf, sinf and exp2f are the device library's: the a's are TOLERANCED (a few float32 ulp of 1 / s against
+ *             the float64 formula), which is why the record is exported; the translations are exact.
+ *   mapping   EXACT given the record: every operation below is rounded once, nothing is fused.  For output pixel (i, j) let (i', j') be the
+ *             window coordinate the symmetry code gives it in bdn_sample_patches, h = (S - 1) / 2, di = i' - h, dj = j' - h:
+ *               y = ((a_ii * di) + (a_ij * dj)) + (h + t_i),   x = ((a_ji * di) + (a_jj * dj)) + (h + t_j)     (relative to the window origin)
+ *             y0 = floorf(y), fy = y - y0, x0, fx alike; tap rows row' + (int)y0 and + 1, tap columns col' + (int)x0 and + 1, each clamped
+ *             into [0, H - 1] / [0, W - 1] (replicate border);  top = ((1 - fx) * v00) + (fx * v01), bot = ((1 - fx) * v10) + (fx * v11),
+ *             out = ((1 - fy) * top) + (fy * bot).  Labels: nearest neighbour with date 1's record, rows row' + (int)floorf(y + 0.5), columns
+ *             alike, clamped the same way; where the unclamped index lies outside the city the label becomes oob_label (0..255; -1:
+ *             the clamped label is kept).  Labels are moved or overwritten, never computed.
+ *   then      gain / bias, noise and erase exactly as in bdn_sample_patches_aug, with the same draws, on the gathered tile.
+ * An identity record gives fx = fy = 0: a finite input then passes through unchanged bit for bit (-0.0 may arrive as +0.0), a rotation
+ * by a multiple of 90 degrees about the centre lands on integers, an integer translation is a shifted crop with replicate clamping.
+ * Non-finite inputs are NOT preserved through the interpolation: 0 * inf is NaN, and a NaN spreads to every element that taps it.
+ * warp_host / warp_dev: both NULL (the records are drawn) or both given: float [n][2][6] records used INSTEAD of the drawn ones, the host
+ * copy checked here (every entry finite, |a| <= 8, |t| <= 2^20), the device copy read by the kernel (the desc_host / desc_dev arrangement).
+ * warp_out (or NULL): DEVICE float [n][2][6], the records used.  S <= 2^24. */
+int bdn_sample_patches_warp(const void* cities_dev, const int32_t* city_hw_host, int n_cities, int C,
+                            const int32_t* desc_host, const int32_t* desc_dev, int n, int S,
+                            float* out_d1, float* out_d2, uint8_t* out_labels, const uint64_t* keys_dev,
+                            uint64_t seed, int J, int flags, float gain, float bias, float sigma, float erase_p,
+                            int lo, int hi, int erase_label, float erase_fill,
+                            int32_t* drawn_geom, float* drawn_radio,
+                            float rotate_rad, float log2_lo, float log2_hi, float misreg, int oob_label,
+                            const float* warp_host, const float* warp_dev, float* warp_out, void* stream);
 
 /* ---- optim.SGD(lr) step, train.py:55,95: p -= lr * grad_scale * g over a flat f32 buffer ---- */
 int bdn_sgd_step(float* params, const float* grads, float lr, float grad_scale, size_t n, void* stream);
