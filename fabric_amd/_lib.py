@@ -22,6 +22,7 @@ def wg_flags(phases=3, kernel=0, blocks=0):
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 _hf = C.POINTER(C.c_float)          # a HOST float array (floats() below), where a void* would be taken for a device pointer
 _hi = C.POINTER(C.c_int32)          # a HOST int32 array (host_int32() below)
+_hu = C.POINTER(C.c_uint64)         # a HOST uint64 array (host_uint64() below)
 
 # name -> (restype, argtypes); mirrors include/bidate_hip.h one to one
 SIGNATURES = {
@@ -120,6 +121,9 @@ SIGNATURES = {
                                     _f, _vp, _vp, _vp]),
     'bdn_sample_patches_warp': (_i, [_vp, _hi, _i, _i, _hi, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _f, _f, _f, _f, _i, _i, _i,
                                      _f, _vp, _vp, _f, _f, _f, _f, _i, _hf, _vp, _vp, _vp]),
+    'bdn_mix_plan': (_i, [C.c_uint64, _hu, _i, _i, _f, _i, _i, _i, _hi, _i, _hi]),
+    'bdn_mix_patches': (_i, [_hi, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'bdn_patch_label_counts': (_i, [_vp, _hi, _i, _hi, _vp, _i, _i, _i, _vp, _vp]),
     'bdn_sgd_step': (_i, [_vp, _vp, _f, _f, _sz, _vp]),
     'bdn_sgd_momentum_step': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _sz, _vp]),
     'bdn_adam_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, C.c_double, C.c_double, _f, _f, _i, _i64, _sz, _vp]),
@@ -178,6 +182,15 @@ def host_int32(a):
     if str(a.dtype) != 'int32' or not a.flags['C_CONTIGUOUS']:
         raise RuntimeError('fabric_amd: host table must be a contiguous int32 array')
     return a.ctypes.data_as(_hi)
+
+
+def host_uint64(a):
+    """A host uint64 table (the sample keys bdn_mix_plan reads): a contiguous uint64 numpy array or the address of one."""
+    if isinstance(a, int):
+        return C.cast(a, _hu)
+    if str(a.dtype) != 'uint64' or not a.flags['C_CONTIGUOUS']:
+        raise RuntimeError('fabric_amd: host table must be a contiguous uint64 array')
+    return a.ctypes.data_as(_hu)
 
 
 def host_float32(a):

@@ -10,9 +10,14 @@ default is off and does no arithmetic.
 
 PatchWarp is the second policy, for what no permutation of pixels expresses (rotation, zoom, misregistration between the dates;
 bdn_sample_patches_warp).  It rides on a PatchAugment and leaves that class, its ABI and its draws as they are.
+
+PatchMix is the third, for augmentation ACROSS samples (bdn_mix_plan, bdn_mix_patches): a rectangle (CutMix) or the changed regions
+(copy-paste) of a donor sample replace the recipient's pixels on both dates and in the labels.  It rides on a PatchAugment too.
 """
 import math
 import operator
+
+import numpy as np
 
 FLAG_SYMMETRY, FLAG_PER_DATE = 1, 2          # AUG_SYMMETRY, AUG_PER_DATE of csrc/scene.hip
 MAX_JITTER = 1 << 24
@@ -158,3 +163,89 @@ class PatchWarp:
 
     def __repr__(self):
         return f'PatchWarp(rotate={self.rotate}, scale={self.scale}, misreg={self.misreg}, oob_label={self.oob_label})'
+
+
+MIX_MODES = {'box': 0, 'object': 1}          # MIX_BOX, MIX_OBJECT of csrc/mix.hip
+MAX_MIX_MARGIN = 16
+
+
+class PatchMix:
+    """Augmentation across samples (bdn_mix_plan, bdn_mix_patches; DevicePatchLoader(augment=..., mix=...)).  With probability p a sample,
+    the recipient, takes every band of both dates and the label byte of ONE donor wherever a mask is set; bits are moved, never computed.
+    The donor is another dataset item, cut and augmented exactly as the loader would yield it in that epoch (its own jitter, symmetry,
+    gain / bias, noise, erase rectangle and warp); it is never itself mixed and may equal the recipient.  It rides on a PatchAugment,
+    whose seed and the recipient's sample key key its draws.
+    mode='box' (CutMix): the mask is a rectangle whose sides are drawn in box_size = (lo, hi), 1 <= lo <= hi <= the patch size, placed
+    uniformly inside the patch.  mode='object' (copy-paste): the mask is (donor labels == paste_label) dilated by a (2 margin + 1)
+    square, margin in 0..16; the ring carries the donor's labels, and both dates switch source at the same pixels, so the seam is not
+    change.  donors: None (any dataset item) or a sorted, non-empty 1-D integer array of dataset indices, the donor pool.
+
+        mix = PatchMix(p=0.5, mode='object', margin=2).donors_from(loader.label_counts(1))
+    """
+
+    def __init__(self, p=0.0, mode='box', box_size=(1, 1), paste_label=1, margin=0, donors=None):
+        try:
+            self.p = float(p)
+        except (TypeError, ValueError):
+            raise ValueError(f'PatchMix: p must be a number, got {p!r}')
+        if not 0.0 <= self.p <= 1.0:
+            raise ValueError(f'PatchMix: p {p} outside [0, 1]')
+        if mode not in MIX_MODES:
+            raise ValueError(f"PatchMix: mode must be 'box' or 'object', got {mode!r}")
+        self.mode = mode
+        try:
+            lo, hi = box_size
+        except (TypeError, ValueError):
+            raise ValueError(f'PatchMix: box_size must be (lo, hi), got {box_size!r}')
+        lo, hi = self._integer('box_size', lo), self._integer('box_size', hi)
+        if not 1 <= lo <= hi:
+            raise ValueError(f'PatchMix: box_size needs integers 1 <= lo <= hi, got {box_size!r}')
+        self.box_size = (lo, hi)
+        self.paste_label, self.margin = self._integer('paste_label', paste_label), self._integer('margin', margin)
+        if not 0 <= self.paste_label <= 255:
+            raise ValueError(f'PatchMix: paste_label {paste_label!r}: a label byte 0..255')
+        if not 0 <= self.margin <= MAX_MIX_MARGIN:
+            raise ValueError(f'PatchMix: margin {margin} outside 0..{MAX_MIX_MARGIN}')
+        if donors is not None:
+            pool = np.asarray(donors)
+            if pool.ndim != 1 or pool.size == 0 or pool.dtype.kind not in 'iu':
+                raise ValueError('PatchMix: donors must be a non-empty 1-D integer array of dataset indices, or None')
+            if int(pool.min()) < 0 or int(pool.max()) >= 1 << 31 or (np.diff(pool.astype(np.int64)) < 0).any():
+                raise ValueError('PatchMix: donors must be sorted dataset indices in [0, 2^31)')
+            donors = np.ascontiguousarray(pool, dtype=np.int32)
+        self.donors = donors
+
+    @staticmethod
+    def _integer(name, v):
+        if isinstance(v, bool):
+            raise ValueError(f'PatchMix: {name} must be an integer, got {v!r}')
+        try:
+            return operator.index(v)
+        except TypeError:
+            raise ValueError(f'PatchMix: {name} must be an integer, got {v!r}')
+
+    @property
+    def off(self):
+        """True when no sample is ever mixed: such a loader issues the calls it issues without the policy."""
+        return self.p == 0.0
+
+    def check(self, S, n_items):
+        """What only the loader knows: the box fits the patch, and every donor is an item of the dataset."""
+        if self.box_size[1] > S:
+            raise ValueError(f'PatchMix: box_size {self.box_size} exceeds the patch size {S}')
+        if self.donors is not None and int(self.donors[-1]) >= n_items:
+            raise ValueError(f'PatchMix: donor {int(self.donors[-1])} is no item of a dataset of {n_items}')
+
+    def donors_from(self, counts, min_pixels=1):
+        """A copy of the policy whose pool is the dataset indices with counts[i] >= min_pixels (counts: loader.label_counts(value), a
+        device tensor, or any integer array): the one host read.  A pool only: jitter and warp may move a donor's content."""
+        counts = counts.cpu().numpy() if hasattr(counts, 'cpu') else np.asarray(counts)
+        pool = np.flatnonzero(counts.reshape(-1) >= self._integer('min_pixels', min_pixels))
+        if pool.size == 0:
+            raise ValueError(f'PatchMix: no dataset item has {min_pixels} or more such pixels: the donor pool is empty')
+        return PatchMix(self.p, self.mode, self.box_size, self.paste_label, self.margin, pool)
+
+    def __repr__(self):
+        donors = None if self.donors is None else f'<{self.donors.size} indices>'
+        return (f'PatchMix(p={self.p}, mode={self.mode!r}, box_size={self.box_size}, paste_label={self.paste_label}, margin={self.margin}, '
+                f'donors={donors})')

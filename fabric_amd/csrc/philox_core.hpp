@@ -22,6 +22,7 @@ constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // key
 
 constexpr uint32_t PHILOX_GEOMETRY = 0, PHILOX_RADIOMETRY = 1, PHILOX_NOISE = 2;      // streams; noise plane p uses PHILOX_NOISE + p
 constexpr uint32_t PHILOX_WARP = 0x57415250u;      // bdn_sample_patches_warp's stream ('WARP'): far above any noise stream 2 .. 2 + 2C - 1
+constexpr uint32_t PHILOX_MIX = 0x4D495820u;       // bdn_mix_plan's stream ('MIX '): distinct from PHILOX_WARP, above every noise stream too
 
 PHILOX_HD Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -76,4 +77,24 @@ PHILOX_HD PhiloxGeom philox_geometry(uint64_t seed, uint64_t sample_key, int row
     g.top = (int)philox_range(b.w[2], (uint32_t)(S - g.eh + 1));
     g.left = (int)philox_range(b.w[3], (uint32_t)(S - g.ew + 1));
     return g;
+}
+
+// ---- stream PHILOX_MIX: whether a sample is mixed, its donor and its rectangle (bdn_mix_plan), integers only except the one comparison
+struct PhiloxMix { int on, pick, top, left, h, w; };
+
+// key: the RECIPIENT's sample key.  p in [0, 1]; 1 <= lo <= hi <= S; n_pool >= 1.  pick in [0, n_pool) indexes the donor pool.  box: slot 1
+// places the h x w rectangle; otherwise (object mode) the rectangle is the patch and slot 1 is not drawn.  An unmixed sample is all zero.
+PHILOX_HD PhiloxMix philox_mix(uint64_t seed, uint64_t sample_key, int S, float p, bool box, int lo, int hi, uint32_t n_pool) {
+    PhiloxMix m{0, 0, 0, 0, 0, 0};
+    const Philox4 a = philox_draw(seed, sample_key, PHILOX_MIX, 0);
+    if (!((float)philox_u24(a.w[0]) * 0x1p-24f < p)) return m;
+    m.on = 1;
+    m.pick = (int)philox_range(a.w[1], n_pool);
+    m.h = lo + (int)philox_range(a.w[2], (uint32_t)(hi - lo + 1));
+    m.w = lo + (int)philox_range(a.w[3], (uint32_t)(hi - lo + 1));
+    if (!box) { m.h = m.w = S; return m; }
+    const Philox4 b = philox_draw(seed, sample_key, PHILOX_MIX, 1);
+    m.top = (int)philox_range(b.w[0], (uint32_t)(S - m.h + 1));
+    m.left = (int)philox_range(b.w[1], (uint32_t)(S - m.w + 1));
+    return m;
 }

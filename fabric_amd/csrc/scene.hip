@@ -2,6 +2,7 @@
 // The two dates of a scene stay resident in HBM as band planes; tiles are gathered straight into the packed
 // NHWC batch and predictions are written straight into the scene mask -- no host-side patch stack.
 #include "common.hpp"
+#include "patch_core.hpp"
 #include "philox_core.hpp"
 #include <climits>
 #include <cmath>
@@ -164,10 +165,7 @@ extern "C" int bdn_argmax_stitch(const float* logits, const int32_t* origins, ui
 // source rows into LDS and then read down an LDS column: a row pitch of 65 dwords puts the 64 lanes of a column read (and of a row
 // write) on distinct banks of their 32-lane groups.  Source rows start at arbitrary columns and S need not be a multiple of 4, so
 // the accesses are dwords (bytes for labels): 64 lanes x 4 B = 256 B per wave instruction, 16 independent loads per thread in flight.
-struct SampleCity { const float* images; const uint8_t* labels; int32_t H, W; };       // bdn_sample_patches' city record, 24 bytes
-
-constexpr int SP_TILE = 64, SP_WAVES = 4, SP_ROWS = SP_TILE / SP_WAVES;
-
+// SampleCity, SP_TILE, SP_WAVES, SP_ROWS: patch_core.hpp (shared with mix.hip).
 template <bool LABELS>
 __global__ __launch_bounds__(SP_TILE * SP_WAVES) void sample_patches_kernel(const SampleCity* __restrict__ cities, const int4* __restrict__ desc,
                                                                             int C, int S, int tiles, uint32_t* __restrict__ o1,
@@ -242,20 +240,8 @@ static int sample_patches_check(const char* who, const void* cities_dev, const i
     if ((uintptr_t)desc_dev % 16 || (uintptr_t)cities_dev % 8) BDN_FAIL(BDN_E_ARG, "%s: desc_dev must be 16-byte and cities_dev 8-byte aligned", who);
     if (n <= 0 || S <= 0 || C <= 0 || n_cities <= 0)
         BDN_FAIL(BDN_E_SHAPE, "%s: need n, S, C, n_cities > 0 (got n=%d S=%d C=%d n_cities=%d)", who, n, S, C, n_cities);
-    for (int k = 0; k < n_cities; k++)
-        if (city_hw_host[2 * k] <= 0 || city_hw_host[2 * k + 1] <= 0)
-            BDN_FAIL(BDN_E_SHAPE, "%s: city %d has shape %d x %d", who, k, city_hw_host[2 * k], city_hw_host[2 * k + 1]);
-    for (int k = 0; k < n; k++) {                            // every address the kernel forms comes from a descriptor checked here
-        const int32_t* e = desc_host + 4 * (size_t)k;
-        const int city = e[0], row = e[1], col = e[2], sym = e[3];
-        if (city < 0 || city >= n_cities) BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: city %d outside [0, %d)", who, k, city, n_cities);
-        if (sym < 0 || sym > 7) BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: sym %d outside [0, 8)", who, k, sym);
-        const long long H = city_hw_host[2 * city], W = city_hw_host[2 * city + 1];
-        if (row < 0 || (long long)row + S > H)
-            BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: row %d + S %d outside H %lld of city %d", who, k, row, S, H, city);
-        if (col < 0 || (long long)col + S > W)
-            BDN_FAIL(BDN_E_ARG, "%s: descriptor %d: col %d + S %d outside W %lld of city %d", who, k, col, S, W, city);
-    }
+    const int rd = patch_desc_check(who, city_hw_host, n_cities, desc_host, n, S);
+    if (rd != BDN_OK) return rd;
     const long long tiles = (S + SP_TILE - 1) / SP_TILE;
     *img_blocks = (long long)n * 2 * C * tiles * tiles;
     if (*img_blocks > INT_MAX) BDN_FAIL(BDN_E_SHAPE, "%s: %lld blocks exceed the grid", who, *img_blocks);

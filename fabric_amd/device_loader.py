@@ -19,13 +19,18 @@ pinned ring of 64-bit sample keys travels beside them.  Index order and batch bo
 With `warp=PatchWarp(...)` beside the policy the batch is cut by bdn_sample_patches_warp: the same draws, and the patch gathered through
 a drawn rotation, zoom and between-date shift with bilinear taps.  A PatchWarp that is `off` changes nothing: the loader then issues the
 calls it issues without one.
+
+With `mix=PatchMix(...)` beside the policy a sample takes, with probability p, a rectangle or the changed regions of a donor sample
+(bdn_mix_plan on the host, bdn_mix_patches on the device).  The donors of a batch are cut by the same call as its n recipients, behind
+them, each exactly as the loader would yield it in that epoch; the slots therefore hold 2 * batch_size rows, and the first n are
+yielded.  A PatchMix that is `off` changes nothing.
 """
 import numpy as np
 import torch
 import torch.utils.data
 
 from . import _lib
-from .augment import PatchAugment, PatchWarp
+from .augment import MIX_MODES, PatchAugment, PatchMix, PatchWarp
 from .utils.dataloaders import _draw_symmetry
 
 
@@ -86,7 +91,12 @@ def plan_keys(indices, epoch, out=None):
 
 
 class _Slot:
-    def __init__(self, batch_size, C, S, device, keys=False, export=False, warp=False):
+    def __init__(self, batch_size, C, S, device, keys=False, export=False, warp=False, mix=False):
+        if mix:                   # the plan of the batch, under the same `done` discipline; its donors are cut behind the recipients
+            self.plan_pin = torch.empty((batch_size, 8), dtype=torch.int32, pin_memory=True)
+            self.plan_np = self.plan_pin.numpy()
+            self.plan_dev = torch.empty((batch_size, 8), dtype=torch.int32, device=device)
+            batch_size = 2 * batch_size
         if keys:                  # the ring of sample keys: rewritten and read under the same `done` discipline as the descriptors
             self.keys_pin = torch.empty((batch_size,), dtype=torch.int64, pin_memory=True)
             self.keys_np = self.keys_pin.numpy().view(np.uint64)
@@ -114,10 +124,13 @@ class DevicePatchLoader:
     both.  `export_drawn=True` (with a policy): `last_drawn` = (int32 [n][8] (row, col, sym, erased, top, left, eh, ew), float32
     [n][2][C][2] (g, b)) of the batch yielded last, valid as long as the batch is.
     `warp`: a PatchWarp (needs `augment`, whose seed and keys its draws use); unless it is `off` the batches are cut by
-    bdn_sample_patches_warp and `last_drawn` gains a third element, the float32 [n][2][6] warp records."""
+    bdn_sample_patches_warp and `last_drawn` gains a third element, the float32 [n][2][6] warp records.
+    `mix`: a PatchMix (needs `augment` too); unless it is `off` the batches are mixed across samples (module docstring), `last_drawn`
+    keeps its elements for the n yielded rows and gains the device int32 [n][8] plan (on, donor_index, donor_row, top, left, h, w, 0)
+    as its last one, and `mixed` / `seen` count the samples mixed / yielded in the pass begun last."""
 
     def __init__(self, dataset, stacks, batch_size, sampler=None, drop_last=False, device=None, depth=3, augment=None,
-                 export_drawn=False, warp=None):
+                 export_drawn=False, warp=None, mix=None):
         if augment is not None:
             if not isinstance(augment, PatchAugment):
                 raise TypeError(f'fabric_amd: augment must be a PatchAugment, got {type(augment).__name__}')
@@ -129,7 +142,15 @@ class DevicePatchLoader:
                 raise TypeError(f'fabric_amd: warp must be a PatchWarp, got {type(warp).__name__}')
             if augment is None:
                 raise ValueError('fabric_amd: warp needs an augment policy (its seed and sample keys key the warp draws)')
+        if mix is not None:
+            if not isinstance(mix, PatchMix):
+                raise TypeError(f'fabric_amd: mix must be a PatchMix, got {type(mix).__name__}')
+            if augment is None:
+                raise ValueError('fabric_amd: mix needs an augment policy (its seed and sample keys key the mix draws)')
+            mix.check(int(dataset.input_size), len(dataset))
         self.augment, self.export_drawn = augment, bool(export_drawn)
+        self.mix = mix if mix is not None and not mix.off else None               # an `off` mix: the calls of a loader without one
+        self.mixed = self.seen = 0                # samples mixed / yielded in the pass begun last (host counts: the plan is made here)
         self.warp = warp if warp is not None and not warp.off else None          # an `off` warp: the bdn_sample_patches_aug path, call for call
         self.last_drawn = None
         self._epoch, self._passes = None, 0
@@ -160,7 +181,7 @@ class DevicePatchLoader:
         self.city_table = torch.from_numpy(rec).to(self.device)
         self.depth = max(2, int(depth))
         self.slots = [_Slot(self.batch_size, self.C, self.S, self.device, keys=augment is not None, export=self.export_drawn,
-                            warp=self.warp is not None)
+                            warp=self.warp is not None, mix=self.mix is not None)
                       for _ in range(self.depth)]
         torch.cuda.synchronize(self.device)                       # uploads and allocations are complete before any stream reads them
         self._k = 0
@@ -178,6 +199,8 @@ class DevicePatchLoader:
                 yield from (slot.geom, slot.radio)
                 if self.warp is not None:
                     yield slot.warp
+            if self.mix is not None:
+                yield slot.plan_dev
 
     def __len__(self):
         return len(self.batch_sampler)
@@ -193,6 +216,7 @@ class DevicePatchLoader:
             return
         epoch = self._epoch if self._epoch is not None else getattr(self.sampler, 'epoch', self._passes)
         self._passes += 1
+        self.mixed = self.seen = 0
         for indices in self.batch_sampler:
             yield self._sample_aug(indices, int(epoch))
 
@@ -207,28 +231,73 @@ class DevicePatchLoader:
             city, i, j = self.dataset.imgs[idx]
             slot.desc_np[k] = (self.city_index[city], i, j, 0)
         plan_keys(indices, epoch, out=slot.keys_np)
+        rows = n if self.mix is None else self._plan_mix(slot, n, epoch)          # the donors' descriptors and keys follow the recipients'
         cur = torch.cuda.current_stream(self.device)
-        desc_dev, keys_dev = slot.desc_dev[:n], slot.keys_dev[:n]
-        desc_dev.copy_(slot.desc_pin[:n], non_blocking=True)
-        keys_dev.copy_(slot.keys_pin[:n], non_blocking=True)
-        d1, d2, labels = slot.d1[:n], slot.d2[:n], slot.labels[:n]
-        geom, radio = (slot.geom[:n], slot.radio[:n]) if self.export_drawn else (None, None)
+        desc_dev, keys_dev = slot.desc_dev[:rows], slot.keys_dev[:rows]
+        desc_dev.copy_(slot.desc_pin[:rows], non_blocking=True)
+        keys_dev.copy_(slot.keys_pin[:rows], non_blocking=True)
+        d1, d2, labels = slot.d1[:rows], slot.d2[:rows], slot.labels[:rows]
+        geom, radio = (slot.geom[:rows], slot.radio[:rows]) if self.export_drawn else (None, None)
         args = (self.city_table.data_ptr(), _lib.host_int32(self.city_hw), len(self.cities), self.C,
-                _lib.host_int32(slot.desc_pin.data_ptr()), desc_dev.data_ptr(), n, self.S, d1.data_ptr(), d2.data_ptr(),
+                _lib.host_int32(slot.desc_pin.data_ptr()), desc_dev.data_ptr(), rows, self.S, d1.data_ptr(), d2.data_ptr(),
                 labels.data_ptr(), keys_dev.data_ptr(), *self.augment.abi_args(), _lib.ptr(geom), _lib.ptr(radio))
         if self.warp is None:
             _lib.call('bdn_sample_patches_aug', *args, cur.cuda_stream)
         else:
-            records = slot.warp[:n] if self.export_drawn else None
+            records = slot.warp[:rows] if self.export_drawn else None
             _lib.call('bdn_sample_patches_warp', *args, *self.warp.abi_args(), None, None, _lib.ptr(records), cur.cuda_stream)
+        if self.mix is not None:
+            plan_dev = slot.plan_dev[:n]
+            plan_dev.copy_(slot.plan_pin[:n], non_blocking=True)
+            _lib.call('bdn_mix_patches', _lib.host_int32(slot.plan_pin.data_ptr()), plan_dev.data_ptr(), n, rows, self.C, self.S,
+                      MIX_MODES[self.mix.mode], self.mix.paste_label, self.mix.margin, d1.data_ptr(), d2.data_ptr(), labels.data_ptr(),
+                      None, cur.cuda_stream)
+            d1, d2, labels = d1[:n], d2[:n], labels[:n]
         if cur.cuda_stream not in self._streams:
             self._streams.add(cur.cuda_stream)
             for t in self._long_lived():
                 t.record_stream(cur)
         slot.done = torch.cuda.Event()
         slot.done.record(cur)
-        self.last_drawn = ((geom, radio) if self.warp is None else (geom, radio, records)) if self.export_drawn else None
+        if self.export_drawn:
+            drawn = (geom, radio) if self.warp is None else (geom, radio, records)
+            self.last_drawn = drawn if self.mix is None else tuple(t[:n] for t in drawn) + (plan_dev,)
+        else:
+            self.last_drawn = None
         return d1, d2, labels
+
+    def _plan_mix(self, slot, n, epoch):
+        """Host half of a mixed batch: the plan of the n recipients in the pinned slot (bdn_mix_plan on their keys), then the descriptor
+        and the sample key of every mixed sample's donor behind the recipients'.  Returns the number of rows to cut, n + donors."""
+        mix = self.mix
+        _lib.call('bdn_mix_plan', self.augment.seed, _lib.host_uint64(slot.keys_pin.data_ptr()), n, self.S, mix.p, MIX_MODES[mix.mode],
+                  *mix.box_size, _lib.host_int32(mix.donors), len(self.dataset) if mix.donors is None else len(mix.donors),
+                  _lib.host_int32(slot.plan_pin.data_ptr()))
+        rows = n
+        for on, donor in slot.plan_np[:n, :2].tolist():
+            if on:
+                city, i, j = self.dataset.imgs[donor]
+                slot.desc_np[rows] = (self.city_index[city], i, j, 0)
+                slot.keys_np[rows] = PatchAugment.sample_key(epoch, donor)
+                rows += 1
+        self.mixed += rows - n
+        self.seen += n
+        return rows
+
+    def label_counts(self, value=1, chunk=4096):
+        """Device int32 [len(dataset)]: how many label bytes of every dataset item's window, at its grid position (no jitter), equal
+        `value` (bdn_patch_label_counts, in chunks of `chunk` descriptors on the current stream).  PatchMix.donors_from turns it into
+        a donor pool."""
+        counts = torch.empty((len(self.dataset),), dtype=torch.int32, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        for a in range(0, len(self.dataset), chunk):
+            desc = np.array([(self.city_index[city], i, j, 0) for city, i, j in self.dataset.imgs[a:a + chunk]], np.int32).reshape(-1, 4)
+            desc_dev = torch.from_numpy(desc).to(self.device)          # from pageable memory: the copy has read `desc` when it returns
+            _lib.call('bdn_patch_label_counts', self.city_table.data_ptr(), _lib.host_int32(self.city_hw), len(self.cities),
+                      _lib.host_int32(desc), desc_dev.data_ptr(), len(desc), self.S, int(value), counts[a:a + len(desc)].data_ptr(),
+                      cur.cuda_stream)
+            desc_dev.record_stream(cur)
+        return counts
 
     def _sample(self, indices):
         """Plan the batch on the host, copy its descriptors through the next pinned slot and launch on the current stream."""

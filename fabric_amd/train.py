@@ -73,14 +73,14 @@ def _patch_datasets(full_load, val_cities, patch_size, stride, augmentation):
 
 
 def make_device_loaders(full_load, val_cities, patch_size, stride, batch_size, augmentation, rank=0, world_size=1, seed=0,
-                        device=None, augment=None, warp=None):
+                        device=None, augment=None, warp=None, mix=None):
     """make_loaders with the patches cut on the device (fabric_amd.device_loader): the same datasets, built and sorted the same way,
     the same ShardSampler and drop_last for training, no augmentation and no drop_last for validation.  `full_load`'s city stacks are
     used in place when they are device tensors (ingest's device= output) and uploaded once otherwise; both loaders share them.  The
     augmentation draws come from the process's global `random` at iteration time, as with make_loaders(num_workers=0).
     `augment`: a fabric_amd.augment.PatchAugment for the TRAINING loader only (its draws then come from the policy's counter-based
     generator and `augmentation` is ignored for it); `warp`: a fabric_amd.augment.PatchWarp beside it, for the training loader only too;
-    validation is never augmented."""
+    `mix`: a fabric_amd.augment.PatchMix beside it, likewise; validation is never augmented."""
     from .device_loader import DevicePatchLoader, device_stacks
     from .parallel import ShardSampler
     device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
@@ -90,17 +90,24 @@ def make_device_loaders(full_load, val_cities, patch_size, stride, batch_size, a
     extra = {} if augment is None else dict(augment=augment)
     if warp is not None:
         extra['warp'] = warp
+    if mix is not None:
+        extra['mix'] = mix
     return (DevicePatchLoader(train_ds, stacks, batch_size, sampler=sampler, drop_last=True, device=device, **extra),
             DevicePatchLoader(val_ds, stacks, batch_size, device=device))
+
+
+MIX_FLAGS = (('p', 0.0), ('mode', 'box'), ('box', None), ('margin', 0), ('donors', 'all'), ('min_pixels', 1))      # --mix_*: name, default
 
 
 def augment_from_opt(opt):
     """The PatchAugment of the --aug_* flags, or None when all are at their defaults.  Raises ValueError for flags that cannot be
     honoured: without --device_patches true (the patches of any other loader are cut on the host) or with values the policy refuses.
-    A warp flag (--aug_rotate / --aug_scale / --aug_misreg) alone is enough: the PatchWarp of warp_from_opt rides on this policy."""
+    A warp flag (--aug_rotate / --aug_scale / --aug_misreg) alone is enough: the PatchWarp of warp_from_opt rides on this policy; so is
+    a --mix_* flag, for the PatchMix of mix_from_opt."""
     given = [f'--aug_{k}' for k, off in (('jitter', 0), ('gain', 0.0), ('bias', 0.0), ('shared_dates', False), ('noise', 0.0),
                                          ('erase_p', 0.0), ('erase_size', None), ('seed', None), ('rotate', 0.0), ('scale', None),
                                          ('misreg', 0.0)) if getattr(opt, f'aug_{k}') != off]
+    given += [f'--mix_{k}' for k, off in MIX_FLAGS if getattr(opt, f'mix_{k}', off) != off]
     if not given:
         return None
     if not opt.device_patches:
@@ -122,6 +129,21 @@ def warp_from_opt(opt):
     from .augment import PatchWarp
     return PatchWarp(rotate=opt.aug_rotate, scale=tuple(opt.aug_scale) if opt.aug_scale else (1.0, 1.0), misreg=opt.aug_misreg,
                      oob_label=opt.ignore_label)
+
+
+def mix_from_opt(opt):
+    """The PatchMix of the --mix_* flags, or None when --mix_p is 0; paste_label is 1, the change class.  The pool of --mix_donors change
+    needs the loader (label_counts) and is set by main.  augment_from_opt refuses the flags without --device_patches true and builds
+    the PatchAugment it rides on."""
+    if not opt.mix_p:
+        return None
+    from .augment import PatchMix
+    mix = PatchMix(p=opt.mix_p, mode=opt.mix_mode, box_size=tuple(opt.mix_box) if opt.mix_box else (1, 1), paste_label=1,
+                   margin=opt.mix_margin)
+    mix.check(opt.patch_size, 1)
+    if opt.mix_min_pixels < 1:
+        raise ValueError(f'--mix_min_pixels {opt.mix_min_pixels}: a donor holds at least one change pixel')
+    return mix
 
 
 def _device_batches(loader, dev, feeder):
@@ -588,6 +610,16 @@ def main(argv=None):
                     help='zoom every patch pair by a factor log-uniform in [LO, HI], 1/8 <= LO <= HI <= 8; above 1 magnifies')
     ap.add_argument('--aug_misreg', type=float, default=0.0, metavar='PX',
                     help='misregistration: sample date 2 shifted against date 1 by up to PX pixels on either axis; the labels follow date 1')
+    ap.add_argument('--mix_p', type=float, default=0.0, metavar='F',
+                    help='--device_patches true: probability that a training sample takes pixels of another one (a donor) on both dates '
+                         'and in the labels (fabric_amd.augment.PatchMix); the epoch record gains train_mix_frac')
+    ap.add_argument('--mix_mode', default='box', choices=['box', 'object'],
+                    help='box: a rectangle of the donor (CutMix; --mix_box); object: the donor\'s change pixels (label 1), dilated by --mix_margin')
+    ap.add_argument('--mix_box', type=int, nargs=2, default=None, metavar=('LO', 'HI'), help='sides of the pasted rectangle, drawn in LO..HI pixels')
+    ap.add_argument('--mix_margin', type=int, default=0, metavar='M', help='--mix_mode object: paste a ring of M pixels (0..16) around the change pixels too')
+    ap.add_argument('--mix_donors', default='all', choices=['all', 'change'],
+                    help='the donor pool: every training patch, or those with at least --mix_min_pixels change pixels at their grid position')
+    ap.add_argument('--mix_min_pixels', type=int, default=1, metavar='K', help='--mix_donors change: the fewest change pixels a donor holds')
     ap.add_argument('--scene_stride', type=int, default=0,
                     help='full validation scenes: 0 = the reference\'s non-overlapping argmax masks (predict_scene); N > 0 = tiles every N px, '
                          'softmax probabilities blended (predict_scene_blended), also writes {city}_epoch_{e}_proba.png and a scene F1 line')
@@ -704,6 +736,7 @@ def main(argv=None):
     try:
         patch_augment = augment_from_opt(opt)
         patch_warp = warp_from_opt(opt) if patch_augment is not None else None
+        patch_mix = mix_from_opt(opt) if patch_augment is not None else None
     except ValueError as e:
         raise SystemExit(str(e))
 
@@ -740,7 +773,13 @@ def main(argv=None):
         train_loader, val_loader = make_device_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
                                                        rank=rank, world_size=world, seed=opt.seed, device=dev,
                                                        **({} if patch_augment is None else dict(augment=patch_augment)),
-                                                       **({} if patch_warp is None else dict(warp=patch_warp)))
+                                                       **({} if patch_warp is None else dict(warp=patch_warp)),
+                                                       **({} if patch_mix is None else dict(mix=patch_mix)))
+        if patch_mix is not None and opt.mix_donors == 'change':      # the pool: training patches that hold change at their grid position
+            try:
+                train_loader.mix = patch_mix.donors_from(train_loader.label_counts(1), opt.mix_min_pixels)
+            except ValueError as e:
+                raise SystemExit(str(e))
     else:
         train_loader, val_loader = make_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
                                                 num_workers=opt.num_workers, rank=rank, world_size=world, seed=opt.seed)
@@ -813,6 +852,8 @@ def main(argv=None):
             tr = train_epoch(step, train_loader, dev, opt.patch_size, feeder)
         else:
             tr = train_epoch_autograd(model, criterion, optimizer, train_loader, dev, opt.patch_size, world, feeder)
+        if patch_mix is not None:                              # this rank's share of mixed samples: host counts of the loader's plans
+            tr['mix_frac'] = train_loader.mixed / max(train_loader.seen, 1)
         with step.ema_weights() if averaging else contextlib.nullcontext():       # --ema_decay / --swa: evaluate the averaged weights
             if val_curve is None:
                 va = validate(model, val_loader, dev, opt.patch_size, criterion, feeder, ignore_index=opt.ignore_label)

@@ -684,6 +684,33 @@ int bdn_sample_patches_warp(const void* cities_dev, const int32_t* city_hw_host,
                             int32_t* drawn_geom, float* drawn_radio,
                             float rotate_rad, float log2_lo, float log2_hi, float misreg, int oob_label,
                             const float* warp_host, const float* warp_dev, float* warp_out, void* stream);
+/* ---- mixing across samples: CutMix boxes (French et al., BMVC 2020) and copy-paste of change objects (Ghiasi et al., CVPR 2021) on
+ * the patches the entries above cut.  No reference: utils/dataloaders.py:148-165 transforms one sample at a time.  A mixed sample (the
+ * recipient) takes every band of both dates and the label byte of ONE donor sample wherever a mask is set; bits are moved, never computed.
+ * bdn_mix_plan: HOST only (no device call, no stream).  keys_host: uint64 [n], 8-byte aligned, the recipients' sample keys.  Draws of
+ *   sample k, from stream 0x4D495820 ('MIX ') keyed by (seed, keys_host[k]) as above:
+ *     slot 0   mixed iff u(w0) < p (p a float32 in [0, 1]);  donor_index = pool[range(w1, n_pool)], pool_host int32 [n_pool] or NULL
+ *              (then pool[i] = i and n_pool is the dataset length);  h = lo + range(w2, hi - lo + 1), w alike from w3; 1 <= lo <= hi <= S.
+ *     slot 1   mode 0 (box) only: top = range(w0, S - h + 1), left = range(w1, S - w + 1).  Mode 1 (object): the rectangle is
+ *              (0, 0, S, S) and slot 1 is not drawn.
+ *   plan_host: int32 [n][8] = (on, donor_index, donor_row, top, left, h, w, 0); donor_row = n + the number of mixed samples before this
+ *   one; an unmixed sample has donor_row = -1 and zeros elsewhere.
+ * bdn_mix_patches: d1, d2 f32 [rows][C][S][S], labels uint8 [rows][S][S]; rows 0..n-1 are recipients, mixed in place, rows n..rows-1
+ *   donors, only read.  plan_host is checked here before the launch (on in 0..1; for a mixed sample n <= donor_row < rows and the
+ *   rectangle inside the patch); plan_dev: the same table in device memory, 16-byte aligned, which the kernel reads.  mode 0: the mask is
+ *   the rectangle.  mode 1: the mask is (donor labels == paste_label) dilated by a (2 margin + 1) square, margin in 0..16, donor labels
+ *   outside the patch unset, confined to the patch; paste_label in 0..255.  The recipient is never read and is written only where the
+ *   mask is set.  mask_out (or NULL): uint8 [n][S][S], 1 where the donor was taken and 0 elsewhere, all of an unmixed sample included.
+ *   One launch whatever the data; no atomics.  S <= 2^14 (offsets inside a plane are 32 bits; every other offset is size_t).
+ * bdn_patch_label_counts: counts_dev int32 [n], counts[k] = the label bytes equal to `value` (0..255) in the S x S window of descriptor k
+ *   (city, row, col, sym; sym is ignored); cities_dev, city_hw_host, desc_host, desc_dev as in bdn_sample_patches, checked the same way.
+ *   Integer sums, no atomics: the same bits every run. */
+int bdn_mix_plan(uint64_t seed, const uint64_t* keys_host, int n, int S, float p, int mode, int lo, int hi,
+                 const int32_t* pool_host, int n_pool, int32_t* plan_host);
+int bdn_mix_patches(const int32_t* plan_host, const int32_t* plan_dev, int n, int rows, int C, int S, int mode, int paste_label, int margin,
+                    float* d1, float* d2, uint8_t* labels, uint8_t* mask_out, void* stream);
+int bdn_patch_label_counts(const void* cities_dev, const int32_t* city_hw_host, int n_cities, const int32_t* desc_host,
+                           const int32_t* desc_dev, int n, int S, int value, int32_t* counts_dev, void* stream);
 
 /* ---- optim.SGD(lr) step, train.py:55,95: p -= lr * grad_scale * g over a flat f32 buffer ---- */
 int bdn_sgd_step(float* params, const float* grads, float lr, float grad_scale, size_t n, void* stream);
