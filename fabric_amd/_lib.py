@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get('BIDATE_LIB') or os.path.join(_HERE, 'csrc', 'libbidat
 BDN_F32, BDN_BF16, BDN_BF16X3, BDN_BF16X2 = 0, 1, 2, 3
 IN_PLAIN, IN_BNRELU = 0, 1
 EVAL_STAGE, EVAL_PAIR, EVAL_CLS = 0, 1, 2
+FUSE_PRODUCT, FUSE_ABSDIFF = 0, 1
+FUSIONS = {'product': FUSE_PRODUCT, 'absdiff': FUSE_ABSDIFF}
 WG_SIMPLE, WG_ROLE = 1, 5
 
 
@@ -57,6 +59,8 @@ SIGNATURES = {
     'bdn_bn_eval_fold_multi': (_i, [_vp, _i, _i, _f, _vp]),
     'bdn_conv3x3_eval': (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_conv3x3_eval_pair': (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_conv3x3_eval_fusion': (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_conv3x3_eval_pair_fusion': (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_conv3x3_eval_cls': (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'bdn_bn_bwd_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
     'bdn_bn_bwd': (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -68,6 +72,9 @@ SIGNATURES = {
     'bdn_bnrelu_pool': (_i, [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     'bdn_fuse_product': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_product_pool': (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_fuse_dates': (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_fuse_dates_pool': (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_fuse_dates_pool_split': (_i, [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     'bdn_upsample2x': (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'bdn_product_pool_split': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     'bdn_upsample2x_split': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -75,6 +82,7 @@ SIGNATURES = {
     'bdn_upsample2x_bwd_rows': (_i, [_i, _i, _i, _i, _i]),
     'bdn_upsample2x_bwd_bs': (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'bdn_enc_skip_bwd': (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_enc_skip_bwd_fusion': (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_enc_skip_bwd_rows': (_i, [_i, _i, _i, _i, _i]),
     'bdn_outc_fwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'bdn_outc_bwd_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -67,7 +67,10 @@ struct ConvArgs {
     //            two DATES of one patch pair (N = 2 pair_stride) -- instead of two consecutive ones.  The block then holds both dates'
     //            activations of its pixels in LDS: `out` [pair_stride,H,W,Cout] receives their product, ep_pool [N,H/2,W/2,Cout] both pooled
     //            maps, and neither date's activation reaches HBM.
-    const float* ep_scale; const float* ep_shift; const void* ep_mul; void* ep_pool; int pair_stride;
+    //   ep_fuse  how two dates' rounded activations meet in `out`, with ep_mul and in paired launches: BDN_FUSE_PRODUCT a * mul as above,
+    //            BDN_FUSE_ABSDIFF |a_d2 - a_d1| (one float32 subtraction, rounded once; FC-Siam-diff).  A runtime, block-uniform field: the
+    //            instantiations are the same.
+    const float* ep_scale; const float* ep_shift; const void* ep_mul; void* ep_pool; int pair_stride; int ep_fuse;
     const float* cls_w; const float* cls_b; int cls_n; float* cls_logits; unsigned char* cls_mask; const int* cls_origins; int cls_H, cls_W;
     // bf16x3 launches on a FLOAT32 source (template flag XF; round 6, bdn_conv3x3_x3src): in0 = the float32 tensor [N,H,W,C0] itself (ld0 = C0), in_bn
     // its producer's BatchNorm table or null.  The staging applies relu(z * scale + shift) and splits the value into bf16 hi + lo on its way into the
@@ -595,6 +598,7 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
         unsigned char* outp = reinterpret_cast<unsigned char*>(a.out) + (size_t)col0 * CF::OES;
         const unsigned char* mulp = reinterpret_cast<const unsigned char*>(a.ep_mul) + (size_t)col0 * CF::OES;
         const bool has_mul = a.ep_mul != nullptr, has_out = a.out != nullptr;       // block-uniform
+        const bool absdiff = a.ep_fuse == BDN_FUSE_ABSDIFF;                         // block-uniform (ep_mul and paired launches)
         const bool full = (n0 + (TI - 1) * istr < a.N) && (y0 + TH <= a.H) && (x0 + TW <= a.W);          // block-uniform
 #define OUT_OFS(i_, dst_)                                   /* byte offset of copy-out unit i_ in the output tensor, ~0 = outside the image */ \
         {                                                                                               \
@@ -707,7 +711,7 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
                             Unit<TO>::unpack(*reinterpret_cast<const uint4*>(otile + slot_ * CF::OSTR + sub_ * 16), fa);
                             Unit<TO>::unpack(*reinterpret_cast<const uint4*>(otile + (slot_ + HALF) * CF::OSTR + sub_ * 16), fb);
 #pragma unroll
-                            for (int e = 0; e < OEPU; e++) fa[e] *= fb[e];
+                            for (int e = 0; e < OEPU; e++) fa[e] = absdiff ? fabsf(fb[e] - fa[e]) : fa[e] * fb[e];
                             *reinterpret_cast<uint4*>(outp + ((unsigned)((n0 * a.H + y_) * a.W + x_) * orow + (unsigned)sub_ * 16u)) = Unit<TO>::pack(fa);
                         }
                     }
@@ -724,7 +728,7 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
             if (has_mul) {                                                                              \
                 float fa[OEPU], fb[OEPU];                                                               \
                 Unit<TO>::unpack(v, fa); Unit<TO>::unpack(mexpr_, fb);                                  \
-                _Pragma("unroll") for (int e = 0; e < OEPU; e++) fa[e] *= fb[e];                         \
+                _Pragma("unroll") for (int e = 0; e < OEPU; e++) fa[e] = absdiff ? fabsf(fb[e] - fa[e]) : fa[e] * fb[e]; \
                 v = Unit<TO>::pack(fa);                                                                 \
             }                                                                                           \
             *reinterpret_cast<uint4*>(outp + (o_)) = v;                                                 \
@@ -1062,7 +1066,7 @@ static int conv3x3_impl(int dtype, const void* in0, int C0, const void* in1, int
     a.bs_z = bs_z; a.bs_bn = bs_bn; a.in2 = nullptr; a.Dz = 0;
     a.bb_z = bb_z; a.bb_bn = bb_bn; a.bb_sums = bb_sums; a.bb_dz = bb_dz; a.bb_invM = 1.f / (float)((size_t)imgs_per_group * H * W);
     a.N = N; a.H = H; a.W = W; a.Cout = Cout;
-    a.ep_scale = a.ep_shift = nullptr; a.ep_mul = nullptr; a.ep_pool = nullptr; a.pair_stride = 0;
+    a.ep_scale = a.ep_shift = nullptr; a.ep_mul = nullptr; a.ep_pool = nullptr; a.pair_stride = 0; a.ep_fuse = BDN_FUSE_PRODUCT;
     a.cls_w = a.cls_b = nullptr; a.cls_n = 0; a.cls_logits = nullptr; a.cls_mask = nullptr; a.cls_origins = nullptr; a.cls_H = a.cls_W = 0; a.x3_split = nullptr;
     const bool x3f = (dtype == BDN_BF16X3 || dtype == BDN_BF16X2);       // (C0 % 16 == 0 was checked above: 64-channel chunks where C0 allows, else 16)
     const ConvPlan g = x3f ? conv_plan_x3f(N, H, W, Cout, imgs_per_group) : conv_plan(N, H, W, Cout, imgs_per_group);
@@ -1131,7 +1135,7 @@ extern "C" int bdn_conv3x3_x3src(int dtype, const float* in, int C0, int in_mode
     a.imgs_per_group = imgs_per_group; a.w = w; a.bias = bias; a.out = out; a.stats_partial = stats_partial;
     a.bs_z = nullptr; a.bs_bn = nullptr; a.bb_z = nullptr; a.bb_bn = nullptr; a.bb_sums = nullptr; a.bb_dz = nullptr; a.bb_invM = 0.f;
     a.N = N; a.H = H; a.W = W; a.Cout = Cout;
-    a.ep_scale = a.ep_shift = nullptr; a.ep_mul = nullptr; a.ep_pool = nullptr; a.pair_stride = 0;
+    a.ep_scale = a.ep_shift = nullptr; a.ep_mul = nullptr; a.ep_pool = nullptr; a.pair_stride = 0; a.ep_fuse = BDN_FUSE_PRODUCT;
     a.cls_w = a.cls_b = nullptr; a.cls_n = 0; a.cls_logits = nullptr; a.cls_mask = nullptr; a.cls_origins = nullptr; a.cls_H = a.cls_W = 0;
     a.x3_split = split_out;
     const ConvPlan g = conv_plan_x3f(N, H, W, Cout, imgs_per_group);
@@ -1187,7 +1191,7 @@ extern "C" const char* bdn_conv3x3_dgrad_bb_variant(int N, int H, int W, int Cou
 // with the conv bias into ep_scale / ep_shift by bdn_bn_eval_fold_multi) -> ReLU in ONE launch that stores the activation.  Optional fused
 // consumers: the date product (mul), MaxPool2d(2) (pool), the 1x1 classifier + argmax (+ scene stitching).  See ConvArgs.
 static int conv3x3_eval_impl(int dtype, const void* in0, int C0, const void* in1, int C1, const void* w, const float* ep_scale, const float* ep_shift,
-                             void* out, const void* mul, void* pool, const float* cls_w, const float* cls_b, int ncls, float* logits,
+                             void* out, const void* mul, int fusion, void* pool, const float* cls_w, const float* cls_b, int ncls, float* logits,
                              unsigned char* mask, const int* origins, int Hs, int Ws, int N, int H, int W, int Cout, void* stream) {
     if (!in0 || !w || !ep_scale || !ep_shift) BDN_FAIL(BDN_E_ARG, "conv3x3_eval: null pointer");
     if (N <= 0 || H <= 0 || W <= 0) BDN_FAIL(BDN_E_SHAPE, "conv3x3_eval: bad N=%d H=%d W=%d", N, H, W);
@@ -1195,6 +1199,7 @@ static int conv3x3_eval_impl(int dtype, const void* in0, int C0, const void* in1
     if (in1 == nullptr) C1 = 0;
     if (C1 < 0 || (in1 && C1 == 0)) BDN_FAIL(BDN_E_SHAPE, "conv3x3_eval: bad C1=%d", C1);
     if (dtype != BDN_BF16 && dtype != BDN_F32) BDN_FAIL(BDN_E_ARG, "conv3x3_eval: bad dtype %d (bf16 / f32)", dtype);
+    if (fusion != BDN_FUSE_PRODUCT && fusion != BDN_FUSE_ABSDIFF) BDN_FAIL(BDN_E_ARG, "conv3x3_eval: bad fusion mode %d", fusion);
     if (pool && (H < 2 || W < 2)) BDN_FAIL(BDN_E_SHAPE, "conv3x3_eval: pooling needs H, W >= 2");
     if (cls_w) {
         if (!cls_b || (!logits && !mask)) BDN_FAIL(BDN_E_ARG, "conv3x3_eval_cls: null pointer");
@@ -1210,7 +1215,7 @@ static int conv3x3_eval_impl(int dtype, const void* in0, int C0, const void* in1
     a.in_bn = nullptr; a.imgs_per_group = N; a.w = w; a.w_kgroups = 0; a.bias = nullptr; a.out = out; a.stats_partial = nullptr;
     a.bs_z = nullptr; a.bs_bn = nullptr; a.bb_z = nullptr; a.bb_bn = nullptr; a.bb_sums = nullptr; a.bb_dz = nullptr; a.bb_invM = 0.f;
     a.N = N; a.H = H; a.W = W; a.Cout = Cout;
-    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.ep_mul = mul; a.ep_pool = pool; a.pair_stride = 0;
+    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.ep_mul = mul; a.ep_pool = pool; a.pair_stride = 0; a.ep_fuse = fusion;
     a.cls_w = cls_w; a.cls_b = cls_b; a.cls_n = ncls; a.cls_logits = logits; a.cls_mask = mask; a.cls_origins = origins; a.cls_H = Hs; a.cls_W = Ws; a.x3_split = nullptr;
     // no statistic groups in eval mode: two images of a small map may always share a tile
     const ConvPlan g = conv_plan(N, H, W, Cout, N % 2 == 0 ? 2 : 1);
@@ -1229,7 +1234,14 @@ static int conv3x3_eval_impl(int dtype, const void* in0, int C0, const void* in1
 extern "C" int bdn_conv3x3_eval(int dtype, const void* in0, int C0, const void* in1, int C1, const void* w,
                                 const float* ep_scale, const float* ep_shift, void* out, const void* mul, void* pool,
                                 int N, int H, int W, int Cout, void* stream) {
-    return conv3x3_eval_impl(dtype, in0, C0, in1, C1, w, ep_scale, ep_shift, out, mul, pool, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0,
+    return conv3x3_eval_impl(dtype, in0, C0, in1, C1, w, ep_scale, ep_shift, out, mul, BDN_FUSE_PRODUCT, pool, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0,
+                             N, H, W, Cout, stream);
+}
+
+extern "C" int bdn_conv3x3_eval_fusion(int dtype, int fusion, const void* in0, int C0, const void* in1, int C1, const void* w,
+                                       const float* ep_scale, const float* ep_shift, void* out, const void* mul, void* pool,
+                                       int N, int H, int W, int Cout, void* stream) {
+    return conv3x3_eval_impl(dtype, in0, C0, in1, C1, w, ep_scale, ep_shift, out, mul, fusion, pool, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0,
                              N, H, W, Cout, stream);
 }
 
@@ -1260,12 +1272,13 @@ static int dispatch_conv_pair(const ConvArgs& a, const ConvPlan& p, hipStream_t 
     return launch_conv<T, 128, 8, 8, 2, 64, 2, 2, false, T, false, false, true>(a, g.n_mtiles, st);
 }
 
-extern "C" int bdn_conv3x3_eval_pair(int dtype, const void* in, int C0, const void* w, const float* ep_scale, const float* ep_shift,
-                                     void* f_out, void* pool, int B, int H, int W, int Cout, void* stream) {
+static int conv3x3_eval_pair_impl(int dtype, int fusion, const void* in, int C0, const void* w, const float* ep_scale, const float* ep_shift,
+                                  void* f_out, void* pool, int B, int H, int W, int Cout, void* stream) {
     if (!in || !w || !ep_scale || !ep_shift || !f_out) BDN_FAIL(BDN_E_ARG, "conv3x3_eval_pair: null pointer");
     if (B <= 0 || H <= 0 || W <= 0) BDN_FAIL(BDN_E_SHAPE, "conv3x3_eval_pair: bad B=%d H=%d W=%d", B, H, W);
     if (Cout <= 0 || Cout % 64) BDN_FAIL(BDN_E_SHAPE, "conv3x3_eval_pair: Cout=%d must be a multiple of 64", Cout);
     if (dtype != BDN_BF16 && dtype != BDN_F32) BDN_FAIL(BDN_E_ARG, "conv3x3_eval_pair: bad dtype %d (bf16 / f32)", dtype);
+    if (fusion != BDN_FUSE_PRODUCT && fusion != BDN_FUSE_ABSDIFF) BDN_FAIL(BDN_E_ARG, "conv3x3_eval_pair: bad fusion mode %d", fusion);
     const int es = dtype == BDN_F32 ? 4 : 2;
     if (C0 <= 0 || (C0 * es) % 128) BDN_FAIL(BDN_E_SHAPE, "conv3x3_eval_pair: C0=%d must be a multiple of %d", C0, 128 / es);
     if (pool && (H < 2 || W < 2)) BDN_FAIL(BDN_E_SHAPE, "conv3x3_eval_pair: pooling needs H, W >= 2");
@@ -1277,7 +1290,7 @@ extern "C" int bdn_conv3x3_eval_pair(int dtype, const void* in, int C0, const vo
     a.in_bn = nullptr; a.imgs_per_group = B; a.w = w; a.w_kgroups = 0; a.bias = nullptr; a.out = f_out; a.stats_partial = nullptr;
     a.bs_z = nullptr; a.bs_bn = nullptr; a.bb_z = nullptr; a.bb_bn = nullptr; a.bb_sums = nullptr; a.bb_dz = nullptr; a.bb_invM = 0.f;
     a.N = 2 * B; a.H = H; a.W = W; a.Cout = Cout;
-    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.ep_mul = nullptr; a.ep_pool = pool; a.pair_stride = B;
+    a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.ep_mul = nullptr; a.ep_pool = pool; a.pair_stride = B; a.ep_fuse = fusion;
     a.cls_w = a.cls_b = nullptr; a.cls_n = 0; a.cls_logits = nullptr; a.cls_mask = nullptr; a.cls_origins = nullptr; a.cls_H = a.cls_W = 0; a.x3_split = nullptr;
     const ConvPlan g = conv_plan_pair(B, H, W, Cout);
     a.tiles_y = g.g.tiles_y; a.tiles_x = g.g.tiles_x; a.n_ntiles = 0;
@@ -1285,11 +1298,21 @@ extern "C" int bdn_conv3x3_eval_pair(int dtype, const void* in, int C0, const vo
     return dtype == BDN_BF16 ? dispatch_conv_pair<bf16s>(a, g, st) : dispatch_conv_pair<float>(a, g, st);
 }
 
+extern "C" int bdn_conv3x3_eval_pair(int dtype, const void* in, int C0, const void* w, const float* ep_scale, const float* ep_shift,
+                                     void* f_out, void* pool, int B, int H, int W, int Cout, void* stream) {
+    return conv3x3_eval_pair_impl(dtype, BDN_FUSE_PRODUCT, in, C0, w, ep_scale, ep_shift, f_out, pool, B, H, W, Cout, stream);
+}
+
+extern "C" int bdn_conv3x3_eval_pair_fusion(int dtype, int fusion, const void* in, int C0, const void* w, const float* ep_scale, const float* ep_shift,
+                                            void* f_out, void* pool, int B, int H, int W, int Cout, void* stream) {
+    return conv3x3_eval_pair_impl(dtype, fusion, in, C0, w, ep_scale, ep_shift, f_out, pool, B, H, W, Cout, stream);
+}
+
 extern "C" int bdn_conv3x3_eval_cls(int dtype, const void* in0, int C0, const void* w, const float* ep_scale, const float* ep_shift, void* act_out,
                                     const float* cls_w, const float* cls_b, int ncls, float* logits, uint8_t* mask, const int32_t* origins,
                                     int Hs, int Ws, int N, int H, int W, int Cout, void* stream) {
     if (!cls_w) BDN_FAIL(BDN_E_ARG, "conv3x3_eval_cls: null pointer");
-    return conv3x3_eval_impl(dtype, in0, C0, nullptr, 0, w, ep_scale, ep_shift, act_out, nullptr, nullptr, cls_w, cls_b, ncls, logits, mask, origins,
+    return conv3x3_eval_impl(dtype, in0, C0, nullptr, 0, w, ep_scale, ep_shift, act_out, nullptr, BDN_FUSE_PRODUCT, nullptr, cls_w, cls_b, ncls, logits, mask, origins,
                              Hs, Ws, N, H, W, Cout, stream);
 }
 
@@ -1367,7 +1390,7 @@ extern "C" int bdn_conv3d(int dtype, const void* in, int C, int in_mode, const f
     a.w = w; a.bias = bias; a.out = out; a.stats_partial = stats_partial; a.bs_z = nullptr; a.bs_bn = nullptr;
     a.N = N * D; a.H = H; a.W = W; a.Cout = Cout;
     a.bb_z = nullptr; a.bb_bn = nullptr; a.bb_sums = nullptr; a.bb_dz = nullptr; a.bb_invM = 0.f;
-    a.ep_scale = a.ep_shift = nullptr; a.ep_mul = nullptr; a.ep_pool = nullptr; a.pair_stride = 0;
+    a.ep_scale = a.ep_shift = nullptr; a.ep_mul = nullptr; a.ep_pool = nullptr; a.pair_stride = 0; a.ep_fuse = BDN_FUSE_PRODUCT;
     a.cls_w = a.cls_b = nullptr; a.cls_n = 0; a.cls_logits = nullptr; a.cls_mask = nullptr; a.cls_origins = nullptr; a.cls_H = a.cls_W = 0; a.x3_split = nullptr;
     const ConvPlan p = conv3d_plan(N * D, H, W, Cout);
     a.tiles_y = p.g.tiles_y; a.tiles_x = p.g.tiles_x; a.n_ntiles = 0;

@@ -1,6 +1,6 @@
 // Stage-boundary kernels between the convolutions (all HBM-bound, NHWC, 16-byte channel units):
 //   bnrelu_pool   nn.MaxPool2d(2) of relu(bn(z))                 reference models/unet_parts.py:40
-//   fuse_product  torch.relu(x_d2 * x_d1)                        reference models/bidate_model.py:35-38
+//   fuse_product  torch.relu(x_d2 * x_d1), or |x_d2 - x_d1|        reference models/bidate_model.py:35-38 (mode: BDN_FUSE_*)
 //   upsample2x    nn.Upsample(x2, bilinear, align_corners) + pad reference models/unet_parts.py:56-58,68-72
 //   ..._bwd       their backward gathers (no atomics: every output element gathers its contributions)
 // Every thread owns one channel unit (its BatchNorm scale/shift stay in registers) and walks pixels.
@@ -116,8 +116,27 @@ extern "C" int bdn_bnrelu(int dtype, const void* z, const float* bn, int imgs_pe
     return BDN_OK;
 }
 
-// ============================================================ date fusion relu(a_d2 * a_d1)
-template <typename T>
+// ============================================================ date fusion relu(a_d2 * a_d1) / |a_d2 - a_d1|
+// The date fusion of two rounded activations (FM = BDN_FUSE_PRODUCT / BDN_FUSE_ABSDIFF, a template parameter of every kernel that carries it:
+// the product instantiations are the code they were).  Both results are >= 0, so the reference's outer relu is a no-op.
+//   forward   f = a1 * a2                        |  f = |a2 - a1|: ONE float32 subtraction, exact sign removal, rounded once on store
+//   backward  dA1 = dF * a2, dA2 = dF * a1       |  dA1 = dF * s, dA2 = -(dF * s), s = sign(a1 - a2) in {-1, 0, +1}: exactly 0 at a tie
+//                                                   (torch.abs's rule; both-dead ReLUs are ties), selected, never multiplied by zero
+template <int FM>
+__device__ __forceinline__ float fuse_fwd(float a1, float a2) {
+    if constexpr (FM == BDN_FUSE_ABSDIFF) return fabsf(a2 - a1);
+    else return a1 * a2;
+}
+template <int FM>
+__device__ __forceinline__ void fuse_bwd(float df, float a1, float a2, float& d1, float& d2) {
+    if constexpr (FM == BDN_FUSE_ABSDIFF) {
+        d1 = a1 > a2 ? df : (a1 < a2 ? -df : 0.f);
+        d2 = a1 > a2 ? -df : (a1 < a2 ? df : 0.f);
+    } else { d1 = df * a2; d2 = df * a1; }
+}
+#define BDN_FUSION_CHECK(name_) if (fusion != BDN_FUSE_PRODUCT && fusion != BDN_FUSE_ABSDIFF) BDN_FAIL(BDN_E_ARG, name_ ": bad fusion mode %d", fusion)
+
+template <typename T, int FM>
 __global__ void fuse_product_kernel(const T* __restrict__ z, const float* __restrict__ bn, T* __restrict__ f, int npix, int C) {
     constexpr int EPU = ET<T>::EPU;
     const int CU = C / EPU, rows = 256 / CU, tid = threadIdx.x, cu = tid % CU, row = tid / CU, c = cu * EPU;
@@ -130,31 +149,43 @@ __global__ void fuse_product_kernel(const T* __restrict__ z, const float* __rest
         Unit<T>::unpack(*reinterpret_cast<const uint4*>(z + (size_t)p * C + c), a);
         Unit<T>::unpack(*reinterpret_cast<const uint4*>(z + ((size_t)npix + p) * C + c), b);
 #pragma unroll
-        for (int i = 0; i < EPU; i++) a[i] = act1<T>(a[i], sc0[i], sh0[i]) * act1<T>(b[i], sc1[i], sh1[i]);   // >= 0: relu is a no-op
+        for (int i = 0; i < EPU; i++) a[i] = fuse_fwd<FM>(act1<T>(a[i], sc0[i], sh0[i]), act1<T>(b[i], sc1[i], sh1[i]));   // >= 0: relu is a no-op
         *reinterpret_cast<uint4*>(f + (size_t)p * C + c) = Unit<T>::pack(a);
     }
 }
 
-extern "C" int bdn_fuse_product(int dtype, const void* z, const float* bn, void* f,
-                                int B, int H, int W, int C, void* stream) {
+template <int FM>
+static int fuse_dates_impl(int dtype, const void* z, const float* bn, void* f, int B, int H, int W, int C, void* stream) {
     if (!z || !bn || !f) BDN_FAIL(BDN_E_ARG, "fuse_product: null pointer");
     if (C % 16 || C > 1024 || 1024 % C) BDN_FAIL(BDN_E_SHAPE, "fuse_product: bad C");
     hipStream_t st = (hipStream_t)stream;
     const int npix = B * H * W;
     if (dtype == BDN_BF16) { const int per = 256 / (C / 8) * ITERS;
-        hipLaunchKernelGGL(fuse_product_kernel<bf16s>, dim3((npix + per - 1) / per), dim3(256), 0, st, (const bf16s*)z, bn, (bf16s*)f, npix, C); }
+        hipLaunchKernelGGL((fuse_product_kernel<bf16s, FM>), dim3((npix + per - 1) / per), dim3(256), 0, st, (const bf16s*)z, bn, (bf16s*)f, npix, C); }
     else if (dtype == BDN_F32) { const int per = 256 / (C / 4) * ITERS;
-        hipLaunchKernelGGL(fuse_product_kernel<float>, dim3((npix + per - 1) / per), dim3(256), 0, st, (const float*)z, bn, (float*)f, npix, C); }
+        hipLaunchKernelGGL((fuse_product_kernel<float, FM>), dim3((npix + per - 1) / per), dim3(256), 0, st, (const float*)z, bn, (float*)f, npix, C); }
     else BDN_FAIL(BDN_E_ARG, "fuse_product: bad dtype");
     BDN_CHECK_LAUNCH("fuse_product");
     return BDN_OK;
+}
+
+extern "C" int bdn_fuse_product(int dtype, const void* z, const float* bn, void* f,
+                                int B, int H, int W, int C, void* stream) {
+    return fuse_dates_impl<BDN_FUSE_PRODUCT>(dtype, z, bn, f, B, H, W, C, stream);
+}
+
+extern "C" int bdn_fuse_dates(int dtype, int fusion, const void* z, const float* bn, void* f,
+                              int B, int H, int W, int C, void* stream) {
+    BDN_FUSION_CHECK("fuse_dates");
+    return fusion == BDN_FUSE_ABSDIFF ? fuse_dates_impl<BDN_FUSE_ABSDIFF>(dtype, z, bn, f, B, H, W, C, stream)
+                                      : fuse_dates_impl<BDN_FUSE_PRODUCT>(dtype, z, bn, f, B, H, W, C, stream);
 }
 
 // ============================================================ product fusion + MaxPool2d(2) in one pass over z
 // reference models/bidate_model.py:35-38 + models/unet_parts.py:40: the skip f = relu(a_d2 * a_d1) of an encoder level
 // and the pooled input of the next level (both dates) both start from a = relu(bn(z)) of the same tensor; one
 // iteration = one 2x2 window x EPU channels x both dates, so z is read from HBM once instead of twice.
-template <typename T>
+template <typename T, int FM>
 __global__ void product_pool_kernel(const T* __restrict__ z, const float* __restrict__ bn, T* __restrict__ f, T* __restrict__ pool,
                                     int B, int H, int W, int C, int ncell, SplitOut sf, SplitOut sp, FastDiv dWc, FastDiv dHc) {
     constexpr int EPU = ET<T>::EPU;
@@ -182,7 +213,7 @@ __global__ void product_pool_kernel(const T* __restrict__ z, const float* __rest
                 for (int i = 0; i < EPU; i++) {
                     a0[i] = act1<T>(a0[i], sc0[i], sh0[i]); a1[i] = act1<T>(a1[i], sc1[i], sh1[i]);
                     m0[i] = fmaxf(m0[i], a0[i]); m1[i] = fmaxf(m1[i], a1[i]);
-                    a0[i] *= a1[i];                                         // >= 0: relu is a no-op
+                    a0[i] = fuse_fwd<FM>(a0[i], a1[i]);                     // >= 0: relu is a no-op
                 }
                 store_out<T>(f, p0 * C + c, sf, p0, c, a0);
             }
@@ -195,15 +226,16 @@ __global__ void product_pool_kernel(const T* __restrict__ z, const float* __rest
     }
 }
 
+template <int FM>
 static int product_pool_impl(int dtype, const void* z, const float* bn, void* f, void* pool, SplitOut sf, SplitOut sp,
                              int B, int H, int W, int C, void* stream) {
     if (C % 16 || C > 1024 || 1024 % C || H < 2 || W < 2) BDN_FAIL(BDN_E_SHAPE, "product_pool: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int ncell = B * ((H + 1) / 2) * ((W + 1) / 2);
     if (dtype == BDN_BF16) { const int per = 256 / (C / 8) * 4;
-        hipLaunchKernelGGL(product_pool_kernel<bf16s>, dim3((ncell + per - 1) / per), dim3(256), 0, st, (const bf16s*)z, bn, (bf16s*)f, (bf16s*)pool, B, H, W, C, ncell, sf, sp, FastDiv((W + 1) / 2), FastDiv((H + 1) / 2)); }
+        hipLaunchKernelGGL((product_pool_kernel<bf16s, FM>), dim3((ncell + per - 1) / per), dim3(256), 0, st, (const bf16s*)z, bn, (bf16s*)f, (bf16s*)pool, B, H, W, C, ncell, sf, sp, FastDiv((W + 1) / 2), FastDiv((H + 1) / 2)); }
     else if (dtype == BDN_F32) { const int per = 256 / (C / 4) * 4;
-        hipLaunchKernelGGL(product_pool_kernel<float>, dim3((ncell + per - 1) / per), dim3(256), 0, st, (const float*)z, bn, (float*)f, (float*)pool, B, H, W, C, ncell, sf, sp, FastDiv((W + 1) / 2), FastDiv((H + 1) / 2)); }
+        hipLaunchKernelGGL((product_pool_kernel<float, FM>), dim3((ncell + per - 1) / per), dim3(256), 0, st, (const float*)z, bn, (float*)f, (float*)pool, B, H, W, C, ncell, sf, sp, FastDiv((W + 1) / 2), FastDiv((H + 1) / 2)); }
     else BDN_FAIL(BDN_E_ARG, "product_pool: bad dtype");
     BDN_CHECK_LAUNCH("product_pool");
     return BDN_OK;
@@ -213,7 +245,16 @@ extern "C" int bdn_product_pool(int dtype, const void* z, const float* bn, void*
                                 int B, int H, int W, int C, void* stream) {
     if (!z || !bn || !f || !pool) BDN_FAIL(BDN_E_ARG, "product_pool: null pointer");
     const SplitOut none = {nullptr, 0, 0, 0};
-    return product_pool_impl(dtype, z, bn, f, pool, none, none, B, H, W, C, stream);
+    return product_pool_impl<BDN_FUSE_PRODUCT>(dtype, z, bn, f, pool, none, none, B, H, W, C, stream);
+}
+
+extern "C" int bdn_fuse_dates_pool(int dtype, int fusion, const void* z, const float* bn, void* f, void* pool,
+                                   int B, int H, int W, int C, void* stream) {
+    if (!z || !bn || !f || !pool) BDN_FAIL(BDN_E_ARG, "fuse_dates_pool: null pointer");
+    BDN_FUSION_CHECK("fuse_dates_pool");
+    const SplitOut none = {nullptr, 0, 0, 0};
+    return fusion == BDN_FUSE_ABSDIFF ? product_pool_impl<BDN_FUSE_ABSDIFF>(dtype, z, bn, f, pool, none, none, B, H, W, C, stream)
+                                      : product_pool_impl<BDN_FUSE_PRODUCT>(dtype, z, bn, f, pool, none, none, B, H, W, C, stream);
 }
 
 // bf16x3 setting: both outputs leave as the [hi | lo] bf16 operands of the convolutions that consume them -- f into channels [0, C) of the
@@ -224,7 +265,17 @@ extern "C" int bdn_product_pool_split(const void* z, const float* bn, void* f_sp
     if (!z || !bn || !f_split || !pool_split) BDN_FAIL(BDN_E_ARG, "product_pool_split: null pointer");
     if (f_half < C || f_ld < f_half + C || f_ld % 8 || f_half % 8) BDN_FAIL(BDN_E_SHAPE, "product_pool_split: bad operand layout ld=%d half=%d", f_ld, f_half);
     const SplitOut sf = {(bf16s*)f_split, f_ld, 0, f_half}, sp = {(bf16s*)pool_split, 2 * C, 0, C};
-    return product_pool_impl(BDN_F32, z, bn, nullptr, nullptr, sf, sp, B, H, W, C, stream);
+    return product_pool_impl<BDN_FUSE_PRODUCT>(BDN_F32, z, bn, nullptr, nullptr, sf, sp, B, H, W, C, stream);
+}
+
+extern "C" int bdn_fuse_dates_pool_split(int fusion, const void* z, const float* bn, void* f_split, int f_ld, int f_half, void* pool_split,
+                                         int B, int H, int W, int C, void* stream) {
+    if (!z || !bn || !f_split || !pool_split) BDN_FAIL(BDN_E_ARG, "fuse_dates_pool_split: null pointer");
+    BDN_FUSION_CHECK("fuse_dates_pool_split");
+    if (f_half < C || f_ld < f_half + C || f_ld % 8 || f_half % 8) BDN_FAIL(BDN_E_SHAPE, "fuse_dates_pool_split: bad operand layout ld=%d half=%d", f_ld, f_half);
+    const SplitOut sf = {(bf16s*)f_split, f_ld, 0, f_half}, sp = {(bf16s*)pool_split, 2 * C, 0, C};
+    return fusion == BDN_FUSE_ABSDIFF ? product_pool_impl<BDN_FUSE_ABSDIFF>(BDN_F32, z, bn, nullptr, nullptr, sf, sp, B, H, W, C, stream)
+                                      : product_pool_impl<BDN_FUSE_PRODUCT>(BDN_F32, z, bn, nullptr, nullptr, sf, sp, B, H, W, C, stream);
 }
 
 // ============================================================ bilinear x2 (align_corners=True) + F.pad
@@ -588,14 +639,14 @@ extern "C" int bdn_upsample2x_bwd_bs(int dtype, const void* dU, int ldU, void* d
     return upsample2x_bwd_impl(dtype, dU, ldU, dsrc, z_prev, bn_prev, bs_partial, B, h, w, H, W, C, stream);
 }
 
-// ============================================================ backward of product fusion + max-pool into encoder outputs
+// ============================================================ backward of the date fusion (FM: fuse_bwd above) + max-pool into encoder outputs
 // one loop iteration = one 2x2 window x EPU channels x both dates.  Two passes over the window: the first finds,
 // per channel and date, WHICH position holds the (first) maximum; the second re-reads z (cache hits), forms the
 // gradients and -- when bs_partial is given -- also the BatchNorm-backward partial sums of the layer (sum g,
 // sum g*z with g = dA * [relu(bn(z)) > 0], on the STORED, rounded dA), so no separate reduction pass reads dA and z.
 // The two-pass variant that never writes dA (sums pass + fused apply pass, 22 % fewer bytes) measured +1.9 % step time in
 // round 2 -- its argmax / product work runs twice -- and lives in tools/experimental/enc_skip_two_pass.hip.inc.
-template <typename T, int EPU>
+template <typename T, int EPU, int FM>
 __global__ __launch_bounds__(256, 1) void enc_skip_bwd_kernel(const T* __restrict__ dF, int ldF, const T* __restrict__ z, const float* __restrict__ bn,
                                     const T* __restrict__ dP, T* __restrict__ dA, float* __restrict__ bs_partial,
                                     int B, int H, int W, int C, int ncell, int IT, FastDiv dWc, FastDiv dHc) {
@@ -667,8 +718,7 @@ __global__ __launch_bounds__(256, 1) void enc_skip_bwd_kernel(const T* __restric
 #pragma unroll
                 for (int i = 0; i < EPU; i++) {
                     const float a0 = act1<T>(f0[i], sc0[i], sh0[i]), a1 = act1<T>(f1[i], sc1[i], sh1[i]);
-                    o0[i] = df[i] * a1;
-                    o1[i] = df[i] * a0;
+                    fuse_bwd<FM>(df[i], a0, a1, o0[i], o1[i]);
                     if (pooled && ((idx0 >> (2 * i)) & 3u) == (unsigned)k) o0[i] += g0[i];
                     if (pooled && ((idx1 >> (2 * i)) & 3u) == (unsigned)k) o1[i] += g1[i];
                 }
@@ -730,8 +780,9 @@ extern "C" int bdn_enc_skip_bwd_rows(int dtype, int B, int H, int W, int C) {
     return enc_skip_bwd_blocks(dtype, B, H, W, C);
 }
 
-extern "C" int bdn_enc_skip_bwd(int dtype, const void* dF, int ldF, const void* z, const float* bn,
-                                const void* dP, void* dA, float* bs_partial, int B, int H, int W, int C, void* stream) {
+template <int FM>
+static int enc_skip_bwd_impl(int dtype, const void* dF, int ldF, const void* z, const float* bn,
+                             const void* dP, void* dA, float* bs_partial, int B, int H, int W, int C, void* stream) {
     if (!dF || !z || !bn || !dA) BDN_FAIL(BDN_E_ARG, "enc_skip_bwd: null pointer");
     if (C % 16 || C > 1024 || 1024 % C || ldF < C || ldF % 16) BDN_FAIL(BDN_E_SHAPE, "enc_skip_bwd: bad shape");
     if (B <= 0 || H <= 0 || W <= 0) BDN_FAIL(BDN_E_SHAPE, "enc_skip_bwd: bad shape");
@@ -739,12 +790,24 @@ extern "C" int bdn_enc_skip_bwd(int dtype, const void* dF, int ldF, const void* 
     const int ncell = B * ((H + 1) / 2) * ((W + 1) / 2);
     const int grid = enc_skip_bwd_blocks(dtype, B, H, W, C);
     if (dtype == BDN_BF16)
-        hipLaunchKernelGGL((enc_skip_bwd_kernel<bf16s, 4>), dim3(grid), dim3(256), bs_partial ? 256 * 4 * 4 * sizeof(float) : 0, st,
+        hipLaunchKernelGGL((enc_skip_bwd_kernel<bf16s, 4, FM>), dim3(grid), dim3(256), bs_partial ? 256 * 4 * 4 * sizeof(float) : 0, st,
                            (const bf16s*)dF, ldF, (const bf16s*)z, bn, (const bf16s*)dP, (bf16s*)dA, bs_partial, B, H, W, C, ncell, enc_skip_bwd_it(dtype, B, H, W, C), FastDiv((W + 1) / 2), FastDiv((H + 1) / 2));
     else if (dtype == BDN_F32)
-        hipLaunchKernelGGL((enc_skip_bwd_kernel<float, 4>), dim3(grid), dim3(256), bs_partial ? 256 * 4 * 4 * sizeof(float) : 0, st,
+        hipLaunchKernelGGL((enc_skip_bwd_kernel<float, 4, FM>), dim3(grid), dim3(256), bs_partial ? 256 * 4 * 4 * sizeof(float) : 0, st,
                            (const float*)dF, ldF, (const float*)z, bn, (const float*)dP, (float*)dA, bs_partial, B, H, W, C, ncell, enc_skip_bwd_it(dtype, B, H, W, C), FastDiv((W + 1) / 2), FastDiv((H + 1) / 2));
     else BDN_FAIL(BDN_E_ARG, "enc_skip_bwd: bad dtype");
     BDN_CHECK_LAUNCH("enc_skip_bwd");
     return BDN_OK;
+}
+
+extern "C" int bdn_enc_skip_bwd(int dtype, const void* dF, int ldF, const void* z, const float* bn,
+                                const void* dP, void* dA, float* bs_partial, int B, int H, int W, int C, void* stream) {
+    return enc_skip_bwd_impl<BDN_FUSE_PRODUCT>(dtype, dF, ldF, z, bn, dP, dA, bs_partial, B, H, W, C, stream);
+}
+
+extern "C" int bdn_enc_skip_bwd_fusion(int dtype, int fusion, const void* dF, int ldF, const void* z, const float* bn,
+                                       const void* dP, void* dA, float* bs_partial, int B, int H, int W, int C, void* stream) {
+    BDN_FUSION_CHECK("enc_skip_bwd_fusion");
+    return fusion == BDN_FUSE_ABSDIFF ? enc_skip_bwd_impl<BDN_FUSE_ABSDIFF>(dtype, dF, ldF, z, bn, dP, dA, bs_partial, B, H, W, C, stream)
+                                      : enc_skip_bwd_impl<BDN_FUSE_PRODUCT>(dtype, dF, ldF, z, bn, dP, dA, bs_partial, B, H, W, C, stream);
 }

@@ -213,11 +213,19 @@ class BiDateEngine:
     f32 MFMA -- the exact parity setting, 1/16 of the bf16 matrix rate) or 'bf16x3' (f32 storage; every GEMM operand split into
     bf16 hi + lo, three bf16 MFMAs per product, fp32 accumulate -- logits within 1e-3 of the reference at matrix-core speed);
     'bf16x3-fast' is bf16x3 with two-term backward GEMMs (same forward, gradients 2-5e-3 relative L2 away).
-    Same kernels: one template parameter, resp. a three times longer reduction for the bf16 kernels."""
+    Same kernels: one template parameter, resp. a three times longer reduction for the bf16 kernels.
 
-    def __init__(self, n_channels, n_classes, precision='bf16'):
+    fusion: how the two dates' features of an encoder level meet in its skip.  'product' = relu(x_d2 * x_d1), the reference's
+    models/bidate_model.py:35-38 and the calls this engine always issued; 'absdiff' = |x_d2 - x_d1| (FC-Siam-diff) through the
+    entry points that take the mode -- the same kernels, the same bytes, no parameters."""
+
+    def __init__(self, n_channels, n_classes, precision='bf16', fusion='product'):
         if precision not in ('bf16', 'fp32', 'bf16x3', 'bf16x3-fast'):
             raise ValueError(f"precision must be 'bf16', 'bf16x3', 'bf16x3-fast' or 'fp32', got {precision!r}")
+        if fusion not in _lib.FUSIONS:
+            raise ValueError(f"fusion must be 'product' or 'absdiff', got {fusion!r}")
+        self.fusion = fusion
+        self.fm = _lib.FUSIONS[fusion]
         self.n_channels, self.n_classes = n_channels, n_classes
         self.precision = precision
         self.dt = BDN_BF16 if precision == 'bf16' else BDN_F32                  # storage type: what the HBM-bound kernels see
@@ -542,12 +550,14 @@ class BiDateEngine:
             if k < 5 and pre:
                 Ld, Ln = by[f'd{5 - k}a'], by[f'e{k + 1}a']
                 hn, wn = ws.dims[k]
-                call('bdn_product_pool_split', ptr(zb), ptr(bnb), ptr(ws.split_buf(('a', Ld.name), B * hk * wk * 2 * Ld.cin)), 2 * Ld.cin, Ld.cin,
-                     ptr(ws.split_buf(('a', Ln.name), 2 * B * hn * wn * 2 * Ln.cin)), B, hk, wk, ENC_CH[k - 1], st)
+                self._fuse('bdn_product_pool_split', 'bdn_fuse_dates_pool_split', (),
+                           ptr(zb), ptr(bnb), ptr(ws.split_buf(('a', Ld.name), B * hk * wk * 2 * Ld.cin)), 2 * Ld.cin, Ld.cin,
+                           ptr(ws.split_buf(('a', Ln.name), 2 * B * hn * wn * 2 * Ln.cin)), B, hk, wk, ENC_CH[k - 1], st)
             elif k < 5:                                     # skip f_k and the pooled input of level k+1 in one pass over z
-                call('bdn_product_pool', self.dt, ptr(zb), ptr(bnb), ptr(ws.f[k]), ptr(ws.pool[k + 1]), B, hk, wk, ENC_CH[k - 1], st)
+                self._fuse('bdn_product_pool', 'bdn_fuse_dates_pool', (self.dt,),
+                           ptr(zb), ptr(bnb), ptr(ws.f[k]), ptr(ws.pool[k + 1]), B, hk, wk, ENC_CH[k - 1], st)
             else:
-                call('bdn_fuse_product', self.dt, ptr(zb), ptr(bnb), ptr(ws.f[k]), B, hk, wk, ENC_CH[k - 1], st)
+                self._fuse('bdn_fuse_product', 'bdn_fuse_dates', (self.dt,), ptr(zb), ptr(bnb), ptr(ws.f[k]), B, hk, wk, ENC_CH[k - 1], st)
         # ---- decoder on the fused skips
         prev, prev_bn, prev_mode, cprev = ws.f[5], None, IN_PLAIN, ENC_CH[4]
         for j in range(1, 5):
@@ -570,6 +580,13 @@ class BiDateEngine:
         call('bdn_outc_fwd', self.dt, ptr(prev), ptr(prev_bn), ptr(P['outc.conv.weight']), ptr(P['outc.conv.bias']),
              ptr(logits), B, H, W, cprev, self.n_classes, st)
         return logits
+
+    def _fuse(self, product_entry, fusion_entry, head, *args):
+        """One date-fusion call site: the product entry point as always, or its generalisation with the mode behind `head` (dtype or nothing)."""
+        if self.fm == _lib.FUSE_PRODUCT:
+            call(product_entry, *head, *args)
+        else:
+            call(fusion_entry, *head, self.fm, *args)
 
     # ------------------------------------------------------------------ eval-shaped forward (round 6)
     def _use_eval_schedule(self):
@@ -621,8 +638,12 @@ class BiDateEngine:
         def stage(L, in0, c0, in1, c1, out, n, hk, wk, mul=None, pool=None):
             wf, _ = self._weights(L, P, False)
             sc, sh = ev[L.name]
-            call('bdn_conv3x3_eval', self.dt, ptr(in0), c0, ptr(in1), c1, ptr(wf), ptr(sc), ptr(sh), ptr(out), ptr(mul), ptr(pool),
-                 n, hk, wk, L.cout, st)
+            if mul is None:
+                call('bdn_conv3x3_eval', self.dt, ptr(in0), c0, ptr(in1), c1, ptr(wf), ptr(sc), ptr(sh), ptr(out), None, ptr(pool),
+                     n, hk, wk, L.cout, st)
+            else:
+                self._fuse('bdn_conv3x3_eval', 'bdn_conv3x3_eval_fusion', (self.dt,),
+                           ptr(in0), c0, ptr(in1), c1, ptr(wf), ptr(sc), ptr(sh), ptr(out), ptr(mul), ptr(pool), n, hk, wk, L.cout, st)
 
         # ---- shared encoder: the first conv of a level on both dates at once, the second per date
         for k in range(1, 6):
@@ -635,8 +656,9 @@ class BiDateEngine:
             if k in self.eval_pair:
                 wf, _ = self._weights(Lb, P, False)
                 sc, sh = ev[Lb.name]
-                call('bdn_conv3x3_eval_pair', self.dt, ptr(za), Lb.cin, ptr(wf), ptr(sc), ptr(sh), ptr(ws.f[k]), ptr(pn), B, hk, wk, Lb.cout, st)
-            else:                                    # per date: date 1 stores its activation, date 2 multiplies its own with it in the copy-out
+                self._fuse('bdn_conv3x3_eval_pair', 'bdn_conv3x3_eval_pair_fusion', (self.dt,),
+                           ptr(za), Lb.cin, ptr(wf), ptr(sc), ptr(sh), ptr(ws.f[k]), ptr(pn), B, hk, wk, Lb.cout, st)
+            else:                                    # per date: date 1 stores its activation, date 2 fuses its own with it in the copy-out
                 stage(Lb, za[:B], Lb.cin, None, 0, zb[:B], B, hk, wk, pool=pn[:B] if k < 5 else None)
                 stage(Lb, za[B:], Lb.cin, None, 0, ws.f[k], B, hk, wk, mul=zb[:B], pool=pn[B:] if k < 5 else None)
         # ---- decoder on the fused skips
@@ -1021,8 +1043,8 @@ class BiDateEngine:
                     dF = dcat[k]
                 dAb = e(2 * B, hk, wk, ck)
                 keep.append(dAb)
-                call('bdn_enc_skip_bwd', self.dt, ptr(dF), dF.shape[3], ptr(ws.z[Lb.name]), ptr(ws.bn[Lb.name]),
-                     ptr(dP), ptr(dAb), ptr(ws.stats), B, hk, wk, ck, st)
+                self._fuse('bdn_enc_skip_bwd', 'bdn_enc_skip_bwd_fusion', (self.dt,), ptr(dF), dF.shape[3], ptr(ws.z[Lb.name]), ptr(ws.bn[Lb.name]),
+                           ptr(dP), ptr(dAb), ptr(ws.stats), B, hk, wk, ck, st)
                 dAa, rows = layer(Lb, 2 * B, ptr(dAb), ck, _lib.load().bdn_enc_skip_bwd_rows(self.dt, B, hk, wk, ck),
                                   (ws.z[La.name], Lb.cin, None, 0, IN_BNRELU, ws.bn[La.name]), prev=La)
                 if end == Lb.name:

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from .unet_parts import down, outconv, up, inconv
+from .._lib import FUSIONS
 from ..engine import BiDateEngine
 
 
@@ -104,8 +105,10 @@ class _BiDateFunction(torch.autograd.Function):
 
 
 class BiDateNet(nn.Module):
-    def __init__(self, n_channels, n_classes, precision=None):
+    def __init__(self, n_channels, n_classes, precision=None, fusion='product'):
         super(BiDateNet, self).__init__()
+        if fusion not in FUSIONS:
+            raise ValueError(f"fusion must be 'product' or 'absdiff', got {fusion!r}")
         self.inc = inconv(n_channels, 64)
         self.down1 = down(64, 128)
         self.down2 = down(128, 256)
@@ -122,11 +125,15 @@ class BiDateNet(nn.Module):
         # 'bf16' = throughput setting; 'bf16x3' = float32 tensors with split bf16 GEMM operands (logits within 1e-3 of the reference at
         # matrix-core speed); 'fp32' = exact f32 MFMA
         self.precision = precision or os.environ.get('BIDATE_PRECISION', 'bf16')
+        # how the two dates' encoder features meet in the skips: 'product' = relu(x_d2 * x_d1), the reference's models/bidate_model.py:35-38;
+        # 'absdiff' = |x_d2 - x_d1| (FC-Siam-diff).  No parameters: the state dict is the same.  Read when the engine is built; assigning
+        # another value rebuilds the engine at the next call, as `precision` does.
+        self.fusion = fusion
         self._engine = None
 
     def engine(self):
-        if self._engine is None or self._engine.precision != self.precision:
-            self._engine = BiDateEngine(self.n_channels, self.n_classes, self.precision)
+        if self._engine is None or self._engine.precision != self.precision or self._engine.fusion != self.fusion:
+            self._engine = BiDateEngine(self.n_channels, self.n_classes, self.precision, self.fusion)     # ValueError for an unknown fusion
         return self._engine
 
     def forward(self, x_d1, x_d2):
@@ -166,7 +173,7 @@ class BiDateNet(nn.Module):
         nn.DataParallel(BiDateNet(13, 2)), utils/helpers.py:333-335).  Such a pickle resolves its class paths to this class through the
         root `models.*` shims, but its __dict__ is the reference's: sub-modules and parameters only.  Everything this class adds is
         derived state and is rebuilt here: the channel counts from the first / last convolution, the numerics setting from
-        BIDATE_PRECISION (default 'bf16'), no engine yet."""
+        BIDATE_PRECISION (default 'bf16'), the date fusion 'product' (the reference's only one), no engine yet."""
         super().__setstate__(state)
         d = self.__dict__
         if 'n_channels' not in d:
@@ -175,4 +182,6 @@ class BiDateNet(nn.Module):
             d['n_classes'] = int(self.outc.conv.weight.shape[0])
         if d.get('precision') is None:
             d['precision'] = os.environ.get('BIDATE_PRECISION', 'bf16')
+        if d.get('fusion') is None:                # the reference's pickles and pickles of this class from before it had the attribute
+            d['fusion'] = 'product'
         d['_engine'] = None

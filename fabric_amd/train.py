@@ -378,10 +378,24 @@ def _lr_scale(text):
 _CKPT = re.compile(r'checkpoint_epoch_(\d+)\.state_dict\.pt$')
 
 
+def resolve_fusion(flag, checkpoint=None, resume=False):
+    """The run's date fusion from --fusion (None when the flag was not given) and the fusion the --resume / --init_from checkpoint's
+    metadata names (None: no checkpoint, or one without the entry = 'product' for a checkpoint, since older runs knew no other).
+    Returns (fusion, note): --resume continues the run it names, so another explicit --fusion is an error (ValueError); --init_from only
+    takes weights, so an explicit --fusion wins and `note` is the one line that says the encoder was trained under the other fusion."""
+    if flag is None:
+        return checkpoint or 'product', None
+    if checkpoint is None or checkpoint == flag:
+        return flag, None
+    if resume:
+        raise ValueError(f'--resume continues a run trained with --fusion {checkpoint}; --fusion {flag} would change the network')
+    return flag, f'--init_from: the checkpoint was trained with fusion {checkpoint!r}; fine-tuning it under fusion {flag!r}'
+
+
 def resume_from(path, device=None, precision=None):
     """--resume DIR/checkpoint_epoch_N.state_dict.pt: (model, optimizer state or None, first epoch N + 1).  The weights and BatchNorm
     buffers come through load_checkpoint; the optimizer state is the sibling optimizer_epoch_N.pt save_if_better wrote, in
-    torch.optim's state_dict() format (absent for a stateless optimizer)."""
+    torch.optim's state_dict() format (absent for a stateless optimizer).  The date fusion comes back from metadata_epoch_N.json."""
     from .utils.helpers import load_checkpoint
     m = _CKPT.search(os.path.basename(path))
     if not m:
@@ -512,6 +526,10 @@ def main(argv=None):
             ap.add_argument(f'--{k}', type=type(v), default=v)
     ap.add_argument('--synthetic', action='store_true', help='use fabric_amd.utils.dataloaders.synthetic_onera()')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'bf16x3', 'bf16x3-fast', 'fp32'])
+    ap.add_argument('--fusion', default=None, choices=['product', 'absdiff'],
+                    help="how the two dates' encoder features meet in the skips: product = relu(x_d2 * x_d1) (the default), absdiff = "
+                         '|x_d2 - x_d1| (FC-Siam-diff); no parameters, same checkpoints.  Recorded in the checkpoint metadata: --resume '
+                         'restores it, --init_from takes it unless the flag is given')
     ap.add_argument('--seed', type=int, default=0, help='seeds the shard permutation, the augmentation draws and the initial weights identically on every rank')
     ap.add_argument('--focal_gamma', type=float, default=None, help='required by --loss_function focal (utils/helpers.py:291)')
     ap.add_argument('--focal_alpha', type=float, default=None, help='focal class weights [a, 1 - a] (utils/metrics.py:13-14); --fused_step true only')
@@ -733,6 +751,12 @@ def main(argv=None):
         raise SystemExit(str(e))
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
+    from .utils.helpers import checkpoint_fusion
+    ckpt = opt.resume or opt.init_from
+    try:
+        fusion, fusion_note = resolve_fusion(opt.fusion, (checkpoint_fusion(ckpt) or 'product') if ckpt else None, resume=bool(opt.resume))
+    except ValueError as e:
+        raise SystemExit(str(e))
     try:
         patch_augment = augment_from_opt(opt)
         patch_warp = warp_from_opt(opt) if patch_augment is not None else None
@@ -784,13 +808,15 @@ def main(argv=None):
         train_loader, val_loader = make_loaders(data, val_cities, opt.patch_size, stride, opt.batch_size, opt.augmentation,
                                                 num_workers=opt.num_workers, rank=rank, world_size=world, seed=opt.seed)
     random.seed(opt.seed * 7919 + rank)                    # different augmentation draws per rank from here on
-    model = BiDateNet(len(opt.band_ids) if opt.band_ids else 13, 2, precision=opt.precision).to(dev)
+    model = BiDateNet(len(opt.band_ids) if opt.band_ids else 13, 2, precision=opt.precision, fusion=fusion).to(dev)
     opt_sd, first_epoch = None, 0
     if opt.resume:
-        model, opt_sd, first_epoch = resume_from(opt.resume, dev, opt.precision)
+        model, opt_sd, first_epoch = resume_from(opt.resume, dev, opt.precision)      # the fusion comes back from the metadata
     elif opt.init_from:
         from .utils.helpers import load_checkpoint
-        model = load_checkpoint(opt.init_from, device=dev, precision=opt.precision)
+        model = load_checkpoint(opt.init_from, device=dev, precision=opt.precision, fusion=fusion)
+        if fusion_note and rank == 0:
+            print(fusion_note, flush=True)
     fused = opt.fused_step or opt.loss_function == 'tversky'
     from .input_pipeline import DeviceFeeder
     from .utils.helpers import get_criterion
@@ -834,7 +860,7 @@ def main(argv=None):
     if opt.val_curve_bins:
         from .utils.metrics import ScoreCurve
         val_curve = ScoreCurve(opt.val_curve_bins, 1, opt.ignore_label)
-    run_meta = dict(meta, **{k: getattr(opt, k) for k in DEFAULTS}, precision=opt.precision, world_size=world)
+    run_meta = dict(meta, **{k: getattr(opt, k) for k in DEFAULTS}, precision=opt.precision, fusion=model.fusion, world_size=world)
     schedule = None
     if scheduled:                                          # host floats only; its position comes from (epoch, batch), so --resume continues it
         from .schedule import LRSchedule

@@ -1,5 +1,7 @@
 """Glue with the reference's names and semantics (utils/helpers.py:24-89, 288-337) for the parts the
 train step needs: running-mean metric dicts, criterion factory, model factory."""
+import os
+
 import numpy as np
 import torch
 
@@ -79,8 +81,26 @@ def get_loaders(opt):
 
 def load_model(opt, device, precision=None):
     """reference utils/helpers.py:317-337 builds nn.DataParallel(BiDateNet(13, 2)); here one process drives one
-    GPU and gradients are exchanged by fabric_amd.parallel (RCCL), so the bare module is returned."""
-    return BiDateNet(13, 2, precision=precision).to(device)
+    GPU and gradients are exchanged by fabric_amd.parallel (RCCL), so the bare module is returned.  `opt.fusion`
+    ('product' / 'absdiff'), when present, selects the date fusion."""
+    return BiDateNet(13, 2, precision=precision, fusion=getattr(opt, 'fusion', None) or 'product').to(device)
+
+
+def checkpoint_fusion(path):
+    """The date fusion a checkpoint file of fabric_amd.train was trained with: the `fusion` entry of the metadata_epoch_N.json
+    beside checkpoint_epoch_N.pt / checkpoint_epoch_N.state_dict.pt / ema_epoch_N.pt, or None (not such a file, no metadata,
+    or metadata from before the entry existed)."""
+    import json
+    import re
+    if not isinstance(path, (str, bytes)) and not hasattr(path, '__fspath__'):
+        return None
+    path = os.fsdecode(path)
+    m = re.match(r'(?:checkpoint|ema)_epoch_(\d+)(?:\.state_dict)?\.pt$', os.path.basename(path))
+    meta = os.path.join(os.path.dirname(path), f'metadata_epoch_{m.group(1)}.json') if m else None
+    if meta is None or not os.path.exists(meta):
+        return None
+    with open(meta) as fh:
+        return json.load(fh).get('fusion')
 
 
 def strip_module_prefix(state_dict):
@@ -89,7 +109,7 @@ def strip_module_prefix(state_dict):
     return {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in state_dict.items()}
 
 
-def load_checkpoint(src, device=None, precision=None, allow_pickle=True):
+def load_checkpoint(src, device=None, precision=None, allow_pickle=True, fusion=None):
     """A usable BiDateNet from anything the reference (or fabric_amd.train) leaves behind.
 
     `src` is a path / file object for torch.load, or an object already loaded:
@@ -102,12 +122,16 @@ def load_checkpoint(src, device=None, precision=None, allow_pickle=True):
         -- the result is a BiDateNet on the averaged weights.
     The result is always a fresh fabric_amd BiDateNet carrying the checkpoint's parameters AND BatchNorm buffers; the channel
     counts come from the tensors.  Mismatched / missing / unexpected keys raise (load_state_dict(strict=True)).
+    The date fusion has no parameters, so no tensor records it: `fusion` when given, else the `fusion` attribute of a pickled BiDateNet,
+    else what checkpoint_fusion() finds in the metadata beside a file fabric_amd.train wrote, else 'product' (the reference's).
 
     Trust: a file is first read with torch.load(weights_only=True) -- tensors and plain containers only, no code runs; that covers
     every state-dict form (incl. the `*.state_dict.pt` fabric_amd.train writes for interchange).  Only when that loader refuses the
     file (a whole-module pickle, train.py:222) is it unpickled in full, which EXECUTES whatever the pickle holds: pass
     allow_pickle=False to refuse such files when the checkpoint does not come from a trusted source."""
     obj = src
+    if fusion is None:
+        fusion = checkpoint_fusion(src)
     if isinstance(src, (str, bytes)) or hasattr(src, 'read') or hasattr(src, '__fspath__'):
         import pickle
         pos = src.tell() if hasattr(src, 'tell') else None
@@ -126,13 +150,15 @@ def load_checkpoint(src, device=None, precision=None, allow_pickle=True):
         obj = obj.module
     if isinstance(obj, torch.nn.Module):
         sd = obj.state_dict()
+        if fusion is None:
+            fusion = getattr(obj, 'fusion', None)
     elif isinstance(obj, dict):
         sd = obj
         for nest in ('state_dict', 'model'):
             if nest in sd and isinstance(sd[nest], dict):
                 sd = sd[nest]
             elif nest in sd and isinstance(sd[nest], torch.nn.Module):
-                return load_checkpoint(sd[nest], device, precision, allow_pickle)
+                return load_checkpoint(sd[nest], device, precision, allow_pickle, fusion)
     else:
         raise TypeError(f'fabric_amd: cannot load a checkpoint from {type(obj).__name__}')
     from ..optim import AVG_COUNT, is_averaged_state
@@ -144,6 +170,6 @@ def load_checkpoint(src, device=None, precision=None, allow_pickle=True):
         n_classes = int(sd['outc.conv.weight'].shape[0])
     except KeyError as e:
         raise RuntimeError(f'fabric_amd: not a BiDateNet checkpoint (missing {e.args[0]!r})') from None
-    model = BiDateNet(n_channels, n_classes, precision=precision)
+    model = BiDateNet(n_channels, n_classes, precision=precision, fusion=fusion or 'product')
     model.load_state_dict(sd, strict=True)
     return model.to(device) if device is not None else model

@@ -38,6 +38,12 @@ enum { BDN_F32 = 0, BDN_BF16 = 1, BDN_BF16X3 = 2,     /* BDN_BF16X3: float32 ten
                            * Accepted by those entry points only. */
 enum { BDN_OK = 0, BDN_E_ARG = -1, BDN_E_SHAPE = -2, BDN_E_HIP = -3 };
 enum { BDN_IN_PLAIN = 0, BDN_IN_BNRELU = 1 };
+/* How the two dates' features of an encoder level meet in its skip (the `fusion` argument of the entry points that carry it):
+ * BDN_FUSE_PRODUCT  relu(x_d2 * x_d1), the reference's models/bidate_model.py:35-38;
+ * BDN_FUSE_ABSDIFF  |x_d2 - x_d1| at the same call sites (FC-Siam-diff, Daudt et al., ICIP 2018): one float32 subtraction of the two
+ *                   rounded activations, the absolute value, one rounding to the storage type.  Backward: dA_d1 = dF * s,
+ *                   dA_d2 = -(dF * s) with s = sign(a_d1 - a_d2) in {-1, 0, +1}; exactly 0 at a_d1 == a_d2 (torch.abs's rule). */
+enum { BDN_FUSE_PRODUCT = 0, BDN_FUSE_ABSDIFF = 1 };
 
 const char* bdn_last_error(void);
 int bdn_version(void);
@@ -291,6 +297,13 @@ int bdn_conv3x3_eval(int dtype, const void* in0, int C0, const void* in1, int C1
                      int N, int H, int W, int Cout, void* stream);
 int bdn_conv3x3_eval_pair(int dtype, const void* in, int C0, const void* w, const float* ep_scale, const float* ep_shift,
                           void* f_out, void* pool, int B, int H, int W, int Cout, void* stream);
+/* The two above with the date fusion as an argument (models/bidate_model.py:35-38 generalised: BDN_FUSE_PRODUCT = the calls above, bit for
+ * bit; BDN_FUSE_ABSDIFF: `out` / f_out receive |a_d2 - a_d1|).  Same kernels, same instantiations: the mode is a runtime field. */
+int bdn_conv3x3_eval_fusion(int dtype, int fusion, const void* in0, int C0, const void* in1, int C1, const void* w,
+                            const float* ep_scale, const float* ep_shift, void* out, const void* mul, void* pool,
+                            int N, int H, int W, int Cout, void* stream);
+int bdn_conv3x3_eval_pair_fusion(int dtype, int fusion, const void* in, int C0, const void* w, const float* ep_scale, const float* ep_shift,
+                                 void* f_out, void* pool, int B, int H, int W, int Cout, void* stream);
 int bdn_conv3x3_eval_cls(int dtype, const void* in0, int C0, const void* w, const float* ep_scale, const float* ep_shift, void* act_out,
                          const float* cls_w, const float* cls_b, int ncls, float* logits, uint8_t* mask, const int32_t* origins,
                          int Hs, int Ws, int N, int H, int W, int Cout, void* stream);
@@ -370,6 +383,16 @@ int bdn_product_pool(int dtype, const void* z, const float* bn, void* f, void* p
 int bdn_product_pool_split(const void* z, const float* bn, void* f_split, int f_ld, int f_half, void* pool_split,
                            int B, int H, int W, int C, void* stream);
 
+/* The three above with the date fusion as an argument (models/bidate_model.py:35-38 generalised; fusion = BDN_FUSE_PRODUCT / BDN_FUSE_ABSDIFF):
+ * f = relu(a_d2 * a_d1) or |a_d2 - a_d1| of the rounded activations a = relu(bn(z)); the pooled maps do not depend on it.  Mode 0 launches the
+ * kernels of bdn_fuse_product / bdn_product_pool / bdn_product_pool_split themselves; the split form stores the [hi | lo] split of the float32 f. */
+int bdn_fuse_dates(int dtype, int fusion, const void* z, const float* bn, void* f,
+                   int B, int H, int W, int C, void* stream);
+int bdn_fuse_dates_pool(int dtype, int fusion, const void* z, const float* bn, void* f, void* pool,
+                        int B, int H, int W, int C, void* stream);
+int bdn_fuse_dates_pool_split(int fusion, const void* z, const float* bn, void* f_split, int f_ld, int f_half, void* pool_split,
+                              int B, int H, int W, int C, void* stream);
+
 /* ---- nn.Upsample(scale_factor=2, bilinear, align_corners=True) + F.pad: models/unet_parts.py:56-58,68-72 ----
  * src: [B,h,w,C] (plain, or raw z with bn when in_mode = BDN_IN_BNRELU); out: [B,H,W,C] with the
  * 2h x 2w map placed at offset ((H-2h)/2, (W-2w)/2) and zeros elsewhere. */
@@ -401,6 +424,11 @@ int bdn_enc_skip_bwd(int dtype, const void* dF, int ldF, const void* z, const fl
  * sums of the layer (per block: sum g, sum g*z; date 1 rows then date 2 rows) -> bdn_bn_bwd_apply(raw_moment = 1); dA then holds
  * the MASKED gradient g = dA * [relu(bn(z)) > 0] (see bdn_conv3x3_dgrad_bs). */
 int bdn_enc_skip_bwd_rows(int dtype, int B, int H, int W, int C);
+/* bdn_enc_skip_bwd with the date fusion as an argument (autograd of models/bidate_model.py:35-38 generalised).  BDN_FUSE_ABSDIFF:
+ * dA_d1 = dF * s + unpool(dP_d1), dA_d2 = -(dF * s) + unpool(dP_d2), s = sign(a_d1 - a_d2) from the rounded activations (0 at a tie, both-dead
+ * ReLUs included); pooling gradient, masking and bs_partial (same rows, formed on the stored, rounded values) as above. */
+int bdn_enc_skip_bwd_fusion(int dtype, int fusion, const void* dF, int ldF, const void* z, const float* bn,
+                            const void* dP, void* dA, float* bs_partial, int B, int H, int W, int C, void* stream);
 
 /* ---- outconv: nn.Conv2d(64, n_classes, 1), models/unet_parts.py:86 ----
  * z: [B,H,W,C] raw output of up4's second conv, bn: [1][4][C]; w: [ncls][C] f32, b: [ncls];
