@@ -515,6 +515,52 @@ def check_boundary_flags(boundary_weight, boundary_classes, boundary_max_dist, f
     return scene_boundary_tol
 
 
+def check_coregister_flags(coregister, cells, bands, min_ncc, band_ids=None, n_bands=13, synthetic_misreg=(0, 0), synthetic=False):
+    """--coregister / --coregister_cells / --coregister_bands / --coregister_min_ncc and --synthetic_misreg together, without a device:
+    returns None (off) or the keyword arguments of coregister_cities; raises ValueError with the reason otherwise.  A band is named by its
+    id in the run's band_ids or by its index."""
+    from .utils import registration as RG
+    if len(synthetic_misreg) != 2 or any(not isinstance(v, int) or isinstance(v, bool) for v in synthetic_misreg):
+        raise ValueError(f'--synthetic_misreg {synthetic_misreg}: two integers DY DX')
+    if tuple(synthetic_misreg) != (0, 0) and not synthetic:
+        raise ValueError('--synthetic_misreg shifts date 2 of the synthetic cities: add --synthetic')
+    if not isinstance(coregister, int) or isinstance(coregister, bool) or not 0 <= coregister <= RG.MAX_SHIFT:
+        raise ValueError(f'--coregister {coregister}: 0 (off) or the search radius in pixels, 1..{RG.MAX_SHIFT}')
+    if coregister == 0:
+        if tuple(cells) != (1, 1) or bands is not None or min_ncc != 0.0:
+            raise ValueError('--coregister_cells / --coregister_bands / --coregister_min_ncc shape an alignment that is not on: add --coregister R')
+        return None
+    if len(cells) != 2 or any(not 1 <= v <= RG.MAX_CELLS for v in cells):
+        raise ValueError(f'--coregister_cells {list(cells)}: NY NX, 1..{RG.MAX_CELLS} each')
+    if not -1.0 <= min_ncc <= 1.0:
+        raise ValueError(f'--coregister_min_ncc {min_ncc}: a correlation in [-1, 1]')
+    n = len(band_ids) if band_ids else n_bands
+    idx = None
+    if bands is not None:
+        idx = []
+        for b in bands:
+            if band_ids and str(b) in list(band_ids):
+                idx.append(list(band_ids).index(str(b)))
+            elif str(b).lstrip('-').isdigit() and 0 <= int(b) < n:
+                idx.append(int(b))
+            else:
+                raise ValueError(f'--coregister_bands {b}: neither one of the band ids {list(band_ids or [])} nor an index in [0, {n})')
+    if not 1 <= (len(idx) if idx is not None else n) <= RG.MAX_BANDS:
+        raise ValueError(f'--coregister_bands: 1..{RG.MAX_BANDS} bands (the run has {n}: name a subset)')
+    return dict(max_shift=coregister, cells=(int(cells[0]), int(cells[1])), bands=idx, min_ncc=float(min_ncc))
+
+
+def coregister_loaded(full_load, coreg, ignore_label, device, log=True):
+    """--coregister: align date 2 of every loaded city to its date 1, in place, once, before any loader or scene pass sees the stacks; one
+    `coreg` log line per city.  Returns the per-city reports."""
+    from .utils.registration import coregister_cities, report_line
+    reports = coregister_cities(full_load, ignore_label=ignore_label, device=device, **coreg)
+    if log:
+        for city, rep in reports.items():
+            print('coreg ' + json.dumps(report_line(city, rep)), flush=True)
+    return reports
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Training change detection network (HIP path)')
     for k, v in DEFAULTS.items():
@@ -659,6 +705,17 @@ def main(argv=None):
                          'and min_area (object_scores on the unfiltered mask with min_area = --scene_min_area; --ignore_label pixels are cut out '
                          'before the areas are measured)')
     ap.add_argument('--scene_connectivity', type=int, default=8, choices=[4, 8], help='connectivity of --scene_min_area / --scene_objects')
+    ap.add_argument('--coregister', type=int, default=0, metavar='R',
+                    help='align date 2 of every city to its date 1 once after loading, on the device (utils/registration.py): the shift is '
+                         'searched over +-R pixels (1..16) by normalised cross-correlation and date 2 is resampled bilinearly; 0: off.  '
+                         'With --ignore_label V, label pixels whose date-2 taps fall outside the scene become V')
+    ap.add_argument('--coregister_cells', type=int, nargs=2, default=[1, 1], metavar=('NY', 'NX'),
+                    help='--coregister: estimate one shift per cell of an NY x NX grid (1..64 each) and interpolate between the cell centres')
+    ap.add_argument('--coregister_bands', nargs='+', default=None, metavar='BAND', help='--coregister: the bands correlated, by id or index (default: all)')
+    ap.add_argument('--coregister_min_ncc', type=float, default=0.0, metavar='F',
+                    help='--coregister: a cell whose peak correlation is below F takes the whole-scene shift')
+    ap.add_argument('--synthetic_misreg', type=int, nargs=2, default=[0, 0], metavar=('DY', 'DX'),
+                    help='--synthetic: shift date 2 of every city by DY DX pixels (integers, replicated edge)')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
                                                      "band_stds, ...): its entries become defaults like utils/parser.py:7-10")
     pre, _ = ap.parse_known_args(argv)
@@ -749,6 +806,11 @@ def main(argv=None):
         scene_min_area = check_object_flags(opt.scene_min_area, opt.scene_objects, opt.scene_connectivity, opt.scene_stride)
     except ValueError as e:
         raise SystemExit(str(e))
+    try:
+        coreg = check_coregister_flags(opt.coregister, opt.coregister_cells, opt.coregister_bands, opt.coregister_min_ncc, opt.band_ids, 13,
+                                       opt.synthetic_misreg, opt.synthetic)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
     from .utils.helpers import checkpoint_fusion
@@ -779,7 +841,10 @@ def main(argv=None):
     scenes = None
     if opt.synthetic:
         data = synthetic_onera(n_cities=6, bands=13, size=(360, 360), **(
-            {} if opt.ignore_label is None else dict(ignore_frac=opt.synthetic_ignore_frac, ignore_value=opt.ignore_label)))
+            {} if opt.ignore_label is None else dict(ignore_frac=opt.synthetic_ignore_frac, ignore_value=opt.ignore_label)),
+            **({} if tuple(opt.synthetic_misreg) == (0, 0) else dict(misreg=tuple(opt.synthetic_misreg))))
+        if coreg is not None:
+            coregister_loaded(data, coreg, opt.ignore_label, dev, log=rank == 0)
         val_cities = ['city4', 'city5']
     else:
         if not opt.band_ids:
@@ -787,6 +852,8 @@ def main(argv=None):
                              'metadata.json); or use --synthetic')
         from .utils import ingest
         scenes = ingest.full_onera_loader(opt.dataset_dir, opt, device=dev)      # city stacks stay in HBM for the scene pass
+        if coreg is not None:                              # before the loaders' views and copies of the stacks are made
+            coregister_loaded(scenes, coreg, opt.ignore_label, dev, log=rank == 0)
         if opt.device_patches:                             # the patch sampler reads the same HBM stacks: no round trip through the host
             data = {c: {'images': d['images'], 'labels': d['labels']} for c, d in scenes.items()}
         else:
@@ -861,6 +928,8 @@ def main(argv=None):
         from .utils.metrics import ScoreCurve
         val_curve = ScoreCurve(opt.val_curve_bins, 1, opt.ignore_label)
     run_meta = dict(meta, **{k: getattr(opt, k) for k in DEFAULTS}, precision=opt.precision, fusion=model.fusion, world_size=world)
+    if coreg is not None:                                  # a checkpoint says how its training pairs were aligned
+        run_meta['coregister'] = dict(coreg, cells=list(coreg['cells']))
     schedule = None
     if scheduled:                                          # host floats only; its position comes from (epoch, batch), so --resume continues it
         from .schedule import LRSchedule

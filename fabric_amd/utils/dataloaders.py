@@ -86,13 +86,18 @@ def metadata_from_shapes(shapes, val_cities, patch_size, stride):
     return train, val
 
 
-def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fraction=0.05, ignore_frac=0.0, ignore_value=255):
+def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fraction=0.05, ignore_frac=0.0, ignore_value=255, misreg=(0, 0)):
     """A `full_load` dict of the reference's schema ({city: {'images': f32[2,C,H,W], 'labels': u8[H,W]}},
     utils/dataloaders.py:138-145) filled with z-scored noise; date 2 = date 1 + small noise + blobs of
     change where the label is 1.  ignore_frac > 0: rectangles of the label raster (nodata borders, unlabelled stretches) are painted
     with `ignore_value` (255) until about that fraction of it is covered, for runs with an ignore label (train.py --ignore_label).
     The rectangles come from a generator of their own and are painted last: the images, and with ignore_frac = 0 the labels, are
-    the arrays this function always returned."""
+    the arrays this function always returned.  misreg = (dy, dx), integers: date 2 is shifted against date 1 and the labels, with a
+    replicated edge, date2'(y, x) = date2(y + dy, x + dx) -- a misregistered pair (fabric_amd.utils.registration estimates (-dy, -dx));
+    (0, 0) draws nothing and moves nothing."""
+    my, mx = (int(v) for v in misreg)
+    if (my, mx) != tuple(misreg):
+        raise ValueError(f'misreg must be a pair of integers (dy, dx), got {misreg!r}')
     r = np.random.default_rng(seed)
     ri = np.random.default_rng([seed, 255]) if ignore_frac > 0 else None
     out = {}
@@ -110,6 +115,8 @@ def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fracti
                 rh, rw = int(ri.integers(h // 16 + 1, h // 4 + 2)), int(ri.integers(w // 16 + 1, w // 4 + 2))
                 y0, x0 = int(ri.integers(0, h - rh + 1)), int(ri.integers(0, w - rw + 1))
                 lbl[y0:y0 + rh, x0:x0 + rw] = ignore_value
+        if (my, mx) != (0, 0):
+            d2 = d2[:, np.clip(np.arange(h) + my, 0, h - 1)][:, :, np.clip(np.arange(w) + mx, 0, w - 1)]
         out[f'city{c}'] = {'images': np.stack([d1, d2]).astype(np.float32), 'labels': lbl}
     return out
 

@@ -1010,6 +1010,56 @@ int bdn_boundary_mask(const uint8_t* src, int fg_value, const uint8_t* valid_src
                       void* stream);
 int bdn_boundary_score(const uint8_t* bnd, const int32_t* d2, long long tol2, long long* out, int H, int W, void* stream);
 
+/* ---- co-registration of the two dates of a scene: the shift between them is estimated by normalised cross-correlation over integer
+ * shifts, per cell of a grid and for the whole scene, refined to a fraction of a pixel, and date 2 is resampled through the shift field.
+ * No reference: the reference assumes co-registered pairs.  Scenes are float32 [C][H][W] planes (what city_stack_device leaves in HBM, per
+ * date); 1 <= C <= 65535, 1 <= H, W <= 32767.  Cells: a grid (ny, nx), 1..64 each, ny <= H, nx <= W; cell (i, j) owns rows
+ * [floor(i H / ny), floor((i + 1) H / ny)) and the columns alike.  Sign convention: d2(y + dy, x + dx) ~ d1(y, x).  A fixed number of launches
+ * whatever the data, no atomics, no host read-back, no kernel waits for another block; the caller never clears a workspace: the same bits
+ * on every run, whatever the workspace held.  A null required pointer, a misaligned one, a value outside its range or a shape outside the
+ * limits is BDN_E_ARG before anything touches a device.
+ * bdn_shift_corr: bands: DEVICE int32 [n_b], 1 <= n_b <= 64, indices into C (an index outside [0, C) reads nothing: its entries are 0).
+ *   R: the search radius, 1..16.  exclude (or NULL): uint8 [H][W]; exclude_value 0..255.
+ *       table[b][i][j][dy + R][dx + R][0..5] = {n, sum a, sum b, sum a^2, sum b^2, sum a b}     (float64, dy-major, dy, dx in [-R, R])
+ *   over the pixels (y, x) of cell (i, j) with a = d1[bands[b]][y][x], b = d2[bands[b]][y + dy][x + dx], for which (y + dy, x + dx) lies
+ *   inside the scene (in whichever cell), neither exclude[y][x] nor exclude[y + dy][x + dx] equals exclude_value, and a and b are both
+ *   finite: a NaN or infinite nodata pixel leaves the sums.  Every product is formed in double from the float32 values, so every term is
+ *   exact; every sum is a chain of double additions in a fixed order, one rounding per term: an entry lies within
+ *   (n - 1) 2^-53 sum |term| of the exact sum, and n is exact.  Two launches: blocks of 256 threads stage a 32 x 32 date-1 tile and the
+ *   date-2 tile with its halo of R in LDS, each thread keeps the sums of up to five shifts in registers while the block walks its tiles;
+ *   then the partials are added in index order.  ws: bdn_shift_corr_workspace_bytes() bytes (0 for arguments outside the limits), 16-byte
+ *   aligned: P partial tables, P = max(1, min(1024 / (ny nx), 256 MiB / the table's bytes)) -- it does not grow with H W (13 bands,
+ *   R = 8: 176 MiB for 1 x 1 and for 8 x 8 cells, for any scene).  The size query is host-only.
+ * bdn_shift_peak: table as above (n_b, R, ny, nx the same).  The score of a shift, per cell and once more for the whole scene (whose table is
+ *   the sum of the cells' tables in (i, j) order, per band and entry), is the mean over the bands of
+ *       NCC = (n Sab - Sa Sb) / sqrt((n Saa - Sa Sa) (n Sbb - Sb Sb))
+ *   over the bands with n >= 2 and both variances > 0, added in band order and divided by their number; a shift with no such band scores -2.
+ *   Float64, one rounding per operation, in exactly the order written (each variance and the covariance a difference of two rounded
+ *   products; the two variances multiplied, then the root, then the quotient): numpy float64 reproduces the score from the same table.
+ *   Peak: the first maximum in raster order; each axis refined by delta = (0.5 (c- - c+)) / ((c- - 2 c0) + c+), clamped to [-0.5, 0.5];
+ *   delta = 0 when the peak sits on the window border, a neighbour is undefined (-2) or the denominator is not < 0.
+ *   report: float64 [ny nx + 1][4] = {dy, dx, ncc, ok}, the last row the whole scene; ok = 0 when every shift is undefined: the shift is
+ *   then (0, 0) and ncc -2.  field: float32 [ny][nx][2] = (dy, dx) of the cell; a cell with ok = 0 or ncc < min_ncc takes the whole-scene
+ *   shift, or (0, 0) if that is not ok either.  One launch of ny nx + 1 blocks; a cell that falls back forms the whole-scene peak itself.
+ * bdn_shift_apply: out[c][y][x] = bilinear(src[c], y + s_y(y, x), x + s_x(y, x)) with a replicate border; out != src.  Float32, every
+ *   operation rounded once, nothing fused, in this order.  The field between cell centres, per axis (rows; columns alike):
+ *       cy_i = 0.5f (r0_i + r1_i - 1);  i0 = the last i with cy_i <= y, clamped to [0, ny - 2];  i1 = i0 + 1;
+ *       t_y = clamp((y - cy_i0) / (cy_i1 - cy_i0), 0, 1);  a grid of one along the axis: i0 = i1 = 0, t_y = 0
+ *       s = ((1 - t_y) * (((1 - t_x) * f[i0][j0]) + (t_x * f[i0][j1]))) + (t_y * (((1 - t_x) * f[i1][j0]) + (t_x * f[i1][j1])))     for s_y and s_x
+ *   The taps and the blend are bdn_sample_patches_warp's ("mapping" above): yy = y + s_y, y0 = floorf(yy), fy = yy - y0, xx, x0, fx alike;
+ *   tap rows (int)y0 and + 1, tap columns (int)x0 and + 1, each clamped into the scene (y0, x0 saturate at +-2^30 first);
+ *       top = ((1 - fx) * v00) + (fx * v01),  bot = ((1 - fx) * v10) + (fx * v11),  out = ((1 - fy) * top) + (fy * bot)
+ *   So a zero field returns finite inputs bit for bit (-0.0 may arrive as +0.0), an integer shift moves bits with a replicated edge, and
+ *   numpy float32 reproduces the output exactly.  Non-finite inputs spread to every element that taps them.  oob (or NULL): uint8 [H][W],
+ *   1 where an unclamped tap of non-zero weight lies outside the scene (the second tap of an axis has weight 0 when its fraction is 0).
+ *   field: DEVICE float32 [ny][nx][2], any finite values.  One launch.
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+size_t bdn_shift_corr_workspace_bytes(int n_b, int H, int W, int R, int ny, int nx);
+int bdn_shift_corr(const float* d1, const float* d2, const int32_t* bands, int n_b, const uint8_t* exclude, int exclude_value,
+                   int R, int ny, int nx, double* table, void* ws, int C, int H, int W, void* stream);
+int bdn_shift_peak(const double* table, int n_b, int R, int ny, int nx, double min_ncc, double* report, float* field, void* stream);
+int bdn_shift_apply(const float* src, const float* field, int ny, int nx, float* out, uint8_t* oob, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
