@@ -176,6 +176,10 @@ SIGNATURES = {
     'bdn_shift_corr': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     'bdn_shift_peak': (_i, [_vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
     'bdn_shift_apply': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_band_quantiles_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'bdn_band_quantiles': (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_transfer_apply': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
+    'bdn_stretch_u8': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 

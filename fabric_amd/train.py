@@ -561,6 +561,85 @@ def coregister_loaded(full_load, coreg, ignore_label, device, log=True):
     return reports
 
 
+def check_radiometric_flags(radiometric, knots=None, value_range=None, bands=None, band_ids=None, n_bands=13, synthetic_radiometry=None,
+                            synthetic=False, checkpoint=None):
+    """--radiometric / --radiometric_knots / --radiometric_range / --radiometric_bands and --synthetic_radiometry together, without a
+    device: returns None (off) or the keyword arguments of normalize_cities; raises ValueError with the reason otherwise.  A flag that
+    was not given is None; `checkpoint` is the `radiometric` entry of the metadata of the run --resume continues (or None): with no
+    --radiometric flag the run keeps the checkpoint's settings, since its weights were trained on pairs matched that way.  A band is
+    named by its id in the run's band_ids or by its index."""
+    from .utils import radiometry as RM
+    if synthetic_radiometry is not None:
+        if len(synthetic_radiometry) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float('inf')
+                                                 for v in synthetic_radiometry):
+            raise ValueError(f'--synthetic_radiometry {synthetic_radiometry}: two finite numbers GAIN BIAS')
+        if not synthetic:
+            raise ValueError('--synthetic_radiometry changes date 2 of the synthetic cities: add --synthetic')
+    if radiometric is None and checkpoint is not None:
+        if knots is not None or value_range is not None or bands is not None:
+            raise ValueError('--radiometric_knots / --radiometric_range / --radiometric_bands would change how the resumed run matches its '
+                             'pairs: give --radiometric too, or none of them')
+        out = dict(checkpoint)
+        if out.get('method') not in ('histogram', 'range'):
+            raise ValueError(f'--resume: the checkpoint metadata holds an unknown radiometric entry {checkpoint!r}')
+        return dict(method=out['method'], knots=int(out.get('knots', 256)), lower=float(out.get('lower', 0.02)),
+                    upper=float(out.get('upper', 0.98)), bands=out.get('bands'))
+    if radiometric not in (None, 'none', 'histogram', 'range'):
+        raise ValueError(f"--radiometric {radiometric}: 'none', 'histogram' or 'range'")
+    if radiometric in (None, 'none'):
+        if knots is not None or value_range is not None or bands is not None:
+            raise ValueError('--radiometric_knots / --radiometric_range / --radiometric_bands shape a matching that is not on: add '
+                             '--radiometric histogram or --radiometric range')
+        return None
+    if radiometric == 'histogram' and value_range is not None:
+        raise ValueError('--radiometric_range names the two quantiles of --radiometric range; --radiometric histogram takes --radiometric_knots')
+    if radiometric == 'range' and knots is not None:
+        raise ValueError('--radiometric_knots counts the knots of --radiometric histogram; --radiometric range takes --radiometric_range LO HI')
+    knots = 256 if knots is None else knots
+    if not isinstance(knots, int) or isinstance(knots, bool) or not 2 <= knots <= RM.MAX_KNOTS:
+        raise ValueError(f'--radiometric_knots {knots}: the number of knots, 2..{RM.MAX_KNOTS}')
+    lo, hi = (0.02, 0.98) if value_range is None else value_range
+    if not 0.0 <= lo < hi <= 1.0:
+        raise ValueError(f'--radiometric_range {lo} {hi}: two quantiles with 0 <= LO < HI <= 1')
+    n = len(band_ids) if band_ids else n_bands
+    idx = None
+    if bands is not None:
+        idx = []
+        for b in bands:
+            if band_ids and str(b) in list(band_ids):
+                idx.append(list(band_ids).index(str(b)))
+            elif str(b).lstrip('-').isdigit() and 0 <= int(b) < n:
+                idx.append(int(b))
+            else:
+                raise ValueError(f'--radiometric_bands {b}: neither one of the band ids {list(band_ids or [])} nor an index in [0, {n})')
+        if len(set(idx)) != len(idx):
+            raise ValueError(f'--radiometric_bands {list(bands)}: a band is named twice')
+    if not 1 <= (len(idx) if idx is not None else n) <= RM.MAX_BANDS:
+        raise ValueError(f'--radiometric_bands: 1..{RM.MAX_BANDS} bands (the run has {n}: name a subset)')
+    return dict(method=radiometric, knots=knots, lower=float(lo), upper=float(hi), bands=idx)
+
+
+def checkpoint_radiometric(path):
+    """The `radiometric` entry of the metadata_epoch_N.json beside a checkpoint file of this program, or None."""
+    m = _CKPT.search(os.path.basename(path)) if path else None
+    meta = os.path.join(os.path.dirname(path), f'metadata_epoch_{m.group(1)}.json') if m else None
+    if meta is None or not os.path.exists(meta):
+        return None
+    with open(meta) as fh:
+        return json.load(fh).get('radiometric')
+
+
+def normalize_loaded(full_load, radiom, ignore_label, device, log=True):
+    """--radiometric: match date 2 of every loaded city to its date 1, in place, once, after --coregister and before any loader or scene
+    pass sees the stacks; one `radiom` log line per city.  Returns the per-city reports."""
+    from .utils.radiometry import normalize_cities, report_line
+    reports = normalize_cities(full_load, ignore_label=ignore_label, device=device, **radiom)
+    if log:
+        for city, rep in reports.items():
+            print('radiom ' + json.dumps(report_line(city, rep)), flush=True)
+    return reports
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Training change detection network (HIP path)')
     for k, v in DEFAULTS.items():
@@ -716,6 +795,17 @@ def main(argv=None):
                     help='--coregister: a cell whose peak correlation is below F takes the whole-scene shift')
     ap.add_argument('--synthetic_misreg', type=int, nargs=2, default=[0, 0], metavar=('DY', 'DX'),
                     help='--synthetic: shift date 2 of every city by DY DX pixels (integers, replicated edge)')
+    ap.add_argument('--radiometric', default=None, choices=['none', 'histogram', 'range'],
+                    help='match the radiometry of date 2 of every city to its date 1 once after loading (and after --coregister), on the '
+                         'device (utils/radiometry.py): histogram = quantile transfer through --radiometric_knots knots per band; range = '
+                         'the line that carries the two --radiometric_range quantiles of date 2 onto those of date 1; none (default): off.  '
+                         '--ignore_label pixels take no part in the fit; --resume keeps the setting of the run it continues')
+    ap.add_argument('--radiometric_knots', type=int, default=None, metavar='K', help='--radiometric histogram: knots per band, 2..1024 (default 256)')
+    ap.add_argument('--radiometric_range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help='--radiometric range: the two quantiles matched (default 0.02 0.98)')
+    ap.add_argument('--radiometric_bands', nargs='+', default=None, metavar='BAND', help='--radiometric: the bands matched, by id or index (default: all)')
+    ap.add_argument('--synthetic_radiometry', type=float, nargs=2, default=None, metavar=('GAIN', 'BIAS'),
+                    help='--synthetic: date 2 of every city becomes GAIN * x + BIAS')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
                                                      "band_stds, ...): its entries become defaults like utils/parser.py:7-10")
     pre, _ = ap.parse_known_args(argv)
@@ -811,6 +901,11 @@ def main(argv=None):
                                        opt.synthetic_misreg, opt.synthetic)
     except ValueError as e:
         raise SystemExit(str(e))
+    try:
+        radiom = check_radiometric_flags(opt.radiometric, opt.radiometric_knots, opt.radiometric_range, opt.radiometric_bands, opt.band_ids, 13,
+                                         opt.synthetic_radiometry, opt.synthetic, checkpoint_radiometric(opt.resume) if opt.resume else None)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if opt.init_from and opt.resume:
         raise SystemExit('--init_from starts a run from given weights, --resume continues one: give one of them')
     from .utils.helpers import checkpoint_fusion
@@ -842,9 +937,12 @@ def main(argv=None):
     if opt.synthetic:
         data = synthetic_onera(n_cities=6, bands=13, size=(360, 360), **(
             {} if opt.ignore_label is None else dict(ignore_frac=opt.synthetic_ignore_frac, ignore_value=opt.ignore_label)),
-            **({} if tuple(opt.synthetic_misreg) == (0, 0) else dict(misreg=tuple(opt.synthetic_misreg))))
+            **({} if tuple(opt.synthetic_misreg) == (0, 0) else dict(misreg=tuple(opt.synthetic_misreg))),
+            **({} if opt.synthetic_radiometry is None else dict(radiometry=tuple(opt.synthetic_radiometry))))
         if coreg is not None:
             coregister_loaded(data, coreg, opt.ignore_label, dev, log=rank == 0)
+        if radiom is not None:                             # after the alignment: resampling moves the histogram slightly
+            normalize_loaded(data, radiom, opt.ignore_label, dev, log=rank == 0)
         val_cities = ['city4', 'city5']
     else:
         if not opt.band_ids:
@@ -854,7 +952,9 @@ def main(argv=None):
         scenes = ingest.full_onera_loader(opt.dataset_dir, opt, device=dev)      # city stacks stay in HBM for the scene pass
         if coreg is not None:                              # before the loaders' views and copies of the stacks are made
             coregister_loaded(scenes, coreg, opt.ignore_label, dev, log=rank == 0)
-        if opt.device_patches:                             # the patch sampler reads the same HBM stacks: no round trip through the host
+        if radiom is not None:
+            normalize_loaded(scenes, radiom, opt.ignore_label, dev, log=rank == 0)
+        if opt.device_patches:                            # the patch sampler reads the same HBM stacks: no round trip through the host
             data = {c: {'images': d['images'], 'labels': d['labels']} for c, d in scenes.items()}
         else:
             data = {c: {'images': d['images'].cpu().numpy(), 'labels': d['labels']} for c, d in scenes.items()}
@@ -930,6 +1030,8 @@ def main(argv=None):
     run_meta = dict(meta, **{k: getattr(opt, k) for k in DEFAULTS}, precision=opt.precision, fusion=model.fusion, world_size=world)
     if coreg is not None:                                  # a checkpoint says how its training pairs were aligned
         run_meta['coregister'] = dict(coreg, cells=list(coreg['cells']))
+    if radiom is not None:                                 # ... and how date 2 was matched: --resume reads it back
+        run_meta['radiometric'] = dict(radiom)
     schedule = None
     if scheduled:                                          # host floats only; its position comes from (epoch, batch), so --resume continues it
         from .schedule import LRSchedule

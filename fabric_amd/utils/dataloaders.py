@@ -86,7 +86,8 @@ def metadata_from_shapes(shapes, val_cities, patch_size, stride):
     return train, val
 
 
-def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fraction=0.05, ignore_frac=0.0, ignore_value=255, misreg=(0, 0)):
+def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fraction=0.05, ignore_frac=0.0, ignore_value=255, misreg=(0, 0),
+                    radiometry=None):
     """A `full_load` dict of the reference's schema ({city: {'images': f32[2,C,H,W], 'labels': u8[H,W]}},
     utils/dataloaders.py:138-145) filled with z-scored noise; date 2 = date 1 + small noise + blobs of
     change where the label is 1.  ignore_frac > 0: rectangles of the label raster (nodata borders, unlabelled stretches) are painted
@@ -94,10 +95,14 @@ def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fracti
     The rectangles come from a generator of their own and are painted last: the images, and with ignore_frac = 0 the labels, are
     the arrays this function always returned.  misreg = (dy, dx), integers: date 2 is shifted against date 1 and the labels, with a
     replicated edge, date2'(y, x) = date2(y + dy, x + dx) -- a misregistered pair (fabric_amd.utils.registration estimates (-dy, -dx));
-    (0, 0) draws nothing and moves nothing."""
+    (0, 0) draws nothing and moves nothing.  radiometry = (gain, bias): date 2 becomes gain * x + bias per band in float32 (one rounding per
+    operation) -- a pair whose dates differ radiometrically (fabric_amd.utils.radiometry removes it); None changes nothing."""
     my, mx = (int(v) for v in misreg)
     if (my, mx) != tuple(misreg):
         raise ValueError(f'misreg must be a pair of integers (dy, dx), got {misreg!r}')
+    if radiometry is not None:
+        if len(radiometry) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v) for v in radiometry):
+            raise ValueError(f'radiometry must be None or a pair of finite numbers (gain, bias), got {radiometry!r}')
     r = np.random.default_rng(seed)
     ri = np.random.default_rng([seed, 255]) if ignore_frac > 0 else None
     out = {}
@@ -117,6 +122,8 @@ def synthetic_onera(n_cities=4, bands=13, size=(300, 260), seed=0, change_fracti
                 lbl[y0:y0 + rh, x0:x0 + rw] = ignore_value
         if (my, mx) != (0, 0):
             d2 = d2[:, np.clip(np.arange(h) + my, 0, h - 1)][:, :, np.clip(np.arange(w) + mx, 0, w - 1)]
+        if radiometry is not None:
+            d2 = (np.float32(radiometry[0]) * d2.astype(np.float32)).astype(np.float32) + np.float32(radiometry[1])
         out[f'city{c}'] = {'images': np.stack([d1, d2]).astype(np.float32), 'labels': lbl}
     return out
 
@@ -128,4 +135,7 @@ def __getattr__(name):
     if name in ('city_loader', 'full_onera_loader', 'label_loader', 'get_train_val_metadata'):
         from . import ingest
         return getattr(ingest, name)
+    if name == 'stretch_8bit':                             # utils/dataloaders.py:38-48, on the device (utils/radiometry.py)
+        from . import radiometry
+        return radiometry.stretch_8bit
     raise AttributeError(name)

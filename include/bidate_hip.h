@@ -1060,6 +1060,51 @@ int bdn_shift_corr(const float* d1, const float* d2, const int32_t* bands, int n
 int bdn_shift_peak(const double* table, int n_b, int R, int ny, int nx, double min_ncc, double* report, float* field, void* stream);
 int bdn_shift_apply(const float* src, const float* field, int ny, int nx, float* out, uint8_t* oob, int C, int H, int W, void* stream);
 
+/* ---- radiometric matching of the two dates of a scene: order statistics per band at many probabilities at once, the piecewise-linear
+ * transfer between two knot tables (quantile transfer: the knots of date 2 onto the knots of date 1), and the reference's stretch_8bit
+ * (utils/dataloaders.py:38-48) arithmetic.  Scenes are float32 [C][H][W] planes; 1 <= C <= 65535, 1 <= H, W <= 32767.  A fixed number of
+ * launches whatever the data, integer atomics only (histogram counts from LDS and global adds: a sum of ones has no order), no float
+ * atomics, no host read-back, no kernel waits for another block; the caller never clears a workspace: the same bits on every run, whatever
+ * the workspace held.  A null required pointer, a misaligned one, a value outside its range or a shape outside the limits is BDN_E_ARG
+ * before anything touches a device.
+ * bdn_band_quantiles: bands: DEVICE int32 [n_b], 1 <= n_b <= 64, indices into C (an index outside [0, C) reads nothing: its count is 0).
+ *   The valid pixels of a band: finite; not at exclude[y][x] == exclude_value when exclude (uint8 [H][W], or NULL) is given; > 0 when
+ *   positive_only = 1 (stretch_8bit's rule).  count[b] (int64) = n, their number.  probs: DEVICE float64 [n_q], 1 <= n_q <= 1024, each in
+ *   [0, 1].  For probability p:   h = p * (n - 1)  (one double multiplication),  lo = floor(h),  hi = min(lo + 1, n - 1),  t = h - lo;
+ *       order[b][q][0..1] = {v_(lo), v_(hi)}   (float32) the exact order statistics, 0-based, in the total order of the bit patterns' keys
+ *                                             (-0.0 below +0.0)
+ *       value[b][q] = a + ((b - a) * t)        (float64) a = v_(lo), b = v_(hi); one rounding per operation, nothing fused
+ *   With n = 0, or for a p outside [0, 1] (NaN included), value and both order entries are NaN.  Method: a radix select over the monotone
+ *   key of a float32 in three levels of 11 + 11 + 10 bits for all 2 n_q ranks of a band together: a histogram of the top digit, the top
+ *   digits the ranks fall in each get a slot, a histogram of the second digit per slot, a slot per wanted 22-bit prefix, a histogram of the
+ *   last digit per slot.  Seven launches (a memset, three histogram passes over the scene, three selects) per group of bands; the bands
+ *   are taken in groups of G = max(1, min(n_b, 128 MiB / band bytes)), band bytes = 16 KiB + n_q (24 KiB + 32 B).
+ *   ws: bdn_band_quantiles_workspace_bytes() = G * band bytes (0 for arguments outside the limits), 16-byte aligned: at most 128 MiB, a
+ *   function of n_b and n_q only -- it does not grow with H W (13 bands: 0.8 MiB at n_q = 2, 78 MiB at n_q = 256).  The size query is host-only.
+ * bdn_transfer_apply: out[c] = f_b(src[c]) for the bands named (bands: DEVICE int32 [n_b], 1 <= n_b <= 64; the first row that names a band
+ *   counts), a copy for the others when out != src; out == src is allowed (pointwise).  s_knots, t_knots: DEVICE float32 [n_b][K], each row
+ *   nondecreasing, 2 <= K <= 1024.  For a finite x, float32, one rounding per operation, nothing fused:
+ *       s_0 <= x < s_{K-1}:   k = the last index with s_k <= x  (so s_{k+1} > s_k);   seg_k(x) = t_k + ((x - s_k) * ((t_{k+1} - t_k) / (s_{k+1} - s_k)))
+ *       x < s_0:              BDN_EXTRAPOLATE_OFFSET: off_0(x);      BDN_EXTRAPOLATE_SLOPE: seg_0(x) if s_1 > s_0, else off_0(x)
+ *       x >= s_{K-1}:         BDN_EXTRAPOLATE_OFFSET: off_{K-1}(x);  BDN_EXTRAPOLATE_SLOPE: seg_{K-2}(x) if s_{K-1} > s_{K-2}, else off_{K-1}(x)
+ *       off_e(x) = x + (t_e - s_e), and x itself where t_e - s_e == 0;   seg_k(x) = x itself where s_k == t_k and s_{k+1} == t_{k+1}
+ *   so a table with t == s returns the source bit for bit.  NaN and infinite pixels pass through with their bits.  A band with a NaN knot
+ *   (what a band without valid pixels in either date gets) or with exact[b] != 0 (exact: DEVICE uint8 [n_b], or NULL) passes through whole.
+ *   The knot tables of the block's band sit in LDS.  One launch.
+ * bdn_stretch_u8: out[c][y][x] (uint8) = trunc(clamp((x - cd[c][0]) * (255.0 / (cd[c][1] - cd[c][0])), 0, 255)) in float64, one rounding per
+ *   operation; src: float32 (src_is_u16 = 0) or uint16 (1) [C][H][W]; cd: DEVICE float64 [C][2] = {c, d}.  A NaN (a NaN pixel, a NaN c or d,
+ *   or x == c when d == c) gives 0; with d == c every x > c gives 255 and every x <= c gives 0.  One launch.
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+#define BDN_EXTRAPOLATE_OFFSET 0
+#define BDN_EXTRAPOLATE_SLOPE 1
+size_t bdn_band_quantiles_workspace_bytes(int n_b, int n_q, int H, int W);
+int bdn_band_quantiles(const float* scene, const int32_t* bands, int n_b, const uint8_t* exclude, int exclude_value, int positive_only,
+                       const double* probs, int n_q, double* value, float* order, long long* count, void* ws, int C, int H, int W,
+                       void* stream);
+int bdn_transfer_apply(const float* src, float* out, const int32_t* bands, int n_b, const float* s_knots, const float* t_knots, int K,
+                       int extrapolate, const uint8_t* exact, int C, int H, int W, void* stream);
+int bdn_stretch_u8(const void* src, int src_is_u16, const double* cd, uint8_t* out, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
