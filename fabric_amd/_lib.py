@@ -180,6 +180,12 @@ SIGNATURES = {
     'bdn_band_quantiles': (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'bdn_transfer_apply': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
     'bdn_stretch_u8': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_mad_workspace_bytes': (_sz, [_i, _i, _i]),
+    'bdn_mad_centre': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_mad_moments': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_mad_solve': (_i, [_vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),
+    'bdn_mad_chi2': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'bdn_mad_mask': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _i, _i, _i, _vp]),
 }
 
 

@@ -619,6 +619,42 @@ def check_radiometric_flags(radiometric, knots=None, value_range=None, bands=Non
     return dict(method=radiometric, knots=knots, lower=float(lo), upper=float(hi), bands=idx)
 
 
+def check_mad_flags(invariant=None, iters=None, tol=None, invariant_min=None, radiom=None, checkpoint=None, explicit=False):
+    """--radiometric_invariant / --mad_iters / --mad_tol / --mad_invariant_min, without a device: returns {} (off) or the extra keyword
+    arguments of normalize_cities (invariant, invariant_min, mad_iters, mad_tol); raises ValueError with the reason otherwise.  `radiom` is
+    what check_radiometric_flags returned, `checkpoint` the `radiometric` entry of the run --resume continues; `explicit`: --radiometric
+    was given.  Like the matching itself, a resumed run keeps the checkpoint's settings unless --radiometric is given again."""
+    from .utils import mad as MAD
+    given = [n for n, v in (('--mad_iters', iters), ('--mad_tol', tol), ('--mad_invariant_min', invariant_min)) if v is not None]
+    if invariant is None and not given and radiom is not None and not explicit and checkpoint and checkpoint.get('invariant') is not None:
+        if checkpoint.get('invariant') != 'mad':
+            raise ValueError(f'--resume: the checkpoint metadata holds an unknown radiometric invariant {checkpoint.get("invariant")!r}')
+        return dict(invariant='mad', invariant_min=float(checkpoint.get('invariant_min', 0.95)), mad_iters=int(checkpoint.get('mad_iters', 30)),
+                    mad_tol=float(checkpoint.get('mad_tol', 1e-3)))
+    if invariant not in (None, 'mad'):
+        raise ValueError(f"--radiometric_invariant {invariant}: 'mad'")
+    if invariant is None:
+        if given:
+            raise ValueError(f'{" / ".join(given)} shape the invariant-pixel selection: add --radiometric_invariant mad')
+        return {}
+    if radiom is None or not explicit:
+        raise ValueError('--radiometric_invariant selects the pixels --radiometric fits its transfer on: add --radiometric histogram or '
+                         '--radiometric range')
+    iters = 30 if iters is None else iters
+    if not isinstance(iters, int) or isinstance(iters, bool) or not 1 <= iters <= MAD.MAX_ITERS:
+        raise ValueError(f'--mad_iters {iters}: the largest number of iterations, 1..{MAD.MAX_ITERS}')
+    tol = 1e-3 if tol is None else tol
+    if not isinstance(tol, (int, float)) or isinstance(tol, bool) or not 0.0 <= tol < float('inf'):
+        raise ValueError(f'--mad_tol {tol}: a finite number >= 0 (0 never stops early)')
+    p = 0.95 if invariant_min is None else invariant_min
+    if not isinstance(p, (int, float)) or isinstance(p, bool) or not 0.0 < p <= 1.0:
+        raise ValueError(f'--mad_invariant_min {p}: a probability in (0, 1]')
+    n = len(radiom['bands']) if radiom.get('bands') is not None else None
+    if n is not None and n > MAD.MAX_BANDS:
+        raise ValueError(f'--radiometric_invariant mad takes 1..{MAD.MAX_BANDS} bands: name a subset with --radiometric_bands')
+    return dict(invariant='mad', invariant_min=float(p), mad_iters=iters, mad_tol=float(tol))
+
+
 def checkpoint_radiometric(path):
     """The `radiometric` entry of the metadata_epoch_N.json beside a checkpoint file of this program, or None."""
     m = _CKPT.search(os.path.basename(path)) if path else None
@@ -632,10 +668,12 @@ def checkpoint_radiometric(path):
 def normalize_loaded(full_load, radiom, ignore_label, device, log=True):
     """--radiometric: match date 2 of every loaded city to its date 1, in place, once, after --coregister and before any loader or scene
     pass sees the stacks; one `radiom` log line per city.  Returns the per-city reports."""
-    from .utils.radiometry import normalize_cities, report_line
+    from .utils.radiometry import mad_line, normalize_cities, report_line
     reports = normalize_cities(full_load, ignore_label=ignore_label, device=device, **radiom)
     if log:
         for city, rep in reports.items():
+            if 'mad' in rep:                               # --radiometric_invariant mad: what the fit of the next line was restricted to
+                print('mad ' + json.dumps(mad_line(city, rep)), flush=True)
             print('radiom ' + json.dumps(report_line(city, rep)), flush=True)
     return reports
 
@@ -804,6 +842,15 @@ def main(argv=None):
     ap.add_argument('--radiometric_range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
                     help='--radiometric range: the two quantiles matched (default 0.02 0.98)')
     ap.add_argument('--radiometric_bands', nargs='+', default=None, metavar='BAND', help='--radiometric: the bands matched, by id or index (default: all)')
+    ap.add_argument('--radiometric_invariant', default=None, choices=['mad'],
+                    help='--radiometric: fit the transfer on invariant pixels only, found without labels by IR-MAD on the device '
+                         '(utils/mad.py): the pixels whose no-change probability reaches --mad_invariant_min.  One `mad` log line per city; '
+                         'recorded in the checkpoint metadata and taken back by --resume')
+    ap.add_argument('--mad_iters', type=int, default=None, metavar='N', help='--radiometric_invariant mad: at most N iterations, 1..1000 (default 30)')
+    ap.add_argument('--mad_tol', type=float, default=None, metavar='F',
+                    help='--radiometric_invariant mad: stop once the canonical correlations move by less than F (default 1e-3; 0: never)')
+    ap.add_argument('--mad_invariant_min', type=float, default=None, metavar='P',
+                    help='--radiometric_invariant mad: the no-change probability from which a pixel counts as invariant (default 0.95)')
     ap.add_argument('--synthetic_radiometry', type=float, nargs=2, default=None, metavar=('GAIN', 'BIAS'),
                     help='--synthetic: date 2 of every city becomes GAIN * x + BIAS')
     ap.add_argument('--metadata', default=None, help="JSON in the reference's metadata.json schema (band_ids, band_means, "
@@ -904,6 +951,10 @@ def main(argv=None):
     try:
         radiom = check_radiometric_flags(opt.radiometric, opt.radiometric_knots, opt.radiometric_range, opt.radiometric_bands, opt.band_ids, 13,
                                          opt.synthetic_radiometry, opt.synthetic, checkpoint_radiometric(opt.resume) if opt.resume else None)
+        mad_kw = check_mad_flags(opt.radiometric_invariant, opt.mad_iters, opt.mad_tol, opt.mad_invariant_min, radiom,
+                                 checkpoint_radiometric(opt.resume) if opt.resume else None, explicit=opt.radiometric not in (None, 'none'))
+        if mad_kw:                                         # without the flag the dict, and with it every call, stays what it was
+            radiom = dict(radiom, **mad_kw)
     except ValueError as e:
         raise SystemExit(str(e))
     if opt.init_from and opt.resume:

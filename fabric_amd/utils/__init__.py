@@ -3,3 +3,4 @@ from .distance import boundary_scores, check_edt_args, distance_transform_sq, si
 from .registration import apply_shift, check_apply_args, check_estimate_args, coregister, coregister_cities, estimate_shift  # noqa: F401
 from .radiometry import (apply_transfer, band_quantiles, check_fit_args, check_quantile_args, check_transfer_args, fit_transfer,  # noqa: F401
                          match_histograms, match_range, normalize_cities)
+from .mad import MadResult, change_mask, check_mad_args, irmad  # noqa: F401

@@ -262,17 +262,34 @@ def match_range(d2, d1, lower=0.02, upper=0.98, bands=None, exclude=None, exclud
     return apply_transfer(d2, tr, out), tr
 
 
-def normalize_cities(full_load, method='histogram', knots=256, lower=0.02, upper=0.98, bands=None, ignore_label=None, device='cuda'):
+def normalize_cities(full_load, method='histogram', knots=256, lower=0.02, upper=0.98, bands=None, ignore_label=None, device='cuda',
+                     invariant=None, invariant_min=0.95, mad_iters=30, mad_tol=1e-3):
     """Match date 2 of every city of a `full_load` dict ({city: {'images': float32 [2,C,H,W], 'labels': uint8 [H,W]}}) to its date 1, in
     place: device stacks are rewritten on the device, numpy stacks are uploaded, matched and written back into the same arrays (numpy in,
     numpy out).  method 'histogram' is match_histograms (knots), 'range' is match_range (lower, upper).  Date 1 and the labels are never
     written; label pixels equal to ignore_label (a byte) are left out of the fit.  Returns {city: report}, report = {'method', 'bands',
     'count': [2][n_b] (date 2, date 1), 'p': (0.02, 0.5, 0.98), 'src', 'dst': [n_b][3] = the quantiles of date 2 before matching and of
-    date 1 at p}; one host read per city, after its launches."""
+    date 1 at p}; one host read per city, after its launches.
+    invariant='mad': the transfer is fitted on invariant pixels only.  Per city, utils.mad.irmad runs on the same bands (ignore_label left
+    out, at most mad_iters iterations, stopping at mad_tol), change_mask(threshold=invariant_min, excluded_out=1) marks the pixels whose
+    no-change probability lies below invariant_min and the ignored ones, and that raster (value 1) is the `exclude` of the fit.  A failed
+    solve (a rank-deficient date, too few pixels) falls back to the exclude above, with one difference: a pixel that is not finite in
+    any named band of either date is left out of the fit of every band (IR-MAD's rule of validity), where the plain path drops
+    non-finite values band by band; on finite data the two are the same raster.  The report gains 'mad': {'ok', 'iters', 'converged',
+    'rho', 'invariant_frac' (of the scene's pixels), 'fallback'}, read with the same single host read.  None (default): the calls above."""
     if method not in ('histogram', 'range'):
         raise ValueError(f"method must be 'histogram' or 'range', got {method!r}")
     if ignore_label is not None and (not _is_int(ignore_label) or not 0 <= ignore_label <= 255):
         raise ValueError(f'ignore_label must be None or a byte 0..255, got {ignore_label!r}')
+    if invariant not in (None, 'mad'):
+        raise ValueError(f"invariant must be None or 'mad', got {invariant!r}")
+    if invariant is not None:
+        from . import mad as MAD
+        if isinstance(invariant_min, bool) or not isinstance(invariant_min, (int, float)) or not 0.0 < invariant_min <= 1.0:
+            raise ValueError(f'invariant_min must be a probability in (0, 1], got {invariant_min!r}')
+        if not _is_int(mad_iters) or not 1 <= mad_iters <= MAD.MAX_ITERS:
+            raise ValueError(f'mad_iters must be an integer 1..{MAD.MAX_ITERS}, got {mad_iters!r}')
+        MAD._number(mad_tol, 'mad_tol', lo=0.0)
     if method == 'range':
         probs, k, mode = list(_check_range(lower, upper)), 2, 'slope'
     else:
@@ -290,15 +307,31 @@ def normalize_cities(full_load, method='histogram', knots=256, lower=0.02, upper
         if ignore_label is not None:
             lab = torch.from_numpy(np.ascontiguousarray(labels)) if not torch.is_tensor(labels) else labels
             exclude = lab.to(stack.device).contiguous()
-        tr, ex = _fit(stack[1], stack[0], probs, k, bands, exclude, ignore_label, mode, extra=REPORT_PROBS)
+        res = inv = None
+        if invariant == 'mad':
+            res = MAD.irmad(stack[0], stack[1], bands, exclude, ignore_label, mad_iters, mad_tol)
+            # after a failed solve every no-change probability is NaN, which the mask turns into 0: the raster then holds 1 at the ignored
+            # pixels (the exclude above) and at the pixels that are not finite in some named band of either date, which the plain path
+            # drops band by band only -- the fallback needs no host read before the fit
+            inv = MAD.change_mask(res, invariant_min, 1)
+            tr, ex = _fit(stack[1], stack[0], probs, k, bands, inv, 1, mode, extra=REPORT_PROBS)
+        else:
+            tr, ex = _fit(stack[1], stack[0], probs, k, bands, exclude, ignore_label, mode, extra=REPORT_PROBS)
         apply_transfer(stack[1], tr, out=stack[1])
         if host:
             images[1] = stack[1].cpu().numpy()
         nb = len(tr.bands)
-        both = torch.cat([ex.flatten(), tr.count.flatten().double()]).cpu().numpy()
+        parts = [ex.flatten(), tr.count.flatten().double()]
+        if res is not None:
+            parts += [res.state, (inv == 0).sum().double().reshape(1)]
+        both = torch.cat(parts).cpu().numpy()
         ex_h = both[:2 * nb * 3].reshape(2, nb, 3)
-        reports[city] = {'method': method, 'bands': list(tr.bands), 'count': both[2 * nb * 3:].astype(np.int64).reshape(2, nb).tolist(),
+        reports[city] = {'method': method, 'bands': list(tr.bands), 'count': both[2 * nb * 3:2 * nb * 4].astype(np.int64).reshape(2, nb).tolist(),
                          'p': list(REPORT_PROBS), 'src': ex_h[0].tolist(), 'dst': ex_h[1].tolist()}
+        if res is not None:
+            m = MAD.read_state(both[2 * nb * 4:-1], nb)
+            reports[city]['mad'] = {'ok': m['ok'], 'iters': m['iters'], 'converged': m['converged'], 'rho': m['rho'].tolist(),
+                                    'invariant_frac': float(both[-1]) / float(inv.numel()), 'fallback': not m['ok']}
     return reports
 
 
@@ -306,6 +339,11 @@ def report_line(city, rep):
     """The fields of train.py's `radiom` log line for one city."""
     return {'city': city, 'method': rep['method'], 'bands': rep['bands'], 'count': rep['count'], 'p': rep['p'], 'src': rep['src'],
             'dst': rep['dst']}
+
+
+def mad_line(city, rep):
+    """The fields of train.py's `mad` log line for one city (normalize_cities(invariant='mad'))."""
+    return dict({'city': city}, **rep['mad'])
 
 
 def _as_stack(band):

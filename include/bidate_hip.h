@@ -1105,6 +1105,77 @@ int bdn_transfer_apply(const float* src, float* out, const int32_t* bands, int n
                        int extrapolate, const uint8_t* exact, int C, int H, int W, void* stream);
 int bdn_stretch_u8(const void* src, int src_is_u16, const double* cd, uint8_t* out, int C, int H, int W, void* stream);
 
+/* ---- IR-MAD, the iteratively reweighted multivariate alteration detection (Nielsen 2007; Canty and Nielsen 2008) between the two dates of
+ * a scene: a canonical correlation analysis of date 1 against date 2 in which every pixel is weighted by its probability of no change,
+ * iterated to a fixed point.  It gives a per-pixel chi-square change statistic with its no-change probability, invariant to any affine
+ * radiometric difference between the dates, and from it an invariant-pixel mask that needs no labels.  Scenes are float32 [C][H][W] planes
+ * per date; 1 <= C <= 65535, 1 <= H, W <= 32767.  bands: DEVICE int32 [n_b], 1 <= n_b <= 32; exclude: NULL or uint8 [H][W] with
+ * exclude_value (a byte).  A fixed number of launches whatever the data, no float atomics, no host read-back, no kernel waits for another
+ * block; the caller never clears a workspace or an output: the same bits on every run, whatever those buffers held.  A null required
+ * pointer, a misaligned one, a value outside its range or a shape outside the limits is BDN_E_ARG before anything touches a device.
+ * Valid pixels: all 2 n_b selected values finite and exclude[y][x] != exclude_value.  A band index outside [0, C) makes every pixel
+ * invalid (nothing is read).  D = 2 n_b; the vector of a pixel is (x, y) = (date 1's n_b values, date 2's n_b values).
+ * bdn_mad_centre: centre[D] (float64) = the unweighted mean of the valid pixels per selected band and date (0 without a valid pixel),
+ *   n_valid (int64) = their number.  Summed in double in a fixed order: block partials, then an index-order finish.  Two launches.
+ * bdn_mad_moments: with z = (x - centre_x, y - centre_y) formed in double and w = weight[y][x] (float32 [H][W]; a weight that is not in
+ *   [0, FLT_MAX] counts as 0; NULL: 1), over the valid pixels
+ *       moments[0] = S0 = sum w;   moments[1 + k] = S1[k] = sum w z_k;
+ *       moments[1 + D + k D - k (k - 1) / 2 + (l - k)] = S2[k][l] = sum w z_k z_l,  k <= l      (1 + D + D (D + 1) / 2 doubles)
+ *   A term is fl(w z_k) z_l, added by one fused multiply-add; every sum is a chain of double additions in an order fixed by (n_b, H, W):
+ *   an entry lies within n 2^-53 sum |term| of the exact sum of its rounded terms, n = the valid pixels.  Block partials go to ws, then an
+ *   index-order reduction.  ws: bdn_mad_workspace_bytes(n_b, H, W) = min(ceil(H W / 64), 768) * 128 * T (T + 1) / 2 bytes,
+ *   T = ceil((D + 1) / 4): bounded whatever the scene size (13 bands: at most 2.6 MiB; 32 bands: 14.3 MiB), 0 for arguments outside the
+ *   limits; the size query is host-only; 16-byte aligned.  bdn_mad_centre takes the same ws.  state: NULL, or the state block of the run:
+ *   with state[CONVERGED] != 0 the call writes nothing.  Two launches.
+ * bdn_mad_solve: one block, float64.  mean_z = S1 / S0, cov = S2 / S0 - mean_z mean_z^T, cut into Sxx, Sxy, Syy; Cholesky Sxx = Lx Lx^T,
+ *   Syy = Ly Ly^T; K = Lx^-1 Sxy Ly^-T; K = U diag(rho) V^T by one-sided Jacobi; a_i = Lx^-T u_i, b_i = Ly^-T v_i: the variates a_i^T x and
+ *   b_i^T y have unit weighted variance and correlation rho_i >= 0.  Ordered by rho descending; rho clamped to at most 1; the sign of
+ *   (a_i, b_i) such that sum_k (Sxx a_i)[k] / sqrt(Sxx[k][k]) >= 0; var_i = max(2 (1 - rho_i), min_var); delta = max_i |rho_i - rho_i of the
+ *   previous solve|, +inf with first = 1.  A singular value of exactly 0 leaves a_i = 0.  The solve fails (ok = 0) when S0 <= 0, when
+ *   n_valid < D + 1, or when a Cholesky pivot is <= 1e-12 times its original diagonal entry (a rank-deficient date): rho, var, a, b and
+ *   delta are then NaN.  state: float64 [BDN_MAD_STATE_DOUBLES(n_b)]:
+ *       [0] iter  [1] ok  [2] converged  [3] skip  [4] delta  [5] S0  [6] n_valid  [7 ..] rho[n_b], var[n_b], mean[D], centre[D],
+ *       a[n_b][n_b] (a[i][k]: coefficient k of variate i), b[n_b][n_b];     mean = centre + mean_z
+ *   Flags: with first = 1 the state's previous content is ignored (iter = 1).  Otherwise, with converged != 0 on entry the solve sets
+ *   skip = 1 and does nothing else.  A solve that works sets iter += 1, skip = 0, converged = (delta < tol), and converged = 1, ok = 0 when
+ *   it fails.  tol >= 0 (0 never stops), min_var > 0.  One launch.
+ * bdn_mad_chi2: with state[SKIP] != 0 the call writes nothing.  Per valid pixel, in double:  M_i = a_i^T (x - mean_x) - b_i^T (y - mean_y),
+ *   chi2 = sum_i M_i^2 / var_i,  nochange = Q(n_b / 2, chi2 / 2), the chi-square tail with n_b degrees of freedom by its finite closed form,
+ *   t = chi2 / 2, h = e^(-t/2):   even n_b = 2m: h sum_{k<m} (h t^k / k!);   odd n_b = 2m + 1: erfc(sqrt t) + h sum_{k=1..m} (h t^(k-1/2) / Gamma(k + 1/2)),
+ *   the terms built by recurrence from h (every term is below 2^16, nothing overflows), clamped to at most 1.  Outputs, each rounded once to
+ *   float32: chi2[H][W]; proba[2][H][W] = {nochange, 1 - nochange} (the layout bdn_score_hist and bdn_threshold_mask take); variates
+ *   (NULL or [n_b][H][W]) = M_i.  An invalid pixel gets chi2 = 0, proba = {1, 0}, variates 0.  With ok = 0 every pixel gets NaN in all
+ *   outputs.  Plane 0 of proba is the next iteration's weight.  One launch.
+ * bdn_mad_mask: mask[y][x] (uint8) = 1 where proba[0][y][x] < threshold, 0 elsewhere (a NaN gives 0), excluded_out (a byte) where the pixel
+ *   is invalid; threshold in [0, 1].  One launch.
+ * Iteration without a host read: centre once, then `iters` times (moments with the state, solve, chi2); the first moments call takes
+ *   state = NULL and weight = NULL, the first solve first = 1, later moments calls weight = plane 0 of proba.  Only the single-block solve
+ *   writes the flags, so no launch reads a flag that the same launch writes: the chi2 of the converged iteration still runs, and every
+ *   launch after it changes no byte anywhere.
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+#define BDN_MAD_STATE_ITER 0
+#define BDN_MAD_STATE_OK 1
+#define BDN_MAD_STATE_CONVERGED 2
+#define BDN_MAD_STATE_SKIP 3
+#define BDN_MAD_STATE_DELTA 4
+#define BDN_MAD_STATE_S0 5
+#define BDN_MAD_STATE_NVALID 6
+#define BDN_MAD_STATE_RHO 7
+#define BDN_MAD_STATE_DOUBLES(n_b) (7 + 6 * (n_b) + 2 * (n_b) * (n_b))
+#define BDN_MAD_MOMENT_DOUBLES(n_b) (1 + 2 * (n_b) + (n_b) * (2 * (n_b) + 1))
+size_t bdn_mad_workspace_bytes(int n_b, int H, int W);
+int bdn_mad_centre(const float* d1, const float* d2, const int32_t* bands, int n_b, const uint8_t* exclude, int exclude_value,
+                   double* centre, long long* n_valid, void* ws, int C, int H, int W, void* stream);
+int bdn_mad_moments(const float* d1, const float* d2, const int32_t* bands, int n_b, const uint8_t* exclude, int exclude_value,
+                    const float* weight, const double* centre, const double* state, double* moments, void* ws, int C, int H, int W,
+                    void* stream);
+int bdn_mad_solve(const double* moments, const double* centre, const long long* n_valid, int n_b, int first, double tol, double min_var,
+                  double* state, void* stream);
+int bdn_mad_chi2(const float* d1, const float* d2, const int32_t* bands, int n_b, const uint8_t* exclude, int exclude_value,
+                 const double* state, float* chi2, float* proba, float* variates, int C, int H, int W, void* stream);
+int bdn_mad_mask(const float* proba, const float* d1, const float* d2, const int32_t* bands, int n_b, const uint8_t* exclude,
+                 int exclude_value, float threshold, int excluded_out, uint8_t* mask, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
