@@ -2,7 +2,19 @@
 // the buffer swap, gradient accumulation and the global gradient norm, and the layer-wise adaptive rules LAMB / LARS (per-tensor norms
 // and trust ratios), and the perturbation and restore of sharpness-aware minimisation (SAM / ASAM).  Memory-bound float4 passes; no
 // atomics, fixed-order reductions.
+//
+// Map of the file:
+//   ungrouped kernels   sgd_kernel, sgdm_kernel, adam_kernel (with sgdm_elem / adam_elem, which every rule reuses), ema_multi_kernel,
+//                       grad_accumulate_kernel: no table, and they alone handle n % 4 tails.
+//   shared helpers      what every table-driven kernel is assembled from, each written once: flat_check / table_check (host), seg_step,
+//                       stage_table (table and per-group parameters into LDS, *dev_scale applied), pass_lookup (grid-stride passes),
+//                       chunk_span (the partial kernels' chunks), wave_sum / block_sum (fixed-order sums of doubles).
+//   rules               RuleSgd / RuleSgdm / RuleAdam / RuleEma / RuleSwap (grouped_kernel), RuleLamb / RuleLars (lw_partial_kernel,
+//                       lw_apply_kernel), sq_acc / sam_acc (the terms of the two norm partials), sam_elem (sam_apply_kernel).
+//   entry points        each section ends with its own: bdn_sgd_step .. bdn_adam_step, the grouped updates and their _ex forms, EMA / swap,
+//                       bdn_grad_accumulate and bdn_grad_norm, bdn_lamb_step / bdn_lars_step, bdn_sam_perturb / bdn_sam_restore.
 #include "common.hpp"
+#include <initializer_list>
 
 // ============================================================ SGD (train.py:55,95)
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float step, size_t n4, size_t n) {
@@ -234,12 +246,156 @@ struct RuleAdam {
     static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v, const Params& a) { adam_elem(p, g, m, v, a); }
 };
 
+// ------------------------------------------------------------ shared helpers of the table-driven kernels
+// Everything between an entry point's arguments and a rule's element function, written once: the grouped updates, EMA / swap, the
+// gradient norm, LAMB / LARS and SAM below differ in their rule and in what they derive from a vector's table entry, not in this.
+//
+// Host side, flat buffers: `need` must not be null; `buffers` must be 16-byte aligned (a null entry -- a rule without that state -- passes);
+// n is a multiple of 4 whose vector count fits the table's 32-bit ends.
+static int flat_check(const char* what, std::initializer_list<const void*> need, std::initializer_list<const void*> buffers, size_t n) {
+    for (const void* q : need)
+        if (!q) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    uintptr_t bits = 0;
+    for (const void* q : buffers) bits |= (uintptr_t)q;
+    if (bits & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
+    if (n % 4 != 0 || n / 4 > 0xffffffffull)
+        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
+    return BDN_OK;
+}
+
+// Host side, a table of `count` entries of `noun` ("segment" / "tensor"): 1..OPT_MAX_SEGS of them, or 0.. where the entry point takes
+// "no table" -- `every` then names what counts without one ("vector" / "element") and is nullptr otherwise; its arrays non-null and
+// 4-byte aligned when there are entries; n_groups, where given, in 1..OPT_MAX_GROUPS.
+static int table_check(const char* what, const char* noun, const char* every, int count, std::initializer_list<const void*> arrays,
+                       const int* n_groups) {
+    if (n_groups && (*n_groups < 1 || *n_groups > OPT_MAX_GROUPS))
+        BDN_FAIL(BDN_E_ARG, "%s: %d groups (1..%d: their hyperparameters travel in the kernel arguments)", what, *n_groups, OPT_MAX_GROUPS);
+    if (every && (count < 0 || count > OPT_MAX_SEGS))
+        BDN_FAIL(BDN_E_ARG, "%s: %d %ss (0..%d; 0: no table, every %s counts)", what, count, noun, OPT_MAX_SEGS, every);
+    if (!every && (count < 1 || count > OPT_MAX_SEGS)) BDN_FAIL(BDN_E_ARG, "%s: %d %ss (1..%d)", what, count, noun, OPT_MAX_SEGS);
+    if (count == 0) return BDN_OK;
+    uintptr_t bits = 0;
+    for (const void* q : arrays) {
+        if (!q && every) BDN_FAIL(BDN_E_ARG, "%s: null pointer (%s table of %d %ss)", what, noun, count, noun);
+        if (!q) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+        bits |= (uintptr_t)q;
+    }
+    if (bits & 3) BDN_FAIL(BDN_E_ARG, "%s: %s table must be 4-byte aligned", what, noun);
+    return BDN_OK;
+}
+
 // One halving step of the lookup "first s with end[s] > i" over the LDS table, which is padded with UINT32_MAX to `cap` entries, a power
 // of two: branch-free, so the OPT_VEC lookups of a pass advance side by side (their LDS reads are independent) and lanes never diverge.
 __device__ __forceinline__ void seg_step(const uint32_t* s_end, int h, uint32_t i, int& s) {
     if (s_end[s + h - 1] <= i) s += h;
 }
 
+// The table's ends and groups into LDS, padded to `cap` entries, a power of two (seg_step's contract), which is returned; the caller
+// places the barrier.  n == 0 -- no table: bdn_ema_update, bdn_swap_segments -- gives one segment of group 0 that covers everything; a
+// pad entry is frozen otherwise.  third(k, in) fills a third per-entry array beside them (in: k is an entry, not a pad), or nothing.
+struct NoThird { __device__ __forceinline__ void operator()(int, bool) const {} };
+template <typename Third>
+__device__ __forceinline__ int stage_table(const uint32_t* __restrict__ end, const int32_t* __restrict__ group, int n, uint32_t* s_end,
+                                           int* s_grp, Third third) {
+    int cap = 1;
+    while (cap < n) cap <<= 1;
+    for (int k = threadIdx.x; k < cap; k += 256) {
+        const bool in = k < n;
+        s_end[k] = in ? end[k] : 0xffffffffu;
+        s_grp[k] = in ? group[k] : (n == 0 ? 0 : OPT_FROZEN);
+        third(k, in);
+    }
+    return cap;
+}
+
+// The same, and the per-group parameters beside the table; with dev_scale (the _ex entry points, LAMB / LARS) grad_scale * *dev_scale is
+// formed here, once per block.  dev_scale == nullptr never touches the staged parameters: the plain forms keep the bits they always gave.
+template <typename Rule, typename Third>
+__device__ __forceinline__ int stage_table(const uint32_t* __restrict__ end, const int32_t* __restrict__ group, int n, uint32_t* s_end,
+                                           int* s_grp, Third third, const GroupArgs<typename Rule::Params>& a,
+                                           const float* __restrict__ dev_scale, typename Rule::Params* s_par) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < OPT_MAX_GROUPS; k++) s_par[k] = a.g[k];
+        if (dev_scale) {
+            const float ds = *dev_scale;
+#pragma unroll
+            for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
+        }
+    }
+    return stage_table(end, group, n, s_end, s_grp, third);
+}
+
+// The table entry s of each of the OPT_VEC vectors i = b0 + u * stride + threadIdx.x of a grid-stride pass, as out[u] = entry(s, i), or
+// -1 for a vector at or behind n4 or behind the table's last end: such a vector is neither read nor written, so a wrong table can not
+// move an access out of the buffers.  EntryIndex yields s itself; a caller that wants more of the entry than its index -- SAM's count of
+// real elements, which reads the entry's end again -- derives it here, where that end is already in a register.  A block's 256
+// consecutive vectors almost always lie in one entry: one lookup of the first vector then serves the block (the first vector is clamped:
+// a pass past the end yields -1 below); the lookup is per lane where they span a boundary or lie behind the table.
+struct EntryIndex { __device__ __forceinline__ int operator()(int s, size_t) const { return s; } };
+static_assert(OPT_FROZEN == -1, "grouped_kernel reads pass_lookup's 'no entry' as the frozen group id");
+template <typename Entry>
+__device__ __forceinline__ void pass_lookup(const uint32_t* s_end, int cap, size_t b0, size_t stride, size_t n4, int (&out)[OPT_VEC],
+                                            Entry entry) {
+    int head[OPT_VEC] = {};
+    for (int h = cap >> 1; h > 0; h >>= 1) {
+#pragma unroll
+        for (int u = 0; u < OPT_VEC; u++) {
+            const size_t first = b0 + u * stride;
+            seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), head[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < OPT_VEC; u++) {
+        const size_t first = b0 + u * stride, i = first + threadIdx.x;
+        out[u] = -1;
+        if (i < n4) {
+            const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
+            int s = head[u];
+            if (!(s_end[s] > last)) {
+                s = 0;
+                for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
+            }
+            if (s_end[s] > i) out[u] = entry(s, i);
+        }
+    }
+}
+
+// The entries of the first and of the last vector of a partial kernel's chunk: equal where the chunk lies in one entry -- one lookup
+// then serves the block -- and different where it spans a boundary, so that every vector (or every piece) looks its own up.
+struct Span { int lo, hi; };
+__device__ __forceinline__ Span chunk_span(const uint32_t* s_end, int cap, size_t first, size_t last) {
+    Span sp{0, 0};
+    for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)first, sp.lo); seg_step(s_end, h, (uint32_t)last, sp.hi); }
+    return sp;
+}
+
+// Fixed-order sums of N doubles per lane.  wave_sum: the wave64 butterfly (__shfl_xor, the same tree in every wave); every lane ends
+// with its wave's sums.  block_sum: the butterfly, then thread 0 adds the four wave sums in wave order and alone holds the block's sums.
+template <int N>
+__device__ __forceinline__ void wave_sum(double (&v)[N]) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+#pragma unroll
+        for (int c = 0; c < N; c++) v[c] += __shfl_xor(v[c], m);
+    }
+}
+template <int N>
+__device__ __forceinline__ void block_sum(double (&v)[N]) {
+    __shared__ double s_wave[4][N];
+    wave_sum(v);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < N; c++) s_wave[threadIdx.x >> 6][c] = v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < N; c++) v[c] = ((s_wave[0][c] + s_wave[1][c]) + s_wave[2][c]) + s_wave[3][c];
+    }
+}
+
+// ------------------------------------------------------------ the grouped update kernel
 template <typename Rule>
 __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                       float* __restrict__ s1, SegTable t, GroupArgs<typename Rule::Params> a,
@@ -247,47 +403,14 @@ __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, con
     __shared__ uint32_t s_end[OPT_MAX_SEGS];
     __shared__ int s_grp[OPT_MAX_SEGS];
     __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
-    int cap = 1;
-    while (cap < t.n_seg) cap <<= 1;
-    for (int k = threadIdx.x; k < cap; k += 256) {
-        s_end[k] = k < t.n_seg ? t.end[k] : 0xffffffffu;
-        s_grp[k] = k < t.n_seg ? t.group[k] : (t.n_seg == 0 ? 0 : OPT_FROZEN);      // no table (bdn_ema_update): one segment of group 0
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < OPT_MAX_GROUPS; k++) s_par[k] = a.g[k];
-        if (dev_scale) {                                     // the _ex entry points: grad_scale * *dev_scale, formed once per block
-            const float ds = *dev_scale;
-#pragma unroll
-            for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
-        }
-    }
+    const int cap = stage_table<Rule>(t.end, t.group, t.n_seg, s_end, s_grp, NoThird{}, a, dev_scale, s_par);
     __syncthreads();
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
-        int gid[OPT_VEC], seg[OPT_VEC] = {};
-        for (int h = cap >> 1; h > 0; h >>= 1) {             // the segment of each pass's first vector (clamped: a pass past the end is skipped below)
+        int gid[OPT_VEC];                                    // the group of each vector; no entry (-1) is OPT_FROZEN
+        pass_lookup(s_end, cap, b0, stride, n4, gid, [&](int s, size_t) { return s_grp[s]; });
 #pragma unroll
-            for (int u = 0; u < OPT_VEC; u++) {
-                const size_t first = b0 + u * stride;
-                seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), seg[u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < OPT_VEC; u++) {
-            const size_t first = b0 + u * stride, i = first + threadIdx.x;
-            int grp = OPT_FROZEN;
-            if (i < n4) {
-                const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
-                int s = seg[u];
-                if (!(s_end[s] > last)) {                    // the block's 256 vectors span a boundary (or lie behind the table): per lane
-                    s = 0;
-                    for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
-                }
-                if (s_end[s] > i) grp = s_grp[s];
-            }
-            gid[u] = (unsigned)grp < (unsigned)t.n_groups ? grp : OPT_FROZEN;
-        }
+        for (int u = 0; u < OPT_VEC; u++) gid[u] = (unsigned)gid[u] < (unsigned)t.n_groups ? gid[u] : OPT_FROZEN;
         float4 P[OPT_VEC], G[OPT_VEC], S0[OPT_VEC] = {}, S1[OPT_VEC] = {};
 #pragma unroll
         for (int u = 0; u < OPT_VEC; u++) {
@@ -318,15 +441,8 @@ __global__ void __launch_bounds__(256) grouped_kernel(float* __restrict__ p, con
 
 static int grouped_check(const char* what, const void* params, const void* grads, const void* s0, const void* s1, const uint32_t* seg_end,
                          const int32_t* seg_group, int n_seg, int n_groups, const float* lr, size_t n) {
-    if (!params || !grads || !seg_end || !seg_group || !lr) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
-    if (n_groups < 1 || n_groups > OPT_MAX_GROUPS)
-        BDN_FAIL(BDN_E_ARG, "%s: %d groups (1..%d: their hyperparameters travel in the kernel arguments)", what, n_groups, OPT_MAX_GROUPS);
-    if (n_seg < 1 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d segments (1..%d)", what, n_seg, OPT_MAX_SEGS);
-    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)s0 | (uintptr_t)s1) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
-    if (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3) BDN_FAIL(BDN_E_ARG, "%s: segment table must be 4-byte aligned", what);
-    if (n % 4 != 0 || n / 4 > 0xffffffffull)
-        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
-    return BDN_OK;
+    if (int rc = flat_check(what, {params, grads, lr}, {params, grads, s0, s1}, n)) return rc;
+    return table_check(what, "segment", nullptr, n_seg, {seg_end, seg_group}, &n_groups);
 }
 
 // The grouped entry points and their _ex forms share one launcher each: dev_scale == nullptr is the plain form (the kernel then never
@@ -465,14 +581,8 @@ struct RuleSwap {                                       // bits are moved, never
 };
 
 static int segments_check(const char* what, const void* a, const void* b, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, size_t n) {
-    if (!a || !b) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
-    if (n_seg < 0 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d segments (0..%d; 0: no table, every vector counts)", what, n_seg, OPT_MAX_SEGS);
-    if (n_seg > 0 && (!seg_end || !seg_group)) BDN_FAIL(BDN_E_ARG, "%s: null pointer (segment table of %d segments)", what, n_seg);
-    if (((uintptr_t)a | (uintptr_t)b) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
-    if (n_seg > 0 && (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3)) BDN_FAIL(BDN_E_ARG, "%s: segment table must be 4-byte aligned", what);
-    if (n % 4 != 0 || n / 4 > 0xffffffffull)
-        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
-    return BDN_OK;
+    if (int rc = flat_check(what, {a, b}, {a, b}, n)) return rc;
+    return table_check(what, "segment", "vector", n_seg, {seg_end, seg_group}, nullptr);
 }
 
 static int ema_params(const char* what, float weight, int copy, EmaParams& q) {
@@ -617,28 +727,20 @@ __global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float* __r
                                                                 double* __restrict__ part, size_t n4) {
     __shared__ uint32_t s_end[OPT_MAX_SEGS];
     __shared__ int s_grp[OPT_MAX_SEGS];
-    __shared__ double s_wave[4];
-    int cap = 1;
-    if (n_seg > 0) {
-        while (cap < n_seg) cap <<= 1;
-        for (int k = threadIdx.x; k < cap; k += 256) {
-            s_end[k] = k < n_seg ? seg_end[k] : 0xffffffffu;
-            s_grp[k] = k < n_seg ? seg_group[k] : OPT_FROZEN;
-        }
-        __syncthreads();
-    }
     const size_t c0 = (size_t)blockIdx.x * NORM_CHUNK;
     // A block's 4096 consecutive vectors almost always lie in one segment: one lookup of its first and of its last vector then serves the
     // block (a frozen block reads nothing at all); a block that spans a boundary looks every vector up.  The sums are the same either way.
+    int cap = 1;
     bool per_lane = false, whole = true;
-    if (n_seg > 0) {
+    if (n_seg > 0) {                                         // no table: nothing is staged or looked up, every vector counts
+        cap = stage_table(seg_end, seg_group, n_seg, s_end, s_grp, NoThird{});
+        __syncthreads();
         const size_t last = (c0 + NORM_CHUNK < n4 ? c0 + NORM_CHUNK : n4) - 1;
-        int s_lo = 0, s_hi = 0;
-        for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)c0, s_lo); seg_step(s_end, h, (uint32_t)last, s_hi); }
-        per_lane = s_lo != s_hi;
-        whole = s_end[s_lo] > last && s_grp[s_lo] != OPT_FROZEN;
+        const Span sp = chunk_span(s_end, cap, c0, last);
+        per_lane = sp.lo != sp.hi;
+        whole = s_end[sp.lo] > last && s_grp[sp.lo] != OPT_FROZEN;
     }
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (int r = 0; r < NORM_ROUNDS; r++) {
         bool take[OPT_VEC];
 #pragma unroll
@@ -658,13 +760,10 @@ __global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float* __r
             if (take[u]) G[u] = reinterpret_cast<const float4*>(g)[i];
         }
 #pragma unroll
-        for (int u = 0; u < OPT_VEC; u++) acc = sq_acc(acc, G[u]);           // a vector not taken adds +0.0: the sum is unchanged
+        for (int u = 0; u < OPT_VEC; u++) acc[0] = sq_acc(acc[0], G[u]);     // a vector not taken adds +0.0: the sum is unchanged
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+    block_sum(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
 }
 
 // the partials added in index order by thread 0 of a 256-thread block (staged through LDS 1024 at a time); the other threads return 0
@@ -703,15 +802,10 @@ extern "C" size_t bdn_grad_norm_workspace_bytes(size_t n) {
 
 extern "C" int bdn_grad_norm(const float* grads, const uint32_t* seg_end, const int32_t* seg_group, int n_seg, float grad_scale,
                              float max_norm, void* workspace, float* out, size_t n, void* stream) {
-    if (!grads || !workspace || !out) BDN_FAIL(BDN_E_ARG, "grad_norm: null pointer");
-    if (n_seg < 0 || n_seg > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "grad_norm: %d segments (0..%d; 0: no table, every element counts)", n_seg, OPT_MAX_SEGS);
-    if (n_seg > 0 && (!seg_end || !seg_group)) BDN_FAIL(BDN_E_ARG, "grad_norm: null pointer (segment table of %d segments)", n_seg);
-    if ((uintptr_t)grads & 15) BDN_FAIL(BDN_E_ARG, "grad_norm: buffers must be 16-byte aligned");
+    if (int rc = flat_check("grad_norm", {grads, workspace, out}, {grads}, n)) return rc;
+    if (int rc = table_check("grad_norm", "segment", "element", n_seg, {seg_end, seg_group}, nullptr)) return rc;
     if ((uintptr_t)workspace & 7) BDN_FAIL(BDN_E_ARG, "grad_norm: workspace must be 8-byte aligned");
     if ((uintptr_t)out & 3) BDN_FAIL(BDN_E_ARG, "grad_norm: out must be 4-byte aligned");
-    if (n_seg > 0 && (((uintptr_t)seg_end | (uintptr_t)seg_group) & 3)) BDN_FAIL(BDN_E_ARG, "grad_norm: segment table must be 4-byte aligned");
-    if (n % 4 != 0 || n / 4 > 0xffffffffull)
-        BDN_FAIL(BDN_E_ARG, "grad_norm: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", n);
     if (!(max_norm >= 0.f)) BDN_FAIL(BDN_E_ARG, "grad_norm: max_norm = %g must be >= 0 (+inf: measure only)", (double)max_norm);
     const size_t n4 = n / 4, nblk = norm_blocks(n4);
     if (nblk) {
@@ -806,22 +900,6 @@ template <bool MOM_> struct RuleLars {
     }
 };
 
-// the table's ends and groups into LDS, padded to a power of two (seg_step's contract), and the per-group parameters beside them
-template <typename P>
-__device__ __forceinline__ int lw_stage(const TenTable& t, const GroupArgs<P>& a, uint32_t* s_end, int* s_grp, P* s_par) {
-    int cap = 1;
-    while (cap < t.n_ten) cap <<= 1;
-    for (int k = threadIdx.x; k < cap; k += 256) {
-        s_end[k] = k < t.n_ten ? t.end[k] : 0xffffffffu;
-        s_grp[k] = k < t.n_ten ? t.group[k] : OPT_FROZEN;
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < OPT_MAX_GROUPS; k++) s_par[k] = a.g[k];
-    }
-    return cap;
-}
-
 // one vector of pass 1: the first `nvalid` elements enter the two sums (a pad is replaced by 0.0, whatever it holds)
 template <typename Rule>
 __device__ __forceinline__ void lw_sum_vec(const float4& P, const float4& G, float4& M, float4& V, int nvalid,
@@ -843,18 +921,11 @@ __global__ void __launch_bounds__(256) lw_partial_kernel(const float* __restrict
     __shared__ uint32_t s_end[OPT_MAX_SEGS];
     __shared__ int s_grp[OPT_MAX_SEGS];
     __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
-    __shared__ double s_wave[4][2];
-    const int cap = lw_stage(t, a, s_end, s_grp, s_par);
-    if (threadIdx.x == 0 && dev_scale) {
-        const float ds = *dev_scale;
-#pragma unroll
-        for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
-    }
+    const int cap = stage_table<Rule>(t.end, t.group, t.n_ten, s_end, s_grp, NoThird{}, a, dev_scale, s_par);
     __syncthreads();
     const size_t c0 = (size_t)blockIdx.x * LW_CHUNK, c1 = c0 + LW_CHUNK < n4 ? c0 + LW_CHUNK : n4;
-    int t_lo = 0, t_hi = 0;
-    for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)c0, t_lo); seg_step(s_end, h, (uint32_t)(c1 - 1), t_hi); }
-    if (t_hi > t.n_ten - 1) t_hi = t.n_ten - 1;              // vectors behind the table's end belong to no tensor
+    const Span sp = chunk_span(s_end, cap, c0, c1 - 1);
+    const int t_lo = sp.lo, t_hi = sp.hi > t.n_ten - 1 ? t.n_ten - 1 : sp.hi;    // vectors behind the table's end belong to no tensor
     const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p);
     const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
     float4* __restrict__ m4 = reinterpret_cast<float4*>(s0);
@@ -869,7 +940,7 @@ __global__ void __launch_bounds__(256) lw_partial_kernel(const float* __restrict
         if (!(lo < hi) || (unsigned)grp >= (unsigned)t.n_groups) return;         // block-uniform: nobody reaches the barrier below
         const typename Rule::Params q = s_par[grp];
         const int tail = (int)(t.len[k] - 4u * (uint32_t)(end - 1 - start));      // real elements of the tensor's last vector
-        double aw = 0.0, ax = 0.0;
+        double acc[2] = {0.0, 0.0};                          // {sum p^2, sum x^2}
         for (int r = 0; r < LW_ROUNDS; r++) {
             float4 P[OPT_VEC] = {}, G[OPT_VEC] = {}, M[OPT_VEC] = {}, V[OPT_VEC] = {};
 #pragma unroll
@@ -884,19 +955,15 @@ __global__ void __launch_bounds__(256) lw_partial_kernel(const float* __restrict
             for (int u = 0; u < OPT_VEC; u++) {
                 const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
                 if (i >= lo && i < hi) {
-                    lw_sum_vec<Rule>(P[u], G[u], M[u], V[u], i + 1 == end ? tail : 4, q, aw, ax);
+                    lw_sum_vec<Rule>(P[u], G[u], M[u], V[u], i + 1 == end ? tail : 4, q, acc[0], acc[1]);
                     if (Rule::LAMB) { m4[i] = M[u]; v4[i] = V[u]; }
                 }
             }
         }
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) { aw += __shfl_xor(aw, m); ax += __shfl_xor(ax, m); }
-        if ((threadIdx.x & 63) == 0) { s_wave[threadIdx.x >> 6][0] = aw; s_wave[threadIdx.x >> 6][1] = ax; }
-        __syncthreads();
+        block_sum(acc);
         if (threadIdx.x == 0) {
             double* o = part + 2 * ((size_t)blockIdx.x + k);
-            o[0] = ((s_wave[0][0] + s_wave[1][0]) + s_wave[2][0]) + s_wave[3][0];
-            o[1] = ((s_wave[0][1] + s_wave[1][1]) + s_wave[2][1]) + s_wave[3][1];
+            o[0] = acc[0]; o[1] = acc[1];
         }
         return;
     }
@@ -909,19 +976,18 @@ __global__ void __launch_bounds__(256) lw_partial_kernel(const float* __restrict
         if (!(lo < hi) || (unsigned)grp >= (unsigned)t.n_groups) continue;        // wave-uniform
         const typename Rule::Params q = s_par[grp];
         const int tail = (int)(t.len[k] - 4u * (uint32_t)(end - 1 - start));
-        double aw = 0.0, ax = 0.0;
+        double acc[2] = {0.0, 0.0};
         for (size_t i = lo + lane; i < hi; i += 64) {
             const float4 P = p4[i], G = g4[i];
             float4 M = {}, V = {};
             if (Rule::LAMB) { M = m4[i]; V = v4[i]; }
-            lw_sum_vec<Rule>(P, G, M, V, i + 1 == end ? tail : 4, q, aw, ax);
+            lw_sum_vec<Rule>(P, G, M, V, i + 1 == end ? tail : 4, q, acc[0], acc[1]);
             if (Rule::LAMB) { m4[i] = M; v4[i] = V; }
         }
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) { aw += __shfl_xor(aw, m); ax += __shfl_xor(ax, m); }
+        wave_sum(acc);                                       // per wave, no barrier: the waves hold different pieces
         if (lane == 0) {
             double* o = part + 2 * ((size_t)blockIdx.x + k);
-            o[0] = aw; o[1] = ax;
+            o[0] = acc[0]; o[1] = acc[1];
         }
     }
 }
@@ -943,16 +1009,15 @@ __global__ void __launch_bounds__(64) lw_finish_kernel(const double* __restrict_
     const size_t start = k ? t.end[k - 1] : 0;
     size_t end = t.end[k];
     if (end > n4) end = n4;
-    double sw = 0.0, sx = 0.0;
+    double acc[2] = {0.0, 0.0};                              // {sum p^2, sum x^2}
     if (start < end) {
         size_t b_hi = (end - 1) / LW_CHUNK;
         if (b_hi > nblk - 1) b_hi = nblk - 1;
-        for (size_t b = start / LW_CHUNK + lane; b <= b_hi; b += 64) { sw += part[2 * (b + k)]; sx += part[2 * (b + k) + 1]; }
+        for (size_t b = start / LW_CHUNK + lane; b <= b_hi; b += 64) { acc[0] += part[2 * (b + k)]; acc[1] += part[2 * (b + k) + 1]; }
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) { sw += __shfl_xor(sw, m); sx += __shfl_xor(sx, m); }
+    wave_sum(acc);
     if (lane != 0) return;
-    const double wn = sqrt(sw), xn = sqrt(sx);
+    const double wn = sqrt(acc[0]), xn = sqrt(acc[1]);
     double ratio = 1.0;
     if (wn > 0.0 && xn > 0.0)
         ratio = LAMB ? wn / xn : (double)a.trust_coef * wn / (xn + (double)a.wd[grp] * wn + (double)a.lars_eps);
@@ -969,37 +1034,16 @@ __global__ void __launch_bounds__(256) lw_apply_kernel(float* __restrict__ p, co
     __shared__ int s_grp[OPT_MAX_SEGS];
     __shared__ float s_ratio[OPT_MAX_SEGS];
     __shared__ typename Rule::Params s_par[OPT_MAX_GROUPS];
-    const int cap = lw_stage(t, a, s_end, s_grp, s_par);
-    for (int k = threadIdx.x; k < cap; k += 256) s_ratio[k] = k < t.n_ten ? trust[3 * k + 2] : 0.f;
-    if (threadIdx.x == 0 && dev_scale) {
-        const float ds = *dev_scale;
-#pragma unroll
-        for (int k = 0; k < OPT_MAX_GROUPS; k++) Rule::scale(s_par[k], ds);
-    }
+    const int cap = stage_table<Rule>(t.end, t.group, t.n_ten, s_end, s_grp,
+                                      [&](int k, bool in) { s_ratio[k] = in ? trust[3 * k + 2] : 0.f; }, a, dev_scale, s_par);
     __syncthreads();
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
-        int gid[OPT_VEC], ten[OPT_VEC], seg[OPT_VEC] = {};
-        for (int h = cap >> 1; h > 0; h >>= 1) {
-#pragma unroll
-            for (int u = 0; u < OPT_VEC; u++) {
-                const size_t first = b0 + u * stride;
-                seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), seg[u]);
-            }
-        }
+        int gid[OPT_VEC], ten[OPT_VEC];
+        pass_lookup(s_end, cap, b0, stride, n4, ten, EntryIndex{});
 #pragma unroll
         for (int u = 0; u < OPT_VEC; u++) {
-            const size_t first = b0 + u * stride, i = first + threadIdx.x;
-            int grp = OPT_FROZEN, s = seg[u];
-            if (i < n4) {
-                const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
-                if (!(s_end[s] > last)) {                    // the block's 256 vectors span a tensor boundary (or lie behind the table): per lane
-                    s = 0;
-                    for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
-                }
-                if (s_end[s] > i) grp = s_grp[s];
-            }
-            ten[u] = s;
+            const int grp = ten[u] >= 0 ? s_grp[ten[u]] : OPT_FROZEN;
             gid[u] = (unsigned)grp < (unsigned)t.n_groups ? grp : OPT_FROZEN;
         }
         float4 P[OPT_VEC], G[OPT_VEC] = {}, S0[OPT_VEC] = {}, S1[OPT_VEC] = {};
@@ -1032,19 +1076,11 @@ static int layerwise_check(const char* what, const void* params, const void* gra
                            const uint32_t* ten_len, const int32_t* ten_group, const int32_t* ten_adapt, int n_tensors, int n_groups,
                            const float* lr, const float* weight_decay, const float* dev_scale, float max_trust, const void* workspace,
                            const float* trust_out, size_t n) {
-    if (!params || !grads || !ten_end || !ten_len || !ten_group || !ten_adapt || !lr || !weight_decay || !workspace || !trust_out)
-        BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
-    if (n_groups < 1 || n_groups > OPT_MAX_GROUPS)
-        BDN_FAIL(BDN_E_ARG, "%s: %d groups (1..%d: their hyperparameters travel in the kernel arguments)", what, n_groups, OPT_MAX_GROUPS);
-    if (n_tensors < 1 || n_tensors > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d tensors (1..%d)", what, n_tensors, OPT_MAX_SEGS);
-    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)s0 | (uintptr_t)s1) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
-    if (((uintptr_t)ten_end | (uintptr_t)ten_len | (uintptr_t)ten_group | (uintptr_t)ten_adapt) & 3)
-        BDN_FAIL(BDN_E_ARG, "%s: tensor table must be 4-byte aligned", what);
+    if (int rc = flat_check(what, {params, grads, lr, weight_decay, workspace, trust_out}, {params, grads, s0, s1}, n)) return rc;
+    if (int rc = table_check(what, "tensor", nullptr, n_tensors, {ten_end, ten_len, ten_group, ten_adapt}, &n_groups)) return rc;
     if ((uintptr_t)dev_scale & 3) BDN_FAIL(BDN_E_ARG, "%s: dev_scale must be 4-byte aligned", what);
     if ((uintptr_t)workspace & 7) BDN_FAIL(BDN_E_ARG, "%s: workspace must be 8-byte aligned", what);
     if ((uintptr_t)trust_out & 3) BDN_FAIL(BDN_E_ARG, "%s: trust_out must be 4-byte aligned", what);
-    if (n % 4 != 0 || n / 4 > 0xffffffffull)
-        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
     if (!(max_trust >= 0.f)) BDN_FAIL(BDN_E_ARG, "%s: max_trust = %g must be >= 0 (0: no clamp)", what, (double)max_trust);
     return BDN_OK;
 }
@@ -1129,25 +1165,26 @@ extern "C" int bdn_lars_step(float* params, const float* grads, float* momentum_
 //              that order, one float32 add, none contracted.  A product that is exactly 0 leaves w's bits alone (-0.0 stays -0.0).
 // bdn_sam_restore is one launch of the same pass shape that copies saved back: bits are moved, never computed.  Both passes move whole
 // float4s; a pad element keeps its own bits throughout.
-__device__ __forceinline__ int sam_stage(const uint32_t* __restrict__ ten_end, const uint32_t* __restrict__ ten_len,
-                                         const int32_t* __restrict__ ten_group, int n_ten, uint32_t* s_end, int* s_grp, int* s_tail) {
-    int cap = 1;
-    while (cap < n_ten) cap <<= 1;
-    for (int k = threadIdx.x; k < cap; k += 256) {
-        const bool in = k < n_ten;
-        const uint32_t end = in ? ten_end[k] : 0xffffffffu, start = (in && k) ? ten_end[k - 1] : 0u;
-        s_end[k] = end;
-        s_grp[k] = in ? ten_group[k] : OPT_FROZEN;
-        s_tail[k] = (in && ten_len) ? (int)(ten_len[k] - 4u * (end - 1u - start)) : 4;   // real elements of the tensor's last vector
+// stage_table's third array: the real elements of each tensor's last vector (4 without ten_len: bdn_sam_restore moves whole vectors)
+struct SamTail {
+    const uint32_t* __restrict__ ten_end;
+    const uint32_t* __restrict__ ten_len;
+    int* s_tail;
+    __device__ __forceinline__ void operator()(int k, bool in) const {
+        s_tail[k] = (in && ten_len) ? (int)(ten_len[k] - 4u * (ten_end[k] - 1u - (k ? ten_end[k - 1] : 0u))) : 4;
     }
-    return cap;
-}
+};
 
 // real elements of vector i in tensor s: 0 when it is frozen or lies behind the table (the vector is then neither read nor written)
 __device__ __forceinline__ int sam_valid(const uint32_t* s_end, const int* s_grp, const int* s_tail, int s, size_t i) {
     if (!(s_end[s] > i) || s_grp[s] < 0) return 0;
     return i + 1 == s_end[s] ? s_tail[s] : 4;
 }
+struct SamValid {                                       // pass_lookup's entry: sam_valid of the vector's tensor
+    const uint32_t* s_end;
+    const int *s_grp, *s_tail;
+    __device__ __forceinline__ int operator()(int s, size_t i) const { return sam_valid(s_end, s_grp, s_tail, s, i); }
+};
 
 template <bool ADAPT>
 __device__ __forceinline__ double sam_acc(double acc, const float4& P, const float4& G, int nvalid) {
@@ -1164,14 +1201,12 @@ __global__ void __launch_bounds__(256) sam_partial_kernel(const float* __restric
                                                           const int32_t* __restrict__ ten_group, int n_ten, double* __restrict__ part, size_t n4) {
     __shared__ uint32_t s_end[OPT_MAX_SEGS];
     __shared__ int s_grp[OPT_MAX_SEGS], s_tail[OPT_MAX_SEGS];
-    __shared__ double s_wave[4];
-    const int cap = sam_stage(ten_end, ten_len, ten_group, n_ten, s_end, s_grp, s_tail);
+    const int cap = stage_table(ten_end, ten_group, n_ten, s_end, s_grp, SamTail{ten_end, ten_len, s_tail});
     __syncthreads();
     const size_t c0 = (size_t)blockIdx.x * NORM_CHUNK, last = (c0 + NORM_CHUNK < n4 ? c0 + NORM_CHUNK : n4) - 1;
-    int t_lo = 0, t_hi = 0;
-    for (int h = cap >> 1; h > 0; h >>= 1) { seg_step(s_end, h, (uint32_t)c0, t_lo); seg_step(s_end, h, (uint32_t)last, t_hi); }
-    const bool per_lane = t_lo != t_hi;                      // the chunk spans a tensor boundary: every vector looks its tensor up
-    double acc = 0.0;
+    const Span sp = chunk_span(s_end, cap, c0, last);
+    const bool per_lane = sp.lo != sp.hi;                    // the chunk spans a tensor boundary: every vector looks its tensor up
+    double acc[1] = {0.0};
     for (int r = 0; r < NORM_ROUNDS; r++) {
         int nv[OPT_VEC];
 #pragma unroll
@@ -1179,7 +1214,7 @@ __global__ void __launch_bounds__(256) sam_partial_kernel(const float* __restric
             const size_t i = c0 + (size_t)(r * OPT_VEC + u) * 256 + threadIdx.x;
             nv[u] = 0;
             if (i < n4) {
-                int s = t_lo;
+                int s = sp.lo;
                 if (per_lane) {
                     s = 0;
                     for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
@@ -1197,13 +1232,10 @@ __global__ void __launch_bounds__(256) sam_partial_kernel(const float* __restric
             }
         }
 #pragma unroll
-        for (int u = 0; u < OPT_VEC; u++) acc = sam_acc<ADAPT>(acc, P[u], G[u], nv[u]);      // a vector not taken adds +0.0
+        for (int u = 0; u < OPT_VEC; u++) acc[0] = sam_acc<ADAPT>(acc[0], P[u], G[u], nv[u]);        // a vector not taken adds +0.0
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+    block_sum(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
 }
 
 __global__ void __launch_bounds__(256) sam_finish_kernel(const double* __restrict__ part, size_t nblk, float rho, float eps,
@@ -1214,34 +1246,6 @@ __global__ void __launch_bounds__(256) sam_finish_kernel(const double* __restric
         const float norm32 = (float)sqrt(sum);
         out[0] = norm32;
         out[1] = rho / (norm32 + eps);
-    }
-}
-
-// nv[u]: the real elements of each of a pass's OPT_VEC vectors (lw_apply_kernel's lookup: one per 256 consecutive vectors where they lie
-// in one tensor, per lane otherwise)
-__device__ __forceinline__ void sam_pass_lookup(const uint32_t* s_end, const int* s_grp, const int* s_tail, int cap, size_t b0, size_t stride,
-                                                size_t n4, int (&nv)[OPT_VEC]) {
-    int seg[OPT_VEC] = {};
-    for (int h = cap >> 1; h > 0; h >>= 1) {
-#pragma unroll
-        for (int u = 0; u < OPT_VEC; u++) {
-            const size_t first = b0 + u * stride;
-            seg_step(s_end, h, (uint32_t)(first < n4 ? first : n4 - 1), seg[u]);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < OPT_VEC; u++) {
-        const size_t first = b0 + u * stride, i = first + threadIdx.x;
-        nv[u] = 0;
-        if (i < n4) {
-            const size_t last = first + 255 < n4 ? first + 255 : n4 - 1;
-            int s = seg[u];
-            if (!(s_end[s] > last)) {
-                s = 0;
-                for (int h = cap >> 1; h > 0; h >>= 1) seg_step(s_end, h, (uint32_t)i, s);
-            }
-            nv[u] = sam_valid(s_end, s_grp, s_tail, s, i);
-        }
     }
 }
 
@@ -1260,13 +1264,13 @@ __global__ void __launch_bounds__(256) sam_apply_kernel(float* __restrict__ p, f
                                                         size_t n4) {
     __shared__ uint32_t s_end[OPT_MAX_SEGS];
     __shared__ int s_grp[OPT_MAX_SEGS], s_tail[OPT_MAX_SEGS];
-    const int cap = sam_stage(ten_end, ten_len, ten_group, n_ten, s_end, s_grp, s_tail);
+    const int cap = stage_table(ten_end, ten_group, n_ten, s_end, s_grp, SamTail{ten_end, ten_len, s_tail});
     __syncthreads();
     const float scale = out[1];
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
-        int nv[OPT_VEC];
-        sam_pass_lookup(s_end, s_grp, s_tail, cap, b0, stride, n4, nv);
+        int nv[OPT_VEC];                                     // the real elements of each of the pass's vectors (<= 0: not touched)
+        pass_lookup(s_end, cap, b0, stride, n4, nv, SamValid{s_end, s_grp, s_tail});
         float4 P[OPT_VEC] = {}, G[OPT_VEC] = {};
 #pragma unroll
         for (int u = 0; u < OPT_VEC; u++) {
@@ -1294,12 +1298,12 @@ __global__ void __launch_bounds__(256) sam_restore_kernel(float* __restrict__ p,
                                                           size_t n4) {
     __shared__ uint32_t s_end[OPT_MAX_SEGS];
     __shared__ int s_grp[OPT_MAX_SEGS], s_tail[OPT_MAX_SEGS];
-    const int cap = sam_stage(ten_end, nullptr, ten_group, n_ten, s_end, s_grp, s_tail);
+    const int cap = stage_table(ten_end, ten_group, n_ten, s_end, s_grp, SamTail{ten_end, nullptr, s_tail});
     __syncthreads();
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t b0 = (size_t)blockIdx.x * 256; b0 < n4; b0 += stride * OPT_VEC) {
         int nv[OPT_VEC];
-        sam_pass_lookup(s_end, s_grp, s_tail, cap, b0, stride, n4, nv);
+        pass_lookup(s_end, cap, b0, stride, n4, nv, SamValid{s_end, s_grp, s_tail});
         float4 S[OPT_VEC] = {};
 #pragma unroll
         for (int u = 0; u < OPT_VEC; u++)
@@ -1312,14 +1316,9 @@ __global__ void __launch_bounds__(256) sam_restore_kernel(float* __restrict__ p,
 
 static int sam_check(const char* what, const void* params, const void* saved, const uint32_t* ten_end, const int32_t* ten_group, int n_tensors,
                      size_t n) {
-    if (!params || !saved || !ten_end || !ten_group) BDN_FAIL(BDN_E_ARG, "%s: null pointer", what);
+    if (int rc = flat_check(what, {params, saved}, {params, saved}, n)) return rc;
     if (params == saved) BDN_FAIL(BDN_E_ARG, "%s: params and saved are the same buffer", what);
-    if (n_tensors < 1 || n_tensors > OPT_MAX_SEGS) BDN_FAIL(BDN_E_ARG, "%s: %d tensors (1..%d)", what, n_tensors, OPT_MAX_SEGS);
-    if (((uintptr_t)params | (uintptr_t)saved) & 15) BDN_FAIL(BDN_E_ARG, "%s: buffers must be 16-byte aligned", what);
-    if (((uintptr_t)ten_end | (uintptr_t)ten_group) & 3) BDN_FAIL(BDN_E_ARG, "%s: tensor table must be 4-byte aligned", what);
-    if (n % 4 != 0 || n / 4 > 0xffffffffull)
-        BDN_FAIL(BDN_E_ARG, "%s: n = %zu must be a multiple of 4 (tensors padded to a float4) below 2^34", what, n);
-    return BDN_OK;
+    return table_check(what, "tensor", nullptr, n_tensors, {ten_end, ten_group}, nullptr);
 }
 
 extern "C" size_t bdn_sam_workspace_bytes(size_t n, int n_tensors) {

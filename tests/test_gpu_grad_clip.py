@@ -72,7 +72,8 @@ def test_accumulate_on_a_sub_range_leaves_the_rest_alone():
 def _table(n, variant, seed=0):
     """-> (device table or None, [(start, stop, id)] in elements or None).  'groups': ~11 segments cut at random float4 boundaries, ids
     cycling through three groups; 'frozen': the same with the first and the last segment frozen (a buffer too short for three segments:
-    one segment, frozen)."""
+    one segment, frozen); 'short': 'groups' with the middle segment frozen and the last end 5 vectors short of n / 4 (fewer where the last
+    segment is shorter than 6 vectors), so that the vectors behind it belong to no segment and do not count."""
     if variant == 'none':
         return None, None
     n4 = n // 4
@@ -83,6 +84,10 @@ def _table(n, variant, seed=0):
     ids = [j % 3 for j in range(len(ends))]
     if variant == 'frozen':
         ids[0] = ids[-1] = FROZEN
+    if variant == 'short':
+        ends[-1] = max(n4 - 5, (cuts[-1] if cuts else 0) + 1)
+        if len(ids) > 2:
+            ids[len(ids) // 2] = FROZEN
     starts = [0] + ends[:-1]
     tab = (guard.guard(torch.tensor(ends, dtype=torch.int64).to(torch.int32), dev), guard.guard(torch.tensor(ids, dtype=torch.int32), dev))
     return tab, [(4 * a, 4 * b, g) for a, b, g in zip(starts, ends, ids)]
@@ -110,7 +115,7 @@ def _check_coef(out, max_norm):
 
 # 4: one vector.  1020 / 1024: one vector short of, and exactly, one pass of a block's 256 lanes.  16388: one vector past the first partial
 # chunk (CHUNK floats per block).  4_000_004: 244 whole chunks and a ragged last block of 577 vectors.
-@pytest.mark.parametrize('variant', ['none', 'groups', 'frozen'])
+@pytest.mark.parametrize('variant', ['none', 'groups', 'frozen', 'short'])
 @pytest.mark.parametrize('n', [4, 1020, 1024, CHUNK + 4, 4_000_004])
 @guarded
 def test_norm_matches_float64_and_skips_frozen_segments(n, variant):
@@ -118,11 +123,13 @@ def test_norm_matches_float64_and_skips_frozen_segments(n, variant):
     gen = torch.Generator(device='cpu').manual_seed(n + len(variant))
     g = torch.randn(n, generator=gen) * 3.0
     tab, segs = _table(n, variant)
-    if variant == 'frozen':
+    if variant in ('frozen', 'short'):
         for a, b, gid in segs:
             if gid == FROZEN:
                 g[a:b] = float('nan')                         # a read of a frozen vector poisons the norm
-        assert bool(torch.isnan(g[:4]).all()) and bool(torch.isnan(g[-4:]).all())
+        g[segs[-1][1]:] = float('nan')                        # and so does a read behind the table's end ('short')
+        assert variant == 'short' or (bool(torch.isnan(g[:4]).all()) and bool(torch.isnan(g[-4:]).all()))
+        assert variant == 'frozen' or n < CHUNK or bool(torch.isnan(g[-20:]).all())
     gs = 0.5
     ref = G.norm(g, segs, gs)
     assert math.isfinite(ref)

@@ -29,6 +29,9 @@ _LAYOUTS = {
     'chunk_edges': dict(sizes=[4096, 4100, 12, 4092, 8192, 3], zero=2),
     'many_small': dict(sizes=[4 + (7 * i) % 9 for i in range(256)], zero=5),
     'frozen_groups': dict(sizes=_B, zero=2, groups=[0, -1, 1, 0, -1, 1, 0], adapt=[1, 1, 1, 0, 1, 1, 0], lrs=[0.01, 0.03], wds=[0.01, 0.0]),
+    # 4096 + 1024 + 256 + 5 vectors, five tensors (three pad entries in the staged table): a 16-vector one, one that ends 3 vectors into
+    # a block of 256, a frozen one, and the last end 5 vectors short of n / 4 -- those hold NaN and are neither read nor written
+    'short_table': dict(sizes=[61, 4042, 7997, 1199, 8195], groups=[0, 1, -1, 0, 1], lrs=[0.01, 0.03], wds=[0.01, 0.0], slack=20),
 }
 _RULES = {
     'lamb': dict(kind='lamb', wd=0.01),
@@ -42,13 +45,13 @@ _RULES = {
 class Lay:
     """A flat layout of `sizes` (every tensor padded to a float4) and its per-tensor table."""
 
-    def __init__(self, sizes, zero=None, groups=None, adapt=None, lrs=None, wds=None):
-        self.sizes, self.zero = list(sizes), zero
+    def __init__(self, sizes, zero=None, groups=None, adapt=None, lrs=None, wds=None, slack=0):
+        self.sizes, self.zero, self.slack = list(sizes), zero, slack       # slack: floats (whole vectors) behind the table's last end
         self.offs, off = [], 0
         for s in self.sizes:
             self.offs.append(off)
             off += (s + 3) // 4 * 4
-        self.n, self.nt = off, len(self.sizes)
+        self.n, self.nt = off + slack, len(self.sizes)
         self.ends = [(o + (s + 3) // 4 * 4) // 4 for o, s in zip(self.offs, self.sizes)]
         self.groups = list(groups) if groups is not None else [0] * self.nt
         self.adapt = list(adapt) if adapt is not None else [1] * self.nt
@@ -80,6 +83,7 @@ class Lay:
             grads[1][::5] = 0.0
         for t in [p] + grads:
             t[~self.real] = pad
+            t[self.n - self.slack:] = float('nan')            # behind the table: a read poisons a norm
         return p, grads
 
 
@@ -147,6 +151,10 @@ def _check_step(name, rule, lay, it, g, rec):
                    {k: lay.split(v) for k, v in s_out.items()}, trust, [lrs[max(gid, 0)] for gid in lay.groups],
                    [wds[max(gid, 0)] for gid in lay.groups], lay.adapt, lay.frozen, name, lay.zero)
     assert bool((p_out != p_in).any()), 'the step changed nothing'
+    if lay.slack:
+        tail = slice(lay.n - lay.slack, lay.n)
+        assert _same(p_out[tail], p_in[tail]) and all(_same(s_out[k][tail], s_in[k][tail]) for k in s_in), \
+            f'{name}: a vector behind the table\'s end was written'
 
 
 @pytest.mark.parametrize('layout', list(_LAYOUTS))

@@ -28,19 +28,22 @@ _LAYOUTS = {
     # more than three partial-sum blocks with a ragged last one; tensor boundaries inside chunks, one tensor over several chunks
     'blocks': dict(sizes=[5, CHUNK, 3, 2 * CHUNK + 6, 4099, 70, 9001], groups=[0, 0, 1, 0, -1, 2, 0]),
     'model': None,                                                            # BiDateNet(3, 2)'s real table, the first block frozen
+    # 4096 + 1024 + 256 + 5 vectors, five tensors (three pad entries in the staged table): a 16-vector one, one that ends 3 vectors into
+    # a block of 256, a frozen one, and the last end 5 vectors short of n / 4 -- those hold NaN and are neither read nor written
+    'short_table': dict(sizes=[61, 4042, 7997, 1199, 8195], groups=[0, 1, -1, 0, 1], slack=20),
 }
 
 
 class Lay:
     """A flat layout of `sizes` (every tensor padded to a float4) and its per-tensor table; group -1 is frozen."""
 
-    def __init__(self, sizes, groups=None):
-        self.sizes = list(sizes)
+    def __init__(self, sizes, groups=None, slack=0):
+        self.sizes, self.slack = list(sizes), slack                 # slack: floats (whole vectors) behind the table's last end
         self.offs, off = [], 0
         for s in self.sizes:
             self.offs.append(off)
             off += (s + 3) // 4 * 4
-        self.n, self.nt = off, len(self.sizes)
+        self.n, self.nt = off + slack, len(self.sizes)
         self.ends = [(o + (s + 3) // 4 * 4) // 4 for o, s in zip(self.offs, self.sizes)]
         self.groups = list(groups) if groups is not None else [0] * self.nt
         self.frozen = {i for i, g in enumerate(self.groups) if g < 0}
@@ -81,6 +84,7 @@ class Lay:
         g[::5] = 0.0
         for t in (p, g):
             t[~self.real] = pad
+            t[self.n - self.slack:] = float('nan')            # behind the table: a read poisons the norm
         return p, g
 
 
