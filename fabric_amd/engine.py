@@ -25,6 +25,7 @@ ENC_CH = (64, 128, 256, 512, 512)           # models/bidate_model.py:10-14
 DEC_OUT = (256, 128, 64, 64)                # models/bidate_model.py:16-19
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+INPUT_GRAD_MAX_BANDS = 16                   # bdn_conv3x3_dgrad_first: Cin_real <= 16 (csrc/dgrad_first.hip)
 
 
 def _round_up(v, m):
@@ -715,6 +716,15 @@ class BiDateEngine:
             return self.bwd_dtype
         return None
 
+    def check_input_grad(self):
+        """Refuse an input gradient the library cannot form: bdn_conv3x3_dgrad_first writes at most INPUT_GRAD_MAX_BANDS columns
+        (it returns BDN_E_SHAPE above that), and backward() reaches it only after the whole chain has been enqueued.  Asked at the
+        door instead -- by backward(dx=...) and by BiDateNet.forward when an image requires grad -- so that nothing is in flight."""
+        if self.n_channels > INPUT_GRAD_MAX_BANDS:
+            raise ValueError(f'fabric_amd: input-image gradients are limited to {INPUT_GRAD_MAX_BANDS} bands (the entry point '
+                             f'bdn_conv3x3_dgrad_first takes Cin_real <= {INPUT_GRAD_MAX_BANDS}); this model has {self.n_channels}. '
+                             f'Parameter gradients (backward without dx, inputs that do not require grad) work at every band count')
+
     def chain_end(self, need, dx=None):
         """Where backward's chain stops: None (it runs to the first layer: every parameter wanted, an input gradient wanted, or the
         first layer itself trainable), 'outc' (no 3x3 layer wanted), or the name of the LAST layer, in backward's order d4b ... d1a,
@@ -768,6 +778,8 @@ class BiDateEngine:
         keys once at the end, so that every gradient bucket is still released exactly once."""
         if bn_mode not in ('batch', 'running'):
             raise ValueError(f"bn_mode must be 'batch' or 'running', got {bn_mode!r}")
+        if dx is not None:
+            self.check_input_grad()                  # before the first launch: nothing of this backward is in flight when it raises
         frozen = bn_mode == 'running'
         B, H, W = ws.B, ws.H, ws.W
         dev = dlogits.device

@@ -50,6 +50,8 @@ class _BiDateFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, x_d1, x_d2, *params):
         eng = module.engine()
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            eng.check_input_grad()            # ValueError above 16 bands, here and not from the middle of backward
         P = dict(module.state_dict(keep_vars=True))
         training = module.training
         logits, ws = eng.forward(x_d1.detach(), x_d2.detach(), {k: v.detach() for k, v in P.items()}, training)

@@ -8,7 +8,8 @@ walk one training step / eval forward of BiDateNet layer by layer (fabric_amd/en
 test can require that every instantiation of the real step has a row; the GPU test records the launches of real steps and checks that
 they equal this enumeration.
 
-Shapes are ragged (H % 8 != 0, W % 16 != 0) wherever the plan allows it.  A plain module (like tests/gpu_util.py), not a conftest.
+ROWS is the table of the 13(16)-band model; WIDE_ROWS adds the first layer of models of 17 to 64 bands (padded to 32, 48 or 64 channels),
+ALL_ROWS is both.  Shapes are ragged (H % 8 != 0, W % 16 != 0) wherever the plan allows it.  A plain module (like tests/gpu_util.py), not a conftest.
 """
 from collections import namedtuple
 
@@ -29,11 +30,15 @@ DTYPE = {'fp32': BDN_F32, 'bf16': BDN_BF16, 'bf16x3': BDN_BF16X3, 'bf16x2': BDN_
 #   eval / eval_pair / eval_cls   bdn_conv3x3_eval / _eval_pair (N = B pairs) / _eval_cls
 #   wgrad      bdn_conv3x3_wgrad_ex at default flags (bf16x3 / bf16x2: split operands); `lanes` = split lanes of its reduction
 #   wgrad_bnbwd  bdn_conv3x3_wgrad_bnbwd (first layer, C0 = 16, Cout = 64)
-Row = namedtuple('Row', 'op prec N H W C0 C1 Cout ipg bnrelu stats inst lanes')
+# creal (WIDE_ROWS): the layer's real input channels when the operand is padded to C0 -- the first layer of a model of creal bands.  The
+#   filter then holds creal channels and goes through the packers with Cin = creal, Cin_pad = C0 and no data-gradient image, the operand's
+#   padded channels are exact zeros, the float64 reference convolves the creal channels, and a wgrad row writes Cout * creal * 9 floats.
+#   None = C0 (every row of ROWS)
+Row = namedtuple('Row', 'op prec N H W C0 C1 Cout ipg bnrelu stats inst lanes creal', defaults=(None,))
 
 
-def _r(op, prec, N, H, W, C0, C1, Cout, ipg, inst, bnrelu=False, stats=True, lanes=None):
-    return Row(op, prec, N, H, W, C0, C1, Cout, ipg, bnrelu, stats, inst, lanes)
+def _r(op, prec, N, H, W, C0, C1, Cout, ipg, inst, bnrelu=False, stats=True, lanes=None, creal=None):
+    return Row(op, prec, N, H, W, C0, C1, Cout, ipg, bnrelu, stats, inst, lanes, creal)
 
 
 def _ck(t, cfg, to, bb=False, ev=False, x3=0, xf=False):
@@ -152,9 +157,49 @@ ROWS = [
 ]
 
 
+# ---- the first layer of models of 17 to 64 bands (cp = 32, 48, 64): 16-channel chunks with more than one chunk (bf16, the split operand),
+# the single chunk of 32 float channels, three 16-channel float chunks, the split-K GEMMs at C0 = 32 / 48 and on the doubled operand, and at
+# 64 padded channels the trunk's kernels on an operand whose real channels end inside the chunk.  Every row carries creal:
+# (creal, C0) = (17, 32), (33, 48), (50, 64), and (64, 64) = a 64-band model, whose first layer has no data-gradient image either.
+# The same smallest ragged shape as the 16-band rows.  A list of its own: the 2 to 4 GB twins of tests/bigtensor.py are made of ROWS.
+WIDE_PAIRS = ((17, 32), (33, 48), (50, 64), (64, 64))
+K1632 = '32,16,16,1,64,4,1,false'                         # bf16: 16-channel chunks, two or three of them
+_WIDE_CONV = {                                            # C0 -> tile configuration of the 4 x 29 x 45 launch
+    'bf16': {32: K1632, 48: K1632, 64: K1616_ONE},
+    'fp32': {32: K1616_ONE, 48: '64,16,16,1,64,4,1,false', 64: K1616},
+    'x3': {32: '32,8,16,1,64,2,2,false', 48: '32,8,16,1,64,2,2,false', 64: K816_64},
+}
+_WIDE_WGRAD = {                                           # C0 -> (GEMM, split lanes of its reduction)
+    'bf16': {32: ('wgrad_kernel<bf16,8,16,1,true>', 16), 48: ('wgrad_kernel<bf16,8,16,1,false>', 16), 64: ('wgrad7_kernel<false>', 8)},
+    'fp32': {32: ('wgrad_kernel<f32,8,16,1,true>', 16), 48: ('wgrad_kernel<f32,8,16,1,false>', 16), 64: ('wgrad_kernel<f32,8,16,1,false>', 8)},
+    'bf16x3': {32: ('wgrad7_kernel<false>+wgrad_x3_combine_kernel', 4), 48: ('wgrad_kernel<bf16,8,16,1,false>+wgrad_x3_combine_kernel', 4),
+               64: ('wgrad7x_kernel<3>', 8)},
+    'bf16x2': {32: ('wgrad7_kernel<false>+wgrad_x3_combine_kernel', 4), 48: ('wgrad_kernel<bf16,8,16,1,false>+wgrad_x3_combine_kernel', 4),
+               64: ('wgrad7x_kernel<2>', 8)},
+}
+
+
+def _wide_rows():
+    out = []
+    for creal, C0 in WIDE_PAIRS:
+        for p, t in (('bf16', BF), ('fp32', F32)):
+            out.append(_r('fwd', p, 4, 29, 45, C0, 0, 64, 2, _ck(t, _WIDE_CONV[p][C0], t), creal=creal))
+            out.append(_r('eval', p, 4, 29, 45, C0, 0, 64, 1, _ck(t, _WIDE_CONV[p][C0], t, ev=True), creal=creal))
+        for p, terms in (('bf16x3', 3), ('bf16x2', 2)):
+            out.append(_r('x3', p, 4, 29, 45, C0, 0, 64, 2, _ck(BF, _WIDE_CONV['x3'][C0], F32, x3=terms), creal=creal))
+        for p in ('bf16', 'fp32', 'bf16x3', 'bf16x2'):
+            g, lanes = _WIDE_WGRAD[p][C0]
+            out.append(_r('wgrad', p, 4, 29, 45, C0, 0, 64, 2, g, lanes=lanes, creal=creal))
+    return out
+
+
+WIDE_ROWS = _wide_rows()
+ALL_ROWS = ROWS + WIDE_ROWS
+
+
 def row_id(r):
     return (f'{r.op}-{r.prec}-{r.N}x{r.H}x{r.W}-{r.C0}' + (f'+{r.C1}' if r.C1 else '') + f'-{r.Cout}-g{r.ipg}'
-            + ('-bnrelu' if r.bnrelu else '') + ('' if r.stats else '-nostats'))
+            + ('-bnrelu' if r.bnrelu else '') + ('' if r.stats else '-nostats') + (f'-real{r.creal}' if r.creal else ''))
 
 
 # ---- statistics reductions on synthetic partials: (rows per group, G).  bdn_bn_finalize / bdn_bn_bwd_finalize take the one-launch path up
@@ -230,8 +275,8 @@ def reduce_lanes(r):
 
 def covered():
     """Every instantiation some row selects, with the wgrad rows' reductions."""
-    out = {i for r in ROWS for i in r.inst.split('+')}
-    out |= {f'wgrad_reduce_kernel<{r.lanes}>' for r in ROWS if r.lanes}
+    out = {i for r in ALL_ROWS for i in r.inst.split('+')}
+    out |= {f'wgrad_reduce_kernel<{r.lanes}>' for r in ALL_ROWS if r.lanes}
     return out
 
 

@@ -9,9 +9,14 @@ reference by ONE stage's rounding, a gradient by backward rounding only, and a f
 
 Shapes (B, c, H, W): s32 (2, 3, 32, 32) level-5 map 2x2; s40x72 (3, 13, 40, 72) the 13 -> 16 band padding, non-square, maps of 8x8 and below
 that folds_bn_bwd refuses beside larger ones; s90 (2, 13, 90, 90) odd maps at 45 and 11 (pad_to, floor pooling).
+Wide inputs: w17 (2, 17, 32, 32), w48 (3, 48, 40, 24), w50 (2, 50, 16, 48): the first layer padded to 32, 48 and 64 channels -- the
+multi-chunk / single-float-chunk forward kernels, and in backward the route the 'nodx' case does NOT take: first_wgrad_dtype is None
+(bdn_conv3x3_wgrad_bnbwd refuses C0 != 16), so the first layer's BatchNorm backward is a pass of its own (bf16x3: it leaves dz split) and
+its weight gradient the generic GEMM with Cin_real < C0 (asserted from the recorded calls).  No dx there: it is refused above 16 bands.
 Matrix: every precision x the three shapes with 'product', batch statistics and dx; per precision 'absdiff' (s40x72), bn_mode='running'
 (s32), no dx = the first_wgrad_fused path (s90), fold_bn_bwd = () (s40x72), wgrad_stream=False (s32), and Gaussian dlogits with exact zeros
-(s40x72).  Everywhere else dlogits is the float64 Tversky(0.1, 0.9) gradient at the engine's own logits, cast to float32.
+(s40x72); 'base' without dx on the three wide shapes and bn_mode='running' on w17.  Everywhere else dlogits is the float64
+Tversky(0.1, 0.9) gradient at the engine's own logits, cast to float32.
 
 Asserted, forward (test_forward_stages), per stage:
   conv        every element |z_engine - z_ref| <= u*|z_ref| + c*A, u = 2^-8 (bf16 storage) / 2^-23 (float32), A = conv(|a|,|w|) + |b|,
@@ -44,6 +49,15 @@ Measured on an MI355X, largest over the cases of a setting (the case, the stage 
     bf16x3       1.52e-5  1.48e-5  1.91e-5  1.91e-5  1.36e-5  1.91e-5  1.48e-5  1.52e-5  1.43e-5
     bf16x3-fast  6.47e-3  6.51e-3  6.63e-3  7.68e-3  9.24e-3  6.63e-3  6.51e-3  6.47e-3  6.60e-3
     bf16         1.10e-2  9.62e-3  1.25e-2  1.32e-2  1.19e-2  1.25e-2  1.03e-2  1.10e-2  9.57e-3
+  wide inputs, same bounds (the per-stage rounding does not depend on the band count; C_CEILING is that of the shortest reduction), worst
+  relative L2 (base-w17 / base-w48 / base-w50 / running-w17), then the largest 1 - cosine, |gain - 1| and conv c over the four:
+    fp32         2.71e-6  2.56e-6  3.21e-6  1.44e-6    5.08e-12 (base-w50)     8.50e-7 (base-w50)     4.60e-7 (running-w17, d1a)
+    bf16x3       1.61e-5  1.51e-5  1.76e-5  1.15e-5    1.54e-10 (base-w50)     3.27e-6 (running-w17)  9.39e-7 (base-w17, d4a)
+    bf16x3-fast  6.16e-3  6.63e-3  6.86e-3  9.92e-3    4.86e-5 (running-w17)   2.34e-3 (running-w17)  9.39e-7 (the bf16x3 forward)
+    bf16         9.16e-3  1.02e-2  1.25e-2  7.95e-3    7.75e-5 (base-w50)      2.14e-3 (base-w17)     1.55e-8 (base-w48, d4a)
+  (three of these exceed the largest value of the 3- and 13-band cases above -- fp32 |gain - 1| 8.50e-7 against 8.43e-7, bf16x3-fast
+  relative L2 9.92e-3 against 9.24e-3 and 1 - cosine 4.86e-5 against 4.26e-5 -- by less than a tenth of the 2 x margin; the constants in
+  tests/forced_ref.py are those of the narrow cases, unchanged)
 The bf16 bound (2.64e-2 / 1.65e-4 / 8.8e-3) sits under the 0.8 / 0.85 of tests/test_gpu_autograd.py by a factor of 30, fp32 (1.04e-5) under
 2e-2, bf16x3 (3.8e-5) and bf16x3-fast (1.85e-2) under 6e-2, and rejects the four wiring mutations of tests/test_forced_ref_cpu.py -- the
 1.02 scaling through |gain - 1| (2.0e-2 against 8.8e-3): relative L2 alone, at 2.64e-2, would have admitted it.
@@ -62,7 +76,9 @@ from oracle import filler
 from tests import forced_ref as R
 
 pytestmark = pytest.mark.gpu
-SHAPES = {'s32': (2, 3, 32, 32), 's40x72': (3, 13, 40, 72), 's90': (2, 13, 90, 90)}
+SHAPES = {'s32': (2, 3, 32, 32), 's40x72': (3, 13, 40, 72), 's90': (2, 13, 90, 90),
+          'w17': (2, 17, 32, 32), 'w48': (3, 48, 40, 24), 'w50': (2, 50, 16, 48)}          # first layer padded to 32, 48 and 64 channels
+WIDE = ('w17', 'w48', 'w50')
 # variant -> (shape, fusion, bn_mode, dlogits, dx, engine attributes, wgrad_stream)
 VARIANTS = {
     'base-s32': ('s32', 'product', 'batch', 'tversky', True, {}, True),
@@ -74,6 +90,11 @@ VARIANTS = {
     'nofold': ('s40x72', 'product', 'batch', 'tversky', True, {'fold_bn_bwd': ()}, True),
     'nostream': ('s32', 'product', 'batch', 'tversky', True, {}, False),
     'gauss': ('s40x72', 'product', 'batch', 'gauss', True, {}, True),
+    # above 16 bands: no input gradient (refused at the door), the first layer on bn_bwd + the generic weight-gradient GEMM
+    'base-w17': ('w17', 'product', 'batch', 'tversky', False, {}, True),
+    'base-w48': ('w48', 'product', 'batch', 'tversky', False, {}, True),
+    'base-w50': ('w50', 'product', 'batch', 'tversky', False, {}, True),
+    'running-w17': ('w17', 'product', 'running', 'tversky', False, {}, True),
 }
 FORWARDS = sorted({v[:3] for v in VARIANTS.values()})
 
@@ -150,7 +171,7 @@ def test_forward_stages(prec, shape, fusion, bn_mode):
 
 @pytest.mark.parametrize('variant', list(VARIANTS))
 @pytest.mark.parametrize('prec', R.PRECISIONS)
-def test_backward(prec, variant):
+def test_backward(prec, variant, monkeypatch):
     shape, fusion, bn_mode, dl_kind, want_dx, attrs, stream = VARIANTS[variant]
     ref = _reference(prec, shape, fusion, bn_mode, dl_kind)
     model, eng, P = _engine(prec, shape, fusion, attrs)
@@ -165,11 +186,30 @@ def test_backward(prec, variant):
         eng.fold_bn_bwd = ('e1b', 'd4a')
         assert eng.folds_bn_bwd(by['e1b'], h, w) and eng.folds_bn_bwd(by['d4a'], h, w), 'the default does not fold at this shape'
         eng.fold_bn_bwd = ()
+    seen = []
+    if shape in WIDE:
+        # the opposite branch of 'nodx': the fused first-layer weight gradient refuses more than 16 padded channels, so the route audited
+        # here is the BatchNorm backward as a pass of its own and bdn_conv3x3_wgrad_ex on the cp-channel operand with c real columns
+        assert not want_dx and eng.cp == (c + 15) // 16 * 16 > 16
+        assert eng.first_wgrad_dtype(2 * b, h, w, b) is None, 'the fused first weight gradient is taken above 16 padded channels'
+        from fabric_amd import engine as engine_mod
+        real = engine_mod.call
+        monkeypatch.setattr(engine_mod, 'call', lambda name, *a: (seen.append((name, a)), real(name, *a))[1])
     grads = {k: torch.full_like(p, float('nan')) for k, p in model.named_parameters()}
     dx = (torch.full_like(x1, float('nan')), torch.full_like(x2, float('nan'))) if want_dx else None
     dl = ref['dlogits']
     eng.backward(ws, dl.cuda(), P, grads, dx=dx, bn_mode=bn_mode, wgrad_stream=stream)
     torch.cuda.synchronize()
+    if shape in WIDE:
+        names = [n for n, _ in seen]
+        assert 'bdn_conv3x3_wgrad_bnbwd' not in names and 'bdn_conv3x3_dgrad_first' not in names
+        # (dtype, dz, Cout, in0, C0, in1, C1, in_mode, in_bn, ipg, partial, dw, Cin_real, N, H, W, flags, stream)
+        first = [a for n, a in seen if n == 'bdn_conv3x3_wgrad_ex' and a[11] == grads['inc.conv.conv.0.weight'].data_ptr()]
+        assert len(first) == 1 and (first[0][4], first[0][12], first[0][13:16]) == (eng.cp, c, (2 * b, h, w)), first
+        if eng.x3:     # dz of the first layer leaves its BatchNorm backward split (hi | lo): no float32 dz, no split pass
+            kind, at = ('bdn_bn_bwd_apply_frozen', 6) if bn_mode == 'running' else ('bdn_bn_bwd_apply_split', 5)      # index of (N, H, W, C)
+            assert [a for n, a in seen if n == kind and tuple(a[at:at + 4]) == (2 * b, h, w, 64)], 'no split BatchNorm backward at full size'
+            assert not [a for n, a in seen if n == 'bdn_split_pack' and tuple(a[-4:-1]) == (2 * b, h, w)]
     got = dict(grads)
     if want_dx:
         got['dx1'], got['dx2'] = dx

@@ -202,3 +202,47 @@ def test_frozen_dz_is_scale_times_masked_gradient(dtype, fused):
         ref_db = torch.where(mask, gf, torch.zeros_like(gf)).double().sum((0, 1, 2))
         assert_close('dbeta', db.cpu(), ref_db.cpu(), 1e-5)
         assert torch.equal(dbias, bn[0, 2] * db)
+
+
+# ------------------------------------------------------------------ above 16 bands: refused at the door
+@pytest.mark.parametrize('prec', ['bf16', 'fp32', 'bf16x3'])
+def test_input_gradient_above_16_bands_is_refused_before_any_launch(prec):
+    """A 17-band model: backward(dx=...) raises ValueError naming the limit and bdn_conv3x3_dgrad_first before its first launch -- the
+    NaN-filled grads and dx hold only NaN afterwards -- and so does the module when an image requires grad.  The engine is left as it
+    was: the next forward + backward without dx gives logits and all 74 gradients bit-equal to those of a freshly built twin."""
+    from fabric_amd import BiDateNet
+    from oracle import filler
+    b, c, s = 2, 17, 32
+    x1, x2, _ = filler.make_inputs(b, c, s, seed=0, different_dates=True)
+    x1, x2 = torch.from_numpy(x1).cuda(), torch.from_numpy(x2).cuda()
+    dl = torch.from_numpy(np.random.default_rng(1).standard_normal((b, 2, s, s)).astype(np.float32) * 1e-3).cuda()
+
+    def build():
+        model = filler.fill_module(BiDateNet(c, 2, precision=prec)).cuda().train()
+        return model, model.engine(), {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
+
+    def step(model, eng, P):
+        logits, ws = eng.forward(x1, x2, P, training=True)
+        grads = {k: torch.full_like(p, float('nan')) for k, p in model.named_parameters()}
+        eng.backward(ws, dl, P, grads)
+        torch.cuda.synchronize()
+        return logits, grads
+
+    model, eng, P = build()
+    logits, ws = eng.forward(x1, x2, P, training=True)
+    grads = {k: torch.full_like(p, float('nan')) for k, p in model.named_parameters()}
+    dx = (torch.full_like(x1, float('nan')), torch.full_like(x2, float('nan')))
+    with pytest.raises(ValueError, match=r'limited to 16 bands.*bdn_conv3x3_dgrad_first'):
+        eng.backward(ws, dl, P, grads, dx=dx)
+    torch.cuda.synchronize()
+    assert len(grads) == 74 and all(bool(torch.isnan(g).all()) for g in grads.values())
+    assert bool(torch.isnan(dx[0]).all()) and bool(torch.isnan(dx[1]).all())
+    with pytest.raises(ValueError, match='bdn_conv3x3_dgrad_first'):
+        model(x1.clone().requires_grad_(True), x2)
+    got_logits, got = step(model, eng, P)
+    twin_logits, twin = step(*build())
+    assert torch.equal(got_logits, twin_logits)
+    assert set(got) == set(twin) and len(got) == 74
+    for k in got:
+        assert torch.isfinite(got[k]).all(), k
+        assert torch.equal(got[k], twin[k]), k

@@ -10,9 +10,16 @@ Element-wise bars:
   float32 outputs   |got - ref| <= 2e-5 max|ref|               (the existing fp32 bar)
   bf16x3 / bf16x2   |got - ref| <= 1e-4 max|ref|               (the existing bar of the split-product kernels)
 LAUNCH_SHAPES_REPORT=<file> appends each row's worst error (in units of its bar) to that file.
+
+Wide rows (launch_cases.WIDE_ROWS, r.creal set): the first layer of a model of creal bands padded to C0 = 32, 48 or 64 channels.  The
+filter holds creal channels and is packed with Cin = creal, Cin_pad = C0 and no data-gradient image, through bdn_pack_weights AND through
+the one-record bdn_pack_weights_multi descriptor the engine uses (bit-equal; bf16 / fp32: equal to the rounded filter with zero columns);
+the operand's padded channels are exact zeros; the reference convolves the creal channels; a weight gradient lands in a guard-banded
+buffer of exactly Cout * creal * 9 floats.  They are held to the same bars as their 16-band and 64-channel neighbours.
 """
 import json
 import os
+import struct
 from types import SimpleNamespace
 
 import numpy as np
@@ -21,9 +28,9 @@ import torch
 import torch.nn.functional as F
 
 from fabric_amd import _lib
-from fabric_amd._lib import BDN_BF16, BDN_BF16X3, IN_BNRELU, IN_PLAIN
+from fabric_amd._lib import BDN_BF16, BDN_BF16X3, BDN_F32, IN_BNRELU, IN_PLAIN
 from tests import launch_cases as lc
-from tests.gpu_util import assert_masked, bn_table, bnrelu_ref, dev, from_nhwc, pack_w, preact, rnd, st, to_nhwc
+from tests.gpu_util import assert_masked, bn_table, bnrelu_ref, dev, frag_to_dense, from_nhwc, pack_w, preact, rnd, st, to_nhwc
 from tests import guard
 from tests.guard import guarded
 
@@ -66,11 +73,48 @@ def _rid(r):
 
 
 def _rows(*ops):
-    return [r for r in lc.ROWS if r.op in ops]
+    return [r for r in lc.ALL_ROWS if r.op in ops]
 
 
 def _assert_variant(r):
     assert lc.instantiation(r) == r.inst, f'{_rid(r)} selects {lc.instantiation(r)}'
+
+
+def _padded(x_nchw, C0):
+    """[N, creal, H, W] -> [N, C0, H, W]: the padded channels are exact zeros."""
+    return F.pad(x_nchw, (0, 0, 0, 0, 0, C0 - x_nchw.shape[1]))
+
+
+def _assert_zero_padding(r, t_nhwc, halves=1):
+    """The padded channels of a wide row's device operand ([.., halves * C0]: the split operand has a hi and a lo half) are exact zeros."""
+    for h in range(halves):
+        pad = t_nhwc[..., h * r.C0 + r.creal:(h + 1) * r.C0]
+        assert pad.numel() == 0 or bool((pad == 0).all()), f'{_rid(r)}: padded operand channels are not zero'
+
+
+def pack_first(prec, w, C0):
+    """Forward filter image of a first layer: w [Cout, creal, 3, 3] packed with Cin = creal, Cin_pad = C0 and wd = NULL, through
+    bdn_pack_weights and through a one-record bdn_pack_weights_multi descriptor (the engine's form: its irregular branch whenever
+    creal < C0 or C0 is no multiple of 64, its LDS tile kernel at creal = C0 = 64 in bf16).  The two images must be equal bit for bit and
+    written in full; bf16 / fp32: also equal to the rounded filter with zero columns above creal.  Returns the descriptor form's image."""
+    Cout, creal = w.shape[:2]
+    x3 = prec in ('bf16x3', 'bf16x2')
+    dt = BDN_BF16X3 if x3 else (BDN_BF16 if prec == 'bf16' else BDN_F32)
+    td = torch.float32 if prec == 'fp32' else torch.bfloat16
+    wdev = dev(w)
+    one, multi = (guard.empty(Cout, 9, (3 if x3 else 1) * C0, dtype=td) for _ in range(2))
+    _lib.call('bdn_pack_weights', dt, wdev.data_ptr(), one.data_ptr(), None, Cout, creal, C0, st())
+    desc = guard.guard(torch.frombuffer(bytearray(struct.pack('<QQQiiii', wdev.data_ptr(), multi.data_ptr(), 0, Cout, creal, C0, 0)),
+                                        dtype=torch.uint8))
+    _lib.call('bdn_pack_weights_multi', dt, desc.data_ptr(), 1, st())
+    torch.cuda.synchronize()
+    assert torch.isfinite(multi.float()).all() and torch.isfinite(one.float()).all(), f'pack {prec} {creal}->{C0}: image not written in full'
+    assert torch.equal(one.view(torch.uint8), multi.view(torch.uint8)), f'pack {prec} {creal}->{C0}: the two packers differ'
+    if not x3:
+        dense = frag_to_dense(prec, multi, Cout, C0)                     # [Cout][9][C0]
+        want = _padded(rnd(prec, w), C0).reshape(Cout, C0, 9).permute(0, 2, 1)
+        assert torch.equal(dense, want), f'pack {prec} {creal}->{C0}: image is not the rounded filter with zero columns'
+    return multi
 
 
 def _grp(t, G):
@@ -127,21 +171,22 @@ def forward_case(r):
     """Inputs and float64 reference of a 'fwd' row (host tensors only)."""
     N, H, W, C0, C1, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg, r.prec
     G = N // ipg
-    x0 = rnd(p, _rand((N, C0, H, W), 1))
+    cr = r.creal or C0                                   # wide rows: the filter and the reference on the real channels only
+    x0 = rnd(p, _rand((N, cr, H, W), 1))
     x1 = rnd(p, _rand((N, C1, H, W), 2)) if C1 else None
-    w = rnd(p, _rand((Cout, C0 + C1, 3, 3), 3, (2.0 / (9 * (C0 + C1))) ** 0.5))
+    w = rnd(p, _rand((Cout, cr + C1, 3, 3), 3, (2.0 / (9 * (cr + C1))) ** 0.5))
     b = _rand((Cout,), 4, 0.1)
     bn_in = bn_table(G, C0, 5) if r.bnrelu else None
     a0 = bnrelu_ref(p, x0, bn_in, ipg) if r.bnrelu else x0
     a = torch.cat([a0, x1], 1) if C1 else a0
     ref = F.conv2d(a.double(), w.double(), b.double(), padding=1)
-    return SimpleNamespace(x0=x0, x1=x1, w=w, b=b, bn_in=bn_in, ref=ref)
+    return SimpleNamespace(x0=_padded(x0, C0), x1=x1, w=w, b=b, bn_in=bn_in, ref=ref)
 
 
 def forward_launch(r, c, d0, d1, out, stats, N=None, ipg=None):
     """bdn_conv3x3 of a 'fwd' row on device operands (N / ipg: those of the launch when they are not the row's)."""
     N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
-    wf, _ = pack_w(r.prec, c.w, r.C0 + r.C1)
+    wf = pack_first(r.prec, c.w, r.C0) if r.creal else pack_w(r.prec, c.w, r.C0 + r.C1)[0]
     dbn, db = (dev(c.bn_in) if r.bnrelu else None), dev(c.b)
     _lib.call('bdn_conv3x3', lc.DTYPE[r.prec], d0.data_ptr(), r.C0, d1.data_ptr() if r.C1 else None, r.C1,
               IN_BNRELU if r.bnrelu else IN_PLAIN, dbn.data_ptr() if r.bnrelu else None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
@@ -170,6 +215,8 @@ def test_forward_and_statistics(r):
     td = torch.bfloat16 if p == 'bf16' else torch.float32
     c = forward_case(r)
     d0, d1 = to_nhwc(p, c.x0), (to_nhwc(p, c.x1) if r.C1 else None)
+    if r.creal:
+        _assert_zero_padding(r, d0)
     out = guard.full((r.N, r.H, r.W, r.Cout), NAN, dtype=td)
     nt = _lib.load().bdn_conv3x3_num_mtiles(r.N, r.H, r.W, r.Cout, r.ipg)
     stats = guard.full((nt, 2, r.Cout), NAN)
@@ -395,6 +442,8 @@ def test_split_product_convolution(r):
     stats = guard.full((nt, 2, Cout), NAN) if r.stats else None
     sp_out = guard.full((N, H, W, 2 * C0), NAN, dtype=torch.bfloat16) if r.op == 'x3src' and r.stats else None
     xin = _split(c.x, ipg) if r.op == 'x3' else to_nhwc('fp32', c.x)
+    if r.creal:
+        _assert_zero_padding(r, xin, halves=2)
     x3_launch(r, c, xin, out, stats, sp_out)
     x3_compare(r, c, out, stats, sp_out)
 
@@ -403,21 +452,22 @@ def x3_case(r):
     """Inputs and float64 reference of an 'x3' / 'x3src' row."""
     N, H, W, C0, Cout, ipg = r.N, r.H, r.W, r.C0, r.Cout, r.ipg
     G = N // ipg
-    x = _rand((N, C0, H, W), 311)
-    w = _rand((Cout, C0, 3, 3), 312, (2.0 / (9 * C0)) ** 0.5)
+    cr = r.creal or C0
+    x = _rand((N, cr, H, W), 311)
+    w = _rand((Cout, cr, 3, 3), 312, (2.0 / (9 * cr)) ** 0.5)
     b = _rand((Cout,), 313, 0.1)
     bn = bn_table(G, C0, 314) if r.bnrelu else None
     a = bnrelu_ref('fp32', x, bn, ipg) if r.bnrelu else x
     wr = w if r.prec == 'bf16x3' else w.to(torch.bfloat16).float()
     ref = F.conv2d(a.double(), wr.double(), b.double(), padding=1)
-    return SimpleNamespace(x=x, w=w, b=b, bn=bn, a=a, ref=ref)
+    return SimpleNamespace(x=_padded(x, C0), w=w, b=b, bn=bn, a=a, ref=ref)
 
 
 def x3_launch(r, c, xin, out, stats, sp_out, N=None, ipg=None):
     """'x3': bdn_conv3x3 on the split operand `xin`; 'x3src': bdn_conv3x3_x3src on the float32 operand `xin`."""
     N, ipg = (r.N if N is None else N), (r.ipg if ipg is None else ipg)
     dt, C0 = lc.DTYPE[r.prec], r.C0
-    wf = _x3_weights(c.w)
+    wf = pack_first(r.prec, c.w, C0) if r.creal else _x3_weights(c.w)
     db = dev(c.b)
     if r.op == 'x3':
         _lib.call('bdn_conv3x3', dt, xin.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg, wf.data_ptr(), db.data_ptr(), out.data_ptr(),
@@ -447,13 +497,14 @@ def x3_compare(r, c, out, stats, sp_out):
 # ------------------------------------------------------------------ eval epilogue
 def _eval_inputs(r, seed):
     p = r.prec
-    x0 = rnd(p, _rand((r.N * (2 if r.op == 'eval_pair' else 1), r.C0, r.H, r.W), seed))
+    cr = r.creal or r.C0
+    x0 = rnd(p, _rand((r.N * (2 if r.op == 'eval_pair' else 1), cr, r.H, r.W), seed))
     x1 = rnd(p, _rand((r.N, r.C1, r.H, r.W), seed + 1)) if r.C1 else None
-    w = rnd(p, _rand((r.Cout, r.C0 + r.C1, 3, 3), seed + 2, (2.0 / (9 * (r.C0 + r.C1))) ** 0.5))
+    w = rnd(p, _rand((r.Cout, cr + r.C1, 3, 3), seed + 2, (2.0 / (9 * (cr + r.C1))) ** 0.5))
     sc, sh = _rand((r.Cout,), seed + 3).abs() + 0.5, _rand((r.Cout,), seed + 4, 0.3)
     a = torch.cat([x0, x1], 1) if r.C1 else x0
     act = torch.relu(F.conv2d(a.double(), w.double(), None, padding=1) * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
-    return x0, x1, w, sc, sh, act
+    return _padded(x0, r.C0), x1, w, sc, sh, act
 
 
 def _pool64(t):
@@ -468,6 +519,8 @@ def test_eval_stage(r):
     p = r.prec
     c = eval_case(r)
     d0, d1 = to_nhwc(p, c.x0), (to_nhwc(p, c.x1) if r.C1 else None)
+    if r.creal:
+        _assert_zero_padding(r, d0)
     outs = eval_outputs(r, r.N)
     eval_launch(r, c, d0, d1, outs)
     eval_compare(r, c, outs)
@@ -502,7 +555,7 @@ def eval_outputs(r, N, born=False):
 def eval_launch(r, c, d0, d1, o, N=None):
     N = r.N if N is None else N
     dt, H, W, Cout = lc.DTYPE[r.prec], r.H, r.W, r.Cout
-    wf, _ = pack_w(r.prec, c.w, r.C0 + r.C1)
+    wf = pack_first(r.prec, c.w, r.C0) if r.creal else pack_w(r.prec, c.w, r.C0 + r.C1)[0]
     dsc, dsh = dev(c.sc), dev(c.sh)
     if r.op == 'eval':
         _lib.call('bdn_conv3x3_eval', dt, d0.data_ptr(), r.C0, d1.data_ptr() if r.C1 else None, r.C1, wf.data_ptr(),
@@ -550,15 +603,16 @@ def weight_gradient_case(r):
     N, H, W, C0, C1, Cout, ipg, p = r.N, r.H, r.W, r.C0, r.C1, r.Cout, r.ipg, r.prec
     G = N // ipg
     sp = 'fp32' if p in ('bf16x3', 'bf16x2') else p
-    x0 = rnd(sp, _rand((N, C0, H, W), 21))
+    cr = r.creal or C0                                   # wide rows: the gradient of the creal real filter channels
+    x0 = rnd(sp, _rand((N, cr, H, W), 21))
     x1 = rnd(sp, _rand((N, C1, H, W), 22)) if C1 else None
     dz = rnd(sp, _rand((N, Cout, H, W), 23))
     bn_in = bn_table(G, C0, 24) if r.bnrelu else None
     a0 = bnrelu_ref(sp, x0, bn_in, ipg) if r.bnrelu else x0
     a = torch.cat([a0, x1], 1) if C1 else a0
     dzr = dz.to(torch.bfloat16).float() if p == 'bf16x2' else dz          # two terms: dz_hi x [a_hi | a_lo]
-    ref = torch.nn.grad.conv2d_weight(a.double(), (Cout, C0 + C1, 3, 3), dzr.double(), padding=1)
-    return SimpleNamespace(x0=x0, x1=x1, dz=dz, bn_in=bn_in, ref=ref)
+    ref = torch.nn.grad.conv2d_weight(a.double(), (Cout, cr + C1, 3, 3), dzr.double(), padding=1)
+    return SimpleNamespace(x0=_padded(x0, C0), x1=x1, dz=dz, bn_in=bn_in, ref=ref)
 
 
 def weight_gradient_launch(r, bn_in, ddz, d0, d1, part, dw, flags=3, N=None, ipg=None):
@@ -568,11 +622,11 @@ def weight_gradient_launch(r, bn_in, ddz, d0, d1, part, dw, flags=3, N=None, ipg
     if r.prec in ('bf16x3', 'bf16x2'):
         assert not r.bnrelu and not C1
         _lib.call('bdn_conv3x3_wgrad_ex', dt, ddz.data_ptr(), Cout, d0.data_ptr(), C0, None, 0, IN_PLAIN, None, ipg,
-                  part.data_ptr(), dw.data_ptr(), C0, N, r.H, r.W, flags, st())
+                  part.data_ptr(), dw.data_ptr(), r.creal or C0, N, r.H, r.W, flags, st())
     else:
         dbn = dev(bn_in) if r.bnrelu else None
         _lib.call('bdn_conv3x3_wgrad_ex', dt, ddz.data_ptr(), Cout, d0.data_ptr(), C0, d1.data_ptr() if C1 else None, C1,
-                  IN_BNRELU if r.bnrelu else IN_PLAIN, dbn.data_ptr() if r.bnrelu else None, ipg, part.data_ptr(), dw.data_ptr(), C0 + C1,
+                  IN_BNRELU if r.bnrelu else IN_PLAIN, dbn.data_ptr() if r.bnrelu else None, ipg, part.data_ptr(), dw.data_ptr(), r.creal or C0 + C1,
                   N, r.H, r.W, flags, st())
     torch.cuda.synchronize()
 
@@ -586,11 +640,13 @@ def run_weight_gradient(r, flags=3):
     nb = lib.bdn_wgrad_workspace_bytes_ex(lc.DTYPE[p], N, H, W, Cout, C0, C1, ipg, IN_BNRELU if r.bnrelu else IN_PLAIN, flags)
     assert flags != 3 or nb <= lib.bdn_wgrad_workspace_bytes(N, H, W, Cout, C0 + C1, ipg)
     part = guard.empty(nb // 4)
-    dw = guard.full((Cout, C0 + C1, 3, 3), NAN)
+    dw = guard.full((Cout, r.creal or C0 + C1, 3, 3), NAN)          # wide rows: exactly Cout * creal * 9 floats between the guards
     if x3:
         ddz, d0, d1 = _split(c.dz, ipg), _split(c.x0, ipg), None
     else:
         ddz, d0, d1 = to_nhwc(p, c.dz), to_nhwc(p, c.x0), (to_nhwc(p, c.x1) if C1 else None)
+    if r.creal:
+        _assert_zero_padding(r, d0, halves=2 if x3 else 1)
     weight_gradient_launch(r, c.bn_in, ddz, d0, d1, part, dw, flags)
     check(f'{_rid(r)} dW', dw, c.ref, 'x3' if x3 else 'fp32')
 
@@ -757,41 +813,50 @@ def _instantiations(seen):
     return out
 
 
-@pytest.mark.parametrize('precision', ['bf16', 'fp32', 'bf16x3', 'bf16x3-fast'])
-def test_training_step_launches_equal_the_enumeration(monkeypatch, precision):
-    """One real forward + backward of BiDateNet(13, 2) at batch 64, 128 x 128: the instantiations its MFMA launches run equal
-    launch_cases.train_step_instantiations (the hand-written walk cannot drift from the engine), and every one of them has a row."""
+_PRECISIONS = ['bf16', 'fp32', 'bf16x3', 'bf16x3-fast']
+# (precision, bands, batch, patch side): the benchmarked step (the ids it always had), and small steps of the wide first layer
+_STEP_CASES = [(p, 13, 64, 128) for p in _PRECISIONS] + [(p, c, 2, 32) for c in (17, 48) for p in _PRECISIONS]
+_STEP_IDS = [p if c == 13 else f'{p}-c{c}' for p, c, _, _ in _STEP_CASES]
+
+
+@pytest.mark.parametrize('precision,c,B,S', _STEP_CASES, ids=_STEP_IDS)
+def test_training_step_launches_equal_the_enumeration(monkeypatch, precision, c, B, S):
+    """One real forward + backward of BiDateNet(13, 2) at batch 64, 128 x 128 -- and of BiDateNet(17, 2) and BiDateNet(48, 2) at batch 2,
+    32 x 32, whose first layer is padded to 32 and 48 channels and takes bn_bwd + the generic GEMM: the instantiations its MFMA launches
+    run equal launch_cases.train_step_instantiations (the hand-written walk cannot drift from the engine), and every one has a row."""
     from fabric_amd import BiDateNet
     torch.manual_seed(0)
-    B, S = 64, 128
-    model = BiDateNet(13, 2, precision=precision).cuda().train()
+    model = BiDateNet(c, 2, precision=precision).cuda().train()
     eng = model.engine()
+    if c > 16:
+        assert eng.first_wgrad_dtype(2 * B, S, S, B) is None
     P = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
-    x1, x2 = torch.randn(B, 13, S, S, device='cuda'), torch.randn(B, 13, S, S, device='cuda')
+    x1, x2 = torch.randn(B, c, S, S, device='cuda'), torch.randn(B, c, S, S, device='cuda')
     seen = _record(monkeypatch)
     logits, ws = eng.forward(x1, x2, P, training=True)
     grads = {k: torch.empty_like(p) for k, p in model.named_parameters()}
     eng.backward(ws, torch.randn_like(logits) * 1e-3, P, grads)
     torch.cuda.synchronize()
     got = _instantiations(seen)
-    want = lc.train_step_instantiations(precision, B, S)
+    want = lc.train_step_instantiations(precision, B, S, n_channels=c)
+    assert all(torch.isfinite(g).all() for g in grads.values())
     assert got == want, f'launched but not enumerated: {sorted(got - want)}; enumerated but not launched: {sorted(want - got)}'
     assert not got - lc.covered(), f'no row for {sorted(got - lc.covered())}'
 
 
-@pytest.mark.parametrize('B', [256, 64], ids=['scene-batch', 'validation'])
-def test_eval_forward_launches_are_covered(monkeypatch, B):
-    """model.eval() forwards (the eval-shaped schedule): a scene-inference batch of 256 tiles of 128 x 128 and a validation batch of 64."""
+@pytest.mark.parametrize('B,c,S', [(256, 13, 128), (64, 13, 128), (2, 17, 32), (2, 48, 32)], ids=['scene-batch', 'validation', 'c17', 'c48'])
+def test_eval_forward_launches_are_covered(monkeypatch, B, c, S):
+    """model.eval() forwards (the eval-shaped schedule): a scene-inference batch of 256 tiles of 128 x 128 and a validation batch of 64;
+    17 and 48 bands at batch 2, 32 x 32 (the multi-chunk first layer with the eval epilogue)."""
     from fabric_amd import BiDateNet
     torch.manual_seed(0)
-    S = 128
-    model = BiDateNet(13, 2, precision='bf16').cuda().eval()
+    model = BiDateNet(c, 2, precision='bf16').cuda().eval()
     eng = model.engine()
     P = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
-    x1, x2 = torch.randn(B, 13, S, S, device='cuda'), torch.randn(B, 13, S, S, device='cuda')
+    x1, x2 = torch.randn(B, c, S, S, device='cuda'), torch.randn(B, c, S, S, device='cuda')
     seen = _record(monkeypatch)
     eng.forward(x1, x2, P, training=False)
     torch.cuda.synchronize()
     got = _instantiations(seen)
-    assert got == lc.eval_forward_instantiations('bf16', B, S)
+    assert got == lc.eval_forward_instantiations('bf16', B, S, n_channels=c)
     assert not got - lc.covered(), f'no row for {sorted(got - lc.covered())}'

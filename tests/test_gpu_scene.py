@@ -135,6 +135,26 @@ def test_predict_scene_matches_oracle(prec):
     assert np.array_equal(img.astype(np.uint8), inf.predict_scene(model, d1, d2, patch_size=p, batch_size=4).cpu().numpy())
 
 
+@pytest.mark.parametrize('prec', ['fp32', 'bf16'])
+@pytest.mark.parametrize('c', [3, 20])
+def test_scene_tiles_equal_patch_batches(prec, c):
+    """The fused scene path (tiles gathered on the device into the padded input, eval schedule, argmax + stitching in the epilogue) gives
+    the mask of the reference-style loop over host-made patch batches (bdn_pack_input, logits, host argmax and stitching), bit for
+    bit.  c = 20: gather_tiles and pack_input at Cpad = 32 into the multi-chunk first layer of the eval schedule."""
+    h, w, p = 88, 75, 32
+    d1, d2 = _scene(c, h, w, 3)
+    model, _ = _calibrated_model(c, prec, d1, d2, p)
+    assert model.engine().cp == (16 if c == 3 else 32)
+    _, hs, ws, lc, lr = inf.tile_origins(h, w, p)
+    p1 = np.ascontiguousarray(inf._get_patches(d1.transpose(1, 2, 0), p)[0].transpose(0, 3, 1, 2))
+    p2 = np.ascontiguousarray(inf._get_patches(d2.transpose(1, 2, 0), p)[0].transpose(0, 3, 1, 2))
+    for bs in (4, 5):                                            # equal batches, ragged last batch
+        img = inf.full_image_mask(inf.predict_patches(model, p1, p2, batch_size=bs), hs, ws, lc, lr, h, w, p).astype(np.uint8)
+        assert 0.02 < img.mean() < 0.98, 'degenerate test scene: the mask has a single class'
+        got = inf.predict_scene(model, torch.from_numpy(d1), torch.from_numpy(d2), patch_size=p, batch_size=bs).cpu().numpy()
+        assert np.array_equal(got, img), bs
+
+
 @pytest.mark.parametrize('pinned', [True, False])
 @pytest.mark.parametrize('band_rows', [8, 32, 50, 4096])
 def test_host_fed_scene_equals_resident_scene(pinned, band_rows):

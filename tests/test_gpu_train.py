@@ -13,9 +13,13 @@ from oracle import filler
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize('prec,tol_logit,tol_loss', [('fp32', 2e-3, 2e-5), ('bf16', 0.3, 5e-3)])
-def test_five_steps_follow_the_oracle(prec, tol_logit, tol_loss):
-    c, b, s, steps, lr = 3, 4, 32, 5, 0.05          # large lr so that a wrong update would be visible
+@pytest.mark.parametrize('prec,tol_logit,tol_loss,c,b', [('fp32', 2e-3, 2e-5, 3, 4), ('bf16', 0.3, 5e-3, 3, 4),
+                                                        ('fp32', 2e-3, 2e-5, 20, 2), ('bf16', 0.3, 5e-3, 20, 2)],
+                         ids=['fp32-0.002-2e-05', 'bf16-0.3-0.005', 'fp32-c20', 'bf16-c20'])
+def test_five_steps_follow_the_oracle(prec, tol_logit, tol_loss, c, b):
+    """c = 20 (batch 2): a first layer padded to 32 channels -- the generic first-layer kernels, param_order(20) and the flat layout
+    with a 64 x 20 x 3 x 3 filter -- under the same bounds."""
+    s, steps, lr = 32, 5, 0.05                      # large lr so that a wrong update would be visible
     x1, x2, lbl = filler.make_inputs(b, c, s, seed=3)
     x1, x2, lbl = torch.from_numpy(x1), torch.from_numpy(x2), torch.from_numpy(lbl)
     model = filler.fill_module(BiDateNet(c, 2, precision=prec))
@@ -29,6 +33,8 @@ def test_five_steps_follow_the_oracle(prec, tol_logit, tol_loss):
         got_logits = ts.last_logits.cpu()
         assert abs(loss.item() - float(ref['loss'])) < tol_loss * (i + 1), (i, loss.item(), float(ref['loss']))
         assert (got_logits - ref['logits']).abs().max() < tol_logit * (i + 1), i
+        g0 = model.inc.conv.conv[0].weight.grad
+        assert tuple(g0.shape) == (64, c, 3, 3) and bool(torch.isfinite(g0).all()) and float(g0.abs().max()) > 0
         p_ref = O.binary_prf(lbl, ref['preds'])
         from fabric_amd.utils.metrics import batch_prf_from_counts
         p_got = batch_prf_from_counts(ts.last_counts.cpu())

@@ -53,3 +53,32 @@ def test_frozen_batchnorm_backward_rejects_bad_arguments():
     _fails('bad shape', f, *ok[:6], 0, *ok[7:])
     _fails('must divide', f, *ok[:9], 48, *ok[10:])
     _fails('bad dtype', f, BDN_BF16X3, *ok[1:])
+
+
+def test_input_gradient_is_refused_at_the_door_above_16_bands():
+    """bdn_conv3x3_dgrad_first takes at most 16 input channels, and backward() reaches it only after the whole chain is enqueued: the
+    engine refuses dx before anything else (no workspace, no device tensor is touched: meta tensors and ws = None do), and the
+    autograd route refuses when an image requires grad, before the forward.  16 bands pass the check."""
+    import torch
+    from fabric_amd import BiDateNet
+    from fabric_amd.engine import INPUT_GRAD_MAX_BANDS, BiDateEngine
+    assert INPUT_GRAD_MAX_BANDS == 16
+    for c in (1, 13, 16):
+        BiDateEngine(c, 2).check_input_grad()
+    dx = (torch.empty(2, 17, 32, 32, device='meta'), torch.empty(2, 17, 32, 32, device='meta'))
+    for c in (17, 32, 64):
+        for prec in ('bf16', 'fp32', 'bf16x3', 'bf16x3-fast'):
+            eng = BiDateEngine(c, 2, prec)
+            with pytest.raises(ValueError, match=r'limited to 16 bands.*bdn_conv3x3_dgrad_first.*' + f'this model has {c}'):
+                eng.backward(None, torch.empty(2, 2, 32, 32, device='meta'), {}, {}, dx=dx)
+    # the module: an image that requires grad is refused before the forward (a CPU tensor would otherwise meet "no CPU path")
+    x = torch.zeros(1, 17, 16, 16)
+    with pytest.raises(ValueError, match='bdn_conv3x3_dgrad_first'):
+        BiDateNet(17, 2)(x.clone().requires_grad_(True), x)
+    with pytest.raises(ValueError, match='bdn_conv3x3_dgrad_first'):
+        BiDateNet(17, 2).eval()(x, x.clone().requires_grad_(True))
+    x = torch.zeros(1, 16, 16, 16)
+    with pytest.raises(RuntimeError, match='no CPU path'):            # 16 bands: past the check, up to the device check
+        BiDateNet(16, 2)(x.clone().requires_grad_(True), x)
+    with pytest.raises(RuntimeError, match='no CPU path'):            # 17 bands without an input gradient: not refused for the width
+        BiDateNet(17, 2)(torch.zeros(1, 17, 16, 16), torch.zeros(1, 17, 16, 16))
