@@ -113,6 +113,8 @@ SIGNATURES = {
     'bdn_criterion_masked': (_i, [_vp, _vp, _i, _f, _f, _f, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_criterion_topk_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'bdn_criterion_topk': (_i, [_vp, _vp, _i, _f, _f, _f, _f, _i, _f, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'bdn_criterion_soft_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'bdn_criterion_soft': (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_lovasz_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'bdn_lovasz_softmax': (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'bdn_ingest_band': (_i, [_i, _vp, _i, _i, _f, _f, _vp, _i, _i, _vp]),

@@ -40,6 +40,20 @@ negative, and it is meant to be ramped up beside a region loss: the weight is pa
 two steps takes effect at the next one (it must have been > 0 at construction, which decides the buffers).  `terms` gains one trailing
 element, after the Lovasz one.  With add-on terms alone the counts are those of confusion_counts().  Data-parallel: each rank normalises by
 its own valid count; with gradient accumulation the maps are computed per micro-step.  w_boundary=0 is the criterion as it was.
+
+Soft targets -- ``bdn_criterion_soft``, the same overlap and focal terms with a target q_c >= 0 per class and a weight w >= 0 per pixel
+(include/bidate_hip.h states the definition; TP = sum w p q, FP = sum w p (1 - q), FN = sum w (1 - p) q; the focal term sums
+q_c a_c m_c (-log p_c) over the classes with q_c > 0 and is normalised by the NUMBER of pixels with w > 0).  Three inputs take this route:
+label_smoothing e in [0, 1) (torch.nn.CrossEntropyLoss's: q = (1 - e) + e / ncls at the label's class and e / ncls elsewhere, a valid
+label >= ncls keeps q = 0), `weights` given to evaluate() (float32 [B,H,W], multiplied into the 0 / 1 weight of ignore_index: confidence
+weights, border down-weighting), and float32 [B,C,H,W] `labels`, taken as the targets themselves (probability maps of a teacher, MixUp
+blends; label_smoothing must be 0 and ignore_index None then: give a weight of 0 instead).  dlogits is exactly 0 where w is not > 0 and
+nothing of such a pixel reaches an output; counts are int32[5] = {TP, FP, FN, correct, valid} of argmax(logits) against the label or
+argmax_c q_c.  Nothing is read back: negative or non-finite targets at a valid pixel are the caller's error.  topk ranks a hard-label term
+and refuses every soft input (ValueError).  w_lovasz and w_boundary compose with label_smoothing and with weights on hard labels: their
+passes run behind the soft entry point on the unchanged labels (and ignore_index), unweighted; with float targets they raise ValueError.
+The soft route needs buffers(soft=True) (label_smoothing > 0 implies it): evaluate() raises on smaller ones rather than reallocate.  With
+label_smoothing 0, no weights and class-index labels every call is issued as it always was.
 """
 
 NAMES = ('tversky', 'dice', 'jaccard', 'focal', 'focal+tversky', 'focal+dice', 'focal+jaccard')
@@ -53,7 +67,7 @@ REDUCE = {'columns': 0, 'image': 1}
 class Criterion:
     def __init__(self, w_overlap=1.0, alpha=0.5, beta=0.5, eps=1e-7, reduce='columns', w_focal=0.0, gamma=0.0, class_alpha=None,
                  size_average=True, ignore_index=None, topk=None, w_lovasz=0.0, lovasz_classes='present', w_boundary=0.0,
-                 boundary_classes='foreground', boundary_max_dist=None):
+                 boundary_classes='foreground', boundary_max_dist=None, label_smoothing=0.0):
         """reduce: 'columns' -- what the reference's train.py gets from [B,H,W] labels, sums over dims (0,2), one ratio per (class,
         column) -- or 'image', dims (0,2,3), one ratio per class ([B,1,H,W] labels there).  class_alpha: None, a float a (class
         weights [a, 1 - a], utils/metrics.py:13-14) or a sequence of ncls class weights.  ignore_index: None -- every pixel carries a label,
@@ -61,7 +75,10 @@ class Criterion:
         focal term is averaged over, the hardest first (module docstring), bdn_criterion_topk.  w_lovasz: the weight of the Lovasz-Softmax term,
         lovasz_classes 'present' or 'all' (module docstring), bdn_lovasz_softmax.  w_boundary: the weight of the boundary term,
         boundary_classes 'foreground' or 'all', boundary_max_dist None or the clamp of the signed distance in pixels (module docstring),
-        bdn_boundary_loss."""
+        bdn_boundary_loss.  label_smoothing: 0 <= e < 1, the smoothed hard-label targets of bdn_criterion_soft (module docstring)."""
+        if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f'label_smoothing must be a number in [0, 1), got {label_smoothing!r}')
+        self.label_smoothing = float(label_smoothing)
         w_overlap, w_focal, w_lovasz, w_boundary = float(w_overlap), float(w_focal), float(w_lovasz), float(w_boundary)
         if not w_boundary >= 0.0:
             raise ValueError(f'criterion weights must be >= 0, got w_boundary={w_boundary}')
@@ -109,6 +126,11 @@ class Criterion:
                 raise ValueError(f'topk needs class weights >= 0, got class_alpha={self.class_alpha}')
             topk, self.topk_ppm = float(topk), ppm
         self.topk = topk
+        if self.label_smoothing > 0.0:
+            if topk is not None:
+                raise ValueError('topk ranks a hard-label focal term: it does not take label_smoothing (soft targets)')
+            if w_overlap == 0.0 and w_focal == 0.0:
+                raise ValueError('label_smoothing acts on the overlap and focal terms: the criterion needs one of their weights')
         self._alpha_dev = {}
 
     @property
@@ -134,12 +156,13 @@ class Criterion:
     @classmethod
     def parse(cls, name, tversky_alpha=0.5, tversky_beta=0.5, focal_gamma=None, focal_alpha=None, weights=(1, 1), eps=1e-7,
               reduce='columns', ignore_index=None, topk=None, lovasz_classes='present', w_boundary=0.0, boundary_classes='foreground',
-              boundary_max_dist=None):
+              boundary_max_dist=None, label_smoothing=0.0):
         """The criterion of a --loss_function name.  weights = (w_focal, w_overlap), used by the compound names only.  topk: a name with a
         focal term only (Criterion raises ValueError otherwise).  LOVASZ_NAMES: 'lovasz' is the Lovasz-Softmax term alone; 'focal+lovasz'
         has weights = (w_focal, w_lovasz) and, with focal_gamma None, gamma 0: cross-entropy + Lovasz, the usual pairing.  w_boundary,
-        boundary_classes, boundary_max_dist: the boundary term beside any name (--boundary_weight)."""
-        bnd = dict(w_boundary=w_boundary, boundary_classes=boundary_classes, boundary_max_dist=boundary_max_dist)      # validated at any weight
+        boundary_classes, boundary_max_dist: the boundary term beside any name (--boundary_weight).  label_smoothing: --label_smoothing."""
+        bnd = dict(w_boundary=w_boundary, boundary_classes=boundary_classes, boundary_max_dist=boundary_max_dist,      # validated at any weight
+                   label_smoothing=label_smoothing)
         if name in LOVASZ_NAMES:
             focal = name != 'lovasz'
             w_focal, w_lovasz = (float(weights[0]), float(weights[1])) if focal else (0.0, 1.0)
@@ -163,6 +186,7 @@ class Criterion:
                 f'w_focal={self.w_focal}, gamma={self.gamma}, class_alpha={self.class_alpha}, size_average={self.size_average}'
                 + (f', ignore_index={self.ignore_index}' if self.ignore_index is not None else '')
                 + (f', topk={self.topk}' if self.topk is not None else '')
+                + (f', label_smoothing={self.label_smoothing}' if self.label_smoothing else '')
                 + (f', w_lovasz={self.w_lovasz}, lovasz_classes={self.lovasz_classes!r}' if self.w_lovasz else '')
                 + (f', w_boundary={self.w_boundary}, boundary_classes={self.boundary_classes!r}, boundary_max_dist={self.boundary_max_dist}'
                    if self.has_boundary else '') + ')')
@@ -179,17 +203,24 @@ class Criterion:
             t = self._alpha_dev[device] = torch.tensor(self.class_alpha, dtype=torch.float32).to(device)
         return t
 
-    def buffers(self, shape, device):
+    def buffers(self, shape, device, soft=False):
         """Persistent outputs for logits of `shape`: (workspace, loss, terms, counts), the `out` of evaluate().  counts is int32[4], or
         int32[5] with an ignore_index; with topk, terms is f32[3] and counts int32[6].  With w_lovasz the workspace also holds
-        bdn_lovasz_softmax's (behind the other, 256-byte aligned) and terms has one more element, the last."""
+        bdn_lovasz_softmax's (behind the other, 256-byte aligned) and terms has one more element, the last.  soft=True (implied by
+        label_smoothing > 0): the buffers of the soft route -- bdn_criterion_soft's workspace in front, counts int32[5] -- which a call
+        with `weights` or float targets needs; such buffers serve that route only."""
         import torch
         from . import _lib
         B, C, H, W = shape
-        masked = self.ignore_index is not None
+        soft = bool(soft) or self.label_smoothing > 0.0
+        if soft and self.topk is not None:
+            raise ValueError('topk ranks a hard-label focal term: it has no soft route')
+        masked = self.ignore_index is not None or soft
         query = _lib.load().bdn_criterion_masked_workspace_bytes if masked else _lib.load().bdn_criterion_workspace_bytes
         if self.topk is not None:
             query = _lib.load().bdn_criterion_topk_workspace_bytes
+        if soft:
+            query = _lib.load().bdn_criterion_soft_workspace_bytes
         n = query(B, C, H, W, REDUCE[self.reduce])
         if n == 0:
             raise RuntimeError(f'fabric_amd: the criterion takes logits [B, 2..8, H, W] with B*H*W < 2^31, got {tuple(shape)}')
@@ -239,7 +270,44 @@ class Criterion:
                   ws.data_ptr() + self._lovasz_offset(n_front), loss.data_ptr(), terms.data_ptr() + 4 * (terms.numel() - 1), _lib.ptr(dlogits),
                   _lib.ptr(phi), B, C, H, W, _lib.stream_ptr())
 
-    def evaluate(self, logits, labels, want_grad=True, out=None, pixel_terms=None, kept=None, pixel_errors=None, ranks=None, phi=None):
+    def _soft_inputs(self, logits, labels, weights):
+        """(soft, targets) of one evaluate() call: whether it takes the soft route, and whether `labels` are float targets.  Checks dtype,
+        shape, device and contiguity of `weights` and of float targets -- nothing is read from them -- and refuses what has no soft form."""
+        import torch
+        B, C, H, W = logits.shape
+        targets = labels.is_floating_point() and tuple(labels.shape) == (B, C, H, W)
+        if not (targets or weights is not None or self.label_smoothing > 0.0):
+            return False, False
+        if self.topk is not None:
+            raise ValueError('topk ranks a hard-label focal term: it takes neither weights nor float targets')
+        if self.w_overlap == 0.0 and self.w_focal == 0.0:
+            raise ValueError('weights and float targets act on the overlap and focal terms: the criterion needs one of their weights')
+        if targets:
+            if self.w_lovasz or self.has_boundary:
+                raise ValueError('the Lovasz and boundary terms are defined on class-index labels: they do not take float targets')
+            if self.label_smoothing > 0.0 or self.ignore_index is not None:
+                raise ValueError('float targets are taken as given: label_smoothing must be 0 and ignore_index None (give a weight of 0)')
+            if labels.dtype != torch.float32 or labels.device != logits.device or not labels.is_contiguous():
+                raise RuntimeError(f'fabric_amd: float targets must be a contiguous float32 [B,C,H,W] tensor on {logits.device}')
+        if weights is not None:
+            if (weights.dtype != torch.float32 or weights.device != logits.device or not weights.is_contiguous()
+                    or tuple(weights.shape) not in ((B, H, W), (B, 1, H, W))):
+                raise RuntimeError(f'fabric_amd: weights must be a contiguous float32 [B,H,W] tensor on {logits.device} for logits '
+                                   f'{tuple(logits.shape)}, got {weights.dtype} {tuple(weights.shape)}')
+        return True, targets
+
+    def _evaluate_soft(self, logits, labels, targets, weights, ws, loss, terms, counts, dlogits, ca):
+        """bdn_criterion_soft: the overlap / focal entry point of a call with label smoothing, weights or float targets."""
+        from . import _lib
+        B, C, H, W = logits.shape
+        _lib.call('bdn_criterion_soft', logits.data_ptr(), None if targets else labels.data_ptr(), labels.data_ptr() if targets else None,
+                  _lib.ptr(weights), -1 if self.ignore_index is None else self.ignore_index, self.label_smoothing, self.w_overlap,
+                  self.alpha, self.beta, self.eps, REDUCE[self.reduce], self.w_focal, self.gamma, _lib.ptr(ca), int(self.size_average),
+                  ws.data_ptr(), loss.data_ptr(), terms.data_ptr(), counts.data_ptr(), _lib.ptr(dlogits), B, C, H, W, _lib.stream_ptr())
+        return loss, terms, counts, dlogits
+
+    def evaluate(self, logits, labels, want_grad=True, out=None, pixel_terms=None, kept=None, pixel_errors=None, ranks=None, phi=None,
+                 weights=None):
         """-> (loss, terms, counts, dlogits) of float32 [B,C,H,W] logits and [B,H,W] or [B,1,H,W] class-index labels, on the current
         stream: loss a 0-dim tensor, terms f32[2] = the unweighted overlap and focal values, counts int32[4] = {TP, FP, FN, correct} of
         argmax(logits), dlogits = d loss / d logits (None without want_grad: no gradient pass is launched).  `out`: buffers() of this
@@ -253,20 +321,35 @@ class Criterion:
         `pixel_errors` (contiguous float32, C*B*H*W) and `ranks` (contiguous int32, C*B*H*W) are optional caller tensors that receive
         every class's errors and 0-based ranks (-1 at ignored pixels).  With w_boundary: bdn_boundary_loss runs last through the same seam;
         terms[-1] is the unweighted boundary value (the Lovasz one, if present, is terms[-2]); `phi` (contiguous float32, C*B*H*W) is an
-        optional caller tensor that receives every class's signed distance (0 for a class that is not included)."""
+        optional caller tensor that receives every class's signed distance (0 for a class that is not included).
+        Soft targets (module docstring): with label_smoothing, with `weights` (contiguous float32 [B,H,W] on the logits' device) or with
+        contiguous float32 [B,C,H,W] `labels` -- taken as targets -- bdn_criterion_soft runs in place of the entry point above; counts is
+        int32[5] and `out` must come from buffers(soft=True).  Only dtype, shape, device and contiguity are checked: no host read."""
         import torch
         from . import _lib
-        if not logits.is_cuda:
-            raise RuntimeError('fabric_amd: the losses run only on a ROCm device -- there is no CPU path')
         if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
+            if not logits.is_cuda:
+                raise RuntimeError('fabric_amd: the losses run only on a ROCm device -- there is no CPU path')
             raise RuntimeError('fabric_amd: the criterion takes contiguous float32 [B,C,H,W] logits')
         B, C, H, W = logits.shape
-        if labels.numel() != B * H * W or tuple(labels.shape) not in ((B, H, W), (B, 1, H, W)):
-            raise RuntimeError(f'labels must be [B,H,W] or [B,1,H,W] for logits {tuple(logits.shape)}, got {tuple(labels.shape)}')
-        if labels.dtype != torch.uint8:
-            labels = labels.to(torch.uint8)
-        labels = labels.contiguous()
-        ws, loss, terms, counts = out if out is not None else self.buffers(logits.shape, logits.device)
+        soft, targets = self._soft_inputs(logits, labels, weights)     # (what has no soft form is refused wherever the tensors live)
+        if not logits.is_cuda:
+            raise RuntimeError('fabric_amd: the losses run only on a ROCm device -- there is no CPU path')
+        if not targets:
+            if labels.numel() != B * H * W or tuple(labels.shape) not in ((B, H, W), (B, 1, H, W)):
+                raise RuntimeError(f'labels must be [B,H,W] or [B,1,H,W] for logits {tuple(logits.shape)}, got {tuple(labels.shape)}')
+            if labels.dtype != torch.uint8:
+                labels = labels.to(torch.uint8)
+            labels = labels.contiguous()
+        ws, loss, terms, counts = out if out is not None else self.buffers(logits.shape, logits.device, soft=soft)
+        if soft:
+            if pixel_terms is not None or kept is not None:
+                raise RuntimeError('fabric_amd: pixel_terms / kept are outputs of a criterion with topk')
+            n_soft = _lib.load().bdn_criterion_soft_workspace_bytes(B, C, H, W, REDUCE[self.reduce])
+            if n_soft == 0:
+                raise RuntimeError(f'fabric_amd: the criterion takes logits [B, 2..8, H, W] with B*H*W < 2^31, got {tuple(logits.shape)}')
+            if counts.numel() < 5 or ws.numel() * ws.element_size() < n_soft:
+                raise RuntimeError('fabric_amd: weights and float targets need the buffers of the soft route: buffers(shape, device, soft=True)')
         dlogits = torch.empty_like(logits) if want_grad else None
         ca = self._class_alpha(logits.device, C)
         if not self.w_lovasz and (pixel_errors is not None or ranks is not None):
@@ -274,12 +357,14 @@ class Criterion:
         if not self.has_boundary and phi is not None:
             raise RuntimeError('fabric_amd: phi is an output of a criterion with w_boundary')
         if not self.w_lovasz and not self.has_boundary:
+            if soft:
+                return self._evaluate_soft(logits, labels, targets, weights, ws, loss, terms, counts, dlogits, ca)
             return self._evaluate_base(logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept)
         for t, dt, what in ((pixel_errors, torch.float32, 'pixel_errors'), (ranks, torch.int32, 'ranks'), (phi, torch.float32, 'phi')):
             if t is not None and (t.device != logits.device or t.dtype != dt or t.numel() != C * B * H * W or not t.is_contiguous()):
                 raise RuntimeError(f'fabric_amd: {what} must be a contiguous {dt} tensor of {C * B * H * W} elements on {logits.device}')
         masked = self.ignore_index is not None
-        query = 'bdn_criterion_topk_workspace_bytes' if self.topk is not None else \
+        query = 'bdn_criterion_soft_workspace_bytes' if soft else 'bdn_criterion_topk_workspace_bytes' if self.topk is not None else \
             'bdn_criterion_masked_workspace_bytes' if masked else 'bdn_criterion_workspace_bytes'
         n_base = getattr(_lib.load(), query)(B, C, H, W, REDUCE[self.reduce])
         if self._addon_only:                               # the counts: the statistics and finish passes of the overlap loss, no gradient pass
@@ -292,6 +377,8 @@ class Criterion:
             else:
                 _lib.call('bdn_criterion', logits.data_ptr(), labels.data_ptr(), 1.0, self.alpha, self.beta, self.eps, REDUCE[self.reduce], 0.0,
                           0.0, None, 1, ws.data_ptr(), loss.data_ptr(), None, counts.data_ptr(), None, B, C, H, W, _lib.stream_ptr())
+        elif soft:                                          # (never add-on only: _soft_inputs refuses that); the add-ons see the labels as they are
+            self._evaluate_soft(logits, labels, targets, weights, ws, loss, terms, counts, dlogits, ca)
         else:
             self._evaluate_base(logits, labels, ws, loss, terms, counts, dlogits, ca, pixel_terms, kept)
         accumulate, n_front = not self._addon_only, n_base    # the first add-on pass of an add-on-only criterion writes, every other one adds

@@ -665,6 +665,35 @@ def checkpoint_radiometric(path):
         return json.load(fh).get('radiometric')
 
 
+def checkpoint_label_smoothing(path):
+    """The `label_smoothing` entry of the metadata_epoch_N.json beside a checkpoint file of this program, or None."""
+    m = _CKPT.search(os.path.basename(path)) if path else None
+    meta = os.path.join(os.path.dirname(path), f'metadata_epoch_{m.group(1)}.json') if m else None
+    if meta is None or not os.path.exists(meta):
+        return None
+    with open(meta) as fh:
+        return json.load(fh).get('label_smoothing')
+
+
+def resolve_label_smoothing(flag, fused_step, loss_topk, checkpoint=None):
+    """--label_smoothing E (None when the flag was not given) with --fused_step / --loss_topk and the `label_smoothing` entry of the
+    metadata of the run --resume continues (or None) -> the run's value (0.0: none).  A resumed run keeps the checkpoint's value unless
+    the flag is given again.  ValueError names what does not fit: the smoothed targets live in the criterion of the fused step
+    (bdn_criterion_soft), and --loss_topk ranks a hard-label term."""
+    e = flag if flag is not None else checkpoint
+    if e is None:
+        return 0.0
+    if isinstance(e, bool) or not isinstance(e, (int, float)) or not 0.0 <= float(e) < 1.0:
+        raise ValueError(f'--label_smoothing {e}: a number in [0, 1)')
+    e = float(e)
+    if e > 0.0 and not fused_step:
+        raise ValueError(f'--label_smoothing {e} is built into the criterion of the fused step (its soft-target kernels): add --fused_step true')
+    if e > 0.0 and loss_topk is not None:
+        raise ValueError(f'--label_smoothing {e} and --loss_topk {loss_topk}: top-k mining ranks a hard-label focal term and takes no '
+                         f'soft targets; give one of them')
+    return e
+
+
 def normalize_loaded(full_load, radiom, ignore_label, device, log=True):
     """--radiometric: match date 2 of every loaded city to its date 1, in place, once, after --coregister and before any loader or scene
     pass sees the stacks; one `radiom` log line per city.  Returns the per-city reports."""
@@ -719,6 +748,10 @@ def main(argv=None):
     ap.add_argument('--ignore_label', type=int, default=None, metavar='V',
                     help='--fused_step true only: pixels labelled V (0..255, e.g. 255 for nodata / unlabelled) are left out of the loss, '
                          'its gradient and the accuracy / precision / recall / F1 (Criterion(ignore_index=V))')
+    ap.add_argument('--label_smoothing', type=float, default=None, metavar='E',
+                    help='--fused_step true only, not with --loss_topk: label smoothing, 0 <= E < 1 -- the target of the overlap and focal '
+                         'terms is (1 - E) + E / ncls at the label\'s class and E / ncls elsewhere (torch.nn.CrossEntropyLoss(label_smoothing=); '
+                         'bdn_criterion_soft).  Recorded in the checkpoint metadata; --resume keeps the value of the run it continues')
     ap.add_argument('--loss_topk', type=float, default=None, metavar='F',
                     help='--fused_step true only, a --loss_function with a focal term: hard-pixel mining, the focal term is averaged over the '
                          'hardest fraction F (0 < F <= 1) of the valid pixels of every batch (Criterion(topk=F)); the epoch record gains '
@@ -889,6 +922,11 @@ def main(argv=None):
             raise SystemExit(f'--loss_topk {opt.loss_topk} is built into the criterion of the fused step: add --fused_step true')
         if not 0.0 < opt.loss_topk <= 1.0:
             raise SystemExit(f'--loss_topk {opt.loss_topk}: a fraction 0 < F <= 1')
+    try:
+        opt.label_smoothing = resolve_label_smoothing(opt.label_smoothing, opt.fused_step, opt.loss_topk,
+                                                      checkpoint_label_smoothing(opt.resume) if opt.resume else None)
+    except ValueError as e:
+        raise SystemExit(str(e))
     try:
         scene_boundary_tol = check_boundary_flags(opt.boundary_weight, opt.boundary_classes, opt.boundary_max_dist, opt.fused_step,
                                                   opt.scene_boundary_tol, opt.scene_stride)
@@ -1083,6 +1121,8 @@ def main(argv=None):
         run_meta['coregister'] = dict(coreg, cells=list(coreg['cells']))
     if radiom is not None:                                 # ... and how date 2 was matched: --resume reads it back
         run_meta['radiometric'] = dict(radiom)
+    if opt.label_smoothing:                                # the criterion's smoothed targets: --resume reads it back
+        run_meta['label_smoothing'] = opt.label_smoothing
     schedule = None
     if scheduled:                                          # host floats only; its position comes from (epoch, batch), so --resume continues it
         from .schedule import LRSchedule

@@ -195,6 +195,7 @@ class TrainStep:
         if self.world > 1:                                   # identical start on every rank (DataParallel broadcasts)
             dist.broadcast(self.flat_params, src=0, group=process_group)
         self._tv = None
+        self._tv_soft, self._weights = None, None              # the soft route's criterion buffers; the pixel weights of the step under way
         self.last_counts = self.last_terms = self.last_dlogits = None
         # detached aliases of every parameter / buffer (same storage), built once: no per-step dict walk
         self._P = {k: v.detach() for k, v in self.model.state_dict(keep_vars=True).items()}
@@ -474,7 +475,7 @@ class TrainStep:
         self.model.engine().invalidate_weights()
         self._bound = self._bindings()
 
-    def step(self, x_d1, x_d2, labels):
+    def step(self, x_d1, x_d2, labels, weights=None):
         """One optimisation step.  Returns the loss as a fresh 0-dim device tensor (no sync; safe to keep in a list like
         the reference loop does with `cd_loss`).  `last_counts` / `last_logits` are persistent buffers that the NEXT step
         overwrites: clone them if they have to outlive it.
@@ -482,9 +483,25 @@ class TrainStep:
         The step's dependency chain (forward, loss, dz chain, SGD) is enqueued on a HIGH-priority HIP stream; the
         weight-gradient GEMMs run beside it on a normal-priority stream (engine.backward), so the chain's kernels get
         compute units first (A/B tools/archive/ab_prio.py: -0.8 % step time).  The caller's current stream is joined on both
-        sides, so the usual stream semantics hold for inputs and outputs."""
+        sides, so the usual stream semantics hold for inputs and outputs.
+
+        Soft targets (bdn_criterion_soft; fabric_amd.criterion's module docstring), with a Criterion only: `weights`, float32 [B,H,W] pixel
+        weights, and / or float32 [B,C,H,W] `labels`, taken as per-pixel target distributions; a Criterion with label_smoothing takes that
+        route with plain labels.  Nothing else in the step changes -- accumulation, SAM (both passes see the same targets and weights),
+        clipping, averaging, frozen BatchNorm, parameter groups and data-parallel runs sit behind dlogits; data-parallel, each rank
+        normalises by its own valid count.  `last_counts` has five entries, {TP, FP, FN, correct, valid}, `last_terms` its usual length."""
         self._not_swapped('step()')
         self._check_bound()
+        if self.criterion is None and (weights is not None or (labels.is_floating_point() and labels.dim() == 4 and labels.shape[1] > 1)):
+            raise ValueError('the default step (criterion=None, bdn_tversky) takes class-index labels only: give TrainStep a criterion, '
+                             "e.g. criterion='tversky', to train on weights or float targets")
+        self._weights = weights
+        try:
+            return self._step_streams(x_d1, x_d2, labels)
+        finally:
+            self._weights = None
+
+    def _step_streams(self, x_d1, x_d2, labels):
         if self._guard and self.collectives_report is None and self.bucketer.active():
             # measure only: the caller may already run its loop on step.stream(), which must not be swapped under it
             self.guard_collectives(*[int(v) for v in (x_d1.shape[0], x_d1.shape[2], x_d1.shape[3])], replace_streams=False)
@@ -870,9 +887,16 @@ class TrainStep:
         """An explicit criterion: bdn_criterion on persistent buffers sized once per shape -> (loss, counts, dlogits); sets last_terms
         and last_dlogits (the gradient this step's backward starts from)."""
         shape = tuple(logits.shape)
-        if self._tv is None or self._tv[1] != shape:
-            self._tv = (self.criterion.buffers(shape, logits.device), shape)
-        loss, terms, counts, dlogits = self.criterion.evaluate(logits, labels, out=self._tv[0])
+        weights = self._weights
+        if weights is None and not (labels.is_floating_point() and tuple(labels.shape) == shape):
+            # the step as it always was (a criterion with label_smoothing: its buffers() are the soft route's)
+            if self._tv is None or self._tv[1] != shape:
+                self._tv = (self.criterion.buffers(shape, logits.device), shape)
+            loss, terms, counts, dlogits = self.criterion.evaluate(logits, labels, out=self._tv[0])
+        else:                                                                  # weights / float targets: the soft route's buffers, kept apart
+            if self._tv_soft is None or self._tv_soft[1] != shape:
+                self._tv_soft = (self.criterion.buffers(shape, logits.device, soft=True), shape)
+            loss, terms, counts, dlogits = self.criterion.evaluate(logits, labels, out=self._tv_soft[0], weights=weights)
         self.last_terms, self.last_dlogits = terms, dlogits
         return loss, counts, dlogits
 

@@ -50,7 +50,7 @@ def get_criterion(opt):
 def criterion_from_opt(opt):
     """fabric_amd.criterion.Criterion of the --loss_function / --tversky_alpha / --tversky_beta / --focal_gamma / --focal_alpha /
     --loss_weights (W_FOCAL W_OVERLAP; focal+lovasz: W_FOCAL W_LOVASZ) / --ignore_label / --loss_topk / --lovasz_classes /
-    --boundary_weight / --boundary_classes / --boundary_max_dist options; ValueError as Criterion.parse raises it."""
+    --boundary_weight / --boundary_classes / --boundary_max_dist / --label_smoothing options; ValueError as Criterion.parse raises it."""
     from ..criterion import Criterion
     return Criterion.parse(opt.loss_function, tversky_alpha=getattr(opt, 'tversky_alpha', 0.5), tversky_beta=getattr(opt, 'tversky_beta', 0.5),
                            focal_gamma=getattr(opt, 'focal_gamma', None), focal_alpha=getattr(opt, 'focal_alpha', None),
@@ -58,7 +58,8 @@ def criterion_from_opt(opt):
                            topk=getattr(opt, 'loss_topk', None), lovasz_classes=getattr(opt, 'lovasz_classes', 'present'),
                            w_boundary=getattr(opt, 'boundary_weight', None) or 0.0,
                            boundary_classes=getattr(opt, 'boundary_classes', 'foreground'),
-                           boundary_max_dist=getattr(opt, 'boundary_max_dist', None))
+                           boundary_max_dist=getattr(opt, 'boundary_max_dist', None),
+                           label_smoothing=getattr(opt, 'label_smoothing', None) or 0.0)
 
 
 def get_loaders(opt):

@@ -148,9 +148,10 @@ class _CriterionFunction(torch.autograd.Function):
     """fabric_amd.criterion.Criterion.evaluate as one autograd node; without a gradient to compute no gradient pass is launched."""
 
     @staticmethod
-    def forward(ctx, logits, labels, criterion, holder):
+    def forward(ctx, logits, labels, criterion, holder, weights=None):
         want = ctx.needs_input_grad[0]
-        loss, terms, counts, dl = criterion.evaluate(logits.detach().contiguous().float(), labels.detach(), want_grad=want)
+        kw = {} if weights is None else {'weights': weights.detach()}
+        loss, terms, counts, dl = criterion.evaluate(logits.detach().contiguous().float(), labels.detach(), want_grad=want, **kw)
         if want:
             ctx.save_for_backward(dl)
         holder['counts'], holder['terms'] = counts, terms
@@ -159,7 +160,7 @@ class _CriterionFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        return dl * g, None, None, None
+        return dl * g, None, None, None, None
 
 
 class CompoundLoss(nn.Module):
@@ -167,15 +168,17 @@ class CompoundLoss(nn.Module):
     the module form for validation and the autograd route.  The criterion's `reduce` decides the overlap reduction, not the label
     rank.  A criterion with a topk (bdn_criterion_topk) runs here as any other: the selection is a constant for the gradient; so does one
     with a w_lovasz (bdn_lovasz_softmax): the order is a constant for the gradient; and one with a w_boundary (bdn_boundary_loss): the
-    signed distance is a constant for the gradient, last_terms[-1] the unweighted boundary value."""
+    signed distance is a constant for the gradient, last_terms[-1] the unweighted boundary value.  Soft targets (bdn_criterion_soft) come
+    in as they do in Criterion.evaluate: a criterion with label_smoothing, `weights` (float32 [B,H,W]) beside the labels, or float32
+    [B,C,H,W] targets as `true`; targets and weights are constants for the gradient, last_counts is int32[5] on that route."""
 
     def __init__(self, criterion):
         super(CompoundLoss, self).__init__()
         self.criterion = criterion
         self._holder = {}
 
-    def forward(self, logits, true):
-        return _CriterionFunction.apply(logits, true, self.criterion, self._holder)
+    def forward(self, logits, true, weights=None):
+        return _CriterionFunction.apply(logits, true, self.criterion, self._holder, weights)
 
     @property
     def last_counts(self):
@@ -194,7 +197,8 @@ def confusion_counts(logits, labels, ignore_index=None):
     """int32[4] device tensor {TP, FP, FN, correct} of argmax(logits, 1) vs labels (what train.py:96-106 hands to sklearn),
     for criteria that do not report it themselves: one pass of the overlap-loss kernel, loss and gradient discarded.
     ignore_index: a label byte 0..255 -> int32[5] = {TP, FP, FN, correct, valid} over the pixels whose label is not ignore_index
-    (the statistics and finish passes of bdn_criterion_masked)."""
+    (the statistics and finish passes of bdn_criterion_masked).  Hard labels only: the counts of soft targets (argmax_c q_c as the pixel's
+    class, the pixels with weight > 0) are the `counts` of Criterion.evaluate on that route."""
     if ignore_index is not None:
         from ..criterion import Criterion
         lg = logits.detach().contiguous().float()

@@ -560,6 +560,41 @@ int bdn_criterion_topk(const float* logits, const uint8_t* labels, int ignore_la
                        float* loss, float* terms, int32_t* counts, float* dlogits, float* pixel_terms, uint8_t* kept,
                        int B, int ncls, int H, int W, void* stream);
 
+/* ---- the criterion on soft targets: label smoothing, pixel weights, probability maps (the reference has none) ----
+ * bdn_criterion_masked's function with a target q_c >= 0 per class and a weight w >= 0 per pixel in place of one class index; v = [w > 0],
+ * p = softmax(logits).  Exactly one of `labels` and `targets` is given:
+ *   labels   uint8 [B,H,W]: lo = smoothing / ncls and hi = (1 - smoothing) + lo, float32 operations of one rounding each; q_c = hi at the
+ *            label's class and lo elsewhere (smoothing in [0, 1); 0 gives the one-hot target).  A valid label >= ncls has q = 0 for every
+ *            class ("labels outside the classes", bdn_tversky: no smoothing mass).  ignore_label: -1 (none) or a byte value, w = 0 there.
+ *   targets  f32 [B,ncls,H,W]: q as given; smoothing must be 0 and ignore_label -1.  Negative or non-finite targets at a valid pixel are
+ *            the caller's error: nothing looks for them.
+ *   weights  NULL (w = 1 at every pixel that is not ignored) or f32 [B,H,W], multiplied into w.
+ *   Overlap  TP_c = sum w p_c q_c, FP_c = sum w p_c (1 - q_c), FN_c = sum w (1 - p_c) q_c over the cells of reduce_w;
+ *            O = 1 - mean TP / (TP + alpha FP + beta FN + eps); a cell without a valid pixel has the ratio 0 / eps = 0.
+ *   Focal    per pixel f = sum_c [q_c > 0] q_c a_c m_c (-log p_c), m_c = max(1 - p_c, 0)^gamma a constant for the gradient (1 at gamma
+ *            0), log p_c = (l_c - max) - log sum exp(l - max); a class with q_c == 0 is selected out, 0 * log 0 is never formed.
+ *            F = scale * sum w f; scale = 1 / n_valid with size_average (1 when n_valid = 0: the sum is then 0), else 1.  n_valid is the
+ *            NUMBER of pixels with w > 0, not the sum of the weights: 0 / 1 weights are ignore_label exactly.
+ *   loss     w_overlap O + w_focal F; a term with weight 0 is selected out and reported as 0.  terms: NULL or f32[2] = {O, F}.
+ *   counts   NULL or int32[5] = {TP, FP, FN, correct, valid}: argmax(logits) against the pixel's class -- the label, or argmax_c q_c --
+ *            over the valid pixels, class 1 positive, the first maximum on both sides.
+ *   dlogits  NULL (no gradient pass) or f32 [B,ncls,H,W]: the gradient, exactly 0.0f for every class at a pixel with v = 0 (written).
+ * A pixel with v = 0 is skipped by a branch before any of its logits or targets is used: inf and NaN there reach no output.  A batch
+ * without a valid pixel gives O = 1, F = 0, zero gradient and zero counts.
+ * Always three launches (two without dlogits): statistics (softmax once per pixel; overlap block partials in float32, the focal partial
+ * in double, the counters), a single-block fixed-order finish that leaves the coefficient tables and the focal scale in the workspace,
+ * and the gradient pass.  No atomics, no memset, no host read-back: the same bits every run, whatever the workspace held.  With labels
+ * the passes read what bdn_criterion_masked's read (plus the weight map if there is one); targets are 4 ncls more bytes per pixel.
+ * BDN_E_ARG before any launch: not exactly one of labels / targets; smoothing outside [0, 1) or NaN, or != 0 with targets; ignore_label
+ * outside -1..255, or != -1 with targets; a negative weight or both zero; negative gamma; ws, loss or logits NULL; ws not 16-byte
+ * aligned or a float32 / int32 pointer not 4-byte aligned.  ws: bdn_criterion_soft_workspace_bytes() bytes (0 outside ncls 2..8 or with
+ * B*H*W >= 2^31).  Data-parallel: each rank normalises by its own valid count. */
+size_t bdn_criterion_soft_workspace_bytes(int B, int ncls, int H, int W, int reduce_w);
+int bdn_criterion_soft(const float* logits, const uint8_t* labels, const float* targets, const float* weights, int ignore_label,
+                       float smoothing, float w_overlap, float alpha, float beta, float eps, int reduce_w, float w_focal, float gamma,
+                       const float* class_alpha, int size_average, void* ws, float* loss, float* terms, int32_t* counts, float* dlogits,
+                       int B, int ncls, int H, int W, void* stream);
+
 /* ---- the Lovasz-Softmax term (Berman, Rahman Triki, Blaschko, CVPR 2018; the reference has none) ----
  * The loss that optimises the Jaccard index itself, batch level (the paper's per_image = False): an add-on term of the criterion of a run,
  * utils/helpers.py:303-312, the loss selection it extends.  ignore_label: -1 (no pixel is ignored) or a byte value 0..255.
