@@ -23,8 +23,22 @@
 // stores the activation; optional date product / 2x2 max-pool / 1x1 classifier + argmax + stitching from the tile in LDS; date-paired
 // tiles), X3 (round 6, bf16x3: hi and lo patches of a chunk in LDS, the terms of the split product into one accumulator) and XF (X3 on a
 // float32 source: BatchNorm+ReLU and the hi / lo split inside the staging).
+// Round 7: two block-uniform fast paths of the training launches, bit-identical to the general code they skip (bdn_conv3x3_force_general turns
+// them off; tests/test_gpu_conv_interior.py compares): a tile whose whole halo lies inside the image stages its patch without validity
+// tests, fallback addresses, zero fill or exec-mask branches (single-chunk and BB kernels, which stage once), and a full tile copies out
+// without bounds tests.  The same staging path inside the multi-chunk main loop and paired accumulator stores were measured and not kept
+// (profiles/conv_interior_ab.txt).
 #include "common.hpp"
 #include <type_traits>
+
+// Compile-time switches of the round-7 prologue / epilogue trims, so that each can be built out and A/B'ed on its own
+// (tools/build_lib_variant.sh --only conv3x3 name "-DBDN_CONV_INTERIOR=0"); profiles/conv_interior_ab.txt has the measurements.
+#ifndef BDN_CONV_INTERIOR
+#define BDN_CONV_INTERIOR 1          // interior fast path of the training launches that stage once (single-chunk and BB kernels)
+#endif
+#ifndef BDN_CONV_FULLCOPY
+#define BDN_CONV_FULLCOPY 1          // full tiles: copy-out without bounds tests
+#endif
 
 struct ConvArgs {
     const void* in0; const void* in1; int C0, C1;
@@ -78,6 +92,8 @@ struct ConvArgs {
     // (optional, [N,H,W,2 C0] bf16 = hi | lo): the blocks of column tile 0 also store their tile's own pixels of the split operand there,
     // for the layer's weight-gradient GEMM (what bdn_split_pack would have written).
     void* x3_split;
+    // bdn_conv3x3_force_general (tests): every block takes the general path -- no interior staging, no full-tile copy-out
+    int force_general;
 };
 
 template <typename T> struct Mma;
@@ -174,7 +190,12 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
 
     // eval-mode kernels (above all the full-resolution 64-channel layers: instruction-issue bound, 14.8 instructions per MFMA of which
     // three quarters are prologue and epilogue): tiles whose halo lies inside the image stage their patches without bounds tests / zero fill
-    const bool interior = EV && y0 >= 1 && x0 >= 1 && y0 + TH + 1 <= a.H && x0 + TW + 1 <= a.W && n0 + (TI - 1) * istr < a.N;
+    // training launches (round 7): the same block-uniform fast path.  At 128x128 36 of 64 16x16 tiles and 84 of 128 8x16 tiles are interior;
+    // their staging carries no validity test, fallback address, zero fill or exec-mask branch per unit.  Border tiles run the general code.
+    // Not for 3x3x3 launches (depth masks) and the fused split product (its own staging macros).
+    constexpr bool INTR = EV || (BDN_CONV_INTERIOR && !D3 && X3 == 0 && (ONE || BB));
+    const bool fast = a.force_general == 0;                                   // block-uniform (bdn_conv3x3_force_general)
+    const bool interior = INTR && fast && y0 >= 1 && x0 >= 1 && y0 + TH + 1 <= a.H && x0 + TW + 1 <= a.W && n0 + (TI - 1) * istr < a.N;
     // ---- activation patch: every thread owns NPU 16-byte units whose pixel / LDS offsets never change
     int p_pix[NPU];                                      // global pixel index of each unit (-1 = zero padding)
     {
@@ -234,7 +255,7 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
            are zeroed at the store */                                                                   \
         const unsigned char* sb_ = reinterpret_cast<const unsigned char*>(src_ + cs_);                  \
         const unsigned cb_ = (unsigned)Cs_ * CF::ES;                                                    \
-        if (EV && interior) {                              /* block-uniform: every unit's pixel is inside the image */ \
+        if (interior) {                                    /* block-uniform: every unit's pixel is inside the image */ \
             _Pragma("unroll") for (int i = 0; i < NPU; i++)                                              \
                 preg[i] = *reinterpret_cast<const uint4*>(sb_ + ((unsigned)p_pix[i] * cb_ + p_subb));   \
         } else {                                                                                        \
@@ -244,8 +265,13 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
         if constexpr (BB) {                                                                             \
             const unsigned char* zb_ = reinterpret_cast<const unsigned char*>(reinterpret_cast<const T*>(a.bb_z) + (c0_)); \
             const unsigned zc_ = (unsigned)a.C0 * CF::ES;                                               \
-            _Pragma("unroll") for (int i = 0; i < NPU; i++)                                              \
-                pregz[i] = *reinterpret_cast<const uint4*>(zb_ + ((unsigned)(p_pix[i] >= 0 ? p_pix[i] : 0) * zc_ + p_subb)); \
+            if (interior) {                                                                             \
+                _Pragma("unroll") for (int i = 0; i < NPU; i++)                                          \
+                    pregz[i] = *reinterpret_cast<const uint4*>(zb_ + ((unsigned)p_pix[i] * zc_ + p_subb)); \
+            } else {                                                                                    \
+                _Pragma("unroll") for (int i = 0; i < NPU; i++)                                          \
+                    pregz[i] = *reinterpret_cast<const uint4*>(zb_ + ((unsigned)(p_pix[i] >= 0 ? p_pix[i] : 0) * zc_ + p_subb)); \
+            }                                                                                           \
         }                                                                                               \
     }
 #define STORE_PATCH(c0_, buf_)                                                                           \
@@ -283,13 +309,22 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
                 _Pragma("unroll") for (int e = 0; e < EPU; e++)                                          \
                     o_[e] = fmaf(fg_[e], bk_[0][e], fmaf(fz_[e], bk_[1][e], bk_[2][e]));                 \
                 preg[i] = Unit<T>::pack(o_);                                                            \
-                if (a.bb_dz != nullptr && ntile == 0 && p_pix[i] >= 0) {      /* the tile's own pixels: the weight-gradient GEMM reads them */ \
+                /* the tile's own pixels: the weight-gradient GEMM reads them.  (interior tiles: every patch pixel exists, the tail units behind the patch do not) */ \
+                if (a.bb_dz != nullptr && ntile == 0 && (interior ? tid + i * 256 < TL::NPIX * UPP : p_pix[i] >= 0)) { \
                     const int u_ = tid + i * 256, pix_ = u_ / UPP, xx_ = pix_ % TL::PW, yy_ = (pix_ / TL::PW) % TL::PH;   \
                     if (xx_ >= 1 && xx_ <= TW && yy_ >= 1 && yy_ <= TH)                                  \
                         *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(a.bb_dz) + ((unsigned)p_pix[i] * ((unsigned)a.C0 * CF::ES) + (unsigned)(bc_) * CF::ES + p_subb)) = preg[i]; \
                 }                                                                                       \
             }                                                                                           \
         }                                                                                               \
+        if (!EV && interior) {                             /* block-uniform: halo inside the image -- no compare, select or exec branch per unit */ \
+            _Pragma("unroll") for (int i = 0; i < NPU; i++) {                                            \
+                const int u_ = tid + i * 256;                                                           \
+                const int pix_ = u_ / UPP, xx_ = pix_ % TL::PW, t_ = pix_ / TL::PW;                      \
+                if (BRANCHFREE || (i + 1) * 256 <= TL::NPIX * UPP || u_ < TL::NPIX * UPP)               \
+                    *reinterpret_cast<uint4*>(pb_ + t_ * ROWP + xx_ * PSTR + (u_ % UPP) * 16) = bn_ ? bnrelu_unit<T>(preg[i], sc_, sh_) : preg[i]; \
+            }                                                                                           \
+        } else                                                                                          \
         _Pragma("unroll") for (int i = 0; i < NPU; i++) {                                                \
             const int u_ = tid + i * 256;                  /* LDS offset recomputed: cheaper than 11 live registers */ \
             const int pix_ = u_ / UPP, xx_ = pix_ % TL::PW, t_ = pix_ / TL::PW;                          \
@@ -806,14 +841,28 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
     }
     unsigned oofs[NPRE];
     uint4 zq[NPRE];
+    // full tiles (block-uniform; every tile of the flagship launches): the copy-out offsets carry no bounds tests, the units no "outside" branch
+    const bool full_copy = BDN_CONV_FULLCOPY && PRE && full_tile && fast;
     if (PRE) {
+        if (full_copy) {
 #pragma unroll
-        for (int i = 0; i < NPRE; i++) OUT_OFS(i, oofs[i])
+            for (int i = 0; i < NPRE; i++) {
+                const int u_ = tid + i * 256, slot_ = u_ / UPR, sub_ = u_ % UPR;
+                int ti_, py_, px_; TL::slot_to_nyx(slot_, ti_, py_, px_);
+                oofs[i] = (unsigned)(((n0 + ti_) * a.H + y0 + py_) * a.W + x0 + px_) * orow + (unsigned)sub_ * 16u;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) OUT_OFS(i, oofs[i])
+        }
     }
     if (bs) {
         // the z units are requested HERE, a whole accumulator pass ahead of their use: inside the copy-out loop every one of them
         // was a dependent HBM round trip behind the store before it (eight per block)
-        if (PRE) {
+        if (PRE && full_copy) {
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) zq[i] = *reinterpret_cast<const uint4*>(bsz + oofs[i]);
+        } else if (PRE) {
 #pragma unroll
             for (int i = 0; i < NPRE; i++) zq[i] = *reinterpret_cast<const uint4*>(bsz + (oofs[i] != 0xffffffffu ? oofs[i] : 0u));
         }
@@ -867,8 +916,9 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
     }
     // copy-out: the tile leaves LDS in 16-byte NHWC units; the offsets were computed (and, for data-gradient launches with the
     // BatchNorm-backward statistics, the z units requested) before the accumulator pass
-#define COPY_UNIT(i_, o_, zexpr_)                                                                        \
-    if ((o_) != 0xffffffffu) {                                                                          \
+#define COPY_UNIT(i_, o_, zexpr_) if ((o_) != 0xffffffffu) COPY_BODY(i_, o_, zexpr_)
+#define COPY_BODY(i_, o_, zexpr_)                                                                        \
+    {                                                                                                   \
         const int u_ = tid + (i_) * 256;                                                                \
         uint4 v = *reinterpret_cast<const uint4*>(otile + (u_ / UPR) * CF::OSTR + (u_ % UPR) * 16);     \
         if (bs) {                                            /* the stored (rounded) gradient is what BatchNorm backward sees; it leaves */ \
@@ -885,8 +935,13 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
         *reinterpret_cast<uint4*>(outp + (o_)) = v;                                                     \
     }
     if constexpr (PRE) {
+        if (full_copy) {
 #pragma unroll
-        for (int i = 0; i < NPRE; i++) COPY_UNIT(i, oofs[i], zq[i])
+            for (int i = 0; i < NPRE; i++) COPY_BODY(i, oofs[i], zq[i])
+        } else {
+#pragma unroll
+            for (int i = 0; i < NPRE; i++) COPY_UNIT(i, oofs[i], zq[i])
+        }
     } else {
 #pragma unroll 1
         for (int i = 0; i < NIT; i++) {
@@ -895,6 +950,7 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
         }
     }
 #undef COPY_UNIT
+#undef COPY_BODY
 #undef OUT_OFS
     if (bs) {
         // lanes tid, tid+UPR, ... of a wave hold the same channels: butterfly over those lane bits, then the four
@@ -926,6 +982,9 @@ __global__ __launch_bounds__(256, (!BB && sizeof(TO) == sizeof(T) && ((ONE && BN
 // its name here (one source of truth for profilers that have to match rocprofv3 kernel names)
 static thread_local bool g_conv_query = false;
 static thread_local char g_conv_variant[160];
+// bdn_conv3x3_force_general: every launch of this thread takes the general path (tests compare the two paths bit for bit)
+static thread_local int g_conv_force_general = 0;
+extern "C" int bdn_conv3x3_force_general(int on) { const int was = g_conv_force_general; g_conv_force_general = on ? 1 : 0; return was; }
 
 template <typename T, int CKB, int TH, int TW, int TI, int BN, int WM, int WN, bool ONE = false, typename TO = T, bool D3 = false, bool BB = false, bool EV = false, int X3 = 0, bool XF = false>
 static int launch_conv(const ConvArgs& a, int n_mtiles, hipStream_t st) {
@@ -946,6 +1005,7 @@ static int launch_conv(const ConvArgs& a, int n_mtiles, hipStream_t st) {
     const int smem_bytes = (CF::MAIN_BYTES + xf_tab > CF::SMEM) ? CF::MAIN_BYTES + xf_tab : CF::SMEM;
     ConvArgs b = a;
     b.n_ntiles = a.Cout / BN;
+    b.force_general = g_conv_force_general;
     hipLaunchKernelGGL(kern, dim3(n_mtiles * b.n_ntiles), dim3(256), smem_bytes, st, b);
     BDN_CHECK_LAUNCH("conv3x3");
     return BDN_OK;

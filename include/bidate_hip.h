@@ -101,6 +101,10 @@ int bdn_conv3x3_num_mtiles_ex(int dtype, int N, int H, int W, int C0, int Cout, 
 /* Name of the kernel instantiation bdn_conv3x3 runs for a shape, e.g. "conv3x3_kernel<bf16,128,8,16,1,128,1,4,false,bf16,false,false>"
  * (the rocprofv3 name with `unsigned short` spelled bf16); "" for an unsupported shape.  Thread-local buffer. */
 const char* bdn_conv3x3_variant(int dtype, int N, int H, int W, int C0, int C1, int Cout, int imgs_per_group);
+/* Test hook: while on (non-zero), every conv3x3 launch of the calling thread -- forward, data gradient, eval mode -- takes the kernels' general
+ * path: no interior-tile staging, no full-tile copy-out.  Both paths compute the same bits; the tests compare
+ * them.  Thread-local, off by default; returns the previous setting. */
+int bdn_conv3x3_force_general(int on);
 
 /* bf16x3 / bf16x2 convolution straight from a FLOAT32 operand (reference: models/unet_parts.py:14-16, BatchNorm -> ReLU -> Conv2d of a
  * double_conv's second half; round 6).  Equals bdn_split_pack(in, in_mode, in_bn) followed by bdn_conv3x3(dtype, ...) bit for bit, in one

@@ -1,5 +1,5 @@
 """Micro-benchmark (test infrastructure): times every conv3x3 (fwd + dgrad) and wgrad launch shape of one
-BiDateNet(13,2) B=64 128x128 bf16 step through the C ABI, with HIP events.  python tools/bench_conv.py [conv|wgrad|all]"""
+BiDateNet(13,2) B=64 128x128 bf16 step through the C ABI, with HIP events.  [ITERS=5] [B=64] [BS=1] python tools/bench_conv.py [conv|wgrad|all]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -26,7 +26,7 @@ for L in build_layers(13):
     if L.name != 'e1a':
         shapes.append((L.name + ' dgrad', n, h, w, L.cout, 0, L.cin, 0))
 
-def timeit(fn, iters=5):
+def timeit(fn, iters=int(os.environ.get('ITERS', 5))):
     fn(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
