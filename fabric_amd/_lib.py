@@ -175,6 +175,11 @@ SIGNATURES = {
     'bdn_signed_distance': (_i, [_vp, _i, _i, _f, _vp, _vp, _i, _i, _i, _vp]),
     'bdn_boundary_mask': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     'bdn_boundary_score': (_i, [_vp, _vp, C.c_longlong, _vp, _i, _i, _vp]),
+    'bdn_cc_mark': (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    'bdn_cc_select': (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    'bdn_d2_mask': (_i, [_vp, _i, _i, _vp, C.c_longlong, _vp]),
+    'bdn_threshold_pair': (_i, [_vp, _i, _f, _f, _vp, _vp, _i, C.c_longlong, _vp]),
+    'bdn_mask_not': (_i, [_vp, _vp, C.c_longlong, _vp]),
     'bdn_shift_corr_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
     'bdn_shift_corr': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     'bdn_shift_peak': (_i, [_vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp]),

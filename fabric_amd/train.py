@@ -488,6 +488,40 @@ def check_object_flags(scene_min_area, scene_objects, scene_connectivity, scene_
     return scene_min_area if scene_min_area > 0 else None
 
 
+def check_cleanup_flags(scene_hysteresis, scene_close, scene_fill_holes, scene_open, scene_threshold, scene_connectivity, scene_stride):
+    """--scene_hysteresis / --scene_close / --scene_fill_holes / --scene_open with --scene_threshold (as check_curve_flags returns it) /
+    --scene_connectivity / --scene_stride, without a device: returns None when all four are off, else the keyword arguments of
+    predict_scene_blended {hysteresis_low, close_radius2, fill_holes, open_radius2} (None = off); raises ValueError with the reason
+    otherwise.  With --scene_threshold val the high threshold is known only after the validation pass: predict_scene_blended refuses a
+    low threshold above it then."""
+    if scene_hysteresis is None and scene_close is None and scene_open is None and scene_fill_holes == 0:
+        return None
+    if scene_stride <= 0:
+        raise ValueError('--scene_hysteresis / --scene_close / --scene_fill_holes / --scene_open clean the blended scene masks: add --scene_stride N > 0')
+    if scene_fill_holes < -1:
+        raise ValueError(f'--scene_fill_holes {scene_fill_holes}: 0 (off), -1 (every hole) or the largest hole filled, in pixels')
+    if scene_hysteresis is not None and scene_threshold == 'argmax':
+        raise ValueError('--scene_hysteresis LOW keeps weak change that hangs on change above --scene_threshold: add --scene_threshold val|FLOAT')
+    from .utils.morphology import check_cleanup_args
+    fill = None if scene_fill_holes == 0 else True if scene_fill_holes == -1 else scene_fill_holes
+    high = 1.0 if scene_threshold == 'val' else None if scene_threshold == 'argmax' else scene_threshold
+    try:
+        check_cleanup_args(high, scene_hysteresis, scene_close, fill, scene_open, scene_connectivity)
+    except ValueError as e:
+        raise ValueError(f'--scene_hysteresis / --scene_close / --scene_fill_holes / --scene_open: {e}')
+    return {'hysteresis_low': scene_hysteresis, 'close_radius2': scene_close, 'fill_holes': fill, 'open_radius2': scene_open}
+
+
+def cleaned_scores(mask, label, ignore_label=None):
+    """scene_scores of the cleaned mask that is written, the pixels with label == ignore_label left out."""
+    m, l = np.asarray(mask) == 1, np.asarray(label)
+    keep = np.ones(l.shape, bool) if ignore_label is None else l != ignore_label
+    pos = (l != 0) & keep
+    counts = np.array([(m & pos).sum(), (m & ~pos & keep).sum(), (~m & pos).sum()])
+    pr, rc, f1 = batch_prf_from_counts(counts)
+    return {'tp': int(counts[0]), 'fp': int(counts[1]), 'fn': int(counts[2]), 'precision': pr, 'recall': rc, 'f1': f1}
+
+
 def check_boundary_flags(boundary_weight, boundary_classes, boundary_max_dist, fused_step, scene_boundary_tol, scene_stride):
     """--boundary_weight / --boundary_classes / --boundary_max_dist / --fused_step and --scene_boundary_tol / --scene_stride together,
     without a device: returns the tolerance for boundary_scores (None: the scene line stays as it is); raises ValueError with the reason
@@ -854,7 +888,19 @@ def main(argv=None):
                     help='--scene_stride N > 0: the scene line gains objects_pred, objects_true, object_precision, object_recall, object_f1 '
                          'and min_area (object_scores on the unfiltered mask with min_area = --scene_min_area; --ignore_label pixels are cut out '
                          'before the areas are measured)')
-    ap.add_argument('--scene_connectivity', type=int, default=8, choices=[4, 8], help='connectivity of --scene_min_area / --scene_objects')
+    ap.add_argument('--scene_connectivity', type=int, default=8, choices=[4, 8],
+                    help='connectivity of --scene_min_area / --scene_objects / --scene_hysteresis / --scene_fill_holes')
+    ap.add_argument('--scene_hysteresis', type=float, default=None, metavar='LOW',
+                    help='--scene_stride N > 0 with --scene_threshold val|FLOAT: P(change) >= LOW is kept where its connected component reaches '
+                         'P(change) >= the threshold (hysteresis_mask, on the device); LOW <= the threshold')
+    ap.add_argument('--scene_close', type=int, default=None, metavar='R2',
+                    help='--scene_stride N > 0: the scene mask is closed with the disc dy^2 + dx^2 <= R2 on the device (binary_closing)')
+    ap.add_argument('--scene_fill_holes', type=int, default=0, metavar='N',
+                    help='--scene_stride N > 0: holes of the scene mask are filled on the device (fill_holes): -1 every hole, N > 0 the holes '
+                         'of at most N pixels; 0: off')
+    ap.add_argument('--scene_open', type=int, default=None, metavar='R2',
+                    help='--scene_stride N > 0: the scene mask is opened with the disc dy^2 + dx^2 <= R2 on the device (binary_opening).  Order: '
+                         'threshold or hysteresis, closing, hole filling, opening, --scene_min_area; the scene line gains cleanup and cleaned')
     ap.add_argument('--coregister', type=int, default=0, metavar='R',
                     help='align date 2 of every city to its date 1 once after loading, on the device (utils/registration.py): the shift is '
                          'searched over +-R pixels (1..16) by normalised cross-correlation and date 2 is resampled bilinearly; 0: off.  '
@@ -979,6 +1025,8 @@ def main(argv=None):
     try:
         scene_thr = check_curve_flags(opt.val_curve_bins, opt.scene_threshold, opt.scene_stride)
         scene_min_area = check_object_flags(opt.scene_min_area, opt.scene_objects, opt.scene_connectivity, opt.scene_stride)
+        scene_cleanup = check_cleanup_flags(opt.scene_hysteresis, opt.scene_close, opt.scene_fill_holes, opt.scene_open, scene_thr,
+                                            opt.scene_connectivity, opt.scene_stride)
     except ValueError as e:
         raise SystemExit(str(e))
     try:
@@ -1123,6 +1171,8 @@ def main(argv=None):
         run_meta['radiometric'] = dict(radiom)
     if opt.label_smoothing:                                # the criterion's smoothed targets: --resume reads it back
         run_meta['label_smoothing'] = opt.label_smoothing
+    if scene_cleanup is not None:                          # how the scene masks written beside this checkpoint were cleaned
+        run_meta['scene_cleanup'] = dict(scene_cleanup, connectivity=opt.scene_connectivity)
     schedule = None
     if scheduled:                                          # host floats only; its position comes from (epoch, batch), so --resume continues it
         from .schedule import LRSchedule
@@ -1155,7 +1205,8 @@ def main(argv=None):
             if scenes is not None and rank == 0:               # train.py:182-205: full validation images
                 _predict_scenes(model, scenes, val_cities, opt, epoch, va['best_threshold'] if scene_thr == 'val' else
                                 None if scene_thr == 'argmax' else scene_thr, min_area=scene_min_area,
-                                **({} if scene_boundary_tol is None else {'boundary_tol': scene_boundary_tol}))
+                                **({} if scene_boundary_tol is None else {'boundary_tol': scene_boundary_tol}),
+                                **({} if scene_cleanup is None else {'cleanup': scene_cleanup}))
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
                                   step.optimizer_state_dict() if fused else optimizer.state_dict(),
@@ -1166,7 +1217,7 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_area=None, boundary_tol=None):
+def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_area=None, boundary_tol=None, cleanup=None):
     """train.py:182-205: the full validation scenes of one epoch, written as PNG masks (and, blended, as probabilities with a scene F1 line).
     threshold (--scene_threshold): None = the argmax masks, else the masks are P(change) >= threshold.  With --val_curve_bins the scene
     line of every city comes from a ScoreCurve over its probabilities and label raster (the run's --ignore_label left out), on the device:
@@ -1177,7 +1228,11 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
     object_scores(mask, truth, ignore_index=--ignore_label, min_area=min_area): the ignore pixels are cut out BEFORE the areas are
     measured, so a component held above min_area only by pixels inside the ignore region is no object, although the PNG keeps it.
     boundary_tol (--scene_boundary_tol, from check_boundary_flags): the scene line gains boundary_precision, boundary_recall, boundary_f1,
-    hausdorff and boundary_tol from boundary_scores(the mask that is written, truth, boundary_tol, ignore_index=--ignore_label)."""
+    hausdorff and boundary_tol from boundary_scores(the mask that is written, truth, boundary_tol, ignore_index=--ignore_label).
+    cleanup (--scene_hysteresis / --scene_close / --scene_fill_holes / --scene_open, from check_cleanup_flags): the keyword arguments of
+    predict_scene_blended that clean the mask on the device, before the area filter: --scene_objects then scores the mask after the
+    opening.  The scene line gains cleanup (the settings) and cleaned = {tp, fp, fn, precision, recall, f1} of the mask that is written
+    against the labels (--ignore_label left out): with --val_curve_bins the other counts come from the probabilities."""
     from .utils import ingest
     from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
     os.makedirs(opt.log_dir, exist_ok=True)
@@ -1191,7 +1246,9 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
             proba, mask = predict_scene_blended(model, st[0], st[1], patch_size=opt.patch_size, stride=opt.scene_stride,
                                                 window=opt.scene_window, symmetries=TTA_SYMMETRIES[opt.scene_tta],
                                                 batch_size=opt.batch_size, **({} if threshold is None else {'threshold': threshold}),
-                                                **({} if min_area is None or objects else {'min_area': min_area, 'connectivity': conn}))
+                                                **({} if min_area is None or objects else {'min_area': min_area}),
+                                                **({} if (min_area is None or objects) and cleanup is None else {'connectivity': conn}),
+                                                **(cleanup or {}))
             raw = mask
             if min_area is not None and objects:             # the unfiltered mask is scored below; the same launches as min_area= above
                 from .utils.objects import remove_small_objects
@@ -1215,6 +1272,9 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
                                                                'object_f1')})
             if min_area is not None or objects:
                 scene_counts[city]['min_area'] = min_area or 1
+            if cleanup is not None:
+                scene_counts[city]['cleanup'] = dict(cleanup)
+                scene_counts[city]['cleaned'] = cleaned_scores(mask.cpu().numpy(), scenes[city]['labels'], getattr(opt, 'ignore_label', None))
             if boundary_tol is not None:
                 from .utils.distance import boundary_scores
                 truth = torch.as_tensor(scenes[city]['labels']).to(device=mask.device, dtype=torch.uint8).contiguous()

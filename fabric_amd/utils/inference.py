@@ -265,7 +265,8 @@ def check_blend_args(h, w, patch_size, stride, window, symmetries, n_classes, ba
 
 @torch.no_grad()
 def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None, window='gaussian', symmetries=(0,), batch_size=64,
-                          band_rows=None, two_streams=None, threshold=None, pos_class=1, min_area=None, connectivity=8):
+                          band_rows=None, two_streams=None, threshold=None, pos_class=1, min_area=None, connectivity=8,
+                          hysteresis_low=None, close_radius2=None, fill_holes=None, open_radius2=None):
     """Class probabilities of a whole scene from overlapping tiles.
 
     Tiles of patch_size at `stride` (default patch_size // 2; blend_tile_origins), each under every code of `symmetries` (codes 0..7 of
@@ -281,10 +282,19 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
     proba[1]: the argmax gives class 0 there (the first maximum), the threshold 0.5 class 1.
     min_area: None: the mask as it is (the launches and the bits of a call without the argument); an integer >= 1: the connected components
     (`connectivity` 4 or 8) of mask == 1 with fewer pixels are removed from the mask (fabric_amd.utils.objects.remove_small_objects, on the
-    current stream behind the finalize / threshold launch, no host read; proba keeps its bits)."""
+    current stream behind the finalize / threshold launch, no host read; proba keeps its bits).
+    hysteresis_low, close_radius2, fill_holes, open_radius2: None: off (all four None: the launches and the bits of a call without them).
+    They clean the mask with fabric_amd.utils.morphology on the current stream, no host read, proba keeps its bits, in this order behind
+    the finalize launch: hysteresis_low (needs threshold, and hysteresis_low <= threshold): the mask is hysteresis_mask(proba,
+    hysteresis_low, threshold, pos_class, connectivity) instead of the plain threshold; close_radius2: binary_closing with that disc;
+    fill_holes (True, or the largest hole area filled): fill_holes under `connectivity`; open_radius2: binary_opening; then min_area."""
     from .metrics import check_threshold
     eng = model.engine()
     threshold, pos_class = check_threshold(threshold, pos_class, eng.n_classes)
+    cleanup = not (hysteresis_low is None and close_radius2 is None and fill_holes is None and open_radius2 is None)
+    if cleanup:
+        from . import morphology
+        morphology.check_cleanup_args(threshold, hysteresis_low, close_radius2, fill_holes, open_radius2, connectivity)
     if min_area is not None:
         from .objects import check_cc_args, remove_small_objects
         check_cc_args(torch.empty(1, 1, dtype=torch.uint8, device='meta'), connectivity, min_area=min_area)
@@ -341,8 +351,12 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
         if feed is not None:
             feed.close()
     _lib.call('bdn_blend_finalize', _lib.ptr(proba), _lib.ptr(wsum), _lib.ptr(mask), ncls, h, w, _lib.stream_ptr())
-    if threshold is not None:
+    if hysteresis_low is not None:
+        morphology.hysteresis_mask(proba, hysteresis_low, threshold, pos_class, connectivity, out=mask)
+    elif threshold is not None:
         _lib.call('bdn_threshold_mask', _lib.ptr(proba), pos_class, threshold, _lib.ptr(mask), ncls, h * w, _lib.stream_ptr())
+    if cleanup:
+        morphology.cleanup_mask(mask, close_radius2, fill_holes, open_radius2, connectivity)
     if min_area is not None:
         remove_small_objects(mask, min_area, connectivity, out=mask)
     return proba, mask

@@ -1049,6 +1049,36 @@ int bdn_boundary_mask(const uint8_t* src, int fg_value, const uint8_t* valid_src
                       void* stream);
 int bdn_boundary_score(const uint8_t* bnd, const int32_t* d2, long long tol2, long long* out, int H, int W, void* stream);
 
+/* ---- cleaning a scene mask: binary reconstruction on bdn_cc_label's labels (hysteresis thresholding, hole filling, border clearing) and
+ * disc morphology as a threshold on bdn_edt's squared distances.  Each replaces a host-side scipy.ndimage call after a device-to-host copy
+ * of the mask of train.py:199 (the reference stops at the pixel mask).  Rasters are [H][W] row-major; 1 <= H, W and H * W <= 2^31 - 2 (the
+ * limits of bdn_cc_label).  Integers only but for the two comparisons of bdn_threshold_pair; a fixed number of launches; nothing is read
+ * back; no loop waits for another thread; every store of a flag stores the same 1, so every output is the same bits on every run.  A null
+ * required pointer, a misaligned one, a value outside its range or a shape outside the limits is BDN_E_ARG before anything touches a
+ * device.  Four pixels per thread where W (n, HW) % 4 == 0 and the pointers are aligned (int32 16, uint8 4 bytes), one otherwise.
+ * bdn_cc_mark (replaces the seed test of scipy.ndimage.binary_propagation / the border test of binary_fill_holes): labels int32 [H][W] as
+ *   bdn_cc_label writes them (0 or 1 + root index).  mark int32 [H][W] (not aliasing labels) is written everywhere by the call: 0, then 1
+ *   at index r if the component rooted at r has a pixel with seed[i] == seed_value (seed uint8 [H][W], NULL: no seed) or, with border != 0,
+ *   a pixel in row 0, row H - 1, column 0 or column W - 1.  Two launches (clear, mark); what mark held before does not matter.
+ * bdn_cc_select (replaces the propagation itself): with sel(i) = labels[i] != 0 and (mark[labels[i] - 1] != 0) == keep_marked and
+ *   min_area <= area[labels[i] - 1] <= max_area,  out[i] (uint8) = (base && base[i] == 1) || sel(i).  mark NULL: no flag test; area NULL
+ *   (bdn_cc_label's areas otherwise): the bounds must be 1 and 2^31 - 1; base NULL: sel alone.  out may alias base.  One launch.
+ * bdn_d2_mask (replaces scipy.ndimage.binary_dilation / binary_erosion with a disc): out[i] (uint8) = greater ? d2[i] > r2 : d2[i] <= r2 for
+ *   n int32 squared distances (bdn_edt with limit r2 + 1 suffices); r2 >= 0, 1 <= n < 2^31.  One launch.
+ * bdn_threshold_pair (replaces two passes of train.py:199's thresholding): mask_low[i] = proba[pos_class][i] >= low and mask_high[i] =
+ *   proba[pos_class][i] >= high (uint8 0 / 1, two different rasters) in one pass over a [ncls][HW] f32 map; a NaN probability gives 0 in
+ *   both.  low / high outside [0, 1], NaN or low > high: BDN_E_ARG.  2 <= ncls <= 256, 1 <= HW <= 2^31 - 2.  One launch.
+ * bdn_mask_not (the background raster that scipy.ndimage.binary_fill_holes labels): out[i] (uint8) = src[i] != 1, 1 <= n < 2^31, out not
+ *   aliasing src.  One launch.
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+int bdn_cc_mark(const int32_t* labels, const uint8_t* seed, int seed_value, int border, int32_t* mark, int H, int W, void* stream);
+int bdn_cc_select(const int32_t* labels, const int32_t* mark, int keep_marked, const int32_t* area, int min_area, int max_area,
+                  const uint8_t* base, uint8_t* out, int H, int W, void* stream);
+int bdn_d2_mask(const int32_t* d2, int r2, int greater, uint8_t* out, long long n, void* stream);
+int bdn_threshold_pair(const float* proba, int pos_class, float low, float high, uint8_t* mask_low, uint8_t* mask_high, int ncls,
+                       long long HW, void* stream);
+int bdn_mask_not(const uint8_t* src, uint8_t* out, long long n, void* stream);
+
 /* ---- co-registration of the two dates of a scene: the shift between them is estimated by normalised cross-correlation over integer
  * shifts, per cell of a grid and for the whole scene, refined to a fraction of a pixel, and date 2 is resampled through the shift field.
  * No reference: the reference assumes co-registered pairs.  Scenes are float32 [C][H][W] planes (what city_stack_device leaves in HBM, per
