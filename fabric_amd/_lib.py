@@ -194,6 +194,9 @@ SIGNATURES = {
     'bdn_mad_solve': (_i, [_vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),
     'bdn_mad_chi2': (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'bdn_mad_mask': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _i, _i, _i, _vp]),
+    'bdn_raster_hist': (_i, [_vp, _vp, _i, _vp, _i, _vp, C.c_longlong, _vp]),
+    'bdn_hist_threshold': (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
+    'bdn_raster_mask': (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, C.c_longlong, _vp]),
 }
 
 

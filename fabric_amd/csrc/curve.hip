@@ -7,6 +7,7 @@
 // arrival order, so the histogram is the same bits on every run, for any grid and any split of the pixels into calls.  There are no float
 // atomics; the curve's floating-point sums run in a fixed order.
 #include "common.hpp"
+#include "hist_core.hpp"
 
 constexpr int SH_THREADS = 256;
 // The grid: one block per 4 x 256 items, at most 2048 blocks (8 per CU; the rest is grid-strided).  Measured at 1024 bins on the training
@@ -19,45 +20,7 @@ constexpr int SH_MAX_BINS = 4096;
 constexpr long long SH_MAX_PIXELS = 1LL << 40;          // a block then counts < 2^32 pixels into its 32-bit LDS cells whatever the grid
 
 // ============================================================ score_hist
-// One add of the wave's pixels into the block's LDS histogram.  key = label_is_pos * n_bins + bin, or < 0 for a lane without a pixel
-// (tail, ignored).  On real data nearly every pixel is a negative in bin 0, and 64 LDS atomics on one address serialise; so the wave
-// first peels off, twice, the lanes that share the key of its first pending lane (a ballot and one add of their count by that lane) --
-// all-equal waves need one add, a wave with a dominant cell and a few strays two -- and only the lanes still pending add for themselves.
-// Must be called by all 64 lanes of the wave together.
-__device__ __forceinline__ void wave_hist_add(unsigned* lds, int key, int lane) {
-    bool pending = key >= 0;
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const unsigned long long act = __ballot(pending);
-        if (!act) return;                                                    // wave-uniform
-        const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)act) - 1);
-        const int k = __builtin_amdgcn_readlane(key, leader);
-        const bool mine = pending && key == k;
-        const unsigned long long same = __ballot(mine);
-        if (lane == leader) atomicAdd(&lds[k], (unsigned)__popcll(same));
-        pending = pending && !mine;
-    }
-    if (pending) atomicAdd(&lds[key], 1u);
-}
-
-template <int PER> struct PixVec;
-template <> struct PixVec<1> {
-    __device__ __forceinline__ static void load(const float* p, float* v) { v[0] = p[0]; }
-    __device__ __forceinline__ static void store(float* p, const float* v) { p[0] = v[0]; }
-    __device__ __forceinline__ static void labels(const uint8_t* p, int* l) { l[0] = p[0]; }
-};
-template <> struct PixVec<4> {
-    __device__ __forceinline__ static void load(const float* p, float* v) {
-        const float4 u = *reinterpret_cast<const float4*>(p);
-        v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
-    }
-    __device__ __forceinline__ static void store(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-    __device__ __forceinline__ static void labels(const uint8_t* p, int* l) {
-        const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
-        l[0] = u & 255; l[1] = u >> 8 & 255; l[2] = u >> 16 & 255; l[3] = u >> 24;
-    }
-};
-
+// The block histogram is filled by wave_hist_add (hist_core.hpp) with key = label_is_pos * n_bins + bin.
 struct ScoreHistArgs {
     const float* x; const uint8_t* labels; unsigned long long* hist; float* scores_out;
     long long HW, Q, total, stride_img, stride_off;      // Q: items per image; total = n_img * Q; the grid's stride over the items, split by Q

@@ -512,6 +512,49 @@ def check_cleanup_flags(scene_hysteresis, scene_close, scene_fill_holes, scene_o
     return {'hysteresis_low': scene_hysteresis, 'close_radius2': scene_close, 'fill_holes': fill, 'open_radius2': scene_open}
 
 
+def checkpoint_entry(path, key):
+    """The `key` entry of the metadata_epoch_N.json beside a checkpoint file of this program, or None."""
+    m = _CKPT.search(os.path.basename(path)) if path else None
+    meta = os.path.join(os.path.dirname(path), f'metadata_epoch_{m.group(1)}.json') if m else None
+    if meta is None or not os.path.exists(meta):
+        return None
+    with open(meta) as fh:
+        return json.load(fh).get(key)
+
+
+def check_auto_threshold_flags(scene_auto_threshold, scene_mad_baseline, scene_mad_iters, scene_threshold, scene_stride, checkpoint=None):
+    """--scene_auto_threshold / --scene_mad_baseline / --scene_mad_iters with --scene_threshold (as check_curve_flags returns it) and
+    --scene_stride, without a device.  checkpoint: the {'scene_auto_threshold', 'scene_mad_baseline'} entries of the metadata of the run
+    --resume continues (or None): a resumed run keeps them unless the flag is given again.  Returns (the method of predict_scene_blended's
+    auto_threshold or None, {'method', 'iters'} of the baseline or None); raises ValueError with the reason otherwise."""
+    from .utils.mad import MAX_ITERS
+    from .utils.thresholds import METHODS
+    kept = checkpoint or {}
+    auto = scene_auto_threshold if scene_auto_threshold is not None else kept.get('scene_auto_threshold')
+    if auto is not None:
+        if auto not in METHODS:
+            raise ValueError(f'--scene_auto_threshold {auto}: one of {", ".join(METHODS)}')
+        if scene_stride <= 0:
+            raise ValueError('--scene_auto_threshold thresholds the blended scene probabilities: add --scene_stride N > 0')
+        if scene_threshold != 'argmax':
+            raise ValueError(f'--scene_auto_threshold selects the threshold on the device, --scene_threshold {scene_threshold} gives one: '
+                             f'leave --scene_threshold at argmax')
+    old = kept.get('scene_mad_baseline') or {}
+    method = scene_mad_baseline if scene_mad_baseline is not None else old.get('method')
+    if method is None:
+        if scene_mad_iters is not None:
+            raise ValueError('--scene_mad_iters counts the iterations of a baseline that is not on: add --scene_mad_baseline METHOD')
+        return auto, None
+    if method not in METHODS:
+        raise ValueError(f'--scene_mad_baseline {method}: one of {", ".join(METHODS)}')
+    if scene_stride <= 0:
+        raise ValueError('--scene_mad_baseline adds to the scene line of the blended scenes: add --scene_stride N > 0')
+    iters = scene_mad_iters if scene_mad_iters is not None else old.get('iters', 30)
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= MAX_ITERS:
+        raise ValueError(f'--scene_mad_iters {iters}: an integer in 1..{MAX_ITERS}')
+    return auto, {'method': method, 'iters': iters}
+
+
 def cleaned_scores(mask, label, ignore_label=None):
     """scene_scores of the cleaned mask that is written, the pixels with label == ignore_label left out."""
     m, l = np.asarray(mask) == 1, np.asarray(label)
@@ -691,22 +734,12 @@ def check_mad_flags(invariant=None, iters=None, tol=None, invariant_min=None, ra
 
 def checkpoint_radiometric(path):
     """The `radiometric` entry of the metadata_epoch_N.json beside a checkpoint file of this program, or None."""
-    m = _CKPT.search(os.path.basename(path)) if path else None
-    meta = os.path.join(os.path.dirname(path), f'metadata_epoch_{m.group(1)}.json') if m else None
-    if meta is None or not os.path.exists(meta):
-        return None
-    with open(meta) as fh:
-        return json.load(fh).get('radiometric')
+    return checkpoint_entry(path, 'radiometric')
 
 
 def checkpoint_label_smoothing(path):
     """The `label_smoothing` entry of the metadata_epoch_N.json beside a checkpoint file of this program, or None."""
-    m = _CKPT.search(os.path.basename(path)) if path else None
-    meta = os.path.join(os.path.dirname(path), f'metadata_epoch_{m.group(1)}.json') if m else None
-    if meta is None or not os.path.exists(meta):
-        return None
-    with open(meta) as fh:
-        return json.load(fh).get('label_smoothing')
+    return checkpoint_entry(path, 'label_smoothing')
 
 
 def resolve_label_smoothing(flag, fused_step, loss_topk, checkpoint=None):
@@ -901,6 +934,16 @@ def main(argv=None):
     ap.add_argument('--scene_open', type=int, default=None, metavar='R2',
                     help='--scene_stride N > 0: the scene mask is opened with the disc dy^2 + dx^2 <= R2 on the device (binary_opening).  Order: '
                          'threshold or hysteresis, closing, hole filling, opening, --scene_min_area; the scene line gains cleanup and cleaned')
+    ap.add_argument('--scene_auto_threshold', type=str, default=None, metavar='METHOD',
+                    help='--scene_stride N > 0 with --scene_threshold argmax: the scene masks are P(change) >= a threshold selected on the device '
+                         'from the histogram of the scene probabilities, by otsu, kittler, rosin or em (utils/thresholds.py: no labels, no '
+                         'validation pass); the scene line gains auto_threshold {method, value, bin, ok}')
+    ap.add_argument('--scene_mad_baseline', type=str, default=None, metavar='METHOD',
+                    help='--scene_stride N > 0: the scene line gains mad_baseline, the counts of the label-free baseline on the scene pair: IR-MAD '
+                         '(utils/mad.py) and its chi2 thresholded by otsu, kittler, rosin or em (auto_change_mask); --ignore_label pixels are '
+                         'left out of the statistic and of the counts')
+    ap.add_argument('--scene_mad_iters', type=int, default=None, metavar='N',
+                    help='the iterations of --scene_mad_baseline (default 30)')
     ap.add_argument('--coregister', type=int, default=0, metavar='R',
                     help='align date 2 of every city to its date 1 once after loading, on the device (utils/registration.py): the shift is '
                          'searched over +-R pixels (1..16) by normalised cross-correlation and date 2 is resampled bilinearly; 0: off.  '
@@ -1027,6 +1070,9 @@ def main(argv=None):
         scene_min_area = check_object_flags(opt.scene_min_area, opt.scene_objects, opt.scene_connectivity, opt.scene_stride)
         scene_cleanup = check_cleanup_flags(opt.scene_hysteresis, opt.scene_close, opt.scene_fill_holes, opt.scene_open, scene_thr,
                                             opt.scene_connectivity, opt.scene_stride)
+        kept = {k: checkpoint_entry(opt.resume, k) for k in ('scene_auto_threshold', 'scene_mad_baseline')} if opt.resume else None
+        scene_auto, scene_mad = check_auto_threshold_flags(opt.scene_auto_threshold, opt.scene_mad_baseline, opt.scene_mad_iters, scene_thr,
+                                                           opt.scene_stride, kept)
     except ValueError as e:
         raise SystemExit(str(e))
     try:
@@ -1173,6 +1219,10 @@ def main(argv=None):
         run_meta['label_smoothing'] = opt.label_smoothing
     if scene_cleanup is not None:                          # how the scene masks written beside this checkpoint were cleaned
         run_meta['scene_cleanup'] = dict(scene_cleanup, connectivity=opt.scene_connectivity)
+    if scene_auto is not None:                             # the label-free threshold of the scene masks: --resume reads it back
+        run_meta['scene_auto_threshold'] = scene_auto
+    if scene_mad is not None:
+        run_meta['scene_mad_baseline'] = dict(scene_mad)
     schedule = None
     if scheduled:                                          # host floats only; its position comes from (epoch, batch), so --resume continues it
         from .schedule import LRSchedule
@@ -1206,7 +1256,9 @@ def main(argv=None):
                 _predict_scenes(model, scenes, val_cities, opt, epoch, va['best_threshold'] if scene_thr == 'val' else
                                 None if scene_thr == 'argmax' else scene_thr, min_area=scene_min_area,
                                 **({} if scene_boundary_tol is None else {'boundary_tol': scene_boundary_tol}),
-                                **({} if scene_cleanup is None else {'cleanup': scene_cleanup}))
+                                **({} if scene_cleanup is None else {'cleanup': scene_cleanup}),
+                                **({} if scene_auto is None else {'auto_threshold': scene_auto}),
+                                **({} if scene_mad is None else {'mad_baseline': scene_mad}))
         if rank == 0:                                          # replica 0's BatchNorm buffers, like DataParallel
             best = save_if_better(model, va, best, run_meta, epoch, opt.log_dir,
                                   step.optimizer_state_dict() if fused else optimizer.state_dict(),
@@ -1217,7 +1269,22 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_area=None, boundary_tol=None, cleanup=None):
+def mad_baseline_scores(d1, d2, label, ignore_label, device, method, iters):
+    """The label-free baseline of one scene pair: irmad + auto_change_mask(method) on the device, scored against the label raster like the
+    `cleaned` entry.  Pixels with label == ignore_label take no part in the statistic, the histogram or the counts."""
+    from .utils.mad import auto_change_mask, irmad
+    g1 = torch.as_tensor(d1).to(device=device, dtype=torch.float32).contiguous()
+    g2 = torch.as_tensor(d2).to(device=device, dtype=torch.float32).contiguous()
+    exclude = None if ignore_label is None else torch.as_tensor(np.asarray(label)).to(device=device, dtype=torch.uint8).contiguous()
+    res = irmad(g1, g2, exclude=exclude, exclude_value=ignore_label, iters=iters)
+    mask, table = auto_change_mask(res, method)
+    d = table.read()[method]
+    return dict({'method': method, 'threshold': d['value'] if d['ok'] else None, 'iters': res.read()['iters']},
+                **cleaned_scores(mask.cpu().numpy(), label, ignore_label))
+
+
+def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_area=None, boundary_tol=None, cleanup=None,
+                    auto_threshold=None, mad_baseline=None):
     """train.py:182-205: the full validation scenes of one epoch, written as PNG masks (and, blended, as probabilities with a scene F1 line).
     threshold (--scene_threshold): None = the argmax masks, else the masks are P(change) >= threshold.  With --val_curve_bins the scene
     line of every city comes from a ScoreCurve over its probabilities and label raster (the run's --ignore_label left out), on the device:
@@ -1232,7 +1299,13 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
     cleanup (--scene_hysteresis / --scene_close / --scene_fill_holes / --scene_open, from check_cleanup_flags): the keyword arguments of
     predict_scene_blended that clean the mask on the device, before the area filter: --scene_objects then scores the mask after the
     opening.  The scene line gains cleanup (the settings) and cleaned = {tp, fp, fn, precision, recall, f1} of the mask that is written
-    against the labels (--ignore_label left out): with --val_curve_bins the other counts come from the probabilities."""
+    against the labels (--ignore_label left out): with --val_curve_bins the other counts come from the probabilities.
+    auto_threshold (--scene_auto_threshold, from check_auto_threshold_flags): the method of predict_scene_blended's auto_threshold; the
+    scene line gains auto_threshold = {method, value, bin, ok} (value None when the rule found no split: the mask is then empty), and its
+    tp / fp / fn / precision / recall / f1 are those of the mask that is written (--ignore_label left out).
+    mad_baseline (--scene_mad_baseline, from check_auto_threshold_flags): {'method', 'iters'}; the scene line gains mad_baseline =
+    {method, threshold, iters, tp, fp, fn, precision, recall, f1} of irmad + auto_change_mask on the scene pair, the label's
+    --ignore_label pixels excluded from the statistic and from the counts (iters: the iterations IR-MAD ran before it converged)."""
     from .utils import ingest
     from .utils.inference import predict_scene, predict_scene_blended, TTA_SYMMETRIES
     os.makedirs(opt.log_dir, exist_ok=True)
@@ -1242,13 +1315,15 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
     objects = getattr(opt, 'scene_objects', False)
     for city in val_cities:
         st = scenes[city]['images']
+        selected = {}
         if opt.scene_stride > 0:
             proba, mask = predict_scene_blended(model, st[0], st[1], patch_size=opt.patch_size, stride=opt.scene_stride,
                                                 window=opt.scene_window, symmetries=TTA_SYMMETRIES[opt.scene_tta],
                                                 batch_size=opt.batch_size, **({} if threshold is None else {'threshold': threshold}),
                                                 **({} if min_area is None or objects else {'min_area': min_area}),
                                                 **({} if (min_area is None or objects) and cleanup is None else {'connectivity': conn}),
-                                                **(cleanup or {}))
+                                                **(cleanup or {}),
+                                                **({} if auto_threshold is None else {'auto_threshold': auto_threshold, 'threshold_out': selected}))
             raw = mask
             if min_area is not None and objects:             # the unfiltered mask is scored below; the same launches as min_area= above
                 from .utils.objects import remove_small_objects
@@ -1275,6 +1350,14 @@ def _predict_scenes(model, scenes, val_cities, opt, epoch, threshold=None, min_a
             if cleanup is not None:
                 scene_counts[city]['cleanup'] = dict(cleanup)
                 scene_counts[city]['cleaned'] = cleaned_scores(mask.cpu().numpy(), scenes[city]['labels'], getattr(opt, 'ignore_label', None))
+            if auto_threshold is not None:
+                d = selected['table'].read()[auto_threshold]
+                scene_counts[city].update(cleaned_scores(mask.cpu().numpy(), scenes[city]['labels'], getattr(opt, 'ignore_label', None)))
+                scene_counts[city]['auto_threshold'] = {'method': auto_threshold, 'value': d['value'] if d['ok'] else None, 'bin': d['bin'],
+                                                        'ok': d['ok']}
+            if mad_baseline is not None:
+                scene_counts[city]['mad_baseline'] = mad_baseline_scores(st[0], st[1], scenes[city]['labels'], getattr(opt, 'ignore_label', None),
+                                                                         proba.device, **mad_baseline)
             if boundary_tol is not None:
                 from .utils.distance import boundary_scores
                 truth = torch.as_tensor(scenes[city]['labels']).to(device=mask.device, dtype=torch.uint8).contiguous()

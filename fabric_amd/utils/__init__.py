@@ -5,4 +5,5 @@ from .morphology import (binary_closing, binary_dilation, binary_erosion, binary
 from .registration import apply_shift, check_apply_args, check_estimate_args, coregister, coregister_cities, estimate_shift  # noqa: F401
 from .radiometry import (apply_transfer, band_quantiles, check_fit_args, check_quantile_args, check_transfer_args, fit_transfer,  # noqa: F401
                          match_histograms, match_range, normalize_cities)
-from .mad import MadResult, change_mask, check_mad_args, irmad  # noqa: F401
+from .mad import MadResult, auto_change_mask, change_mask, check_mad_args, irmad  # noqa: F401
+from .thresholds import RasterHistogram, ThresholdTable, auto_threshold, bin_edges  # noqa: F401

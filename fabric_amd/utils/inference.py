@@ -265,8 +265,8 @@ def check_blend_args(h, w, patch_size, stride, window, symmetries, n_classes, ba
 
 @torch.no_grad()
 def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None, window='gaussian', symmetries=(0,), batch_size=64,
-                          band_rows=None, two_streams=None, threshold=None, pos_class=1, min_area=None, connectivity=8,
-                          hysteresis_low=None, close_radius2=None, fill_holes=None, open_radius2=None):
+                          band_rows=None, two_streams=None, threshold=None, pos_class=1, min_area=None, auto_threshold=None,
+                          threshold_out=None, connectivity=8, hysteresis_low=None, close_radius2=None, fill_holes=None, open_radius2=None):
     """Class probabilities of a whole scene from overlapping tiles.
 
     Tiles of patch_size at `stride` (default patch_size // 2; blend_tile_origins), each under every code of `symmetries` (codes 0..7 of
@@ -287,10 +287,16 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
     They clean the mask with fabric_amd.utils.morphology on the current stream, no host read, proba keeps its bits, in this order behind
     the finalize launch: hysteresis_low (needs threshold, and hysteresis_low <= threshold): the mask is hysteresis_mask(proba,
     hysteresis_low, threshold, pos_class, connectivity) instead of the plain threshold; close_radius2: binary_closing with that disc;
-    fill_holes (True, or the largest hole area filled): fill_holes under `connectivity`; open_radius2: binary_opening; then min_area."""
+    fill_holes (True, or the largest hole area filled): fill_holes under `connectivity`; open_radius2: binary_opening; then min_area.
+    auto_threshold: None: off (the launches and the bits of a call without it); 'otsu', 'kittler', 'rosin' or 'em': the threshold is
+    selected on the device from the histogram of proba[pos_class] over [0, 1] in 1024 linear bins (fabric_amd.utils.thresholds) and the mask
+    is proba[pos_class] >= that threshold (bdn_raster_mask in place of bdn_threshold_mask: the number never leaves the device; all zeros
+    when the rule finds no split); three more launches, proba keeps its bits.  Refused together with threshold or hysteresis_low, which
+    take their numbers by value.  threshold_out: a dict that receives the ThresholdTable under 'table'."""
     from .metrics import check_threshold
     eng = model.engine()
     threshold, pos_class = check_threshold(threshold, pos_class, eng.n_classes)
+    check_auto_threshold_args(auto_threshold, threshold_out, threshold, hysteresis_low)
     cleanup = not (hysteresis_low is None and close_radius2 is None and fill_holes is None and open_radius2 is None)
     if cleanup:
         from . import morphology
@@ -355,11 +361,30 @@ def predict_scene_blended(model, scene_d1, scene_d2, patch_size=128, stride=None
         morphology.hysteresis_mask(proba, hysteresis_low, threshold, pos_class, connectivity, out=mask)
     elif threshold is not None:
         _lib.call('bdn_threshold_mask', _lib.ptr(proba), pos_class, threshold, _lib.ptr(mask), ncls, h * w, _lib.stream_ptr())
+    elif auto_threshold is not None:
+        from . import thresholds
+        _, table = thresholds.auto_threshold(proba[pos_class], auto_threshold, 1024, 'linear', 0.0, 1.0, out=mask)
+        if threshold_out is not None:
+            threshold_out['table'] = table
     if cleanup:
         morphology.cleanup_mask(mask, close_radius2, fill_holes, open_radius2, connectivity)
     if min_area is not None:
         remove_small_objects(mask, min_area, connectivity, out=mask)
     return proba, mask
+
+
+def check_auto_threshold_args(auto_threshold=None, threshold_out=None, threshold=None, hysteresis_low=None):
+    """Validate the auto_threshold= / threshold_out= pair of predict_scene_blended without touching a device."""
+    if threshold_out is not None and not isinstance(threshold_out, dict):
+        raise ValueError(f'threshold_out must be None or a dict, got {type(threshold_out).__name__}')
+    if auto_threshold is None:
+        if threshold_out is not None:
+            raise ValueError('threshold_out needs auto_threshold')
+        return
+    from .thresholds import check_method
+    check_method(auto_threshold)
+    if threshold is not None or hysteresis_low is not None:
+        raise ValueError('auto_threshold selects the threshold on the device; threshold and hysteresis_low take theirs by value: give one or the other')
 
 
 def _check_widest(eng, batch_size, patch_size):

@@ -139,3 +139,37 @@ def change_mask(result, threshold=0.01, excluded_out=0, out=None):
               _lib.ptr(result.exclude), result.exclude_value, float(threshold), excluded_out, _lib.ptr(out), int(result.d1.shape[0]), h, w,
               _lib.stream_ptr())
     return out
+
+
+def check_auto_mask_args(result, method='rosin', on='chi2', n_bins=1024, spacing='sqrt', chi2_max=None, excluded_out=0, out=None):
+    """Validate the arguments of auto_change_mask without touching a device.  Returns the raster the threshold is selected on."""
+    from . import thresholds as T
+    if not isinstance(result, MadResult):
+        raise ValueError(f'result must be a MadResult (irmad), got {type(result).__name__}')
+    T.check_method(method)
+    if on not in ('chi2', 'proba'):
+        raise ValueError(f"on must be 'chi2' or 'proba', got {on!r}")
+    T._check_bins(n_bins, spacing)
+    if spacing == 'log':
+        raise ValueError("spacing 'log' cannot start at 0, where chi2 and the change probability start; use 'linear' or 'sqrt'")
+    if chi2_max is not None:
+        if on != 'chi2':
+            raise ValueError("chi2_max goes with on='chi2'")
+        _number(chi2_max, 'chi2_max', lo=0.0, lo_open=True)
+    raster = result.chi2 if on == 'chi2' else result.proba[1]
+    T.check_raster_args(raster, None, None, out, excluded_out)
+    return raster
+
+
+def auto_change_mask(result, method='rosin', on='chi2', n_bins=1024, spacing='sqrt', chi2_max=None, excluded_out=0, out=None):
+    """The change mask of `result` (a MadResult) at a threshold selected from the histogram of its own statistic
+    (fabric_amd.utils.thresholds): `on` = 'chi2', binned over [0, chi2_max] (None: the largest chi2 of a valid pixel, found on the device),
+    or 'proba', the change probability, over [0, 1]; `method` one of 'otsu', 'kittler', 'rosin', 'em'.  The pixels that took no part
+    (bdn_mad_mask's invalid pixels) are left out of the histogram and get `excluded_out`.  Returns (mask uint8 [H,W]: 1 where the
+    statistic >= the threshold, ThresholdTable); a rule without a split (a failed solve's NaN raster) gives an all-zero mask.  Five
+    launches behind the maximum, no host read.  change_mask is the fixed-probability route."""
+    from . import thresholds as T
+    raster = check_auto_mask_args(result, method, on, n_bins, spacing, chi2_max, excluded_out, out)
+    _need_device(raster, 'auto_change_mask')
+    invalid = change_mask(result, threshold=0.0, excluded_out=1)           # no probability lies below 0: 1 exactly at the invalid pixels
+    return T.auto_threshold(raster, method, n_bins, spacing, 0.0, chi2_max if on == 'chi2' else 1.0, False, invalid, 1, excluded_out, out=out)

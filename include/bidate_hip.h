@@ -1245,6 +1245,78 @@ int bdn_mad_chi2(const float* d1, const float* d2, const int32_t* bands, int n_b
 int bdn_mad_mask(const float* proba, const float* d1, const float* d2, const int32_t* bands, int n_b, const uint8_t* exclude,
                  int exclude_value, float threshold, int excluded_out, uint8_t* mask, int C, int H, int W, void* stream);
 
+/* ---- thresholds without labels: the histogram of a float raster, four selection rules on it, and a mask at a threshold that lives on the
+ * device.  The reference has one operating point, the argmax of train.py:199; a change statistic without labels (IR-MAD's chi2 above, a
+ * scene's change probability from a city without ground truth) gets its threshold from the histogram of the statistic itself.  A null
+ * required pointer, a misaligned pointer or a value outside its range is BDN_E_ARG before any launch; the outputs are the same bits on
+ * every run.
+ * bdn_raster_hist: raster float32 [HW] (HW is 64-bit, 1..2^40); exclude: NULL or uint8 [HW] with exclude_value (a byte); edges: float32
+ *   [n_bins + 1], non-decreasing, 2 <= n_bins <= 4096; hist: uint64 [n_bins + 3], the kernel ADDS into it -- zero it once, then accumulate
+ *   rasters or tiles, as bdn_score_hist does.  A pixel with exclude == exclude_value or a value that is not finite is skipped and counted
+ *   in hist[n_bins + 2].  v < edges[0] is counted in hist[n_bins] (below), v > edges[n_bins] in hist[n_bins + 1] (above); every other v in
+ *   bin max{i < n_bins : edges[i] <= v}, i.e. np.searchsorted(edges[:n_bins], v, side='right') - 1: a value equal to the last edge lands in
+ *   the last bin, -0.0 == 0.0.  The bin comes from comparisons with the edges alone (a bisection of the table staged in LDS), no float
+ *   arithmetic takes part: the counts are exact whatever the spacing.  The bisection's index stays in [0, n_bins - 1] for any table, sorted
+ *   or not.  LDS and global integer atomics carry the counts.  Four pixels per thread where HW % 4 == 0 and raster is 16-byte, exclude
+ *   4-byte aligned, one otherwise.  One launch.
+ * bdn_hist_threshold: one launch of one block, float64.  c = hist[0 .. n_bins) (below, above and skipped take no part), N = sum c;
+ *   coord: float64 [n_bins], non-decreasing: the coordinate of each bin the criteria are computed in (the bin centres, or their sqrt or
+ *   log); every criterion uses y_i = coord[i] - M, M = (sum c_i coord_i) / N.  A split t in 1..n_bins-1 puts the bins < t in class 0 and the
+ *   bins >= t in class 1; its threshold is edges[t], so that the mask v >= edges[t] has exactly sum c[t:] + above ones.  Counts and their
+ *   prefix sums are 64-bit integers.  Floating-point sums over the bins have a fixed order: thread k of 256 adds the bins
+ *   [k per, (k + 1) per), per = ceil(n_bins / 256), ascending from 0; the 256 partials are added in thread order from 0; a prefix sum
+ *   continues the sum of the earlier threads' partials with the owner's bins.  No product is contracted into a fused multiply-add.
+ *   methods: a mask of BDN_THR_*.  Ties go to the first (lowest) t.
+ *     OTSU: the first t that maximises n0 n1 (m0 - m1)^2 over the splits with n0, n1 > 0 (class 1's sums are totals minus prefixes).
+ *     KITTLER: the first t that minimises J = 1 + (P0 ln v0 + P1 ln v1) - 2 (P0 ln P0 + P1 ln P1), P_k = n_k / N, v_k the class variance
+ *       sum c y^2 / n_k - m_k^2, over the splits with both v_k > 0 (Kittler and Illingworth 1986; ln v = 2 ln s).
+ *     ROSIN: p = the first maximum bin, e = the last occupied bin; needs e >= p + 2; the first i in (p, e) that maximises
+ *       (c[e] - c[p]) (i - p) - (e - p) (c[i] - c[p]), the distance from the chord (Rosin 2001), in signed 64-bit integers: bit-exact.
+ *       N >= 2^49 gives OK = 0.  Right tails only.
+ *     EM: two Gaussians fitted to the histogram (Bruzzone and Prieto 2000), started from Kittler's split (Otsu's if Kittler has none) with
+ *       that split's class weights, means and variances; variances are floored at (the smallest positive coord[i+1] - coord[i])^2 / 12.
+ *       Step j evaluates the log-likelihood L_j and the responsibilities under the current parameters; it stops before updating them when
+ *       j > 1 and |L_j - L_{j-1}| <= em_tol |L_j|, otherwise updates, up to em_iters steps (1..1000; em_tol finite, >= 0; 0 stops only where L repeats bit for bit).  t = the first bin
+ *       above the last bin with y <= m0, up to the last bin with y <= m1, at which ln w1 + ln N(y_t; m1, v1) >= ln w0 + ln N(y_t; m0, v0);
+ *       OK = 0 without such a bin, with m1 <= m0, or when a class weight reaches 0.
+ *   table: float64 [4][BDN_THR_COLS], row = OTSU, KITTLER, ROSIN, EM; thr: float32 [4] = edges[BIN].  Columns: OK; BIN = t; VALUE =
+ *   edges[t]; CRIT (the criterion at t; EM: LOGLIK); N0, N1 = sum c[:t], sum c[t:]; MEAN0, MEAN1, SD0, SD1: of the two classes of the split,
+ *   each summed for itself (EM: the fitted parameters); W1 = N1 / N (EM: the fitted weight); ITERS, LOGLIK (EM; 0 otherwise); N; BELOW;
+ *   ABOVE.  A method that was not requested or has nothing to split (fewer than two occupied bins, N = 0, no valid split) leaves a row of
+ *   zeros and thr = NaN: every call writes all of table and thr.
+ * bdn_raster_mask: mask[i] (uint8) = raster[i] >= *thr (below = 1: raster[i] < *thr) for a finite raster[i], 0 for a non-finite one,
+ *   excluded_out (a byte) where exclude[i] == exclude_value.  thr: ONE float32 in device memory (an entry of bdn_hist_threshold's thr): no
+ *   host read between selecting a threshold and applying it.  A NaN threshold gives 0 at every pixel that is not excluded.  Four pixels
+ *   per thread where HW % 4 == 0 and raster is 16-byte, exclude and mask 4-byte aligned, one otherwise.  One launch.
+ * Every pointer is device memory; nothing waits for the device; all work is enqueued on `stream`. ---- */
+#define BDN_THR_OTSU 1
+#define BDN_THR_KITTLER 2
+#define BDN_THR_ROSIN 4
+#define BDN_THR_EM 8
+#define BDN_THR_COL_OK 0
+#define BDN_THR_COL_BIN 1
+#define BDN_THR_COL_VALUE 2
+#define BDN_THR_COL_CRIT 3
+#define BDN_THR_COL_N0 4
+#define BDN_THR_COL_N1 5
+#define BDN_THR_COL_MEAN0 6
+#define BDN_THR_COL_MEAN1 7
+#define BDN_THR_COL_SD0 8
+#define BDN_THR_COL_SD1 9
+#define BDN_THR_COL_W1 10
+#define BDN_THR_COL_ITERS 11
+#define BDN_THR_COL_LOGLIK 12
+#define BDN_THR_COL_N 13
+#define BDN_THR_COL_BELOW 14
+#define BDN_THR_COL_ABOVE 15
+#define BDN_THR_COLS 16
+int bdn_raster_hist(const float* raster, const uint8_t* exclude, int exclude_value, const float* edges, int n_bins,
+                    unsigned long long* hist, long long HW, void* stream);
+int bdn_hist_threshold(const unsigned long long* hist, const double* coord, const float* edges, int n_bins, int methods, int em_iters,
+                       double em_tol, double* table, float* thr, void* stream);
+int bdn_raster_mask(const float* raster, const uint8_t* exclude, int exclude_value, const float* thr, int below, int excluded_out,
+                    uint8_t* mask, long long HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
